@@ -14,7 +14,18 @@ Launching: `python bench.py --gpus N` with WORLD_SIZE unset starts N rank proces
 127.0.0.1) BEFORE anything touches the GPU in this process, waits for them and exits with their status; under
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` it is one of the ranks.  Rank 0 prints ONE JSON line.
 
-Extra objects in the line:
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline needs: models, the weight-prefetch tuner, W untimed
+and K timed clips of the headline algorithm, the outputs of the last timed clip when `--dump-outputs DIR` is given, and the line
+(metric, value, unit, ms_per_step = milliseconds per timed clip, ...).  Everything else — the other algorithm of `--algo both`, the
+in-situ profiles and rooflines, the timer calibration, the batched / config4 / g256 legs, the CPU baseline and, at N > 1, the shard
+self-check and the collective probe — runs only under `--full`, as described below.
+
+--dump-outputs DIR writes what the timed path returned for its last clip (rank 0): DIR/latents.npy, the all-gathered final latents,
+and DIR/frames_u8.npy, the decoded uint8 frames, as float32 (`--mode train` / `train_step`: DIR/loss.npy).  An array larger than its
+share of DUMP_ELEMS is written as a fixed sample (`<name>_sample.npy`: sorted flat indices drawn from a generator seeded with 0), so a
+dump stays under 48 MB.  Inputs and weights are seeded: the same arguments give the same inputs in every run.
+
+Extra objects in the line (`--full`):
   roofline     — the dominant kernel = the GEMM class (to_qkv / out-proj / fc1 / fc2, csrc/gemm.hip) with the LARGEST time per forward, timed
                  in situ with HIP events attached to the kernel's own dispatch (hipExtLaunchKernel) during real forwards; algorithmic FLOPs
                  per launch / mean duration; plus the FLOP-weighted aggregate over the four GEMM classes, the worst class and every class's
@@ -162,7 +173,31 @@ def parse_args(argv=None):
                          "one DiT forward over the window, MSE vs the v-target), data-parallel, metric samples/s (not the headline); "
                          "train_step = the whole optimisation step (SURVEY.md 8(f)1): that forward, backward, gradient all-reduce, "
                          "clip + AdamW")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the other algorithm of --algo both, in-situ profiles / rooflines, timer calibration, "
+                         "the config2 / config3, config4 and g256 legs, the CPU baseline, and at N > 1 the shard self-check and collective probe")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step as DIR/<name>.npy (float32; a fixed seeded sample of a large array)")
     return ap.parse_args(argv)
+
+
+DUMP_ELEMS = 12 << 20       # float32 elements of one --dump-outputs directory in all (48 MB), shared evenly by its arrays
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each tensor of `arrays` (name -> tensor or None) as dirname/<name>.npy in float32.  One that exceeds its share of DUMP_ELEMS
+    is written as a fixed sample instead, dirname/<name>_sample.npy: the flattened tensor at sorted flat indices drawn from a generator seeded with 0."""
+    import numpy as np
+    import torch
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    share = DUMP_ELEMS // max(1, len(arrays))
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > share:
+            idx = torch.randint(t.numel(), (share,), generator=torch.Generator().manual_seed(0)).sort().values
+            t, name = t.reshape(-1)[idx.to(t.device)], name + "_sample"
+        np.save(os.path.join(dirname, name + ".npy"), t.float().cpu().numpy())
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -219,6 +254,8 @@ def bench_train(args, world, rank, dev, dist, torch):
         t = torch.tensor([el], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = t.item()
+    if rank == 0 and args.dump_outputs and args.steps > 0:
+        dump_outputs(args.dump_outputs, {"loss": loss.reshape(1)})
     if rank == 0:
         flops = B * ((3 if full else 1) * dit_forward_flops(5 * P_TOK, 5, 15, 1) + 5 * 96.6e9)   # DiT forward (+ 2x for backward) + VAE encode
         extra = {}
@@ -560,8 +597,12 @@ def bench_generate(args, world, rank, dev, dist, torch):
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(nclips):
-            one_clip(inp, cached, steps)
+        out = None
+        for i in range(nclips):
+            r = one_clip(inp, cached, steps)
+            if i == nclips - 1:             # the last clip's (latents, frames): what --dump-outputs writes; the earlier ones are freed at once
+                out = r
+            del r
         torch.cuda.synchronize()
         el = time.perf_counter() - t0       # (taken before the closing barrier: no collective inside the timing; the MAX over ranks is the slowest rank)
         if world > 1:
@@ -569,7 +610,7 @@ def bench_generate(args, world, rank, dev, dist, torch):
             t = torch.tensor([el], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = t.item()
-        return el
+        return el, out
 
     def fused_gflop(M, frames_b, frames_t, prof, classes, gflop):
         """The fused to_qkv + attention launches (gtav_dit_fused_launches) are booked under the attention class of their half — one class, one kernel.  Their algorithmic
@@ -770,14 +811,49 @@ def bench_generate(args, world, rank, dev, dist, torch):
     results = {}
     for algo in algos:
         if algo == head:         # the headline: exactly --steps timed clips after --warmup untimed ones
-            results[algo] = (timed(inp, algo == "cached", args.steps, args.warmup), args.steps)
-        else:                    # the extra algorithm: bounded (--cached-clips), one short warm-up clip with the same shapes / graph keys
+            e, out = timed(inp, algo == "cached", args.steps, args.warmup)
+            results[algo] = (e, args.steps)
+            if rank == 0 and args.dump_outputs and out is not None:
+                dump_outputs(args.dump_outputs, {"latents": out[0], "frames_u8": out[1]})
+            del out
+        elif args.full:          # the extra algorithm: bounded (--cached-clips), one short warm-up clip with the same shapes / graph keys
             nc = max(1, min(args.steps, args.cached_clips))
-            results[algo] = (timed(inp, algo == "cached", nc, 1, short_warm=True), nc)
+            results[algo] = (timed(inp, algo == "cached", nc, 1, short_warm=True)[0], nc)
+        else:
+            continue
         leg_done("headline_" + algo)
     el = results[head][0]
     gen_frames = world * B * (total - n_prompt)
     value = gen_frames * args.steps / el
+
+    def headline_line():
+        cfg_name = ("DiT-S/2 (608M) + ViT-L/20 VAE, native 360x640 frames -> 16x18x32 latents" if args.geometry == "native" else
+                    "DiT-S/2 widths on a 16x16 latent grid + ViT-L/16 VAE, g256 preset: 256x256 frames -> 16x16x16 latents (SURVEY.md 8(d))")
+        return {
+            "metric": "generated frames/sec (32-frame clip, 100 noise steps)", "value": round(value, 4), "unit": "generated frames/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(el / args.steps * 1e3, 2),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "fp16 (fp32 accumulate/residual)",
+            "data": "synthetic (seeded CPU-generated prompt frames + noise by global sample id, hash-seeded random weights incl. adaLN)" +
+                    (" — REHEARSAL: all ranks on one GPU over gloo, the numbers mean nothing" if os.environ.get("GTAV_BENCH_REHEARSE_ONE_GPU") == "1" and world > 1 else ""),
+            "config": {"workload": "BASELINE configs[%d]: %s, %d frames (%d prompt), %d noise steps, batch %d per GPU%s" %
+                                   (2 if args.use_actions else 1, cfg_name, total, n_prompt, steps, B,
+                                    ", action-conditioned" if args.use_actions else ", no actions"),
+                       "global_batch": world * B, "algorithm": "window-recompute (reference behaviour)" if head == "window" else "ctx-cached",
+                       "parallelism": "batch-sharded x%d (one process per GPU), one all-gather of latents per clip" % world,
+                       "vae_in_timed_region": vae is not None, "geometry": args.geometry},
+            "full": args.full,
+            "all_frames_per_s": round(world * B * total * args.steps / el, 4),          # B * 32 / wall (SURVEY.md 8(d))
+            "dit_forwards_per_s": round(world * (total - n_prompt) * (steps + 1) * args.steps / el, 2),   # batched forwards of B samples
+            "weight_prefetch": prefetch_choice,
+        }
+
+    if not args.full:            # a plain run: the headline figure and nothing else
+        if rank == 0:
+            line = headline_line()
+            line.update(algo_report(B, results))
+            line["wall"] = {"total_s": round(time.time() - T_START, 1), "legs_s": leg_wall}
+            print(json.dumps(line))
+        return
     roofline, dit_step, (xw, tw) = profile_forward(B, inp[2])
     roofline_cached = dit_step_cached = None
     if "cached" in results:
@@ -793,7 +869,7 @@ def bench_generate(args, world, rank, dev, dist, torch):
         if "cached" in algos and 256 <= Bb * P_TOK <= 1536:      # the context-cached step of this leg (Bb x one frame of tokens) is in the prefetch's range: tune it at that size
             from gtav_amd.generate import tune_weight_prefetch
             bpf = tune_weight_prefetch(dit, Bb, window=1, use_actions=True, latent_hw=(LH, LW))
-        bres = {algo: (timed(binp, algo == "cached", args.batched_clips, 1, short_warm=True), args.batched_clips) for algo in algos}
+        bres = {algo: (timed(binp, algo == "cached", args.batched_clips, 1, short_warm=True)[0], args.batched_clips) for algo in algos}
         broof, bstep, _ = profile_forward(Bb, binp[2])
         broof_c, bstep_c = profile_cached_step(Bb, binp[2]) if "cached" in bres else (None, None)
         bel = bres["window" if "window" in bres else algos[0]][0]
@@ -935,25 +1011,8 @@ def bench_generate(args, world, rank, dev, dist, torch):
 
     leg_done("cpu_baseline")
     if rank == 0:
-        cfg_name = ("DiT-S/2 (608M) + ViT-L/20 VAE, native 360x640 frames -> 16x18x32 latents" if args.geometry == "native" else
-                    "DiT-S/2 widths on a 16x16 latent grid + ViT-L/16 VAE, g256 preset: 256x256 frames -> 16x16x16 latents (SURVEY.md 8(d))")
-        line = {
-            "metric": "generated frames/sec (32-frame clip, 100 noise steps)", "value": round(value, 4), "unit": "generated frames/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(el / args.steps * 1e3, 2),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "fp16 (fp32 accumulate/residual)",
-            "data": "synthetic (seeded CPU-generated prompt frames + noise by global sample id, hash-seeded random weights incl. adaLN)" +
-                    (" — REHEARSAL: all ranks on one GPU over gloo, the numbers mean nothing" if os.environ.get("GTAV_BENCH_REHEARSE_ONE_GPU") == "1" and world > 1 else ""),
-            "config": {"workload": "BASELINE configs[%d]: %s, %d frames (%d prompt), %d noise steps, batch %d per GPU%s" %
-                                   (2 if args.use_actions else 1, cfg_name, total, n_prompt, steps, B,
-                                    ", action-conditioned" if args.use_actions else ", no actions"),
-                       "global_batch": world * B, "algorithm": "window-recompute (reference behaviour)" if head == "window" else "ctx-cached",
-                       "parallelism": "batch-sharded x%d (one process per GPU), one all-gather of latents per clip" % world,
-                       "vae_in_timed_region": vae is not None, "geometry": args.geometry},
-            "all_frames_per_s": round(world * B * total * args.steps / el, 4),          # B * 32 / wall (SURVEY.md 8(d))
-            "dit_forwards_per_s": round(world * (total - n_prompt) * (steps + 1) * args.steps / el, 2),   # batched forwards of B samples
-            "roofline": roofline, "cpu_baseline": cpu, "dit_step": dit_step,
-            "roofline_cached": roofline_cached, "dit_step_cached": dit_step_cached, "weight_prefetch": prefetch_choice,
-        }
+        line = headline_line()
+        line.update({"roofline": roofline, "cpu_baseline": cpu, "dit_step": dit_step, "roofline_cached": roofline_cached, "dit_step_cached": dit_step_cached})
         line.update(algo_report(B, results))
         line["timer"] = timer_calibration()
         line["wall"] = {"total_s": round(time.time() - T_START, 1), "budget_s": args.wall_budget, "legs_s": leg_wall, "skipped_legs": skipped_legs}

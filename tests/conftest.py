@@ -7,6 +7,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+# torch's CPU sin / cos run through MKL's vector math, whose last bits depend on the code branch MKL picks for the host CPU: its AVX-512 branch on an
+# Intel CPU, its generic branch on an AMD one whatever the CPU offers.  Several oracle tests compare with tests/golden bit for bit (the timestep
+# embedding, the product's host tables), so the session pins the branch every x86-64 CPU can run alike (MKL conditional numerical reproducibility,
+# COMPATIBLE); g0_constants and g1_ops_dit were recorded under the same setting (tools/make_golden.py).  MKL reads it at its first call: it is set
+# here, before any test computes anything, and passes to the subprocesses tests start.
+os.environ.setdefault("MKL_CBWR", "COMPATIBLE")
+
 
 # tests/exp/ holds the checks of code that exists only in the EXPERIMENTS build (csrc/build.sh exp -> libgtav_amd_exp.so: the LayerNorm fold, the persistent
 # 256-token-tile kernel — measured slower, kept for tools/).  One process never mixes the two libraries, so they run in a session of their own:

@@ -191,6 +191,35 @@ def test_bench_launcher_unit():
     assert rc == 2 and __import__("time").time() - t0 < 120
 
 
+def test_bench_full_option_and_dump_outputs(tmp_path):
+    """A plain run is not --full; --dump-outputs writes float32 .npy files, a large array as a fixed seeded sample of its flat elements, the
+    whole directory within 64 MB, identical from call to call."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not a.full and a.dump_outputs is None and a.steps == 3
+    a = bench.parse_args(["--full", "--dump-outputs", str(tmp_path)])
+    assert a.full and a.dump_outputs == str(tmp_path)
+    g = torch.Generator().manual_seed(1)
+    lat = torch.randn(1, 32, 16, 18, 32, generator=g)
+    frames = torch.randint(0, 256, (1, 32, 360, 640, 3), generator=g, dtype=torch.uint8)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"latents": lat, "frames_u8": frames, "absent": None})
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["frames_u8_sample.npy", "latents.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    la, fa = np.load(tmp_path / "a" / "latents.npy"), np.load(tmp_path / "a" / "frames_u8_sample.npy")
+    assert la.dtype == np.float32 and la.shape == tuple(lat.shape) and np.array_equal(la, lat.numpy())
+    assert fa.dtype == np.float32 and fa.ndim == 1 and fa.size == bench.DUMP_ELEMS // 2
+    idx = torch.randint(frames.numel(), (fa.size,), generator=torch.Generator().manual_seed(0)).sort().values
+    assert np.array_equal(fa, frames.reshape(-1)[idx].float().numpy())
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+
+
 def test_video_writer_and_one_hot(tmp_path):
     """§8(f)2 host side: uint8 frames -> Motion-JPEG AVI (RIFF structure, frame count, size, round trip within JPEG error),
     .npy and PNG-directory outputs; the 25-way action one-hot with -1 -> zero row (web_dataset.py:22-38)."""

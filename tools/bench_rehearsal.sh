@@ -8,7 +8,7 @@ OUT=${1:-gpurun_out/rehearsal}
 mkdir -p "$OUT"
 export GTAV_BENCH_REHEARSE_ONE_GPU=1 HSA_ENABLE_IPC_MODE_LEGACY=0
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 2 --steps 1 --warmup 1 \
-    --batched-clips 1 > "$OUT/bench_gpus2_generate.json" 2> "$OUT/bench_gpus2_generate.err"
+    --full --batched-clips 1 > "$OUT/bench_gpus2_generate.json" 2> "$OUT/bench_gpus2_generate.err"
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29542 bench.py --gpus 2 --steps 2 --warmup 1 \
     --mode train_step > "$OUT/bench_gpus2_train_step.json" 2> "$OUT/bench_gpus2_train_step.err"
 tail -c 600 "$OUT/bench_gpus2_generate.json"; echo; tail -c 600 "$OUT/bench_gpus2_train_step.json"; echo

@@ -1,6 +1,9 @@
 """Generates tests/golden/*.safetensors by running the ACTUAL reference (/root/reference) on CPU.
 
 Run in the build container only:   PYTHONDONTWRITEBYTECODE=1 python tools/make_golden.py
+g0_constants and g1_ops_dit, which tests compare bit for bit or nearly so, were recorded with MKL_CBWR=COMPATIBLE, the MKL branch
+tests/conftest.py pins (torch's CPU sin / cos differ in the last bits between MKL's branches); the other files, compared within
+tolerances, come from MKL's AVX-512 branch.
 The reference is imported through tools/ref_shim.py (stubs for the absent third-party packages); its
 modules are loaded with this repo's deterministic synthetic weights (gtav_amd.weights.synth_state_dict, every
 matrix non-zero — the reference's own init zeroes the adaLN gates, which would make every block the identity).

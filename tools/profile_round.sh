@@ -9,7 +9,7 @@ ROOT=$PWD
 OUT=$ROOT/gpurun_out/prof
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-COMMON="--no-cpu-baseline --batched-clips 0 --train-leg-steps 0 --g256-clips 0 --warmup 0"
+COMMON="--full --no-cpu-baseline --batched-clips 0 --train-leg-steps 0 --g256-clips 0 --warmup 0"
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/config2_window" -o run -- python3 "$ROOT/bench.py" --batch-per-gpu 8 --use-actions --algo window --steps 1 $COMMON > "$OUT/config2_window.json" 2> "$OUT/config2_window.err"
 echo "config2 window done" 

@@ -17,6 +17,6 @@ rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/config4_step" -o r
 echo "config4 step done"
 cd "$ROOT"
 find "$OUT" -name "*kernel_trace.csv" -delete
-python3 bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+python3 bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 echo "bench done"
 ls -R "$OUT" | head -40

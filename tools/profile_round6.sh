@@ -10,7 +10,7 @@ OUT=$ROOT/gpurun_out/prof6
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 LEGS=${@:-c1 c2w c2c}
-COMMON="--no-cpu-baseline --config4-steps 0 --g256-clips 0 --warmup 0"
+COMMON="--full --no-cpu-baseline --config4-steps 0 --g256-clips 0 --warmup 0"
 for leg in $LEGS; do
   case $leg in
     c1)  ARGS="--algo both --steps 2 --cached-clips 1 --batched-clips 0"; LEGNAME=headline ;;
