@@ -59,6 +59,56 @@ const OperandOps OPS_BF16 = {bf_gemm, bf_ln_modulate, bf_ln_affine, bf_patchify,
 }  // namespace
 const OperandOps& gtav::operand_ops(bool bf16) { return bf16 ? OPS_BF16 : OPS_F16; }
 
+// ---- the training step's launchers per operand type (ops_bf16.h TrainOps) ----
+namespace {
+typedef const __bf16* cbp;
+typedef __bf16* bp;
+int f16_dw_grouped(const GemmDwGroup* g, int n, int K, int* ef, hipStream_t st, bool tn) { return launch_gemm_dw_grouped(g, n, K, ef, st, tn); }
+int bf_gemm_tn(const GemmParams& p, hipStream_t st) { return gtav_bf16::launch_gemm_tn(bfp(p), st); }
+int bf_dw_grouped(const GemmDwGroup* g, int n, int K, int* ef, hipStream_t st, bool tn) {
+    return gtav_bf16::launch_gemm_dw_grouped(reinterpret_cast<const gtav_bf16::GemmDwGroup*>(g), n, K, ef, st, tn);
+}
+int bf_transpose(const f16* src, int R, int C, f16* dst, hipStream_t st) { return gtav_bf16::launch_transpose_tiled_f16((cbp)src, R, C, (bp)dst, st); }
+int bf_convert_T(const float* src, int lds, int R, int C, f16* dst, hipStream_t st) { return gtav_bf16::launch_convert_T_f16(src, lds, R, C, (bp)dst, st); }
+int bf_gelu(const f16* u, f16* h, size_t n, hipStream_t st) { return gtav_bf16::launch_gelu_tiled((cbp)u, (bp)h, n, st); }
+int bf_gelu_bwd(const f16* dh, const f16* u, f16* du, size_t n, int* ef, hipStream_t st) { return gtav_bf16::launch_gelu_bwd_tiled((cbp)dh, (cbp)u, (bp)du, n, ef, st); }
+int bf_gelu_bwd_colsum(const f16* dh, const f16* u, f16* du, int M, int N, float* db, float* ws, int* ef, hipStream_t st) {
+    return gtav_bf16::launch_gelu_bwd_tiled_colsum((cbp)dh, (cbp)u, (bp)du, M, N, db, ws, ef, st);
+}
+int bf_gate_bwd(const float* dres, const float* gate, int ms, int rpm, int M, int D, f16* dy, int* ef, hipStream_t st) {
+    return gtav_bf16::launch_gate_bwd(dres, gate, ms, rpm, M, D, (bp)dy, ef, st);
+}
+int bf_frame_reduce_gate(const float* dres, const f16* y, int frames, int P, int D, float* dgate, int ms, hipStream_t st) {
+    return gtav_bf16::launch_frame_reduce_gate(dres, (cbp)y, frames, P, D, dgate, ms, st);
+}
+int bf_gate_bwd_fused(const float* dres, const f16* y, const float* gate, int ms, int frames, int P, int D, f16* dy, float* dgate, float* db, float* ws, int* ef,
+                      hipStream_t st) {
+    return gtav_bf16::launch_gate_bwd_fused(dres, (cbp)y, gate, ms, frames, P, D, (bp)dy, dgate, db, ws, ef, st);
+}
+int bf_colsum(const f16* dy, int M, int N, float* db, float* ws, hipStream_t st) { return gtav_bf16::launch_colsum_tiled_f16((cbp)dy, M, N, db, ws, st); }
+int bf_to_tiled(const float* a, int M, int D, f16* out, int* ef, hipStream_t st) { return gtav_bf16::launch_to_tiled_f16(a, M, D, (bp)out, ef, st); }
+int bf_mse_bwd(const float* vp, const float* vt, int B, int T, int C, int H, int W, int p, float scale, f16* dfo, int ldf, int* ef, hipStream_t st) {
+    return gtav_bf16::launch_mse_bwd_patch(vp, vt, B, T, C, H, W, p, scale, (bp)dfo, ldf, ef, st);
+}
+int bf_attn_spatial_bwd(const f16* Q, const f16* K, const f16* Vt, const f16* dO, int NB, int heads, int S, int D, const float* cs, f16* dqkv, int* ef,
+                        hipStream_t st) {
+    return gtav_bf16::launch_attn_spatial_bwd((cbp)Q, (cbp)K, (cbp)Vt, (cbp)dO, NB, heads, S, D, cs, (bp)dqkv, ef, st);
+}
+int bf_attn_temporal_bwd(const f16* q, const f16* kv, const f16* dO, int B, int P, int D, int T, int Tmax, const float* cs, f16* dqkv, int* ef, hipStream_t st) {
+    return gtav_bf16::launch_attn_temporal_bwd((cbp)q, (cbp)kv, (cbp)dO, B, P, D, T, Tmax, cs, (bp)dqkv, ef, st);
+}
+int bf_adamw_multi(const AdamParam* params, const AdamItem* items, int n, const float* ctl, float lr, float b1, float b2, float eps, float wd, hipStream_t st) {
+    return gtav_bf16::launch_adamw_multi(reinterpret_cast<const gtav_bf16::AdamParam*>(params), reinterpret_cast<const gtav_bf16::AdamItem*>(items), n, ctl, lr,
+                                         b1, b2, eps, wd, st);
+}
+const TrainOps TRAIN_F16 = {launch_gemm_tn, f16_dw_grouped, launch_transpose_tiled_f16, launch_convert_T_f16, launch_gelu_tiled, launch_gelu_bwd_tiled,
+                            launch_gelu_bwd_tiled_colsum, launch_gate_bwd, launch_frame_reduce_gate, launch_gate_bwd_fused, launch_colsum_tiled_f16,
+                            launch_to_tiled_f16, launch_mse_bwd_patch, launch_attn_spatial_bwd, launch_attn_temporal_bwd, launch_adamw_multi, false};
+const TrainOps TRAIN_BF16 = {bf_gemm_tn, bf_dw_grouped, bf_transpose, bf_convert_T, bf_gelu, bf_gelu_bwd, bf_gelu_bwd_colsum, bf_gate_bwd, bf_frame_reduce_gate,
+                             bf_gate_bwd_fused, bf_colsum, bf_to_tiled, bf_mse_bwd, bf_attn_spatial_bwd, bf_attn_temporal_bwd, bf_adamw_multi, true};
+}  // namespace
+const TrainOps& gtav::train_ops(bool bf16) { return bf16 ? TRAIN_BF16 : TRAIN_F16; }
+
 extern "C" {
 
 const char* gtav_last_error(void) { return gtav::last_error(); }

@@ -753,7 +753,11 @@ int gtav_dit_set_operand_dtype(gtav_dit* h, int32_t group, int32_t dtype) {
     GTAV_REQUIRE(h, "dit_set_operand_dtype: null handle");
     GTAV_REQUIRE(dtype == GTAV_OPERAND_F16 || dtype == GTAV_OPERAND_BF16, "dit_set_operand_dtype: dtype %d (0 = fp16, 1 = bf16)", dtype);
     GTAV_REQUIRE(group >= -1 && group < h->n_groups, "dit_set_operand_dtype: group %d outside [-1, %d)", group, h->n_groups);
-    GTAV_REQUIRE(!h->tr.on || dtype == GTAV_OPERAND_F16, "dit_set_operand_dtype: a training handle keeps fp16 operands (its backward pass and loss scaling are fp16)");
+    if (h->tr.on && h->tr.bf16)   // enabled by gtav_dit_train_enable_typed(.., GTAV_OPERAND_BF16): every group is bf16 and stays so
+        GTAV_REQUIRE(dtype == GTAV_OPERAND_BF16, "dit_set_operand_dtype: a bf16 training handle keeps bf16 operands in every group (its masters, optimizer state and "
+                     "loss scale were set up for them; create a new handle to train on fp16 operands)");
+    else
+        GTAV_REQUIRE(!h->tr.on || dtype == GTAV_OPERAND_F16, "dit_set_operand_dtype: a training handle keeps fp16 operands (its backward pass and loss scaling are fp16)");
     int changed = 0;
     for (int g = (group < 0 ? 0 : group); g < (group < 0 ? h->n_groups : group + 1); ++g) {
         if ((h->grp_bf16[g] != 0) == (dtype == GTAV_OPERAND_BF16)) continue;

@@ -105,7 +105,7 @@ struct WeightTable {
         }
         else RET_IF(launch_copy_f32(src, sl.C, sl.R, sl.C, (float*)sl.dst, sl.Cp, sl.c0, s));
         if (sl.master && sl.kind == SLOT_F16_PAD) RET_IF(launch_copy_f32(src, sl.C, sl.R, sl.C, sl.master, sl.C, 0, s));
-        if (sl.wT) RET_IF(launch_convert_T_f16(src, sl.C, sl.R, sl.C, sl.wT, s));
+        if (sl.wT) RET_IF(train_ops(sl.bf16).convert_T(src, sl.C, sl.R, sl.C, sl.wT, s));
         sl.set = true;
         return 0;
     }
@@ -285,6 +285,7 @@ struct gtav_dit {
     int n_groups = 0;
     bool any_bf16 = false;
     const OperandOps& ops(int g) const { return operand_ops(grp_bf16[g] != 0); }
+    const TrainOps& tops(int g) const { return train_ops(grp_bf16[g] != 0); }   // the training step's launchers of group g (api_train.hip)
     int* err_of(int g) const { return err_flag + 4 + g; }
     int* frame_idx = nullptr;   // [maxB * maxT]
     StepParams* step_dev = nullptr;
@@ -355,8 +356,9 @@ struct gtav_dit {
     // ---- training: saved activations of the last training forward, backward workspace, optimizer state ----
     struct Train {
         bool on = false, have_fwd = false, have_actions = false;
+        bool bf16 = false;                  // every operand group bf16 (gtav_dit_train_enable_typed): no group may change its type while training is on
         int B = 0, T = 0, M = 0, Mp = 0, rows = 0;
-        float loss_scale = 65536.0f;
+        float loss_scale = 65536.0f;        // (1 on a bf16 handle)
         float grad_div = 1.0f;              // the arena holds the sum over this many ranks (gtav_dit_set_grad_divisor)
         std::vector<Slot*> params;          // trainable slots in a fixed (sorted-by-name) order
         float* grad_arena = nullptr;        // all gradients, contiguous (one all-reduce); caller-owned when passed to train_enable

@@ -8,6 +8,9 @@ static int g_fuse_ln = GTAV_ENV_INT("GTAV_FUSE_LN_BWD", 1);     // experiments b
 static int g_fuse_gate = GTAV_ENV_INT("GTAV_FUSE_GATE", 1);     // experiments build: 0 = gate_bwd, frame_reduce_gate and the bias column sums as three launches (A/B runs)
 static int g_dw_tn = GTAV_ENV_INT("GTAV_DW_TN", 1);             // experiments build: 0 = transposed operand copies in front of the grouped launch (A/B runs)
 
+// gtav_dit_train_enable after its operand-type checks: trainable slots, fp32 masters, AdamW state, saved-activation and backward workspace
+static int train_enable_body(gtav_dit* h, float* grad_arena_dev, int64_t grad_arena_numel);
+
 extern "C" {
 
 // ================================================================================================
@@ -16,11 +19,36 @@ extern "C" {
 // :965-970 clip_grad_norm_ / optimizer.step / zero_grad.  Mixed precision like the reference's bf16 autocast + fp32 master
 // weights, with fp16 operands and a loss scale in place of bf16's exponent range: activation gradients travel as fp16 GEMM
 // operands multiplied by tr.loss_scale, weight gradients / LayerNorm statistics / the residual-stream gradient are fp32.
+// gtav_dit_train_enable_typed(.., GTAV_OPERAND_BF16) runs the same step on bf16 operands (the reference's own autocast type): every launch below that
+// reads or writes a 2-byte tensor goes through the operand group's launcher set (h->ops(g) / h->tops(g)), the twins of the same kernels (ops_bf16.h).
 // ================================================================================================
 int gtav_dit_train_enable(gtav_dit* h, float* grad_arena_dev, int64_t grad_arena_numel) {
     GTAV_REQUIRE(h, "train_enable: null handle");
     GTAV_REQUIRE(!h->tr.on, "train_enable: already enabled");
     GTAV_REQUIRE(!h->any_bf16, "train_enable: the training step runs on fp16 operands (gtav_dit_set_operand_dtype(h, -1, GTAV_OPERAND_F16) first)");
+    return train_enable_body(h, grad_arena_dev, grad_arena_numel);
+}
+
+int gtav_dit_train_enable_typed(gtav_dit* h, float* grad_arena_dev, int64_t grad_arena_numel, int32_t dtype) {
+    GTAV_REQUIRE(h, "train_enable_typed: null handle");
+    GTAV_REQUIRE(dtype == GTAV_OPERAND_F16 || dtype == GTAV_OPERAND_BF16, "train_enable_typed: dtype %d (0 = fp16, 1 = bf16)", dtype);
+    if (dtype == GTAV_OPERAND_F16) return gtav_dit_train_enable(h, grad_arena_dev, grad_arena_numel);
+    GTAV_REQUIRE(!h->tr.on, "train_enable: already enabled");
+    int nb = 0;
+    for (unsigned char b : h->grp_bf16) nb += b != 0;
+    GTAV_REQUIRE(nb == 0 || nb == h->n_groups, "train_enable_typed: %d of the %d operand groups are bf16; a training handle has one operand type for every group", nb,
+                 h->n_groups);
+    // (before the type switch, which un-sets the weight slots it converts)
+    for (auto& kv : h->wt.slots) GTAV_REQUIRE(!kv.second.set, "train_enable: call it before any gtav_dit_set_weight (the fp32 masters are filled by set_weight)");
+    RET_IF(gtav_dit_set_operand_dtype(h, -1, GTAV_OPERAND_BF16));
+    h->tr.bf16 = true;
+    h->tr.loss_scale = 1.0f;   // bf16 has fp32's exponent range: the reference trains it without a scaler (gtav_dit_set_loss_scale still applies)
+    return train_enable_body(h, grad_arena_dev, grad_arena_numel);
+}
+
+}  // extern "C"
+
+static int train_enable_body(gtav_dit* h, float* grad_arena_dev, int64_t grad_arena_numel) {
     for (auto& kv : h->wt.slots) GTAV_REQUIRE(!kv.second.set, "train_enable: call it before any gtav_dit_set_weight (the fp32 masters are filled by set_weight)");
     gtav_dit::Train& t = h->tr;
     Arena& a = h->arena;
@@ -119,6 +147,8 @@ int gtav_dit_train_enable(gtav_dit* h, float* grad_arena_dev, int64_t grad_arena
     return 0;
 }
 
+extern "C" {
+
 int gtav_dit_train_param_count(gtav_dit* h, int64_t* numel) {
     GTAV_REQUIRE(h && numel, "train_param_count: null argument");
     int64_t c = 0;
@@ -179,20 +209,21 @@ int gtav_dit_train_forward(gtav_dit* h, const float* x, const int64_t* t64, cons
     RET_IF(launch_silu(tr.cpre, D, h->Sc, D, rows, D, s));
     RET_IF(launch_skinny_f32(h->Sc, D, h->w_ada, h->b_ada, h->mod, h->MODW, rows, h->MODW, D, 0, s));
     const float* mod = h->mod;
-    RET_IF(launch_patchify(x, nullptr, NB, h->C, h->H, h->W, h->p, tr.xp, h->Kpe, 1.f, 0.f, h->err_flag, s));
+    const OperandOps& oe = h->ops(2 * L), &ofin = h->ops(2 * L + 1);   // patch embedding, final layer (the half-blocks: h->ops(i) below)
+    RET_IF(oe.patchify(x, nullptr, NB, h->C, h->H, h->W, h->p, tr.xp, h->Kpe, 1.f, 0.f, h->err_flag, s));
     GemmParams g;
     memset(&g, 0, sizeof(g));
     g.X = tr.xp; g.ldx = h->Kpe; g.W = h->w_pe; g.M = M; g.N = D; g.K = h->Kpe; g.bias = h->b_pe; g.out = tr.res[0]; g.ldo = D;
-    RET_IF(launch_gemm(g, EPI_F32, s));
+    RET_IF(oe.gemm(g, EPI_F32, s));
     LnPending pend;
     bool have_pend = false;
-    auto resid_gemm = [&](const f16* X, const f16* Wt, int K, const float* bias, const float* gate, float* x_out, f16* y_save) -> int {
+    auto resid_gemm = [&](const OperandOps& o, const f16* X, const f16* Wt, int K, const float* bias, const float* gate, float* x_out, f16* y_save) -> int {
         GemmParams q;
         memset(&q, 0, sizeof(q));
         q.X = X; q.ldx = K; q.W = Wt; q.M = M; q.N = D; q.K = K; q.out = h->parts; q.ldo = D;
         q.splitk = gemm_choose_splitk(M, D, K);
         GTAV_REQUIRE((size_t)q.splitk * M <= h->parts_rows, "split-K slabs exceed workspace");
-        RET_IF(launch_gemm(q, EPI_PARTIAL, s));
+        RET_IF(o.gemm(q, EPI_PARTIAL, s));
         memset(&pend, 0, sizeof(pend));
         pend.parts = h->parts; pend.nsplit = q.splitk; pend.slab_stride = (size_t)M * D; pend.ld = D; pend.bias = bias;
         pend.gate = gate; pend.gate_stride = h->MODW; pend.gate_rows = nullptr; pend.rows_per_gate = P;
@@ -206,31 +237,32 @@ int gtav_dit_train_forward(gtav_dit* h, const float* x, const int64_t* t64, cons
             const gtav_dit::Half& w = h->halves[i];
             gtav_dit::Train::HB& b = tr.hb[i];
             const float* mb = mod + (size_t)i * 6 * D;
+            const OperandOps& o = h->ops(i);
             // LN1 normalises r_{2i} (= r_{2i-1} + gate (fc2 of the previous half-block), written to res[2i] by this launch)
-            RET_IF(launch_ln_modulate(i == 0 ? tr.res[0] : tr.res[2 * i - 1], D, b.xnA, D, M, D, mb, mb + D, h->MODW, nullptr, P, have_pend ? &pend : nullptr, h->err_flag, s));
+            RET_IF(o.ln_modulate(i == 0 ? tr.res[0] : tr.res[2 * i - 1], D, b.xnA, D, M, D, mb, mb + D, h->MODW, nullptr, P, have_pend ? &pend : nullptr, h->err_flag, s));
             have_pend = false;
             memset(&g, 0, sizeof(g));
             g.X = b.xnA; g.ldx = D; g.W = w.w_qkv; g.M = M; g.N = 3 * D; g.K = D; g.D = D; g.S = P; g.err_flag = h->err_flag;
             if (hf == 0) { g.qkv_mode = QKV_SPATIAL; g.q = b.q; g.k = b.k; g.v = b.v; g.rope_cs = h->rope_s.cs_dev; }
             else { g.qkv_mode = QKV_TEMPORAL; g.q = b.q; g.k = b.k; g.v = b.k; g.Tq = T; g.t0 = 0; g.Tmax = h->maxT; g.rope_cs = h->rope_t.cs_dev; }
-            RET_IF(launch_gemm(g, EPI_QKV, s));
-            if (hf == 0) RET_IF(launch_attn_spatial(b.q, b.k, b.v, b.ao, NB, h->heads, P, s));
-            else RET_IF(launch_attn_temporal(b.q, b.k, b.ao, B, P, D, T, 0, h->maxT, s));
-            RET_IF(resid_gemm(b.ao, w.w_out, D, w.b_out, mb + 2 * D, tr.res[2 * i + 1], b.y1));
-            RET_IF(launch_ln_modulate(tr.res[2 * i], D, b.xnB, D, M, D, mb + 3 * D, mb + 4 * D, h->MODW, nullptr, P, &pend, h->err_flag, s));
+            RET_IF(o.gemm(g, EPI_QKV, s));
+            if (hf == 0) RET_IF(o.attn_spatial(b.q, b.k, b.v, b.ao, NB, h->heads, P, s, false));
+            else RET_IF(o.attn_temporal(b.q, b.k, b.ao, B, P, D, T, 0, h->maxT, s));
+            RET_IF(resid_gemm(o, b.ao, w.w_out, D, w.b_out, mb + 2 * D, tr.res[2 * i + 1], b.y1));
+            RET_IF(o.ln_modulate(tr.res[2 * i], D, b.xnB, D, M, D, mb + 3 * D, mb + 4 * D, h->MODW, nullptr, P, &pend, h->err_flag, s));
             have_pend = false;
             memset(&g, 0, sizeof(g));
             g.X = b.xnB; g.ldx = D; g.W = w.w_fc1; g.M = M; g.N = h->Hm; g.K = D; g.bias = w.b_fc1; g.out = b.u; g.ldo = h->Hm_pad; g.err_flag = h->err_flag;
             if (g_fuse_gelu_fwd) g.out2 = b.hh;             // h = GELU(u) as a second image of the same epilogue (gemm.h out2)
-            RET_IF(launch_gemm(g, EPI_F16_TILED, s));       // the pre-activation is kept: gelu'(u) in the backward pass
-            if (!g_fuse_gelu_fwd) RET_IF(launch_gelu_tiled(b.u, b.hh, (size_t)round_up(M, 128) * h->Hm_pad, s));
-            RET_IF(resid_gemm(b.hh, w.w_fc2, h->Hm_pad, w.b_fc2, mb + 5 * D, tr.res[2 * i + 2], b.y2));
+            RET_IF(o.gemm(g, EPI_F16_TILED, s));            // the pre-activation is kept: gelu'(u) in the backward pass
+            if (!g_fuse_gelu_fwd) RET_IF(h->tops(i).gelu_tiled(b.u, b.hh, (size_t)round_up(M, 128) * h->Hm_pad, s));
+            RET_IF(resid_gemm(o, b.hh, w.w_fc2, h->Hm_pad, w.b_fc2, mb + 5 * D, tr.res[2 * i + 2], b.y2));
         }
     const float* mf = mod + (size_t)L * 12 * D;
-    RET_IF(launch_ln_modulate(tr.res[4 * L - 1], D, tr.xnF, D, M, D, mf, mf + D, h->MODW, nullptr, P, &pend, h->err_flag, s));
+    RET_IF(ofin.ln_modulate(tr.res[4 * L - 1], D, tr.xnF, D, M, D, mf, mf + D, h->MODW, nullptr, P, &pend, h->err_flag, s));
     memset(&g, 0, sizeof(g));
     g.X = tr.xnF; g.ldx = D; g.W = h->w_final; g.M = M; g.N = h->Nfin; g.K = D; g.bias = h->b_final; g.out = h->fo; g.ldo = h->Nfin;
-    RET_IF(launch_gemm(g, EPI_F32, s));
+    RET_IF(ofin.gemm(g, EPI_F32, s));
     RET_IF(launch_unpatchify(h->fo, h->Nfin, out, NB, h->C, h->H, h->W, h->p, 0, 1.f, 0.f, s));
     tr.B = B; tr.T = T; tr.M = M; tr.Mp = round_up(M, 64); tr.rows = rows; tr.have_actions = actions != nullptr; tr.have_fwd = true;
     return 0;
@@ -263,12 +295,15 @@ int gtav_dit_train_backward_phases(gtav_dit* h, const float* v_pred, const float
     const int D = h->D, P = h->P, L = h->L, B = tr.B, T = tr.T, M = tr.M, Mp = tr.Mp, NB = B * T, rows = tr.rows, Hp = h->Hm_pad, MODW = h->MODW;
     const int ldhc = D + h->Apad;
     auto slot = [&](const std::string& n) -> Slot& { return h->wt.slots[n]; };
+    // launcher sets of the operand group being differentiated (final layer, half-block i, patch embedding): set where each part begins
+    const OperandOps* op = &h->ops(2 * L + 1);
+    const TrainOps* to = &h->tops(2 * L + 1);
     // dX = dY W: A = dY tile-major [M][Kc], WT = tile-major W^T [N][Kc]
     auto gemm_dx = [&](const f16* A, const f16* WT, int N, int Kc, int epi, void* out, int ldo) -> int {
         GemmParams q;
         memset(&q, 0, sizeof(q));
         q.X = A; q.ldx = Kc; q.W = WT; q.M = M; q.N = N; q.K = Kc; q.out = out; q.ldo = ldo; q.err_flag = h->err_flag;
-        return launch_gemm(q, epi, s);
+        return op->gemm(q, epi, s);
     };
     // dW[n][k] += sum_m dY[m][n] X[m][k]: both operands transposed to [.][Mp] (tokens are the contraction), accumulating epilogue
     // Half-blocks of production widths defer their four dW GEMMs into ONE grouped launch of 256 x 256 tiles (flush_dw; gemm.h)
@@ -299,7 +334,7 @@ int gtav_dit_train_backward_phases(gtav_dit* h, const float* v_pred, const float
         if (!ndw) return 0;
         const int n = ndw;
         ndw = 0;
-        return launch_gemm_dw_grouped(dwg, n, tn_dw ? M : Mp, h->err_flag, s, tn_dw);
+        return to->gemm_dw_grouped(dwg, n, tn_dw ? M : Mp, h->err_flag, s, tn_dw);
     };
     auto gemm_dw = [&](const f16* dY, int N, const f16* X, int K, float* grad, int slot_i = -1) -> int {
         if (tn_dw && slot_i >= 0) {
@@ -307,8 +342,8 @@ int gtav_dit_train_backward_phases(gtav_dit* h, const float* v_pred, const float
             return 0;
         }
         if (defer_dw && slot_i >= 0) {
-            RET_IF(launch_transpose_tiled_f16(dY, M, N, tr.tAg[slot_i], s));
-            RET_IF(launch_transpose_tiled_f16(X, M, K, tr.tBg[slot_i], s));
+            RET_IF(to->transpose_tiled(dY, M, N, tr.tAg[slot_i], s));
+            RET_IF(to->transpose_tiled(X, M, K, tr.tBg[slot_i], s));
             dwg[ndw++] = GemmDwGroup{tr.tAg[slot_i], tr.tBg[slot_i], grad, N, K, K};
             return 0;
         }
@@ -316,14 +351,14 @@ int gtav_dit_train_backward_phases(gtav_dit* h, const float* v_pred, const float
             GemmParams q;
             memset(&q, 0, sizeof(q));
             q.X = dY; q.ldx = N; q.W = X; q.M = N; q.N = K; q.K = M; q.out = grad; q.ldo = K;
-            return launch_gemm_tn(q, s);
+            return to->gemm_tn(q, s);
         }
-        RET_IF(launch_transpose_tiled_f16(dY, M, N, tr.tA, s));
-        RET_IF(launch_transpose_tiled_f16(X, M, K, tr.tB, s));
+        RET_IF(to->transpose_tiled(dY, M, N, tr.tA, s));
+        RET_IF(to->transpose_tiled(X, M, K, tr.tB, s));
         GemmParams q;
         memset(&q, 0, sizeof(q));
         q.X = tr.tA; q.ldx = Mp; q.W = tr.tB; q.M = N; q.N = K; q.K = Mp; q.out = grad; q.ldo = K;
-        return launch_gemm(q, EPI_RESID, s);
+        return op->gemm(q, EPI_RESID, s);
     };
     const float scale = 2.0f * tr.loss_scale / ((float)B * (float)(h->C * h->H * h->W));
     GTAV_REQUIRE(h->Nfin <= 64, "train_backward: a final projection wider than 64 features is not implemented");
@@ -336,20 +371,20 @@ int gtav_dit_train_backward_phases(gtav_dit* h, const float* v_pred, const float
     };
     // ---- phase 0: loss -> final projection -> final LayerNorm ----
     if (phase_begin <= 0 && 0 < phase_end) {
-    RET_IF(launch_mse_bwd_patch(v_pred, v_target, B, T, h->C, h->H, h->W, h->p, scale, tr.dfo, 64, h->err_flag, s));
+    RET_IF(to->mse_bwd_patch(v_pred, v_target, B, T, h->C, h->H, h->W, h->p, scale, tr.dfo, 64, h->err_flag, s));
     {
         Slot& wf = slot("final_layer.linear.weight");
         // db: column sums over the 64-wide (zero-padded) dfo, only the first Nfin belong to the bias: sum into a scratch row first
         GTAV_CHECK_HIP(hipMemsetAsync(tr.dSc, 0, 64 * sizeof(float), s));
-        RET_IF(launch_colsum_tiled_f16(tr.dfo, M, 64, tr.dSc, tr.red_ws, s));
+        RET_IF(to->colsum_tiled(tr.dfo, M, 64, tr.dSc, tr.red_ws, s));
         RET_IF(launch_add_f32(slot("final_layer.linear.bias").grad, tr.dSc, slot("final_layer.linear.bias").grad, h->Nfin, s));
         // dW_final [Nfin][D] += dfo^T xnF   (M = Nfin rows of the 64-row transposed operand)
-        RET_IF(launch_transpose_tiled_f16(tr.dfo, M, 64, tr.tA, s));
-        RET_IF(launch_transpose_tiled_f16(tr.xnF, M, D, tr.tB, s));
+        RET_IF(to->transpose_tiled(tr.dfo, M, 64, tr.tA, s));
+        RET_IF(to->transpose_tiled(tr.xnF, M, D, tr.tB, s));
         GemmParams q;
         memset(&q, 0, sizeof(q));
         q.X = tr.tA; q.ldx = Mp; q.W = tr.tB; q.M = h->Nfin; q.N = D; q.K = Mp; q.out = wf.grad; q.ldo = D;
-        RET_IF(launch_gemm(q, EPI_RESID, s));
+        RET_IF(op->gemm(q, EPI_RESID, s));
         // d xnF = dfo W_final  -> fp32 [M][D]
         RET_IF(gemm_dx(tr.dfo, wf.wT, D, 64, EPI_F32, tr.dtmp, D));
         const float* mf = mod + (size_t)L * 12 * D;
@@ -369,25 +404,27 @@ int gtav_dit_train_backward_phases(gtav_dit* h, const float* v_pred, const float
         const std::string P_(pre);
         const float* mb = mod + (size_t)i * 6 * D;
         float* dmb = dmod + (size_t)i * 6 * D;
+        op = &h->ops(i);
+        to = &h->tops(i);
         // r_{2i+2} = r_{2i+1} + gate_mlp y2
         // (defer_bias: the partial sums of the half-block's three bias gradients go to three regions of the workspace and ONE launch adds them at the end of the half-block)
         float* const ws_fc2 = tr.red_ws, *const ws_out = tr.red_ws + (defer_bias ? (size_t)NB * D : 0), *const ws_fc1 = tr.red_ws + (defer_bias ? (size_t)2 * NB * D : 0);   // (not deferred: every reduction follows its partial sums at once and the regions may coincide)
         if (fuse_gate) {
-            RET_IF(launch_gate_bwd_fused(tr.dres, b.y2, mb + 5 * D, MODW, NB, P, D, tr.g_d, dmb + 5 * D, defer_bias ? nullptr : slot(P_ + "mlp.fc2.bias").grad, ws_fc2, h->err_flag, s));
+            RET_IF(to->gate_bwd_fused(tr.dres, b.y2, mb + 5 * D, MODW, NB, P, D, tr.g_d, dmb + 5 * D, defer_bias ? nullptr : slot(P_ + "mlp.fc2.bias").grad, ws_fc2, h->err_flag, s));
         } else {
-            RET_IF(launch_gate_bwd(tr.dres, mb + 5 * D, MODW, P, M, D, tr.g_d, h->err_flag, s));
-            RET_IF(launch_frame_reduce_gate(tr.dres, b.y2, NB, P, D, dmb + 5 * D, MODW, s));
-            RET_IF(launch_colsum_tiled_f16(tr.g_d, M, D, slot(P_ + "mlp.fc2.bias").grad, tr.red_ws, s));
+            RET_IF(to->gate_bwd(tr.dres, mb + 5 * D, MODW, P, M, D, tr.g_d, h->err_flag, s));
+            RET_IF(to->frame_reduce_gate(tr.dres, b.y2, NB, P, D, dmb + 5 * D, MODW, s));
+            RET_IF(to->colsum_tiled(tr.g_d, M, D, slot(P_ + "mlp.fc2.bias").grad, tr.red_ws, s));
         }
         RET_IF(gemm_dw(tr.g_d, D, b.hh, Hp, slot(P_ + "mlp.fc2.weight").grad, 0));
         RET_IF(gemm_dx(tr.g_d, slot(P_ + "mlp.fc2.weight").wT, Hp, D, EPI_F16_TILED, tr.g_h, Hp));
         if (defer_bias) {
-            RET_IF(launch_gelu_bwd_tiled_colsum(tr.g_h, b.u, tr.g_u, M, Hp, nullptr, ws_fc1, h->err_flag, s));
+            RET_IF(to->gelu_bwd_tiled_colsum(tr.g_h, b.u, tr.g_u, M, Hp, nullptr, ws_fc1, h->err_flag, s));
         } else if (g_fuse_gelu && colsum_workspace(round_up(M, 128), Hp) <= ws_cap) {
-            RET_IF(launch_gelu_bwd_tiled_colsum(tr.g_h, b.u, tr.g_u, M, Hp, slot(P_ + "mlp.fc1.bias").grad, tr.red_ws, h->err_flag, s));
+            RET_IF(to->gelu_bwd_tiled_colsum(tr.g_h, b.u, tr.g_u, M, Hp, slot(P_ + "mlp.fc1.bias").grad, tr.red_ws, h->err_flag, s));
         } else {
-            RET_IF(launch_gelu_bwd_tiled(tr.g_h, b.u, tr.g_u, (size_t)round_up(M, 128) * Hp, h->err_flag, s));
-            RET_IF(launch_colsum_tiled_f16(tr.g_u, M, Hp, slot(P_ + "mlp.fc1.bias").grad, tr.red_ws, s));
+            RET_IF(to->gelu_bwd_tiled(tr.g_h, b.u, tr.g_u, (size_t)round_up(M, 128) * Hp, h->err_flag, s));
+            RET_IF(to->colsum_tiled(tr.g_u, M, Hp, slot(P_ + "mlp.fc1.bias").grad, tr.red_ws, s));
         }
         RET_IF(gemm_dw(tr.g_u, Hp, b.xnB, D, slot(P_ + "mlp.fc1.weight").grad, 1));
         RET_IF(gemm_dx(tr.g_u, slot(P_ + "mlp.fc1.weight").wT, D, Hp, EPI_F32, tr.dtmp, D));
@@ -395,16 +432,16 @@ int gtav_dit_train_backward_phases(gtav_dit* h, const float* v_pred, const float
         // r_{2i+1} = r_{2i} + gate_msa y1
         f16* const g_o = tn_dw ? tr.g_d2 : tr.g_d;   // (the fc2 weight gradient above still reads g_d when the grouped launch is deferred without copies)
         if (fuse_gate) {
-            RET_IF(launch_gate_bwd_fused(tr.dres, b.y1, mb + 2 * D, MODW, NB, P, D, g_o, dmb + 2 * D, defer_bias ? nullptr : slot(P_ + "attn.to_out.bias").grad, ws_out, h->err_flag, s));
+            RET_IF(to->gate_bwd_fused(tr.dres, b.y1, mb + 2 * D, MODW, NB, P, D, g_o, dmb + 2 * D, defer_bias ? nullptr : slot(P_ + "attn.to_out.bias").grad, ws_out, h->err_flag, s));
         } else {
-            RET_IF(launch_gate_bwd(tr.dres, mb + 2 * D, MODW, P, M, D, g_o, h->err_flag, s));
-            RET_IF(launch_frame_reduce_gate(tr.dres, b.y1, NB, P, D, dmb + 2 * D, MODW, s));
-            RET_IF(launch_colsum_tiled_f16(g_o, M, D, slot(P_ + "attn.to_out.bias").grad, tr.red_ws, s));
+            RET_IF(to->gate_bwd(tr.dres, mb + 2 * D, MODW, P, M, D, g_o, h->err_flag, s));
+            RET_IF(to->frame_reduce_gate(tr.dres, b.y1, NB, P, D, dmb + 2 * D, MODW, s));
+            RET_IF(to->colsum_tiled(g_o, M, D, slot(P_ + "attn.to_out.bias").grad, tr.red_ws, s));
         }
         RET_IF(gemm_dw(g_o, D, b.ao, D, slot(P_ + "attn.to_out.weight").grad, 2));
         RET_IF(gemm_dx(g_o, slot(P_ + "attn.to_out.weight").wT, D, D, EPI_F16, tr.dao, D));
-        if (hf == 0) RET_IF(launch_attn_spatial_bwd(b.q, b.k, b.v, tr.dao, NB, h->heads, P, D, h->rope_s.cs_dev, tr.g_qkv, h->err_flag, s));
-        else RET_IF(launch_attn_temporal_bwd(b.q, b.k, tr.dao, B, P, D, T, h->maxT, h->rope_t.cs_dev, tr.g_qkv, h->err_flag, s));
+        if (hf == 0) RET_IF(to->attn_spatial_bwd(b.q, b.k, b.v, tr.dao, NB, h->heads, P, D, h->rope_s.cs_dev, tr.g_qkv, h->err_flag, s));
+        else RET_IF(to->attn_temporal_bwd(b.q, b.k, tr.dao, B, P, D, T, h->maxT, h->rope_t.cs_dev, tr.g_qkv, h->err_flag, s));
         RET_IF(gemm_dw(tr.g_qkv, 3 * D, b.xnA, D, slot(P_ + "attn.to_qkv.weight").grad, 3));
         if (defer_bias) {
             const float* wsv[3] = {ws_fc2, ws_out, ws_fc1};
@@ -420,8 +457,10 @@ int gtav_dit_train_backward_phases(gtav_dit* h, const float* v_pred, const float
     }
     if (!(phase_begin <= L + 1 && L + 1 < phase_end)) return 0;
     // ---- phase L + 1: patch embedding: r_0 = xp W_pe^T + b_pe ----
+    op = &h->ops(2 * L);
+    to = &h->tops(2 * L);
     RET_IF(launch_colsum_f32(tr.dres, D, M, D, slot("x_embedder.proj.bias").grad, tr.red_ws, s));
-    RET_IF(launch_to_tiled_f16(tr.dres, M, D, tr.g_d, h->err_flag, s));
+    RET_IF(to->to_tiled(tr.dres, M, D, tr.g_d, h->err_flag, s));
     {
         Slot& wpe = slot("x_embedder.proj.weight");
         GTAV_REQUIRE(wpe.C == h->Kpe, "train_backward: a patch embedding with padded K (%d of %d) is not implemented", wpe.C, h->Kpe);
@@ -483,8 +522,8 @@ int gtav_dit_adamw_step(gtav_dit* h, float lr, float beta1, float beta2, float e
     // overflow (non-finite norm, or a saturated fp16 gradient / activation recorded in the error word) skips the step on the device; the
     // Adam step count and its bias corrections live in ctl[4..6] and advance only with applied steps
     RET_IF(launch_clip_coef(tr.ctl, tr.sumsq_part, sumsq_parts(tr.grad_count), 1.0f / (tr.loss_scale * tr.grad_div), max_grad_norm, beta1, beta2, h->err_flag, s));
-    // one launch: AdamW on every parameter + the fp16 W / W^T operands of the GEMM weights rewritten from the updated masters
-    RET_IF(launch_adamw_multi(tr.adam_params, tr.adam_items, tr.adam_n_items, tr.ctl, lr, beta1, beta2, eps, weight_decay, s));
+    // one launch: AdamW on every parameter + the 2-byte W / W^T operands of the GEMM weights rewritten from the updated masters (in the handle's operand type)
+    RET_IF(train_ops(tr.bf16).adamw_multi(tr.adam_params, tr.adam_items, tr.adam_n_items, tr.ctl, lr, beta1, beta2, eps, weight_decay, s));
     RET_IF(launch_add_f32(h->b_t2, h->b_ext, h->b_t2a, h->D, s));   // fused bias of c when actions are given (gtav_dit_finalize)
     h->prepared.valid = false;
     h->kvrec.valid = false;

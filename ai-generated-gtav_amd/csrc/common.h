@@ -36,6 +36,16 @@ __device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c, int, int, int
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 #endif
 }
+// The K = 16 form, A (16 x 16) x B (16 x 16) + C: the training backward's spatial attention feeds P / dS straight from an accumulator, whose layout is
+// already the A operand of the transposed tile (train.hip attn_spatial_bwd_mfma_kernel).  v_mfma_f32_16x16x16_f16 / v_mfma_f32_16x16x16_bf16 (same rate).
+typedef short i16x4_ __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ f32x4 mfma16k16(f16x4 a, f16x4 b, f32x4 c) {
+#ifdef GTAV_BF16_OPERANDS
+    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(i16x4_, a), __builtin_bit_cast(i16x4_, b), c, 0, 0, 0);
+#else
+    return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0);
+#endif
+}
 // c + a[0] b[0] + a[1] b[1] in fp32 (v_dot2_f32_f16 / v_dot2c_f32_bf16)
 __device__ __forceinline__ float dot2acc(f16x2 a, f16x2 b, float c, bool) {
 #ifdef GTAV_BF16_OPERANDS

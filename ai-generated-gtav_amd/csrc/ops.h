@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include "gemm.h"
+#include "struct_layout.h"
 
 namespace gtav {
 
@@ -227,5 +228,12 @@ constexpr float kAttnQScale = 0.125f * 1.4426950408889634f;   // 1 / sqrt(64) * 
 // q [B*Tq*P][D] row-major for frames t0 .. t0+Tq-1; kv cache [B][Tmax][P][2][D]; O logical like q but TILE-MAJOR.
 int launch_attn_temporal(const f16* q, const f16* kv, f16* O, int B, int P, int D, int Tq, int t0, int Tmax,
                          hipStream_t stream);
+
+// the structs that api.hip / api_train.hip pass to the bf16 twins through a reference cast: this translation unit's layout against struct_layout.h
+GTAV_LAYOUT_ASSERT(GemmParams)
+GTAV_LAYOUT_ASSERT(LnPending)
+GTAV_LAYOUT_ASSERT(GemmDwGroup)
+GTAV_LAYOUT_ASSERT(AdamParam)
+GTAV_LAYOUT_ASSERT(AdamItem)
 
 }  // namespace gtav

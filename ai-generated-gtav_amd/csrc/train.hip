@@ -478,9 +478,8 @@ __global__ void mse_bwd_patch_kernel(const float* __restrict__ vpred, const floa
 // Query rows are processed 16 at a time: their P and dS rows live in LDS, dK / dV accumulate in registers (thread = (d, key group)).
 // ------------------------------------------------------------------------------------------------------------------------
 constexpr int AB_MAXS = 160;   // S <= 160 (DiT: 144)
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float dot8(const f16x8& a, const f16x8& b, float acc) {
-    // v_dot2_f32_f16: two fp16 products accumulated in fp32 per instruction
+    // v_dot2_f32_f16 (bf16 twin: v_dot2c_f32_bf16): two 2-byte products accumulated in fp32 per instruction
     acc = dot2acc(f16x2{a[0], a[1]}, f16x2{b[0], b[1]}, acc, false);
     acc = dot2acc(f16x2{a[2], a[3]}, f16x2{b[2], b[3]}, acc, false);
     acc = dot2acc(f16x2{a[4], a[5]}, f16x2{b[4], b[5]}, acc, false);
@@ -778,7 +777,7 @@ __global__ __launch_bounds__(64 * ABM_NW) void attn_spatial_bwd_mfma_kernel(cons
 #pragma unroll
                     for (int ft = 0; ft < 4; ++ft) {
                         const f16x4 kT = lds_read_tr(sK + (16 * j + 4 * g + (c >> 2)) * LP + 16 * ft + 4 * (c & 3));   // A[row = feature 16 ft + c][k = key 4 g + e]
-                        dqa[ft] = __builtin_amdgcn_mfma_f32_16x16x16f16(kT, dsT, dqa[ft], 0, 0, 0);           // rows: features 16 ft + 4 g + r; column: query c
+                        dqa[ft] = mfma16k16(kT, dsT, dqa[ft]);           // rows: features 16 ft + 4 g + r; column: query c
                     }
                 }
             }
@@ -823,8 +822,8 @@ __global__ __launch_bounds__(64 * ABM_NW) void attn_spatial_bwd_mfma_kernel(cons
             for (int ft = 0; ft < 4; ++ft) {
                 const f16x4 goT = lds_read_tr(sdO + (16 * i + 4 * g + (c >> 2)) * LP + 16 * ft + 4 * (c & 3));   // B[k = query 4 g + e][col = feature 16 ft + c]
                 const f16x4 qT = lds_read_tr(sQ + (16 * i + 4 * g + (c >> 2)) * LP + 16 * ft + 4 * (c & 3));
-                dVa[ft] = __builtin_amdgcn_mfma_f32_16x16x16f16(ph, goT, dVa[ft], 0, 0, 0);     // rows: keys 16 j + 4 g + r; column: feature 16 ft + c
-                dKa[ft] = __builtin_amdgcn_mfma_f32_16x16x16f16(dsh, qT, dKa[ft], 0, 0, 0);
+                dVa[ft] = mfma16k16(ph, goT, dVa[ft]);     // rows: keys 16 j + 4 g + r; column: feature 16 ft + c
+                dKa[ft] = mfma16k16(dsh, qT, dKa[ft]);
             }
         }
         // dK_j (RoPE^T: the pair partner of feature 16 ft + c is the neighbouring lane c ^ 1) and dV_j -> LDS rows of K_j / V_j

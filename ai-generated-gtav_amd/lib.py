@@ -71,6 +71,7 @@ SIGNATURES = {
     "gtav_dit_autorange": [_p, C.POINTER(C.c_int32), _p],
     "gtav_dit_train_param_count": [_p, C.POINTER(C.c_int64)],
     "gtav_dit_train_enable": [_p, _p, _l],
+    "gtav_dit_train_enable_typed": [_p, _p, _l, _i],
     "gtav_dit_set_loss_scale": [_p, _f],
     "gtav_dit_set_grad_divisor": [_p, _f],
     "gtav_dit_zero_grad": [_p, _p],

@@ -144,11 +144,19 @@ class DiT(_HipModule):
     _prefix = "gtav_dit"
 
     def __init__(self, input_h=18, input_w=32, patch_size=2, in_channels=16, hidden_size=1024, depth=12, num_heads=16,
-                 mlp_ratio=4.0, external_cond_dim=25, max_frames=5, *, max_batch=1, init_weights=True, trainable=False, range_policy="report"):
+                 mlp_ratio=4.0, external_cond_dim=25, max_frames=5, *, max_batch=1, init_weights=True, trainable=False, range_policy="report",
+                 train_dtype=torch.float16):
         super().__init__()
         self._trainable = bool(trainable)    # keyword-only, not in the reference: keeps fp32 masters, gradients and AdamW state on the GPU
+        # operand type of the training step (include/gtav_amd.h gtav_dit_train_enable_typed): torch.bfloat16 is the reference's `--mixed_precision bf16`
+        # (fp32 range, no loss scaling needed), torch.float16 the default (loss-scaled)
+        if train_dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError(f"train_dtype: {train_dtype} (torch.float16 or torch.bfloat16)")
+        if train_dtype == torch.bfloat16 and not self._trainable:
+            raise ValueError("train_dtype=torch.bfloat16 needs trainable=True (an inference model picks its operand type with set_operand_dtype)")
+        self._train_bf16 = self._trainable and train_dtype == torch.bfloat16
         self._grads = None
-        self._loss_scale = 65536.0
+        self._loss_scale = 1.0 if self._train_bf16 else 65536.0
         self.in_channels = in_channels
         self.out_channels = in_channels
         self.patch_size = patch_size
@@ -167,7 +175,7 @@ class DiT(_HipModule):
         self._schedule = None
         # operand groups (include/gtav_amd.h "operand type"): 2 l / 2 l + 1 = spatial / temporal half of block l, 2 depth = patch embedding, 2 depth + 1 = final layer
         self.n_operand_groups = 2 * depth + 2
-        self._bf16_groups = set()
+        self._bf16_groups = set(range(self.n_operand_groups)) if self._train_bf16 else set()
         self.range_policy = range_policy
         if range_policy not in ("report", "auto"):
             raise ValueError("range_policy must be 'report' (check() raises when an fp16 activation saturated) or 'auto' (check() moves the saturated "
@@ -253,7 +261,10 @@ class DiT(_HipModule):
                     _lib.check(L.gtav_dit_train_param_count(self._handle, C.byref(n)))
                     # one contiguous fp32 gradient arena owned by torch: a single all-reduce covers the whole model (train.py)
                     self._grads = torch.zeros(n.value, device=self.device, dtype=torch.float32)
-                    _lib.check(L.gtav_dit_train_enable(self._handle, self._grads.data_ptr(), n.value))
+                    if self._train_bf16:
+                        _lib.check(L.gtav_dit_train_enable_typed(self._handle, self._grads.data_ptr(), n.value, 1))
+                    else:
+                        _lib.check(L.gtav_dit_train_enable(self._handle, self._grads.data_ptr(), n.value))
                     _lib.check(L.gtav_dit_set_loss_scale(self._handle, self._loss_scale))
                     if self.grad_divisor != 1.0:
                         _lib.check(L.gtav_dit_set_grad_divisor(self._handle, self.grad_divisor))
@@ -345,6 +356,11 @@ class DiT(_HipModule):
     @property
     def loss_scale(self) -> float:
         return self._loss_scale
+
+    @property
+    def train_dtype(self):
+        """Operand type of the training step: torch.bfloat16 (train_dtype=torch.bfloat16) or torch.float16."""
+        return torch.bfloat16 if self._train_bf16 else torch.float16
 
     @loss_scale.setter
     def loss_scale(self, v: float):
@@ -532,10 +548,13 @@ class DiT(_HipModule):
     def set_operand_dtype(self, dtype, groups=None):
         """torch.float16 (default: 6-9e-4 relative L2 per forward against the fp32 reference, range +-65504) or torch.bfloat16 (the reference's own autocast type:
         fp32 range, ~8e-3) for the 2-byte GEMM / attention operands of `groups` (None = every layer group; group numbering: n_operand_groups).  The weights of
-        the changed groups are converted again from the fp32 host copies at the next call."""
+        the changed groups are converted again from the fp32 host copies at the next call.  A trainable model keeps the type of its train_dtype: bf16 is
+        a no-op on a bf16-trainable model and fp16 raises there; an fp16-trainable model refuses bf16."""
         if dtype not in (torch.float16, torch.bfloat16):
             raise ValueError(f"set_operand_dtype: {dtype} (torch.float16 or torch.bfloat16)")
-        if self._trainable and dtype == torch.bfloat16:
+        if self._train_bf16 and dtype == torch.float16:
+            raise _lib.GtavError("set_operand_dtype: a bf16-trainable DiT (train_dtype=torch.bfloat16) keeps bf16 operands in every layer group")
+        if self._trainable and not self._train_bf16 and dtype == torch.bfloat16:
             raise _lib.GtavError("set_operand_dtype: a trainable DiT keeps fp16 operands (its backward pass and loss scaling are fp16)")
         gs = set(range(self.n_operand_groups)) if groups is None else {int(g) for g in groups}
         if any(g < 0 or g >= self.n_operand_groups for g in gs):

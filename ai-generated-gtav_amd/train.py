@@ -349,16 +349,21 @@ def save_model(dit, path: str):
     _w.save_state_dict_file(dit.state_dict(), path)
 
 
+def _operand_dtype_name(dit) -> str:
+    """step.json's "operand_dtype": the training step's operand type ("bf16" for DiT(train_dtype=torch.bfloat16), else "fp16")."""
+    return "bf16" if getattr(dit, "train_dtype", torch.float16) == torch.bfloat16 else "fp16"
+
+
 def save_state(dit, ckpt_dir: str, global_step: int, epoch: int, extra: Optional[dict] = None):
     """train_dit.py:765-800 `save_checkpoint`: <dir>/model.safetensors (fp32 masters), <dir>/optimizer.safetensors (AdamW moments + step
-    counters), <dir>/step.json {"step", "epoch", "loss_scale", ...}.  Rank 0 writes; the caller barriers around it like the reference."""
+    counters), <dir>/step.json {"step", "epoch", "loss_scale", "operand_dtype", ...}.  Rank 0 writes; the caller barriers around it like the reference."""
     import json
     import os
     from safetensors.torch import save_file
     os.makedirs(ckpt_dir, exist_ok=True)
     save_model(dit, os.path.join(ckpt_dir, "model.safetensors"))
     save_file({k: v.contiguous() for k, v in dit.opt_state_dict().items()}, os.path.join(ckpt_dir, "optimizer.safetensors"))
-    state = {"step": int(global_step), "epoch": int(epoch), "loss_scale": float(dit.loss_scale)}
+    state = {"step": int(global_step), "epoch": int(epoch), "loss_scale": float(dit.loss_scale), "operand_dtype": _operand_dtype_name(dit)}
     state.update(extra or {})
     with open(os.path.join(ckpt_dir, "step.json"), "w") as f:
         json.dump(state, f)
@@ -376,7 +381,9 @@ def load_state(dit, ckpt_dir: str, steps_per_epoch: Optional[int] = None, gradie
     dit.load_opt_state_dict(load_file(os.path.join(ckpt_dir, "optimizer.safetensors")))
     with open(os.path.join(ckpt_dir, "step.json")) as f:
         state = json.load(f)
-    if "loss_scale" in state:
+    # the loss scale belongs to the operand type it was found for: a bf16 run's scale (1 by default) would let an fp16 backward underflow, so it is restored
+    # only into a handle of the same type (a checkpoint without "operand_dtype" is fp16).  The masters and moments are fp32 and load either way.
+    if "loss_scale" in state and state.get("operand_dtype", "fp16") == _operand_dtype_name(dit):
         dit.loss_scale = float(state["loss_scale"])
     if steps_per_epoch:
         state["skip_iter"] = (state["step"] % int(steps_per_epoch)) * int(gradient_accumulation_steps)

@@ -170,9 +170,17 @@ int gtav_timer_calibrate(int32_t spin_us, int32_t reps, double* event_us_mean, d
  * gtav_dit_train_enable must be called right after gtav_dit_create (before any gtav_dit_set_weight).  grad_arena_dev (optional):
  * caller-owned device buffer of gtav_dit_train_param_count floats that receives all gradients contiguously, parameters in the
  * lexicographic order of their state-dict names (NULL: the handle allocates it).  These calls allocate (enable) or synchronise
- * (train_stats); forward / backward / adamw_step only enqueue. */
+ * (train_stats); forward / backward / adamw_step only enqueue.
+ * gtav_dit_train_enable_typed picks the operand type of the whole training step (the reference's `--mixed_precision bf16`):
+ *   GTAV_OPERAND_F16    exactly gtav_dit_train_enable (which refuses a handle with any bf16 operand group).
+ *   GTAV_OPERAND_BF16   every operand group is set to bf16, then training is enabled (a handle whose groups are all bf16 already is accepted, one with
+ *                       mixed groups is refused).  Forward, backward and the optimizer's rewrite of the W / W^T operand images all run on bf16 operands
+ *                       (fp32 range: no activation or gradient store saturates, so the error word's saturation bit is never raised by a finite value; a
+ *                       non-finite gradient norm or store still skips the step).  The loss scale starts at 1 (the reference runs bf16 without a scaler);
+ *                       gtav_dit_set_loss_scale still applies.  gtav_dit_set_operand_dtype on such a handle accepts bf16 (nothing to do) and refuses fp16. */
 int gtav_dit_train_param_count(gtav_dit* h, int64_t* numel);
 int gtav_dit_train_enable(gtav_dit* h, float* grad_arena_dev, int64_t grad_arena_numel);
+int gtav_dit_train_enable_typed(gtav_dit* h, float* grad_arena_dev, int64_t grad_arena_numel, int32_t dtype);
 int gtav_dit_set_loss_scale(gtav_dit* h, float scale);
 /* Data-parallel training: the gradient arena holds the SUM over `divisor` ranks (all-reduce SUM) — gtav_dit_adamw_step and gtav_dit_train_stats
  * then work on arena / (loss scale x divisor), i.e. the rank average DDP would have produced, without a pass over the 2.4 GB arena.  Default 1. */
@@ -227,7 +235,7 @@ int gtav_dit_check(gtav_dit* h, void* stream);
  *   groups of a DiT handle: 2 l = spatial half of block l, 2 l + 1 = its temporal half, 2 depth = the patch embedding, 2 depth + 1 = the final layer
  *   gtav_dit_set_operand_dtype(h, group, dtype)   group -1 = every group.  The fp16 / bf16 images of the changed groups' GEMM weights become stale: send those weights
  *       again with gtav_dit_set_weight (any weight may be re-sent) and call gtav_dit_finalize.  Drops the captured graphs and the cached context.  Training handles
- *       keep fp16 operands.
+ *       keep the operand type they were enabled with (gtav_dit_train_enable: fp16; gtav_dit_train_enable_typed: fp16 or bf16 for every group).
  *   gtav_dit_autorange(h, &n, stream)   gtav_dit_check that RECOVERS: every fp16 group whose stores saturated since the last check is switched to bf16
  *       (*n_switched of them; weights to be re-sent as above, results since the last check to be recomputed); other errors are reported like gtav_dit_check.
  * The VAE handle has one type for all its layers. */

@@ -1,6 +1,8 @@
 """Times the DiT optimisation step (forward + loss, backward, AdamW) at batch 16 on latents through the EXPERIMENTS library, so that the GTAV_* overrides apply
 (e.g. GTAV_DW_TN=0: transposed operand copies in front of the grouped weight-gradient launch; GTAV_DW_GROUPED=0).  One configuration per process: run it
-twice in one gpurun call for an A/B on one box.   Usage (GPU box): GTAV_DW_TN=0 python tools/train_step_time.py [--steps 8] [--batch 16]"""
+twice in one job for an A/B on one box.   Usage (GPU box): GTAV_DW_TN=0 python tools/train_step_time.py [--steps 8] [--batch 16]
+--dtype fp16 | bf16: the operand type of the training step (DiT(train_dtype=...)) on the PRODUCT library instead (no GTAV_* overrides there): the fp16 / bf16
+A/B of profiles/round7/train_step_bf16_ab.txt."""
 import argparse
 import json
 import os
@@ -17,14 +19,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--dtype", choices=("fp16", "bf16"), default=None, help="operand type of the training step, on the product library")
     a = ap.parse_args()
-    L.load_experiments()
+    if a.dtype is None:
+        L.load_experiments()
+    else:
+        L.load()
     import gtav_amd.weights as W
     from gtav_amd.model.dit import DiT_models
     from gtav_amd.train import training_step
     dev = torch.device("cuda", 0)
     B = a.batch
-    dit = DiT_models["DiT-S/2"](init_weights=False, max_batch=B, trainable=True)
+    train_dtype = torch.bfloat16 if a.dtype == "bf16" else torch.float16
+    dit = DiT_models["DiT-S/2"](init_weights=False, max_batch=B, trainable=True, train_dtype=train_dtype)
     dit.load_state_dict(W.synth_state_dict(W.dit_param_shapes(depth=16), seed=0))
     g = torch.Generator().manual_seed(7)
     lat = (torch.randn(B, 5, 16, 18, 32, generator=g) * 0.5).to(dev)
@@ -47,7 +54,7 @@ def main():
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / a.steps * 1e3
     applied, skipped, gnorm = dit.train_stats()
-    print(json.dumps({"batch": B, "ms_per_step": round(ms, 3), "loss": float(loss), "grad_norm": gnorm, "skipped": skipped,
+    print(json.dumps({"batch": B, "dtype": a.dtype or "fp16 (experiments library)", "ms_per_step": round(ms, 3), "loss": float(loss), "grad_norm": gnorm, "skipped": skipped,
                       "env": {k: v for k, v in os.environ.items() if k.startswith("GTAV_")}}))
 
 
