@@ -244,6 +244,10 @@ int gtav_op_attn_temporal(const void* q, const void* kv, void* o, int32_t B, int
                           int32_t Tmax, void* stream) {
     return launch_attn_temporal((const f16*)q, (const f16*)kv, (f16*)o, B, P, D, Tq, t0, Tmax, (hipStream_t)stream);
 }
+int gtav_op_attn_temporal_bf16(const void* q, const void* kv, void* o, int32_t B, int32_t P, int32_t D, int32_t Tq, int32_t t0,
+                               int32_t Tmax, void* stream) {
+    return gtav_bf16::launch_attn_temporal((const __bf16*)q, (const __bf16*)kv, (__bf16*)o, B, P, D, Tq, t0, Tmax, (hipStream_t)stream);
+}
 int gtav_op_qkv_head_major(const void* w, void* w_hm, int32_t D, void* stream) {
     return launch_qkv_head_major((const f16*)w, (f16*)w_hm, D, (hipStream_t)stream);
 }

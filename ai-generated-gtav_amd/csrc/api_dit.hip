@@ -287,7 +287,7 @@ int gtav_dit_create(const gtav_dit_config* c, gtav_dit** out) {
                  "only head_dim 64 is implemented (hidden %d, heads %d)", c->hidden_size, c->num_heads);
     GTAV_REQUIRE(c->input_h % c->patch_size == 0 && c->input_w % c->patch_size == 0, "input %dx%d not divisible by patch %d",
                  c->input_h, c->input_w, c->patch_size);
-    GTAV_REQUIRE(c->max_frames >= 1 && c->max_frames <= 8, "max_frames=%d must be in [1, 8]", c->max_frames);
+    GTAV_REQUIRE(c->max_frames >= 1 && c->max_frames <= 32, "max_frames=%d must be in [1, 32]", c->max_frames);
     GTAV_REQUIRE(c->max_batch >= 1 && c->depth >= 1, "bad max_batch/depth");
     RET_IF(skinny_init());
     gtav_dit* h = new gtav_dit();

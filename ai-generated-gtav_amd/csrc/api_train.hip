@@ -11,6 +11,13 @@ static int g_dw_tn = GTAV_ENV_INT("GTAV_DW_TN", 1);             // experiments b
 // gtav_dit_train_enable after its operand-type checks: trainable slots, fp32 masters, AdamW state, saved-activation and backward workspace
 static int train_enable_body(gtav_dit* h, float* grad_arena_dev, int64_t grad_arena_numel);
 
+// The training step serves windows of at most 8 frames: refused by name before anything on the handle is allocated or changed.
+static int train_window_ok(const gtav_dit* h) {
+    GTAV_REQUIRE(h->maxT <= 8, "train_enable: training is implemented for windows of at most 8 frames (the backward temporal attention and the adaLN-gradient "
+                 "reduction are sized for it); this handle was created with max_frames=%d", h->maxT);
+    return 0;
+}
+
 extern "C" {
 
 // ================================================================================================
@@ -24,6 +31,7 @@ extern "C" {
 // ================================================================================================
 int gtav_dit_train_enable(gtav_dit* h, float* grad_arena_dev, int64_t grad_arena_numel) {
     GTAV_REQUIRE(h, "train_enable: null handle");
+    RET_IF(train_window_ok(h));
     GTAV_REQUIRE(!h->tr.on, "train_enable: already enabled");
     GTAV_REQUIRE(!h->any_bf16, "train_enable: the training step runs on fp16 operands (gtav_dit_set_operand_dtype(h, -1, GTAV_OPERAND_F16) first)");
     return train_enable_body(h, grad_arena_dev, grad_arena_numel);
@@ -33,6 +41,7 @@ int gtav_dit_train_enable_typed(gtav_dit* h, float* grad_arena_dev, int64_t grad
     GTAV_REQUIRE(h, "train_enable_typed: null handle");
     GTAV_REQUIRE(dtype == GTAV_OPERAND_F16 || dtype == GTAV_OPERAND_BF16, "train_enable_typed: dtype %d (0 = fp16, 1 = bf16)", dtype);
     if (dtype == GTAV_OPERAND_F16) return gtav_dit_train_enable(h, grad_arena_dev, grad_arena_numel);
+    RET_IF(train_window_ok(h));   // before the type switch below changes the handle
     GTAV_REQUIRE(!h->tr.on, "train_enable: already enabled");
     int nb = 0;
     for (unsigned char b : h->grp_bf16) nb += b != 0;

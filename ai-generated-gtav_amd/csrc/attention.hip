@@ -452,6 +452,110 @@ __global__ __launch_bounds__(256) void attn_temporal_kernel(const f16* __restric
     }
 }
 
+// Windows of 9 .. 32 visible frames (t0 + Tq > 8).  The register-resident kernel above cannot be instantiated there (3 x 32 x 4 VGPRs of
+// K / V / Q per lane), so this one keeps the QUERIES in registers and streams the cache past them: same thread map (8 features per lane,
+// 8 lanes per head, D/8 lanes per column, 16-byte loads, whole 2 D-half cache rows per column), grid.y = groups of QG query frames.
+// A block reads frames 0 .. t0 + (its last query) once, FB frames per round trip with the next FB already in flight, and folds every
+// frame into the running softmax (m, den, acc[8]) of each query that may see it; whole frames beyond a query's causal limit are skipped
+// by wave-uniform branches, frames >= t0 + Tq are never loaded.
+// The arithmetic of one query is a fixed sequence over keys 0 .. t0 + tl that depends on nothing else (not on QG, FB, the group it
+// falls in or the other queries of the block): the window launch (Tq = T) and the context-cached launch (Tq = 1, QG = 1) give the same
+// bits.  Rescaling on a new maximum is a per-lane condition (a lane whose maximum stands multiplies by nothing), so the skipped
+// branch changes no value either.
+template <int QG, int FB>
+__global__ __launch_bounds__(256) void attn_temporal_stream_kernel(const f16* __restrict__ q, const f16* __restrict__ kv,
+                                                                   f16* __restrict__ O, int ncol, int P, int D, int Tq, int t0, int Tmax) {
+#pragma clang fp contract(off)   // both instantiations must round alike: only the explicit fma below is fused
+    const int tpc = D >> 3;                                     // threads per column
+    const int ci = threadIdx.x / tpc, lc = threadIdx.x - ci * tpc;
+    const int bp = blockIdx.x * ((int)blockDim.x / tpc) + ci;
+    if (bp >= ncol) return;                                     // whole 8-lane head groups leave together (tpc % 8 == 0); no barrier below
+    const int b = bp / P, p = bp - b * P;
+    const int c = lc * 8;
+    const int tl0 = blockIdx.y * QG;
+    const int nq = Tq - tl0 < QG ? Tq - tl0 : QG;               // queries of this block: frames t0 + tl0 .. t0 + tl0 + nq - 1
+    const int Tk = t0 + tl0 + nq;                               // frames 0 .. Tk - 1 are visible to its last query
+    union H8 { f16x8 v; f16x2 h[4]; };
+    H8 qv[QG];
+    float m[QG], den[QG], acc[QG][8];
+#pragma unroll
+    for (int j = 0; j < QG; ++j) {
+        qv[j].v = f16x8{};
+        if (j < nq) qv[j].v = *(const f16x8*)(q + (((size_t)b * Tq + tl0 + j) * P + p) * D + c);
+        m[j] = -INFINITY; den[j] = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[j][e] = 0.f;
+    }
+    const size_t fstride = (size_t)P * 2 * D;                   // halves between two frames of one column
+    const f16* const base = kv + ((size_t)b * Tmax * P + p) * 2 * D + c;
+    H8 kc[FB], vc[FB];
+#pragma unroll
+    for (int i = 0; i < FB; ++i) {
+        kc[i].v = f16x8{}; vc[i].v = f16x8{};
+        if (i < Tk) {
+            kc[i].v = *(const f16x8*)(base + i * fstride);
+            vc[i].v = *(const f16x8*)(base + i * fstride + D);
+        }
+    }
+    for (int tb = 0; tb < Tk; tb += FB) {
+        H8 kn[FB], vn[FB];
+#pragma unroll
+        for (int i = 0; i < FB; ++i) {
+            kn[i].v = f16x8{}; vn[i].v = f16x8{};
+            if (tb + FB + i < Tk) {
+                kn[i].v = *(const f16x8*)(base + (size_t)(tb + FB + i) * fstride);
+                vn[i].v = *(const f16x8*)(base + (size_t)(tb + FB + i) * fstride + D);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < FB; ++i) {
+            const int t = tb + i;
+            if (t < Tk) {
+                float vf[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) vf[e] = (float)vc[i].v[e];
+#pragma unroll
+                for (int j = 0; j < QG; ++j) {
+                    if (j < nq && t <= t0 + tl0 + j) {  // causal (model/attention.py:62-64), wave-uniform
+                        float d = 0.f;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) d = dot2acc(qv[j].h[e], kc[i].h[e], d, false);
+                        const float s = group8_sum(d) * 0.125f;
+                        if (s > m[j]) {                 // new maximum (always at t = 0: m = -inf gives a factor 2^-inf = 0 on den = acc = 0)
+                            const float r = __builtin_amdgcn_exp2f((m[j] - s) * 1.4426950408889634f);
+                            den[j] *= r;
+#pragma unroll
+                            for (int e = 0; e < 8; ++e) acc[j][e] *= r;
+                            m[j] = s;
+                        }
+                        const float pr = __builtin_amdgcn_exp2f((s - m[j]) * 1.4426950408889634f);   // argument <= 0
+                        den[j] += pr;
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) acc[j][e] = __builtin_fmaf(pr, vf[e], acc[j][e]);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < FB; ++i) { kc[i] = kn[i]; vc[i] = vn[i]; }
+    }
+#pragma unroll
+    for (int j = 0; j < QG; ++j) {
+        if (j < nq) {
+            const size_t row = ((size_t)b * Tq + tl0 + j) * P + p;
+            const float inv = 1.0f / den[j];
+            f16x8 o8;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                float r = acc[j][e] * inv;
+                asm volatile("" : "+v"(r));   // the product is rounded to fp32 first in every instantiation (no v_fma_mix fold of multiply + conversion: one rounding less)
+                o8[e] = (f16)r;
+            }
+            *(f16x8*)(O + tiled_off((int)row, c, D)) = o8;
+        }
+    }
+}
+
 }  // namespace
 
 // output as paired 16-byte write-through stores (common.h store_f16x4_paired); experiments build: GTAV_ATTN_SC1=1 enables it
@@ -540,12 +644,25 @@ int launch_attn_spatial(const f16* Q, const f16* K, const f16* Vt, f16* O, int N
 int launch_attn_temporal(const f16* q, const f16* kv, f16* O, int B, int P, int D, int Tq, int t0, int Tmax,
                          hipStream_t stream) {
     GTAV_REQUIRE(D % 256 == 0 && D <= 2048, "attn_temporal: D=%d must be a multiple of 256 and <= 2048", D);
-    GTAV_REQUIRE(Tq > 0 && t0 >= 0 && t0 + Tq <= Tmax && Tmax <= 8, "attn_temporal: window t0=%d Tq=%d Tmax=%d (max 8)", t0, Tq, Tmax);
+    GTAV_REQUIRE(Tq > 0 && t0 >= 0 && t0 + Tq <= Tmax && Tmax <= 32, "attn_temporal: window t0=%d Tq=%d Tmax=%d (max 32)", t0, Tq, Tmax);
+    GTAV_REQUIRE(P > 0 && B > 0 && (long long)B * Tq * P < (1ll << 31), "attn_temporal: B=%d P=%d Tq=%d", B, P, Tq);
+    const int tpc = D / 8, cpb = tpc >= 256 ? 1 : 256 / tpc;  // threads per column, columns per block
+    // The kernel is chosen by the number of VISIBLE frames, never by the cache stride Tmax: a window of <= 8 frames runs the same
+    // kernel, and gives the same bits, whatever capacity its handle was built for.
+    const int Tvis = t0 + Tq;
+    if (Tvis > 8) {
+        if (Tq == 1) {
+            GTAV_LAUNCH((attn_temporal_stream_kernel<1, 8>), dim3(cdiv(B * P, cpb), 1), dim3(tpc * cpb), 0, stream, q, kv, O, B * P, P, D, Tq, t0, Tmax);
+        } else {
+            GTAV_LAUNCH((attn_temporal_stream_kernel<8, 4>), dim3(cdiv(B * P, cpb), cdiv(Tq, 8)), dim3(tpc * cpb), 0, stream, q, kv, O, B * P, P, D, Tq, t0, Tmax);
+        }
+        GTAV_CHECK_HIP(hipGetLastError());
+        return 0;
+    }
     static const int split_max = GTAV_ENV_INT("GTAV_ATTN_T_SPLIT_MAX", 1024);
     const int split = (Tq > 1 && B * P < split_max) ? 1 : 0;   // few columns: one block per (column group, query frame)
-    const int tpc = D / 8, cpb = tpc >= 256 ? 1 : 256 / tpc;  // threads per column, columns per block
     const dim3 grid(cdiv(B * P, cpb), split ? Tq : 1), block(tpc * cpb);
-    if (Tmax <= 5) GTAV_LAUNCH(attn_temporal_kernel<5>, grid, block, 0, stream, q, kv, O, B * P, P, D, Tq, t0, Tmax, split);
+    if (Tvis <= 5) GTAV_LAUNCH(attn_temporal_kernel<5>, grid, block, 0, stream, q, kv, O, B * P, P, D, Tq, t0, Tmax, split);
     else GTAV_LAUNCH(attn_temporal_kernel<8>, grid, block, 0, stream, q, kv, O, B * P, P, D, Tq, t0, Tmax, split);
     GTAV_CHECK_HIP(hipGetLastError());
     return 0;

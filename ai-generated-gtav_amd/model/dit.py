@@ -137,6 +137,10 @@ class _HipModule:
         self._dirty = False
 
 
+MAX_FRAMES = 32        # gtav_dit_create's range (include/gtav_amd.h gtav_dit_config.max_frames)
+TRAIN_MAX_FRAMES = 8   # gtav_dit_train_enable's
+
+
 class DiT(_HipModule):
     """model/dit.py:228-376.  `max_batch` (keyword-only, not in the reference) pre-sizes the HBM workspace;
     it grows automatically when a larger batch arrives."""
@@ -161,13 +165,16 @@ class DiT(_HipModule):
         self.out_channels = in_channels
         self.patch_size = patch_size
         self.num_heads = num_heads
+        if max_frames > MAX_FRAMES:
+            raise ValueError(f"max_frames={max_frames}: the temporal attention serves windows of at most {MAX_FRAMES} frames")
         self._max_frames = max_frames
         self.input_h, self.input_w, self.hidden_size, self.depth = input_h, input_w, hidden_size, depth
         self.mlp_ratio, self.external_cond_dim = mlp_ratio, external_cond_dim
         self._cfg_kwargs = dict(input_h=input_h, input_w=input_w, patch_size=patch_size, in_channels=in_channels,
                                 hidden_size=hidden_size, depth=depth, num_heads=num_heads, mlp_ratio=mlp_ratio,
                                 external_cond_dim=external_cond_dim)
-        self._capacity_b, self._capacity_t = max_batch, max(max_frames, 1)
+        # a trainable handle is never sized beyond the window the training step implements: _ensure refuses longer ones by name
+        self._capacity_b, self._capacity_t = max_batch, min(max(max_frames, 1), TRAIN_MAX_FRAMES if self._trainable else MAX_FRAMES)
         self._capacity_rows = 0
         hd = hidden_size // num_heads
         self._spatial_freqs = _w.rope_freqs_pixel(hd // 2, 256)   # model/dit.py:259-261
@@ -190,11 +197,14 @@ class DiT(_HipModule):
 
     @max_frames.setter
     def max_frames(self, v):
+        if int(v) > MAX_FRAMES:   # before the handle is touched: the model stays as it was
+            raise ValueError(f"max_frames={int(v)}: the temporal attention serves windows of at most {MAX_FRAMES} frames")
         self._max_frames = int(v)
-        if v > self._capacity_t:
+        cap = min(int(v), TRAIN_MAX_FRAMES) if self._trainable else int(v)
+        if cap > self._capacity_t:
             if self._handle and self._trainable and self._grads is not None:
                 raise RuntimeError("a trainable DiT cannot grow its window after training was enabled: construct it with the largest max_frames")
-            self._capacity_t = int(v)
+            self._capacity_t = cap
             self._free()
 
     def _shapes(self):
@@ -229,6 +239,12 @@ class DiT(_HipModule):
 
     # ------------------------------------------------------------------------------------------
     def _ensure(self, B: int, T: int, cond_rows: int = 0):
+        # window limits first, before a handle is rebuilt or destroyed
+        if T > MAX_FRAMES:
+            raise ValueError(f"a window of {T} frames: the temporal attention serves at most {MAX_FRAMES} (max_frames <= {MAX_FRAMES})")
+        if self._trainable and T > TRAIN_MAX_FRAMES:
+            raise ValueError(f"a window of {T} frames on a trainable DiT: the training step (backward temporal attention, adaLN-gradient reduction) is "
+                             f"implemented for at most {TRAIN_MAX_FRAMES} frames; windows up to {MAX_FRAMES} need trainable=False")
         grow = (cond_rows > max(self._capacity_rows, self._capacity_b * self._capacity_t)) or T > self._capacity_t or B > self._capacity_b
         if grow and self._handle and self._trainable and self._grads is not None:
             # the fp32 masters and the AdamW state live only in the handle: refuse BEFORE anything is destroyed (the handle stays usable)

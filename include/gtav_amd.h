@@ -54,6 +54,13 @@ typedef struct gtav_dit_config {
     int32_t input_h, input_w, patch_size, in_channels, hidden_size, depth, num_heads;
     float mlp_ratio;
     int32_t external_cond_dim, max_frames;
+    /* max_frames: 1 .. 32, the longest temporal window (T of a forward, cur - start + 1 of a sampler step) the handle serves.  It sizes the
+     * temporal K/V caches, depth * max_batch * max_frames * P * 2 * hidden_size * 2 bytes (P = tokens per frame): 47 MB for DiT-S/2 at batch 1
+     * and 5 frames, 2.4 GB at batch 8 and 32 frames, and the activation arenas (max_batch * max_frames * P token rows).  The temporal attention
+     * kernel is chosen per call by the frames a call can see (t0 + Tq), never by this capacity: up to 5 and up to 8 visible frames run the
+     * register-resident kernels, 9 .. 32 the streaming kernel (csrc/attention.hip), so a window of <= 8 frames gives the same bits on any
+     * handle.  The fused temporal to_qkv + attention launch serves five-frame windows only.  Training (gtav_dit_train_enable*) is implemented
+     * for max_frames <= 8 and refuses a larger handle. */
     /* capacity of the handle's workspace */
     int32_t max_batch;      /* largest B of a forward / denoise call */
     int32_t max_cond_rows;  /* rows of the conditioning (adaLN) table; >= max_batch * max_frames */
@@ -350,6 +357,9 @@ int gtav_op_attn_spatial(const void* q_dev, const void* k_dev, const void* vt_de
                          int32_t heads, int32_t S, void* stream);
 int gtav_op_attn_temporal(const void* q_dev, const void* kv_dev, void* o_dev, int32_t B, int32_t P, int32_t D,
                           int32_t Tq, int32_t t0, int32_t Tmax, void* stream);
+/* The same launch on bf16 operands (q, kv, o hold bf16; the twin the bf16 operand groups of a handle run). */
+int gtav_op_attn_temporal_bf16(const void* q_dev, const void* kv_dev, void* o_dev, int32_t B, int32_t P, int32_t D,
+                               int32_t Tq, int32_t t0, int32_t Tmax, void* stream);
 /* Temporal half of a full-window step as ONE kernel (gtav_dit_set_fused_temporal): x rows in (b, 16 positions, frame, position in
  * group) order, w = the to_qkv weight in head-major row order (gtav_op_qkv_head_major of the tile-major [3 D][D] weight); writes K / V
  * of every token to the temporal cache kv [B][Tmax][P][2 D] and the attention output o (f16 tile-major, rows in (b, frame, position)

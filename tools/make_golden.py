@@ -247,6 +247,54 @@ def g10_frame_loop(rd, ref_schedule):
     save("g10_frame_loop.safetensors", out)
 
 
+@torch.no_grad()
+def g12_long_window(rd, ref_denoise_step, ref_schedule):
+    """G12 / G13: temporal windows of 9 .. 32 frames on the reference's own DiT (small width, `max_frames` up to 32), recorded under
+    MKL_CBWR=COMPATIBLE.  g12_long_window: the temporal RoPE angles of 32 positions, a forward at B = 1, T = 32 with actions and one at
+    B = 2, T = 12 without.  g13_long_window_steps: `denoise_step` on a 20-frame buffer with start_frame = 4 (a 16-frame window) at noise
+    index 4 and 0 of 10 steps (v_pred, the last frame of x_pred), and a rollout in the G5 pattern with max_frames = 9: one prompt frame,
+    11 frames in all, 3 noise steps (4 forwards per frame, 40 forwards, windows of 2 .. 9 frames and two slides)."""
+    from model.rotary_embedding_torch import RotaryEmbedding
+    tp = RotaryEmbedding(dim=64)
+    g12 = {"rope_temporal_angles_T32": tp.forward(torch.arange(32).float(), tp.freqs, seq_len=32).clone()}
+    sd = W.synth_state_dict(W.dit_param_shapes(**SMALL_DIT), seed=21)
+    m = load_into(rd.DiT(**SMALL_DIT, max_frames=32), sd)
+    g = torch.Generator().manual_seed(31)
+    x = torch.randn(1, 32, 16, 8, 16, generator=g)
+    t = torch.randint(0, 1000, (1, 32), generator=g)
+    a = one_hot_actions(1, 32, g)
+    g12.update({"x_b1t32": x, "t_b1t32": t, "a_b1t32": a, "out_b1t32": m(x, t, a)})
+    x = torch.randn(2, 12, 16, 8, 16, generator=g)
+    t = torch.randint(0, 1000, (2, 12), generator=g)
+    g12.update({"x_b2t12": x, "t_b2t12": t, "out_b2t12": m(x, t, None)})
+    save("g12_long_window.safetensors", g12)
+
+    ac = torch.cumprod(1.0 - ref_schedule(1000).float(), dim=0)[:, None, None, None]
+    x4 = torch.randn(1, 20, 16, 8, 16, generator=g)
+    a4 = one_hot_actions(1, 20, g)
+    nr = torch.linspace(0, 999, 11)
+    g13 = {"x": x4, "actions": a4}
+    for idx in (4, 0):
+        xp, vp = ref_denoise_step(m, x4, a4, idx, 15, nr, ac, start_frame=4, dtype=torch.bfloat16)
+        g13[f"x_pred_last_{idx}"], g13[f"v_pred_{idx}"] = xp[:, -1:].clone(), vp
+    m.max_frames = 9
+    B, total, steps = 2, 11, 3
+    x0 = torch.randn(B, 1, 16, 8, 16, generator=g) * 0.5
+    noise = torch.randn(B, total - 1, 16, 8, 16, generator=g)
+    a5 = one_hot_actions(B, total, g)
+    xx = x0.clone()
+    nr5 = torch.linspace(0, 999, steps + 1)
+    for i in range(1, total):
+        chunk = torch.clamp(noise[:, i - 1: i], -20, 20)
+        xx = torch.cat([xx, chunk], dim=1)
+        start = max(0, i + 1 - m.max_frames)
+        for noise_idx in reversed(range(0, steps + 1)):
+            xp, _ = ref_denoise_step(m, xx, a5, noise_idx, 15, nr5, ac, start_frame=start, dtype=torch.bfloat16)
+            xx[:, -1:] = xp[:, -1:]
+    g13.update({"roll_x_prompt": x0, "roll_noise": noise, "roll_actions": a5, "roll_latents": xx})
+    save("g13_long_window_steps.safetensors", g13)
+
+
 def resize_probe_image(H, W):
     """A deterministic uint8 image (H, W, 3) from integer arithmetic only (no RNG: the tests rebuild it bit for bit): smooth ramps + a fine texture."""
     y = torch.arange(H).view(H, 1, 1)
@@ -281,6 +329,8 @@ def main():
     if "--only-g11" in sys.argv:
         return g11_resize()
     rd, rv, ref_denoise_step, ref_schedule = ref_shim.import_reference()
+    if "--only-g12" in sys.argv:
+        return g12_long_window(rd, ref_denoise_step, ref_schedule)
     g11_resize()
     if "--only-g9-g10" in sys.argv:
         g10_frame_loop(rd, ref_schedule)
@@ -443,6 +493,7 @@ def main():
     g7_harness(rd, rv, ref_denoise_step, ref_schedule, full_dit=True)
     g1_per_op(rd, rv)
     g8_training(rd)
+    g12_long_window(rd, ref_denoise_step, ref_schedule)
     save("g3_full_vae.safetensors", {"mean": post.mean, "logvar": post.logvar, "z": z, "decoded_stride4": dec[:, :, ::4, ::4].clone(),
                                      "decoded_row100": dec[:, :, 100].clone()})
 

@@ -1,7 +1,7 @@
 """Per-kernel-class in-situ times of ONE sampler step (window or context-cached) at a given batch, plus the captured-graph time of the same step.
 Product library.  The classes come from the handle's profiler (HIP events attached to each dispatch, gtav_dit_profile); with the profiler on the
 step runs eagerly, so the graph time is measured separately, profiler off.
-Usage (GPU box): python tools/step_profile.py [--batch 8] [--cached] [--actions] [--steps 30]"""
+Usage (GPU box): python tools/step_profile.py [--batch 8] [--cached] [--actions] [--steps 30] [--window 5] [--bf16]"""
 import argparse
 import json
 import os
@@ -20,6 +20,8 @@ def main():
     ap.add_argument("--cached", action="store_true")
     ap.add_argument("--actions", action="store_true")
     ap.add_argument("--steps", type=int, default=30, help="noise steps per generated frame in the measurement")
+    ap.add_argument("--window", type=int, default=5, help="frames per window (up to 32; above 8 the temporal attention is the streaming kernel)")
+    ap.add_argument("--bf16", action="store_true", help="every operand group on bf16 operands")
     ap.add_argument("--exp", action="store_true", help="experiments build (GTAV_* environment overrides)")
     ap.add_argument("--json", default="")
     a = ap.parse_args()
@@ -34,9 +36,13 @@ def main():
     B = a.batch
     dit = DiT_models["DiT-S/2"](init_weights=False, max_batch=B)
     dit.load_state_dict(W.synth_state_dict(W.dit_param_shapes(depth=16), seed=0))
-    dit.reserve(B, 5, a.steps)
+    T = a.window
+    dit.max_frames = T
+    dit.reserve(B, T, a.steps)
+    if a.bf16:
+        dit.set_operand_dtype(torch.bfloat16)
     g = torch.Generator().manual_seed(3)
-    F = 6
+    F = T + 1
     x = (torch.randn(B, F, 16, 18, 32, generator=g) * 0.5).to(dev)
     act = None
     if a.actions:
@@ -46,7 +52,7 @@ def main():
     nr = torch.linspace(0, 999, a.steps + 1)
     t_of = [int(v) for v in nr]
     order = list(reversed(range(a.steps + 1)))
-    i, start = 5, 1
+    i, start = T, 1
 
     xbuf = torch.empty_like(x)          # ONE buffer: the captured graph is keyed by it
 
@@ -83,11 +89,11 @@ def main():
     torch.cuda.synchronize()
     prof = dit.profile_read()
     dit.profile(False)
-    M = B * 144 * (1 if a.cached else 5)
+    M = B * 144 * (1 if a.cached else T)
     D, HM = 1024, 4096
     gflop = {"gemm_qkv": 2.0 * M * 3 * D * D, "gemm_out": 2.0 * M * D * D, "gemm_fc1": 2.0 * M * HM * D, "gemm_fc2": 2.0 * M * HM * D}
     ev_ms, ev_n = prof.pop("empty_event_pair")
-    out = {"batch": B, "algo": "cached" if a.cached else "window", "tokens_per_step": M, "graph_ms_per_step": round(graph_ms, 4), "classes": {}}
+    out = {"batch": B, "window": T, "operands": "bf16" if a.bf16 else "fp16", "algo": "cached" if a.cached else "window", "tokens_per_step": M, "graph_ms_per_step": round(graph_ms, 4), "classes": {}}
     tot = 0.0
     for k, (ms, cnt) in prof.items():
         e = {"ms_per_step": round(ms / nprof, 4), "launches_per_step": cnt // nprof}
