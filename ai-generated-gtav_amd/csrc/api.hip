@@ -275,6 +275,11 @@ int gtav_op_attn_spatial_bwd(const void* q, const void* k, const void* vt, const
     return launch_attn_spatial_bwd((const f16*)q, (const f16*)k, (const f16*)vt, (const f16*)d_o, NB, heads, S, heads * 64, rope_cs, (f16*)dqkv, nullptr,
                                    (hipStream_t)stream);
 }
+int gtav_op_attn_spatial_bwd_bf16(const void* q, const void* k, const void* vt, const void* d_o, int32_t NB, int32_t heads, int32_t S,
+                                  const float* rope_cs, void* dqkv, void* stream) {
+    return gtav_bf16::launch_attn_spatial_bwd((const __bf16*)q, (const __bf16*)k, (const __bf16*)vt, (const __bf16*)d_o, NB, heads, S, heads * 64, rope_cs,
+                                              (__bf16*)dqkv, nullptr, (hipStream_t)stream);
+}
 int gtav_op_gemm_tn(const void* x, const void* w, int32_t M, int32_t N, int32_t K, float* out, int32_t ldo, void* stream) {
     GemmParams q;
     memset(&q, 0, sizeof(q));

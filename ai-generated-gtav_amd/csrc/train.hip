@@ -477,7 +477,7 @@ __global__ void mse_bwd_patch_kernel(const float* __restrict__ vpred, const floa
 // interleaved-pair RoPE (the transpose of a rotation is the rotation by the negative angle).
 // Query rows are processed 16 at a time: their P and dS rows live in LDS, dK / dV accumulate in registers (thread = (d, key group)).
 // ------------------------------------------------------------------------------------------------------------------------
-constexpr int AB_MAXS = 160;   // S <= 160 (DiT: 144)
+constexpr int AB_MAXS = 160;   // bound of the two LDS-resident kernels (DiT: 144); longer frames and S % 16 == 8 run attn_spatial_bwd_stream_kernel
 __device__ __forceinline__ float dot8(const f16x8& a, const f16x8& b, float acc) {
     // v_dot2_f32_f16 (bf16 twin: v_dot2c_f32_bf16): two 2-byte products accumulated in fp32 per instruction
     acc = dot2acc(f16x2{a[0], a[1]}, f16x2{b[0], b[1]}, acc, false);
@@ -856,6 +856,300 @@ __global__ __launch_bounds__(64 * ABM_NW) void attn_spatial_bwd_mfma_kernel(cons
         *(uint4*)(dqkv + tiled_off((int)m, head * 64 + 8 * ch, 3 * D)) = o.u;
         *(uint4*)(dqkv + tiled_off((int)m, D + head * 64 + 8 * ch, 3 * D)) = *(const uint4*)(sK + srow * LP + 8 * ch);
         *(uint4*)(dqkv + tiled_off((int)m, 2 * D + head * 64 + 8 * ch, 3 * D)) = *(const uint4*)(sV + srow * LP + 8 * ch);
+    }
+    sat_report(amax, err_flag);
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// The streaming form for frames of more than 160 tokens, and for any S % 16 == 8: the same mathematics, operand layouts and 2-byte roundings
+// (P, dS) as the kernel above, but neither side of the S x S problem is resident.  One block of eight waves per (frame, head); the only per-S
+// state in LDS is the two row statistics (8 bytes per query), everything else is a 64-row chunk of the streamed side:
+//   query pass, per group of 8 query tiles (wave w: tile 8 qg + w, its Q_i / dO_i fragments in registers, read straight from global memory):
+//     sweep 1 streams K / V^T in 64-key chunks (V^T is transposed into [key][feature] rows on the way into LDS) and keeps a PER-LANE running
+//       maximum, sum and sum P dP over the lane's own key columns (c, c + 16, ...): no cross-lane traffic per chunk; the 16 lanes of a row are
+//       combined once at the end of the sweep -> lse2[q], Dq[q] (LDS, for the key pass, and registers);
+//     sweep 2 streams the same chunks again: S_ij, dP_ij, dS_ij = P (dP - Dq) / 8, dQ_i^T += K_j^T dS_ij^T exactly as above; dQ_i leaves from the
+//       accumulators (RoPE^T pairs are two registers of one lane) as 8-byte stores;
+//   key pass, per group of 8 key tiles (wave w: tile 8 kg + w, K_j / V_j fragments and dK_j / dV_j in registers): streams Q / dO in 64-query
+//     chunks, the loop body of the kernel above; dK_j / dV_j go through a private 16-row LDS image into 16-byte stores.
+// Every output element is accumulated by ONE wave in a fixed order (ascending key chunks for dQ, ascending query chunks for dK / dV): no atomics,
+// no cross-wave reduction, so launches are bitwise reproducible.  The price is 7 tile products per (i, j) where the resident kernel has 5 (plus the
+// 2 of the statistics sweep in both).  Staging is double-buffered through registers: the global loads of chunk n + 1 are in flight while chunk n is
+// computed.  S may be any positive multiple of 8: rows at or beyond S are never read (zero-filled on the way into LDS / registers), padded keys
+// are masked out of P, padded queries are not stored.  LDS: 40 960 + 8 round_up(S, 16) bytes (S <= 15 360).
+// ------------------------------------------------------------------------------------------------------------------------
+constexpr int ABS_LP = 72, ABS_NW = 8, ABS_CH = 64;
+static inline size_t attn_bwd_stream_lds(int S) {
+    return (size_t)2 * ABS_CH * ABS_LP * 2 + (size_t)ABS_NW * 16 * ABS_LP * 2 + (size_t)ABS_NW * 256 * 2 + (size_t)2 * round_up(S, 16) * 4;
+}
+__global__ __launch_bounds__(64 * ABS_NW) void attn_spatial_bwd_stream_kernel(const f16* __restrict__ Q, const f16* __restrict__ K, const f16* __restrict__ Vt,
+                                                                              const f16* __restrict__ dO, int heads, int S, int D,
+                                                                              const float* __restrict__ rope_cs, f16* __restrict__ dqkv, int* err_flag) {
+    constexpr int LP = ABS_LP, NW = ABS_NW, CH = ABS_CH, NT = 64 * ABS_NW, TPC = CH / 16;
+    static_assert(NT == CH * 8, "one 16-byte piece of each staged array per thread");
+    extern __shared__ __attribute__((aligned(16))) char smraw[];
+    f16* sA = (f16*)smraw;                 // [CH][LP]: K chunk (query pass) / Q chunk (key pass)
+    f16* sB = sA + CH * LP;                // [CH][LP]: V chunk as [key][feature] / dO chunk
+    f16* sout = sB + CH * LP;              // [NW][16][LP]: dK_j, then dV_j, of the wave
+    f16* sscr = sout + NW * 16 * LP;       // [NW][16][16]: dS tile of the wave as [key][query]
+    float* slse = (float*)(sscr + NW * 256);
+    const int nt = (S + 15) >> 4, nch = (S + CH - 1) / CH, ngrp = (nt + NW - 1) / NW;
+    float* sDq = slse + nt * 16;
+    const int item = blockIdx.x, nb = item / heads, head = item % heads;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, g = lane >> 4;
+    const f16* q = Q + (size_t)item * S * 64;
+    const f16* k = K + (size_t)item * S * 64;
+    const f16* vt = Vt + (size_t)item * 64 * S;
+    const f16* go = dO + (size_t)nb * S * D + head * 64;
+    const float cexp = 0.125f * 1.4426950408889634f;
+    // this thread's 16-byte piece of a chunk: row-major arrays (row prow, features 8 pch ..) and V^T (feature vd, keys vs0 ..: lanes along the feature,
+    // conflict-free 2-byte LDS stores)
+    const int prow = tid >> 3, pch = tid & 7, vd = tid & 63, vs0 = (tid >> 6) << 3;
+    const uint4 z4 = uint4{0u, 0u, 0u, 0u};
+    const f16x8 z8 = __builtin_bit_cast(f16x8, z4);
+    uint4 pa = z4, pb = z4;
+    auto load_kv = [&](int r0) {
+        pa = r0 + prow < S ? *(const uint4*)(k + (size_t)(r0 + prow) * 64 + 8 * pch) : z4;
+        pb = r0 + vs0 < S ? *(const uint4*)(vt + (size_t)vd * S + r0 + vs0) : z4;
+    };
+    auto store_kv = [&]() {
+        *(uint4*)(sA + prow * LP + 8 * pch) = pa;
+        const f16x8 v8 = __builtin_bit_cast(f16x8, pb);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) sB[(vs0 + e) * LP + vd] = v8[e];
+    };
+    auto load_qg = [&](int r0) {
+        pa = r0 + prow < S ? *(const uint4*)(q + (size_t)(r0 + prow) * 64 + 8 * pch) : z4;
+        pb = r0 + prow < S ? *(const uint4*)(go + (size_t)(r0 + prow) * D + 8 * pch) : z4;
+    };
+    auto store_qg = [&]() {
+        *(uint4*)(sA + prow * LP + 8 * pch) = pa;
+        *(uint4*)(sB + prow * LP + 8 * pch) = pb;
+    };
+    float amax = 0.f;
+    // ---- query pass ----
+    for (int qg = 0; qg < ngrp; ++qg) {
+        const int i = qg * NW + w, qrow = 16 * i + c;
+        const bool act = i < nt, qok = qrow < S;
+        f16x8 qa[2], ga[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            qa[h] = qok ? *(const f16x8*)(q + (size_t)qrow * 64 + 32 * h + 8 * g) : z8;
+            ga[h] = qok ? *(const f16x8*)(go + (size_t)qrow * D + 32 * h + 8 * g) : z8;
+        }
+        // sweep 1: row statistics, per lane over its own key columns
+        f32x4 mx = f32x4{-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f}, sum = f32x4{0.f, 0.f, 0.f, 0.f}, pd = sum;
+        load_kv(0);
+        for (int ci = 0; ci < nch; ++ci) {
+            __syncthreads();
+            store_kv();
+            __syncthreads();
+            if (ci + 1 < nch) load_kv((ci + 1) * CH);
+            if (!act) continue;
+            f32x4 sa[TPC], da[TPC];
+            f32x4 cm = mx;
+#pragma unroll
+            for (int jt = 0; jt < TPC; ++jt) {
+                sa[jt] = da[jt] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (CH * ci + 16 * jt < S) {
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const f16x8 kb = *(const f16x8*)(sA + (16 * jt + c) * LP + 32 * h + 8 * g);
+                        const f16x8 vb = *(const f16x8*)(sB + (16 * jt + c) * LP + 32 * h + 8 * g);
+                        sa[jt] = mfma16(qa[h], kb, sa[jt], 0, 0, 0);
+                        da[jt] = mfma16(ga[h], vb, da[jt], 0, 0, 0);
+                    }
+                    if (CH * ci + 16 * jt + c < S)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) cm[r] = fmaxf(cm[r], sa[jt][r]);
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float sc = __builtin_amdgcn_exp2f((mx[r] - cm[r]) * cexp);
+                sum[r] *= sc;
+                pd[r] *= sc;
+                mx[r] = cm[r];
+            }
+#pragma unroll
+            for (int jt = 0; jt < TPC; ++jt)
+                if (CH * ci + 16 * jt + c < S)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float pe = __builtin_amdgcn_exp2f((sa[jt][r] - mx[r]) * cexp);
+                        sum[r] += pe;
+                        pd[r] = __builtin_fmaf(pe, da[jt][r], pd[r]);
+                    }
+        }
+        f32x4 lse, dqr;
+        {
+            f32x4 rm = mx;
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) rm[r] = fmaxf(rm[r], __shfl_xor(rm[r], o, 64));
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float sc = __builtin_amdgcn_exp2f((mx[r] - rm[r]) * cexp);   // a lane without a valid key column: 2^-huge = 0
+                sum[r] *= sc;
+                pd[r] *= sc;
+            }
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    sum[r] += __shfl_xor(sum[r], o, 64);
+                    pd[r] += __shfl_xor(pd[r], o, 64);
+                }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                lse[r] = rm[r] * cexp + __builtin_amdgcn_logf(sum[r]);   // v_log_f32 = log2
+                dqr[r] = pd[r] / sum[r];
+            }
+            if (act && c == 0) {
+                *(f32x4*)(slse + 16 * i + 4 * g) = lse;
+                *(f32x4*)(sDq + 16 * i + 4 * g) = dqr;
+            }
+        }
+        // sweep 2: dQ_i^T[feature][query] = sum_j K_j^T dS_ij^T
+        f32x4 dqa[4];
+#pragma unroll
+        for (int ft = 0; ft < 4; ++ft) dqa[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
+        f16* scr0 = sscr + w * 256;
+        load_kv(0);
+        for (int ci = 0; ci < nch; ++ci) {
+            __syncthreads();
+            store_kv();
+            __syncthreads();
+            if (ci + 1 < nch) load_kv((ci + 1) * CH);
+            if (!act) continue;
+#pragma unroll
+            for (int jt = 0; jt < TPC; ++jt) {
+                if (CH * ci + 16 * jt < S) {
+                    f32x4 sa = f32x4{0.f, 0.f, 0.f, 0.f}, da = sa;
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const f16x8 kb = *(const f16x8*)(sA + (16 * jt + c) * LP + 32 * h + 8 * g);
+                        const f16x8 vb = *(const f16x8*)(sB + (16 * jt + c) * LP + 32 * h + 8 * g);
+                        sa = mfma16(qa[h], kb, sa, 0, 0, 0);
+                        da = mfma16(ga[h], vb, da, 0, 0, 0);
+                    }
+                    const bool kok = CH * ci + 16 * jt + c < S;
+                    f16x4 dsh;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float pe = kok ? __builtin_amdgcn_exp2f(sa[r] * cexp - lse[r]) : 0.f;
+                        dsh[r] = (f16)__builtin_amdgcn_fmed3f(pe * (da[r] - dqr[r]) * 0.125f, -F16_MAX, F16_MAX);
+                    }
+                    *(f16x4*)(scr0 + c * 16 + 4 * g) = dsh;                                       // scratch[key c][queries 4 g ..]
+                    __builtin_amdgcn_wave_barrier();
+                    const f16x4 dsT = lds_read_tr(scr0 + (4 * g + (c >> 2)) * 16 + 4 * (c & 3));    // B[k = key 4 g + e][col = query c]
+#pragma unroll
+                    for (int ft = 0; ft < 4; ++ft) {
+                        const f16x4 kT = lds_read_tr(sA + (16 * jt + 4 * g + (c >> 2)) * LP + 16 * ft + 4 * (c & 3));   // A[row = feature 16 ft + c][k = key 4 g + e]
+                        dqa[ft] = mfma16k16(kT, dsT, dqa[ft]);           // rows: features 16 ft + 4 g + r; column: query c
+                    }
+                    __builtin_amdgcn_wave_barrier();
+                }
+            }
+        }
+        if (act && qok) {   // RoPE^T: the pair partner of feature 16 ft + 4 g + r is register r ^ 1 of the same lane
+            const size_t m = (size_t)nb * S + qrow;
+#pragma unroll
+            for (int ft = 0; ft < 4; ++ft) {
+                const f32x4 a = dqa[ft], cs = *(const f32x4*)(rope_cs + (size_t)qrow * 64 + 16 * ft + 4 * g);
+                *(f16x4*)(dqkv + tiled_off((int)m, head * 64 + 16 * ft + 4 * g, 3 * D)) =
+                    sat4(a[0] * cs[0] + a[1] * cs[1], a[1] * cs[0] - a[0] * cs[1], a[2] * cs[2] + a[3] * cs[3], a[3] * cs[2] - a[2] * cs[3], amax);
+            }
+        }
+    }
+    // ---- key pass ----
+    f16* so = sout + w * 16 * LP;
+    for (int kg = 0; kg < ngrp; ++kg) {
+        const int j = kg * NW + w, krow = 16 * j + c;
+        const bool act = j < nt, kok = krow < S;
+        f16x8 kb[2], vb[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            kb[h] = kok ? *(const f16x8*)(k + (size_t)krow * 64 + 32 * h + 8 * g) : z8;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) vb[h][e] = kok ? vt[(size_t)(32 * h + 8 * g + e) * S + krow] : (f16)0.f;
+        }
+        f32x4 dKa[4], dVa[4];
+#pragma unroll
+        for (int ft = 0; ft < 4; ++ft) dKa[ft] = dVa[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
+        load_qg(0);
+        for (int ci = 0; ci < nch; ++ci) {
+            __syncthreads();
+            store_qg();
+            __syncthreads();
+            if (ci + 1 < nch) load_qg((ci + 1) * CH);
+            if (!act) continue;
+#pragma unroll
+            for (int it = 0; it < TPC; ++it) {
+                if (CH * ci + 16 * it < S) {
+                    const int i = TPC * ci + it;
+                    f32x4 sa = f32x4{0.f, 0.f, 0.f, 0.f}, da = sa;
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const f16x8 qa = *(const f16x8*)(sA + (16 * it + c) * LP + 32 * h + 8 * g);
+                        const f16x8 ga = *(const f16x8*)(sB + (16 * it + c) * LP + 32 * h + 8 * g);
+                        sa = mfma16(qa, kb[h], sa, 0, 0, 0);     // rows: queries 16 i + 4 g + r; column: key 16 j + c
+                        da = mfma16(ga, vb[h], da, 0, 0, 0);
+                    }
+                    // query rows at or beyond S: Q = dO = 0 in the chunk and their statistics are those of a zero query (finite, Dq = 0), so dS = 0 and P meets dO = 0
+                    const f32x4 l4 = *(const f32x4*)(slse + 16 * i + 4 * g), d4 = *(const f32x4*)(sDq + 16 * i + 4 * g);
+                    f16x4 ph, dsh;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float pe = kok ? __builtin_amdgcn_exp2f(sa[r] * cexp - l4[r]) : 0.f;
+                        const float dsv = pe * (da[r] - d4[r]) * 0.125f;
+                        amax = fmaxf(amax, fabsf(dsv));
+                        ph[r] = (f16)pe;
+                        dsh[r] = (f16)__builtin_amdgcn_fmed3f(dsv, -F16_MAX, F16_MAX);
+                    }
+#pragma unroll
+                    for (int ft = 0; ft < 4; ++ft) {
+                        const f16x4 goT = lds_read_tr(sB + (16 * it + 4 * g + (c >> 2)) * LP + 16 * ft + 4 * (c & 3));   // B[k = query 4 g + e][col = feature 16 ft + c]
+                        const f16x4 qT = lds_read_tr(sA + (16 * it + 4 * g + (c >> 2)) * LP + 16 * ft + 4 * (c & 3));
+                        dVa[ft] = mfma16k16(ph, goT, dVa[ft]);     // rows: keys 16 j + 4 g + r; column: feature 16 ft + c
+                        dKa[ft] = mfma16k16(dsh, qT, dKa[ft]);
+                    }
+                }
+            }
+        }
+        if (!act) continue;
+        // dK_j (RoPE^T: the pair partner of feature 16 ft + c is the neighbouring lane c ^ 1), then dV_j, through the wave's 16-row image into 16-byte stores
+#pragma unroll
+        for (int ft = 0; ft < 4; ++ft) {
+            const int d = 16 * ft + c;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int key = min(16 * j + 4 * g + r, S - 1);      // (a padded key row holds zeros and is not stored)
+                const float mine = dKa[ft][r], other = __shfl_xor(mine, 1, 64);
+                const float co = rope_cs[(size_t)key * 64 + (d & ~1)], si = rope_cs[(size_t)key * 64 + (d | 1)];
+                const float dk = (d & 1) ? mine * co - other * si : mine * co + other * si;
+                amax = fmaxf(amax, fmaxf(fabsf(dk), fabsf(dVa[ft][r])));
+                so[(4 * g + r) * LP + d] = (f16)__builtin_amdgcn_fmed3f(dk, -F16_MAX, F16_MAX);
+            }
+        }
+#pragma unroll
+        for (int part = 0; part < 2; ++part) {
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const int p = lane + 64 * t, row = p >> 3, ch = p & 7, key = 16 * j + row;
+                if (key < S)
+                    *(uint4*)(dqkv + tiled_off((int)((size_t)nb * S + key), (1 + part) * D + head * 64 + 8 * ch, 3 * D)) = *(const uint4*)(so + row * LP + 8 * ch);
+            }
+            __builtin_amdgcn_wave_barrier();
+            if (part == 0) {
+#pragma unroll
+                for (int ft = 0; ft < 4; ++ft)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) so[(4 * g + r) * LP + 16 * ft + c] = (f16)__builtin_amdgcn_fmed3f(dVa[ft][r], -F16_MAX, F16_MAX);
+            }
+        }
     }
     sat_report(amax, err_flag);
 }
@@ -1495,7 +1789,14 @@ static int g_attn_bwd_valu = GTAV_ENV_INT("GTAV_ATTN_BWD_VALU", 0);   // experim
 static int g_attn_bwd_dbg = GTAV_ENV_INT("GTAV_ATTN_BWD_DBG", 0);     // experiments build: timing variants of the MFMA kernel (wrong results)
 int launch_attn_spatial_bwd(const f16* Q, const f16* K, const f16* Vt, const f16* dO, int NB, int heads, int S, int D, const float* rope_cs, f16* dqkv,
                             int* err_flag, hipStream_t stream) {
-    GTAV_REQUIRE(S > 0 && S <= AB_MAXS && S % 16 == 0 && D == heads * 64, "attn_spatial_bwd: S=%d (<= %d, %% 16), D=%d", S, AB_MAXS, D);
+    GTAV_REQUIRE(S > 0 && S % 8 == 0 && D == heads * 64, "attn_spatial_bwd: S=%d must be a positive multiple of 8 (tokens per frame) and D=%d must be 64 x heads", S, D);
+    if (S > AB_MAXS || S % 16 != 0) {   // the streaming kernel; S <= 160 with S % 16 == 0 stays on the resident kernel below, bit for bit
+        const size_t lds = attn_bwd_stream_lds(S);
+        GTAV_REQUIRE(lds <= 160 * 1024, "attn_spatial_bwd: S=%d needs %zu bytes of LDS for its row statistics (S <= 15360)", S, lds);
+        hipLaunchKernelGGL(attn_spatial_bwd_stream_kernel, dim3(NB * heads), dim3(64 * ABS_NW), lds, stream, Q, K, Vt, dO, heads, S, D, rope_cs, dqkv, err_flag);
+        GTAV_CHECK_HIP(hipGetLastError());
+        return 0;
+    }
     constexpr int NT = 512;
     const size_t lds_valu = (size_t)4 * S * 72 * 2 + (size_t)2 * (NT / 16) * (S + 4) * 4;
     const size_t lds_mfma = (size_t)4 * S * ABM_LP * 2 + (size_t)S * ABM_DQP * 4 + (size_t)2 * S * 4 + (size_t)ABM_NW * 256 * 2;

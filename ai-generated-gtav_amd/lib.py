@@ -136,6 +136,7 @@ SIGNATURES = {
     "gtav_op_gemm_tn": [_p, _p, _i, _i, _i, _p, _i, _p],
     "gtav_op_gemm_dw_grouped": [_i, _p, _p, _p, _p, _p, _p, _i, _p],
     "gtav_op_attn_spatial_bwd": [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p],
+    "gtav_op_attn_spatial_bwd_bf16": [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p],
     "gtav_op_gemm_qkvt_attn": [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p],
     "gtav_op_qkv_head_major_spatial": [_p, _p, _i, _p],
     "gtav_op_gemm_qkvs_attn": [_p, _p, _i, _i, _i, _p, _p, _p],

@@ -376,9 +376,14 @@ int gtav_op_gemm_qkvs_attn(const void* x_f16_dev, const void* w_hm_f16_dev, int3
                            void* stream);
 /* Backward of the spatial attention (model/attention.py:99-136) for NB x heads (frame, head) items of S tokens: q, k [item][S][64]
  * (RoPE applied), vt [item][64][S], d_o fp16 row-major [NB S][heads 64]; writes the gradient of the to_qkv output, fp16 tile-major
- * logical [NB S][3 heads 64] (dq | dk | dv, dq / dk rotated back through the RoPE).  S % 16 == 0, S <= 160. */
+ * logical [NB S][3 heads 64] (dq | dk | dv, dq / dk rotated back through the RoPE).  S is any positive multiple of 8 (the forward's rule), up to 15 360:
+ * S <= 160 with S % 16 == 0 runs the kernel that keeps the whole (frame, head) in LDS, every other S the streaming kernel (64-row chunks of the
+ * streamed side, row statistics recomputed in a pre-pass); both are free of atomics: two launches give the same bits.  Buffers are not padded: nothing at
+ * or beyond row S of an item is read.  The _bf16 form takes bf16 q / k / vt / d_o and writes bf16 (the training step of a bf16 handle). */
 int gtav_op_attn_spatial_bwd(const void* q_dev, const void* k_dev, const void* vt_dev, const void* d_o_dev, int32_t NB, int32_t heads,
                              int32_t S, const float* rope_cs_dev, void* dqkv_dev, void* stream);
+int gtav_op_attn_spatial_bwd_bf16(const void* q_dev, const void* k_dev, const void* vt_dev, const void* d_o_dev, int32_t NB, int32_t heads,
+                                  int32_t S, const float* rope_cs_dev, void* dqkv_dev, void* stream);
 /* Weight-gradient GEMM (train_dit.py:680 accelerator.backward, the dW = dY^T X of every Linear): out[m][n] += sum_t x[t][m] * w[t][n] with
  * both operands the ordinary tile-major fp16 activations [K tokens][features] (x: M features, w: N features); out f32 row-major [M][ldo],
  * accumulated in place.  M, N multiples of 128, K a multiple of 64. */

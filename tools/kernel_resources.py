@@ -11,6 +11,8 @@ extra = sys.argv[3:]
 r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-pass-failed",
                     "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", "/dev/null"] + extra, capture_output=True, text=True)
 blocks = re.split(r"remark: Function Name: ", r.stderr)[1:]
+if not blocks:      # the compile failed (or has no kernels): show why instead of handing c++filt an empty list, which makes it wait on stdin
+    sys.exit(r.stderr[-4000:] or "no kernels found")
 names = [b.split()[0] for b in blocks]
 dem = subprocess.run(["c++filt"] + names, capture_output=True, text=True).stdout.strip().split("\n")
 for b, d in zip(blocks, dem):

@@ -19,6 +19,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--latent-hw", type=int, nargs=2, default=[18, 32], help="latent height and width (36 64: 576 tokens per frame)")
     ap.add_argument("--dtype", choices=("fp16", "bf16"), default=None, help="operand type of the training step, on the product library")
     a = ap.parse_args()
     if a.dtype is None:
@@ -31,16 +32,19 @@ def main():
     dev = torch.device("cuda", 0)
     B = a.batch
     train_dtype = torch.bfloat16 if a.dtype == "bf16" else torch.float16
-    dit = DiT_models["DiT-S/2"](init_weights=False, max_batch=B, trainable=True, train_dtype=train_dtype)
-    dit.load_state_dict(W.synth_state_dict(W.dit_param_shapes(depth=16), seed=0))
+    LH, LW = a.latent_hw
+    from gtav_amd.model.dit import DiT
+    dit = DiT(input_h=LH, input_w=LW, patch_size=2, hidden_size=1024, depth=16, num_heads=16, max_frames=5, init_weights=False, max_batch=B, trainable=True,
+              train_dtype=train_dtype)   # DiT-S/2 at the given latent size
+    dit.load_state_dict(W.synth_state_dict(W.dit_param_shapes(depth=16, input_h=LH, input_w=LW), seed=0))
     g = torch.Generator().manual_seed(7)
-    lat = (torch.randn(B, 5, 16, 18, 32, generator=g) * 0.5).to(dev)
+    lat = (torch.randn(B, 5, 16, LH, LW, generator=g) * 0.5).to(dev)
     actions = torch.zeros(B, 5, 25, device=dev)
     actions[:, :, 3] = 1
     tgt = torch.randint(1, 51, (B,), generator=g)
     ctx = torch.randint(1, 41, (B,), generator=g)
-    ctx_noise = torch.randn(B, 4, 16, 18, 32, generator=g).to(dev)
-    noise = torch.randn(B, 1, 16, 18, 32, generator=g).to(dev)
+    ctx_noise = torch.randn(B, 4, 16, LH, LW, generator=g).to(dev)
+    noise = torch.randn(B, 1, 16, LH, LW, generator=g).to(dev)
 
     def step():
         return training_step(dit, lat, actions, tgt, ctx, ctx_noise, noise, lr=1e-5, weight_decay=0.01, max_grad_norm=1.0, world_size=1)
@@ -54,7 +58,7 @@ def main():
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / a.steps * 1e3
     applied, skipped, gnorm = dit.train_stats()
-    print(json.dumps({"batch": B, "dtype": a.dtype or "fp16 (experiments library)", "ms_per_step": round(ms, 3), "loss": float(loss), "grad_norm": gnorm, "skipped": skipped,
+    print(json.dumps({"batch": B, "latent_hw": [LH, LW], "dtype": a.dtype or "fp16 (experiments library)", "ms_per_step": round(ms, 3), "loss": float(loss), "grad_norm": gnorm, "skipped": skipped,
                       "env": {k: v for k, v in os.environ.items() if k.startswith("GTAV_")}}))
 
 
