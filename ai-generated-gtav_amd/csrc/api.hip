@@ -2,8 +2,10 @@
 // enqueue the kernel sequence of each reference entry point on the caller's stream.
 #include "api_internal.h"
 
-namespace gtav_shared { thread_local hipEvent_t g_launch_ev[2] = {nullptr, nullptr}; }   // common.h GTAV_LAUNCH: the profiler's event pair for the next launch of this thread
-namespace gtav {
+#include <type_traits>
+
+namespace gtav_shared {   // common.h: shared by the fp16 objects and their bf16 twins
+thread_local hipEvent_t g_launch_ev[2] = {nullptr, nullptr};   // GTAV_LAUNCH: the profiler's event pair for the next launch of this thread
 static thread_local char g_err[1024] = "";
 void set_error(const char* fmt, ...) {
     va_list ap;
@@ -12,106 +14,49 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 const char* last_error() { return g_err; }
-}  // namespace gtav
-// the bf16 twin objects (ops_bf16.h) report through the same thread-local string
-namespace gtav_bf16 {
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(gtav::g_err, sizeof(gtav::g_err), fmt, ap);
-    va_end(ap);
-}
-const char* last_error() { return gtav::g_err; }
-}  // namespace gtav_bf16
+}  // namespace gtav_shared
 
-// ---- the two sets of launchers (ops_bf16.h): fp16 operands (default) and their bf16 twins ----
+// ---- the two sets of launchers (ops_bf16.h GTAV_OPERAND_OPS): fp16 operands (default) and their bf16 twins ----
 namespace {
-const gtav_bf16::GemmParams& bfp(const GemmParams& p) { return reinterpret_cast<const gtav_bf16::GemmParams&>(p); }
-const gtav_bf16::LnPending* bfl(const LnPending* p) { return reinterpret_cast<const gtav_bf16::LnPending*>(p); }
-int f16_attn_spatial(const f16* Q, const f16* K, const f16* Vt, f16* O, int NB, int heads, int S, hipStream_t st, bool qp) { return launch_attn_spatial(Q, K, Vt, O, NB, heads, S, st, qp); }
-int bf_gemm(const GemmParams& p, int epi, hipStream_t st) { return gtav_bf16::launch_gemm(bfp(p), epi, st); }
-int bf_ln_modulate(float* x, int ldx, f16* out, int ldo, int M, int D, const float* shift, const float* scale, int mod_stride, const int* rows, int rpm,
-                   const LnPending* pend, int* ef, hipStream_t st) {
-    return gtav_bf16::launch_ln_modulate(x, ldx, (__bf16*)out, ldo, M, D, shift, scale, mod_stride, rows, rpm, bfl(pend), ef, st);
-}
-int bf_ln_affine(float* x, int ldx, f16* out, int ldo, int M, int D, const float* gamma, const float* beta, const LnPending* pend, int* ef, hipStream_t st) {
-    return gtav_bf16::launch_ln_affine(x, ldx, (__bf16*)out, ldo, M, D, gamma, beta, bfl(pend), ef, st);
-}
-int bf_patchify(const float* img, const int* fi, int NB, int C, int H, int W, int p, f16* out, int ldo, float a, float b, int* ef, hipStream_t st) {
-    return gtav_bf16::launch_patchify(img, fi, NB, C, H, W, p, (__bf16*)out, ldo, a, b, ef, st);
-}
-int f16_convert_pad(const float* src, int lds, int R, int C, f16* dst, int Rp, int Cp, float scale, int tiled, hipStream_t st, int* ef) {
-    return launch_convert_pad_f16(src, lds, R, C, dst, Rp, Cp, scale, tiled, st, ef);
-}
-int bf_convert_pad(const float* src, int lds, int R, int C, f16* dst, int Rp, int Cp, float scale, int tiled, hipStream_t st, int* ef) {
-    return gtav_bf16::launch_convert_pad_f16(src, lds, R, C, (__bf16*)dst, Rp, Cp, scale, tiled, st, ef);
-}
-int bf_unpad(const f16* src, int lds, int R, int C, float* dst, int tiled, hipStream_t st) { return gtav_bf16::launch_unpad_f16_to_f32((const __bf16*)src, lds, R, C, dst, tiled, st); }
-int bf_attn_spatial(const f16* Q, const f16* K, const f16* Vt, f16* O, int NB, int heads, int S, hipStream_t st, bool qp) {
-    return gtav_bf16::launch_attn_spatial((const __bf16*)Q, (const __bf16*)K, (const __bf16*)Vt, (__bf16*)O, NB, heads, S, st, qp);
-}
-int bf_attn_temporal(const f16* q, const f16* kv, f16* O, int B, int P, int D, int Tq, int t0, int Tmax, hipStream_t st) {
-    return gtav_bf16::launch_attn_temporal((const __bf16*)q, (const __bf16*)kv, (__bf16*)O, B, P, D, Tq, t0, Tmax, st);
-}
-const OperandOps OPS_F16 = {launch_gemm, launch_ln_modulate, launch_ln_affine, launch_patchify, f16_convert_pad, launch_unpad_f16_to_f32, f16_attn_spatial,
-                            launch_attn_temporal, false};
-const OperandOps OPS_BF16 = {bf_gemm, bf_ln_modulate, bf_ln_affine, bf_patchify, bf_convert_pad, bf_unpad, bf_attn_spatial, bf_attn_temporal, true};
+// The type the twin declares where the fp16 signature has T: 2-byte pointers and the parameter structs that name `f16` change namespace, the rest is itself.
+template <class T> struct twin_arg { typedef T type; };
+template <> struct twin_arg<const f16*> { typedef const __bf16* type; };
+template <> struct twin_arg<f16*> { typedef __bf16* type; };
+// The two views of a struct are one text (gemm_typed.inc / ops_typed.inc) that differs in the pointee of 2-byte pointers only; checked here all the same.
+#define GTAV_TWIN_STRUCT(S)                                                                                                                     \
+    static_assert(sizeof(S) == sizeof(gtav_bf16::S) && alignof(S) == alignof(gtav_bf16::S) && std::is_standard_layout<S>::value &&             \
+                      std::is_standard_layout<gtav_bf16::S>::value, #S ": the fp16 and the bf16 view differ");                                  \
+    template <> struct twin_arg<const S&> { typedef const gtav_bf16::S& type; };                                                                \
+    template <> struct twin_arg<const S*> { typedef const gtav_bf16::S* type; };
+GTAV_TWIN_STRUCT(GemmParams)
+GTAV_TWIN_STRUCT(LnPending)
+GTAV_TWIN_STRUCT(GemmDwGroup)
+GTAV_TWIN_STRUCT(AdamParam)
+GTAV_TWIN_STRUCT(AdamItem)
+#undef GTAV_TWIN_STRUCT
+// twin_call<fp16 signature, twin's signature, twin>::call has the fp16 signature and calls the twin with every argument cast to the type the twin declares.
+// A twin whose signature is not the mapped fp16 one does not compile.
+template <class Sig, class TwinSig, TwinSig* Fn> struct twin_call;
+template <class... A, class... B, int (*Fn)(B...)> struct twin_call<int(A...), int(B...), Fn> {
+    static_assert((std::is_same<typename twin_arg<A>::type, B>::value && ...), "a bf16 twin's signature differs from its fp16 launcher's");
+    template <class To, class From> static To cast(From a) {
+        if constexpr (std::is_same<To, From>::value) return a;
+        else return reinterpret_cast<To>(a);
+    }
+    static int call(A... a) { return Fn(cast<B, A>(a)...); }
+};
+#define GTAV_OPS_F16(field, launcher) &launcher,
+#define GTAV_OPS_BF16(field, launcher) &twin_call<decltype(launcher), decltype(gtav_bf16::launcher), &gtav_bf16::launcher>::call,
+const OperandOps OPS_F16 = {GTAV_OPERAND_OPS(GTAV_OPS_F16) false};
+const OperandOps OPS_BF16 = {GTAV_OPERAND_OPS(GTAV_OPS_BF16) true};
+#undef GTAV_OPS_F16
+#undef GTAV_OPS_BF16
 }  // namespace
 const OperandOps& gtav::operand_ops(bool bf16) { return bf16 ? OPS_BF16 : OPS_F16; }
 
-// ---- the training step's launchers per operand type (ops_bf16.h TrainOps) ----
-namespace {
-typedef const __bf16* cbp;
-typedef __bf16* bp;
-int f16_dw_grouped(const GemmDwGroup* g, int n, int K, int* ef, hipStream_t st, bool tn) { return launch_gemm_dw_grouped(g, n, K, ef, st, tn); }
-int bf_gemm_tn(const GemmParams& p, hipStream_t st) { return gtav_bf16::launch_gemm_tn(bfp(p), st); }
-int bf_dw_grouped(const GemmDwGroup* g, int n, int K, int* ef, hipStream_t st, bool tn) {
-    return gtav_bf16::launch_gemm_dw_grouped(reinterpret_cast<const gtav_bf16::GemmDwGroup*>(g), n, K, ef, st, tn);
-}
-int bf_transpose(const f16* src, int R, int C, f16* dst, hipStream_t st) { return gtav_bf16::launch_transpose_tiled_f16((cbp)src, R, C, (bp)dst, st); }
-int bf_convert_T(const float* src, int lds, int R, int C, f16* dst, hipStream_t st) { return gtav_bf16::launch_convert_T_f16(src, lds, R, C, (bp)dst, st); }
-int bf_gelu(const f16* u, f16* h, size_t n, hipStream_t st) { return gtav_bf16::launch_gelu_tiled((cbp)u, (bp)h, n, st); }
-int bf_gelu_bwd(const f16* dh, const f16* u, f16* du, size_t n, int* ef, hipStream_t st) { return gtav_bf16::launch_gelu_bwd_tiled((cbp)dh, (cbp)u, (bp)du, n, ef, st); }
-int bf_gelu_bwd_colsum(const f16* dh, const f16* u, f16* du, int M, int N, float* db, float* ws, int* ef, hipStream_t st) {
-    return gtav_bf16::launch_gelu_bwd_tiled_colsum((cbp)dh, (cbp)u, (bp)du, M, N, db, ws, ef, st);
-}
-int bf_gate_bwd(const float* dres, const float* gate, int ms, int rpm, int M, int D, f16* dy, int* ef, hipStream_t st) {
-    return gtav_bf16::launch_gate_bwd(dres, gate, ms, rpm, M, D, (bp)dy, ef, st);
-}
-int bf_frame_reduce_gate(const float* dres, const f16* y, int frames, int P, int D, float* dgate, int ms, hipStream_t st) {
-    return gtav_bf16::launch_frame_reduce_gate(dres, (cbp)y, frames, P, D, dgate, ms, st);
-}
-int bf_gate_bwd_fused(const float* dres, const f16* y, const float* gate, int ms, int frames, int P, int D, f16* dy, float* dgate, float* db, float* ws, int* ef,
-                      hipStream_t st) {
-    return gtav_bf16::launch_gate_bwd_fused(dres, (cbp)y, gate, ms, frames, P, D, (bp)dy, dgate, db, ws, ef, st);
-}
-int bf_colsum(const f16* dy, int M, int N, float* db, float* ws, hipStream_t st) { return gtav_bf16::launch_colsum_tiled_f16((cbp)dy, M, N, db, ws, st); }
-int bf_to_tiled(const float* a, int M, int D, f16* out, int* ef, hipStream_t st) { return gtav_bf16::launch_to_tiled_f16(a, M, D, (bp)out, ef, st); }
-int bf_mse_bwd(const float* vp, const float* vt, int B, int T, int C, int H, int W, int p, float scale, f16* dfo, int ldf, int* ef, hipStream_t st) {
-    return gtav_bf16::launch_mse_bwd_patch(vp, vt, B, T, C, H, W, p, scale, (bp)dfo, ldf, ef, st);
-}
-int bf_attn_spatial_bwd(const f16* Q, const f16* K, const f16* Vt, const f16* dO, int NB, int heads, int S, int D, const float* cs, f16* dqkv, int* ef,
-                        hipStream_t st) {
-    return gtav_bf16::launch_attn_spatial_bwd((cbp)Q, (cbp)K, (cbp)Vt, (cbp)dO, NB, heads, S, D, cs, (bp)dqkv, ef, st);
-}
-int bf_attn_temporal_bwd(const f16* q, const f16* kv, const f16* dO, int B, int P, int D, int T, int Tmax, const float* cs, f16* dqkv, int* ef, hipStream_t st) {
-    return gtav_bf16::launch_attn_temporal_bwd((cbp)q, (cbp)kv, (cbp)dO, B, P, D, T, Tmax, cs, (bp)dqkv, ef, st);
-}
-int bf_adamw_multi(const AdamParam* params, const AdamItem* items, int n, const float* ctl, float lr, float b1, float b2, float eps, float wd, hipStream_t st) {
-    return gtav_bf16::launch_adamw_multi(reinterpret_cast<const gtav_bf16::AdamParam*>(params), reinterpret_cast<const gtav_bf16::AdamItem*>(items), n, ctl, lr,
-                                         b1, b2, eps, wd, st);
-}
-const TrainOps TRAIN_F16 = {launch_gemm_tn, f16_dw_grouped, launch_transpose_tiled_f16, launch_convert_T_f16, launch_gelu_tiled, launch_gelu_bwd_tiled,
-                            launch_gelu_bwd_tiled_colsum, launch_gate_bwd, launch_frame_reduce_gate, launch_gate_bwd_fused, launch_colsum_tiled_f16,
-                            launch_to_tiled_f16, launch_mse_bwd_patch, launch_attn_spatial_bwd, launch_attn_temporal_bwd, launch_adamw_multi, false};
-const TrainOps TRAIN_BF16 = {bf_gemm_tn, bf_dw_grouped, bf_transpose, bf_convert_T, bf_gelu, bf_gelu_bwd, bf_gelu_bwd_colsum, bf_gate_bwd, bf_frame_reduce_gate,
-                             bf_gate_bwd_fused, bf_colsum, bf_to_tiled, bf_mse_bwd, bf_attn_spatial_bwd, bf_attn_temporal_bwd, bf_adamw_multi, true};
-}  // namespace
-const TrainOps& gtav::train_ops(bool bf16) { return bf16 ? TRAIN_BF16 : TRAIN_F16; }
-
 extern "C" {
 
-const char* gtav_last_error(void) { return gtav::last_error(); }
+const char* gtav_last_error(void) { return last_error(); }
 int gtav_abi_version(void) { return 4; }   // 3: training step (gtav_dit_train_*), collectives (gtav_comm_*); 4: LayerNorm fold switch, optimizer state (gtav_dit_{get,set}_opt_state)
 
 // ------------------------------------------------------------------------------------------------
@@ -240,13 +185,16 @@ int gtav_op_ln_affine(const float* x, void* out, int32_t M, int32_t D, const flo
 int gtav_op_attn_spatial(const void* q, const void* k, const void* vt, void* o, int32_t NB, int32_t heads, int32_t S, void* stream) {
     return launch_attn_spatial((const f16*)q, (const f16*)k, (const f16*)vt, (f16*)o, NB, heads, S, (hipStream_t)stream);
 }
+static int op_attn_temporal(bool bf16, const void* q, const void* kv, void* o, int32_t B, int32_t P, int32_t D, int32_t Tq, int32_t t0, int32_t Tmax, void* stream) {
+    return operand_ops(bf16).attn_temporal((const f16*)q, (const f16*)kv, (f16*)o, B, P, D, Tq, t0, Tmax, (hipStream_t)stream);
+}
 int gtav_op_attn_temporal(const void* q, const void* kv, void* o, int32_t B, int32_t P, int32_t D, int32_t Tq, int32_t t0,
                           int32_t Tmax, void* stream) {
-    return launch_attn_temporal((const f16*)q, (const f16*)kv, (f16*)o, B, P, D, Tq, t0, Tmax, (hipStream_t)stream);
+    return op_attn_temporal(false, q, kv, o, B, P, D, Tq, t0, Tmax, stream);
 }
 int gtav_op_attn_temporal_bf16(const void* q, const void* kv, void* o, int32_t B, int32_t P, int32_t D, int32_t Tq, int32_t t0,
                                int32_t Tmax, void* stream) {
-    return gtav_bf16::launch_attn_temporal((const __bf16*)q, (const __bf16*)kv, (__bf16*)o, B, P, D, Tq, t0, Tmax, (hipStream_t)stream);
+    return op_attn_temporal(true, q, kv, o, B, P, D, Tq, t0, Tmax, stream);
 }
 int gtav_op_qkv_head_major(const void* w, void* w_hm, int32_t D, void* stream) {
     return launch_qkv_head_major((const f16*)w, (f16*)w_hm, D, (hipStream_t)stream);
@@ -270,15 +218,18 @@ int gtav_op_gemm_qkvs_attn(const void* x, const void* w_hm, int32_t M, int32_t D
     g.qkv_mode = QKV_SPATIAL; g.out = o; g.ldo = D; g.rope_cs = rope_cs;
     return launch_gemm_qkvs_attn(g, (hipStream_t)stream);
 }
+static int op_attn_spatial_bwd(bool bf16, const void* q, const void* k, const void* vt, const void* d_o, int32_t NB, int32_t heads, int32_t S, const float* rope_cs,
+                               void* dqkv, void* stream) {
+    return operand_ops(bf16).attn_spatial_bwd((const f16*)q, (const f16*)k, (const f16*)vt, (const f16*)d_o, NB, heads, S, heads * 64, rope_cs, (f16*)dqkv, nullptr,
+                                              (hipStream_t)stream);
+}
 int gtav_op_attn_spatial_bwd(const void* q, const void* k, const void* vt, const void* d_o, int32_t NB, int32_t heads, int32_t S,
                              const float* rope_cs, void* dqkv, void* stream) {
-    return launch_attn_spatial_bwd((const f16*)q, (const f16*)k, (const f16*)vt, (const f16*)d_o, NB, heads, S, heads * 64, rope_cs, (f16*)dqkv, nullptr,
-                                   (hipStream_t)stream);
+    return op_attn_spatial_bwd(false, q, k, vt, d_o, NB, heads, S, rope_cs, dqkv, stream);
 }
 int gtav_op_attn_spatial_bwd_bf16(const void* q, const void* k, const void* vt, const void* d_o, int32_t NB, int32_t heads, int32_t S,
                                   const float* rope_cs, void* dqkv, void* stream) {
-    return gtav_bf16::launch_attn_spatial_bwd((const __bf16*)q, (const __bf16*)k, (const __bf16*)vt, (const __bf16*)d_o, NB, heads, S, heads * 64, rope_cs,
-                                              (__bf16*)dqkv, nullptr, (hipStream_t)stream);
+    return op_attn_spatial_bwd(true, q, k, vt, d_o, NB, heads, S, rope_cs, dqkv, stream);
 }
 int gtav_op_gemm_tn(const void* x, const void* w, int32_t M, int32_t N, int32_t K, float* out, int32_t ldo, void* stream) {
     GemmParams q;

@@ -105,7 +105,7 @@ struct WeightTable {
         }
         else RET_IF(launch_copy_f32(src, sl.C, sl.R, sl.C, (float*)sl.dst, sl.Cp, sl.c0, s));
         if (sl.master && sl.kind == SLOT_F16_PAD) RET_IF(launch_copy_f32(src, sl.C, sl.R, sl.C, sl.master, sl.C, 0, s));
-        if (sl.wT) RET_IF(train_ops(sl.bf16).convert_T(src, sl.C, sl.R, sl.C, sl.wT, s));
+        if (sl.wT) RET_IF(operand_ops(sl.bf16).convert_T(src, sl.C, sl.R, sl.C, sl.wT, s));
         sl.set = true;
         return 0;
     }
@@ -285,7 +285,6 @@ struct gtav_dit {
     int n_groups = 0;
     bool any_bf16 = false;
     const OperandOps& ops(int g) const { return operand_ops(grp_bf16[g] != 0); }
-    const TrainOps& tops(int g) const { return train_ops(grp_bf16[g] != 0); }   // the training step's launchers of group g (api_train.hip)
     int* err_of(int g) const { return err_flag + 4 + g; }
     int* frame_idx = nullptr;   // [maxB * maxT]
     StepParams* step_dev = nullptr;

@@ -27,7 +27,7 @@ extern "C" {
 // weights, with fp16 operands and a loss scale in place of bf16's exponent range: activation gradients travel as fp16 GEMM
 // operands multiplied by tr.loss_scale, weight gradients / LayerNorm statistics / the residual-stream gradient are fp32.
 // gtav_dit_train_enable_typed(.., GTAV_OPERAND_BF16) runs the same step on bf16 operands (the reference's own autocast type): every launch below that
-// reads or writes a 2-byte tensor goes through the operand group's launcher set (h->ops(g) / h->tops(g)), the twins of the same kernels (ops_bf16.h).
+// reads or writes a 2-byte tensor goes through the operand group's launcher set (h->ops(g): ops_bf16.h OperandOps), the twins of the same kernels.
 // ================================================================================================
 int gtav_dit_train_enable(gtav_dit* h, float* grad_arena_dev, int64_t grad_arena_numel) {
     GTAV_REQUIRE(h, "train_enable: null handle");
@@ -264,7 +264,7 @@ int gtav_dit_train_forward(gtav_dit* h, const float* x, const int64_t* t64, cons
             g.X = b.xnB; g.ldx = D; g.W = w.w_fc1; g.M = M; g.N = h->Hm; g.K = D; g.bias = w.b_fc1; g.out = b.u; g.ldo = h->Hm_pad; g.err_flag = h->err_flag;
             if (g_fuse_gelu_fwd) g.out2 = b.hh;             // h = GELU(u) as a second image of the same epilogue (gemm.h out2)
             RET_IF(o.gemm(g, EPI_F16_TILED, s));            // the pre-activation is kept: gelu'(u) in the backward pass
-            if (!g_fuse_gelu_fwd) RET_IF(h->tops(i).gelu_tiled(b.u, b.hh, (size_t)round_up(M, 128) * h->Hm_pad, s));
+            if (!g_fuse_gelu_fwd) RET_IF(h->ops(i).gelu_tiled(b.u, b.hh, (size_t)round_up(M, 128) * h->Hm_pad, s));
             RET_IF(resid_gemm(o, b.hh, w.w_fc2, h->Hm_pad, w.b_fc2, mb + 5 * D, tr.res[2 * i + 2], b.y2));
         }
     const float* mf = mod + (size_t)L * 12 * D;
@@ -306,7 +306,6 @@ int gtav_dit_train_backward_phases(gtav_dit* h, const float* v_pred, const float
     auto slot = [&](const std::string& n) -> Slot& { return h->wt.slots[n]; };
     // launcher sets of the operand group being differentiated (final layer, half-block i, patch embedding): set where each part begins
     const OperandOps* op = &h->ops(2 * L + 1);
-    const TrainOps* to = &h->tops(2 * L + 1);
     // dX = dY W: A = dY tile-major [M][Kc], WT = tile-major W^T [N][Kc]
     auto gemm_dx = [&](const f16* A, const f16* WT, int N, int Kc, int epi, void* out, int ldo) -> int {
         GemmParams q;
@@ -343,7 +342,7 @@ int gtav_dit_train_backward_phases(gtav_dit* h, const float* v_pred, const float
         if (!ndw) return 0;
         const int n = ndw;
         ndw = 0;
-        return to->gemm_dw_grouped(dwg, n, tn_dw ? M : Mp, h->err_flag, s, tn_dw);
+        return op->gemm_dw_grouped(dwg, n, tn_dw ? M : Mp, h->err_flag, s, tn_dw);
     };
     auto gemm_dw = [&](const f16* dY, int N, const f16* X, int K, float* grad, int slot_i = -1) -> int {
         if (tn_dw && slot_i >= 0) {
@@ -351,8 +350,8 @@ int gtav_dit_train_backward_phases(gtav_dit* h, const float* v_pred, const float
             return 0;
         }
         if (defer_dw && slot_i >= 0) {
-            RET_IF(to->transpose_tiled(dY, M, N, tr.tAg[slot_i], s));
-            RET_IF(to->transpose_tiled(X, M, K, tr.tBg[slot_i], s));
+            RET_IF(op->transpose_tiled(dY, M, N, tr.tAg[slot_i], s));
+            RET_IF(op->transpose_tiled(X, M, K, tr.tBg[slot_i], s));
             dwg[ndw++] = GemmDwGroup{tr.tAg[slot_i], tr.tBg[slot_i], grad, N, K, K};
             return 0;
         }
@@ -360,10 +359,10 @@ int gtav_dit_train_backward_phases(gtav_dit* h, const float* v_pred, const float
             GemmParams q;
             memset(&q, 0, sizeof(q));
             q.X = dY; q.ldx = N; q.W = X; q.M = N; q.N = K; q.K = M; q.out = grad; q.ldo = K;
-            return to->gemm_tn(q, s);
+            return op->gemm_tn(q, s);
         }
-        RET_IF(to->transpose_tiled(dY, M, N, tr.tA, s));
-        RET_IF(to->transpose_tiled(X, M, K, tr.tB, s));
+        RET_IF(op->transpose_tiled(dY, M, N, tr.tA, s));
+        RET_IF(op->transpose_tiled(X, M, K, tr.tB, s));
         GemmParams q;
         memset(&q, 0, sizeof(q));
         q.X = tr.tA; q.ldx = Mp; q.W = tr.tB; q.M = N; q.N = K; q.K = Mp; q.out = grad; q.ldo = K;
@@ -380,16 +379,16 @@ int gtav_dit_train_backward_phases(gtav_dit* h, const float* v_pred, const float
     };
     // ---- phase 0: loss -> final projection -> final LayerNorm ----
     if (phase_begin <= 0 && 0 < phase_end) {
-    RET_IF(to->mse_bwd_patch(v_pred, v_target, B, T, h->C, h->H, h->W, h->p, scale, tr.dfo, 64, h->err_flag, s));
+    RET_IF(op->mse_bwd_patch(v_pred, v_target, B, T, h->C, h->H, h->W, h->p, scale, tr.dfo, 64, h->err_flag, s));
     {
         Slot& wf = slot("final_layer.linear.weight");
         // db: column sums over the 64-wide (zero-padded) dfo, only the first Nfin belong to the bias: sum into a scratch row first
         GTAV_CHECK_HIP(hipMemsetAsync(tr.dSc, 0, 64 * sizeof(float), s));
-        RET_IF(to->colsum_tiled(tr.dfo, M, 64, tr.dSc, tr.red_ws, s));
+        RET_IF(op->colsum_tiled(tr.dfo, M, 64, tr.dSc, tr.red_ws, s));
         RET_IF(launch_add_f32(slot("final_layer.linear.bias").grad, tr.dSc, slot("final_layer.linear.bias").grad, h->Nfin, s));
         // dW_final [Nfin][D] += dfo^T xnF   (M = Nfin rows of the 64-row transposed operand)
-        RET_IF(to->transpose_tiled(tr.dfo, M, 64, tr.tA, s));
-        RET_IF(to->transpose_tiled(tr.xnF, M, D, tr.tB, s));
+        RET_IF(op->transpose_tiled(tr.dfo, M, 64, tr.tA, s));
+        RET_IF(op->transpose_tiled(tr.xnF, M, D, tr.tB, s));
         GemmParams q;
         memset(&q, 0, sizeof(q));
         q.X = tr.tA; q.ldx = Mp; q.W = tr.tB; q.M = h->Nfin; q.N = D; q.K = Mp; q.out = wf.grad; q.ldo = D;
@@ -414,26 +413,25 @@ int gtav_dit_train_backward_phases(gtav_dit* h, const float* v_pred, const float
         const float* mb = mod + (size_t)i * 6 * D;
         float* dmb = dmod + (size_t)i * 6 * D;
         op = &h->ops(i);
-        to = &h->tops(i);
         // r_{2i+2} = r_{2i+1} + gate_mlp y2
         // (defer_bias: the partial sums of the half-block's three bias gradients go to three regions of the workspace and ONE launch adds them at the end of the half-block)
         float* const ws_fc2 = tr.red_ws, *const ws_out = tr.red_ws + (defer_bias ? (size_t)NB * D : 0), *const ws_fc1 = tr.red_ws + (defer_bias ? (size_t)2 * NB * D : 0);   // (not deferred: every reduction follows its partial sums at once and the regions may coincide)
         if (fuse_gate) {
-            RET_IF(to->gate_bwd_fused(tr.dres, b.y2, mb + 5 * D, MODW, NB, P, D, tr.g_d, dmb + 5 * D, defer_bias ? nullptr : slot(P_ + "mlp.fc2.bias").grad, ws_fc2, h->err_flag, s));
+            RET_IF(op->gate_bwd_fused(tr.dres, b.y2, mb + 5 * D, MODW, NB, P, D, tr.g_d, dmb + 5 * D, defer_bias ? nullptr : slot(P_ + "mlp.fc2.bias").grad, ws_fc2, h->err_flag, s));
         } else {
-            RET_IF(to->gate_bwd(tr.dres, mb + 5 * D, MODW, P, M, D, tr.g_d, h->err_flag, s));
-            RET_IF(to->frame_reduce_gate(tr.dres, b.y2, NB, P, D, dmb + 5 * D, MODW, s));
-            RET_IF(to->colsum_tiled(tr.g_d, M, D, slot(P_ + "mlp.fc2.bias").grad, tr.red_ws, s));
+            RET_IF(op->gate_bwd(tr.dres, mb + 5 * D, MODW, P, M, D, tr.g_d, h->err_flag, s));
+            RET_IF(op->frame_reduce_gate(tr.dres, b.y2, NB, P, D, dmb + 5 * D, MODW, s));
+            RET_IF(op->colsum_tiled(tr.g_d, M, D, slot(P_ + "mlp.fc2.bias").grad, tr.red_ws, s));
         }
         RET_IF(gemm_dw(tr.g_d, D, b.hh, Hp, slot(P_ + "mlp.fc2.weight").grad, 0));
         RET_IF(gemm_dx(tr.g_d, slot(P_ + "mlp.fc2.weight").wT, Hp, D, EPI_F16_TILED, tr.g_h, Hp));
         if (defer_bias) {
-            RET_IF(to->gelu_bwd_tiled_colsum(tr.g_h, b.u, tr.g_u, M, Hp, nullptr, ws_fc1, h->err_flag, s));
+            RET_IF(op->gelu_bwd_tiled_colsum(tr.g_h, b.u, tr.g_u, M, Hp, nullptr, ws_fc1, h->err_flag, s));
         } else if (g_fuse_gelu && colsum_workspace(round_up(M, 128), Hp) <= ws_cap) {
-            RET_IF(to->gelu_bwd_tiled_colsum(tr.g_h, b.u, tr.g_u, M, Hp, slot(P_ + "mlp.fc1.bias").grad, tr.red_ws, h->err_flag, s));
+            RET_IF(op->gelu_bwd_tiled_colsum(tr.g_h, b.u, tr.g_u, M, Hp, slot(P_ + "mlp.fc1.bias").grad, tr.red_ws, h->err_flag, s));
         } else {
-            RET_IF(to->gelu_bwd_tiled(tr.g_h, b.u, tr.g_u, (size_t)round_up(M, 128) * Hp, h->err_flag, s));
-            RET_IF(to->colsum_tiled(tr.g_u, M, Hp, slot(P_ + "mlp.fc1.bias").grad, tr.red_ws, s));
+            RET_IF(op->gelu_bwd_tiled(tr.g_h, b.u, tr.g_u, (size_t)round_up(M, 128) * Hp, h->err_flag, s));
+            RET_IF(op->colsum_tiled(tr.g_u, M, Hp, slot(P_ + "mlp.fc1.bias").grad, tr.red_ws, s));
         }
         RET_IF(gemm_dw(tr.g_u, Hp, b.xnB, D, slot(P_ + "mlp.fc1.weight").grad, 1));
         RET_IF(gemm_dx(tr.g_u, slot(P_ + "mlp.fc1.weight").wT, D, Hp, EPI_F32, tr.dtmp, D));
@@ -441,16 +439,16 @@ int gtav_dit_train_backward_phases(gtav_dit* h, const float* v_pred, const float
         // r_{2i+1} = r_{2i} + gate_msa y1
         f16* const g_o = tn_dw ? tr.g_d2 : tr.g_d;   // (the fc2 weight gradient above still reads g_d when the grouped launch is deferred without copies)
         if (fuse_gate) {
-            RET_IF(to->gate_bwd_fused(tr.dres, b.y1, mb + 2 * D, MODW, NB, P, D, g_o, dmb + 2 * D, defer_bias ? nullptr : slot(P_ + "attn.to_out.bias").grad, ws_out, h->err_flag, s));
+            RET_IF(op->gate_bwd_fused(tr.dres, b.y1, mb + 2 * D, MODW, NB, P, D, g_o, dmb + 2 * D, defer_bias ? nullptr : slot(P_ + "attn.to_out.bias").grad, ws_out, h->err_flag, s));
         } else {
-            RET_IF(to->gate_bwd(tr.dres, mb + 2 * D, MODW, P, M, D, g_o, h->err_flag, s));
-            RET_IF(to->frame_reduce_gate(tr.dres, b.y1, NB, P, D, dmb + 2 * D, MODW, s));
-            RET_IF(to->colsum_tiled(g_o, M, D, slot(P_ + "attn.to_out.bias").grad, tr.red_ws, s));
+            RET_IF(op->gate_bwd(tr.dres, mb + 2 * D, MODW, P, M, D, g_o, h->err_flag, s));
+            RET_IF(op->frame_reduce_gate(tr.dres, b.y1, NB, P, D, dmb + 2 * D, MODW, s));
+            RET_IF(op->colsum_tiled(g_o, M, D, slot(P_ + "attn.to_out.bias").grad, tr.red_ws, s));
         }
         RET_IF(gemm_dw(g_o, D, b.ao, D, slot(P_ + "attn.to_out.weight").grad, 2));
         RET_IF(gemm_dx(g_o, slot(P_ + "attn.to_out.weight").wT, D, D, EPI_F16, tr.dao, D));
-        if (hf == 0) RET_IF(to->attn_spatial_bwd(b.q, b.k, b.v, tr.dao, NB, h->heads, P, D, h->rope_s.cs_dev, tr.g_qkv, h->err_flag, s));
-        else RET_IF(to->attn_temporal_bwd(b.q, b.k, tr.dao, B, P, D, T, h->maxT, h->rope_t.cs_dev, tr.g_qkv, h->err_flag, s));
+        if (hf == 0) RET_IF(op->attn_spatial_bwd(b.q, b.k, b.v, tr.dao, NB, h->heads, P, D, h->rope_s.cs_dev, tr.g_qkv, h->err_flag, s));
+        else RET_IF(op->attn_temporal_bwd(b.q, b.k, tr.dao, B, P, D, T, h->maxT, h->rope_t.cs_dev, tr.g_qkv, h->err_flag, s));
         RET_IF(gemm_dw(tr.g_qkv, 3 * D, b.xnA, D, slot(P_ + "attn.to_qkv.weight").grad, 3));
         if (defer_bias) {
             const float* wsv[3] = {ws_fc2, ws_out, ws_fc1};
@@ -467,9 +465,8 @@ int gtav_dit_train_backward_phases(gtav_dit* h, const float* v_pred, const float
     if (!(phase_begin <= L + 1 && L + 1 < phase_end)) return 0;
     // ---- phase L + 1: patch embedding: r_0 = xp W_pe^T + b_pe ----
     op = &h->ops(2 * L);
-    to = &h->tops(2 * L);
     RET_IF(launch_colsum_f32(tr.dres, D, M, D, slot("x_embedder.proj.bias").grad, tr.red_ws, s));
-    RET_IF(to->to_tiled(tr.dres, M, D, tr.g_d, h->err_flag, s));
+    RET_IF(op->to_tiled(tr.dres, M, D, tr.g_d, h->err_flag, s));
     {
         Slot& wpe = slot("x_embedder.proj.weight");
         GTAV_REQUIRE(wpe.C == h->Kpe, "train_backward: a patch embedding with padded K (%d of %d) is not implemented", wpe.C, h->Kpe);
@@ -532,7 +529,7 @@ int gtav_dit_adamw_step(gtav_dit* h, float lr, float beta1, float beta2, float e
     // Adam step count and its bias corrections live in ctl[4..6] and advance only with applied steps
     RET_IF(launch_clip_coef(tr.ctl, tr.sumsq_part, sumsq_parts(tr.grad_count), 1.0f / (tr.loss_scale * tr.grad_div), max_grad_norm, beta1, beta2, h->err_flag, s));
     // one launch: AdamW on every parameter + the 2-byte W / W^T operands of the GEMM weights rewritten from the updated masters (in the handle's operand type)
-    RET_IF(train_ops(tr.bf16).adamw_multi(tr.adam_params, tr.adam_items, tr.adam_n_items, tr.ctl, lr, beta1, beta2, eps, weight_decay, s));
+    RET_IF(operand_ops(tr.bf16).adamw_multi(tr.adam_params, tr.adam_items, tr.adam_n_items, tr.ctl, lr, beta1, beta2, eps, weight_decay, s));
     RET_IF(launch_add_f32(h->b_t2, h->b_ext, h->b_t2a, h->D, s));   // fused bias of c when actions are given (gtav_dit_finalize)
     h->prepared.valid = false;
     h->kvrec.valid = false;

@@ -13,6 +13,8 @@
 // the same kernels, tiles, layouts and launch heuristics with `f16` = __bf16 — v_mfma_f32_16x16x32_bf16, v_cvt_pk_bf16_f32 (round to nearest even),
 // v_dot2c_f32_bf16 — in a namespace of their own (the macro renames `gtav` for the whole translation unit).  api_dit.hip picks a set of launchers per half-block
 // (gtav_dit_set_operand_dtype / the automatic switch of gtav_dit_autorange); the fp16 objects are unchanged by this, bit for bit.
+// Every declaration that names `f16` (parameter structs, launcher prototypes) is ONE text, gemm_typed.inc / ops_typed.inc, read inside whichever namespace `gtav`
+// stands for and once more by the host code as namespace gtav_bf16 (ops_bf16.h, which also holds the one list of launchers dispatched per operand type).
 #ifdef GTAV_BF16_OPERANDS
 #define GTAV_F16_T __bf16
 #else
@@ -63,9 +65,17 @@ constexpr int WAVE = 64;
 // marker-packet overhead and agree with rocprofv3's kernel trace (round 6, gtav_timer_calibrate on a spin kernel of known device duration: the pair reads
 // device time + 0.60 us, rocprofv3 device time + 0.62 us — profiles/timer_calibration.json).
 }  // namespace gtav
-namespace gtav_shared { extern thread_local hipEvent_t g_launch_ev[2]; }   // one slot for the fp16 objects and their bf16 twins (defined in api.hip)
+// what the fp16 objects and their bf16 twins share, whatever the operand type: the profiler's event slot, the error string (both defined in api.hip) and PrefetchDesc
+namespace gtav_shared {
+extern thread_local hipEvent_t g_launch_ev[2];
+// ---- error plumbing (C-ABI functions never throw; they return an int and set this string) ----
+void set_error(const char* fmt, ...);
+const char* last_error();
+}  // namespace gtav_shared
 namespace gtav {
 using gtav_shared::g_launch_ev;
+using gtav_shared::set_error;
+using gtav_shared::last_error;
 #define GTAV_LAUNCH(kern, grid, block, shmem, stream, ...)                                                              \
     do {                                                                                                                \
         if (gtav_shared::g_launch_ev[0]) {                                                                                     \
@@ -75,10 +85,6 @@ using gtav_shared::g_launch_ev;
             hipLaunchKernelGGL(kern, grid, block, shmem, stream, __VA_ARGS__);                                          \
         }                                                                                                               \
     } while (0)
-
-// ---- error plumbing (C-ABI functions never throw; they return an int and set this string) ----
-void set_error(const char* fmt, ...);
-const char* last_error();
 
 #define GTAV_CHECK_HIP(expr)                                                              \
     do {                                                                                  \
@@ -131,11 +137,17 @@ __host__ __device__ __forceinline__ size_t tiled_off(int r, int k, int K) {
 // block from the same XCD's L2, 1.3 us from another XCD's / the Infinity Cache, 3.1 us from HBM), and the consumer's tile map gives XCD x a
 // contiguous eighth of its (K slice, row panel) order.  W is tile-major [rt row tiles of 128][nkt K tiles of 64] x 16 KiB; with `splitk` K
 // slices the XCDs split K first, then the row tiles (gemm.hip tile_map).  Speed only: nothing depends on where a block really runs.
+// (A member of GemmParams that does not name the operand type: ONE type for both namespaces.)
+}  // namespace gtav
+namespace gtav_shared {
 struct PrefetchDesc {
     const void* next;     // nullptr = off
     int rt, nkt, splitk;  // splitk >= 1, nkt % splitk == 0, splitk divides 8 or is a multiple of 8
     int kt_limit;         // > 0: only the first kt_limit K tiles of every (row tile, K slice) — what the consumer's prologue waits for; 0 = the whole slice
 };
+}  // namespace gtav_shared
+namespace gtav {
+using gtav_shared::PrefetchDesc;
 // The caller is thread `t` of the `nt` threads of the j-th of `nb` prefetching blocks of XCD `xcd`.  `sink` receives every load: keep it alive
 // (asm volatile("" :: "v"(sink))) until a later wait proves the loads returned, or until the wave ends.
 __device__ __forceinline__ void l2_prefetch_slice(const PrefetchDesc& d, int xcd, int j, int nb, int t, int nt, unsigned& sink) {

@@ -46,6 +46,25 @@ def test_product_library_has_no_experiment_knobs():
         assert "getenv(" not in text, f"{src}: raw getenv outside GTAV_ENV_INT"
 
 
+def test_operand_typed_declarations_are_one_unconditional_text():
+    """gemm_typed.inc / ops_typed.inc are read once per operand type (fp16 objects, bf16 twins, and both by the host code): a preprocessor directive there
+    could give two builds different structs or prototypes.  Every launcher of the per-operand-type list (ops_bf16.h) has its prototype in one of them."""
+    csrc = os.path.join(ROOT, "ai-generated-gtav_amd", "csrc")
+    texts = {n: open(os.path.join(csrc, n)).read() for n in ("gemm_typed.inc", "ops_typed.inc")}
+    for name, text in texts.items():
+        directives = [ln for ln in text.splitlines() if ln.lstrip().startswith("#")]
+        assert not directives, f"{name}: preprocessor directive in the shared declarations: {directives}"
+    both = "\n".join(texts.values())
+    for s in ("GemmParams", "GemmDwGroup", "LnPending", "AdamParam", "AdamItem"):
+        assert re.search(rf"\bstruct {s} \{{", both) and re.search(rf"static_assert\(sizeof\({s}\) == \d+,", both), s
+    hdr = open(os.path.join(csrc, "ops_bf16.h")).read()
+    listed = re.findall(r"^\s*F\((\w+), (\w+)\)", hdr[hdr.index("#define GTAV_OPERAND_OPS(F)"):], flags=re.M)
+    fields, launchers = [f for f, _ in listed], [fn for _, fn in listed]
+    assert len(listed) >= 24 and len(set(fields)) == len(listed) and len(set(launchers)) == len(listed), listed
+    for fn in launchers:
+        assert len(re.findall(rf"^int {fn}\(", both, flags=re.M)) == 1, f"{fn}: listed in GTAV_OPERAND_OPS but not declared (once) in a *_typed.inc"
+
+
 def test_cabi_argument_validation_without_gpu():
     """Entry points reject bad arguments before touching the device (no compute without a GPU)."""
     lib = L.load()
