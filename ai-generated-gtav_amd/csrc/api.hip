@@ -231,6 +231,19 @@ int gtav_op_attn_spatial_bwd_bf16(const void* q, const void* k, const void* vt, 
                                   const float* rope_cs, void* dqkv, void* stream) {
     return op_attn_spatial_bwd(true, q, k, vt, d_o, NB, heads, S, rope_cs, dqkv, stream);
 }
+static int op_attn_temporal_bwd(bool bf16, const void* q, const void* kv, const void* d_o, int32_t B, int32_t P, int32_t D, int32_t T, int32_t Tmax, const float* rope_cs,
+                                void* dqkv, void* stream) {
+    GTAV_REQUIRE(q && kv && d_o && rope_cs && dqkv, "op_attn_temporal_bwd: null argument");
+    return operand_ops(bf16).attn_temporal_bwd((const f16*)q, (const f16*)kv, (const f16*)d_o, B, P, D, T, Tmax, rope_cs, (f16*)dqkv, nullptr, (hipStream_t)stream);
+}
+int gtav_op_attn_temporal_bwd(const void* q, const void* kv, const void* d_o, int32_t B, int32_t P, int32_t D, int32_t T, int32_t Tmax,
+                              const float* rope_cs, void* dqkv, void* stream) {
+    return op_attn_temporal_bwd(false, q, kv, d_o, B, P, D, T, Tmax, rope_cs, dqkv, stream);
+}
+int gtav_op_attn_temporal_bwd_bf16(const void* q, const void* kv, const void* d_o, int32_t B, int32_t P, int32_t D, int32_t T, int32_t Tmax,
+                                   const float* rope_cs, void* dqkv, void* stream) {
+    return op_attn_temporal_bwd(true, q, kv, d_o, B, P, D, T, Tmax, rope_cs, dqkv, stream);
+}
 int gtav_op_gemm_tn(const void* x, const void* w, int32_t M, int32_t N, int32_t K, float* out, int32_t ldo, void* stream) {
     GemmParams q;
     memset(&q, 0, sizeof(q));

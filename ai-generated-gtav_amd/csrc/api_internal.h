@@ -356,6 +356,7 @@ struct gtav_dit {
     struct Train {
         bool on = false, have_fwd = false, have_actions = false;
         bool bf16 = false;                  // every operand group bf16 (gtav_dit_train_enable_typed): no group may change its type while training is on
+        int window = 8;                     // frames a training handle may be sized for (gtav_dit_train_allow_window raises it to at most 32)
         int B = 0, T = 0, M = 0, Mp = 0, rows = 0;
         float loss_scale = 65536.0f;        // (1 on a bf16 handle)
         float grad_div = 1.0f;              // the arena holds the sum over this many ranks (gtav_dit_set_grad_divisor)

@@ -11,8 +11,14 @@ static int g_dw_tn = GTAV_ENV_INT("GTAV_DW_TN", 1);             // experiments b
 // gtav_dit_train_enable after its operand-type checks: trainable slots, fp32 masters, AdamW state, saved-activation and backward workspace
 static int train_enable_body(gtav_dit* h, float* grad_arena_dev, int64_t grad_arena_numel);
 
-// The training step serves windows of at most 8 frames: refused by name before anything on the handle is allocated or changed.
+// The training step serves windows of at most 8 frames unless the caller opted in to longer ones (gtav_dit_train_allow_window): refused by name before anything on
+// the handle is allocated or changed.
 static int train_window_ok(const gtav_dit* h) {
+    if (h->tr.window > 8) {
+        GTAV_REQUIRE(h->maxT <= h->tr.window, "train_enable: gtav_dit_train_allow_window allowed training windows of at most %d frames on this handle; it was created "
+                     "with max_frames=%d", h->tr.window, h->maxT);
+        return 0;
+    }
     GTAV_REQUIRE(h->maxT <= 8, "train_enable: training is implemented for windows of at most 8 frames (the backward temporal attention and the adaLN-gradient "
                  "reduction are sized for it); this handle was created with max_frames=%d", h->maxT);
     return 0;
@@ -29,6 +35,15 @@ extern "C" {
 // gtav_dit_train_enable_typed(.., GTAV_OPERAND_BF16) runs the same step on bf16 operands (the reference's own autocast type): every launch below that
 // reads or writes a 2-byte tensor goes through the operand group's launcher set (h->ops(g): ops_bf16.h OperandOps), the twins of the same kernels.
 // ================================================================================================
+// Opt-in to training windows of up to max_frames <= 32 frames (the default, 8, is what train_window_ok otherwise enforces): between create and train_enable only.
+int gtav_dit_train_allow_window(gtav_dit* h, int32_t max_frames) {
+    GTAV_REQUIRE(h, "train_allow_window: null handle");
+    GTAV_REQUIRE(!h->tr.on, "train_allow_window: training is already enabled on this handle (call it between gtav_dit_create and gtav_dit_train_enable)");
+    GTAV_REQUIRE(max_frames >= 8 && max_frames <= 32, "train_allow_window: max_frames=%d outside [8, 32]", max_frames);
+    h->tr.window = max_frames;
+    return 0;
+}
+
 int gtav_dit_train_enable(gtav_dit* h, float* grad_arena_dev, int64_t grad_arena_numel) {
     GTAV_REQUIRE(h, "train_enable: null handle");
     RET_IF(train_window_ok(h));

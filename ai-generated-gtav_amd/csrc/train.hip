@@ -1237,6 +1237,121 @@ __global__ __launch_bounds__(256) void attn_temporal_bwd_kernel(const f16* __res
     sat_report(amax, err_flag);
 }
 
+// The same backward for windows of 9 .. 32 frames (runtime T): the T x T problem of an item no longer fits the registers of its 16 lanes, so q / dO / k / v
+// are streamed from memory (an item's 4 T rows of 128 bytes stay in L2) in two passes over the same thread map, loads, RoPE^T and saturating stores:
+//   1. queries t ascending: q_t / dO_t once, the scores and dP of keys s <= t go to LDS (a runtime-indexed register array would go to scratch, and key loops
+//      unrolled to 32 cost 252 VGPRs), softmax in the resident kernel's arithmetic and order, dq_t accumulated over s ascending and stored; the row maximum,
+//      1 / row sum and sum_s P dP of query t are kept in LDS for pass 2 (16 items x 32 queries x 16 bytes).
+//   2. keys s ascending: k_s / v_s once, P and dS of queries t >= s recomputed from those statistics, dk_s / dv_s accumulated over t ascending and stored.
+// Every output element is accumulated by one lane group in one fixed order: no atomics, launches are bit-repeatable.  Lanes of items past B P heads stay
+// alive for the shuffles on the last item's (in-bounds) addresses and store nothing; cache frames at or beyond T are never read.
+__global__ __launch_bounds__(256) void attn_temporal_bwd_stream_kernel(const f16* __restrict__ q, const f16* __restrict__ kv, const f16* __restrict__ dO, int B,
+                                                                       int P, int D, int T, int Tmax, const float* __restrict__ rope_cs,
+                                                                       f16* __restrict__ dqkv, int* err_flag) {
+    constexpr int TS = 32;                       // the largest window (launch_attn_temporal_bwd checks T <= TS)
+    __shared__ f32x4 stat[16][TS];               // per item of the block and query: row maximum, 1 / row sum, sum_s P dP
+    __shared__ float row[16][TS][2];             // per item of the block, the query in hand: score (then exp(score - max)) and dP of every key
+    const int heads = D >> 6;
+    const int gidx = (int)(((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4), l = threadIdx.x & 15, grp = threadIdx.x >> 4;
+    const int items = B * P * heads;
+    const bool valid = gidx < items;
+    const int it = valid ? gidx : items - 1;
+    const int head = it % heads, p = (it / heads) % P, b = it / (heads * P);
+    const int col = head * 64 + 4 * l;
+    const f16* const qb = q + (((size_t)b * T) * P + p) * D + col;            // row t of the item: + t * rs
+    const f16* const gb = dO + (((size_t)b * T) * P + p) * D + col;
+    const f16* const kb = kv + (((size_t)b * Tmax) * P + p) * 2 * D + col;    // k of frame s: + s * cs, v: + D behind it
+    const size_t rs = (size_t)P * D, cs = (size_t)P * 2 * D;
+    auto ld4 = [](const f16* a, float (&o)[4]) {
+        const f16x4 x = *(const f16x4*)a;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = (float)x[e];
+    };
+    auto dot16 = [&](const float (&a)[4], const float (&b2)[4]) {
+        float s = (a[0] * b2[0] + a[1] * b2[1]) + (a[2] * b2[2] + a[3] * b2[3]);
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        return s;
+    };
+    // RoPE^T of a dq / dk row of frame t
+    auto unrope = [&](const float (&a)[4], int t, float (&o)[4]) {
+        const f32x4 c = *(const f32x4*)(rope_cs + (size_t)t * 64 + 4 * l);
+        o[0] = a[0] * c[0] + a[1] * c[1]; o[1] = a[1] * c[0] - a[0] * c[1];
+        o[2] = a[2] * c[2] + a[3] * c[3]; o[3] = a[3] * c[2] - a[2] * c[3];
+    };
+    float amax = 0.f;
+    // ---- pass 1: queries ----
+    for (int t = 0; t < T; ++t) {
+        float qv[4], go[4], mx = -INFINITY;
+        ld4(qb + t * rs, qv);
+        ld4(gb + t * rs, go);
+        for (int s = 0; s <= t; ++s) {
+            float kk[4], vv[4];
+            ld4(kb + s * cs, kk);
+            ld4(kb + s * cs + D, vv);
+            const float sc = dot16(qv, kk) * 0.125f, dp = dot16(go, vv);   // (the same bits in all 16 lanes of the item)
+            mx = fmaxf(mx, sc);
+            if (l == 0) { row[grp][s][0] = sc; row[grp][s][1] = dp; }
+        }
+        __builtin_amdgcn_wave_barrier();
+        float sum = 0.f;
+        for (int s = 0; s <= t; ++s) {
+            const float e = __expf(row[grp][s][0] - mx);
+            sum += e;
+            if (l == 0) row[grp][s][0] = e;
+        }
+        __builtin_amdgcn_wave_barrier();
+        const float inv = 1.0f / sum;
+        float dsum = 0.f;
+        for (int s = 0; s <= t; ++s) {
+            dsum += (row[grp][s][0] * inv) * row[grp][s][1];
+        }
+        float dq[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int s = 0; s <= t; ++s) {
+            float kk[4];
+            ld4(kb + s * cs, kk);
+            const float ds = (row[grp][s][0] * inv) * (row[grp][s][1] - dsum) * 0.125f;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) dq[e] += ds * kk[e];
+        }
+        __builtin_amdgcn_wave_barrier();   // (the next query's scores overwrite row[grp])
+        if (l == 0) stat[grp][t] = f32x4{mx, inv, dsum, 0.f};
+        if (valid) {
+            float o[4];
+            unrope(dq, t, o);
+            *(f16x4*)(dqkv + tiled_off((int)(((size_t)b * T + t) * P + p), col, 3 * D)) = sat4(o[0], o[1], o[2], o[3], amax);
+        }
+    }
+    __syncthreads();   // (the statistics of an item are written and read by its own 16 lanes only; every thread of the block is alive)
+    // ---- pass 2: keys ----
+    for (int s = 0; s < T; ++s) {
+        float kk[4], vv[4], dk[4] = {0.f, 0.f, 0.f, 0.f}, dv[4] = {0.f, 0.f, 0.f, 0.f};
+        ld4(kb + s * cs, kk);
+        ld4(kb + s * cs + D, vv);
+        for (int t = s; t < T; ++t) {
+            float qv[4], go[4];
+            ld4(qb + t * rs, qv);
+            ld4(gb + t * rs, go);
+            const f32x4 st = stat[grp][t];
+            const float pr = __expf(dot16(qv, kk) * 0.125f - st[0]) * st[1];
+            const float ds = pr * (dot16(go, vv) - st[2]) * 0.125f;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                dk[e] += ds * qv[e];
+                dv[e] += pr * go[e];
+            }
+        }
+        if (valid) {
+            const int m = (int)(((size_t)b * T + s) * P + p);
+            float o[4];
+            unrope(dk, s, o);
+            *(f16x4*)(dqkv + tiled_off(m, D + col, 3 * D)) = sat4(o[0], o[1], o[2], o[3], amax);
+            *(f16x4*)(dqkv + tiled_off(m, 2 * D + col, 3 * D)) = sat4(dv[0], dv[1], dv[2], dv[3], amax);
+        }
+    }
+    sat_report(amax, err_flag);
+}
+
 // ------------------------------------------------------------------------------------------------------------------------
 // fp32 conditioning path (tens of rows): SiLU, the two small GEMM forms of a Linear's backward, and the adaLN mega-projection.
 // ------------------------------------------------------------------------------------------------------------------------
@@ -1831,9 +1946,15 @@ int launch_attn_spatial_bwd(const f16* Q, const f16* K, const f16* Vt, const f16
 }
 int launch_attn_temporal_bwd(const f16* q, const f16* kv, const f16* dO, int B, int P, int D, int T, int Tmax, const float* rope_cs, f16* dqkv, int* err_flag,
                              hipStream_t stream) {
-    GTAV_REQUIRE(T >= 1 && T <= 8 && T <= Tmax && D % 64 == 0, "attn_temporal_bwd: T=%d", T);
+    GTAV_REQUIRE(T >= 1 && T <= 32 && T <= Tmax, "attn_temporal_bwd: a window of T=%d frames (1 .. 32, and at most the cache's Tmax=%d)", T, Tmax);
+    GTAV_REQUIRE(B >= 1 && P >= 1 && D >= 64 && D % 64 == 0 && (size_t)B * P * (D / 64) <= (size_t)1 << 27, "attn_temporal_bwd: B=%d P=%d D=%d", B, P, D);
     const size_t threads = (size_t)B * P * (D / 64) * 16;
     const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
+    if (T > 8) {   // the streaming kernel; T <= 8 stays on the register-resident kernel below, bit for bit
+        hipLaunchKernelGGL(attn_temporal_bwd_stream_kernel, grid, block, 0, stream, q, kv, dO, B, P, D, T, Tmax, rope_cs, dqkv, err_flag);
+        GTAV_CHECK_HIP(hipGetLastError());
+        return 0;
+    }
 #define GTAV_TB(TT) case TT: hipLaunchKernelGGL(attn_temporal_bwd_kernel<TT>, grid, block, 0, stream, q, kv, dO, B, P, D, Tmax, rope_cs, dqkv, err_flag); break
     switch (T) { GTAV_TB(1); GTAV_TB(2); GTAV_TB(3); GTAV_TB(4); GTAV_TB(5); GTAV_TB(6); GTAV_TB(7); GTAV_TB(8); }
 #undef GTAV_TB

@@ -70,6 +70,7 @@ SIGNATURES = {
     "gtav_dit_get_operand_dtype": [_p, _i, C.POINTER(C.c_int32)],
     "gtav_dit_autorange": [_p, C.POINTER(C.c_int32), _p],
     "gtav_dit_train_param_count": [_p, C.POINTER(C.c_int64)],
+    "gtav_dit_train_allow_window": [_p, _i],
     "gtav_dit_train_enable": [_p, _p, _l],
     "gtav_dit_train_enable_typed": [_p, _p, _l, _i],
     "gtav_dit_set_loss_scale": [_p, _f],
@@ -137,6 +138,8 @@ SIGNATURES = {
     "gtav_op_gemm_dw_grouped": [_i, _p, _p, _p, _p, _p, _p, _i, _p],
     "gtav_op_attn_spatial_bwd": [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p],
     "gtav_op_attn_spatial_bwd_bf16": [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p],
+    "gtav_op_attn_temporal_bwd": [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p],
+    "gtav_op_attn_temporal_bwd_bf16": [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p],
     "gtav_op_gemm_qkvt_attn": [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p],
     "gtav_op_qkv_head_major_spatial": [_p, _p, _i, _p],
     "gtav_op_gemm_qkvs_attn": [_p, _p, _i, _i, _i, _p, _p, _p],

@@ -138,7 +138,7 @@ class _HipModule:
 
 
 MAX_FRAMES = 32        # gtav_dit_create's range (include/gtav_amd.h gtav_dit_config.max_frames)
-TRAIN_MAX_FRAMES = 8   # gtav_dit_train_enable's
+TRAIN_MAX_FRAMES = 8   # gtav_dit_train_enable's default; DiT(train_max_frames=n) raises it to n <= MAX_FRAMES (gtav_dit_train_allow_window)
 
 
 class DiT(_HipModule):
@@ -149,9 +149,18 @@ class DiT(_HipModule):
 
     def __init__(self, input_h=18, input_w=32, patch_size=2, in_channels=16, hidden_size=1024, depth=12, num_heads=16,
                  mlp_ratio=4.0, external_cond_dim=25, max_frames=5, *, max_batch=1, init_weights=True, trainable=False, range_policy="report",
-                 train_dtype=torch.float16):
+                 train_dtype=torch.float16, train_max_frames=None):
         super().__init__()
         self._trainable = bool(trainable)    # keyword-only, not in the reference: keeps fp32 masters, gradients and AdamW state on the GPU
+        # opt-in to training windows of up to train_max_frames frames (include/gtav_amd.h gtav_dit_train_allow_window); None: TRAIN_MAX_FRAMES.  The saved
+        # activations are sized by max_batch x min(max_frames, train_max_frames): about 1.3 MB per token for DiT-S/2, 6 GB for one 32-frame sample
+        if train_max_frames is not None:
+            if not TRAIN_MAX_FRAMES <= int(train_max_frames) <= MAX_FRAMES:
+                raise ValueError(f"train_max_frames={train_max_frames}: the training step serves windows of {TRAIN_MAX_FRAMES} to {MAX_FRAMES} frames")
+            if not self._trainable:
+                raise ValueError("train_max_frames needs trainable=True (an inference model serves windows of up to max_frames as it is)")
+            train_max_frames = int(train_max_frames)
+        self._train_max_frames = train_max_frames
         # operand type of the training step (include/gtav_amd.h gtav_dit_train_enable_typed): torch.bfloat16 is the reference's `--mixed_precision bf16`
         # (fp32 range, no loss scaling needed), torch.float16 the default (loss-scaled)
         if train_dtype not in (torch.float16, torch.bfloat16):
@@ -174,7 +183,7 @@ class DiT(_HipModule):
                                 hidden_size=hidden_size, depth=depth, num_heads=num_heads, mlp_ratio=mlp_ratio,
                                 external_cond_dim=external_cond_dim)
         # a trainable handle is never sized beyond the window the training step implements: _ensure refuses longer ones by name
-        self._capacity_b, self._capacity_t = max_batch, min(max(max_frames, 1), TRAIN_MAX_FRAMES if self._trainable else MAX_FRAMES)
+        self._capacity_b, self._capacity_t = max_batch, min(max(max_frames, 1), self._train_window if self._trainable else MAX_FRAMES)
         self._capacity_rows = 0
         hd = hidden_size // num_heads
         self._spatial_freqs = _w.rope_freqs_pixel(hd // 2, 256)   # model/dit.py:259-261
@@ -190,6 +199,11 @@ class DiT(_HipModule):
         if init_weights:
             self.initialize_weights()
 
+    @property
+    def _train_window(self):
+        """Longest window the training step of this model serves: TRAIN_MAX_FRAMES unless train_max_frames opted in to more."""
+        return TRAIN_MAX_FRAMES if self._train_max_frames is None else self._train_max_frames
+
     # `max_frames` is read AND assigned by callers (generate.py:139,204)
     @property
     def max_frames(self):
@@ -200,7 +214,7 @@ class DiT(_HipModule):
         if int(v) > MAX_FRAMES:   # before the handle is touched: the model stays as it was
             raise ValueError(f"max_frames={int(v)}: the temporal attention serves windows of at most {MAX_FRAMES} frames")
         self._max_frames = int(v)
-        cap = min(int(v), TRAIN_MAX_FRAMES) if self._trainable else int(v)
+        cap = min(int(v), self._train_window) if self._trainable else int(v)
         if cap > self._capacity_t:
             if self._handle and self._trainable and self._grads is not None:
                 raise RuntimeError("a trainable DiT cannot grow its window after training was enabled: construct it with the largest max_frames")
@@ -242,7 +256,10 @@ class DiT(_HipModule):
         # window limits first, before a handle is rebuilt or destroyed
         if T > MAX_FRAMES:
             raise ValueError(f"a window of {T} frames: the temporal attention serves at most {MAX_FRAMES} (max_frames <= {MAX_FRAMES})")
-        if self._trainable and T > TRAIN_MAX_FRAMES:
+        if self._trainable and self._train_max_frames is not None and T > self._train_max_frames:
+            raise ValueError(f"a window of {T} frames on a trainable DiT constructed with train_max_frames={self._train_max_frames}: the handle's saved "
+                             f"activations are sized for at most {self._train_max_frames} frames (train_max_frames <= {MAX_FRAMES})")
+        if self._trainable and self._train_max_frames is None and T > TRAIN_MAX_FRAMES:
             raise ValueError(f"a window of {T} frames on a trainable DiT: the training step (backward temporal attention, adaLN-gradient reduction) is "
                              f"implemented for at most {TRAIN_MAX_FRAMES} frames; windows up to {MAX_FRAMES} need trainable=False")
         grow = (cond_rows > max(self._capacity_rows, self._capacity_b * self._capacity_t)) or T > self._capacity_t or B > self._capacity_b
@@ -277,6 +294,8 @@ class DiT(_HipModule):
                     _lib.check(L.gtav_dit_train_param_count(self._handle, C.byref(n)))
                     # one contiguous fp32 gradient arena owned by torch: a single all-reduce covers the whole model (train.py)
                     self._grads = torch.zeros(n.value, device=self.device, dtype=torch.float32)
+                    if self._train_max_frames is not None:
+                        _lib.check(L.gtav_dit_train_allow_window(self._handle, self._train_max_frames))
                     if self._train_bf16:
                         _lib.check(L.gtav_dit_train_enable_typed(self._handle, self._grads.data_ptr(), n.value, 1))
                     else:

@@ -184,7 +184,14 @@ int gtav_timer_calibrate(int32_t spin_us, int32_t reps, double* event_us_mean, d
  *                       mixed groups is refused).  Forward, backward and the optimizer's rewrite of the W / W^T operand images all run on bf16 operands
  *                       (fp32 range: no activation or gradient store saturates, so the error word's saturation bit is never raised by a finite value; a
  *                       non-finite gradient norm or store still skips the step).  The loss scale starts at 1 (the reference runs bf16 without a scaler);
- *                       gtav_dit_set_loss_scale still applies.  gtav_dit_set_operand_dtype on such a handle accepts bf16 (nothing to do) and refuses fp16. */
+ *                       gtav_dit_set_loss_scale still applies.  gtav_dit_set_operand_dtype on such a handle accepts bf16 (nothing to do) and refuses fp16.
+ * Training window: by default gtav_dit_train_enable[_typed] refuses a handle created with max_frames > 8.  gtav_dit_train_allow_window(h, n), 8 <= n <= 32,
+ * called between gtav_dit_create and gtav_dit_train_enable[_typed] (it fails afterwards), raises that limit to n frames for this handle: the backward temporal
+ * attention then runs its streaming kernel on windows of 9 .. 32 frames (gtav_op_attn_temporal_bwd) and the adaLN-gradient reduction its general kernel above 80
+ * conditioning rows (max_batch x max_frames); windows of <= 8 frames run the same kernels and give the same bits as on a default handle.  What it costs: the saved
+ * activations are sized by max_batch x max_frames at enable time, about 1.3 MB per token for DiT-S/2, i.e. about 6 GB for ONE 32-frame sample of
+ * 144 tokens per frame.  The call itself allocates nothing. */
+int gtav_dit_train_allow_window(gtav_dit* h, int32_t max_frames);
 int gtav_dit_train_param_count(gtav_dit* h, int64_t* numel);
 int gtav_dit_train_enable(gtav_dit* h, float* grad_arena_dev, int64_t grad_arena_numel);
 int gtav_dit_train_enable_typed(gtav_dit* h, float* grad_arena_dev, int64_t grad_arena_numel, int32_t dtype);
@@ -384,6 +391,18 @@ int gtav_op_attn_spatial_bwd(const void* q_dev, const void* k_dev, const void* v
                              int32_t S, const float* rope_cs_dev, void* dqkv_dev, void* stream);
 int gtav_op_attn_spatial_bwd_bf16(const void* q_dev, const void* k_dev, const void* vt_dev, const void* d_o_dev, int32_t NB, int32_t heads,
                                   int32_t S, const float* rope_cs_dev, void* dqkv_dev, void* stream);
+/* Backward of the causal temporal attention (model/attention.py:41-71) for B x P x (D / 64) (sample, position, head) items of T frames: q [B T P][D] row-major
+ * (row (b T + t) P + p, RoPE applied), kv = the temporal cache [B][Tmax][P][2][D] (k with RoPE, v; the ROW index uses T, the cache slot Tmax), d_o row-major
+ * [B T P][D], rope_cs = the temporal table [>= T][32][cos, sin]; writes the gradient of the to_qkv output, tile-major logical [B T P][3 D] (dq | dk | dv, dq / dk
+ * rotated back through row t of the table).  1 <= T <= 8 runs the kernel that keeps an item's whole T x T problem in registers, 9 <= T <= 32 the streaming kernel
+ * (a query pass that keeps three softmax statistics per query in LDS, then a key pass that recomputes the probabilities from them); T > 32 or T > Tmax is refused.
+ * Both are free of atomics: two launches give the same bits, and an item's result does not depend on B.  Nothing at or beyond frame T of the cache, or behind row
+ * B T P of q / d_o, is read.  Like the spatial pair, the kernel-level entry runs without an error word: stores saturate at the operand type's largest finite value,
+ * unreported (the training step passes the handle's error word).  The _bf16 form takes bf16 q / kv / d_o and writes bf16 (the training step of a bf16 handle). */
+int gtav_op_attn_temporal_bwd(const void* q_dev, const void* kv_dev, const void* d_o_dev, int32_t B, int32_t P, int32_t D, int32_t T, int32_t Tmax,
+                              const float* rope_cs_dev, void* dqkv_dev, void* stream);
+int gtav_op_attn_temporal_bwd_bf16(const void* q_dev, const void* kv_dev, const void* d_o_dev, int32_t B, int32_t P, int32_t D, int32_t T, int32_t Tmax,
+                                   const float* rope_cs_dev, void* dqkv_dev, void* stream);
 /* Weight-gradient GEMM (train_dit.py:680 accelerator.backward, the dW = dY^T X of every Linear): out[m][n] += sum_t x[t][m] * w[t][n] with
  * both operands the ordinary tile-major fp16 activations [K tokens][features] (x: M features, w: N features); out f32 row-major [M][ldo],
  * accumulated in place.  M, N multiples of 128, K a multiple of 64. */

@@ -2,7 +2,9 @@
 (e.g. GTAV_DW_TN=0: transposed operand copies in front of the grouped weight-gradient launch; GTAV_DW_GROUPED=0).  One configuration per process: run it
 twice in one job for an A/B on one box.   Usage (GPU box): GTAV_DW_TN=0 python tools/train_step_time.py [--steps 8] [--batch 16]
 --dtype fp16 | bf16: the operand type of the training step (DiT(train_dtype=...)) on the PRODUCT library instead (no GTAV_* overrides there): the fp16 / bf16
-A/B of profiles/round7/train_step_bf16_ab.txt."""
+A/B of profiles/round7/train_step_bf16_ab.txt.
+--frames N: clips of N frames whose one target frame sees a window of N frames (default 5); above 8 the model is constructed with train_max_frames=N
+(profiles/long_window_train/: batch 8 x 8, 4 x 16 and 2 x 32 frames, 9 216 tokens each)."""
 import argparse
 import json
 import os
@@ -20,6 +22,7 @@ def main():
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--latent-hw", type=int, nargs=2, default=[18, 32], help="latent height and width (36 64: 576 tokens per frame)")
+    ap.add_argument("--frames", type=int, default=5, help="frames per clip = the window of the step (above 8: DiT(train_max_frames=frames))")
     ap.add_argument("--dtype", choices=("fp16", "bf16"), default=None, help="operand type of the training step, on the product library")
     a = ap.parse_args()
     if a.dtype is None:
@@ -33,21 +36,22 @@ def main():
     B = a.batch
     train_dtype = torch.bfloat16 if a.dtype == "bf16" else torch.float16
     LH, LW = a.latent_hw
+    F = a.frames
     from gtav_amd.model.dit import DiT
-    dit = DiT(input_h=LH, input_w=LW, patch_size=2, hidden_size=1024, depth=16, num_heads=16, max_frames=5, init_weights=False, max_batch=B, trainable=True,
-              train_dtype=train_dtype)   # DiT-S/2 at the given latent size
+    dit = DiT(input_h=LH, input_w=LW, patch_size=2, hidden_size=1024, depth=16, num_heads=16, max_frames=F, init_weights=False, max_batch=B, trainable=True,
+              train_dtype=train_dtype, train_max_frames=F if F > 8 else None)   # DiT-S/2 at the given latent size
     dit.load_state_dict(W.synth_state_dict(W.dit_param_shapes(depth=16, input_h=LH, input_w=LW), seed=0))
     g = torch.Generator().manual_seed(7)
-    lat = (torch.randn(B, 5, 16, LH, LW, generator=g) * 0.5).to(dev)
-    actions = torch.zeros(B, 5, 25, device=dev)
+    lat = (torch.randn(B, F, 16, LH, LW, generator=g) * 0.5).to(dev)
+    actions = torch.zeros(B, F, 25, device=dev)
     actions[:, :, 3] = 1
     tgt = torch.randint(1, 51, (B,), generator=g)
     ctx = torch.randint(1, 41, (B,), generator=g)
-    ctx_noise = torch.randn(B, 4, 16, LH, LW, generator=g).to(dev)
+    ctx_noise = torch.randn(B, F - 1, 16, LH, LW, generator=g).to(dev)
     noise = torch.randn(B, 1, 16, LH, LW, generator=g).to(dev)
 
     def step():
-        return training_step(dit, lat, actions, tgt, ctx, ctx_noise, noise, lr=1e-5, weight_decay=0.01, max_grad_norm=1.0, world_size=1)
+        return training_step(dit, lat, actions, tgt, ctx, ctx_noise, noise, lr=1e-5, weight_decay=0.01, max_grad_norm=1.0, world_size=1, n_prompt_frames=F - 1)
 
     for _ in range(3):
         step()
@@ -58,7 +62,7 @@ def main():
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / a.steps * 1e3
     applied, skipped, gnorm = dit.train_stats()
-    print(json.dumps({"batch": B, "latent_hw": [LH, LW], "dtype": a.dtype or "fp16 (experiments library)", "ms_per_step": round(ms, 3), "loss": float(loss), "grad_norm": gnorm, "skipped": skipped,
+    print(json.dumps({"batch": B, "frames": F, "latent_hw": [LH, LW], "dtype": a.dtype or "fp16 (experiments library)", "ms_per_step": round(ms, 3), "loss": float(loss), "grad_norm": gnorm, "skipped": skipped,
                       "env": {k: v for k, v in os.environ.items() if k.startswith("GTAV_")}}))
 
 
