@@ -1,8 +1,14 @@
 // Laboratory half of gemm.hip: compiled ONLY into libgtav_amd_exp.so (csrc/build.sh exp, -DGTAV_EXPERIMENTS), included by gemm.hip right in front of
 // launch_epi.  Everything here measured slower than what launch_gemm's heuristic picks and is kept for A/B runs of the tools under tools/ (forced block
-// shapes, GTAV_* environment overrides): the persistent ping-pong kernel of round 2 (shape 16), and the block shapes 8 / 9 (96-wide tiles of round 1),
-// 21 / 23 / 25 / 27 / 28 (loader-wave variants), 30 / 32 / 33 (persistent loader-wave variants), 40 / 41 (persistent 256-token tiles with a K split of the remainder, round 4) and 42 (256 x 256 persistent tile on sixteen waves in two groups).
-// The product library (libgtav_amd.so) contains none of it and refuses these shape numbers.
+// shapes, GTAV_* environment overrides):
+//   * kernels of their own: the persistent 256-token tiles with a K split of the remainder (gemm_p256_kernel, shapes 40 / 41, round 4), the persistent ping-pong
+//     kernel (gemm_pp_kernel, shape 16, round 2), the 256 x 256 persistent tile on sixteen waves in two groups (gemm_s16_kernel, shape 42), the antiphase
+//     256 x 256 main loop (mainloop256_pp / gemm256_pp_kernel, shape 17, round 6) and the loader-wave kernel with the weight operand straight into registers
+//     (mainloop_lw / gemm_lw_kernel / launch_lw, shapes 22 / 18, round 6);
+//   * further instantiations of the product's kernels: 8 / 9 (96-wide tiles of round 1), 21 / 23 / 25 / 27 / 28 (loader-wave variants), 30 / 32 / 33 (persistent
+//     loader-wave variants).
+// launch_experiment_shape, at the end, is the one hook launch_epi calls.  The product library (libgtav_amd.so) contains none of it and refuses these seventeen
+// shape numbers in one place (launch_epi).
 #pragma once
 namespace {
 // ---------------------------------------------------------------------------------------------------------------------
@@ -732,8 +738,13 @@ __global__ __launch_bounds__(1024, 1) void gemm_pp_kernel(GemmParams p) {
 
 
 
-// ---- launcher of the ping-pong kernel ----
 } // namespace
+// ---- launcher of the ping-pong kernel ----
+// Round-2 measurement (profiles/round2/pp_stamps_v1.txt): correct and bit-identical to the one-shot kernels, the overlap works (MAIN
+// phases run back to back), but with only 8 of the 16 waves computing, a K-step costs 1.15-1.25 us against 0.68 us of fill time: the
+// barrier-synchronised waves serialise into fill / read / MFMA phases, where two independent co-resident blocks interleave them.
+// fc1 at M = 5760: 71-76 us against 57 us for shape 12.  Not selected by the heuristic (GTAV_PP=1 in the experiments build or a
+// forced shape 16 run it); the de-phased shape 12 above gets the same overlap with 16 computing waves.
 static int g_pp_enable = GTAV_ENV_INT("GTAV_PP", 0);
 bool gemm_pp_ok(int M, int N, int K, int epi) {
     if (!(epi == EPI_GELU_TANH || epi == EPI_GELU_ERF || epi == EPI_QKV || epi == EPI_RESID)) return false;
@@ -1083,7 +1094,436 @@ static int launch_s16(const GemmParams& p, hipStream_t stream) {
     return 0;
 }
 
-// Block shapes of the experiments build.  `handled` = the shape was one of them (rc is the launch's status).
+// ---- antiphase 256 x 256 main loop (shape 17) ----
+// The same 256 x 256 tile, LDS image, fill schedule and accumulator layout as mainloop256, run as TWO WAVE GROUPS IN ANTIPHASE (round 6; cdna_hip_programming.md
+// "The 256^2 8-phase template"): waves 0-3 and waves 4-7 — one wave of each group per SIMD — execute the same phase sequence one barrier interval apart, so that on
+// every SIMD one wave issues its 16 MFMAs of a phase (s_setprio 1) while its partner issues the fragment reads and the LDS-DMA fills of its next phase and waits for
+// the reads to land.  In the lockstep loop both waves of a SIMD reach their reads at the same time and the matrix pipe waits out the LDS round trip with them
+// (docs/LABNOTES.md 4.11: reads + MFMAs without fills 1.18 us per K-tile against 0.77 us of MFMA issue); here that latency and the address-pipe time of a fill
+// (a wave that issues an LDS-DMA instruction is held until the pipe accepts it) lie under the partner's MFMAs.  Price: two barriers per phase.
+//   phase p of a wave:   [L]  fill one half-tile | fragment reads of the phase | (phase 4: counted vmcnt) | lgkmcnt(0) | barrier
+//                        [M]  16 MFMAs                                                                                | barrier
+//   K-tile t (parity b):  L1 W0(t+1) | wa (W rows 0-63: 8 reads), xa (tokens 0-31: 4)     M1 wa x xa
+//                         L2 W1(t+1) | xb (tokens 32-63: 4)                               M2 wa x xb
+//                         L3 X0(t+2) | wb (W rows 64-127: 8)                              M3 wb x xb
+//                         L4 X1(t+2) | vmcnt(4): all but X0 / X1(t+2) landed              M4 wb x xa
+// Group 1 starts one barrier late and group 0 ends one barrier late: barrier instance k closes group 0's section k and group 1's section k - 1.
+// WAR: a slot is refilled at least one barrier after every wave's last read of it HAS RETURNED — the lgkmcnt(0) stands in FRONT of the barrier that ends a read section
+// (X slots of parity b: last read L2(t), refilled L3(t) by group 0 while group 1 is in M2(t), its L2 reads retired before the barrier between; W slots: last read
+// L3(t), refilled L1(t+1)).  RAW: a wave reads K-tile t+1 (from L1(t+1) on) only behind BOTH groups' vmcnt(4) of L4(t): group 0's own stands two barriers back, group
+// 1's one barrier back (its L4(t) ends at the barrier that ends group 0's M4(t)); group 1 reads after group 0's by construction.  LDS-DMA data is ordered for a
+// ds_read by exactly that: the issuing wave's counted vmcnt, then a barrier the reader has passed (MI355X_MICROARCH.md).
+template <bool TR, typename AfterPrologue>
+__device__ __forceinline__ void mainloop256_pp(const GemmParams& p, char* smem, int n0, int m0, int kt0, int nkt,
+                                               f32x4 (&acc)[8][4], BlockStamps& bs, AfterPrologue after_prologue) {
+    constexpr int PAR = 4 * TILE_BYTES;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wn = w & 1, wm = w >> 1;
+    const bool late = w >= 4;                        // group 1: one barrier interval behind group 0
+    const int nktot = p.K / TK;
+    const int last_wt = ((p.N + 127) >> 7) - 1, last_rt = (p.M - 1) >> 7;
+    const int wt0 = n0 >> 7, wt1 = wt0 + 1 < last_wt ? wt0 + 1 : last_wt;     // ragged edges re-read a valid tile (masked)
+    const int rt0 = (m0 >> 7) < last_rt ? (m0 >> 7) : last_rt, rt1 = (m0 >> 7) + 1 < last_rt ? (m0 >> 7) + 1 : last_rt;
+    const size_t po = (size_t)(2 * w) * 1024 + lane * 16;
+    const char* const sw0 = (const char*)p.W + ((size_t)wt0 * nktot + kt0) * TILE_BYTES + po;
+    const char* const sw1 = (const char*)p.W + ((size_t)wt1 * nktot + kt0) * TILE_BYTES + po;
+    const char* const sx0 = (const char*)p.X + ((size_t)rt0 * nktot + kt0) * TILE_BYTES + po;
+    const char* const sx1 = (const char*)p.X + ((size_t)rt1 * nktot + kt0) * TILE_BYTES + po;
+    char* const dst0 = smem + (2 * w) * 1024;
+    auto stage = [&](const char* src, int h, int t) {
+        const char* s = src + (size_t)t * TILE_BYTES;
+        char* d = dst0 + (t & 1) * PAR + h * TILE_BYTES;
+        glds16(s, d);
+        glds16(s + 1024, d + 1024);
+    };
+    const int li = lane & 15, g = lane >> 4;
+    int woff[2], xoff[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int ch = ((4 * s + g) ^ (li & 7)) << 4;
+        woff[s] = wn * TILE_BYTES + li * 128 + ch;
+        xoff[s] = (2 + (wm >> 1)) * TILE_BYTES + (64 * (wm & 1) + li) * 128 + ch;
+    }
+    auto mma = [&](const f16x8& wv, const f16x8& xv, f32x4& c) {
+        if (TR) c = mfma16(xv, wv, c, 0, 0, 0);
+        else c = mfma16(wv, xv, c, 0, 0, 0);
+    };
+    // end of a read / fill section: this wave's LDS reads have returned (the WAR rule above), then the barrier; nothing may be scheduled across
+    auto end_l = [&]() {
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto end_m = [&]() {
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_barrier" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+    };
+
+    stage(sx0, 2, 0); stage(sx1, 3, 0); stage(sw0, 0, 0); stage(sw1, 1, 0);
+    if (nkt > 1) {
+        stage(sx0, 2, 1); stage(sx1, 3, 1);
+        asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");
+    } else {
+        asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+    }
+    after_prologue();
+    const bool fills = !GTAV_DBG(p, 1);
+    GTAV_STAMP(bs.t[1]);
+    if (late) end_m();                               // group 1 enters the loop one interval behind
+    for (int t = 0; t < nkt; ++t) {
+        const char* b = smem + (t & 1) * PAR;
+        const bool n1 = t + 1 < nkt && fills, n2 = t + 2 < nkt && fills;
+        f16x8 wa[2][4], wb[2][4], xa[2][2], xb[2][2];
+        // ---- L1 / M1 ----
+        if (n1) stage(sw0, 0, t + 1);
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) xa[s][j] = *(const f16x8*)(b + xoff[s] + j * 16 * 128);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) wa[s][i] = *(const f16x8*)(b + woff[s] + i * 16 * 128);
+        }
+        end_l();
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) mma(wa[s][i], xa[s][j], acc[i][j]);
+        __builtin_amdgcn_s_setprio(0);
+        end_m();
+        // ---- L2 / M2 ----
+        if (n1) stage(sw1, 1, t + 1);
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) xb[s][j] = *(const f16x8*)(b + xoff[s] + (2 + j) * 16 * 128);
+        end_l();
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) mma(wa[s][i], xb[s][j], acc[i][2 + j]);
+        __builtin_amdgcn_s_setprio(0);
+        end_m();
+        // ---- L3 / M3 ----
+        if (n2) stage(sx0, 2, t + 2);
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) wb[s][i] = *(const f16x8*)(b + woff[s] + (4 + i) * 16 * 128);
+        end_l();
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) mma(wb[s][i], xb[s][j], acc[4 + i][2 + j]);
+        __builtin_amdgcn_s_setprio(0);
+        end_m();
+        // ---- L4 / M4 ----
+        if (n2) stage(sx1, 3, t + 2);
+        __builtin_amdgcn_sched_barrier(0);
+        if (n2) asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");   // K-tile t + 1 complete (this wave's share): everything but X0 / X1(t+2)
+        else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) mma(wb[s][i], xa[s][j], acc[4 + i][j]);
+        __builtin_amdgcn_s_setprio(0);
+        end_m();
+    }
+    if (!late) end_m();                              // group 0 leaves one interval late: every wave has executed the same number of barriers
+}
+
+// gemm256_kernel around the antiphase main loop (block shape 17): the same launch bounds, LDS array, bias prefetch and epilogue
+template <int EPI>
+__global__ __launch_bounds__(512, 1) void gemm256_pp_kernel(GemmParams p) {
+    __shared__ __attribute__((aligned(16))) char smem[8 * TILE_BYTES + (EPI == EPI_QKV ? 2048 : 0)];   // + qkv_staged's token table
+    BlockStamps bs;
+    bs.begin(p);
+    int n0, m0, ks, kt0, nkt;
+    tile_map<EPI == EPI_PARTIAL, 256, 256>(p, n0, m0, ks, kt0, nkt);
+    f32x4 acc[8][4];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    bool tr = false;
+    f32x4 pbias[8];
+    auto pf = [&]() { prefetch_bias<EPI, 8, 4>(p, n0, pbias); };
+    auto nopf = []() {};
+    if constexpr (EPI == EPI_QKV) {
+        tr = (p.qkv_mode == QKV_SPATIAL) && (n0 >= 2 * p.D);
+        if (tr) mainloop256_pp<true>(p, smem, n0, m0, kt0, nkt, acc, bs, nopf);
+        else mainloop256_pp<false>(p, smem, n0, m0, kt0, nkt, acc, bs, nopf);
+        pf();   // the QKV variant is at the 256-register limit: fetch after the main loop
+    } else {
+        mainloop256_pp<false>(p, smem, n0, m0, kt0, nkt, acc, bs, pf);
+    }
+    GTAV_STAMP(bs.t[2]);
+    epilogue<EPI, 8, 4, 4>(p, acc, pbias, smem, n0, m0, ks, tr);
+    bs.end(p);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Loader-wave GEMM with the WEIGHT operand straight into registers (shape 22, round 6).
+//
+// What bounds the loader-wave kernel at a few hundred tokens (the batch-1 window step: one 128 x 96 tile per CU, 16 K-steps) is how many fill bytes a CU keeps in
+// flight against the latency of a weight that comes from HBM or the Infinity Cache: the ring holds NS - 1 = 3 stages of 28 KiB, of which 16 KiB are W — 48 KiB of W
+// in flight per CU — and the K-step costs 0.45-0.5 us where ingest (64 B/clk) and the matrix pipes need 0.2-0.25 (profiles/round6/*per_class*: out-proj with 8
+// K-steps 6.1 us, fc2's slices with 16 K-steps 9.9 us).  LDS capacity caps the ring; the register file does not: 8 compute waves x D = 4 K-steps x 4 KiB of W
+// fragments = 128 KiB in flight per CU.  So here
+//   * the compute waves load their OWN W fragments (16 features x 32 k per 16-byte lane load: the tile-major image makes a fragment half of eight 128-byte lines)
+//     D K-steps ahead into a register ring (plain global loads: hipcc counts their vmcnt itself; the waves issue no other vector-memory operation in the loop);
+//   * the loader waves move only X (the activations: L2-hot, 12 KiB per K-step) through the LDS ring, as before;
+//   * W never touches LDS: the ring is 12 KiB per stage and the LDS array serves X fragment reads only.
+// Price: the WM = 2 waves that share a W row tile each load it (W crosses the CU's texture path twice: 32 + 12 = 44 KiB of ingest per K-step against 28).
+// ---------------------------------------------------------------------------------------------------------------------
+template <bool TR, int NS, int FI, int FJ, int WN, int WM, int NL, int D, typename AfterPrologue>
+__device__ __forceinline__ void mainloop_lw(const GemmParams& p, char* smem, int n0, int m0, int kt0, int nkt,
+                                            f32x4 (&acc)[FI][FJ], BlockStamps& bs, AfterPrologue after_prologue) {
+    static_assert(NS >= 3 && NL >= 1 && D >= 2 && D % 2 == 0 && (FI == 1 || FI == 2), "X ring of at least 3 stages; an even W register ring; 1 or 2 feature tiles per wave");
+    constexpr int XPC = 2 * FJ * WM;                         // 1-KiB X pieces per stage
+    constexpr int G = (XPC + NL - 1) / NL;
+    constexpr int STAGE_BYTES = XPC * 1024;
+    constexpr bool XDB = FI * FJ * 2 + 2 * FJ * 8 <= 96;     // X fragments of two K-steps in registers (one-step software pipeline) only while they fit
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wraw = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nktot = p.K / TK;
+    if (wraw < NL) {
+        // ------------------------------------------------ loader wave: X only ------------------------------------------------
+        const int lw = wraw;
+        const int last_rt = (p.M - 1) >> 7;
+        const unsigned voff = (unsigned)lane * 16u;
+        const unsigned smem0 = lds_offset(smem);
+        const char* sb[G];
+        unsigned ldso[G];
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            int q = lw * G + i;
+            q = q < XPC ? q : XPC - 1;                       // the last wave repeats the final piece (same bytes, same place)
+            const int row = m0 + 8 * q;
+            int rt = row >> 7;
+            rt = rt < last_rt ? rt : last_rt;                // ragged edge: re-read a valid tile (results are masked)
+            sb[i] = (const char*)p.X + ((size_t)rt * nktot + kt0) * TILE_BYTES + ((row & 127) >> 3) * 1024;
+            ldso[i] = smem0 + q * 1024;
+        }
+        auto stage = [&](int t) {
+            const unsigned so = (unsigned)(t % NS) * STAGE_BYTES;
+            const size_t go = (size_t)t * TILE_BYTES;
+#pragma unroll
+            for (int i = 0; i < G; ++i) glds16_s(sb[i] + go, voff, ldso[i] + so);
+        };
+        const int npro = nkt < NS - 1 ? nkt : NS - 1;
+        for (int t = 0; t < npro; ++t) stage(t);
+        for (int t = 0; t < nkt; ++t) {
+            wait_vm_ring<NS, G>(nkt - 1 - t);                // this wave's share of tile t has landed
+            wg_barrier();
+            if (t == 0) GTAV_STAMP(bs.t[1]);
+            if (t + NS - 1 < nkt && !GTAV_DBG(p, 1)) stage(t + NS - 1);
+        }
+        return;
+    }
+    // ------------------------------------------------ compute wave ------------------------------------------------
+    const int w = wraw - NL;
+    const int wn = w % WN, wm = w / WN;
+    const int li = lane & 15, g = lane >> 4;
+    int xoff[2];
+    // this lane's W fragment source: row n0 + 16 FI wn + 16 i + li of the tile-major weight, 16-byte chunk 4 s + g of its 128-byte row (common.h tiled_off)
+    const int last_wt = ((p.N + 127) >> 7) - 1;
+    const int wrow = n0 + 16 * FI * wn + li;                 // (+ 16 i: 16 FI WN <= 128 and n0 % 128 == 0 keep every i inside one row tile)
+    int wrt = wrow >> 7;
+    wrt = wrt < last_wt ? wrt : last_wt;
+    int soff[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int ch = ((4 * s + g) ^ (li & 7)) << 4;
+        xoff[s] = (16 * FJ * wm + li) * 128 + ch;
+        soff[s] = ch;                                        // (row & 7) == (li & 7): n0 + 16 FI wn + 16 i is a multiple of 8
+    }
+    after_prologue();   // register loads the epilogue wants early (bias): OLDER than every W load, so the first W wait covers them
+    // The W loads and their waits are inline asm with hand-counted vmcnt: behind plain loads hipcc's wait-count pass loses the ring at the loop's back edge and
+    // drains to vmcnt(3) ... vmcnt(0) inside every K-step (seen in the first build of this loop: no load stayed in flight across a step).  A wait statement names
+    // the registers it retires as in-out operands, so no use of them can be scheduled above it (the pattern of mainloop256_tn).  vmcnt retires in issue order
+    // and these waves issue nothing else in the loop: when K-step u is consumed, the loads issued after its own are those of steps u + 1 .. min(u + D - 1, nkt - 1).
+    f16x8 wr[D][2][FI];
+    const unsigned wvoff0 = (unsigned)((wrow & 127) * 128 + soff[0]), wvoff1 = (unsigned)((wrow & 127) * 128 + soff[1]);
+    const char* const wbase = (const char*)p.W + ((size_t)wrt * nktot + kt0) * TILE_BYTES;    // wave-uniform
+    auto ldw = [&](int t, f16x8 (&dst)[2][FI]) {
+        const char* sb = wbase + (size_t)t * TILE_BYTES;
+#pragma unroll
+        for (int i = 0; i < FI; ++i) {
+            asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(dst[0][i]) : "v"(wvoff0), "s"(sb), "n"(i * 2048) : "memory");
+            asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(dst[1][i]) : "v"(wvoff1), "s"(sb), "n"(i * 2048) : "memory");
+        }
+    };
+    // slot `a` is consumed while the loads of YOUNGER later K-steps (2 FI each) may still be in flight.  ONE asm statement per call site and a compile-time count:
+    // a run-time choice between wait statements makes the in-out registers phis of several definitions, and hipcc then copies them — in one of the paths AHEAD of
+    // the wait, i.e. before the data has landed (seen in the second build of this loop).  Hence the loop below has no branch around a wait: a steady part in which
+    // every step has D - 1 younger steps in flight, and a tail of exactly D steps with D - 1, ..., 0 (host-checked: K-steps per slice a multiple of D).
+    auto wait_w = [&](f16x8 (&a)[2][FI], auto younger) {
+        constexpr int CNT = decltype(younger)::value * 2 * FI;
+        if constexpr (FI == 2) asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a[0][0]), "+v"(a[0][1]), "+v"(a[1][0]), "+v"(a[1][1]) : "n"(CNT));
+        else asm volatile("s_waitcnt vmcnt(%2)" : "+v"(a[0][0]), "+v"(a[1][0]) : "n"(CNT));
+    };
+#pragma unroll
+    for (int d = 0; d < D; ++d) ldw(d, wr[d]);
+    auto mmh = [&](const f16x8 (&wf)[FI], const f16x8 (&xv)[FJ]) {      // one 32-deep half of a K-step
+#pragma unroll
+        for (int i = 0; i < FI; ++i)
+#pragma unroll
+            for (int j = 0; j < FJ; ++j) {
+                if (TR) acc[i][j] = mfma16(xv[j], wf[i], acc[i][j], 0, 0, 0);
+                else acc[i][j] = mfma16(wf[i], xv[j], acc[i][j], 0, 0, 0);
+            }
+    };
+    const bool domm = !GTAV_DBG(p, 2);
+    auto rdx = [&](int t, f16x8 (&dst)[2][FJ]) {
+        const char* b = smem + (t % NS) * STAGE_BYTES;
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int j = 0; j < FJ; ++j) dst[s][j] = *(const f16x8*)(b + xoff[s] + j * 16 * 128);
+    };
+    if constexpr (XDB) {
+        // one-step software pipeline on the X side (as mainloop_l): barrier u + 1 | read X(u + 1) | MFMAs of K-step u (W from register slot u % D) | refill the slot with step u + D
+        f16x8 xf[2][2][FJ];
+        auto next_x = [&](int t, f16x8 (&dst)[2][FJ]) {    // barrier t (X stage t complete and visible), then its fragment reads
+            wait_lgkm0();
+            wg_barrier();
+            rdx(t, dst);
+        };
+        auto mm = [&](const f16x8 (&wf)[2][FI], const f16x8 (&xv)[2][FJ]) { mmh(wf[0], xv[0]); mmh(wf[1], xv[1]); };
+        next_x(0, xf[0]);
+        GTAV_STAMP(bs.t[1]);
+        auto steady = [&](int u0, auto dc) {
+            constexpr int d = decltype(dc)::value;
+            next_x(u0 + d + 1, xf[(d + 1) & 1]);
+            wait_w(wr[d], std::integral_constant<int, D - 1>{});
+            if (domm) mm(wr[d], xf[d & 1]);
+            __builtin_amdgcn_sched_barrier(0);
+            ldw(u0 + d + D, wr[d]);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        auto tail = [&](int u0, auto dc) {
+            constexpr int d = decltype(dc)::value;
+            if constexpr (d + 1 < D) next_x(u0 + d + 1, xf[(d + 1) & 1]);
+            wait_w(wr[d], std::integral_constant<int, D - 1 - d>{});
+            if (domm) mm(wr[d], xf[d & 1]);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        auto run = [&](auto&& f, int u0) {
+            if constexpr (D == 4) { f(u0, std::integral_constant<int, 0>{}); f(u0, std::integral_constant<int, 1>{}); f(u0, std::integral_constant<int, 2>{}); f(u0, std::integral_constant<int, 3>{}); }
+            else { static_assert(D == 8, "rings of 4 or 8 K-steps");
+                   f(u0, std::integral_constant<int, 0>{}); f(u0, std::integral_constant<int, 1>{}); f(u0, std::integral_constant<int, 2>{}); f(u0, std::integral_constant<int, 3>{});
+                   f(u0, std::integral_constant<int, 4>{}); f(u0, std::integral_constant<int, 5>{}); f(u0, std::integral_constant<int, 6>{}); f(u0, std::integral_constant<int, 7>{}); }
+        };
+        for (int u0 = 0; u0 < nkt - D; u0 += D) run(steady, u0);     // (nkt % D == 0: slot and X set of step u0 + d are d and d & 1)
+        run(tail, nkt - D);
+    } else {
+        // wide token tiles (FJ = 6: 48 fragment registers per K-step): no second X set — barrier u | read both halves of X(u) | MFMAs half 0 behind lgkmcnt(FJ),
+        // half 1 behind lgkmcnt(0) | refill.  The co-resident compute wave of the SIMD covers the LDS round trip.
+        f16x8 xf[2][FJ];
+        auto step = [&](int u, auto dc, auto yc, bool refill) {
+            constexpr int d = decltype(dc)::value;
+            wait_lgkm0();
+            wg_barrier();
+            if (u == 0) GTAV_STAMP(bs.t[1]);
+            rdx(u, xf);
+            wait_w(wr[d], yc);
+            if (domm) { mmh(wr[d][0], xf[0]); mmh(wr[d][1], xf[1]); }
+            __builtin_amdgcn_sched_barrier(0);
+            if (refill) ldw(u + D, wr[d]);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        static_assert(D == 8 || D == 4, "rings of 4 or 8 K-steps");
+#define GTAV_LW_STEADY(dd) step(u0 + dd, std::integral_constant<int, dd>{}, std::integral_constant<int, D - 1>{}, true)
+#define GTAV_LW_TAIL(dd) step(nkt - D + dd, std::integral_constant<int, dd>{}, std::integral_constant<int, D - 1 - dd>{}, false)
+        for (int u0 = 0; u0 < nkt - D; u0 += D) {
+            GTAV_LW_STEADY(0); GTAV_LW_STEADY(1); GTAV_LW_STEADY(2); GTAV_LW_STEADY(3);
+            if constexpr (D == 8) { GTAV_LW_STEADY(4); GTAV_LW_STEADY(5); GTAV_LW_STEADY(6); GTAV_LW_STEADY(7); }
+        }
+        GTAV_LW_TAIL(0); GTAV_LW_TAIL(1); GTAV_LW_TAIL(2); GTAV_LW_TAIL(3);
+        if constexpr (D == 8) { GTAV_LW_TAIL(4); GTAV_LW_TAIL(5); GTAV_LW_TAIL(6); GTAV_LW_TAIL(7); }
+#undef GTAV_LW_STEADY
+#undef GTAV_LW_TAIL
+    }
+}
+
+template <int EPIX, int NS, int FI, int FJ, int WN, int WM, int NL, int D>
+__global__ __launch_bounds__(64 * (WN * WM + NL), 1) void gemm_lw_kernel(GemmParams p) {
+    constexpr int EPI = epi_base(EPIX);
+    static_assert(!epi_is_fold_consumer(EPIX) && EPI != EPI_RESID_FOLD, "no LayerNorm-fold epilogues on this kernel");
+    constexpr int TNB = 16 * FI * WN, TM = 16 * FJ * WM;
+    static_assert(TNB <= 128 && 128 % TNB == 0, "a block's features stay inside one 128-row weight tile");
+    extern __shared__ __attribute__((aligned(16))) char smem_l[];
+    char* smem = smem_l;
+#define GTAV_PIN_S(x) asm volatile("" ::"s"(x))
+    GTAV_PIN_S(p.X); GTAV_PIN_S(p.W); GTAV_PIN_S(p.M); GTAV_PIN_S(p.N); GTAV_PIN_S(p.K); GTAV_PIN_S(p.splitk);
+    GTAV_PIN_S(p.tm.tiles_m); GTAV_PIN_S(p.tm.tiles_n); GTAV_PIN_S(p.tm.gn); GTAV_PIN_S(p.tm.group); GTAV_PIN_S(p.tm.tiles);
+    GTAV_PIN_S(p.tm.rcp_tiles); GTAV_PIN_S(p.tm.rcp_group); GTAV_PIN_S(p.tm.rcp_gn); GTAV_PIN_S(p.tm.rcp_gnlast);
+    GTAV_PIN_S(p.bias); GTAV_PIN_S(p.out); GTAV_PIN_S(p.ldo); GTAV_PIN_S(p.qkv_mode); GTAV_PIN_S(p.D);
+#undef GTAV_PIN_S
+    BlockStamps bs;
+    bs.begin(p);
+    int n0, m0, ks, kt0, nkt;
+    tile_map_fast<EPI == EPI_PARTIAL, TNB, TM>(p, n0, m0, ks, kt0, nkt);
+    f32x4 acc[FI][FJ];
+#pragma unroll
+    for (int i = 0; i < FI; ++i)
+#pragma unroll
+        for (int j = 0; j < FJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    bool tr = false;
+    f32x4 pbias[FI];
+    FoldTok<FJ> ft;
+    auto pf = [&]() { prefetch_bias<EPI, FI, WM, WN, NL>(p, n0, pbias); };
+    if constexpr (EPI == EPI_QKV) {
+        tr = (p.qkv_mode == QKV_SPATIAL) && (n0 >= 2 * p.D);
+        if (tr) mainloop_lw<true, NS, FI, FJ, WN, WM, NL, D>(p, smem, n0, m0, kt0, nkt, acc, bs, pf);
+        else mainloop_lw<false, NS, FI, FJ, WN, WM, NL, D>(p, smem, n0, m0, kt0, nkt, acc, bs, pf);
+    } else {
+        mainloop_lw<false, NS, FI, FJ, WN, WM, NL, D>(p, smem, n0, m0, kt0, nkt, acc, bs, pf);
+    }
+    GTAV_STAMP(bs.t[2]);
+    epilogue<EPIX, FI, FJ, WM, WN, NL, false>(p, acc, pbias, smem, n0, m0, ks, tr, acc, ft);
+    bs.end(p);
+}
+
+// loader-wave kernel with the weight operand straight into registers (shape 22): dynamic LDS = the X ring, or the epilogue's image if that is larger
+template <int EPI, int NS, int FI, int FJ, int WN, int WM, int NL, int D>
+static int launch_lw(const GemmParams& p, int splitk, hipStream_t stream) {
+    constexpr int TNB = 16 * FI * WN, TM = 16 * FJ * WM;
+    constexpr int RING = NS * 2 * FJ * WM * 1024;
+    constexpr int PNB = (TNB / 8 + 7) / 8 * 8 * 16, PTB = (TM / 8 + 7) / 8 * 8 * 16;
+    constexpr int EPIB = (TM * PNB > TNB * PTB ? TM * PNB : TNB * PTB) + TM * 8;      // qkv_staged's pitched image + token table (gemm_l_kernel)
+    constexpr int GELUB = (TNB / 64 > 0 ? TNB / 64 : 1) * TM * 128;                     // the tile-major GELU image
+    constexpr int LDS = RING > EPIB ? (RING > GELUB ? RING : GELUB) : (EPIB > GELUB ? EPIB : GELUB);
+    static unsigned long long attr_devs = 0;
+    int dev = 0;
+    GTAV_REQUIRE(device_cus(&dev) > 0, "gemm: no current device");
+    if (!(attr_devs >> (dev & 63) & 1)) {
+        GTAV_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_lw_kernel<EPI, NS, FI, FJ, WN, WM, NL, D>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+        attr_devs |= 1ull << (dev & 63);
+    }
+    GemmParams q = p;
+    if (int rc_ = fill_tile_map(q.tm, p.M, p.N, p.K, TM, TNB, splitk)) return rc_;
+    const dim3 grid(q.tm.tiles * splitk);
+    GTAV_LAUNCH((gemm_lw_kernel<EPI, NS, FI, FJ, WN, WM, NL, D>), grid, dim3(64 * (WN * WM + NL)), LDS, stream, q);
+    GTAV_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 // persistent 256-token-tile kernel (shapes 40 / 41): one block per CU; whole rounds of tiles + a two-way K split of a remainder of <= grid / 2 tiles
 template <int EPI, int FI>
 static int launch_p256(const GemmParams& p, hipStream_t stream) {
@@ -1117,7 +1557,7 @@ static int launch_p256(const GemmParams& p, hipStream_t stream) {
     return 0;
 }
 
-
+// Block shapes of the experiments build.  `handled` = the shape was one of them (rc is the launch's status).
 template <int EPI>
 static int launch_experiment_shape(GemmParams& p, int ns, int shape, int splitk, hipStream_t stream, bool& handled) {
     (void)ns;
@@ -1164,6 +1604,33 @@ static int launch_experiment_shape(GemmParams& p, int ns, int shape, int splitk,
         }
     }
     if constexpr (!FOLDISH) {
+        // Round 6, measured SLOWER (profiles/round6/weight_operand_straight_into_registers_shapes_22_18.txt): the captured batch-1 step 2.05 -> 2.26 ms
+        // (shape 22) / 2.12 -> 2.23 ms (shape 18), bit-identical results.  More weight bytes in flight per CU (128 KiB in registers against 48 KiB of the LDS ring) buy
+        // nothing at M = 720: the K-step of the loader-wave kernel is not waiting for the weight.
+        // shape 20's tile, the weight operand straight into registers 4 K-steps ahead (its K loop is written for K-steps per slice that are a multiple of 4: else shape 20)
+        if (shape == 22) {
+            if ((p.K / TK / (splitk > 0 ? splitk : 1)) % 4 == 0) return launch_lw<EPI, 4, 2, 3, 4, 2, 4, 4>(p, splitk, stream);
+            return launch_l<EPI, 4, 2, 3, 4, 2, 4>(p, splitk, stream);
+        }
+        // ... and with the eight compute waves side by side along the features (16 features x all 96 tokens each): every W fragment is loaded by exactly one wave,
+        // 8 K-steps ahead
+        if (shape == 18) {
+            if ((p.K / TK / (splitk > 0 ? splitk : 1)) % 8 == 0) return launch_lw<EPI, 4, 1, 6, 8, 1, 4, 8>(p, splitk, stream);
+            return launch_l<EPI, 4, 2, 3, 4, 2, 4>(p, splitk, stream);
+        }
+        // Shape 7 (launch_epi: its grid, group width and narrow-output rule) with the two wave groups of a block in antiphase (gemm256_pp_kernel).  Round 6: correct,
+        // race-screened (profiles/round6/race_screen_shape17.txt) and within +-1 % of shape 7 on the shapes that select it (fc2 / projection at M >= 11 520, fc1 -7 % at
+        // M = 11 520 where shape 12 is still ahead of both at the model level): the K-tile is bound by how many fill bytes a CU keeps in flight, not by how its two
+        // waves per SIMD interleave reads and MFMAs (profiles/round6/antiphase_256x256_main_loop_shape17_vs_shape7_vs_heuristic.txt: main loop 26.9 vs 27.2 us)
+        if (shape == 17) {
+            GTAV_REQUIRE(!p.out2 || EPI == EPI_F16_TILED, "gemm: a second output image (out2) exists for EPI_F16_TILED on the staged epilogue only (epilogue %d, block shape %d)", (int)EPI, shape);
+            set_gn(256, 256);
+            if (!g_force_gn && splitk == 1 && p.N <= 1024 && (size_t)p.M >= 8 * (size_t)p.N) p.tm.gn = cdiv(p.N, 256);
+            const dim3 grid(cdiv(p.M, 256) * cdiv(p.N, 256) * splitk);
+            GEMM_LAUNCH((gemm256_pp_kernel<EPI>), grid, dim3(512));
+            GTAV_CHECK_HIP(hipGetLastError());
+            return 0;
+        }
         // measured slower than the shapes the heuristic picks (docs/LABNOTES.md 4.1.1)
         if (shape == 21) return launch_l<EPI, 3, 4, 4, 4, 2, 4>(p, splitk, stream);   // 256 x 128, 8 compute + 4 loader waves
         if (shape == 23) return launch_l<EPI, 4, 4, 3, 2, 2, 4>(p, splitk, stream);   // 128 x 96, 4 compute waves of 64 x 48 + 4 loader waves

@@ -58,7 +58,7 @@ def test_persistent_256_token_tile_kernel(shape, M, N, K):
 
 @pytest.mark.parametrize("shape", [22, 18])
 def test_weight_operand_straight_into_registers(shape):
-    """Block shapes 22 / 18 (round 6; csrc/gemm.hip mainloop_lw): the 128 x 96 loader-wave tile with the weight operand loaded by the compute waves straight into a
+    """Block shapes 22 / 18 (round 6; csrc/gemm_experiments.inc mainloop_lw): the 128 x 96 loader-wave tile with the weight operand loaded by the compute waves straight into a
     register ring 4 / 8 K-steps ahead (hand-counted vmcnt), X through the LDS ring as before — measured slower than shape 20, kept for the record.  Every epilogue
     through the product suite's shape sweep (K-steps per slice that are not a multiple of the ring depth fall back to shape 20)."""
     import test_gpu_ops as T

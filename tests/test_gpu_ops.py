@@ -651,6 +651,32 @@ def test_gemm_other_tiles_all_epilogues(shape):
         lib.gtav_op_gemm_set_wm(0)
 
 
+EXPERIMENT_SHAPES = (8, 9, 16, 17, 18, 21, 22, 23, 25, 27, 28, 30, 32, 33, 40, 41, 42)
+
+
+def test_product_refuses_the_experiment_block_shapes():
+    """Every block shape of csrc/gemm_experiments.inc is refused by the product library by name, before anything is launched (the output
+    stays as it was), and the refusal leaves nothing behind: the next unforced GEMM on the same buffers is right."""
+    lib = L.load()
+    M, N, K = 96, 96, 64
+    x = _rand(M, K, seed=1).half()
+    w = _rand(N, K, scale=1 / math.sqrt(K), seed=2)
+    b = _rand(N, seed=3)
+    w16, xd, bd = pad_weight_f16(w), to_tiled_f16(x), b.to(dev())
+    out = torch.full((M, N), float("nan"), device=dev())
+    try:
+        for shape in EXPERIMENT_SHAPES:
+            lib.gtav_op_gemm_set_wm(shape)
+            with pytest.raises(L.GtavError) as e:
+                gemm(xd, w16, bd, M, N, K, 0, out, N)
+            assert f"block shape {shape}" in str(e.value) and "exists only in the experiments build" in str(e.value), (shape, str(e.value))
+            assert torch.isnan(out).all(), shape
+    finally:
+        lib.gtav_op_gemm_set_wm(0)
+    gemm(xd, w16, bd, M, N, K, 0, out, N)
+    assert rel_l2(out, x.float() @ w.half().float().t() + b) < 2e-5
+
+
 @pytest.mark.parametrize("shape", [31])
 @pytest.mark.parametrize("M,N,K", [(5760, 4096, 1024), (5760, 1024, 4096), (2312, 384, 896), (192, 128, 64), (11520, 1024, 1024), (100, 256, 128)])
 def test_persistent_loader_wave_kernel(shape, M, N, K):

@@ -46,6 +46,27 @@ def test_product_library_has_no_experiment_knobs():
         assert "getenv(" not in text, f"{src}: raw getenv outside GTAV_ENV_INT"
 
 
+def test_product_sources_hold_no_experiment_kernels():
+    """The kernels only the experiments build can reach (antiphase 256 x 256 main loop, weight operand straight into registers, VALU spatial attention
+    backward) live in the two *_experiments.inc files, and train.hip reads its one only under GTAV_EXPERIMENTS (gemm.hip: launch_epi's hook, likewise)."""
+    csrc = os.path.join(ROOT, "ai-generated-gtav_amd", "csrc")
+    text = {n: open(os.path.join(csrc, n)).read() for n in ("gemm.hip", "train.hip", "gemm_experiments.inc", "train_experiments.inc")}
+    moved = ("mainloop256_pp", "mainloop_lw", "gemm_lw_kernel", "launch_lw", "attn_spatial_bwd_kernel<")
+    for src in ("gemm.hip", "train.hip"):
+        for name in moved:
+            assert name not in text[src], f"{src} names {name}: experiments-only code belongs in the *_experiments.inc files"
+    for name in ("mainloop256_pp", "mainloop_lw"):
+        assert re.search(rf"^__device__ __forceinline__ void {name}\(", text["gemm_experiments.inc"], flags=re.M), name
+    assert re.search(r"^__global__ .*\bvoid gemm_lw_kernel\(", text["gemm_experiments.inc"], flags=re.M)
+    assert re.search(r"^static int launch_lw\(", text["gemm_experiments.inc"], flags=re.M)
+    assert re.search(r"^__global__ .*\bvoid attn_spatial_bwd_kernel\(", text["train_experiments.inc"], flags=re.M)
+    for src, inc in (("gemm.hip", "gemm_experiments.inc"), ("train.hip", "train_experiments.inc")):
+        lines = text[src].splitlines()
+        at = [i for i, ln in enumerate(lines) if inc in ln and ln.lstrip().startswith("#include")]
+        assert len(at) == 1, (src, at)
+        assert lines[at[0] - 1].strip() == "#ifdef GTAV_EXPERIMENTS" and lines[at[0] + 1].strip() == "#endif", (src, lines[at[0] - 1:at[0] + 2])
+
+
 def test_operand_typed_declarations_are_one_unconditional_text():
     """gemm_typed.inc / ops_typed.inc are read once per operand type (fp16 objects, bf16 twins, and both by the host code): a preprocessor directive there
     could give two builds different structs or prototypes.  Every launcher of the per-operand-type list (ops_bf16.h) has its prototype in one of them."""

@@ -1,5 +1,5 @@
 """Timeline of the persistent ping-pong GEMM (experiments build): per block, s_memrealtime at entry, at the end of each tile's MAIN
-loop and at the end of the last epilogue (csrc/gemm.hip gemm_pp_kernel).  Prints the phase durations.
+loop and at the end of the last epilogue (csrc/gemm_experiments.inc gemm_pp_kernel).  Prints the phase durations.
 Usage (GPU box): python tools/pp_stamps.py [--m 5760] [--only fc1,qkv]"""
 import argparse
 import os
