@@ -54,6 +54,13 @@ const OperandOps OPS_BF16 = {GTAV_OPERAND_OPS(GTAV_OPS_BF16) true};
 }  // namespace
 const OperandOps& gtav::operand_ops(bool bf16) { return bf16 ? OPS_BF16 : OPS_F16; }
 
+// Operand type of the kernel-level entry points below that have no _bf16 sibling (include/gtav_amd_testing.h gtav_op_set_operand_dtype): per thread, fp16 unless
+// a test says otherwise.  op_ops() is the set of launchers they dispatch through; the fp16 set holds the launchers they called directly before the hook existed.
+static thread_local bool g_op_bf16 = false;
+static const OperandOps& op_ops() { return operand_ops(g_op_bf16); }
+// the fused launches exist for fp16 operands only (the handle never runs them on a bf16 layer group)
+#define GTAV_OP_F16_ONLY(name) GTAV_REQUIRE(!g_op_bf16, name ": fp16 operands only, there is no bf16 twin of this launch (gtav_op_set_operand_dtype)")
+
 extern "C" {
 
 const char* gtav_last_error(void) { return last_error(); }
@@ -139,7 +146,7 @@ int gtav_op_gemm_f16(const void* x, int32_t ldx, const void* w, const float* bia
     if (epilogue == EPI_PARTIAL) g.splitk = gate_stride > 0 ? gate_stride : 1;  // split-K factor travels in gate_stride
     g.X = (const f16*)x; g.ldx = ldx; g.W = (const f16*)w; g.M = M; g.N = N; g.K = K; g.bias = bias; g.out = out; g.ldo = ldo;
     g.gate = gate; g.gate_stride = gate_stride; g.rows_per_gate = rows_per_gate;
-    return launch_gemm(g, epilogue, (hipStream_t)stream);
+    return op_ops().gemm(g, epilogue, (hipStream_t)stream);
 }
 int gtav_op_gemm_qkv(const void* x, int32_t ldx, const void* w, const float* bias, int32_t M, int32_t D, int32_t mode, void* q,
                      void* k, void* v, int32_t S, int32_t Tq, int32_t t0, int32_t Tmax, const float* rope_cs, void* stream) {
@@ -148,7 +155,7 @@ int gtav_op_gemm_qkv(const void* x, int32_t ldx, const void* w, const float* bia
     g.X = (const f16*)x; g.ldx = ldx; g.W = (const f16*)w; g.M = M; g.N = 3 * D; g.K = D; g.bias = bias; g.D = D; g.S = S;
     g.qkv_mode = mode; g.q = (f16*)q; g.k = (f16*)k; g.v = (f16*)v; g.Tq = Tq; g.t0 = t0; g.Tmax = Tmax;
     g.rope_cs = rope_cs;
-    return launch_gemm(g, EPI_QKV, (hipStream_t)stream);
+    return op_ops().gemm(g, EPI_QKV, (hipStream_t)stream);
 }
 #ifdef GTAV_EXPERIMENTS   // csrc/experiments.h
 int gtav_op_gemm_fold_producer(const void* x, const void* w, const float* bias, float* resid, int32_t M, int32_t N, int32_t K, const float* gate,
@@ -177,13 +184,18 @@ int gtav_op_skinny_f32(const float* x, int32_t ldx, const float* w, const float*
 }
 int gtav_op_ln_modulate(const float* x, void* out, int32_t M, int32_t D, const float* shift, const float* scale,
                         int32_t mod_stride, int32_t rows_per_mod, void* stream) {
-    return launch_ln_modulate((float*)x, D, (f16*)out, D, M, D, shift, scale, mod_stride, nullptr, rows_per_mod, nullptr, nullptr, (hipStream_t)stream);
+    return op_ops().ln_modulate((float*)x, D, (f16*)out, D, M, D, shift, scale, mod_stride, nullptr, rows_per_mod, nullptr, nullptr, (hipStream_t)stream);
 }
 int gtav_op_ln_affine(const float* x, void* out, int32_t M, int32_t D, const float* gamma, const float* beta, void* stream) {
-    return launch_ln_affine((float*)x, D, (f16*)out, D, M, D, gamma, beta, nullptr, nullptr, (hipStream_t)stream);
+    return op_ops().ln_affine((float*)x, D, (f16*)out, D, M, D, gamma, beta, nullptr, nullptr, (hipStream_t)stream);
 }
 int gtav_op_attn_spatial(const void* q, const void* k, const void* vt, void* o, int32_t NB, int32_t heads, int32_t S, void* stream) {
-    return launch_attn_spatial((const f16*)q, (const f16*)k, (const f16*)vt, (f16*)o, NB, heads, S, (hipStream_t)stream);
+    return op_ops().attn_spatial((const f16*)q, (const f16*)k, (const f16*)vt, (f16*)o, NB, heads, S, (hipStream_t)stream, false);
+}
+// the form the VAE runs: q carries 1/8 log2 e (GemmParams::rope_cs_q); launch_attn_spatial refuses the sequence lengths whose kernel takes plain q
+int gtav_op_attn_spatial_prescaled(const void* q, const void* k, const void* vt, void* o, int32_t NB, int32_t heads, int32_t S, void* stream) {
+    GTAV_REQUIRE(attn_spatial_wants_prescaled_q(S), "op_attn_spatial_prescaled: S=%d runs a kernel that takes plain q", S);
+    return op_ops().attn_spatial((const f16*)q, (const f16*)k, (const f16*)vt, (f16*)o, NB, heads, S, (hipStream_t)stream, true);
 }
 static int op_attn_temporal(bool bf16, const void* q, const void* kv, void* o, int32_t B, int32_t P, int32_t D, int32_t Tq, int32_t t0, int32_t Tmax, void* stream) {
     return operand_ops(bf16).attn_temporal((const f16*)q, (const f16*)kv, (f16*)o, B, P, D, Tq, t0, Tmax, (hipStream_t)stream);
@@ -197,10 +209,12 @@ int gtav_op_attn_temporal_bf16(const void* q, const void* kv, void* o, int32_t B
     return op_attn_temporal(true, q, kv, o, B, P, D, Tq, t0, Tmax, stream);
 }
 int gtav_op_qkv_head_major(const void* w, void* w_hm, int32_t D, void* stream) {
+    GTAV_OP_F16_ONLY("op_qkv_head_major");
     return launch_qkv_head_major((const f16*)w, (f16*)w_hm, D, (hipStream_t)stream);
 }
 int gtav_op_gemm_qkvt_attn(const void* x_tperm, const void* w_hm, int32_t M, int32_t D, int32_t P, int32_t Tq, int32_t t0,
                            int32_t Tmax, const float* rope_cs, void* kv, void* o, void* stream) {
+    GTAV_OP_F16_ONLY("op_gemm_qkvt_attn");
     GemmParams g;
     memset(&g, 0, sizeof(g));
     g.X = (const f16*)x_tperm; g.ldx = D; g.W = (const f16*)w_hm; g.M = M; g.N = 3 * D; g.K = D; g.D = D; g.S = P;
@@ -209,9 +223,11 @@ int gtav_op_gemm_qkvt_attn(const void* x_tperm, const void* w_hm, int32_t M, int
     return launch_gemm_qkvt_attn(g, (hipStream_t)stream);
 }
 int gtav_op_qkv_head_major_spatial(const void* w, void* w_hm, int32_t D, void* stream) {
+    GTAV_OP_F16_ONLY("op_qkv_head_major_spatial");
     return launch_qkv_head_major((const f16*)w, (f16*)w_hm, D, (hipStream_t)stream, 1);
 }
 int gtav_op_gemm_qkvs_attn(const void* x, const void* w_hm, int32_t M, int32_t D, int32_t P, const float* rope_cs, void* o, void* stream) {
+    GTAV_OP_F16_ONLY("op_gemm_qkvs_attn");
     GemmParams g;
     memset(&g, 0, sizeof(g));
     g.X = (const f16*)x; g.ldx = D; g.W = (const f16*)w_hm; g.M = M; g.N = 3 * D; g.K = D; g.D = D; g.S = P;
@@ -248,14 +264,14 @@ int gtav_op_gemm_tn(const void* x, const void* w, int32_t M, int32_t N, int32_t 
     GemmParams q;
     memset(&q, 0, sizeof(q));
     q.X = (const f16*)x; q.ldx = M; q.W = (const f16*)w; q.M = M; q.N = N; q.K = K; q.out = out; q.ldo = ldo;
-    return launch_gemm_tn(q, (hipStream_t)stream);
+    return op_ops().gemm_tn(q, (hipStream_t)stream);
 }
 int gtav_op_gemm_dw_grouped(int32_t n, const void* const* x, const void* const* w, float* const* out, const int32_t* M, const int32_t* N, const int32_t* ldo,
                             int32_t K, void* stream) {
     GTAV_REQUIRE(n >= 1 && n <= GEMM_DW_MAX_GROUPS && x && w && out && M && N && ldo, "op_gemm_dw_grouped: 1 .. %d groups", GEMM_DW_MAX_GROUPS);
     GemmDwGroup g[GEMM_DW_MAX_GROUPS];
     for (int i = 0; i < n; ++i) g[i] = GemmDwGroup{(const f16*)x[i], (const f16*)w[i], out[i], M[i], N[i], ldo[i]};
-    return launch_gemm_dw_grouped(g, n, K, nullptr, (hipStream_t)stream);
+    return op_ops().gemm_dw_grouped(g, n, K, nullptr, (hipStream_t)stream, false);
 }
 int gtav_op_gemm_splitk_ln(const void* x, int32_t ldx, const void* w, const float* bias, int32_t M, int32_t N, int32_t K,
                            int32_t splitk, float* parts, float* resid, const float* gate, int32_t gate_stride,
@@ -265,24 +281,26 @@ int gtav_op_gemm_splitk_ln(const void* x, int32_t ldx, const void* w, const floa
     memset(&g, 0, sizeof(g));
     g.X = (const f16*)x; g.ldx = ldx; g.W = (const f16*)w; g.M = M; g.N = N; g.K = K; g.out = parts; g.ldo = N;
     g.splitk = splitk > 0 ? splitk : gemm_choose_splitk(M, N, K);
-    RET_IF(launch_gemm(g, EPI_PARTIAL, (hipStream_t)stream));
+    RET_IF(op_ops().gemm(g, EPI_PARTIAL, (hipStream_t)stream));
     LnPending pd;
     memset(&pd, 0, sizeof(pd));
     pd.parts = parts; pd.nsplit = g.splitk; pd.slab_stride = (size_t)M * N; pd.ld = N; pd.bias = bias; pd.gate = gate;
     pd.gate_stride = gate_stride; pd.rows_per_gate = rows_per_gate;
-    return launch_ln_modulate(resid, N, (f16*)out_f16, N, M, N, shift, scale, mod_stride, nullptr, rows_per_gate, &pd, nullptr, (hipStream_t)stream);
+    return op_ops().ln_modulate(resid, N, (f16*)out_f16, N, M, N, shift, scale, mod_stride, nullptr, rows_per_gate, &pd, nullptr, (hipStream_t)stream);
 }
 int gtav_op_rope_interleave(const float* cos_t, const float* sin_t, float* cs, int32_t npos, void* stream) {
     return launch_rope_interleave(cos_t, sin_t, cs, npos, (hipStream_t)stream);
 }
 int gtav_op_gemm_choose_splitk(int32_t M, int32_t N, int32_t K) { return gemm_choose_splitk(M, N, K); }
 int gtav_op_gemm_resid_inplace(int32_t M, int32_t N, int32_t K) { return gemm_resid_inplace_ok(M, N, K, 0) ? 1 : 0; }
-void gtav_op_gemm_set_stages(int32_t ns) { gemm_set_stages(ns); }
+// the forced ring depth / block shape are thread_locals of gemm.hip, one pair per operand type: both are set, so a forced shape reaches the twin too
+void gtav_op_gemm_set_stages(int32_t ns) { gemm_set_stages(ns); gtav_bf16::gemm_set_stages(ns); }
 #ifdef GTAV_EXPERIMENTS
 void gtav_op_gemm_set_debug(int32_t bits) { gemm_set_debug(bits); }   // libgtav_amd_exp.so only (csrc/experiments.h)
 void gtav_op_gemm_set_stamps(void* buf_dev, int32_t max_blocks) { gemm_set_stamps((unsigned long long*)buf_dev, max_blocks); }
 #endif
-void gtav_op_gemm_set_wm(int32_t wm) { gemm_set_wm(wm); }
+void gtav_op_gemm_set_wm(int32_t wm) { gemm_set_wm(wm); gtav_bf16::gemm_set_wm(wm); }
+void gtav_op_set_operand_dtype(int32_t dtype) { g_op_bf16 = dtype == GTAV_OPERAND_BF16; }
 
 // Calibration of the in-situ profiler (gtav_dit_profile / gtav_vae_profile): `reps` launches of a one-wave kernel that spins `spin_us` microseconds on the
 // device's own 100 MHz clock, enqueued back to back, each with an event pair attached to its dispatch exactly like a profiled kernel.  Returns the mean event-pair
@@ -324,7 +342,7 @@ int gtav_timer_calibrate(int32_t spin_us, int32_t reps, double* event_us_mean, d
 
 int gtav_op_convert_f16(const float* src, int32_t lds, int32_t R, int32_t C, void* dst, int32_t Rp, int32_t Cp, int32_t tiled,
                         void* stream) {
-    return launch_convert_pad_f16(src, lds, R, C, (f16*)dst, Rp, Cp, 1.0f, tiled, (hipStream_t)stream);
+    return op_ops().convert_pad(src, lds, R, C, (f16*)dst, Rp, Cp, 1.0f, tiled, (hipStream_t)stream, nullptr);
 }
 
 }  // extern "C"

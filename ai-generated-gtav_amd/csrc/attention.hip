@@ -128,6 +128,15 @@ __global__ __launch_bounds__(64 * NW) void attn_spatial_1p_kernel(const f16* __r
 //     6 more MFMAs per key block instead of 48 additions per lane, and no cross-lane sum at the end)
 //   profiles/round5/attn_flash_*: 373 -> 159 us (first version) -> see there, per 80-frame x 16-head launch
 constexpr float kLazyThr = 8.0f;   // in exponent units (log2)
+// Plain q on bf16 operands: q * (1/8 log2 e) rounded to bf16 again is an error of up to 2^-9 per element ahead of a dot product with k — against a key of
+// large norm that is percents of a probability (tests/test_gpu_ops_typed.py: the running-max-jump case missed its per-row bound by it).  The twin therefore
+// scales q by 1/8 only (a power of two: exact) and keeps its scores in the natural logarithm's unit: the factor log2 e goes onto the fp32 score in front of
+// v_exp_f32, and the threshold is the same factor 2^8 in that unit.  The fp16 objects (11-bit q, the rounding is 8 times smaller) are unchanged.
+#ifdef GTAV_BF16_OPERANDS
+constexpr bool kPlainQNaturalUnit = true;
+#else
+constexpr bool kPlainQNaturalUnit = false;
+#endif
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
@@ -154,6 +163,8 @@ __device__ __forceinline__ float max_over_g(float v) {
 template <int NQT, int OCC, bool RAGGED, bool PRESCALED>   // OCC = blocks per CU the register budget must admit; RAGGED: S % 64 != 0; PRESCALED: Q holds q / 8 log2 e
 __global__ __launch_bounds__(256, OCC) void attn_flash_kernel(const f16* __restrict__ Q, const f16* __restrict__ K, const f16* __restrict__ Vt,
                                                             f16* __restrict__ O, int heads, int S, int nfh, int nqb, int sc1) {
+    constexpr bool NAT = !PRESCALED && kPlainQNaturalUnit;   // scores in units of ln, not log2 (see kPlainQNaturalUnit)
+    constexpr float kLog2e = 1.4426950408889634f, kThr = NAT ? kLazyThr * 0.6931471805599453f : kLazyThr;
     const bool dbg_force = (sc1 & 2) != 0;
     constexpr int SLOT = 16384, NSLOT = 3;          // per slot: K block [64 keys][128 B] | Vt block [64 d][128 B]
     __shared__ __attribute__((aligned(1024))) char smem[NSLOT * SLOT];
@@ -236,7 +247,7 @@ __global__ __launch_bounds__(256, OCC) void attn_flash_kernel(const f16* __restr
 #pragma unroll
             for (int h = 0; h < 2; ++h)
 #pragma unroll
-                for (int e = 0; e < 8; ++e) qf[qt][h][e] = (f16)((float)qf[qt][h][e] * kScaleLog2e);
+                for (int e = 0; e < 8; ++e) qf[qt][h][e] = (f16)((float)qf[qt][h][e] * (NAT ? 0.125f : kScaleLog2e));
     }
 
     // per-lane LDS offsets of the fragment reads inside a slot.  Key tile kt holds the keys 32 (kt >> 1) + 8 (i >> 2) + 4 (kt & 1) + (i & 3) on its rows i
@@ -317,7 +328,7 @@ __global__ __launch_bounds__(256, OCC) void attn_flash_kernel(const f16* __restr
                 im = max(max(__float_as_int(s0), __float_as_int(s1)), im);
                 im = max(max(__float_as_int(s2_), __float_as_int(s3)), im);
             }
-            need = need || (im > __float_as_int(kLazyThr));
+            need = need || (im > __float_as_int(kThr));
         }
         if (__any(need)) {   // rare after the first block: a jump of the maximum.  Everything at the old reference is rescaled exactly once, the pending scores re-based
 #pragma unroll
@@ -331,7 +342,7 @@ __global__ __launch_bounds__(256, OCC) void attn_flash_kernel(const f16* __restr
                 const float bm = max_over_g(m);
                 const float delta = kb == 0 ? bm : __builtin_fmaxf(bm, 0.f);   // the reference only ever rises after the first block
                 if (kb != 0) {
-                    const float alpha = __builtin_amdgcn_exp2f(-delta);
+                    const float alpha = __builtin_amdgcn_exp2f(NAT ? -delta * kLog2e : -delta);
 #pragma unroll
                     for (int dt = 0; dt < 5; ++dt) o[qt][dt] = o[qt][dt] * alpha;
                 }
@@ -350,8 +361,13 @@ __global__ __launch_bounds__(256, OCC) void attn_flash_kernel(const f16* __restr
             for (int qt = 0; qt < NQT; ++qt)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    pf[qt][r] = (f16)__builtin_amdgcn_exp2f(sc[qt][2 * s2][r]);
-                    pf[qt][4 + r] = (f16)__builtin_amdgcn_exp2f(sc[qt][2 * s2 + 1][r]);
+                    if constexpr (NAT) {
+                        pf[qt][r] = (f16)__builtin_amdgcn_exp2f(sc[qt][2 * s2][r] * kLog2e);
+                        pf[qt][4 + r] = (f16)__builtin_amdgcn_exp2f(sc[qt][2 * s2 + 1][r] * kLog2e);
+                    } else {
+                        pf[qt][r] = (f16)__builtin_amdgcn_exp2f(sc[qt][2 * s2][r]);
+                        pf[qt][4 + r] = (f16)__builtin_amdgcn_exp2f(sc[qt][2 * s2 + 1][r]);
+                    }
                 }
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {

@@ -63,7 +63,10 @@ __global__ __launch_bounds__(256) void ln_wave_row_kernel(const float* __restric
         s2 += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
     }
     const float t1 = wave_sum_dpp(s1), t2 = wave_sum_dpp(s2);
-    const float m1 = t1 / (float)D, mean = kshift + m1;
+    // The row is centred as (x - K) - mean(x - K): both differences are small and (nearly) exact.  x - (K + mean(x - K)) would round the mean to an ulp of
+    // |K| first — for a row of 300 +- 0.02 that is 1.5e-5, 7.6e-4 of the standard deviation, the same offset in every element of the row
+    // (tests/test_gpu_ops_typed.py::test_layernorm_statistics_with_a_large_mean found it: per-row relative L2 8.4e-4 against the bound of 5e-4)
+    const float m1 = t1 / (float)D;
     const float var = fmaxf(t2 / (float)D - m1 * m1, 0.f);
     const float rstd = 1.0f / sqrtf(var + 1e-6f);
     float amax = 0.f;
@@ -72,7 +75,7 @@ __global__ __launch_bounds__(256) void ln_wave_row_kernel(const float* __restric
         float yv[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float xh = (v[i][e] - mean) * rstd;
+            const float xh = ((v[i][e] - kshift) - m1) * rstd;
             if (MODE == 0) {
                 const float sc = av[i][e] + 1e-6f;
                 yv[e] = xh * (1.0f + sc) + bv[i][e];
@@ -185,11 +188,11 @@ __global__ __launch_bounds__(512) void ln_row_block_kernel(float* __restrict__ x
     float t1 = 0.f, t2 = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) { t1 += i < nw ? red[i] : 0.f; t2 += i < nw ? red[8 + i] : 0.f; }   // red[] is read with ds_read_b128s, not a counted loop
-    const float m1 = t1 / (float)D, mean = kshift + m1;
+    const float m1 = t1 / (float)D;
     const float var = fmaxf(t2 / (float)D - m1 * m1, 0.f);
     const float rstd = 1.0f / sqrtf(var + 1e-6f);
     if (!act) return;
-    const float dd[4] = {v[0] - mean, v[1] - mean, v[2] - mean, v[3] - mean};
+    const float dd[4] = {a0 - m1, a1 - m1, a2 - m1, a3 - m1};   // (x - K) - mean(x - K), never x - fl(K + mean(x - K)): see ln_wave_row_kernel
     float yv[4], amax = 0.f;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {

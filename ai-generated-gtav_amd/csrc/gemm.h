@@ -47,10 +47,7 @@ bool gemm_pp_ok(int M, int N, int K, int epi);
 bool gemm_resid_inplace_ok(int M, int N, int K, int rows_per_gate);
 // Split-K factor used for a residual GEMM of this shape (1 = no split): fills the 256 CUs when M is small.
 int gemm_choose_splitk(int M, int N, int K);
-// Pipeline depth override for experiments (0 = heuristic, else 2 or 4 LDS stages).
-void gemm_set_stages(int ns);
-// Block shape override (0 = heuristic; shape numbers in gemm.hip launch_epi).  Every shape computes the same result.
-void gemm_set_wm(int wm);
+// (gemm_set_stages / gemm_set_wm, the forced ring depth and block shape of the tests, are per operand type: gemm_typed.inc)
 #ifdef GTAV_EXPERIMENTS
 void gemm_set_debug(int bits);   // timing experiments, WRONG results
 // per-block timeline: 8 x u64 per block {s_memtime at entry, first K-tile landed, main loop done, epilogue done (end);

@@ -149,9 +149,11 @@ SIGNATURES = {
     "gtav_op_gemm_resid_inplace": [_i, _i, _i],
     "gtav_op_gemm_set_stages": [_i],
     "gtav_op_gemm_set_wm": [_i],
+    "gtav_op_set_operand_dtype": [_i],
+    "gtav_op_attn_spatial_prescaled": [_p, _p, _p, _p, _i, _i, _i, _p],
 }
 _RESTYPES = {"gtav_last_error": C.c_char_p, "gtav_dit_destroy": None, "gtav_vae_destroy": None, "gtav_op_gemm_set_stages": None,
-             "gtav_op_gemm_set_wm": None}
+             "gtav_op_gemm_set_wm": None, "gtav_op_set_operand_dtype": None}
 
 _lib = None
 

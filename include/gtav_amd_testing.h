@@ -1,12 +1,24 @@
 /* gtav_amd — test hooks of libgtav_amd.so.  NOT part of the product interface (include/gtav_amd.h): nothing in a binding of the
  * reference's API needs them.  tests/ use them to run every GEMM block shape the launch heuristic can pick through every epilogue.
  *
- * Both settings are PER THREAD (thread_local in csrc/gemm.hip), like the handles: forcing a shape on one thread never changes what
+ * All settings are PER THREAD (thread_local in csrc/gemm.hip), like the handles: forcing a shape on one thread never changes what
  * another thread's handle launches.  Every choice computes the same result.  0 restores the heuristic.
  *   gtav_op_gemm_set_stages   LDS ring depth of the 128 x 128 tiles: 2 or 4
  *   gtav_op_gemm_set_wm       block shape: 2, 3 (128 x 128, 4 / 8 waves), 7 (256 x 256), 11 (64 x 48), 12 (128 x 192), 13 (128 x 96, 4 waves), 14 (64 x 96),
  *                             20 / 24 / 26 (loader-wave kernel, 128 x 96 / 64 x 48 / 64 x 96 tiles), 31 (persistent loader-wave kernel, 128 x 192 tiles, 3-stage ring; its 4-stage / 256 x 128 / 128 x 256 forms 30 / 32 / 33 exist in the experiments build only)
  *                             — csrc/gemm.hip launch_epi
+ *
+ * gtav_op_set_operand_dtype   operand type of the kernel-level entry points (gtav_op_*) that have no _bf16 sibling: GTAV_OPERAND_F16 (0, the default) or
+ *                             GTAV_OPERAND_BF16 (1), PER THREAD like the two above.  With bf16 set, gtav_op_gemm_f16, gtav_op_gemm_qkv, gtav_op_ln_modulate,
+ *                             gtav_op_ln_affine, gtav_op_attn_spatial[_prescaled], gtav_op_gemm_tn, gtav_op_gemm_dw_grouped, gtav_op_gemm_splitk_ln and
+ *                             gtav_op_convert_f16 launch the bf16 twins (the objects a bf16 layer group of a handle runs) and every 2-byte buffer they read or
+ *                             write holds bf16.  Entry points with a _bf16 sibling (attn_temporal, attn_spatial_bwd, attn_temporal_bwd) keep their fixed type, the
+ *                             type-free ones (skinny_f32, rope_interleave, the elementwise math) are unaffected, and the fused fp16-only launches
+ *                             (gtav_op_gemm_qkvt_attn, gtav_op_gemm_qkvs_attn, gtav_op_qkv_head_major[_spatial]) refuse by name.  At the default every entry point
+ *                             launches what it launched before the hook existed.  gtav_op_gemm_set_stages / _set_wm set the forced shape of BOTH operand types.
+ * gtav_op_attn_spatial_prescaled   gtav_op_attn_spatial on a q that already carries 1/8 log2 e (the form the VAE's flash attention runs, GemmParams::rope_cs_q);
+ *                             refused at the sequence lengths whose kernel takes plain q.  Honours the operand type above.
+ * tests/test_gpu_ops_typed.py runs every one of these in both operand types against fp64 math with per-element bounds.
  * (Timing experiments that change results, and the block shapes that measured slower than these, exist only in the separate
  * -DGTAV_EXPERIMENTS build: csrc/build.sh exp -> libgtav_amd_exp.so, loaded by tools/ only.) */
 #ifndef GTAV_AMD_TESTING_H
@@ -20,6 +32,8 @@ extern "C" {
 
 void gtav_op_gemm_set_stages(int32_t ns);
 void gtav_op_gemm_set_wm(int32_t wm);
+void gtav_op_set_operand_dtype(int32_t dtype);   /* GTAV_OPERAND_F16 (default) / GTAV_OPERAND_BF16, per thread */
+int gtav_op_attn_spatial_prescaled(const void* q, const void* k, const void* vt, void* o, int32_t NB, int32_t heads, int32_t S, void* stream);
 
 #ifdef __cplusplus
 }

@@ -30,6 +30,23 @@ def untile(buf, R, K):
     return flat[tiled_index(R, K).reshape(-1)].reshape(R, K)
 
 
+def untile_typed(buf, R, K):
+    """tile-major 2-byte device buffer of either operand type -> row-major (R, K) CPU tensor of the same type; the bit patterns are carried through (an index
+    gather on the int16 view: no value is converted on the way)."""
+    flat = buf.reshape(-1).view(torch.int16).cpu()
+    return flat[tiled_index(R, K).reshape(-1)].reshape(R, K).view(buf.dtype)
+
+
+def to_tiled(x, dtype):
+    """(R, K) -> tile-major `dtype` image (round_up(R, 128) * round_up(K, 64) elements, zero padded) on the GPU, built on the HOST: torch's own round to nearest
+    even and tiled_index.  No kernel of the library touches the operand, so a test of the bf16 twins does not depend on the convert_pad twin it also tests."""
+    R, K = x.shape
+    Rp, Kp = (R + 127) // 128 * 128, (K + 63) // 64 * 64
+    flat = torch.zeros(Rp * Kp, dtype=torch.int16)
+    flat[tiled_index(R, Kp).reshape(R, Kp)[:, :K].reshape(-1)] = x.to(dtype).contiguous().view(torch.int16).reshape(-1)
+    return flat.view(dtype).reshape(Rp, Kp).to(dev())
+
+
 def to_tiled_f16(x):
     """fp32/fp16 (R, K) -> tile-major fp16 (round_up(R,128) * round_up(K,64) halves, zero padded) on the GPU."""
     R, K = x.shape
