@@ -357,6 +357,14 @@ struct gtav_dit {
         bool on = false, have_fwd = false, have_actions = false;
         bool bf16 = false;                  // every operand group bf16 (gtav_dit_train_enable_typed): no group may change its type while training is on
         int window = 8;                     // frames a training handle may be sized for (gtav_dit_train_allow_window raises it to at most 32)
+        // Activation recomputation (gtav_dit_train_set_recompute): the forward keeps the L + 1 block-input states and ONE block's worth of everything else,
+        // the backward re-runs a block's forward just before differentiating it.  res / hb keep their 4 L + 1 / 2 L entries, as aliases: res[k], k % 4 != 0, is
+        // one of three ring states, hb[i] is image set i % 2.  rc_block: the block whose ring states and images are in place (-1: none); kshift[l], l >= 1: the
+        // statistics' shift of every row in the first LayerNorm of block l (LnPending::k_save), which the re-run of that launch needs to give the same bits.
+        bool recompute = false;
+        int rc_block = -1;
+        std::vector<float*> kshift;
+        size_t saved_bytes = 0;             // bytes of res, hb, xnF, xp (and kshift): gtav_dit_train_saved_bytes
         int B = 0, T = 0, M = 0, Mp = 0, rows = 0;
         float loss_scale = 65536.0f;        // (1 on a bf16 handle)
         float grad_div = 1.0f;              // the arena holds the sum over this many ranks (gtav_dit_set_grad_divisor)

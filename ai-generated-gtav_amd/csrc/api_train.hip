@@ -44,6 +44,21 @@ int gtav_dit_train_allow_window(gtav_dit* h, int32_t max_frames) {
     return 0;
 }
 
+// Opt-in to activation recomputation (api_internal.h Train::recompute): between create and train_enable only, like gtav_dit_train_allow_window.
+int gtav_dit_train_set_recompute(gtav_dit* h, int32_t enable) {
+    GTAV_REQUIRE(h, "train_set_recompute: null handle");
+    GTAV_REQUIRE(!h->tr.on, "train_set_recompute: training is already enabled on this handle (call it between gtav_dit_create and gtav_dit_train_enable)");
+    h->tr.recompute = enable != 0;
+    return 0;
+}
+
+int gtav_dit_train_saved_bytes(gtav_dit* h, int64_t* bytes) {
+    GTAV_REQUIRE(h && bytes, "train_saved_bytes: null argument");
+    GTAV_REQUIRE(h->tr.on, "train_saved_bytes: training is not enabled");
+    *bytes = (int64_t)h->tr.saved_bytes;
+    return 0;
+}
+
 int gtav_dit_train_enable(gtav_dit* h, float* grad_arena_dev, int64_t grad_arena_numel) {
     GTAV_REQUIRE(h, "train_enable: null handle");
     RET_IF(train_window_ok(h));
@@ -141,18 +156,38 @@ static int train_enable_body(gtav_dit* h, float* grad_arena_dev, int64_t grad_ar
         t.adam_n_items = (int)ai.size();
     }
     const size_t Mx = round_up(h->Mmax, 128), Mp = round_up(h->Mmax, 64), Mm = h->Mmax;
-    t.res.resize(4 * L + 1);
-    for (auto& r : t.res) RET_IF(a.alloc_t(&r, Mx * D));
+    // saved activations (counted: gtav_dit_train_saved_bytes).  Recompute mode: the block inputs r_0, r_4, .. r_4L, three ring states for the ones inside a block,
+    // two image sets (spatial / temporal half-block) and one shift per row for every block but the first
+    t.saved_bytes = 0;
+    auto saved = [&](auto** p, size_t n) -> int {
+        RET_IF(a.alloc_t(p, n));
+        t.saved_bytes += n * sizeof(**p);
+        return 0;
+    };
+    t.res.assign(4 * L + 1, nullptr);
+    if (t.recompute) {
+        float* ring[3];
+        for (auto& r : ring) RET_IF(saved(&r, Mx * D));
+        for (int k = 0; k <= 4 * L; ++k) {
+            if (k % 4 == 0) RET_IF(saved(&t.res[k], Mx * D));
+            else t.res[k] = ring[k % 4 - 1];
+        }
+        t.kshift.assign(L, nullptr);
+        for (int l = 1; l < L; ++l) RET_IF(saved(&t.kshift[l], Mx));
+    } else {
+        for (auto& r : t.res) RET_IF(saved(&r, Mx * D));
+    }
     t.hb.resize(2 * L);
     for (int i = 0; i < 2 * L; ++i) {
         gtav_dit::Train::HB& b = t.hb[i];
-        RET_IF(a.alloc_t(&b.xnA, Mx * D)); RET_IF(a.alloc_t(&b.ao, Mx * D)); RET_IF(a.alloc_t(&b.y1, Mx * D)); RET_IF(a.alloc_t(&b.xnB, Mx * D));
-        RET_IF(a.alloc_t(&b.u, Mx * Hp)); RET_IF(a.alloc_t(&b.hh, Mx * Hp)); RET_IF(a.alloc_t(&b.y2, Mx * D));
-        RET_IF(a.alloc_t(&b.q, Mx * D));
-        if (i % 2 == 0) { RET_IF(a.alloc_t(&b.k, Mx * D)); RET_IF(a.alloc_t(&b.v, Mx * D)); }
-        else { RET_IF(a.alloc_t(&b.k, Mx * 2 * D)); b.v = b.k; }
+        if (t.recompute && i >= 2) { b = t.hb[i - 2]; continue; }
+        RET_IF(saved(&b.xnA, Mx * D)); RET_IF(saved(&b.ao, Mx * D)); RET_IF(saved(&b.y1, Mx * D)); RET_IF(saved(&b.xnB, Mx * D));
+        RET_IF(saved(&b.u, Mx * Hp)); RET_IF(saved(&b.hh, Mx * Hp)); RET_IF(saved(&b.y2, Mx * D));
+        RET_IF(saved(&b.q, Mx * D));
+        if (i % 2 == 0) { RET_IF(saved(&b.k, Mx * D)); RET_IF(saved(&b.v, Mx * D)); }
+        else { RET_IF(saved(&b.k, Mx * 2 * D)); b.v = b.k; }
     }
-    RET_IF(a.alloc_t(&t.xnF, Mx * D)); RET_IF(a.alloc_t(&t.xp, Mx * h->Kpe));
+    RET_IF(saved(&t.xnF, Mx * D)); RET_IF(saved(&t.xp, Mx * h->Kpe));
     const size_t R = h->max_rows;
     RET_IF(a.alloc_t(&t.z0, R * D)); RET_IF(a.alloc_t(&t.cpre, R * D));
     RET_IF(a.alloc_t(&t.dres, Mx * D)); RET_IF(a.alloc_t(&t.dtmp, Mx * D)); RET_IF(a.alloc_t(&t.stats, 2 * Mx));
@@ -168,6 +203,92 @@ static int train_enable_body(gtav_dit* h, float* grad_arena_dev, int64_t grad_ar
         for (int i = 0; i < 4; ++i) { RET_IF(a.alloc_t(&t.tAg[i], ra[i] * Mp)); RET_IF(a.alloc_t(&t.tBg[i], rb[i] * Mp)); }
     }
     t.on = true;
+    return 0;
+}
+
+// Both half-blocks of block l of the training forward (gtav_dit_train_forward runs it for l = 0 .. L - 1).  Every residual GEMM stores split-K slabs and leaves
+// the update to the next LayerNorm launch (`pend`): on return the block's last fc2 branch is still pending, and the first LayerNorm of block l + 1 (or the final
+// layer's) applies it, writes r_{4l+4} and the branch image y2.
+// rerun (recompute mode, train_rerun_block): the block starts from its stored input r_4l, which already holds the update that the forward's first LayerNorm
+// applied, so that launch runs without one — on the row-block kernel and with the statistics' shift the forward's launch kept (LnPending::k_load).
+static int train_block_forward(gtav_dit* h, int l, int B, int T, bool rerun, LnPending& pend, bool& have_pend, hipStream_t s) {
+    gtav_dit::Train& tr = h->tr;
+    const int D = h->D, P = h->P, NB = B * T, M = NB * P;
+    const float* mod = h->mod;
+    GemmParams g;
+    auto resid_gemm = [&](const OperandOps& o, const f16* X, const f16* Wt, int K, const float* bias, const float* gate, float* x_out, f16* y_save) -> int {
+        GemmParams q;
+        memset(&q, 0, sizeof(q));
+        q.X = X; q.ldx = K; q.W = Wt; q.M = M; q.N = D; q.K = K; q.out = h->parts; q.ldo = D;
+        q.splitk = gemm_choose_splitk(M, D, K);
+        GTAV_REQUIRE((size_t)q.splitk * M <= h->parts_rows, "split-K slabs exceed workspace");
+        RET_IF(o.gemm(q, EPI_PARTIAL, s));
+        memset(&pend, 0, sizeof(pend));
+        pend.parts = h->parts; pend.nsplit = q.splitk; pend.slab_stride = (size_t)M * D; pend.ld = D; pend.bias = bias;
+        pend.gate = gate; pend.gate_stride = h->MODW; pend.gate_rows = nullptr; pend.rows_per_gate = P;
+        pend.x_out = x_out; pend.y_save = y_save;
+        have_pend = true;
+        return 0;
+    };
+    for (int hf = 0; hf < 2; ++hf) {
+        const int i = l * 2 + hf;
+        const gtav_dit::Half& w = h->halves[i];
+        gtav_dit::Train::HB& b = tr.hb[i];
+        const float* mb = mod + (size_t)i * 6 * D;
+        const OperandOps& o = h->ops(i);
+        // LN1 normalises r_{2i} (= r_{2i-1} + gate (fc2 of the previous half-block), written to res[2i] by this launch)
+        if (rerun && hf == 0 && l > 0) {
+            GTAV_REQUIRE(!have_pend, "train_block_forward: a re-run starts from a stored block input");
+            LnPending k0;
+            memset(&k0, 0, sizeof(k0));
+            k0.k_load = tr.kshift[l];
+            RET_IF(o.ln_modulate(tr.res[2 * i], D, b.xnA, D, M, D, mb, mb + D, h->MODW, nullptr, P, &k0, h->err_flag, s));
+        } else {
+            if (tr.recompute && hf == 0 && l > 0) pend.k_save = tr.kshift[l];   // (l > 0: the previous block's fc2 is pending)
+            RET_IF(o.ln_modulate(i == 0 ? tr.res[0] : tr.res[2 * i - 1], D, b.xnA, D, M, D, mb, mb + D, h->MODW, nullptr, P, have_pend ? &pend : nullptr, h->err_flag, s));
+        }
+        have_pend = false;
+        memset(&g, 0, sizeof(g));
+        g.X = b.xnA; g.ldx = D; g.W = w.w_qkv; g.M = M; g.N = 3 * D; g.K = D; g.D = D; g.S = P; g.err_flag = h->err_flag;
+        if (hf == 0) { g.qkv_mode = QKV_SPATIAL; g.q = b.q; g.k = b.k; g.v = b.v; g.rope_cs = h->rope_s.cs_dev; }
+        else { g.qkv_mode = QKV_TEMPORAL; g.q = b.q; g.k = b.k; g.v = b.k; g.Tq = T; g.t0 = 0; g.Tmax = h->maxT; g.rope_cs = h->rope_t.cs_dev; }
+        RET_IF(o.gemm(g, EPI_QKV, s));
+        if (hf == 0) RET_IF(o.attn_spatial(b.q, b.k, b.v, b.ao, NB, h->heads, P, s, false));
+        else RET_IF(o.attn_temporal(b.q, b.k, b.ao, B, P, D, T, 0, h->maxT, s));
+        RET_IF(resid_gemm(o, b.ao, w.w_out, D, w.b_out, mb + 2 * D, tr.res[2 * i + 1], b.y1));
+        RET_IF(o.ln_modulate(tr.res[2 * i], D, b.xnB, D, M, D, mb + 3 * D, mb + 4 * D, h->MODW, nullptr, P, &pend, h->err_flag, s));
+        have_pend = false;
+        memset(&g, 0, sizeof(g));
+        g.X = b.xnB; g.ldx = D; g.W = w.w_fc1; g.M = M; g.N = h->Hm; g.K = D; g.bias = w.b_fc1; g.out = b.u; g.ldo = h->Hm_pad; g.err_flag = h->err_flag;
+        if (g_fuse_gelu_fwd) g.out2 = b.hh;             // h = GELU(u) as a second image of the same epilogue (gemm.h out2)
+        RET_IF(o.gemm(g, EPI_F16_TILED, s));            // the pre-activation is kept: gelu'(u) in the backward pass
+        if (!g_fuse_gelu_fwd) RET_IF(h->ops(i).gelu_tiled(b.u, b.hh, (size_t)round_up(M, 128) * h->Hm_pad, s));
+        RET_IF(resid_gemm(o, b.hh, w.w_fc2, h->Hm_pad, w.b_fc2, mb + 5 * D, tr.res[2 * i + 2], b.y2));
+    }
+    return 0;
+}
+
+// Recompute mode: the forward of block l of the last gtav_dit_train_forward again, from its stored input state into the ring states and the two image sets: the
+// same launches on the same inputs, so the same bits (the first LayerNorm: see train_block_forward).  The block's last fc2 branch was applied, and its image y2
+// written, by the first LayerNorm of block l + 1: that launch runs again at the end (it rewrites r_{4l+4} and kshift[l + 1] with the values they hold; its
+// normalised output is not needed and goes to the backward workspace g_d, free between two blocks' backward passes).  The last block's activations are in
+// place after the forward; a second backward pass over the same forward re-runs it too, and ends with the final layer's LayerNorm as the forward does.
+static int train_rerun_block(gtav_dit* h, int l, hipStream_t s) {
+    gtav_dit::Train& tr = h->tr;
+    const int D = h->D, L = h->L, i = 2 * l + 2;
+    GTAV_REQUIRE(l >= 0 && l < L, "train_backward: no block %d to re-run", l);
+    LnPending pend;
+    bool have_pend = false;
+    tr.rc_block = -1;
+    RET_IF(train_block_forward(h, l, tr.B, tr.T, true, pend, have_pend, s));
+    const float* mb = h->mod + (size_t)i * 6 * D;   // (i = 2 L: the final layer's shift and scale)
+    if (l < L - 1) {
+        pend.k_save = tr.kshift[l + 1];
+        RET_IF(h->ops(i).ln_modulate(tr.res[2 * i - 1], D, tr.g_d, D, tr.M, D, mb, mb + D, h->MODW, nullptr, h->P, &pend, h->err_flag, s));
+    } else {
+        RET_IF(h->ops(2 * L + 1).ln_modulate(tr.res[4 * L - 1], D, tr.xnF, D, tr.M, D, mb, mb + D, h->MODW, nullptr, h->P, &pend, h->err_flag, s));
+    }
+    tr.rc_block = l;
     return 0;
 }
 
@@ -225,6 +346,7 @@ int gtav_dit_train_forward(gtav_dit* h, const float* x, const int64_t* t64, cons
     const int D = h->D, P = h->P, NB = B * T, M = NB * P, L = h->L, rows = NB, ldhc = D + h->Apad;
     h->prepared.valid = false;
     h->kvrec.valid = false;
+    tr.rc_block = -1;   // (recompute mode: this forward overwrites the ring states and the image sets; if it fails partway, no block is in place)
     // conditioning path with its pre-activations kept (dit_cond applies SiLU inside the skinny GEMM)
     RET_IF(launch_cond_inputs(t64, rows, 1, nullptr, 0, h->sincos, h->E, actions, h->A, 0, h->A, h->HC, ldhc, D, h->Apad, h->err_flag, s));
     RET_IF(launch_skinny_f32(h->E, 256, h->w_t0, h->b_t0, tr.z0, D, rows, D, 256, 0, s));
@@ -241,47 +363,7 @@ int gtav_dit_train_forward(gtav_dit* h, const float* x, const int64_t* t64, cons
     RET_IF(oe.gemm(g, EPI_F32, s));
     LnPending pend;
     bool have_pend = false;
-    auto resid_gemm = [&](const OperandOps& o, const f16* X, const f16* Wt, int K, const float* bias, const float* gate, float* x_out, f16* y_save) -> int {
-        GemmParams q;
-        memset(&q, 0, sizeof(q));
-        q.X = X; q.ldx = K; q.W = Wt; q.M = M; q.N = D; q.K = K; q.out = h->parts; q.ldo = D;
-        q.splitk = gemm_choose_splitk(M, D, K);
-        GTAV_REQUIRE((size_t)q.splitk * M <= h->parts_rows, "split-K slabs exceed workspace");
-        RET_IF(o.gemm(q, EPI_PARTIAL, s));
-        memset(&pend, 0, sizeof(pend));
-        pend.parts = h->parts; pend.nsplit = q.splitk; pend.slab_stride = (size_t)M * D; pend.ld = D; pend.bias = bias;
-        pend.gate = gate; pend.gate_stride = h->MODW; pend.gate_rows = nullptr; pend.rows_per_gate = P;
-        pend.x_out = x_out; pend.y_save = y_save;
-        have_pend = true;
-        return 0;
-    };
-    for (int l = 0; l < L; ++l)
-        for (int hf = 0; hf < 2; ++hf) {
-            const int i = l * 2 + hf;
-            const gtav_dit::Half& w = h->halves[i];
-            gtav_dit::Train::HB& b = tr.hb[i];
-            const float* mb = mod + (size_t)i * 6 * D;
-            const OperandOps& o = h->ops(i);
-            // LN1 normalises r_{2i} (= r_{2i-1} + gate (fc2 of the previous half-block), written to res[2i] by this launch)
-            RET_IF(o.ln_modulate(i == 0 ? tr.res[0] : tr.res[2 * i - 1], D, b.xnA, D, M, D, mb, mb + D, h->MODW, nullptr, P, have_pend ? &pend : nullptr, h->err_flag, s));
-            have_pend = false;
-            memset(&g, 0, sizeof(g));
-            g.X = b.xnA; g.ldx = D; g.W = w.w_qkv; g.M = M; g.N = 3 * D; g.K = D; g.D = D; g.S = P; g.err_flag = h->err_flag;
-            if (hf == 0) { g.qkv_mode = QKV_SPATIAL; g.q = b.q; g.k = b.k; g.v = b.v; g.rope_cs = h->rope_s.cs_dev; }
-            else { g.qkv_mode = QKV_TEMPORAL; g.q = b.q; g.k = b.k; g.v = b.k; g.Tq = T; g.t0 = 0; g.Tmax = h->maxT; g.rope_cs = h->rope_t.cs_dev; }
-            RET_IF(o.gemm(g, EPI_QKV, s));
-            if (hf == 0) RET_IF(o.attn_spatial(b.q, b.k, b.v, b.ao, NB, h->heads, P, s, false));
-            else RET_IF(o.attn_temporal(b.q, b.k, b.ao, B, P, D, T, 0, h->maxT, s));
-            RET_IF(resid_gemm(o, b.ao, w.w_out, D, w.b_out, mb + 2 * D, tr.res[2 * i + 1], b.y1));
-            RET_IF(o.ln_modulate(tr.res[2 * i], D, b.xnB, D, M, D, mb + 3 * D, mb + 4 * D, h->MODW, nullptr, P, &pend, h->err_flag, s));
-            have_pend = false;
-            memset(&g, 0, sizeof(g));
-            g.X = b.xnB; g.ldx = D; g.W = w.w_fc1; g.M = M; g.N = h->Hm; g.K = D; g.bias = w.b_fc1; g.out = b.u; g.ldo = h->Hm_pad; g.err_flag = h->err_flag;
-            if (g_fuse_gelu_fwd) g.out2 = b.hh;             // h = GELU(u) as a second image of the same epilogue (gemm.h out2)
-            RET_IF(o.gemm(g, EPI_F16_TILED, s));            // the pre-activation is kept: gelu'(u) in the backward pass
-            if (!g_fuse_gelu_fwd) RET_IF(h->ops(i).gelu_tiled(b.u, b.hh, (size_t)round_up(M, 128) * h->Hm_pad, s));
-            RET_IF(resid_gemm(o, b.hh, w.w_fc2, h->Hm_pad, w.b_fc2, mb + 5 * D, tr.res[2 * i + 2], b.y2));
-        }
+    for (int l = 0; l < L; ++l) RET_IF(train_block_forward(h, l, B, T, false, pend, have_pend, s));
     const float* mf = mod + (size_t)L * 12 * D;
     RET_IF(ofin.ln_modulate(tr.res[4 * L - 1], D, tr.xnF, D, M, D, mf, mf + D, h->MODW, nullptr, P, &pend, h->err_flag, s));
     memset(&g, 0, sizeof(g));
@@ -289,6 +371,7 @@ int gtav_dit_train_forward(gtav_dit* h, const float* x, const int64_t* t64, cons
     RET_IF(ofin.gemm(g, EPI_F32, s));
     RET_IF(launch_unpatchify(h->fo, h->Nfin, out, NB, h->C, h->H, h->W, h->p, 0, 1.f, 0.f, s));
     tr.B = B; tr.T = T; tr.M = M; tr.Mp = round_up(M, 64); tr.rows = rows; tr.have_actions = actions != nullptr; tr.have_fwd = true;
+    tr.rc_block = L - 1;   // (recompute mode: the ring states and the two image sets hold the last block)
     return 0;
 }
 
@@ -298,6 +381,8 @@ int gtav_dit_train_forward(gtav_dit* h, const float* x, const int64_t* t64, cons
 int gtav_dit_train_get_residual(gtav_dit* h, int32_t k, float* dst, int64_t numel, void* stream) {
     GTAV_REQUIRE(h && dst && h->tr.on && h->tr.have_fwd, "train_get_residual: no saved forward");
     GTAV_REQUIRE(k >= 0 && k <= 4 * h->L, "train_get_residual: k=%d must be in [0, %d]", k, 4 * h->L);
+    GTAV_REQUIRE(!h->tr.recompute || k % 4 == 0, "train_get_residual: k=%d is a state inside a block, which a handle in recompute mode (gtav_dit_train_set_recompute) "
+                 "does not keep: k must be a multiple of 4 (block inputs, 4 * depth = the input of the final layer)", k);
     GTAV_REQUIRE(numel == (int64_t)h->tr.M * h->D, "train_get_residual: expected %lld elements", (long long)h->tr.M * h->D);
     GTAV_CHECK_HIP(hipMemcpyAsync(dst, h->tr.res[k], numel * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
@@ -421,6 +506,8 @@ int gtav_dit_train_backward_phases(gtav_dit* h, const float* v_pred, const float
         const int l = i / 2, hf = i % 2;
         const int phase = L - l;
         if (phase < phase_begin || phase >= phase_end) continue;
+        // recompute mode: the activations of block l are rebuilt at the head of its phase (the last block's are still those of the forward)
+        if (tr.recompute && tr.rc_block != l) RET_IF(train_rerun_block(h, l, s));
         gtav_dit::Train::HB& b = tr.hb[i];
         char pre[64];
         snprintf(pre, sizeof(pre), "blocks.%d.%c_", l, hf == 0 ? 's' : 't');

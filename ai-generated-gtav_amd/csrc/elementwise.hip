@@ -96,7 +96,9 @@ __global__ __launch_bounds__(256) void ln_wave_row_kernel(const float* __restric
 #else
 #define LN_DBG(pd, b) false
 #endif
-template <int MODE, bool PEND>
+// KS: where the shift K of the statistics comes from (LnPending::k_save / k_load): 0 = the row's first element, 1 = the same and kept in pd.k_save[m],
+// 2 = pd.k_load[m] (the re-run of a launch that applied a pending update, from the updated row: same K, same sums, same bits)
+template <int MODE, bool PEND, int KS = 0>
 __global__ __launch_bounds__(512) void ln_row_block_kernel(float* __restrict__ x, int ldx, f16* __restrict__ out, int M, int D,
                                                            const float* __restrict__ p0, const float* __restrict__ p1,
                                                            int mod_stride, const int* __restrict__ rows, int rows_per_mod,
@@ -149,7 +151,7 @@ __global__ __launch_bounds__(512) void ln_row_block_kernel(float* __restrict__ x
         gr = m / pd.rows_per_gate;
         if (pd.gate_rows && !LN_DBG(pd, 0x2000)) gr = pd.gate_rows[gr];
     }
-    const float kshift = LN_DBG(pd, 0x200) ? 0.f : xr[0];   // the shift of the one-pass statistics below (same cache line as thread 0's own load)
+    const float kshift = LN_DBG(pd, 0x200) ? 0.f : KS == 2 ? pd.k_load[m] : xr[0];   // the shift of the one-pass statistics below (same cache line as thread 0's own load)
     if (act && !LN_DBG(pd, 0x100)) {
         av = *(const f32x4*)((MODE == 0 ? p1 + (size_t)row * mod_stride : p0) + c);
         bv = *(const f32x4*)((MODE == 0 ? p0 + (size_t)row * mod_stride : p1) + c);
@@ -167,6 +169,7 @@ __global__ __launch_bounds__(512) void ln_row_block_kernel(float* __restrict__ x
         }
         if (pd.gate) y = y * g4;
         v = v + y;
+        if (KS == 1 && threadIdx.x == 0) pd.k_save[m] = kshift;
         // (the updated row is stored BEHIND the block barrier of the statistics below: in place it overwrites xr[0], which every wave of the
         // block reads as the shift K of the one-pass statistics — a wave that started late must not see the updated value there)
     }
@@ -699,7 +702,13 @@ static int g_ln_wave_row_min = GTAV_ENV_INT("GTAV_LN_WAVE_ROW_MIN", 0);
         pd_.err_flag = err_flag;                                                                          \
         GTAV_REQUIRE(pd_.tperm_T == 0 || (pd_.tperm_P % 16 == 0 && M % (pd_.tperm_T * pd_.tperm_P) == 0), "ln: bad output row permutation"); \
         const bool upd_ = pend && pend->parts;   /* a LnPending without slabs carries the output row permutation only */ \
-        if (!upd_ && pd_.tperm_T == 0 && M >= g_ln_wave_row_min && (D == 256 || D == 512 || D == 1024 || D == 2048)) { \
+        GTAV_REQUIRE(!pd_.k_save || (upd_ && !pd_.k_load), "ln: k_save needs a pending update and excludes k_load");                          \
+        GTAV_REQUIRE(!pd_.k_load || !upd_, "ln: k_load excludes a pending update");                                                            \
+        if (pd_.k_save || pd_.k_load) { /* the statistics' shift kept / given: always one block per row (LnPending::k_save) */                 \
+            const dim3 g_(M), b_(round_up(D / 4, 64));                                                    \
+            if (pd_.k_save) GTAV_LAUNCH((ln_row_block_kernel<MODE, true, 1>), g_, b_, 0, stream, x, ldx, out, M, D, P0, P1, STRIDE, ROWS, RPM, pd_); \
+            else GTAV_LAUNCH((ln_row_block_kernel<MODE, false, 2>), g_, b_, 0, stream, x, ldx, out, M, D, P0, P1, STRIDE, ROWS, RPM, pd_);      \
+        } else if (!upd_ && pd_.tperm_T == 0 && M >= g_ln_wave_row_min && (D == 256 || D == 512 || D == 1024 || D == 2048)) { \
             if (D == 256) LN_WAVE_ROW_(MODE, 1, P0, P1, STRIDE, ROWS, RPM);                               \
             else if (D == 512) LN_WAVE_ROW_(MODE, 2, P0, P1, STRIDE, ROWS, RPM);                          \
             else if (D == 1024) LN_WAVE_ROW_(MODE, 4, P0, P1, STRIDE, ROWS, RPM);                         \

@@ -31,8 +31,14 @@ struct LnPending {
     // to row ((b * (tperm_P / 16) + p / 16) * tperm_T + t) * 16 + p % 16 — 16 positions x all frames of the window contiguous, the
     // X-tile order of the fused temporal QKV + attention GEMM (gemm.hip gemm_qkvt_attn_kernel).  0 = identity.
     int tperm_T, tperm_P;
+    // Shift K of the one-pass statistics (row-block kernel only; one float per row; both null: K = the row's first element before the pending update).
+    // k_save: the launch also stores its K there (needs `parts`).  k_load: the launch reads K from there and has no pending update: a training handle in
+    // recompute mode re-runs a block from its stored input state, which already holds the update the forward's launch applied, and gets the forward's
+    // bits only with the forward's K and the forward's reduction order (api_train.hip train_rerun_block).
+    float* k_save;
+    const float* k_load;
 };
-static_assert(sizeof(LnPending) == 104, "LnPending: every build and both operand types must see the same struct");
+static_assert(sizeof(LnPending) == 120, "LnPending: every build and both operand types must see the same struct");
 
 // LayerNorm outputs are GEMM A-operands: fp16 TILE-MAJOR with logical row length D (buffer rows padded to 128).
 // LayerNorm(eps=1e-6, no affine) + adaLN modulate -> fp16  (model/dit.py:19-27,163-181)

@@ -190,8 +190,19 @@ int gtav_timer_calibrate(int32_t spin_us, int32_t reps, double* event_us_mean, d
  * attention then runs its streaming kernel on windows of 9 .. 32 frames (gtav_op_attn_temporal_bwd) and the adaLN-gradient reduction its general kernel above 80
  * conditioning rows (max_batch x max_frames); windows of <= 8 frames run the same kernels and give the same bits as on a default handle.  What it costs: the saved
  * activations are sized by max_batch x max_frames at enable time, about 1.3 MB per token for DiT-S/2, i.e. about 6 GB for ONE 32-frame sample of
- * 144 tokens per frame.  The call itself allocates nothing. */
+ * 144 tokens per frame.  The call itself allocates nothing.
+ * Activation recomputation: gtav_dit_train_set_recompute(h, 1), called between gtav_dit_create and gtav_dit_train_enable[_typed] (it fails afterwards and changes
+ * nothing then), makes the training forward keep only the depth + 1 block-input residual states; every other saved activation exists for ONE block at a time (three
+ * residual states, the images of two half-blocks), and the backward pass re-runs a block's forward from its input state at the head of the block's phase (the last
+ * block's activations are still those of the forward).  The kernels are deterministic and the re-run repeats the forward's launches, so v_pred, the loss, the error
+ * words, every gradient and every optimizer step are the same bits as on a default handle; what changes is memory (DiT-S/2: 0.147 MB per token instead of 1.31,
+ * DESIGN.md 7) and time (measured at batch 16 x 5 frames x 144 tokens: 0.96 of the forward's time more per step, 48.5 -> 62.7 ms).  gtav_dit_train_get_residual then serves k % 4 == 0 only (the other states do not outlive their
+ * block).  The call itself allocates nothing; it combines with gtav_dit_train_allow_window, both operand types and every frame size.
+ * gtav_dit_train_saved_bytes: bytes of the saved-activation buffers of an enabled training handle in either mode (the residual states, the per-half-block images,
+ * the final LayerNorm's output, the patch matrix and, in recompute mode, 4 bytes per token and block of LayerNorm statistics' shifts). */
 int gtav_dit_train_allow_window(gtav_dit* h, int32_t max_frames);
+int gtav_dit_train_set_recompute(gtav_dit* h, int32_t enable);
+int gtav_dit_train_saved_bytes(gtav_dit* h, int64_t* bytes);
 int gtav_dit_train_param_count(gtav_dit* h, int64_t* numel);
 int gtav_dit_train_enable(gtav_dit* h, float* grad_arena_dev, int64_t grad_arena_numel);
 int gtav_dit_train_enable_typed(gtav_dit* h, float* grad_arena_dev, int64_t grad_arena_numel, int32_t dtype);
@@ -207,7 +218,8 @@ int gtav_dit_train_forward(gtav_dit* h, const float* x_dev, const int64_t* t_dev
  * gtav_dit_train_forward, v_target (B,C,H,W). */
 int gtav_dit_train_backward(gtav_dit* h, const float* v_pred_dev, const float* v_target_dev, void* stream);
 /* Residual stream of the last training forward: state r_k after k of the 4*depth branch additions (k even: 0 = patch embedding,
- * 4 = output of block 0, ..., 4*depth = input of the final layer), fp32 [B*T*P][hidden] in token order (b, t, p). */
+ * 4 = output of block 0, ..., 4*depth = input of the final layer), fp32 [B*T*P][hidden] in token order (b, t, p).  A handle in recompute mode
+ * (gtav_dit_train_set_recompute) keeps the states with k % 4 == 0 and refuses every other k. */
 int gtav_dit_train_get_residual(gtav_dit* h, int32_t k, float* dst_dev, int64_t numel, void* stream);
 /* The same pass in phases [phase_begin, phase_end): 0 = loss + final layer, p in 1..depth = block depth - p (after it every gradient named
  * "blocks.<depth-p>.*" is complete), depth + 1 = patch embedding + timestep / action embedders.  Lets the host all-reduce one block's
