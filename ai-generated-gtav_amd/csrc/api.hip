@@ -140,19 +140,17 @@ static int op_sk_workspace(GemmParams& g) {
 int gtav_op_gemm_f16(const void* x, int32_t ldx, const void* w, const float* bias, void* out, int32_t ldo, int32_t M, int32_t N,
                      int32_t K, int32_t epilogue, const float* gate, int32_t gate_stride, int32_t rows_per_gate, void* stream) {
     GTAV_REQUIRE((epilogue >= 0 && epilogue <= 4) || epilogue == EPI_PARTIAL || epilogue == EPI_F16_TILED, "op_gemm_f16: epilogue %d", epilogue);
-    GemmParams g;
-    memset(&g, 0, sizeof(g));
+    GemmParams g = gemm_params((const f16*)x, ldx, (const f16*)w, M, N, K);
     RET_IF(op_sk_workspace(g));
     if (epilogue == EPI_PARTIAL) g.splitk = gate_stride > 0 ? gate_stride : 1;  // split-K factor travels in gate_stride
-    g.X = (const f16*)x; g.ldx = ldx; g.W = (const f16*)w; g.M = M; g.N = N; g.K = K; g.bias = bias; g.out = out; g.ldo = ldo;
+    g.bias = bias; g.out = out; g.ldo = ldo;
     g.gate = gate; g.gate_stride = gate_stride; g.rows_per_gate = rows_per_gate;
     return op_ops().gemm(g, epilogue, (hipStream_t)stream);
 }
 int gtav_op_gemm_qkv(const void* x, int32_t ldx, const void* w, const float* bias, int32_t M, int32_t D, int32_t mode, void* q,
                      void* k, void* v, int32_t S, int32_t Tq, int32_t t0, int32_t Tmax, const float* rope_cs, void* stream) {
-    GemmParams g;
-    memset(&g, 0, sizeof(g));
-    g.X = (const f16*)x; g.ldx = ldx; g.W = (const f16*)w; g.M = M; g.N = 3 * D; g.K = D; g.bias = bias; g.D = D; g.S = S;
+    GemmParams g = gemm_params((const f16*)x, ldx, (const f16*)w, M, 3 * D, D);
+    g.bias = bias; g.D = D; g.S = S;
     g.qkv_mode = mode; g.q = (f16*)q; g.k = (f16*)k; g.v = (f16*)v; g.Tq = Tq; g.t0 = t0; g.Tmax = Tmax;
     g.rope_cs = rope_cs;
     return op_ops().gemm(g, EPI_QKV, (hipStream_t)stream);
@@ -160,9 +158,8 @@ int gtav_op_gemm_qkv(const void* x, int32_t ldx, const void* w, const float* bia
 #ifdef GTAV_EXPERIMENTS   // csrc/experiments.h
 int gtav_op_gemm_fold_producer(const void* x, const void* w, const float* bias, float* resid, int32_t M, int32_t N, int32_t K, const float* gate,
                                const float* next_scale, int32_t mod_stride, int32_t tokens_per_frame, void* a_out, float* stats_out, void* stream) {
-    GemmParams g;
-    memset(&g, 0, sizeof(g));
-    g.X = (const f16*)x; g.ldx = K; g.W = (const f16*)w; g.M = M; g.N = N; g.K = K; g.bias = bias; g.out = resid; g.ldo = N;
+    GemmParams g = gemm_params((const f16*)x, K, (const f16*)w, M, N, K);
+    g.bias = bias; g.out = resid; g.ldo = N;
     g.gate = gate; g.gate_stride = mod_stride; g.rows_per_gate = tokens_per_frame;
     g.f_P = tokens_per_frame; g.f_scale = next_scale; g.f_stats_out = stats_out; g.f_a = (f16*)a_out;
     return launch_gemm(g, EPI_RESID_FOLD, (hipStream_t)stream);
@@ -170,9 +167,8 @@ int gtav_op_gemm_fold_producer(const void* x, const void* w, const float* bias, 
 int gtav_op_gemm_fold_consumer(const void* a, const void* w, int32_t M, int32_t N, int32_t K, int32_t epi, const float* stats, const float* c1, const float* c2,
                                int32_t ldc, int32_t tokens_per_frame, void* out, int32_t ldo, void* stream) {
     GTAV_REQUIRE(epi == EPI_F32 || epi == EPI_GELU_TANH, "gemm_fold_consumer: epilogue %d (0 = f32 row-major, 2 = GELU-tanh fp16 tile-major)", epi);
-    GemmParams g;
-    memset(&g, 0, sizeof(g));
-    g.X = (const f16*)a; g.ldx = K; g.W = (const f16*)w; g.M = M; g.N = N; g.K = K; g.out = out; g.ldo = ldo;
+    GemmParams g = gemm_params((const f16*)a, K, (const f16*)w, M, N, K);
+    g.out = out; g.ldo = ldo;
     g.f_P = tokens_per_frame; g.f_stats = stats; g.f_nslot = K / 64; g.f_c1 = c1; g.f_c2 = c2; g.f_ldc = ldc;
     return launch_gemm(g, epi == EPI_F32 ? EPI_F32_FOLD : EPI_GELU_TANH_FOLD, (hipStream_t)stream);
 }
@@ -215,9 +211,8 @@ int gtav_op_qkv_head_major(const void* w, void* w_hm, int32_t D, void* stream) {
 int gtav_op_gemm_qkvt_attn(const void* x_tperm, const void* w_hm, int32_t M, int32_t D, int32_t P, int32_t Tq, int32_t t0,
                            int32_t Tmax, const float* rope_cs, void* kv, void* o, void* stream) {
     GTAV_OP_F16_ONLY("op_gemm_qkvt_attn");
-    GemmParams g;
-    memset(&g, 0, sizeof(g));
-    g.X = (const f16*)x_tperm; g.ldx = D; g.W = (const f16*)w_hm; g.M = M; g.N = 3 * D; g.K = D; g.D = D; g.S = P;
+    GemmParams g = gemm_params((const f16*)x_tperm, D, (const f16*)w_hm, M, 3 * D, D);
+    g.D = D; g.S = P;
     g.qkv_mode = QKV_TEMPORAL; g.k = (f16*)kv; g.v = (f16*)kv; g.out = o; g.ldo = D; g.Tq = Tq; g.t0 = t0; g.Tmax = Tmax;
     g.rope_cs = rope_cs;
     return launch_gemm_qkvt_attn(g, (hipStream_t)stream);
@@ -228,9 +223,8 @@ int gtav_op_qkv_head_major_spatial(const void* w, void* w_hm, int32_t D, void* s
 }
 int gtav_op_gemm_qkvs_attn(const void* x, const void* w_hm, int32_t M, int32_t D, int32_t P, const float* rope_cs, void* o, void* stream) {
     GTAV_OP_F16_ONLY("op_gemm_qkvs_attn");
-    GemmParams g;
-    memset(&g, 0, sizeof(g));
-    g.X = (const f16*)x; g.ldx = D; g.W = (const f16*)w_hm; g.M = M; g.N = 3 * D; g.K = D; g.D = D; g.S = P;
+    GemmParams g = gemm_params((const f16*)x, D, (const f16*)w_hm, M, 3 * D, D);
+    g.D = D; g.S = P;
     g.qkv_mode = QKV_SPATIAL; g.out = o; g.ldo = D; g.rope_cs = rope_cs;
     return launch_gemm_qkvs_attn(g, (hipStream_t)stream);
 }
@@ -261,9 +255,8 @@ int gtav_op_attn_temporal_bwd_bf16(const void* q, const void* kv, const void* d_
     return op_attn_temporal_bwd(true, q, kv, d_o, B, P, D, T, Tmax, rope_cs, dqkv, stream);
 }
 int gtav_op_gemm_tn(const void* x, const void* w, int32_t M, int32_t N, int32_t K, float* out, int32_t ldo, void* stream) {
-    GemmParams q;
-    memset(&q, 0, sizeof(q));
-    q.X = (const f16*)x; q.ldx = M; q.W = (const f16*)w; q.M = M; q.N = N; q.K = K; q.out = out; q.ldo = ldo;
+    GemmParams q = gemm_params((const f16*)x, M, (const f16*)w, M, N, K);
+    q.out = out; q.ldo = ldo;
     return op_ops().gemm_tn(q, (hipStream_t)stream);
 }
 int gtav_op_gemm_dw_grouped(int32_t n, const void* const* x, const void* const* w, float* const* out, const int32_t* M, const int32_t* N, const int32_t* ldo,
@@ -277,9 +270,8 @@ int gtav_op_gemm_splitk_ln(const void* x, int32_t ldx, const void* w, const floa
                            int32_t splitk, float* parts, float* resid, const float* gate, int32_t gate_stride,
                            int32_t rows_per_gate, void* out_f16, const float* shift, const float* scale, int32_t mod_stride,
                            void* stream) {
-    GemmParams g;
-    memset(&g, 0, sizeof(g));
-    g.X = (const f16*)x; g.ldx = ldx; g.W = (const f16*)w; g.M = M; g.N = N; g.K = K; g.out = parts; g.ldo = N;
+    GemmParams g = gemm_params((const f16*)x, ldx, (const f16*)w, M, N, K);
+    g.out = parts; g.ldo = N;
     g.splitk = splitk > 0 ? splitk : gemm_choose_splitk(M, N, K);
     RET_IF(op_ops().gemm(g, EPI_PARTIAL, (hipStream_t)stream));
     LnPending pd;

@@ -63,6 +63,14 @@ static int fold_alloc(gtav_dit* h) {
 // the fused spatial to_qkv + attention launch: from 5 frames on (measured from 80 blocks up; a context-cached batch-1 step is 16 blocks: the split path's skinny kernels serve it)
 static bool fused_spatial_ok(int M, int D, int P) { return gemm_qkvs_attn_ok(M, D, P) && M / P >= 5 && (M / P) * (D / 64) >= 80; }
 
+// Does half-block hb run its to_qkv projection and its attention as ONE launch, at M tokens in Tq frames from window index t0?  (Temporal halves: batch-1 window
+// steps, gemm_qkvt_attn_kernel; spatial halves: gemm_qkvs_attn_kernel.)  The forward, its prefetch plan and gtav_dit_fused_launches all ask here: the prefetch must
+// warm the weight image the launch reads, and bench.py's launch accounting must report what the step did.  (A spatial half behind a folded seam B steps aside.)
+static bool dit_half_fused(const gtav_dit* h, int hb, int M, int Tq, int t0) {
+    if (h->tr.on || h->ops(hb).bf16 || !h->halves[hb].w_qkv_hm) return false;
+    return (hb & 1) ? h->fuse_tattn && gemm_qkvt_attn_ok(M, h->D, h->P, Tq, t0) : h->fuse_sattn && fused_spatial_ok(M, h->D, h->P);
+}
+
 // LayerNorm fold: which seams run folded at M tokens (seam A = out-proj -> fc1, seam B = fc2 -> next to_qkv / final projection)
 static void fold_policy(const gtav_dit* h, int M, bool& fa, bool& fb) {
     const gtav_dit::Fold& f = h->fold;
@@ -84,19 +92,85 @@ static int dit_fold_tables(gtav_dit* h, int rows, bool fa, bool fb, hipStream_t 
     return launch_gemm_grouped(f.groups_dev, ng, h->Hm > 3 * h->D ? h->Hm : 3 * h->D, rows, h->D, s);
 #endif
 }
+// consumer side of a folded seam: q.X = xn holds x (1 + scale), statistics in fold.stats, tables of seam `seam` (N columns each) in ctab
+static void fold_consumer(const gtav_dit* h, GemmParams& q, int seam, int N, const int* mod_rows, const float* ctab) {
+    const gtav_dit::Fold& fo = h->fold;
+    q.bias = nullptr;
+    q.f_P = h->P; q.f_rows = mod_rows; q.f_stats = fo.stats; q.f_nslot = h->D / 64;
+    q.f_c1 = ctab + fo.col_c[seam]; q.f_c2 = q.f_c1 + N; q.f_ldc = fo.CTW;
+}
+// producer side: in-place gated residual update + operand and statistics of the LayerNorm that follows (scale vectors at `next_scale`)
+static int fold_producer(gtav_dit* h, int cls, const f16* X, const f16* Wt, int M, int K, const float* bias, const ResidGate& gt, const float* next_scale, hipStream_t s) {
+    GemmParams q = gemm_params(X, K, Wt, M, h->D, K);
+    q.out = h->resid; q.ldo = h->D; q.bias = bias; q.err_flag = h->err_flag;
+    q.gate = gt.gate; q.gate_stride = gt.stride; q.gate_rows = gt.rows; q.rows_per_gate = gt.rows_per_gate;
+    q.f_P = h->P; q.f_rows = gt.rows; q.f_scale = next_scale; q.f_stats_out = h->fold.stats; q.f_a = h->xn;
+    PROF(h, cls, s, launch_gemm(q, EPI_RESID_FOLD, s));
+    return 0;
+}
+
+// the conditioning MLP over `rows` rows of E / HC (launch_cond_inputs*): timestep embedding -> c (+ actions) -> the modulation table h->mod
+static int dit_cond_mlp(gtav_dit* h, int rows, bool have_actions, hipStream_t s) {
+    const int ldhc = h->D + h->Apad;
+    RET_IF(launch_skinny_f32(h->E, 256, h->w_t0, h->b_t0, h->HC, ldhc, rows, h->D, 256, 1, s));
+    RET_IF(launch_skinny_f32(h->HC, ldhc, h->w_t2cat, have_actions ? h->b_t2a : h->b_t2, h->Sc, h->D, rows, h->D, ldhc, 1, s));
+    return launch_skinny_f32(h->Sc, h->D, h->w_ada, h->b_ada, h->mod, h->MODW, rows, h->MODW, h->D, 0, s);
+}
 
 static int dit_cond(gtav_dit* h, const int64_t* t64, int rows, int Tq, const StepParams* sp, int use_cur, const float* actions,
                     int64_t act_outer, int64_t act_inner, hipStream_t s) {
     GTAV_REQUIRE(rows <= h->max_rows, "conditioning rows %d exceed max_cond_rows %d", rows, h->max_rows);
-    const int ldhc = h->D + h->Apad;
-    RET_IF(launch_cond_inputs(t64, rows, Tq, sp, use_cur, h->sincos, h->E, actions, act_outer, act_inner, h->A, h->HC, ldhc,
+    RET_IF(launch_cond_inputs(t64, rows, Tq, sp, use_cur, h->sincos, h->E, actions, act_outer, act_inner, h->A, h->HC, h->D + h->Apad,
                               h->D, h->Apad, h->err_flag, s));
-    RET_IF(launch_skinny_f32(h->E, 256, h->w_t0, h->b_t0, h->HC, ldhc, rows, h->D, 256, 1, s));
-    RET_IF(launch_skinny_f32(h->HC, ldhc, h->w_t2cat, actions ? h->b_t2a : h->b_t2, h->Sc, h->D, rows, h->D, ldhc, 1, s));
-    RET_IF(launch_skinny_f32(h->Sc, h->D, h->w_ada, h->b_ada, h->mod, h->MODW, rows, h->MODW, h->D, 0, s));
+    RET_IF(dit_cond_mlp(h, rows, actions != nullptr, s));
     bool fa, fb;
     fold_policy(h, rows * h->P, fa, fb);     // one forward over these rows' frames: the LayerNorm-fold tables of the seams it will fold
     return dit_fold_tables(h, rows, fa, fb, s);
+}
+
+// L2 prefetch of the NEXT GEMM's weight by the loader-wave kernels (gemm.h pf_next), planned once per forward: at the few hundred tokens of a batch-1 step every
+// launch otherwise starts on weights that come from HBM.
+// (Not at the 144 tokens of a context-cached step: those launches are short weight streams themselves, and a second stream beside them cost 1.5 % of the step —
+// profiles/round3/sampler_ab_cached_skinny_shapes_and_prefetch.txt.)
+// (Prefetching for to_qkv / fc1 from the LayerNorm launch right in front of them instead — 64 extra blocks beside its row blocks — gained nothing for the consumers
+// and made every LayerNorm 1.6 us longer: profiles/round3/*prefetch_from_layernorm_vs_from_gemm.txt.  The issuing GEMM pays 0.6-0.9 us for its prefetch, the
+// consumer gains 1.5-2 us.)
+struct DitPrefetch {
+    const gtav_dit* h;
+    int M, Tq, t0;
+    bool on;
+    DitPrefetch(const gtav_dit* h_, int M_, int Tq_, int t0_) : h(h_), M(M_), Tq(Tq_), t0(t0_) {
+        const int pf_max_m = 1536;   // (above: measured slower, the persistent large-M kernels lose more than their successors gain)
+        static const int pf_min_m = GTAV_ENV_INT("GTAV_PF_MIN_M", 256);   // 320 tokens (window step of the 256 x 256-frame preset): -2.1 %; 144 (cached step): +1.5 %; experiments build: A/B
+        on = h->w_prefetch && M >= pf_min_m && M <= pf_max_m;
+    }
+    // what the GEMM launch at position `pos` of half-block `hb` (launch order: 0 to_qkv, 1 out-proj, 2 fc1, 3 fc2) prefetches: the weight of the next GEMM launch of
+    // the step, nothing past the last half-block.  (One more launch of lead — the weight of the GEMM after the next — was measured in round 5 and gained nothing on
+    // either kind of GPU: profiles/round5/prefetch_box_survey.txt.)
+    PrefetchDesc after(int hb, int pos) const {
+        const int q = pos + 1, hb2 = hb + q / 4, consumer = (q + 3) % 4;   // class of the next launch in gtav_dit::w_prefetch_cls: 3 to_qkv, 0 out-proj, 1 fc1, 2 fc2
+        if (!on || hb2 >= 2 * h->L) return kNoPrefetch;
+        const int v = h->w_prefetch_cls[consumer];      // 0 skip, 1 the whole slice, k >= 2: the first k K tiles of every row tile
+        if (!v) return kNoPrefetch;
+        const gtav_dit::Half& w2 = h->halves[hb2];
+        const int D = h->D;
+        const f16* W; int N, K, sk = 1;
+        if (consumer == 3) { W = dit_half_fused(h, hb2, M, Tq, t0) ? w2.w_qkv_hm : w2.w_qkv; N = 3 * D; K = D; }
+        else if (consumer == 0) { W = w2.w_out; N = D; K = D; sk = gemm_choose_splitk(M, D, D); }
+        else if (consumer == 1) { W = w2.w_fc1; N = h->Hm; K = D; }
+        else { W = w2.w_fc2; N = D; K = h->Hm_pad; sk = gemm_choose_splitk(M, D, h->Hm_pad); }
+        const int nkt = K / 64;
+        if (sk < 1 || nkt % sk || (sk >= 8 ? sk % 8 : 8 % sk)) sk = 1;
+        return PrefetchDesc{W, cdiv(N, 128), nkt, sk, v >= 2 ? v : 0};
+    }
+};
+
+// Large M: the gated residual update x += gate * (acc + bias) in the epilogue of the persistent ping-pong GEMM instead of slabs — its read-modify-write hides under the
+// other wave group's main loop, and without split-K slabs the next LayerNorm only reads resid.  (With the one-shot kernels the same epilogue was a loss: B = 8 out-proj
+// 0.77 -> 1.26 ms per forward; resid_inplace_min_m keeps that experiment reachable in the experiments build.)  (Also on training handles: this plain forward keeps no
+// activations.)
+static bool dit_resid_inplace(const gtav_dit* h, int M, int K) {
+    return gemm_pp_ok(M, h->D, K, EPI_RESID) || (gemm_choose_splitk(M, h->D, K) == 1 && M >= h->resid_inplace_min_m) || gemm_resid_inplace_ok(M, h->D, K, h->P);
 }
 
 // x_src: frames of C*H*W floats; frame_index (device, optional) selects the NB = B*Tq frames to process.
@@ -107,178 +181,80 @@ static int dit_forward_core(gtav_dit* h, const float* x_src, const int* frame_in
     GTAV_REQUIRE(M <= h->Mmax, "forward: %d tokens exceed workspace (%d)", M, h->Mmax);
     bool fold_a, fold_b;
     fold_policy(h, M, fold_a, fold_b);
-    const gtav_dit::Fold& fo = h->fold;
-    // consumer side of a folded seam: X = xn holds x (1 + scale), statistics in fo.stats, tables of seam `seam`
-    auto fold_consumer = [&](GemmParams& q, int seam, int N) {
-        q.bias = nullptr;
-        q.f_P = P; q.f_rows = mod_rows; q.f_stats = fo.stats; q.f_nslot = D / 64;
-        q.f_c1 = ctab + fo.col_c[seam]; q.f_c2 = q.f_c1 + N; q.f_ldc = fo.CTW;
-    };
-    // producer side: in-place gated residual update + operand and statistics of the LayerNorm that follows (scale vectors at `next_scale`)
-    auto fold_producer = [&](int cls, const f16* X, const f16* Wt, int K, const float* bias, const float* gate, const float* next_scale) -> int {
-        GemmParams q;
-        memset(&q, 0, sizeof(q));
-        q.X = X; q.ldx = K; q.W = Wt; q.M = M; q.N = D; q.K = K; q.out = h->resid; q.ldo = D; q.bias = bias; q.err_flag = h->err_flag;
-        q.gate = gate; q.gate_stride = h->MODW; q.gate_rows = mod_rows; q.rows_per_gate = P;
-        q.f_P = P; q.f_rows = mod_rows; q.f_scale = next_scale; q.f_stats_out = fo.stats; q.f_a = h->xn;
-        PROF(h, cls, s, launch_gemm(q, EPI_RESID_FOLD, s));
+    const DitPrefetch pf(h, M, Tq, t0);
+    DeferredResid rd{h->parts, h->parts_rows * (size_t)D, h->resid, M, D, &h->prof, s};
+    auto gate = [&](const float* g) { return ResidGate{g, h->MODW, mod_rows, P}; };
+    auto ln = [&](const OperandOps& o, const float* shift, const float* scale, int* ef) -> int {   // resid (+ the pending update) -> xn
+        PROF(h, PC_LN, s, o.ln_modulate(h->resid, D, h->xn, D, M, D, shift, scale, h->MODW, mod_rows, P, rd.take(), ef, s));
         return 0;
     };
     const int g_embed = 2 * h->L, g_final = 2 * h->L + 1;      // operand groups (gtav_dit::grp_bf16)
     // (patchify reports a non-finite input and a finite latent beyond the fp16 range into the embedding group's word: gtav_dit_check folds every word together)
     PROF(h, PC_OTHER, s, h->ops(g_embed).patchify(x_src, frame_index, NB, h->C, h->H, h->W, h->p, h->xp, h->Kpe, 1.f, 0.f, h->err_of(g_embed), s));
-    GemmParams g;
-    memset(&g, 0, sizeof(g));
-    g.X = h->xp; g.ldx = h->Kpe; g.W = h->w_pe; g.M = M; g.N = D; g.K = h->Kpe; g.bias = h->b_pe; g.out = h->resid; g.ldo = D;
-    PROF(h, PC_OTHER, s, h->ops(g_embed).gemm(g, EPI_F32, s));
-    // Residual GEMMs (out-proj, fc2) write split-K partial slabs; the LayerNorm that always follows reduces them and
-    // applies bias + gate + residual (LnPending), so the GEMM epilogue has no read-modify-write and small-M
-    // launches can spread their K loop over all CUs.
-    LnPending pend;
-    bool have_pend = false;
-    // L2 prefetch of the NEXT GEMM's weight by the loader-wave kernels (gemm.h pf_next): at the few hundred tokens of a batch-1 step every launch
-    // otherwise starts on weights that come from HBM
-    const int pf_max_m = 1536;   // (above: measured slower, the persistent large-M kernels lose more than their successors gain)
-    // (not at the 144 tokens of a context-cached step: those launches are short weight streams themselves, and a second stream beside them cost
-    // 1.5 % of the step — profiles/round3/sampler_ab_cached_skinny_shapes_and_prefetch.txt)
-    // (Prefetching for to_qkv / fc1 from the LayerNorm launch right in front of them instead — 64 extra blocks beside its row blocks — gained nothing
-    // for the consumers and made every LayerNorm 1.6 us longer: profiles/round3/*prefetch_from_layernorm_vs_from_gemm.txt.  The issuing GEMM pays
-    // 0.6-0.9 us for its prefetch, the consumer gains 1.5-2 us.)
-    static const int pf_min_m = GTAV_ENV_INT("GTAV_PF_MIN_M", 256);   // 320 tokens (window step of the 256 x 256-frame preset): -2.1 %; 144 (cached step): +1.5 %; experiments build: A/B
-    const bool pf_on = h->w_prefetch && M >= pf_min_m && M <= pf_max_m;
-    // what the GEMM launch at position `pos` of half-block `hb` (launch order: 0 to_qkv, 1 out-proj, 2 fc1, 3 fc2) prefetches: the weight of the next GEMM
-    // launch of the step.  (One more launch of lead — the weight of the GEMM after the next — was measured in round 5 and gained nothing on either kind
-    // of GPU: profiles/round5/prefetch_box_survey.txt.)
-    struct PfNext { const f16* W; int N, K, sk, consumer; };
-    auto pf_target = [&](int hb, int pos) -> PfNext {
-        const int q = pos + 1, hb2 = hb + q / 4, p2 = q % 4;
-        if (!pf_on || hb2 >= 2 * h->L) return PfNext{nullptr, 0, 0, 1, 0};
-        const gtav_dit::Half& w2 = h->halves[hb2];
-        if (p2 == 0) {
-            const bool fused2 = !h->tr.on && w2.w_qkv_hm && !h->ops(hb2).bf16 &&
-                                ((hb2 & 1) ? h->fuse_tattn && gemm_qkvt_attn_ok(M, D, P, Tq, t0) : h->fuse_sattn && fused_spatial_ok(M, D, P));
-            return PfNext{fused2 ? w2.w_qkv_hm : w2.w_qkv, 3 * D, D, 1, 3};
-        }
-        if (p2 == 1) return PfNext{w2.w_out, D, D, gemm_choose_splitk(M, D, D), 0};
-        if (p2 == 2) return PfNext{w2.w_fc1, h->Hm, D, 1, 1};
-        return PfNext{w2.w_fc2, D, h->Hm_pad, gemm_choose_splitk(M, D, h->Hm_pad), 2};
-    };
-    auto set_pf = [&](GemmParams& q, const PfNext& t) {
-        const int v = h->w_prefetch_cls[t.consumer];      // 0 skip, 1 the whole slice, k >= 2: the first k K tiles of every row tile
-        if (!pf_on || !t.W || !v) return;
-        const int nkt = t.K / 64;
-        int skn = t.sk;
-        if (skn < 1 || nkt % skn || (skn >= 8 ? skn % 8 : 8 % skn)) skn = 1;
-        q.pf = PrefetchDesc{t.W, cdiv(t.N, 128), nkt, skn, v >= 2 ? v : 0};
-    };
-    auto resid_gemm = [&](const OperandOps& ops, int cls, const f16* X, int ldx, const f16* Wt, int K, const float* bias, const float* gate, const PfNext& pfn) -> int {
-        GemmParams q;
-        memset(&q, 0, sizeof(q));
-        q.X = X; q.ldx = ldx; q.W = Wt; q.M = M; q.N = D; q.K = K; q.out = h->parts; q.ldo = D;
-        set_pf(q, pfn);
-        q.splitk = gemm_choose_splitk(M, D, K);
-        if (gemm_pp_ok(M, D, K, EPI_RESID) || (q.splitk == 1 && M >= h->resid_inplace_min_m) || gemm_resid_inplace_ok(M, D, K, P)) {   // (also on training handles: this plain forward keeps no activations)
-            // Large M: gated residual update x += gate * (acc + bias) in the epilogue of the persistent ping-pong GEMM — its
-            // read-modify-write hides under the other wave group's main loop, and without split-K slabs the next LayerNorm only
-            // reads resid.  (With the one-shot kernels the same epilogue was a loss: B = 8 out-proj 0.77 -> 1.26 ms per forward;
-            // resid_inplace_min_m keeps that experiment reachable in the experiments build.)
-            q.splitk = 0; q.out = h->resid; q.bias = bias; q.gate = gate; q.gate_stride = h->MODW; q.gate_rows = mod_rows;
-            q.rows_per_gate = P;
-            PROF(h, cls, s, ops.gemm(q, EPI_RESID, s));
-            have_pend = false;
-            return 0;
-        }
-        GTAV_REQUIRE((size_t)q.splitk * M <= h->parts_rows, "split-K slabs exceed workspace");
-        PROF(h, cls, s, ops.gemm(q, EPI_PARTIAL, s));
-        memset(&pend, 0, sizeof(pend));
-        pend.parts = h->parts; pend.nsplit = q.splitk; pend.slab_stride = (size_t)M * D; pend.ld = D; pend.bias = bias;
-        pend.gate = gate; pend.gate_stride = h->MODW; pend.gate_rows = mod_rows; pend.rows_per_gate = P;
-        have_pend = true;
-        return 0;
-    };
+    GemmParams pe = gemm_params(h->xp, h->Kpe, h->w_pe, M, D, h->Kpe);
+    pe.bias = h->b_pe; pe.out = h->resid; pe.ldo = D;
+    PROF(h, PC_OTHER, s, h->ops(g_embed).gemm(pe, EPI_F32, s));
     bool folded_in = false;   // the LayerNorm in front of the next to_qkv / final projection was folded into the fc2 before it (seam B)
-    for (int l = 0; l < h->L; ++l) {
-        for (int hf = 0; hf < 2; ++hf) {
-            const int hb = l * 2 + hf;
-            const gtav_dit::Half& w = h->halves[hb];
-            const OperandOps& ops = h->ops(hb);     // this half-block's operand type: every 2-byte tensor below lives and dies inside the half-block
-            int* const ef = h->err_of(hb);
-            const float* mb = mod + (size_t)hb * 6 * D;
-            // temporal half of a batch-1 window step: QKV projection and attention in one launch, on LayerNorm rows written in
-            // (b, 16 positions, frame) tile order
-            const bool fused_t = hf == 1 && h->fuse_tattn && !h->tr.on && !ops.bf16 && w.w_qkv_hm && gemm_qkvt_attn_ok(M, D, P, Tq, t0);
-            if (fused_t) {
-                if (!have_pend) memset(&pend, 0, sizeof(pend));   // no slabs (the residual GEMM before updated in place): the descriptor carries the row permutation only
-                pend.tperm_T = Tq; pend.tperm_P = P;
-            }
-            if (!folded_in)
-                PROF(h, PC_LN, s, ops.ln_modulate(h->resid, D, h->xn, D, M, D, mb, mb + D, h->MODW, mod_rows, P, (have_pend || fused_t) ? &pend : nullptr, ef, s));
-            have_pend = false;
-            memset(&g, 0, sizeof(g));
-            g.X = h->xn; g.ldx = D; g.W = w.w_qkv; g.M = M; g.N = 3 * D; g.K = D; g.D = D; g.S = P; g.err_flag = ef;
-            if (folded_in) fold_consumer(g, 2 * hb, 3 * D);
-            set_pf(g, pf_target(hb, 0));
-            const bool fused_s = hf == 0 && h->fuse_sattn && !h->tr.on && !ops.bf16 && !folded_in && w.w_qkv_hm && fused_spatial_ok(M, D, P);
-            if (fused_t) {
-                g.W = w.w_qkv_hm; g.qkv_mode = QKV_TEMPORAL; g.k = h->kvcache[l]; g.v = h->kvcache[l]; g.out = h->ao; g.ldo = D;
-                g.Tq = Tq; g.t0 = t0; g.Tmax = h->maxT; g.rope_cs = h->rope_t.cs_dev;
-                PROF(h, PC_ATTN_T, s, launch_gemm_qkvt_attn(g, s));   // profiled as the attention class: one class = one kernel (gtav_dit_fused_launches tells a reader which it was)
-            } else if (fused_s) {
-                g.W = w.w_qkv_hm; g.qkv_mode = QKV_SPATIAL; g.out = h->ao; g.ldo = D; g.rope_cs = h->rope_s.cs_dev;
-                PROF(h, PC_ATTN_S, s, launch_gemm_qkvs_attn(g, s));
-            } else {
-                if (hf == 0) {
-                    g.qkv_mode = QKV_SPATIAL; g.q = h->qs; g.k = h->ks; g.v = h->vts;
-                    g.rope_cs = h->rope_s.cs_dev;
-                } else {
-                    g.qkv_mode = QKV_TEMPORAL; g.q = h->qt; g.k = h->kvcache[l]; g.v = h->kvcache[l];
-                    g.Tq = Tq; g.t0 = t0; g.Tmax = h->maxT;
-                    g.rope_cs = h->rope_t.cs_dev;
-                }
-                PROF(h, PC_QKV, s, ops.gemm(g, folded_in ? EPI_QKV_FOLD : EPI_QKV, s));
-                if (hf == 0) PROF(h, PC_ATTN_S, s, ops.attn_spatial(h->qs, h->ks, h->vts, h->ao, NB, h->heads, P, s, false));
-                else PROF(h, PC_ATTN_T, s, ops.attn_temporal(h->qt, h->kvcache[l], h->ao, B, P, D, Tq, t0, h->maxT, s));
-            }
-            folded_in = false;
-            memset(&g, 0, sizeof(g));
-            g.X = h->xn; g.ldx = D; g.W = w.w_fc1; g.M = M; g.N = h->Hm; g.K = D; g.bias = w.b_fc1; g.out = h->hbuf; g.ldo = h->Hm_pad; g.err_flag = ef;
-            set_pf(g, pf_target(hb, 2));
-            if (fold_a) {
-                // seam A: out-proj updates the residual in place and emits fc1's operand + row statistics; fc1 normalises in its epilogue
-                RET_IF(fold_producer(PC_OUT, h->ao, w.w_out, D, w.b_out, mb + 2 * D, mb + 4 * D));
-                fold_consumer(g, 2 * hb + 1, h->Hm);
-                PROF(h, PC_FC1, s, launch_gemm(g, EPI_GELU_TANH_FOLD, s));
-            } else {
-                RET_IF(resid_gemm(ops, PC_OUT, h->ao, D, w.w_out, D, w.b_out, mb + 2 * D, pf_target(hb, 1)));
-                PROF(h, PC_LN, s, ops.ln_modulate(h->resid, D, h->xn, D, M, D, mb + 3 * D, mb + 4 * D, h->MODW, mod_rows, P, have_pend ? &pend : nullptr, ef, s));
-                have_pend = false;
-                PROF(h, PC_FC1, s, ops.gemm(g, EPI_GELU_TANH, s));
-            }
-            if (fold_b) {
-                // seam B: the LayerNorm that follows fc2 is the next half-block's first one (scale_msa) or the final layer's
-                const float* next_scale = hb + 1 < 2 * h->L ? mod + (size_t)(hb + 1) * 6 * D + D : mod + (size_t)h->L * 12 * D + D;
-                RET_IF(fold_producer(PC_FC2, h->hbuf, w.w_fc2, h->Hm_pad, w.b_fc2, mb + 5 * D, next_scale));
-                folded_in = true;
-            } else {
-                RET_IF(resid_gemm(ops, PC_FC2, h->hbuf, h->Hm_pad, w.w_fc2, h->Hm_pad, w.b_fc2, mb + 5 * D, pf_target(hb, 3)));
-            }
+    for (int hb = 0; hb < 2 * h->L; ++hb) {
+        const int l = hb / 2, hf = hb % 2;
+        const gtav_dit::Half& w = h->halves[hb];
+        const OperandOps& ops = h->ops(hb);     // this half-block's operand type: every 2-byte tensor below lives and dies inside the half-block
+        int* const ef = h->err_of(hb);
+        const float* mb = mod + (size_t)hb * 6 * D;
+        // temporal half of a batch-1 window step: QKV projection and attention in one launch, on LayerNorm rows written in (b, 16 positions, frame) tile order
+        const bool fused = dit_half_fused(h, hb, M, Tq, t0), fused_t = fused && hf == 1, fused_s = fused && hf == 0 && !folded_in;
+        if (fused_t) rd.permute_rows(Tq, P);
+        if (!folded_in) RET_IF(ln(ops, mb, mb + D, ef));
+        GemmParams g = gemm_params(h->xn, D, fused_t || fused_s ? w.w_qkv_hm : w.w_qkv, M, 3 * D, D);
+        g.D = D; g.S = P; g.err_flag = ef; g.pf = pf.after(hb, 0);
+        if (folded_in) fold_consumer(h, g, 2 * hb, 3 * D, mod_rows, ctab);
+        if (hf == 0) { g.qkv_mode = QKV_SPATIAL; g.rope_cs = h->rope_s.cs_dev; }
+        else { g.qkv_mode = QKV_TEMPORAL; g.k = h->kvcache[l]; g.v = h->kvcache[l]; g.Tq = Tq; g.t0 = t0; g.Tmax = h->maxT; g.rope_cs = h->rope_t.cs_dev; }
+        if (fused_t || fused_s) {
+            g.out = h->ao; g.ldo = D;
+            // profiled as the attention class: one class = one kernel (gtav_dit_fused_launches tells a reader which it was)
+            if (fused_t) PROF(h, PC_ATTN_T, s, launch_gemm_qkvt_attn(g, s));
+            else PROF(h, PC_ATTN_S, s, launch_gemm_qkvs_attn(g, s));
+        } else {
+            if (hf == 0) { g.q = h->qs; g.k = h->ks; g.v = h->vts; }
+            else g.q = h->qt;
+            PROF(h, PC_QKV, s, ops.gemm(g, folded_in ? EPI_QKV_FOLD : EPI_QKV, s));
+            if (hf == 0) PROF(h, PC_ATTN_S, s, ops.attn_spatial(h->qs, h->ks, h->vts, h->ao, NB, h->heads, P, s, false));
+            else PROF(h, PC_ATTN_T, s, ops.attn_temporal(h->qt, h->kvcache[l], h->ao, B, P, D, Tq, t0, h->maxT, s));
+        }
+        folded_in = false;
+        GemmParams fc1 = gemm_params(h->xn, D, w.w_fc1, M, h->Hm, D);
+        fc1.bias = w.b_fc1; fc1.out = h->hbuf; fc1.ldo = h->Hm_pad; fc1.err_flag = ef; fc1.pf = pf.after(hb, 2);
+        if (fold_a) {
+            // seam A: out-proj updates the residual in place and emits fc1's operand + row statistics; fc1 normalises in its epilogue
+            RET_IF(fold_producer(h, PC_OUT, h->ao, w.w_out, M, D, w.b_out, gate(mb + 2 * D), mb + 4 * D, s));
+            fold_consumer(h, fc1, 2 * hb + 1, h->Hm, mod_rows, ctab);
+            PROF(h, PC_FC1, s, launch_gemm(fc1, EPI_GELU_TANH_FOLD, s));
+        } else {
+            RET_IF(rd.gemm(ops, PC_OUT, h->ao, D, w.w_out, D, w.b_out, gate(mb + 2 * D), dit_resid_inplace(h, M, D), pf.after(hb, 1)));
+            RET_IF(ln(ops, mb + 3 * D, mb + 4 * D, ef));
+            PROF(h, PC_FC1, s, ops.gemm(fc1, EPI_GELU_TANH, s));
+        }
+        if (fold_b) {
+            // seam B: the LayerNorm that follows fc2 is the next half-block's first one (scale_msa) or the final layer's
+            const float* next_scale = hb + 1 < 2 * h->L ? mod + (size_t)(hb + 1) * 6 * D + D : mod + (size_t)h->L * 12 * D + D;
+            RET_IF(fold_producer(h, PC_FC2, h->hbuf, w.w_fc2, M, h->Hm_pad, w.b_fc2, gate(mb + 5 * D), next_scale, s));
+            folded_in = true;
+        } else {
+            RET_IF(rd.gemm(ops, PC_FC2, h->hbuf, h->Hm_pad, w.w_fc2, h->Hm_pad, w.b_fc2, gate(mb + 5 * D), dit_resid_inplace(h, M, h->Hm_pad), pf.after(hb, 3)));
         }
     }
     const float* mf = mod + (size_t)h->L * 12 * D;
-    if (!folded_in)
-        PROF(h, PC_LN, s, h->ops(g_final).ln_modulate(h->resid, D, h->xn, D, M, D, mf, mf + D, h->MODW, mod_rows, P, have_pend ? &pend : nullptr, h->err_of(g_final), s));
-    memset(&g, 0, sizeof(g));
-    g.X = h->xn; g.ldx = D; g.W = h->w_final; g.M = M; g.N = h->Nfin; g.K = D; g.bias = h->b_final; g.out = h->fo; g.ldo = h->Nfin;
-    if (folded_in) fold_consumer(g, 4 * h->L, h->Nfin);
-    PROF(h, PC_OTHER, s, h->ops(g_final).gemm(g, folded_in ? EPI_F32_FOLD : EPI_F32, s));
+    if (!folded_in) RET_IF(ln(h->ops(g_final), mf, mf + D, h->err_of(g_final)));
+    GemmParams fin = gemm_params(h->xn, D, h->w_final, M, h->Nfin, D);
+    fin.bias = h->b_final; fin.out = h->fo; fin.ldo = h->Nfin;
+    if (folded_in) fold_consumer(h, fin, 4 * h->L, h->Nfin, mod_rows, ctab);
+    PROF(h, PC_OTHER, s, h->ops(g_final).gemm(fin, folded_in ? EPI_F32_FOLD : EPI_F32, s));
     PROF(h, PC_OTHER, s, launch_unpatchify(h->fo, h->Nfin, v_out, NB, h->C, h->H, h->W, h->p, 0, 1.f, 0.f, s));
-    PROF(h, PC_EMPTY, s, 0);   // an event pair around nothing: the per-pair overhead to subtract from every class
     return h->prof.collect(s);
 }
 
 extern "C" {
-
-
 
 int gtav_dit_create(const gtav_dit_config* c, gtav_dit** out) {
     GTAV_REQUIRE(c && out, "dit_create: null argument");
@@ -424,16 +400,16 @@ int gtav_dit_finalize(gtav_dit* h, void* stream) {
     RET_IF(launch_add_f32(h->b_t2, h->b_ext, h->b_t2a, D, s));
     // rotary frequencies: loaded values win, otherwise the constructor formulas (dit.py:259-262)
     std::vector<float> fs(16), ft(32);
-    if (h->wt.slots["spatial_rotary_emb.freqs"].set) GTAV_CHECK_HIP(hipMemcpy(fs.data(), h->freqs_s_dev, 64, hipMemcpyDeviceToHost));
+    if (h->wt.is_set("spatial_rotary_emb.freqs")) GTAV_CHECK_HIP(hipMemcpy(fs.data(), h->freqs_s_dev, 64, hipMemcpyDeviceToHost));
     else { std::vector<float> l = linspace_f32(1.0f, 128.0f, 16); for (int i = 0; i < 16; ++i) fs[i] = l[i] * (float)M_PI; }
-    if (h->wt.slots["temporal_rotary_emb.freqs"].set) GTAV_CHECK_HIP(hipMemcpy(ft.data(), h->freqs_t_dev, 128, hipMemcpyDeviceToHost));
+    if (h->wt.is_set("temporal_rotary_emb.freqs")) GTAV_CHECK_HIP(hipMemcpy(ft.data(), h->freqs_t_dev, 128, hipMemcpyDeviceToHost));
     else for (int i = 0; i < 32; ++i) ft[i] = 1.0f / powf(10000.0f, (float)(2 * i) / 64.0f);
-    if (!(h->wt.slots["tables.rope_spatial_cos"].set && h->wt.slots["tables.rope_spatial_sin"].set)) {
+    if (!(h->wt.is_set("tables.rope_spatial_cos") && h->wt.is_set("tables.rope_spatial_sin"))) {
         std::vector<float> c, sn;
         build_axial_table(fs, h->gh, h->gw, c, sn);
         RET_IF(upload(h->rope_s.cos_dev, c)); RET_IF(upload(h->rope_s.sin_dev, sn));
     }
-    if (!(h->wt.slots["tables.rope_temporal_cos"].set && h->wt.slots["tables.rope_temporal_sin"].set)) {
+    if (!(h->wt.is_set("tables.rope_temporal_cos") && h->wt.is_set("tables.rope_temporal_sin"))) {
         std::vector<float> c((size_t)h->maxT * 64), sn((size_t)h->maxT * 64);
         for (int t = 0; t < h->maxT; ++t)
             for (int d = 0; d < 64; ++d) {
@@ -442,7 +418,7 @@ int gtav_dit_finalize(gtav_dit* h, void* stream) {
             }
         RET_IF(upload(h->rope_t.cos_dev, c)); RET_IF(upload(h->rope_t.sin_dev, sn));
     }
-    if (!h->wt.slots["tables.timestep_sincos"].set) {
+    if (!h->wt.is_set("tables.timestep_sincos")) {
         std::vector<float> tab((size_t)1000 * 256);
         for (int k = 0; k < 128; ++k) {
             const float f = expf(-logf(10000.0f) * (float)k / 128.0f);
@@ -515,12 +491,9 @@ int gtav_dit_prepare_frame(gtav_dit* h, int32_t B, int32_t F, int32_t start, int
     // the host array may be freed by the caller after this call returns: synchronous copy (once per generated frame)
     GTAV_CHECK_HIP(hipStreamSynchronize(s));
     GTAV_CHECK_HIP(hipMemcpy(h->t_steps_dev, t_steps_host, n_steps * sizeof(int), hipMemcpyHostToDevice));
-    const int ldhc = h->D + h->Apad;
-    RET_IF(launch_cond_inputs_frame(rows, B, T, F, start, cur, t_ctx, h->t_steps_dev, h->sincos, h->E, actions, h->A, h->HC, ldhc,
+    RET_IF(launch_cond_inputs_frame(rows, B, T, F, start, cur, t_ctx, h->t_steps_dev, h->sincos, h->E, actions, h->A, h->HC, h->D + h->Apad,
                                     h->D, h->Apad, h->err_flag, s));
-    RET_IF(launch_skinny_f32(h->E, 256, h->w_t0, h->b_t0, h->HC, ldhc, rows, h->D, 256, 1, s));
-    RET_IF(launch_skinny_f32(h->HC, ldhc, h->w_t2cat, actions ? h->b_t2a : h->b_t2, h->Sc, h->D, rows, h->D, ldhc, 1, s));
-    RET_IF(launch_skinny_f32(h->Sc, h->D, h->w_ada, h->b_ada, h->mod, h->MODW, rows, h->MODW, h->D, 0, s));
+    RET_IF(dit_cond_mlp(h, rows, actions != nullptr, s));
     {   // LayerNorm-fold tables of every row, for the seams a full-window step (B T P tokens) or a context-cached step (B P tokens) folds
         bool fa, fb, fa1, fb1;
         fold_policy(h, B * T * h->P, fa, fb);
@@ -532,6 +505,40 @@ int gtav_dit_prepare_frame(gtav_dit* h, int32_t B, int32_t F, int32_t start, int
     h->prepared.valid = true; h->prepared.B = B; h->prepared.F = F; h->prepared.start = start; h->prepared.cur = cur;
     h->prepared.n_steps = n_steps; h->prepared.actions = actions;
     return 0;
+}
+
+// hipGraph path of the sampler step: the first step of a new (shape, buffers) key runs eagerly (warm-up: lazy module load, function attributes), the second one is
+// captured, later ones replay the captured graph (~240 kernel nodes, one launch).  *out: the graph to launch, or null = run this step eagerly — the key's first step,
+// or capture is not available here, and then use_graph goes off for good.  A step body that fails inside the capture returns its own code.
+static int dit_step_graph(gtav_dit* h, float* x, int B, int F, int T, const float* actions, int mode, float* v_out, bool prepared, hipGraphExec_t* out) {
+    *out = nullptr;
+    const gtav_dit::GraphKey key{B, F, T, mode * 2 + (prepared ? 1 : 0), x, actions, v_out};
+    auto it = h->graphs.find(key);
+    if (it == h->graphs.end()) {
+        if (h->graphs.size() > 64) h->drop_graphs();
+        h->graphs[key] = nullptr;
+        return 0;
+    }
+    *out = it->second;
+    if (*out) return 0;
+    // capture on a private non-blocking stream (stream capture is not permitted on the legacy null stream, which is
+    // what torch hands out by default); nothing executes during capture, the graph is launched on the caller's stream
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    int rc = 0;
+    bool ok = h->cap_stream || hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking) == hipSuccess;
+    if (ok && hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
+        (void)hipGetLastError();
+        ok = false;
+    } else if (ok) {
+        rc = denoise_step_body(h, x, B, F, T, actions, mode, v_out, prepared, h->cap_stream);
+        ok = hipStreamEndCapture(h->cap_stream, &graph) == hipSuccess && !rc && graph;
+        ok = ok && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess && exec;
+        if (graph) (void)hipGraphDestroy(graph);
+    }
+    if (ok) *out = it->second = exec;
+    else h->use_graph = false;
+    return rc;
 }
 
 int gtav_dit_denoise_step(gtav_dit* h, float* x, int32_t B, int32_t F, int32_t start, int32_t cur, int32_t t_ctx,
@@ -567,52 +574,10 @@ int gtav_dit_denoise_step(gtav_dit* h, float* x, int32_t B, int32_t F, int32_t s
                              mode == 1, s));
     if (prepared) RET_IF(launch_gather_rows(h->mod, h->mod_rows_dev, h->mod_changed, h->mod_cur, B * (mode == 1 ? 1 : T), h->MODW,
                                             h->prepared.fold_tables ? h->fold.ctab : nullptr, h->fold.ctab_cur, h->fold.CTW, s));
-    if (!h->use_graph || h->prof.on) return denoise_step_body(h, x, B, F, T, actions, mode, v_out, prepared, s);
-
-    // hipGraph path: the first step of a new (shape, buffers) key runs eagerly (warm-up: lazy module load, function
-    // attributes), the second one is captured, later ones replay the captured graph (~240 kernel nodes, one launch).
-    gtav_dit::GraphKey key{B, F, T, mode * 2 + (prepared ? 1 : 0), x, actions, v_out};
-    auto it = h->graphs.find(key);
-    if (it == h->graphs.end()) {
-        if (h->graphs.size() > 64) {
-            for (auto& kv : h->graphs)
-                if (kv.second) (void)hipGraphExecDestroy(kv.second);
-            h->graphs.clear();
-        }
-        h->graphs[key] = nullptr;
-        return denoise_step_body(h, x, B, F, T, actions, mode, v_out, prepared, s);
-    }
-    if (!it->second) {
-        // capture on a private non-blocking stream (stream capture is not permitted on the legacy null stream, which is
-        // what torch hands out by default); nothing executes during capture, the graph is launched on the caller's stream
-        if (!h->cap_stream && hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking) != hipSuccess) {
-            h->use_graph = false;
-            return denoise_step_body(h, x, B, F, T, actions, mode, v_out, prepared, s);
-        }
-        hipGraph_t graph = nullptr;
-        if (hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-            (void)hipGetLastError();
-            h->use_graph = false;
-            return denoise_step_body(h, x, B, F, T, actions, mode, v_out, prepared, s);
-        }
-        const int rc = denoise_step_body(h, x, B, F, T, actions, mode, v_out, prepared, h->cap_stream);
-        const hipError_t ce = hipStreamEndCapture(h->cap_stream, &graph);
-        if (rc || ce != hipSuccess || !graph) {
-            if (graph) (void)hipGraphDestroy(graph);
-            h->use_graph = false;  // capture is not available here: fall back to eager launches for good
-            if (rc) return rc;
-            return denoise_step_body(h, x, B, F, T, actions, mode, v_out, prepared, s);
-        }
-        hipGraphExec_t exec = nullptr;
-        const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (ie != hipSuccess || !exec) {
-            h->use_graph = false;
-            return denoise_step_body(h, x, B, F, T, actions, mode, v_out, prepared, s);
-        }
-        it->second = exec;
-    }
-    GTAV_CHECK_HIP(hipGraphLaunch(it->second, s));
+    hipGraphExec_t exec = nullptr;
+    if (h->use_graph && !h->prof.on) RET_IF(dit_step_graph(h, x, B, F, T, actions, mode, v_out, prepared, &exec));
+    if (!exec) return denoise_step_body(h, x, B, F, T, actions, mode, v_out, prepared, s);
+    GTAV_CHECK_HIP(hipGraphLaunch(exec, s));
     return 0;
 }
 
@@ -630,11 +595,7 @@ int gtav_dit_set_weight_prefetch(gtav_dit* h, int32_t enable) {
     int cls[4];
     for (int c = 0; c < 4; ++c) cls[c] = enable == 0 ? 0 : enable == 1 ? 1 : (enable >> (4 * c)) & 15;
     const bool on = cls[0] || cls[1] || cls[2] || cls[3];
-    if (h->w_prefetch != on || memcmp(cls, h->w_prefetch_cls, sizeof(cls))) {   // captured sampler steps carry the other kernel parameters
-        for (auto& kv : h->graphs)
-            if (kv.second) (void)hipGraphExecDestroy(kv.second);
-        h->graphs.clear();
-    }
+    if (h->w_prefetch != on || memcmp(cls, h->w_prefetch_cls, sizeof(cls))) h->drop_graphs();   // captured sampler steps carry the other kernel parameters
     h->w_prefetch = on;
     memcpy(h->w_prefetch_cls, cls, sizeof(cls));
     return 0;
@@ -646,84 +607,57 @@ int gtav_dit_set_fold(gtav_dit* h, int32_t mode, int32_t min_tokens_a, int32_t m
     if (min_tokens_a >= 0) h->fold.min_m_a = min_tokens_a;
     if (min_tokens_b >= 0) h->fold.min_m_b = min_tokens_b;
     if (mode == 2 || (mode == 1 && (h->fold.min_m_a < (1 << 30) || h->fold.min_m_b < (1 << 30)))) RET_IF(fold_alloc(h));
-    for (auto& kv : h->graphs)       // captured sampler steps contain the other kernel sequence
-        if (kv.second) (void)hipGraphExecDestroy(kv.second);
-    h->graphs.clear();
+    h->drop_graphs();                // captured sampler steps contain the other kernel sequence
     h->prepared.valid = false;       // the per-frame tables were built for the old policy
     h->fold.mode = mode;
     return 0;
 }
 #endif
 
-int gtav_dit_set_fused_temporal(gtav_dit* h, int32_t enable) {
-    GTAV_REQUIRE(h, "dit_set_fused_temporal: null handle");
-    if (h->fuse_tattn != (enable != 0)) {   // captured sampler steps contain the other kernel sequence
-        for (auto& kv : h->graphs)
-            if (kv.second) (void)hipGraphExecDestroy(kv.second);
-        h->graphs.clear();
-    }
-    if (enable && h->P % 16 == 0 && h->D % 256 == 0 && h->maxT >= 5) {
-        // first enable: head-major copies of the temporal to_qkv weights (3 D^2 halves per block); filled here if the weights are
-        // already final, otherwise by gtav_dit_finalize
+// the switch of one fused to_qkv + attention launch (`flag`: fuse_sattn of the spatial halves, hf = 0, or fuse_tattn of the temporal ones, hf = 1).  First enable
+// on a geometry that has the launch (`geom_ok`): head-major copies of those halves' to_qkv weights (3 D^2 halves per block); filled here if the weights are already
+// final, otherwise by gtav_dit_finalize
+static int dit_set_fused(gtav_dit* h, bool& flag, int hf, bool geom_ok, bool enable) {
+    if (flag != enable) h->drop_graphs();   // captured sampler steps contain the other kernel sequence
+    if (enable && geom_ok) {
         for (int l = 0; l < h->L; ++l) {
-            gtav_dit::Half& w = h->halves[l * 2 + 1];
+            gtav_dit::Half& w = h->halves[l * 2 + hf];
             if (w.w_qkv_hm) continue;
             RET_IF(h->arena.alloc_t(&w.w_qkv_hm, (size_t)3 * h->D * h->D));
-            if (h->finalized) RET_IF(launch_qkv_head_major(w.w_qkv, w.w_qkv_hm, h->D, nullptr));
+            if (h->finalized) RET_IF(launch_qkv_head_major(w.w_qkv, w.w_qkv_hm, h->D, nullptr, hf ? 0 : 1));
         }
         if (h->finalized) GTAV_CHECK_HIP(hipDeviceSynchronize());
     }
-    h->fuse_tattn = enable != 0;
+    flag = enable;
     return 0;
 }
-
+int gtav_dit_set_fused_temporal(gtav_dit* h, int32_t enable) {
+    GTAV_REQUIRE(h, "dit_set_fused_temporal: null handle");
+    return dit_set_fused(h, h->fuse_tattn, 1, h->P % 16 == 0 && h->D % 256 == 0 && h->maxT >= 5, enable != 0);
+}
 int gtav_dit_set_fused_spatial(gtav_dit* h, int32_t enable) {
     GTAV_REQUIRE(h, "dit_set_fused_spatial: null handle");
-    if (h->fuse_sattn != (enable != 0)) {   // captured sampler steps contain the other kernel sequence
-        for (auto& kv : h->graphs)
-            if (kv.second) (void)hipGraphExecDestroy(kv.second);
-        h->graphs.clear();
-    }
-    if (enable && h->P == 144 && h->D % 256 == 0) {
-        // first enable: head-major copies of the spatial to_qkv weights (3 D^2 halves per block), as for the temporal switch
-        for (int l = 0; l < h->L; ++l) {
-            gtav_dit::Half& w = h->halves[l * 2];
-            if (w.w_qkv_hm) continue;
-            RET_IF(h->arena.alloc_t(&w.w_qkv_hm, (size_t)3 * h->D * h->D));
-            if (h->finalized) RET_IF(launch_qkv_head_major(w.w_qkv, w.w_qkv_hm, h->D, nullptr, 1));
-        }
-        if (h->finalized) GTAV_CHECK_HIP(hipDeviceSynchronize());
-    }
-    h->fuse_sattn = enable != 0;
-    return 0;
+    return dit_set_fused(h, h->fuse_sattn, 0, h->P == 144 && h->D % 256 == 0, enable != 0);
 }
 
 int gtav_dit_fused_launches(gtav_dit* h, int32_t B, int32_t T, int32_t t0) {
     if (!h || B < 1 || T < 1) return 0;
-    const int M = B * T * h->P;
     int mask = 0;
-    for (int hb = 0; hb < 2 * h->L; ++hb) {
-        const gtav_dit::Half& w = h->halves[hb];
-        if (h->tr.on || h->ops(hb).bf16 || !w.w_qkv_hm) continue;
-        if (!(hb & 1) && h->fuse_sattn && fused_spatial_ok(M, h->D, h->P)) mask |= 1;
-        if ((hb & 1) && h->fuse_tattn && gemm_qkvt_attn_ok(M, h->D, h->P, T, t0)) mask |= 2;
-    }
+    for (int hb = 0; hb < 2 * h->L; ++hb)
+        if (dit_half_fused(h, hb, B * T * h->P, T, t0)) mask |= (hb & 1) ? 2 : 1;
     return mask;
 }
 
 int gtav_dit_profile(gtav_dit* h, int32_t enable) {
     GTAV_REQUIRE(h, "dit_profile: null handle");
-    h->prof.on = enable != 0;
-    h->prof.used = 0;
-    for (int i = 0; i < PC_COUNT; ++i) { h->prof.ms[i] = 0; h->prof.n[i] = 0; }
+    h->prof.reset(enable != 0);
     return 0;
 }
 int gtav_dit_profile_read(gtav_dit* h, double* ms_by_class, int64_t* launches_by_class) {
     GTAV_REQUIRE(h && ms_by_class && launches_by_class, "dit_profile_read: null argument");
-    for (int i = 0; i < PC_COUNT; ++i) { ms_by_class[i] = h->prof.ms[i]; launches_by_class[i] = h->prof.n[i]; }
+    h->prof.read(ms_by_class, launches_by_class);
     return 0;
 }
-
 
 // the handle's error words (gtav_dit::err_flag): copied back, cleared on the device; `words` gets 4 + n_groups ints
 static int dit_read_err_words(gtav_dit* h, std::vector<int>& words, hipStream_t s) {
@@ -741,12 +675,6 @@ int gtav_dit_check(gtav_dit* h, void* stream) {
     int flag = w[0];
     for (int g = 0; g < h->n_groups; ++g) flag |= w[4 + g];
     return report_err_flag(flag, "DiT");
-}
-
-static void dit_drop_graphs(gtav_dit* h) {
-    for (auto& kv : h->graphs)
-        if (kv.second) (void)hipGraphExecDestroy(kv.second);
-    h->graphs.clear();
 }
 
 int gtav_dit_set_operand_dtype(gtav_dit* h, int32_t group, int32_t dtype) {
@@ -769,7 +697,7 @@ int gtav_dit_set_operand_dtype(gtav_dit* h, int32_t group, int32_t dtype) {
         // captured steps hold the other kernels; the temporal K/V caches of a switched half hold the other encoding
         h->finalized = false;
         h->kvrec.valid = false;
-        dit_drop_graphs(h);
+        h->drop_graphs();
     }
     h->any_bf16 = false;
     for (unsigned char b : h->grp_bf16) h->any_bf16 |= b != 0;

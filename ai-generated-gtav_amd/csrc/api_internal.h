@@ -74,6 +74,11 @@ struct WeightTable {
     // clamped by the conversion AND raises ERR_F16_SAT there, so that check() reports it and gtav_dit_autorange moves the group to bf16
     int* err_words = nullptr;
     bool err_per_group = false;
+    // lookups that never insert (slots[n] on a misspelt name would make a blank Slot, whose null pointers the next launch writes through)
+    Slot* find(const std::string& n) { auto it = slots.find(n); return it == slots.end() ? nullptr : &it->second; }
+    bool is_set(const std::string& n) { const Slot* sl = find(n); return sl && sl->set; }
+    // every slot trains but the constants (requires_grad False upstream): the tables.* overrides and the rotary frequencies
+    static bool trainable_name(const std::string& n) { return n.rfind("tables.", 0) != 0 && n.find("rotary_emb.freqs") == std::string::npos; }
     void add_f16(const std::string& n, int R, int C, f16* dst, int Rp, int Cp, int group = -1) {
         slots[n] = Slot{SLOT_F16_PAD, R, C, dst, Rp, Cp, 0, false, true};
         slots[n].group = group;
@@ -170,7 +175,6 @@ inline void build_axial_table(const std::vector<float>& freqs, int gh, int gw, s
             }
 }
 
-
 // In-situ kernel timing (opt-in): HIP events on the launch stream around every kernel of a forward,
 // accumulated per kernel class.  Used by bench.py for the roofline line; off in normal operation.
 enum ProfClass { PC_LN = 0, PC_QKV, PC_ATTN_S, PC_ATTN_T, PC_OUT, PC_FC1, PC_FC2, PC_OTHER, PC_EMPTY, PC_COUNT };
@@ -214,8 +218,11 @@ struct Profiler {
         used += 2;
         return 0;
     }
+    // end of a forward: one more event pair, around nothing (the per-pair overhead to subtract from every class), then every pair's time goes to its class
     int collect(hipStream_t s) {
-        if (!on || used == 0) return 0;
+        if (!on) return 0;
+        RET_IF(begin(PC_EMPTY, s));
+        RET_IF(end(s));
         GTAV_CHECK_HIP(hipStreamSynchronize(s));
         for (size_t i = 0; i < used; i += 2) {
             float t = 0.f;
@@ -225,6 +232,14 @@ struct Profiler {
         }
         used = 0;
         return 0;
+    }
+    void reset(bool enable) {   // gtav_dit_profile / gtav_vae_profile
+        on = enable;
+        used = 0;
+        for (int i = 0; i < PC_COUNT; ++i) { ms[i] = 0; n[i] = 0; }
+    }
+    void read(double* ms_by_class, int64_t* launches_by_class) const {
+        for (int i = 0; i < PC_COUNT; ++i) { ms_by_class[i] = ms[i]; launches_by_class[i] = n[i]; }
     }
     ~Profiler() {
         for (hipEvent_t e : ev) (void)hipEventDestroy(e);
@@ -245,6 +260,76 @@ inline int report_err_flag(int flag, const char* who) {
                  "last check are finite but clipped (the reference runs this path in bf16, which has fp32 range)", who);
     return 0;
 }
+
+// X [M][K] (ldx) times W [N][K]: every other field zero.  Zero-filled by memset, padding included: a captured graph bakes the argument bytes of its launches in.
+inline GemmParams gemm_params(const f16* X, int ldx, const f16* W, int M, int N, int K) {
+    GemmParams g;
+    memset(&g, 0, sizeof(g));
+    g.X = X; g.ldx = ldx; g.W = W; g.M = M; g.N = N; g.K = K;
+    return g;
+}
+
+const PrefetchDesc kNoPrefetch{nullptr, 0, 0, 0, 0};
+
+// The deferred residual update of one forward (DiT, DiT training, VAE blocks).  Residual GEMMs (out-proj, fc2) write split-K partial slabs; the LayerNorm that
+// always follows reduces them and applies bias + gate + residual (LnPending), so the GEMM epilogue has no read-modify-write and small-M launches can spread
+// their K loop over all CUs.  This type owns the descriptor and whether one is pending: gemm() fills it, take() hands it to the next LayerNorm launch exactly once.
+struct ResidGate { const float* gate; int stride; const int* rows; int rows_per_gate; };   // x += gate[row] * branch (GemmParams::gate ..); all zero: no gate (VAE)
+struct DeferredResid {
+    float* parts; size_t parts_floats;   // the handle's slab workspace and its capacity
+    float* resid;                        // the residual stream (the in-place alternative updates it)
+    int M, N;
+    Profiler* prof;                      // books the GEMM under its class; null: the training forward, which is not profiled
+    hipStream_t s;
+    LnPending pend;
+    bool pending = false;
+    // x += gate * (X W^T + bias): `inplace` = in the GEMM's EPI_RESID epilogue (the caller's large-M predicate), else as slabs left to the next LayerNorm.  pf: L2
+    // prefetch of the next weight (DiT); x_out / y_save: LnPending's, the training forward's.
+    int gemm(const OperandOps& ops, int cls, const f16* X, int ldx, const f16* W, int K, const float* bias, const ResidGate& gt, bool inplace,
+             const PrefetchDesc& pf = kNoPrefetch, float* x_out = nullptr, f16* y_save = nullptr) {
+        GemmParams q = gemm_params(X, ldx, W, M, N, K);
+        q.out = parts; q.ldo = N; q.pf = pf;
+        if (inplace) {
+            q.out = resid; q.bias = bias; q.gate = gt.gate; q.gate_stride = gt.stride; q.gate_rows = gt.rows; q.rows_per_gate = gt.rows_per_gate;
+        } else {
+            q.splitk = gemm_choose_splitk(M, N, K);
+            GTAV_REQUIRE((size_t)q.splitk * M * N <= parts_floats, "split-K slabs exceed workspace");
+        }
+        if (prof) RET_IF(prof->begin(cls, s));
+        RET_IF(ops.gemm(q, inplace ? EPI_RESID : EPI_PARTIAL, s));
+        if (prof) RET_IF(prof->end(s));
+        pending = !inplace;
+        if (inplace) return 0;
+        memset(&pend, 0, sizeof(pend));
+        pend.parts = parts; pend.nsplit = q.splitk; pend.slab_stride = (size_t)M * N; pend.ld = N; pend.bias = bias;
+        pend.gate = gt.gate; pend.gate_stride = gt.stride; pend.gate_rows = gt.rows; pend.rows_per_gate = gt.rows_per_gate;
+        pend.x_out = x_out; pend.y_save = y_save;
+        return 0;
+    }
+    // the `pend` argument of the LayerNorm launch that follows: the descriptor if there is one (it is consumed: applying an update twice is the bug this prevents)
+    const LnPending* take() {
+        const bool was = pending;
+        pending = false;
+        return was ? &pend : nullptr;
+    }
+    // the next LayerNorm writes its rows in the tile order of the fused temporal launch (LnPending::tperm_*); with no slabs pending (the residual GEMM before
+    // updated in place) the descriptor carries the row permutation only
+    void permute_rows(int T, int P) {
+        if (!pending) memset(&pend, 0, sizeof(pend));
+        pend.tperm_T = T; pend.tperm_P = P;
+        pending = true;
+    }
+    // recompute mode: the next LayerNorm, which applies the pending update, also keeps the shift of its statistics (LnPending::k_save needs the slabs) ...
+    void save_shift(float* k) { pend.k_save = k; }
+    // ... and the re-run of that launch from the stored block input, which already holds the update, reads it back (LnPending::k_load) and applies nothing
+    int load_shift(const float* k) {
+        GTAV_REQUIRE(!pending, "train_block_forward: a re-run starts from a stored block input");
+        memset(&pend, 0, sizeof(pend));
+        pend.k_load = k;
+        pending = true;
+        return 0;
+    }
+};
 
 }  // namespace api
 }  // namespace gtav
@@ -344,9 +429,13 @@ struct gtav_dit {
         int *gcol_dev = nullptr, *gscale_dev = nullptr;
     } fold;
     hipStream_t cap_stream = nullptr;            // private stream the step is captured on (the caller's may be the null stream)
-    ~gtav_dit() {
+    void drop_graphs() {   // whatever changes the kernel sequence or the kernel parameters of a step: captured steps hold the old ones
         for (auto& kv : graphs)
             if (kv.second) (void)hipGraphExecDestroy(kv.second);
+        graphs.clear();
+    }
+    ~gtav_dit() {
+        drop_graphs();
         if (cap_stream) (void)hipStreamDestroy(cap_stream);
     }
     float* ac_table = nullptr;  // alphas_cumprod [1000]
@@ -369,11 +458,18 @@ struct gtav_dit {
         float loss_scale = 65536.0f;        // (1 on a bf16 handle)
         float grad_div = 1.0f;              // the arena holds the sum over this many ranks (gtav_dit_set_grad_divisor)
         std::vector<Slot*> params;          // trainable slots in a fixed (sorted-by-name) order
+        // the slots the backward pass writes gradients of, resolved by name once (train_enable): per half-block (to_qkv has no bias), final layer, embedders;
+        // ext: null without external_cond
+        struct Linear { Slot *w = nullptr, *b = nullptr; };
+        struct HalfSlots { Linear qkv, out, fc1, fc2, ada; };
+        std::vector<HalfSlots> hs;          // [2 L]
+        Linear fin, fin_ada, pe, t0, t2, ext;
         float* grad_arena = nullptr;        // all gradients, contiguous (one all-reduce); caller-owned when passed to train_enable
         size_t grad_count = 0;
         float* ctl = nullptr;               // [8]: sumsq, step coefficient, skipped steps, grad norm, applied steps, bias corrections
         float *ln_part = nullptr;   // per-(frame, 16-row chunk) partial rows of the fused LayerNorm backward (train.hip ln_mod_bwd_fused_kernel)
         float *red_ws = nullptr, *sumsq_part = nullptr;   // partial sums of the fixed-order reductions (bias gradients, gradient norm)
+        size_t red_ws_floats = 0;           // size of red_ws: what train_enable allocated is what the backward pass's fusions are bounded by
         AdamParam* adam_params = nullptr;   // device tables of the multi-tensor AdamW launch
         AdamItem* adam_items = nullptr;
         int adam_n_items = 0;

@@ -8,9 +8,6 @@ static int g_fuse_ln = GTAV_ENV_INT("GTAV_FUSE_LN_BWD", 1);     // experiments b
 static int g_fuse_gate = GTAV_ENV_INT("GTAV_FUSE_GATE", 1);     // experiments build: 0 = gate_bwd, frame_reduce_gate and the bias column sums as three launches (A/B runs)
 static int g_dw_tn = GTAV_ENV_INT("GTAV_DW_TN", 1);             // experiments build: 0 = transposed operand copies in front of the grouped launch (A/B runs)
 
-// gtav_dit_train_enable after its operand-type checks: trainable slots, fp32 masters, AdamW state, saved-activation and backward workspace
-static int train_enable_body(gtav_dit* h, float* grad_arena_dev, int64_t grad_arena_numel);
-
 // The training step serves windows of at most 8 frames unless the caller opted in to longer ones (gtav_dit_train_allow_window): refused by name before anything on
 // the handle is allocated or changed.
 static int train_window_ok(const gtav_dit* h) {
@@ -24,69 +21,36 @@ static int train_window_ok(const gtav_dit* h) {
     return 0;
 }
 
-extern "C" {
-
-// ================================================================================================
-// DiT training step (SURVEY.md 8(f)1): forward with saved activations, backward, AdamW.
-// Reference: train_dit.py:649-650 (forward + mse), :680 accelerator.backward, :232-238 AdamW(betas 0.9 / 0.999, eps 1e-7),
-// :965-970 clip_grad_norm_ / optimizer.step / zero_grad.  Mixed precision like the reference's bf16 autocast + fp32 master
-// weights, with fp16 operands and a loss scale in place of bf16's exponent range: activation gradients travel as fp16 GEMM
-// operands multiplied by tr.loss_scale, weight gradients / LayerNorm statistics / the residual-stream gradient are fp32.
-// gtav_dit_train_enable_typed(.., GTAV_OPERAND_BF16) runs the same step on bf16 operands (the reference's own autocast type): every launch below that
-// reads or writes a 2-byte tensor goes through the operand group's launcher set (h->ops(g): ops_bf16.h OperandOps), the twins of the same kernels.
-// ================================================================================================
-// Opt-in to training windows of up to max_frames <= 32 frames (the default, 8, is what train_window_ok otherwise enforces): between create and train_enable only.
-int gtav_dit_train_allow_window(gtav_dit* h, int32_t max_frames) {
-    GTAV_REQUIRE(h, "train_allow_window: null handle");
-    GTAV_REQUIRE(!h->tr.on, "train_allow_window: training is already enabled on this handle (call it between gtav_dit_create and gtav_dit_train_enable)");
-    GTAV_REQUIRE(max_frames >= 8 && max_frames <= 32, "train_allow_window: max_frames=%d outside [8, 32]", max_frames);
-    h->tr.window = max_frames;
+// The slots whose gradients the backward pass writes, by name, once (after the gradients were laid out): a name that is not a trainable slot is refused here
+// instead of becoming a write through a null pointer in the middle of a step.
+static int train_linear(gtav_dit* h, const std::string& n, gtav_dit::Train::Linear* out, bool bias = true) {
+    out->w = h->wt.find(n + ".weight");
+    out->b = bias ? h->wt.find(n + ".bias") : nullptr;
+    GTAV_REQUIRE(out->w && out->w->grad && (!bias || (out->b && out->b->grad)), "train_enable: the model has no trainable Linear '%s'", n.c_str());
     return 0;
 }
-
-// Opt-in to activation recomputation (api_internal.h Train::recompute): between create and train_enable only, like gtav_dit_train_allow_window.
-int gtav_dit_train_set_recompute(gtav_dit* h, int32_t enable) {
-    GTAV_REQUIRE(h, "train_set_recompute: null handle");
-    GTAV_REQUIRE(!h->tr.on, "train_set_recompute: training is already enabled on this handle (call it between gtav_dit_create and gtav_dit_train_enable)");
-    h->tr.recompute = enable != 0;
-    return 0;
+static int train_resolve_slots(gtav_dit* h) {
+    gtav_dit::Train& t = h->tr;
+    t.hs.resize(2 * h->L);
+    for (int i = 0; i < 2 * h->L; ++i) {
+        char pre[64];
+        snprintf(pre, sizeof(pre), "blocks.%d.%c_", i / 2, i % 2 == 0 ? 's' : 't');
+        const std::string P_(pre);
+        RET_IF(train_linear(h, P_ + "attn.to_qkv", &t.hs[i].qkv, false));
+        RET_IF(train_linear(h, P_ + "attn.to_out", &t.hs[i].out));
+        RET_IF(train_linear(h, P_ + "mlp.fc1", &t.hs[i].fc1));
+        RET_IF(train_linear(h, P_ + "mlp.fc2", &t.hs[i].fc2));
+        RET_IF(train_linear(h, P_ + "adaLN_modulation.1", &t.hs[i].ada));
+    }
+    RET_IF(train_linear(h, "final_layer.linear", &t.fin));
+    RET_IF(train_linear(h, "final_layer.adaLN_modulation.1", &t.fin_ada));
+    RET_IF(train_linear(h, "x_embedder.proj", &t.pe));
+    RET_IF(train_linear(h, "t_embedder.mlp.0", &t.t0));
+    RET_IF(train_linear(h, "t_embedder.mlp.2", &t.t2));
+    return h->A > 0 ? train_linear(h, "external_cond", &t.ext) : 0;
 }
 
-int gtav_dit_train_saved_bytes(gtav_dit* h, int64_t* bytes) {
-    GTAV_REQUIRE(h && bytes, "train_saved_bytes: null argument");
-    GTAV_REQUIRE(h->tr.on, "train_saved_bytes: training is not enabled");
-    *bytes = (int64_t)h->tr.saved_bytes;
-    return 0;
-}
-
-int gtav_dit_train_enable(gtav_dit* h, float* grad_arena_dev, int64_t grad_arena_numel) {
-    GTAV_REQUIRE(h, "train_enable: null handle");
-    RET_IF(train_window_ok(h));
-    GTAV_REQUIRE(!h->tr.on, "train_enable: already enabled");
-    GTAV_REQUIRE(!h->any_bf16, "train_enable: the training step runs on fp16 operands (gtav_dit_set_operand_dtype(h, -1, GTAV_OPERAND_F16) first)");
-    return train_enable_body(h, grad_arena_dev, grad_arena_numel);
-}
-
-int gtav_dit_train_enable_typed(gtav_dit* h, float* grad_arena_dev, int64_t grad_arena_numel, int32_t dtype) {
-    GTAV_REQUIRE(h, "train_enable_typed: null handle");
-    GTAV_REQUIRE(dtype == GTAV_OPERAND_F16 || dtype == GTAV_OPERAND_BF16, "train_enable_typed: dtype %d (0 = fp16, 1 = bf16)", dtype);
-    if (dtype == GTAV_OPERAND_F16) return gtav_dit_train_enable(h, grad_arena_dev, grad_arena_numel);
-    RET_IF(train_window_ok(h));   // before the type switch below changes the handle
-    GTAV_REQUIRE(!h->tr.on, "train_enable: already enabled");
-    int nb = 0;
-    for (unsigned char b : h->grp_bf16) nb += b != 0;
-    GTAV_REQUIRE(nb == 0 || nb == h->n_groups, "train_enable_typed: %d of the %d operand groups are bf16; a training handle has one operand type for every group", nb,
-                 h->n_groups);
-    // (before the type switch, which un-sets the weight slots it converts)
-    for (auto& kv : h->wt.slots) GTAV_REQUIRE(!kv.second.set, "train_enable: call it before any gtav_dit_set_weight (the fp32 masters are filled by set_weight)");
-    RET_IF(gtav_dit_set_operand_dtype(h, -1, GTAV_OPERAND_BF16));
-    h->tr.bf16 = true;
-    h->tr.loss_scale = 1.0f;   // bf16 has fp32's exponent range: the reference trains it without a scaler (gtav_dit_set_loss_scale still applies)
-    return train_enable_body(h, grad_arena_dev, grad_arena_numel);
-}
-
-}  // extern "C"
-
+// gtav_dit_train_enable after its operand-type checks: trainable slots, fp32 masters, AdamW state, saved-activation and backward workspace
 static int train_enable_body(gtav_dit* h, float* grad_arena_dev, int64_t grad_arena_numel) {
     for (auto& kv : h->wt.slots) GTAV_REQUIRE(!kv.second.set, "train_enable: call it before any gtav_dit_set_weight (the fp32 masters are filled by set_weight)");
     gtav_dit::Train& t = h->tr;
@@ -96,11 +60,10 @@ static int train_enable_body(gtav_dit* h, float* grad_arena_dev, int64_t grad_ar
     size_t count = 0;
     std::vector<std::string> names;
     for (auto& kv : h->wt.slots) {
-        const std::string& n = kv.first;
-        if (n.rfind("tables.", 0) == 0 || n.find("rotary_emb.freqs") != std::string::npos) continue;   // constants (requires_grad False upstream)
+        if (!WeightTable::trainable_name(kv.first)) continue;
         kv.second.trainable = true;
         t.params.push_back(&kv.second);
-        names.push_back(n);
+        names.push_back(kv.first);
         count += (size_t)kv.second.R * kv.second.C;
     }
     t.grad_count = count;
@@ -128,7 +91,9 @@ static int train_enable_body(gtav_dit* h, float* grad_arena_dev, int64_t grad_ar
         }
     }
     RET_IF(a.alloc_t(&t.ctl, 8));
-    RET_IF(a.alloc_t(&t.red_ws, colsum_workspace(h->Mmax > h->max_rows ? h->Mmax : h->max_rows, h->Hm_pad > 6 * D ? h->Hm_pad : 6 * D)));
+    RET_IF(train_resolve_slots(h));
+    t.red_ws_floats = colsum_workspace(h->Mmax > h->max_rows ? h->Mmax : h->max_rows, h->Hm_pad > 6 * D ? h->Hm_pad : 6 * D);
+    RET_IF(a.alloc_t(&t.red_ws, t.red_ws_floats));
     RET_IF(a.alloc_t(&t.sumsq_part, (size_t)sumsq_parts(count)));
     {
         std::vector<AdamParam> ap;
@@ -206,64 +171,104 @@ static int train_enable_body(gtav_dit* h, float* grad_arena_dev, int64_t grad_ar
     return 0;
 }
 
+extern "C" {
+
+// ================================================================================================
+// DiT training step (SURVEY.md 8(f)1): forward with saved activations, backward, AdamW.
+// Reference: train_dit.py:649-650 (forward + mse), :680 accelerator.backward, :232-238 AdamW(betas 0.9 / 0.999, eps 1e-7),
+// :965-970 clip_grad_norm_ / optimizer.step / zero_grad.  Mixed precision like the reference's bf16 autocast + fp32 master
+// weights, with fp16 operands and a loss scale in place of bf16's exponent range: activation gradients travel as fp16 GEMM
+// operands multiplied by tr.loss_scale, weight gradients / LayerNorm statistics / the residual-stream gradient are fp32.
+// gtav_dit_train_enable_typed(.., GTAV_OPERAND_BF16) runs the same step on bf16 operands (the reference's own autocast type): every launch below that
+// reads or writes a 2-byte tensor goes through the operand group's launcher set (h->ops(g): ops_bf16.h OperandOps), the twins of the same kernels.
+// ================================================================================================
+// Opt-in to training windows of up to max_frames <= 32 frames (the default, 8, is what train_window_ok otherwise enforces): between create and train_enable only.
+int gtav_dit_train_allow_window(gtav_dit* h, int32_t max_frames) {
+    GTAV_REQUIRE(h, "train_allow_window: null handle");
+    GTAV_REQUIRE(!h->tr.on, "train_allow_window: training is already enabled on this handle (call it between gtav_dit_create and gtav_dit_train_enable)");
+    GTAV_REQUIRE(max_frames >= 8 && max_frames <= 32, "train_allow_window: max_frames=%d outside [8, 32]", max_frames);
+    h->tr.window = max_frames;
+    return 0;
+}
+
+// Opt-in to activation recomputation (api_internal.h Train::recompute): between create and train_enable only, like gtav_dit_train_allow_window.
+int gtav_dit_train_set_recompute(gtav_dit* h, int32_t enable) {
+    GTAV_REQUIRE(h, "train_set_recompute: null handle");
+    GTAV_REQUIRE(!h->tr.on, "train_set_recompute: training is already enabled on this handle (call it between gtav_dit_create and gtav_dit_train_enable)");
+    h->tr.recompute = enable != 0;
+    return 0;
+}
+
+int gtav_dit_train_saved_bytes(gtav_dit* h, int64_t* bytes) {
+    GTAV_REQUIRE(h && bytes, "train_saved_bytes: null argument");
+    GTAV_REQUIRE(h->tr.on, "train_saved_bytes: training is not enabled");
+    *bytes = (int64_t)h->tr.saved_bytes;
+    return 0;
+}
+
+int gtav_dit_train_enable(gtav_dit* h, float* grad_arena_dev, int64_t grad_arena_numel) {
+    GTAV_REQUIRE(h, "train_enable: null handle");
+    RET_IF(train_window_ok(h));
+    GTAV_REQUIRE(!h->tr.on, "train_enable: already enabled");
+    GTAV_REQUIRE(!h->any_bf16, "train_enable: the training step runs on fp16 operands (gtav_dit_set_operand_dtype(h, -1, GTAV_OPERAND_F16) first)");
+    return train_enable_body(h, grad_arena_dev, grad_arena_numel);
+}
+
+int gtav_dit_train_enable_typed(gtav_dit* h, float* grad_arena_dev, int64_t grad_arena_numel, int32_t dtype) {
+    GTAV_REQUIRE(h, "train_enable_typed: null handle");
+    GTAV_REQUIRE(dtype == GTAV_OPERAND_F16 || dtype == GTAV_OPERAND_BF16, "train_enable_typed: dtype %d (0 = fp16, 1 = bf16)", dtype);
+    if (dtype == GTAV_OPERAND_F16) return gtav_dit_train_enable(h, grad_arena_dev, grad_arena_numel);
+    RET_IF(train_window_ok(h));   // before the type switch below changes the handle
+    GTAV_REQUIRE(!h->tr.on, "train_enable: already enabled");
+    int nb = 0;
+    for (unsigned char b : h->grp_bf16) nb += b != 0;
+    GTAV_REQUIRE(nb == 0 || nb == h->n_groups, "train_enable_typed: %d of the %d operand groups are bf16; a training handle has one operand type for every group", nb,
+                 h->n_groups);
+    // (before the type switch, which un-sets the weight slots it converts)
+    for (auto& kv : h->wt.slots) GTAV_REQUIRE(!kv.second.set, "train_enable: call it before any gtav_dit_set_weight (the fp32 masters are filled by set_weight)");
+    RET_IF(gtav_dit_set_operand_dtype(h, -1, GTAV_OPERAND_BF16));
+    h->tr.bf16 = true;
+    h->tr.loss_scale = 1.0f;   // bf16 has fp32's exponent range: the reference trains it without a scaler (gtav_dit_set_loss_scale still applies)
+    return train_enable_body(h, grad_arena_dev, grad_arena_numel);
+}
+
+}  // extern "C"
+
 // Both half-blocks of block l of the training forward (gtav_dit_train_forward runs it for l = 0 .. L - 1).  Every residual GEMM stores split-K slabs and leaves
-// the update to the next LayerNorm launch (`pend`): on return the block's last fc2 branch is still pending, and the first LayerNorm of block l + 1 (or the final
+// the update to the next LayerNorm launch (`rd`): on return the block's last fc2 branch is still pending, and the first LayerNorm of block l + 1 (or the final
 // layer's) applies it, writes r_{4l+4} and the branch image y2.
 // rerun (recompute mode, train_rerun_block): the block starts from its stored input r_4l, which already holds the update that the forward's first LayerNorm
 // applied, so that launch runs without one — on the row-block kernel and with the statistics' shift the forward's launch kept (LnPending::k_load).
-static int train_block_forward(gtav_dit* h, int l, int B, int T, bool rerun, LnPending& pend, bool& have_pend, hipStream_t s) {
+static int train_block_forward(gtav_dit* h, int l, int B, int T, bool rerun, DeferredResid& rd, hipStream_t s) {
     gtav_dit::Train& tr = h->tr;
     const int D = h->D, P = h->P, NB = B * T, M = NB * P;
-    const float* mod = h->mod;
-    GemmParams g;
-    auto resid_gemm = [&](const OperandOps& o, const f16* X, const f16* Wt, int K, const float* bias, const float* gate, float* x_out, f16* y_save) -> int {
-        GemmParams q;
-        memset(&q, 0, sizeof(q));
-        q.X = X; q.ldx = K; q.W = Wt; q.M = M; q.N = D; q.K = K; q.out = h->parts; q.ldo = D;
-        q.splitk = gemm_choose_splitk(M, D, K);
-        GTAV_REQUIRE((size_t)q.splitk * M <= h->parts_rows, "split-K slabs exceed workspace");
-        RET_IF(o.gemm(q, EPI_PARTIAL, s));
-        memset(&pend, 0, sizeof(pend));
-        pend.parts = h->parts; pend.nsplit = q.splitk; pend.slab_stride = (size_t)M * D; pend.ld = D; pend.bias = bias;
-        pend.gate = gate; pend.gate_stride = h->MODW; pend.gate_rows = nullptr; pend.rows_per_gate = P;
-        pend.x_out = x_out; pend.y_save = y_save;
-        have_pend = true;
-        return 0;
-    };
     for (int hf = 0; hf < 2; ++hf) {
         const int i = l * 2 + hf;
         const gtav_dit::Half& w = h->halves[i];
         gtav_dit::Train::HB& b = tr.hb[i];
-        const float* mb = mod + (size_t)i * 6 * D;
+        const float* mb = h->mod + (size_t)i * 6 * D;
         const OperandOps& o = h->ops(i);
+        auto gate = [&](const float* g) { return ResidGate{g, h->MODW, nullptr, P}; };
         // LN1 normalises r_{2i} (= r_{2i-1} + gate (fc2 of the previous half-block), written to res[2i] by this launch)
-        if (rerun && hf == 0 && l > 0) {
-            GTAV_REQUIRE(!have_pend, "train_block_forward: a re-run starts from a stored block input");
-            LnPending k0;
-            memset(&k0, 0, sizeof(k0));
-            k0.k_load = tr.kshift[l];
-            RET_IF(o.ln_modulate(tr.res[2 * i], D, b.xnA, D, M, D, mb, mb + D, h->MODW, nullptr, P, &k0, h->err_flag, s));
-        } else {
-            if (tr.recompute && hf == 0 && l > 0) pend.k_save = tr.kshift[l];   // (l > 0: the previous block's fc2 is pending)
-            RET_IF(o.ln_modulate(i == 0 ? tr.res[0] : tr.res[2 * i - 1], D, b.xnA, D, M, D, mb, mb + D, h->MODW, nullptr, P, have_pend ? &pend : nullptr, h->err_flag, s));
-        }
-        have_pend = false;
-        memset(&g, 0, sizeof(g));
-        g.X = b.xnA; g.ldx = D; g.W = w.w_qkv; g.M = M; g.N = 3 * D; g.K = D; g.D = D; g.S = P; g.err_flag = h->err_flag;
+        const bool from_stored = rerun && hf == 0 && l > 0;
+        if (from_stored) RET_IF(rd.load_shift(tr.kshift[l]));
+        else if (tr.recompute && hf == 0 && l > 0) rd.save_shift(tr.kshift[l]);   // (l > 0: the previous block's fc2 is pending)
+        RET_IF(o.ln_modulate(from_stored ? tr.res[2 * i] : i == 0 ? tr.res[0] : tr.res[2 * i - 1], D, b.xnA, D, M, D, mb, mb + D, h->MODW, nullptr, P, rd.take(), h->err_flag, s));
+        GemmParams g = gemm_params(b.xnA, D, w.w_qkv, M, 3 * D, D);
+        g.D = D; g.S = P; g.err_flag = h->err_flag;
         if (hf == 0) { g.qkv_mode = QKV_SPATIAL; g.q = b.q; g.k = b.k; g.v = b.v; g.rope_cs = h->rope_s.cs_dev; }
         else { g.qkv_mode = QKV_TEMPORAL; g.q = b.q; g.k = b.k; g.v = b.k; g.Tq = T; g.t0 = 0; g.Tmax = h->maxT; g.rope_cs = h->rope_t.cs_dev; }
         RET_IF(o.gemm(g, EPI_QKV, s));
         if (hf == 0) RET_IF(o.attn_spatial(b.q, b.k, b.v, b.ao, NB, h->heads, P, s, false));
         else RET_IF(o.attn_temporal(b.q, b.k, b.ao, B, P, D, T, 0, h->maxT, s));
-        RET_IF(resid_gemm(o, b.ao, w.w_out, D, w.b_out, mb + 2 * D, tr.res[2 * i + 1], b.y1));
-        RET_IF(o.ln_modulate(tr.res[2 * i], D, b.xnB, D, M, D, mb + 3 * D, mb + 4 * D, h->MODW, nullptr, P, &pend, h->err_flag, s));
-        have_pend = false;
-        memset(&g, 0, sizeof(g));
-        g.X = b.xnB; g.ldx = D; g.W = w.w_fc1; g.M = M; g.N = h->Hm; g.K = D; g.bias = w.b_fc1; g.out = b.u; g.ldo = h->Hm_pad; g.err_flag = h->err_flag;
-        if (g_fuse_gelu_fwd) g.out2 = b.hh;             // h = GELU(u) as a second image of the same epilogue (gemm.h out2)
-        RET_IF(o.gemm(g, EPI_F16_TILED, s));            // the pre-activation is kept: gelu'(u) in the backward pass
+        RET_IF(rd.gemm(o, PC_OUT, b.ao, D, w.w_out, D, w.b_out, gate(mb + 2 * D), false, kNoPrefetch, tr.res[2 * i + 1], b.y1));
+        RET_IF(o.ln_modulate(tr.res[2 * i], D, b.xnB, D, M, D, mb + 3 * D, mb + 4 * D, h->MODW, nullptr, P, rd.take(), h->err_flag, s));
+        GemmParams fc1 = gemm_params(b.xnB, D, w.w_fc1, M, h->Hm, D);
+        fc1.bias = w.b_fc1; fc1.out = b.u; fc1.ldo = h->Hm_pad; fc1.err_flag = h->err_flag;
+        if (g_fuse_gelu_fwd) fc1.out2 = b.hh;             // h = GELU(u) as a second image of the same epilogue (gemm.h out2)
+        RET_IF(o.gemm(fc1, EPI_F16_TILED, s));            // the pre-activation is kept: gelu'(u) in the backward pass
         if (!g_fuse_gelu_fwd) RET_IF(h->ops(i).gelu_tiled(b.u, b.hh, (size_t)round_up(M, 128) * h->Hm_pad, s));
-        RET_IF(resid_gemm(o, b.hh, w.w_fc2, h->Hm_pad, w.b_fc2, mb + 5 * D, tr.res[2 * i + 2], b.y2));
+        RET_IF(rd.gemm(o, PC_FC2, b.hh, h->Hm_pad, w.w_fc2, h->Hm_pad, w.b_fc2, gate(mb + 5 * D), false, kNoPrefetch, tr.res[2 * i + 2], b.y2));
     }
     return 0;
 }
@@ -277,31 +282,25 @@ static int train_rerun_block(gtav_dit* h, int l, hipStream_t s) {
     gtav_dit::Train& tr = h->tr;
     const int D = h->D, L = h->L, i = 2 * l + 2;
     GTAV_REQUIRE(l >= 0 && l < L, "train_backward: no block %d to re-run", l);
-    LnPending pend;
-    bool have_pend = false;
+    DeferredResid rd{h->parts, h->parts_rows * (size_t)D, nullptr, tr.M, D, nullptr, s};
     tr.rc_block = -1;
-    RET_IF(train_block_forward(h, l, tr.B, tr.T, true, pend, have_pend, s));
+    RET_IF(train_block_forward(h, l, tr.B, tr.T, true, rd, s));
     const float* mb = h->mod + (size_t)i * 6 * D;   // (i = 2 L: the final layer's shift and scale)
-    if (l < L - 1) {
-        pend.k_save = tr.kshift[l + 1];
-        RET_IF(h->ops(i).ln_modulate(tr.res[2 * i - 1], D, tr.g_d, D, tr.M, D, mb, mb + D, h->MODW, nullptr, h->P, &pend, h->err_flag, s));
-    } else {
-        RET_IF(h->ops(2 * L + 1).ln_modulate(tr.res[4 * L - 1], D, tr.xnF, D, tr.M, D, mb, mb + D, h->MODW, nullptr, h->P, &pend, h->err_flag, s));
-    }
+    const bool last = l == L - 1;   // (then 2 i - 1 = 4 L - 1, and the launch is the final layer's)
+    if (!last) rd.save_shift(tr.kshift[l + 1]);
+    RET_IF(h->ops(last ? 2 * L + 1 : i).ln_modulate(tr.res[2 * i - 1], D, last ? tr.xnF : tr.g_d, D, tr.M, D, mb, mb + D, h->MODW, nullptr, h->P, rd.take(), h->err_flag, s));
     tr.rc_block = l;
     return 0;
 }
 
 extern "C" {
 
+
 int gtav_dit_train_param_count(gtav_dit* h, int64_t* numel) {
     GTAV_REQUIRE(h && numel, "train_param_count: null argument");
     int64_t c = 0;
-    for (auto& kv : h->wt.slots) {
-        const std::string& n = kv.first;
-        if (n.rfind("tables.", 0) == 0 || n.find("rotary_emb.freqs") != std::string::npos) continue;
-        c += (int64_t)kv.second.R * kv.second.C;
-    }
+    for (auto& kv : h->wt.slots)
+        if (WeightTable::trainable_name(kv.first)) c += (int64_t)kv.second.R * kv.second.C;
     *numel = c;
     return 0;
 }
@@ -357,17 +356,15 @@ int gtav_dit_train_forward(gtav_dit* h, const float* x, const int64_t* t64, cons
     const float* mod = h->mod;
     const OperandOps& oe = h->ops(2 * L), &ofin = h->ops(2 * L + 1);   // patch embedding, final layer (the half-blocks: h->ops(i) below)
     RET_IF(oe.patchify(x, nullptr, NB, h->C, h->H, h->W, h->p, tr.xp, h->Kpe, 1.f, 0.f, h->err_flag, s));
-    GemmParams g;
-    memset(&g, 0, sizeof(g));
-    g.X = tr.xp; g.ldx = h->Kpe; g.W = h->w_pe; g.M = M; g.N = D; g.K = h->Kpe; g.bias = h->b_pe; g.out = tr.res[0]; g.ldo = D;
+    GemmParams g = gemm_params(tr.xp, h->Kpe, h->w_pe, M, D, h->Kpe);
+    g.bias = h->b_pe; g.out = tr.res[0]; g.ldo = D;
     RET_IF(oe.gemm(g, EPI_F32, s));
-    LnPending pend;
-    bool have_pend = false;
-    for (int l = 0; l < L; ++l) RET_IF(train_block_forward(h, l, B, T, false, pend, have_pend, s));
+    DeferredResid rd{h->parts, h->parts_rows * (size_t)D, nullptr, M, D, nullptr, s};   // no in-place target (the backward pass needs every state and branch), no profiler
+    for (int l = 0; l < L; ++l) RET_IF(train_block_forward(h, l, B, T, false, rd, s));
     const float* mf = mod + (size_t)L * 12 * D;
-    RET_IF(ofin.ln_modulate(tr.res[4 * L - 1], D, tr.xnF, D, M, D, mf, mf + D, h->MODW, nullptr, P, &pend, h->err_flag, s));
-    memset(&g, 0, sizeof(g));
-    g.X = tr.xnF; g.ldx = D; g.W = h->w_final; g.M = M; g.N = h->Nfin; g.K = D; g.bias = h->b_final; g.out = h->fo; g.ldo = h->Nfin;
+    RET_IF(ofin.ln_modulate(tr.res[4 * L - 1], D, tr.xnF, D, M, D, mf, mf + D, h->MODW, nullptr, P, rd.take(), h->err_flag, s));
+    g = gemm_params(tr.xnF, D, h->w_final, M, h->Nfin, D);
+    g.bias = h->b_final; g.out = h->fo; g.ldo = h->Nfin;
     RET_IF(ofin.gemm(g, EPI_F32, s));
     RET_IF(launch_unpatchify(h->fo, h->Nfin, out, NB, h->C, h->H, h->W, h->p, 0, 1.f, 0.f, s));
     tr.B = B; tr.T = T; tr.M = M; tr.Mp = round_up(M, 64); tr.rows = rows; tr.have_actions = actions != nullptr; tr.have_fwd = true;
@@ -388,63 +385,53 @@ int gtav_dit_train_get_residual(gtav_dit* h, int32_t k, float* dst, int64_t nume
     return 0;
 }
 
-// Backward of loss = mean((v_pred[:, -1] - v_target)^2) through the forward saved by gtav_dit_train_forward.  Gradients are ADDED to the
-// gradient arena (gtav_dit_zero_grad first), multiplied by the loss scale.
-// Phases of the backward pass (gtav_dit_train_backward_phases): 0 = loss, final projection, final LayerNorm; 1 .. L = the blocks in
-// reverse, phase p = block L - p (both half-blocks and the block's adaLN projection: after phase p every gradient named "blocks.<L-p>.*" is
-// complete, so its slice of the arena can be all-reduced while the earlier blocks are still being differentiated); L + 1 = patch embedding
-// and the shared conditioning path (t_embedder, external_cond).  tr.dres / tr.dmod carry the state from one phase to the next.
-int gtav_dit_train_backward_phases(gtav_dit* h, const float* v_pred, const float* v_target, int32_t phase_begin, int32_t phase_end, void* stream) {
-    GTAV_REQUIRE(h && v_pred && v_target, "train_backward: null argument");
-    GTAV_REQUIRE(h->tr.on && h->tr.have_fwd, "train_backward: no saved forward (gtav_dit_train_forward)");
-    GTAV_REQUIRE(phase_begin >= 0 && phase_begin <= phase_end && phase_end <= h->L + 2, "train_backward: phases [%d, %d) outside [0, %d]", phase_begin, phase_end,
-                 h->L + 2);
-    hipStream_t s = (hipStream_t)stream;
-    gtav_dit::Train& tr = h->tr;
-    const int D = h->D, P = h->P, L = h->L, B = tr.B, T = tr.T, M = tr.M, Mp = tr.Mp, NB = B * T, rows = tr.rows, Hp = h->Hm_pad, MODW = h->MODW;
-    const int ldhc = D + h->Apad;
-    auto slot = [&](const std::string& n) -> Slot& { return h->wt.slots[n]; };
-    // launcher sets of the operand group being differentiated (final layer, half-block i, patch embedding): set where each part begins
-    const OperandOps* op = &h->ops(2 * L + 1);
-    // dX = dY W: A = dY tile-major [M][Kc], WT = tile-major W^T [N][Kc]
-    auto gemm_dx = [&](const f16* A, const f16* WT, int N, int Kc, int epi, void* out, int ldo) -> int {
-        GemmParams q;
-        memset(&q, 0, sizeof(q));
-        q.X = A; q.ldx = Kc; q.W = WT; q.M = M; q.N = N; q.K = Kc; q.out = out; q.ldo = ldo; q.err_flag = h->err_flag;
-        return op->gemm(q, epi, s);
-    };
-    // dW[n][k] += sum_m dY[m][n] X[m][k]: both operands transposed to [.][Mp] (tokens are the contraction), accumulating epilogue
-    // Half-blocks of production widths defer their four dW GEMMs into ONE grouped launch of 256 x 256 tiles (flush_dw; gemm.h)
-    GemmDwGroup dwg[GEMM_DW_MAX_GROUPS];
+}  // extern "C"
+
+// One call of the backward pass: what its parts share (set up by gtav_dit_train_backward_phases from the shapes of the saved forward), and the parts
+struct TrainBackward {
+    gtav_dit* h;
+    gtav_dit::Train& tr;
+    hipStream_t s;
+    const int D, P, L, B, T, M, Mp, NB, rows, Hp, MODW;
+    const OperandOps* op;   // launcher set of the operand group being differentiated (final layer, half-block i, patch embedding): set where each part begins
+    bool defer_dw = false, tn_dw, fuse_ln, fuse_gate, defer_bias;   // which fusions the shapes of this step allow (the constructor says when)
+    GemmDwGroup dwg[GEMM_DW_MAX_GROUPS];   // the pending grouped weight gradients
     int ndw = 0;
-    bool defer_dw = false;
-    if (tr.tAg[0] && g_dw_grouped) {
-        const GemmDwGroup probe[4] = {{tr.tAg[0], tr.tBg[0], tr.dres, D, Hp, Hp}, {tr.tAg[1], tr.tBg[1], tr.dres, Hp, D, D}, {tr.tAg[2], tr.tBg[2], tr.dres, D, D, D},
-                                      {tr.tAg[3], tr.tBg[3], tr.dres, 3 * D, D, D}};
-        defer_dw = gemm_dw_grouped_ok(probe, 4, Mp);
+
+    TrainBackward(gtav_dit* h_, hipStream_t s_)
+        : h(h_), tr(h_->tr), s(s_), D(h->D), P(h->P), L(h->L), B(tr.B), T(tr.T), M(tr.M), Mp(tr.Mp), NB(B * T), rows(tr.rows), Hp(h->Hm_pad), MODW(h->MODW), op(&h->ops(2 * L + 1)) {
+        // Half-blocks of production widths defer their four dW GEMMs into ONE grouped launch of 256 x 256 tiles (flush_dw; gemm.h)
+        if (tr.tAg[0] && g_dw_grouped) {
+            const GemmDwGroup probe[4] = {{tr.tAg[0], tr.tBg[0], tr.dres, D, Hp, Hp}, {tr.tAg[1], tr.tBg[1], tr.dres, Hp, D, D}, {tr.tAg[2], tr.tBg[2], tr.dres, D, D, D},
+                                          {tr.tAg[3], tr.tBg[3], tr.dres, 3 * D, D, D}};
+            defer_dw = gemm_dw_grouped_ok(probe, 4, Mp);
+        }
+        // Whole 128-token row tiles: the grouped launch contracts over the rows of the tile-major operands THEMSELVES (transposing LDS reads, gemm.hip
+        // mainloop256_tn) — no transposed copies (8 of the 17 us transposes per half-block).  The operands must then live until flush_dw: the out-projection's
+        // dY gets a buffer of its own (g_d2), the saved activations and g_u / g_qkv are not rewritten inside a half-block.
+        tn_dw = defer_dw && g_dw_tn && M % 128 == 0;
+        fuse_ln = g_fuse_ln && tr.ln_part && M == NB * P && NB <= rows;   // LayerNorm backward and its per-frame reduction in one launch (train.hip ln_mod_bwd_fused_kernel)
+        // gate backward, the gate's own gradient and the bias gradient of the Linear in front of it in one pass over dres (train.hip gate_bwd_fused_kernel): the
+        // per-frame partial sums of the bias gradient (NB x D floats) must fit the reduction workspace
+        fuse_gate = g_fuse_gate && M == NB * P && (size_t)NB * D <= tr.red_ws_floats;
+        // ... and the partial sums of the half-block's three bias gradients go to three regions of the workspace, which ONE launch adds at the end of the half-block
+        defer_bias = fuse_gate && g_fuse_gelu && (size_t)2 * NB * D + (size_t)gelu_bwd_colsum_splits(M) * Hp <= tr.red_ws_floats;
     }
-    // Whole 128-token row tiles: the grouped launch contracts over the rows of the tile-major operands THEMSELVES (transposing LDS reads, gemm.hip
-    // mainloop256_tn) — no transposed copies (8 of the 17 us transposes per half-block).  The operands must then live until flush_dw: the out-projection's
-    // dY gets a buffer of its own (g_d2), the saved activations and g_u / g_qkv are not rewritten inside a half-block.
-    const bool tn_dw = defer_dw && g_dw_tn && M % 128 == 0;
-    // gate backward, the gate's own gradient and the bias gradient of the Linear in front of it in one pass over dres (train.hip gate_bwd_fused_kernel): the
-    // per-frame partial sums of the bias gradient (NB x D floats) must fit the reduction workspace
-    const bool fuse_ln = g_fuse_ln && tr.ln_part && M == NB * P && NB <= rows;
-    auto ln_bwd = [&](const float* dxn, const float* x, const float* scale, int accumulate, float* dshift, float* dscale) -> int {
-        if (fuse_ln) return launch_ln_mod_bwd_fused(dxn, x, scale, MODW, NB, P, D, tr.dres, accumulate, dshift, dscale, tr.ln_part, s);
-        RET_IF(launch_ln_mod_bwd(dxn, x, scale, MODW, P, M, D, tr.dres, accumulate, tr.stats, s));
-        return launch_frame_reduce_ln(dxn, x, tr.stats, NB, P, D, dshift, dscale, MODW, s);
-    };
-    const size_t ws_cap = colsum_workspace(h->Mmax > h->max_rows ? h->Mmax : h->max_rows, h->Hm_pad > 6 * D ? h->Hm_pad : 6 * D);   // floats of tr.red_ws
-    const bool fuse_gate = g_fuse_gate && M == NB * P && (size_t)NB * D <= ws_cap;
-    const bool defer_bias = fuse_gate && g_fuse_gelu && (size_t)2 * NB * D + (size_t)gelu_bwd_colsum_splits(M) * Hp <= ws_cap;
-    auto flush_dw = [&]() -> int {
+    // dX = dY W: A = dY tile-major [M][Kc], WT = tile-major W^T [N][Kc]
+    int gemm_dx(const f16* A, const f16* WT, int N, int Kc, int epi, void* out, int ldo) {
+        GemmParams q = gemm_params(A, Kc, WT, M, N, Kc);
+        q.out = out; q.ldo = ldo; q.err_flag = h->err_flag;
+        return op->gemm(q, epi, s);
+    }
+    int flush_dw() {
         if (!ndw) return 0;
         const int n = ndw;
         ndw = 0;
         return op->gemm_dw_grouped(dwg, n, tn_dw ? M : Mp, h->err_flag, s, tn_dw);
-    };
-    auto gemm_dw = [&](const f16* dY, int N, const f16* X, int K, float* grad, int slot_i = -1) -> int {
+    }
+    // dW[n][k] += sum_m dY[m][n] X[m][k]: both operands transposed to [.][Mp] (tokens are the contraction), accumulating epilogue; slot_i >= 0: one of the four of a
+    // half-block (fc2, fc1, out-proj, QKV), deferred into its grouped launch where that is on
+    int gemm_dw(const f16* dY, int N, const f16* X, int K, float* grad, int slot_i = -1) {
         if (tn_dw && slot_i >= 0) {
             dwg[ndw++] = GemmDwGroup{dY, X, grad, N, K, K};
             return 0;
@@ -456,141 +443,158 @@ int gtav_dit_train_backward_phases(gtav_dit* h, const float* v_pred, const float
             return 0;
         }
         if (gemm_tn_pays(N, K, M)) {   // contraction over the rows of the tile-major operands themselves (transposing LDS reads): no transposes
-            GemmParams q;
-            memset(&q, 0, sizeof(q));
-            q.X = dY; q.ldx = N; q.W = X; q.M = N; q.N = K; q.K = M; q.out = grad; q.ldo = K;
+            GemmParams q = gemm_params(dY, N, X, N, K, M);
+            q.out = grad; q.ldo = K;
             return op->gemm_tn(q, s);
         }
         RET_IF(op->transpose_tiled(dY, M, N, tr.tA, s));
         RET_IF(op->transpose_tiled(X, M, K, tr.tB, s));
-        GemmParams q;
-        memset(&q, 0, sizeof(q));
-        q.X = tr.tA; q.ldx = Mp; q.W = tr.tB; q.M = N; q.N = K; q.K = Mp; q.out = grad; q.ldo = K;
+        GemmParams q = gemm_params(tr.tA, Mp, tr.tB, N, K, Mp);
+        q.out = grad; q.ldo = K;
         return op->gemm(q, EPI_RESID, s);
-    };
-    const float scale = 2.0f * tr.loss_scale / ((float)B * (float)(h->C * h->H * h->W));
-    GTAV_REQUIRE(h->Nfin <= 64, "train_backward: a final projection wider than 64 features is not implemented");
-    const float* mod = h->mod;
-    float* dmod = tr.dmod;
+    }
+    int ln_bwd(const float* dxn, const float* x, const float* scale, int accumulate, float* dshift, float* dscale) {
+        if (fuse_ln) return launch_ln_mod_bwd_fused(dxn, x, scale, MODW, NB, P, D, tr.dres, accumulate, dshift, dscale, tr.ln_part, s);
+        RET_IF(launch_ln_mod_bwd(dxn, x, scale, MODW, P, M, D, tr.dres, accumulate, tr.stats, s));
+        return launch_frame_reduce_ln(dxn, x, tr.stats, NB, P, D, dshift, dscale, MODW, s);
+    }
     // gradient of one adaLN projection (rows [row0, row0 + n) of W_ada / b_ada) from the dmod columns its LayerNorm / gate backward filled
-    auto ada_grads = [&](size_t row0, int n, const std::string& wn, const std::string& bn) -> int {
-        RET_IF(launch_gemm_tn_f32(dmod + row0, MODW, h->Sc, D, rows, n, D, slot(wn).grad, D, s));
-        return launch_colsum_f32(dmod + row0, MODW, rows, n, slot(bn).grad, tr.red_ws, s);
-    };
-    // ---- phase 0: loss -> final projection -> final LayerNorm ----
-    if (phase_begin <= 0 && 0 < phase_end) {
+    int ada_grads(size_t row0, int n, const Slot* w, const Slot* b) {
+        RET_IF(launch_gemm_tn_f32(tr.dmod + row0, MODW, h->Sc, D, rows, n, D, w->grad, D, s));
+        return launch_colsum_f32(tr.dmod + row0, MODW, rows, n, b->grad, tr.red_ws, s);
+    }
+    // r' = r + gate y backward: dY of the branch (tr.dres gate -> g_out), the gate's gradient (dgate), and the bias gradient of the Linear that made y (ws: its
+    // partial sums under fuse_gate; deferred: left there for the one launch at the end of the half-block)
+    int gate_bwd(const f16* y, const float* gate, float* dgate, f16* g_out, float* dbias, float* ws) {
+        if (fuse_gate) return op->gate_bwd_fused(tr.dres, y, gate, MODW, NB, P, D, g_out, dgate, defer_bias ? nullptr : dbias, ws, h->err_flag, s);
+        RET_IF(op->gate_bwd(tr.dres, gate, MODW, P, M, D, g_out, h->err_flag, s));
+        RET_IF(op->frame_reduce_gate(tr.dres, y, NB, P, D, dgate, MODW, s));
+        return op->colsum_tiled(g_out, M, D, dbias, tr.red_ws, s);
+    }
+    int final_layer(const float* v_pred, const float* v_target);
+    int half_block(int i);
+    int embedders();
+};
+
+// ---- phase 0: loss -> final projection -> final LayerNorm ----
+int TrainBackward::final_layer(const float* v_pred, const float* v_target) {
+    const float scale = 2.0f * tr.loss_scale / ((float)B * (float)(h->C * h->H * h->W));
+    op = &h->ops(2 * L + 1);
     RET_IF(op->mse_bwd_patch(v_pred, v_target, B, T, h->C, h->H, h->W, h->p, scale, tr.dfo, 64, h->err_flag, s));
-    {
-        Slot& wf = slot("final_layer.linear.weight");
-        // db: column sums over the 64-wide (zero-padded) dfo, only the first Nfin belong to the bias: sum into a scratch row first
-        GTAV_CHECK_HIP(hipMemsetAsync(tr.dSc, 0, 64 * sizeof(float), s));
-        RET_IF(op->colsum_tiled(tr.dfo, M, 64, tr.dSc, tr.red_ws, s));
-        RET_IF(launch_add_f32(slot("final_layer.linear.bias").grad, tr.dSc, slot("final_layer.linear.bias").grad, h->Nfin, s));
-        // dW_final [Nfin][D] += dfo^T xnF   (M = Nfin rows of the 64-row transposed operand)
-        RET_IF(op->transpose_tiled(tr.dfo, M, 64, tr.tA, s));
-        RET_IF(op->transpose_tiled(tr.xnF, M, D, tr.tB, s));
-        GemmParams q;
-        memset(&q, 0, sizeof(q));
-        q.X = tr.tA; q.ldx = Mp; q.W = tr.tB; q.M = h->Nfin; q.N = D; q.K = Mp; q.out = wf.grad; q.ldo = D;
-        RET_IF(op->gemm(q, EPI_RESID, s));
-        // d xnF = dfo W_final  -> fp32 [M][D]
-        RET_IF(gemm_dx(tr.dfo, wf.wT, D, 64, EPI_F32, tr.dtmp, D));
-        const float* mf = mod + (size_t)L * 12 * D;
-        float* dmf = dmod + (size_t)L * 12 * D;
-        RET_IF(ln_bwd(tr.dtmp, tr.res[4 * L], mf + D, 0, dmf, dmf + D));
-        RET_IF(ada_grads((size_t)L * 12 * D, 2 * D, "final_layer.adaLN_modulation.1.weight", "final_layer.adaLN_modulation.1.bias"));
+    // db: column sums over the 64-wide (zero-padded) dfo, only the first Nfin belong to the bias: sum into a scratch row first
+    GTAV_CHECK_HIP(hipMemsetAsync(tr.dSc, 0, 64 * sizeof(float), s));
+    RET_IF(op->colsum_tiled(tr.dfo, M, 64, tr.dSc, tr.red_ws, s));
+    RET_IF(launch_add_f32(tr.fin.b->grad, tr.dSc, tr.fin.b->grad, h->Nfin, s));
+    // dW_final [Nfin][D] += dfo^T xnF   (M = Nfin rows of the 64-row transposed operand)
+    RET_IF(op->transpose_tiled(tr.dfo, M, 64, tr.tA, s));
+    RET_IF(op->transpose_tiled(tr.xnF, M, D, tr.tB, s));
+    GemmParams q = gemm_params(tr.tA, Mp, tr.tB, h->Nfin, D, Mp);
+    q.out = tr.fin.w->grad; q.ldo = D;
+    RET_IF(op->gemm(q, EPI_RESID, s));
+    // d xnF = dfo W_final  -> fp32 [M][D]
+    RET_IF(gemm_dx(tr.dfo, tr.fin.w->wT, D, 64, EPI_F32, tr.dtmp, D));
+    const float* mf = h->mod + (size_t)L * 12 * D;
+    float* dmf = tr.dmod + (size_t)L * 12 * D;
+    RET_IF(ln_bwd(tr.dtmp, tr.res[4 * L], mf + D, 0, dmf, dmf + D));
+    return ada_grads((size_t)L * 12 * D, 2 * D, tr.fin_ada.w, tr.fin_ada.b);
+}
+
+// ---- half-block i of phases 1 .. L (the blocks in reverse: temporal half-block, then spatial); tr.dres = d loss / d (residual state) ----
+int TrainBackward::half_block(int i) {
+    const gtav_dit::Train::HB& b = tr.hb[i];
+    const gtav_dit::Train::HalfSlots& p = tr.hs[i];
+    const float* mb = h->mod + (size_t)i * 6 * D;
+    float* dmb = tr.dmod + (size_t)i * 6 * D;
+    op = &h->ops(i);
+    // r_{2i+2} = r_{2i+1} + gate_mlp y2
+    float* const ws_fc2 = tr.red_ws, *const ws_out = tr.red_ws + (defer_bias ? (size_t)NB * D : 0), *const ws_fc1 = tr.red_ws + (defer_bias ? (size_t)2 * NB * D : 0);   // (not deferred: every reduction follows its partial sums at once and the regions may coincide)
+    RET_IF(gate_bwd(b.y2, mb + 5 * D, dmb + 5 * D, tr.g_d, p.fc2.b->grad, ws_fc2));
+    RET_IF(gemm_dw(tr.g_d, D, b.hh, Hp, p.fc2.w->grad, 0));
+    RET_IF(gemm_dx(tr.g_d, p.fc2.w->wT, Hp, D, EPI_F16_TILED, tr.g_h, Hp));
+    if (defer_bias) {
+        RET_IF(op->gelu_bwd_tiled_colsum(tr.g_h, b.u, tr.g_u, M, Hp, nullptr, ws_fc1, h->err_flag, s));
+    } else if (g_fuse_gelu && colsum_workspace(round_up(M, 128), Hp) <= tr.red_ws_floats) {
+        RET_IF(op->gelu_bwd_tiled_colsum(tr.g_h, b.u, tr.g_u, M, Hp, p.fc1.b->grad, tr.red_ws, h->err_flag, s));
+    } else {
+        RET_IF(op->gelu_bwd_tiled(tr.g_h, b.u, tr.g_u, (size_t)round_up(M, 128) * Hp, h->err_flag, s));
+        RET_IF(op->colsum_tiled(tr.g_u, M, Hp, p.fc1.b->grad, tr.red_ws, s));
     }
+    RET_IF(gemm_dw(tr.g_u, Hp, b.xnB, D, p.fc1.w->grad, 1));
+    RET_IF(gemm_dx(tr.g_u, p.fc1.w->wT, D, Hp, EPI_F32, tr.dtmp, D));
+    RET_IF(ln_bwd(tr.dtmp, tr.res[2 * i + 1], mb + 4 * D, 1, dmb + 3 * D, dmb + 4 * D));
+    // r_{2i+1} = r_{2i} + gate_msa y1
+    f16* const g_o = tn_dw ? tr.g_d2 : tr.g_d;   // (the fc2 weight gradient above still reads g_d when the grouped launch is deferred without copies)
+    RET_IF(gate_bwd(b.y1, mb + 2 * D, dmb + 2 * D, g_o, p.out.b->grad, ws_out));
+    RET_IF(gemm_dw(g_o, D, b.ao, D, p.out.w->grad, 2));
+    RET_IF(gemm_dx(g_o, p.out.w->wT, D, D, EPI_F16, tr.dao, D));
+    if (i % 2 == 0) RET_IF(op->attn_spatial_bwd(b.q, b.k, b.v, tr.dao, NB, h->heads, P, D, h->rope_s.cs_dev, tr.g_qkv, h->err_flag, s));
+    else RET_IF(op->attn_temporal_bwd(b.q, b.k, tr.dao, B, P, D, T, h->maxT, h->rope_t.cs_dev, tr.g_qkv, h->err_flag, s));
+    RET_IF(gemm_dw(tr.g_qkv, 3 * D, b.xnA, D, p.qkv.w->grad, 3));
+    if (defer_bias) {
+        const float* wsv[3] = {ws_fc2, ws_out, ws_fc1};
+        float* dbv[3] = {p.fc2.b->grad, p.out.b->grad, p.fc1.b->grad};
+        const int spv[3] = {NB, NB, gelu_bwd_colsum_splits(M)}, nv[3] = {D, D, Hp};
+        RET_IF(launch_colsum_reduce_multi(wsv, dbv, spv, nv, 3, s));
     }
-    // ---- phases 1 .. L: the blocks in reverse (temporal half-block, then spatial); tr.dres = d loss / d (residual state) ----
-    for (int i = 2 * L - 1; i >= 0; --i) {
-        const int l = i / 2, hf = i % 2;
-        const int phase = L - l;
-        if (phase < phase_begin || phase >= phase_end) continue;
-        // recompute mode: the activations of block l are rebuilt at the head of its phase (the last block's are still those of the forward)
-        if (tr.recompute && tr.rc_block != l) RET_IF(train_rerun_block(h, l, s));
-        gtav_dit::Train::HB& b = tr.hb[i];
-        char pre[64];
-        snprintf(pre, sizeof(pre), "blocks.%d.%c_", l, hf == 0 ? 's' : 't');
-        const std::string P_(pre);
-        const float* mb = mod + (size_t)i * 6 * D;
-        float* dmb = dmod + (size_t)i * 6 * D;
-        op = &h->ops(i);
-        // r_{2i+2} = r_{2i+1} + gate_mlp y2
-        // (defer_bias: the partial sums of the half-block's three bias gradients go to three regions of the workspace and ONE launch adds them at the end of the half-block)
-        float* const ws_fc2 = tr.red_ws, *const ws_out = tr.red_ws + (defer_bias ? (size_t)NB * D : 0), *const ws_fc1 = tr.red_ws + (defer_bias ? (size_t)2 * NB * D : 0);   // (not deferred: every reduction follows its partial sums at once and the regions may coincide)
-        if (fuse_gate) {
-            RET_IF(op->gate_bwd_fused(tr.dres, b.y2, mb + 5 * D, MODW, NB, P, D, tr.g_d, dmb + 5 * D, defer_bias ? nullptr : slot(P_ + "mlp.fc2.bias").grad, ws_fc2, h->err_flag, s));
-        } else {
-            RET_IF(op->gate_bwd(tr.dres, mb + 5 * D, MODW, P, M, D, tr.g_d, h->err_flag, s));
-            RET_IF(op->frame_reduce_gate(tr.dres, b.y2, NB, P, D, dmb + 5 * D, MODW, s));
-            RET_IF(op->colsum_tiled(tr.g_d, M, D, slot(P_ + "mlp.fc2.bias").grad, tr.red_ws, s));
-        }
-        RET_IF(gemm_dw(tr.g_d, D, b.hh, Hp, slot(P_ + "mlp.fc2.weight").grad, 0));
-        RET_IF(gemm_dx(tr.g_d, slot(P_ + "mlp.fc2.weight").wT, Hp, D, EPI_F16_TILED, tr.g_h, Hp));
-        if (defer_bias) {
-            RET_IF(op->gelu_bwd_tiled_colsum(tr.g_h, b.u, tr.g_u, M, Hp, nullptr, ws_fc1, h->err_flag, s));
-        } else if (g_fuse_gelu && colsum_workspace(round_up(M, 128), Hp) <= ws_cap) {
-            RET_IF(op->gelu_bwd_tiled_colsum(tr.g_h, b.u, tr.g_u, M, Hp, slot(P_ + "mlp.fc1.bias").grad, tr.red_ws, h->err_flag, s));
-        } else {
-            RET_IF(op->gelu_bwd_tiled(tr.g_h, b.u, tr.g_u, (size_t)round_up(M, 128) * Hp, h->err_flag, s));
-            RET_IF(op->colsum_tiled(tr.g_u, M, Hp, slot(P_ + "mlp.fc1.bias").grad, tr.red_ws, s));
-        }
-        RET_IF(gemm_dw(tr.g_u, Hp, b.xnB, D, slot(P_ + "mlp.fc1.weight").grad, 1));
-        RET_IF(gemm_dx(tr.g_u, slot(P_ + "mlp.fc1.weight").wT, D, Hp, EPI_F32, tr.dtmp, D));
-        RET_IF(ln_bwd(tr.dtmp, tr.res[2 * i + 1], mb + 4 * D, 1, dmb + 3 * D, dmb + 4 * D));
-        // r_{2i+1} = r_{2i} + gate_msa y1
-        f16* const g_o = tn_dw ? tr.g_d2 : tr.g_d;   // (the fc2 weight gradient above still reads g_d when the grouped launch is deferred without copies)
-        if (fuse_gate) {
-            RET_IF(op->gate_bwd_fused(tr.dres, b.y1, mb + 2 * D, MODW, NB, P, D, g_o, dmb + 2 * D, defer_bias ? nullptr : slot(P_ + "attn.to_out.bias").grad, ws_out, h->err_flag, s));
-        } else {
-            RET_IF(op->gate_bwd(tr.dres, mb + 2 * D, MODW, P, M, D, g_o, h->err_flag, s));
-            RET_IF(op->frame_reduce_gate(tr.dres, b.y1, NB, P, D, dmb + 2 * D, MODW, s));
-            RET_IF(op->colsum_tiled(g_o, M, D, slot(P_ + "attn.to_out.bias").grad, tr.red_ws, s));
-        }
-        RET_IF(gemm_dw(g_o, D, b.ao, D, slot(P_ + "attn.to_out.weight").grad, 2));
-        RET_IF(gemm_dx(g_o, slot(P_ + "attn.to_out.weight").wT, D, D, EPI_F16, tr.dao, D));
-        if (hf == 0) RET_IF(op->attn_spatial_bwd(b.q, b.k, b.v, tr.dao, NB, h->heads, P, D, h->rope_s.cs_dev, tr.g_qkv, h->err_flag, s));
-        else RET_IF(op->attn_temporal_bwd(b.q, b.k, tr.dao, B, P, D, T, h->maxT, h->rope_t.cs_dev, tr.g_qkv, h->err_flag, s));
-        RET_IF(gemm_dw(tr.g_qkv, 3 * D, b.xnA, D, slot(P_ + "attn.to_qkv.weight").grad, 3));
-        if (defer_bias) {
-            const float* wsv[3] = {ws_fc2, ws_out, ws_fc1};
-            float* dbv[3] = {slot(P_ + "mlp.fc2.bias").grad, slot(P_ + "attn.to_out.bias").grad, slot(P_ + "mlp.fc1.bias").grad};
-            const int spv[3] = {NB, NB, gelu_bwd_colsum_splits(M)}, nv[3] = {D, D, Hp};
-            RET_IF(launch_colsum_reduce_multi(wsv, dbv, spv, nv, 3, s));
-        }
-        RET_IF(flush_dw());
-        RET_IF(gemm_dx(tr.g_qkv, slot(P_ + "attn.to_qkv.weight").wT, D, 3 * D, EPI_F32, tr.dtmp, D));
-        RET_IF(ln_bwd(tr.dtmp, tr.res[2 * i], mb + D, 1, dmb, dmb + D));
-        // all six dmod chunks of this half-block are in place: its adaLN projection's gradients
-        RET_IF(ada_grads((size_t)i * 6 * D, 6 * D, P_ + "adaLN_modulation.1.weight", P_ + "adaLN_modulation.1.bias"));
-    }
-    if (!(phase_begin <= L + 1 && L + 1 < phase_end)) return 0;
-    // ---- phase L + 1: patch embedding: r_0 = xp W_pe^T + b_pe ----
+    RET_IF(flush_dw());
+    RET_IF(gemm_dx(tr.g_qkv, p.qkv.w->wT, D, 3 * D, EPI_F32, tr.dtmp, D));
+    RET_IF(ln_bwd(tr.dtmp, tr.res[2 * i], mb + D, 1, dmb, dmb + D));
+    // all six dmod chunks of this half-block are in place: its adaLN projection's gradients
+    return ada_grads((size_t)i * 6 * D, 6 * D, p.ada.w, p.ada.b);
+}
+
+// ---- phase L + 1: patch embedding: r_0 = xp W_pe^T + b_pe ----
+int TrainBackward::embedders() {
+    const int ldhc = D + h->Apad;
     op = &h->ops(2 * L);
-    RET_IF(launch_colsum_f32(tr.dres, D, M, D, slot("x_embedder.proj.bias").grad, tr.red_ws, s));
+    RET_IF(launch_colsum_f32(tr.dres, D, M, D, tr.pe.b->grad, tr.red_ws, s));
     RET_IF(op->to_tiled(tr.dres, M, D, tr.g_d, h->err_flag, s));
-    {
-        Slot& wpe = slot("x_embedder.proj.weight");
-        GTAV_REQUIRE(wpe.C == h->Kpe, "train_backward: a patch embedding with padded K (%d of %d) is not implemented", wpe.C, h->Kpe);
-        RET_IF(gemm_dw(tr.g_d, D, tr.xp, h->Kpe, wpe.grad));
-    }
+    GTAV_REQUIRE(tr.pe.w->C == h->Kpe, "train_backward: a patch embedding with padded K (%d of %d) is not implemented", tr.pe.w->C, h->Kpe);
+    RET_IF(gemm_dw(tr.g_d, D, tr.xp, h->Kpe, tr.pe.w->grad));
     // ---- the shared conditioning path (fp32, `rows` = B T rows): c = W_2 SiLU(W_0 e + b_0) + b_2 (+ W_ext a + b_ext), SiLU(c) feeds every adaLN
     // projection (their own gradients were taken block by block above) ----
-    RET_IF(launch_ada_bwd_dx(dmod, MODW, h->w_ada, D, rows, tr.dSc, tr.ada_part, s));
+    RET_IF(launch_ada_bwd_dx(tr.dmod, MODW, h->w_ada, D, rows, tr.dSc, tr.ada_part, s));
     RET_IF(launch_silu_bwd(tr.dSc, D, tr.cpre, D, tr.dc, D, rows, D, s));
-    RET_IF(launch_colsum_f32(tr.dc, D, rows, D, slot("t_embedder.mlp.2.bias").grad, tr.red_ws, s));
-    RET_IF(launch_gemm_tn_f32(tr.dc, D, h->HC, ldhc, rows, D, D, slot("t_embedder.mlp.2.weight").grad, D, s));
+    RET_IF(launch_colsum_f32(tr.dc, D, rows, D, tr.t2.b->grad, tr.red_ws, s));
+    RET_IF(launch_gemm_tn_f32(tr.dc, D, h->HC, ldhc, rows, D, D, tr.t2.w->grad, D, s));
     if (tr.have_actions) {
-        RET_IF(launch_colsum_f32(tr.dc, D, rows, D, slot("external_cond.bias").grad, tr.red_ws, s));
-        RET_IF(launch_gemm_tn_f32(tr.dc, D, h->HC + D, ldhc, rows, D, h->A, slot("external_cond.weight").grad, h->A, s));
+        RET_IF(launch_colsum_f32(tr.dc, D, rows, D, tr.ext.b->grad, tr.red_ws, s));
+        RET_IF(launch_gemm_tn_f32(tr.dc, D, h->HC + D, ldhc, rows, D, h->A, tr.ext.w->grad, h->A, s));
     }
     RET_IF(launch_gemm_nn_f32(tr.dc, D, h->w_t2cat, ldhc, rows, D, D, tr.dh0, D, s));
     RET_IF(launch_silu_bwd(tr.dh0, D, tr.z0, D, tr.dz0, D, rows, D, s));
-    RET_IF(launch_colsum_f32(tr.dz0, D, rows, D, slot("t_embedder.mlp.0.bias").grad, tr.red_ws, s));
-    RET_IF(launch_gemm_tn_f32(tr.dz0, D, h->E, 256, rows, D, 256, slot("t_embedder.mlp.0.weight").grad, 256, s));
+    RET_IF(launch_colsum_f32(tr.dz0, D, rows, D, tr.t0.b->grad, tr.red_ws, s));
+    RET_IF(launch_gemm_tn_f32(tr.dz0, D, h->E, 256, rows, D, 256, tr.t0.w->grad, 256, s));
     // Last kernel of the backward pass: a saturated / non-finite fp16 store on THIS rank becomes +inf in the embedder bucket (the one the data-parallel
     // harness all-reduces last, train.gradient_buckets), so the skip decision of the optimizer step is the same on every rank (ops.h)
-    RET_IF(launch_overflow_publish(h->err_flag, slot("x_embedder.proj.bias").grad, s));
+    return launch_overflow_publish(h->err_flag, tr.pe.b->grad, s);
+}
+
+extern "C" {
+
+// Backward of loss = mean((v_pred[:, -1] - v_target)^2) through the forward saved by gtav_dit_train_forward.  Gradients are ADDED to the
+// gradient arena (gtav_dit_zero_grad first), multiplied by the loss scale.
+// Phases of the backward pass (gtav_dit_train_backward_phases): 0 = loss, final projection, final LayerNorm; 1 .. L = the blocks in
+// reverse, phase p = block L - p (both half-blocks and the block's adaLN projection: after phase p every gradient named "blocks.<L-p>.*" is
+// complete, so its slice of the arena can be all-reduced while the earlier blocks are still being differentiated); L + 1 = patch embedding
+// and the shared conditioning path (t_embedder, external_cond).  tr.dres / tr.dmod carry the state from one phase to the next.
+int gtav_dit_train_backward_phases(gtav_dit* h, const float* v_pred, const float* v_target, int32_t phase_begin, int32_t phase_end, void* stream) {
+    GTAV_REQUIRE(h && v_pred && v_target, "train_backward: null argument");
+    GTAV_REQUIRE(h->tr.on && h->tr.have_fwd, "train_backward: no saved forward (gtav_dit_train_forward)");
+    GTAV_REQUIRE(phase_begin >= 0 && phase_begin <= phase_end && phase_end <= h->L + 2, "train_backward: phases [%d, %d) outside [0, %d]", phase_begin, phase_end,
+                 h->L + 2);
+    GTAV_REQUIRE(h->Nfin <= 64, "train_backward: a final projection wider than 64 features is not implemented");
+    TrainBackward bw(h, (hipStream_t)stream);
+    const int L = h->L;
+    if (phase_begin <= 0 && 0 < phase_end) RET_IF(bw.final_layer(v_pred, v_target));
+    for (int i = 2 * L - 1; i >= 0; --i) {
+        const int l = i / 2, phase = L - l;
+        if (phase < phase_begin || phase >= phase_end) continue;
+        // recompute mode: the activations of block l are rebuilt at the head of its phase (the last block's are still those of the forward)
+        if (h->tr.recompute && h->tr.rc_block != l) RET_IF(train_rerun_block(h, l, bw.s));
+        RET_IF(bw.half_block(i));
+    }
+    if (phase_begin <= L + 1 && L + 1 < phase_end) RET_IF(bw.embedders());
     return 0;
 }
 

@@ -25,50 +25,33 @@ struct gtav_vae {
 
 static int vae_blocks(gtav_vae* h, std::vector<gtav_vae::Block>& blocks, int dim, int heads, const RopeTable& rope, int N,
                       const float* g_last, const float* b_last, hipStream_t s) {
-    // pre-LN blocks (model/vae.py:154-157); residual GEMMs are deferred into the next LayerNorm (see dit_forward_core),
+    // pre-LN blocks (model/vae.py:154-157); residual GEMMs are deferred into the next LayerNorm (api_internal.h DeferredResid),
     // the trailing enc_norm / dec_norm (g_last, b_last) consumes the last one and leaves LN(x) in h->xn.
     const int M = N * h->S, Hm = (int)(dim * h->cfg.mlp_ratio), Hm_pad = round_up(Hm, 128);
-    GemmParams g;
-    LnPending pend;
-    bool have_pend = false;
-    auto resid_gemm = [&](int cls, const f16* X, int ldx, const f16* Wt, int K, const float* bias) -> int {
-        GemmParams q;
-        memset(&q, 0, sizeof(q));
-        q.X = X; q.ldx = ldx; q.W = Wt; q.M = M; q.N = dim; q.K = K; q.out = h->parts; q.ldo = dim;
-        if (gemm_resid_inplace_ok(M, dim, K, 0)) {   // large M: in-place residual epilogue of the persistent loader-wave kernel (see dit_forward_core): no slab round trip
-            q.out = h->resid; q.bias = bias;
-            PROF(h, cls, s, h->ops->gemm(q, EPI_RESID, s));
-            have_pend = false;
-            return 0;
-        }
-        q.splitk = gemm_choose_splitk(M, dim, K);
-        GTAV_REQUIRE((size_t)q.splitk * M * dim <= h->parts_rows * (size_t)h->Dmax, "split-K slabs exceed workspace");
-        PROF(h, cls, s, h->ops->gemm(q, EPI_PARTIAL, s));
-        memset(&pend, 0, sizeof(pend));
-        pend.parts = h->parts; pend.nsplit = q.splitk; pend.slab_stride = (size_t)M * dim; pend.ld = dim; pend.bias = bias;
-        have_pend = true;
+    DeferredResid rd{h->parts, h->parts_rows * (size_t)h->Dmax, h->resid, M, dim, &h->prof, s};
+    const ResidGate no_gate{nullptr, 0, nullptr, 0};
+    auto ln = [&](const float* gamma, const float* beta) -> int {
+        PROF(h, PC_LN, s, h->ops->ln_affine(h->resid, dim, h->xn, dim, M, dim, gamma, beta, rd.take(), h->err_flag, s));
         return 0;
     };
+    // (large M, gemm_resid_inplace_ok: in-place residual epilogue of the persistent loader-wave kernel, see api_dit.hip dit_resid_inplace: no slab round trip)
     for (auto& b : blocks) {
-        PROF(h, PC_LN, s, h->ops->ln_affine(h->resid, dim, h->xn, dim, M, dim, b.g1, b.b1, have_pend ? &pend : nullptr, h->err_flag, s));
-        have_pend = false;
-        memset(&g, 0, sizeof(g));
-        g.X = h->xn; g.ldx = dim; g.W = b.w_qkv; g.M = M; g.N = 3 * dim; g.K = dim; g.bias = b.b_qkv; g.D = dim; g.S = h->S;
+        RET_IF(ln(b.g1, b.b1));
+        GemmParams g = gemm_params(h->xn, dim, b.w_qkv, M, 3 * dim, dim);
+        g.bias = b.b_qkv; g.D = dim; g.S = h->S;
         g.qkv_mode = QKV_SPATIAL; g.q = h->q; g.k = h->k; g.v = h->vt; g.rope_cs = rope.cs_dev; g.err_flag = h->err_flag;
         const bool qps = attn_spatial_wants_prescaled_q(h->S);   // long sequences: q leaves the epilogue in the exponent's unit of the flash attention kernel
         g.rope_cs_q = qps ? rope.csq_dev : nullptr;
         PROF(h, PC_QKV, s, h->ops->gemm(g, EPI_QKV, s));
         PROF(h, PC_ATTN_S, s, h->ops->attn_spatial(h->q, h->k, h->vt, h->ao, N, heads, h->S, s, qps));
-        RET_IF(resid_gemm(PC_OUT, h->ao, dim, b.w_proj, dim, b.b_proj));
-        PROF(h, PC_LN, s, h->ops->ln_affine(h->resid, dim, h->xn, dim, M, dim, b.g2, b.b2, have_pend ? &pend : nullptr, h->err_flag, s));
-        have_pend = false;
-        memset(&g, 0, sizeof(g));
-        g.X = h->xn; g.ldx = dim; g.W = b.w_fc1; g.M = M; g.N = Hm; g.K = dim; g.bias = b.b_fc1; g.out = h->hbuf; g.ldo = Hm_pad; g.err_flag = h->err_flag;
-        PROF(h, PC_FC1, s, h->ops->gemm(g, EPI_GELU_ERF, s));
-        RET_IF(resid_gemm(PC_FC2, h->hbuf, Hm_pad, b.w_fc2, Hm_pad, b.b_fc2));
+        RET_IF(rd.gemm(*h->ops, PC_OUT, h->ao, dim, b.w_proj, dim, b.b_proj, no_gate, gemm_resid_inplace_ok(M, dim, dim, 0)));
+        RET_IF(ln(b.g2, b.b2));
+        GemmParams fc1 = gemm_params(h->xn, dim, b.w_fc1, M, Hm, dim);
+        fc1.bias = b.b_fc1; fc1.out = h->hbuf; fc1.ldo = Hm_pad; fc1.err_flag = h->err_flag;
+        PROF(h, PC_FC1, s, h->ops->gemm(fc1, EPI_GELU_ERF, s));
+        RET_IF(rd.gemm(*h->ops, PC_FC2, h->hbuf, Hm_pad, b.w_fc2, Hm_pad, b.b_fc2, no_gate, gemm_resid_inplace_ok(M, dim, Hm_pad, 0)));
     }
-    PROF(h, PC_LN, s, h->ops->ln_affine(h->resid, dim, h->xn, dim, M, dim, g_last, b_last, have_pend ? &pend : nullptr, h->err_flag, s));
-    return 0;
+    return ln(g_last, b_last);
 }
 
 extern "C" {
@@ -173,7 +156,7 @@ int gtav_vae_finalize(gtav_vae* h, void* stream) {
     GTAV_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
     // model/vae.py:71-76: RotaryEmbedding(dim = head_dim // 4 = 16, pixel, max_freq = H*W) -> 8 freqs, 32 rotated dims
     auto build = [&](RopeTable& r, const char* cn, const char* sn_) -> int {
-        if (h->wt.slots[cn].set && h->wt.slots[sn_].set) return 0;
+        if (h->wt.is_set(cn) && h->wt.is_set(sn_)) return 0;
         std::vector<float> l = linspace_f32(1.0f, (float)(h->S) / 2.0f, 8), fr(8), c, sn;
         for (int i = 0; i < 8; ++i) fr[i] = l[i] * (float)M_PI;
         build_axial_table(fr, h->gh, h->gw, c, sn);
@@ -200,19 +183,14 @@ int gtav_vae_encode(gtav_vae* h, const float* img, float in_scale, float in_shif
     hipStream_t s = (hipStream_t)stream;
     const int De = h->cfg.enc_dim, M = N * h->S;
     PROF(h, PC_OTHER, s, h->ops->patchify(img, nullptr, N, 3, h->H, h->W, h->p, h->xp, h->Kp, in_scale, in_shift, h->err_flag, s));
-    GemmParams g;
-    memset(&g, 0, sizeof(g));
-    g.X = h->xp; g.ldx = h->Kp; g.W = h->w_patch; g.M = M; g.N = De; g.K = h->Kp; g.bias = h->b_patch; g.out = h->resid; g.ldo = De;
+    GemmParams g = gemm_params(h->xp, h->Kp, h->w_patch, M, De, h->Kp);
+    g.bias = h->b_patch; g.out = h->resid; g.ldo = De;
     PROF(h, PC_OTHER, s, h->ops->gemm(g, EPI_F32, s));
     RET_IF(vae_blocks(h, h->enc, De, h->cfg.enc_heads, h->rope_e, N, h->g_enc, h->be_enc, s));
-    memset(&g, 0, sizeof(g));
-    g.X = h->xn; g.ldx = De; g.W = h->w_quant; g.M = M; g.N = h->Mom; g.K = De; g.bias = h->b_quant; g.out = moments; g.ldo = h->Mom;
+    g = gemm_params(h->xn, De, h->w_quant, M, h->Mom, De);
+    g.bias = h->b_quant; g.out = moments; g.ldo = h->Mom;
     PROF(h, PC_OTHER, s, h->ops->gemm(g, EPI_F32, s));
     if (h->cfg.use_variational) PROF(h, PC_OTHER, s, launch_clamp_cols(moments, M, h->Mom, h->Lat, h->Mom, -30.f, 20.f, s));
-    if (h->prof.on) {
-        RET_IF(h->prof.begin(PC_EMPTY, s));
-        RET_IF(h->prof.end(s));
-    }
     return h->prof.collect(s);
 }
 
@@ -224,32 +202,25 @@ int gtav_vae_decode(gtav_vae* h, const float* z, float z_scale, float* img, floa
     hipStream_t s = (hipStream_t)stream;
     const int Dd = h->cfg.dec_dim, M = N * h->S;
     PROF(h, PC_OTHER, s, h->ops->convert_pad(z, h->Lat, M, h->Lat, h->zin, round_up(M, 128), 64, z_scale, 1, s, h->err_flag));
-    GemmParams g;
-    memset(&g, 0, sizeof(g));
-    g.X = h->zin; g.ldx = 64; g.W = h->w_post; g.M = M; g.N = Dd; g.K = 64; g.bias = h->b_post; g.out = h->resid; g.ldo = Dd;
+    GemmParams g = gemm_params(h->zin, 64, h->w_post, M, Dd, 64);
+    g.bias = h->b_post; g.out = h->resid; g.ldo = Dd;
     PROF(h, PC_OTHER, s, h->ops->gemm(g, EPI_F32, s));
     RET_IF(vae_blocks(h, h->dec, Dd, h->cfg.dec_heads, h->rope_d, N, h->g_dec, h->be_dec, s));
-    memset(&g, 0, sizeof(g));
-    g.X = h->xn; g.ldx = Dd; g.W = h->w_pred; g.M = M; g.N = h->Npred; g.K = Dd; g.bias = h->b_pred; g.out = h->po; g.ldo = h->Npred;
+    g = gemm_params(h->xn, Dd, h->w_pred, M, h->Npred, Dd);
+    g.bias = h->b_pred; g.out = h->po; g.ldo = h->Npred;
     PROF(h, PC_OTHER, s, h->ops->gemm(g, EPI_F32, s));
     PROF(h, PC_OTHER, s, launch_unpatchify(h->po, h->Npred, img, N, 3, h->H, h->W, h->p, 1, out_scale, out_shift, s));
-    if (h->prof.on) {
-        RET_IF(h->prof.begin(PC_EMPTY, s));
-        RET_IF(h->prof.end(s));
-    }
     return h->prof.collect(s);
 }
 
 int gtav_vae_profile(gtav_vae* h, int32_t enable) {
     GTAV_REQUIRE(h, "vae_profile: null handle");
-    h->prof.on = enable != 0;
-    h->prof.used = 0;
-    for (int i = 0; i < PC_COUNT; ++i) { h->prof.ms[i] = 0; h->prof.n[i] = 0; }
+    h->prof.reset(enable != 0);
     return 0;
 }
 int gtav_vae_profile_read(gtav_vae* h, double* ms_by_class, int64_t* launches_by_class) {
     GTAV_REQUIRE(h && ms_by_class && launches_by_class, "vae_profile_read: null argument");
-    for (int i = 0; i < PC_COUNT; ++i) { ms_by_class[i] = h->prof.ms[i]; launches_by_class[i] = h->prof.n[i]; }
+    h->prof.read(ms_by_class, launches_by_class);
     return 0;
 }
 
