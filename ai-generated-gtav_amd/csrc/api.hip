@@ -88,6 +88,51 @@ int gtav_vtarget(const float* x, const float* noise, const float* alpha, float* 
                  void* stream) {
     return launch_vtarget(x, noise, alpha, vt, rows, n, clamp_abs, (hipStream_t)stream);
 }
+// ---- counter-based noise (DESIGN.md "Noise streams"): everything is validated before a launch, a bad call touches no device ----
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// rows of n floats on grid.y, four elements per thread
+#define GTAV_RNG_ROWS(name, rows, n)                                                                                                    \
+    GTAV_REQUIRE((n) >= 4 && (n) % 4 == 0, name ": a row of %d floats (a multiple of 4: one generator call makes four elements)", (int)(n)); \
+    GTAV_REQUIRE((rows) >= 1 && (rows) <= 65535, name ": %d rows (1 .. 65535)", (int)(rows))
+int gtav_rng_normal(float* out, int64_t sample_stride, int32_t rows, int32_t n, uint64_t seed, uint32_t draw, uint32_t sample0, uint32_t slot0,
+                    uint32_t slots_per_sample, float clamp_abs, void* stream) {
+    GTAV_REQUIRE(out, "rng_normal: null pointer");
+    GTAV_RNG_ROWS("rng_normal", rows, n);
+    GTAV_REQUIRE(slots_per_sample >= 1, "rng_normal: slots_per_sample 0");
+    GTAV_REQUIRE(clamp_abs >= 0.0f, "rng_normal: clamp_abs %g (>= 0; infinity for no clamp)", (double)clamp_abs);
+    GTAV_REQUIRE(aligned16(out) && sample_stride >= 0 && sample_stride % 4 == 0, "rng_normal: out and sample_stride (%lld floats) must keep every row 16-byte aligned",
+                 (long long)sample_stride);
+    GTAV_REQUIRE((uint32_t)rows <= slots_per_sample || sample_stride >= (int64_t)slots_per_sample * n,
+                 "rng_normal: sample_stride %lld is less than the %u x %d floats of a sample's rows", (long long)sample_stride, slots_per_sample, n);
+    return launch_rng_normal(out, (size_t)sample_stride, rows, n, RngDraw{seed, draw, sample0, slot0, slots_per_sample}, clamp_abs, (hipStream_t)stream);
+}
+int gtav_noise_window_rng(const float* x, const float* alpha, float* x_noisy, float* v_target, int32_t B, int32_t W, int32_t n, uint64_t seed, uint32_t draw,
+                          uint32_t sample0, float clamp_abs, void* stream) {
+    GTAV_REQUIRE(x && alpha && x_noisy && v_target, "noise_window_rng: null pointer");
+    GTAV_REQUIRE(B >= 1 && W >= 1, "noise_window_rng: B=%d W=%d", B, W);
+    GTAV_RNG_ROWS("noise_window_rng", (int64_t)B * W, n);
+    GTAV_REQUIRE(clamp_abs >= 0.0f, "noise_window_rng: clamp_abs %g (>= 0; infinity for no clamp)", (double)clamp_abs);
+    GTAV_REQUIRE(aligned16(x) && aligned16(x_noisy) && aligned16(v_target), "noise_window_rng: x, x_noisy and v_target must be 16-byte aligned");
+    return launch_noise_window_rng(x, alpha, x_noisy, v_target, B, W, n, RngDraw{seed, draw, sample0, 0u, (uint32_t)W}, clamp_abs, (hipStream_t)stream);
+}
+int gtav_vae_posterior_sample(const float* moments, float* z, int32_t frames, int32_t tokens, int32_t latent_dim, uint64_t seed, uint32_t draw,
+                              uint32_t sample0, uint32_t slot0, uint32_t slots_per_sample, void* stream) {
+    GTAV_REQUIRE(moments && z, "vae_posterior_sample: null pointer");
+    GTAV_REQUIRE(latent_dim >= 4 && latent_dim % 4 == 0, "vae_posterior_sample: latent_dim %d (a multiple of 4: one generator call makes four elements)", latent_dim);
+    GTAV_REQUIRE(tokens >= 1 && (int64_t)tokens * latent_dim < (int64_t)1 << 30, "vae_posterior_sample: %d tokens x %d", tokens, latent_dim);
+    GTAV_RNG_ROWS("vae_posterior_sample", frames, tokens * latent_dim);
+    GTAV_REQUIRE(slots_per_sample >= 1, "vae_posterior_sample: slots_per_sample 0");
+    GTAV_REQUIRE(aligned16(moments) && aligned16(z), "vae_posterior_sample: moments and z must be 16-byte aligned");
+    return launch_vae_posterior_sample(moments, z, frames, tokens, latent_dim, RngDraw{seed, draw, sample0, slot0, slots_per_sample}, (hipStream_t)stream);
+}
+int gtav_op_rng_bits(uint32_t* out, int32_t rows, int32_t n, uint64_t seed, uint32_t draw, uint32_t sample0, uint32_t slot0, uint32_t slots_per_sample,
+                     void* stream) {
+    GTAV_REQUIRE(out && aligned16(out), "op_rng_bits: null or unaligned pointer");
+    GTAV_RNG_ROWS("op_rng_bits", rows, n);
+    GTAV_REQUIRE(slots_per_sample >= 1, "op_rng_bits: slots_per_sample 0");
+    return launch_rng_bits(out, rows, n, RngDraw{seed, draw, sample0, slot0, slots_per_sample}, (hipStream_t)stream);
+}
+#undef GTAV_RNG_ROWS
 int gtav_axpy_f32(float* y, const float* x, float alpha, int64_t n, void* stream) {
     GTAV_REQUIRE(y && x && n > 0, "axpy_f32: bad argument");
     return launch_axpy_f32(y, x, alpha, (size_t)n, (hipStream_t)stream);

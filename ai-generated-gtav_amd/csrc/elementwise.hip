@@ -1,5 +1,5 @@
 // Memory-bound kernels around the GEMMs: LayerNorm+modulate, patch gather/scatter, conversions,
-// conditioning inputs, the DDIM update and the training-side noising / v-target / MSE.
+// conditioning inputs, the DDIM update, the training-side noising / v-target / MSE and the counter-based noise.
 // All are HBM-bound; every global access is 8-16 B per lane, rows are walked by whole waves.
 #include "ops.h"
 
@@ -481,6 +481,20 @@ __global__ void ddim_update_step_kernel(float* __restrict__ x, size_t frames_per
         xf[i] = ddim_one(xf[i], v[b * v_stride + i], at, an, fin);
 }
 
+// The noising and the v-target of one element (train_dit.py:625-645), shared by the kernels that read their noise from memory and by the one that draws it
+// (noise_window_rng_kernel), which must agree to the bit.  Contraction is OFF: left to itself the compiler keeps add_noise_kernel / vtarget_kernel at two
+// products and a sum (packed multiplies) but fuses one product into an fma in the kernel that computes both expressions, and the last bit moves.  The pragma
+// states what the two old kernels have always computed.
+__device__ __forceinline__ float clamp_noise(float z, float clamp_abs) { return fminf(fmaxf(z, -clamp_abs), clamp_abs); }
+__device__ __forceinline__ float add_noise_one(float x, float z, float sa, float s1) {
+#pragma clang fp contract(off)
+    return x * sa + s1 * z;
+}
+__device__ __forceinline__ float vtarget_one(float x, float z, float sa, float s1) {
+#pragma clang fp contract(off)
+    return sa * z - s1 * x;
+}
+
 __global__ void add_noise_kernel(const float* __restrict__ x, const float* __restrict__ noise, const float* __restrict__ alpha,
                                  float* __restrict__ out, int n, float clamp_abs) {
     const int r = blockIdx.y;
@@ -488,8 +502,7 @@ __global__ void add_noise_kernel(const float* __restrict__ x, const float* __res
     const float sa = sqrtf(a), s1 = sqrtf(1.0f - a);
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const size_t o = (size_t)r * n + i;
-        const float z = fminf(fmaxf(noise[o], -clamp_abs), clamp_abs);
-        out[o] = x[o] * sa + s1 * z;
+        out[o] = add_noise_one(x[o], clamp_noise(noise[o], clamp_abs), sa, s1);
     }
 }
 
@@ -500,10 +513,105 @@ __global__ void vtarget_kernel(const float* __restrict__ x, const float* __restr
     const float sa = sqrtf(a), s1 = sqrtf(1.0f - a);
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const size_t o = (size_t)r * n + i;
-        const float z = fminf(fmaxf(noise[o], -clamp_abs), clamp_abs);
-        vt[o] = sa * z - s1 * x[o];
+        vt[o] = vtarget_one(x[o], clamp_noise(noise[o], clamp_abs), sa, s1);
     }
 }
+
+// ------------------------------------------------------------------------------------------
+// Counter-based noise (DESIGN.md "Noise streams"): Philox4x32-10 keyed by the 64-bit seed, counter (e >> 2, slot, sample, draw) for element e of a row
+// (one latent frame of one sample).  A draw is a pure function of those numbers: no launch geometry, batch split or call history enters.  One thread makes
+// one Philox call = four consecutive elements and stores 16 bytes.  Plain fp32, no 2-byte operand: compiled with the fp16 objects only.
+//   u(x) = ((x >> 9) + 0.5) 2^-23            exact in fp32, strictly inside (0, 1)
+//   (z0, z1) = sqrt(-2 ln u(x0)) (cos, sin)(2 pi u(x1)), (z2, z3) likewise from (x2, x3)      |z| <= sqrt(48 ln 2) = 5.768
+// logf / sincospif are the accurate library forms (the fast intrinsics lose the 2^-17 bound of tests/test_gpu_rng.py near u -> 1); sincospif takes 2 u, which
+// is exact, so the angle is never rounded.
+// ------------------------------------------------------------------------------------------
+#ifndef GTAV_BF16_OPERANDS
+__device__ __forceinline__ u32x4 philox4x32_10(u32x4 c, unsigned k0, unsigned k1) {
+#pragma unroll
+    for (int round = 0; round < 10; ++round) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
+        c = u32x4{hi1 ^ c[1] ^ k0, lo1, hi0 ^ c[3] ^ k1, lo0};
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return c;
+}
+// where the rows of a call sit in the stream: row r is frame slot slot0 + r % slots_per_sample of sample sample0 + r / slots_per_sample
+struct RngStream {
+    unsigned k0, k1, draw, sample0, slot0, slots_per_sample;
+};
+__device__ __forceinline__ u32x4 rng_bits4(const RngStream& s, unsigned row, unsigned quad) {
+    return philox4x32_10(u32x4{quad, s.slot0 + row % s.slots_per_sample, s.sample0 + row / s.slots_per_sample, s.draw}, s.k0, s.k1);
+}
+__device__ __forceinline__ float rng_u01(unsigned x) { return ((float)(x >> 9) + 0.5f) * 0x1p-23f; }
+__device__ __forceinline__ f32x4 rng_normal4(u32x4 x) {
+    const float r0 = sqrtf(-2.0f * logf(rng_u01(x[0]))), r1 = sqrtf(-2.0f * logf(rng_u01(x[2])));
+    float s0, c0, s1, c1;
+    sincospif(2.0f * rng_u01(x[1]), &s0, &c0);
+    sincospif(2.0f * rng_u01(x[3]), &s1, &c1);
+    return f32x4{r0 * c0, r0 * s0, r1 * c1, r1 * s1};
+}
+
+// raw words of rows x n (test hook): out[r][4 q .. 4 q + 3]
+__global__ __launch_bounds__(256) void rng_bits_kernel(unsigned* __restrict__ out, int n, RngStream s) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= (n >> 2)) return;
+    *(u32x4*)(out + (size_t)blockIdx.y * n + 4 * (size_t)q) = rng_bits4(s, blockIdx.y, q);
+}
+
+// clamped normals into rows of n floats: the rows of one sample are contiguous, samples are sample_stride floats apart
+__global__ __launch_bounds__(256) void rng_normal_kernel(float* __restrict__ out, size_t sample_stride, int n, RngStream s, float clamp_abs) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= (n >> 2)) return;
+    const unsigned r = blockIdx.y;
+    f32x4 z = rng_normal4(rng_bits4(s, r, q));
+#pragma unroll
+    for (int j = 0; j < 4; ++j) z[j] = clamp_noise(z[j], clamp_abs);
+    *(f32x4*)(out + (r / s.slots_per_sample) * sample_stride + (size_t)(r % s.slots_per_sample) * n + 4 * (size_t)q) = z;
+}
+
+// The training window in one launch (train_dit.py:625-645): x (B, W, n), alpha (B, W) -> x_noisy (B, W, n) and, from the last slot, v_target (B, n).  The noise
+// of row (b, w) is the stream's (sample0 + b, slot w); it is never stored.  Same per-element expressions as add_noise_kernel / vtarget_kernel.
+__global__ __launch_bounds__(256) void noise_window_rng_kernel(const float* __restrict__ x, const float* __restrict__ alpha, float* __restrict__ x_noisy,
+                                                               float* __restrict__ v_target, int W, int n, RngStream s, float clamp_abs) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= (n >> 2)) return;
+    const unsigned r = blockIdx.y;          // s.slots_per_sample == W, s.slot0 == 0: row r = (b, w)
+    const float a = alpha[r];
+    const float sa = sqrtf(a), s1 = sqrtf(1.0f - a);
+    const f32x4 z = rng_normal4(rng_bits4(s, r, q));
+    const size_t o = (size_t)r * n + 4 * (size_t)q;
+    const f32x4 xv = *(const f32x4*)(x + o);
+    f32x4 y, v;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float zj = clamp_noise(z[j], clamp_abs);
+        y[j] = add_noise_one(xv[j], zj, sa, s1);
+        v[j] = vtarget_one(xv[j], zj, sa, s1);
+    }
+    *(f32x4*)(x_noisy + o) = y;
+    if (r % W == (unsigned)W - 1) *(f32x4*)(v_target + (size_t)(r / W) * n + 4 * (size_t)q) = v;
+}
+
+// DiagonalGaussianDistribution.sample (model/vae.py:36-39): moments (frames, tokens, 2 L) -> z (frames, tokens, L) = mean + exp(0.5 clamp(logvar, -30, 20)) N;
+// a row of the stream is one frame's tokens x L block (L % 4 == 0: a thread's four elements lie in one token)
+__global__ __launch_bounds__(256) void vae_posterior_sample_kernel(const float* __restrict__ mom, float* __restrict__ zout, int tokens, int L, RngStream s) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    const int n = tokens * L;
+    if (q >= (n >> 2)) return;
+    const unsigned r = blockIdx.y;
+    const int e = 4 * q, tok = e / L, l = e % L;
+    const float* m = mom + ((size_t)r * tokens + tok) * 2 * L + l;
+    const f32x4 mean = *(const f32x4*)m, logvar = *(const f32x4*)(m + L);
+    const f32x4 z = rng_normal4(rng_bits4(s, r, q));
+    f32x4 y;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) y[j] = mean[j] + expf(0.5f * fminf(fmaxf(logvar[j], -30.0f), 20.0f)) * z[j];
+    *(f32x4*)(zout + (size_t)r * n + e) = y;
+}
+#endif  // !GTAV_BF16_OPERANDS
 
 // deterministic two-stage mean of squared differences
 __global__ __launch_bounds__(256) void mse_partial_kernel(const float* __restrict__ a, size_t a_stride, const float* __restrict__ b,
@@ -894,6 +1002,34 @@ int launch_vtarget(const float* x, const float* noise, const float* alpha, float
     GTAV_CHECK_HIP(hipGetLastError());
     return 0;
 }
+
+#ifndef GTAV_BF16_OPERANDS
+// The callers (api.hip) have validated: n % 4 == 0, 1 <= rows <= 65535 (grid.y), 16-byte aligned rows, slots_per_sample >= 1.
+static RngStream rng_stream(const RngDraw& d) {
+    return RngStream{(unsigned)(d.seed & 0xffffffffu), (unsigned)(d.seed >> 32), d.draw, d.sample0, d.slot0, d.slots_per_sample};
+}
+int launch_rng_bits(uint32_t* out, int rows, int n, const RngDraw& d, hipStream_t stream) {
+    hipLaunchKernelGGL(rng_bits_kernel, dim3(cdiv(n >> 2, 256), rows), dim3(256), 0, stream, out, n, rng_stream(d));
+    GTAV_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+int launch_rng_normal(float* out, size_t sample_stride, int rows, int n, const RngDraw& d, float clamp_abs, hipStream_t stream) {
+    hipLaunchKernelGGL(rng_normal_kernel, dim3(cdiv(n >> 2, 256), rows), dim3(256), 0, stream, out, sample_stride, n, rng_stream(d), clamp_abs);
+    GTAV_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+int launch_noise_window_rng(const float* x, const float* alpha, float* x_noisy, float* v_target, int B, int W, int n, const RngDraw& d, float clamp_abs,
+                            hipStream_t stream) {
+    hipLaunchKernelGGL(noise_window_rng_kernel, dim3(cdiv(n >> 2, 256), B * W), dim3(256), 0, stream, x, alpha, x_noisy, v_target, W, n, rng_stream(d), clamp_abs);
+    GTAV_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+int launch_vae_posterior_sample(const float* moments, float* z, int frames, int tokens, int L, const RngDraw& d, hipStream_t stream) {
+    hipLaunchKernelGGL(vae_posterior_sample_kernel, dim3(cdiv(tokens * L >> 2, 256), frames), dim3(256), 0, stream, moments, z, tokens, L, rng_stream(d));
+    GTAV_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+#endif  // !GTAV_BF16_OPERANDS
 
 int launch_mse(const float* a, size_t a_stride, const float* b, size_t b_stride, int rows, int n, float* out_scalar,
                hipStream_t stream) {

@@ -91,6 +91,22 @@ int launch_vtarget(const float* x, const float* noise, const float* alpha /*[row
 int launch_mse(const float* a, size_t a_stride, const float* b, size_t b_stride, int rows, int n, float* out_scalar,
                hipStream_t stream);
 
+// Counter-based noise (DESIGN.md "Noise streams"): Philox4x32-10, key = the two halves of `seed`, counter (element >> 2, slot, sample, draw).  Row r of a call is
+// frame slot slot0 + r % slots_per_sample of sample sample0 + r / slots_per_sample.  fp32 only: defined in the fp16 object of elementwise.hip, no bf16 twin.
+// n % 4 == 0, rows <= 65535 and 16-byte aligned rows are the callers' to check (api.hip).
+struct RngDraw {
+    uint64_t seed;
+    uint32_t draw, sample0, slot0, slots_per_sample;
+};
+int launch_rng_bits(uint32_t* out, int rows, int n, const RngDraw& d, hipStream_t stream);                                       // raw words, rows contiguous
+// clamp(N(0,1), +-clamp_abs) into rows of n floats; the rows of a sample are contiguous, samples sample_stride floats apart
+int launch_rng_normal(float* out, size_t sample_stride, int rows, int n, const RngDraw& d, float clamp_abs, hipStream_t stream);
+// launch_add_noise over x (B, W, n) + launch_vtarget of its last slot with the noise of (sample0 + b, slot w) drawn in the launch (d.slot0 = 0, d.slots_per_sample = W)
+int launch_noise_window_rng(const float* x, const float* alpha /*[B][W]*/, float* x_noisy, float* v_target /*[B][n]*/, int B, int W, int n, const RngDraw& d,
+                            float clamp_abs, hipStream_t stream);
+// z (frames, tokens, L) = mean + exp(0.5 clamp(logvar, -30, 20)) N from moments (frames, tokens, 2 L); a row of the stream is one frame
+int launch_vae_posterior_sample(const float* moments, float* z, int frames, int tokens, int L, const RngDraw& d, hipStream_t stream);
+
 // ---- train.hip (backward pass + optimizer) ---------------------------------------------
 int launch_ln_mod_bwd(const float* dxn, const float* x, const float* scale, int mod_stride, int rows_per_mod, int M, int D, float* dres, int accumulate,
                       float* stats, hipStream_t stream);

@@ -50,9 +50,9 @@ def vae_decode_frames(x: torch.Tensor, vae, scaling_factor: float = SCALING_FACT
 
 
 @torch.inference_mode()
-def generate_latents(model, x_prompt: torch.Tensor, total_frames: int, noise_steps: int, noise_chunks: torch.Tensor,
+def generate_latents(model, x_prompt: torch.Tensor, total_frames: int, noise_steps: int, noise_chunks: Optional[torch.Tensor] = None,
                      actions: Optional[torch.Tensor] = None, stabilization_level: int = 15, noise_abs_max: float = 20.0,
-                     clamp_min: float = 1e-4, ctx_cache: bool = False, hoist_cond: bool = True) -> torch.Tensor:
+                     clamp_min: float = 1e-4, ctx_cache: bool = False, hoist_cond: bool = True, rng=None) -> torch.Tensor:
     """generate.py:186-220.  x_prompt (B, n_prompt, C, h, w) latents; noise_chunks (B, total-n_prompt, C, h, w)
     standard-normal draws (clamped to +-noise_abs_max here, generate.py:201-202); actions (B, total, 25) or None.
     ctx_cache=False re-runs the whole window on every noise step exactly like the reference;
@@ -60,16 +60,28 @@ def generate_latents(model, x_prompt: torch.Tensor, total_frames: int, noise_ste
     taking the context K/V of the temporal layers from the cache (same result, ~4.8x less work).
     hoist_cond=True builds the conditioning (adaLN) table of all noise steps of a frame in one batch per frame (the
     conditioning never depends on x); False recomputes it inside every step like DiT.forward does. Same results.
+    Exactly one of noise_chunks and rng (a gtav_amd.rng.NoiseSource) is given.  With rng the clip takes one draw number and the new frames are filled in
+    place on the device, clamp included: frame f of sample b is slot f of sample rng.sample0 + b (DESIGN.md "Noise streams").
     Returns latents (B, total_frames, C, h, w) on the model's device."""
+    if (noise_chunks is None) == (rng is None):
+        raise ValueError("generate_latents: give exactly one of noise_chunks and rng")
     dev = model.device
     B, n_prompt = x_prompt.shape[:2]
     x = torch.empty((B, total_frames, *x_prompt.shape[2:]), device=dev, dtype=torch.float32)
     x[:, :n_prompt] = x_prompt.to(dev, torch.float32)                          # copies only: torch is storage here
-    x[:, n_prompt:] = noise_chunks.to(dev, torch.float32)
     fsz = x[0, 0].numel()
-    with torch.cuda.device(dev):                                               # generate.py:201-202 clamp, as a HIP kernel
-        _lib.check(_lib.load().gtav_clamp_frames(x.data_ptr(), B, total_frames, n_prompt, fsz, -float(noise_abs_max),
-                                                 float(noise_abs_max), _lib.current_stream()))
+    n_new = total_frames - n_prompt
+    if rng is not None:
+        draw = rng.next_draw()
+        with torch.cuda.device(dev):                                           # generate.py:201-202 randn + clamp, one launch
+            if n_new > 0:
+                _lib.check(_lib.load().gtav_rng_normal(x[:, n_prompt:].data_ptr(), total_frames * fsz, B * n_new, fsz, rng.seed, draw,
+                                                       rng.sample0 & 0xFFFFFFFF, n_prompt, n_new, float(noise_abs_max), _lib.current_stream()))
+    else:
+        x[:, n_prompt:] = noise_chunks.to(dev, torch.float32)
+        with torch.cuda.device(dev):                                           # generate.py:201-202 clamp, as a HIP kernel
+            _lib.check(_lib.load().gtav_clamp_frames(x.data_ptr(), B, total_frames, n_prompt, fsz, -float(noise_abs_max),
+                                                     float(noise_abs_max), _lib.current_stream()))
     act = actions.to(dev, torch.float32).contiguous() if actions is not None else None
     model.set_schedule(_alphas_cumprod(clamp_min))
     noise_range = torch.linspace(0, 999, noise_steps + 1)                      # generate.py:194 (float)
@@ -226,14 +238,15 @@ def shard_inputs(global_batch: int, rank: int, world: int, n_prompt: int, total_
     return list(range(lo, hi)), torch.stack([f for f, _ in ins]), torch.stack([n for _, n in ins])
 
 
-def generate_clip(dit, vae, frames: torch.Tensor, noise: torch.Tensor, total_frames: int, noise_steps: int,
-                  actions: Optional[torch.Tensor] = None, ctx_cache: bool = False, to_uint8: bool = True, gather: bool = True):
+def generate_clip(dit, vae, frames: torch.Tensor, noise: Optional[torch.Tensor], total_frames: int, noise_steps: int,
+                  actions: Optional[torch.Tensor] = None, ctx_cache: bool = False, to_uint8: bool = True, gather: bool = True, rng=None):
     """One rank's whole clip (reference generate.py:main for its shard of the batch): VAE-encode the prompt frames,
     run the denoising loop, all-gather the final latents over the ranks (the path's only collective, RCCL over xGMI
-    under the nccl backend) and decode this rank's own frames.  Returns (gathered latents, decoded local frames)."""
+    under the nccl backend) and decode this rank's own frames.  Exactly one of noise and rng (a NoiseSource whose sample0 is the global id of this rank's
+    first sample) is given, as in generate_latents.  Returns (gathered latents, decoded local frames)."""
     n_prompt = frames.shape[1]
     x0 = vae_encode(frames.to(vae.device), vae, n_prompt)
-    x = generate_latents(dit, x0, total_frames, noise_steps, noise, actions, ctx_cache=ctx_cache)
+    x = generate_latents(dit, x0, total_frames, noise_steps, noise, actions, ctx_cache=ctx_cache, rng=rng)
     xg = all_gather_latents(x) if gather else x
     out = vae_decode_frames(x, vae, to_uint8=to_uint8)
     vae.check()

@@ -50,6 +50,7 @@ class VaeConfig(C.Structure):
 
 
 _p, _i, _f, _l = C.c_void_p, C.c_int32, C.c_float, C.c_int64
+_u32, _u64 = C.c_uint32, C.c_uint64
 
 # name -> argtypes (restype is int unless listed in _RESTYPES)
 SIGNATURES = {
@@ -119,6 +120,10 @@ SIGNATURES = {
     "gtav_ddim_update": [_p, _p, _p, _i, _i, _p, _p, _i, _p],
     "gtav_add_noise": [_p, _p, _p, _p, _i, _i, _f, _p],
     "gtav_vtarget": [_p, _p, _p, _p, _i, _i, _f, _p],
+    "gtav_rng_normal": [_p, _l, _i, _i, _u64, _u32, _u32, _u32, _u32, _f, _p],
+    "gtav_noise_window_rng": [_p, _p, _p, _p, _i, _i, _i, _u64, _u32, _u32, _f, _p],
+    "gtav_vae_posterior_sample": [_p, _p, _i, _i, _i, _u64, _u32, _u32, _u32, _u32, _p],
+    "gtav_op_rng_bits": [_p, _i, _i, _u64, _u32, _u32, _u32, _u32, _p],
     "gtav_mse": [_p, _l, _p, _l, _i, _i, _p, _p],
     "gtav_axpy_f32": [_p, _p, _f, _l, _p],
     "gtav_frames_to_u8": [_p, _p, _i, _i, _i, _p],

@@ -32,8 +32,21 @@ class DiagonalGaussianDistribution:
     def var(self):
         return torch.zeros_like(self.mean) if self.deterministic else torch.exp(self.logvar)
 
-    def sample(self):
-        return self.mean + self.std * torch.randn(self.mean.shape).to(device=self.parameters.device)
+    def sample(self, rng=None, slot0: int = 0, slots_per_sample: int = 1):
+        """mean + std * N(0,1).  Default: the draw is made on the CPU by torch's generator and copied (model/vae.py:36-39).  rng (a gtav_amd.rng.NoiseSource):
+        one launch on the device (gtav_vae_posterior_sample), one draw number; frame r of the batch is slot slot0 + r % slots_per_sample of sample
+        rng.sample0 + r // slots_per_sample (DESIGN.md "Noise streams")."""
+        if rng is None:
+            return self.mean + self.std * torch.randn(self.mean.shape).to(device=self.parameters.device)
+        if self.deterministic:
+            return self.mean.clone()
+        mom = self.parameters.to(torch.float32).contiguous()
+        N, tokens, two_l = mom.shape
+        z = torch.empty((N, tokens, two_l // 2), device=mom.device, dtype=torch.float32)
+        with torch.cuda.device(mom.device):
+            _lib.check(_lib.load().gtav_vae_posterior_sample(mom.data_ptr(), z.data_ptr(), N, tokens, two_l // 2, rng.seed, rng.next_draw(),
+                                                             rng.sample0 & 0xFFFFFFFF, slot0, slots_per_sample, _lib.current_stream()))
+        return z
 
     def mode(self):
         return self.mean
@@ -190,10 +203,10 @@ class AutoencoderKL(_HipModule):
         _lib.check(_lib.load().gtav_vae_profile_read(self._handle, ms, n))
         return {k: (ms[i], n[i]) for i, k in enumerate(self.PROFILE_CLASSES)}
 
-    def autoencode(self, input, sample_posterior=True):
-        """model/vae.py:340-347."""
+    def autoencode(self, input, sample_posterior=True, rng=None):
+        """model/vae.py:340-347.  rng (a gtav_amd.rng.NoiseSource): the posterior is sampled on the device, frame r of the batch as sample rng.sample0 + r."""
         posterior = self.encode(input)
-        z = posterior.sample() if (self.use_variational and sample_posterior) else posterior.mode()
+        z = posterior.sample(rng=rng) if (self.use_variational and sample_posterior) else posterior.mode()
         return self.decode(z), posterior, z
 
     def forward(self, inputs, labels=None, split="train"):

@@ -1,6 +1,7 @@
 """Training forward + loss (reference train_dit.py:329-351 `encode_frames`, :554-682 `_shared_step`, forward part):
 noise the context and target frames, run the DiT once over the window, MSE against the v-target of the
-last frame.  Random draws are arguments so that parity runs can inject them."""
+last frame.  Random draws are arguments so that parity runs can inject them; with `rng=` (a gtav_amd.rng.NoiseSource) the step makes them itself:
+the noise indices on the host, the Gaussian noise inside the launch that consumes it (DESIGN.md "Noise streams")."""
 from __future__ import annotations
 
 from typing import Optional
@@ -8,6 +9,7 @@ from typing import Optional
 import torch
 
 from . import lib as _lib
+from . import rng as _rng
 from .generate import vae_encode
 from .utils import alphas_cumprod as _alphas_cumprod
 
@@ -18,11 +20,18 @@ def encode_frames(vae, frames: torch.Tensor) -> torch.Tensor:
     return vae_encode(frames, vae, frames.shape[1])
 
 
-def _frame_step(dit, latents, actions, i, target_noise_idx, ctx_noise_idx, ctx_noise, noise, nr, ac, noise_abs_max, keep_activations):
-    """One iteration of the frame loop of `_shared_step` (train_dit.py:590-650) for target frame i: returns (loss (1,), v_pred, v_target)."""
+def _frame_step(dit, latents, actions, i, target_noise_idx, ctx_noise_idx, ctx_noise, noise, nr, ac, noise_abs_max, keep_activations, rng=None,
+                noise_steps=None, ctx_max_noise_idx=None):
+    """One iteration of the frame loop of `_shared_step` (train_dit.py:590-650) for target frame i: returns (loss (1,), v_pred, v_target).
+    With `rng` the frame takes one draw number: the two noise indices of every sample come from the host stream (train_dit.py:574-587) and the window's noise
+    (slots 0 .. W - 1 of sample rng.sample0 + b) is drawn inside the one launch that noises the window and makes the v-target."""
     dev = dit.device
     L = _lib.load()
     B = latents.shape[0]
+    if rng is not None:
+        draw = rng.next_draw()
+        target_noise_idx = rng.randint(1, noise_steps + 1, B, _rng.SLOT_TARGET_IDX, draw).tolist()
+        ctx_noise_idx = rng.randint(1, ctx_max_noise_idx + 1, B, _rng.SLOT_CTX_IDX, draw).tolist()
     tgt = [int(v) for v in target_noise_idx]
     ctx = [min(int(c), t_) for c, t_ in zip(ctx_noise_idx, tgt)]                       # train_dit.py:587 torch.minimum
     start = max(0, i + 1 - dit.max_frames)
@@ -35,20 +44,26 @@ def _frame_step(dit, latents, actions, i, target_noise_idx, ctx_noise_idx, ctx_n
     a = actions[:, start: i + 1].to(dev, torch.float32).contiguous() if actions is not None else None
     n = x_curr[0, 0].numel()
     alpha = ac[t].to(dev).contiguous()                                                  # (B, W)
-    all_noise = torch.empty_like(x_curr)                                                # copies only: torch is storage here
-    all_noise[:, :-1] = ctx_noise.to(dev, torch.float32)
-    all_noise[:, -1:] = noise.to(dev, torch.float32)
     x_noisy = torch.empty_like(x_curr)
     stream = _lib.current_stream()
-    with torch.cuda.device(dev):
-        _lib.check(L.gtav_add_noise(x_curr.data_ptr(), all_noise.data_ptr(), alpha.data_ptr(), x_noisy.data_ptr(), B * W, n,
-                                    noise_abs_max, stream))
-        x_last = x_curr[:, -1].contiguous()
-        nz_last = all_noise[:, -1].contiguous()
-        a_last = alpha[:, -1].contiguous()
-        v_target = torch.empty_like(x_last)
-        _lib.check(L.gtav_vtarget(x_last.data_ptr(), nz_last.data_ptr(), a_last.data_ptr(), v_target.data_ptr(), B, n,
-                                  noise_abs_max, stream))
+    if rng is not None:
+        v_target = torch.empty((B, *x_curr.shape[2:]), device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            _lib.check(L.gtav_noise_window_rng(x_curr.data_ptr(), alpha.data_ptr(), x_noisy.data_ptr(), v_target.data_ptr(), B, W, n, rng.seed, draw,
+                                               rng.sample0 & 0xFFFFFFFF, noise_abs_max, stream))
+    else:
+        all_noise = torch.empty_like(x_curr)                                            # copies only: torch is storage here
+        all_noise[:, :-1] = ctx_noise.to(dev, torch.float32)
+        all_noise[:, -1:] = noise.to(dev, torch.float32)
+        with torch.cuda.device(dev):
+            _lib.check(L.gtav_add_noise(x_curr.data_ptr(), all_noise.data_ptr(), alpha.data_ptr(), x_noisy.data_ptr(), B * W, n,
+                                        noise_abs_max, stream))
+            x_last = x_curr[:, -1].contiguous()
+            nz_last = all_noise[:, -1].contiguous()
+            a_last = alpha[:, -1].contiguous()
+            v_target = torch.empty_like(x_last)
+            _lib.check(L.gtav_vtarget(x_last.data_ptr(), nz_last.data_ptr(), a_last.data_ptr(), v_target.data_ptr(), B, n,
+                                      noise_abs_max, stream))
     v_pred = dit.forward_train(x_noisy, t, a) if keep_activations else dit(x_noisy, t, a)
     out = torch.empty(1 + B, device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
@@ -70,27 +85,38 @@ def _per_frame(arg, n_iter, what):
 
 
 @torch.inference_mode()
-def forward_loss(dit, latents: torch.Tensor, actions: Optional[torch.Tensor], target_noise_idx, ctx_noise_idx, ctx_noise, noise,
+def forward_loss(dit, latents: torch.Tensor, actions: Optional[torch.Tensor], target_noise_idx=None, ctx_noise_idx=None, ctx_noise=None, noise=None,
                  noise_steps: int = 50, n_prompt_frames: int = 4, noise_abs_max: float = 20.0, clamp_min: float = 1e-6,
-                 keep_activations: bool = False, on_frame=None):
+                 keep_activations: bool = False, on_frame=None, rng=None, ctx_max_noise_idx: Optional[int] = None):
     """train_dit.py:590-682 `_shared_step`: for every target frame i in [n_prompt_frames, total_frames) noise the window that ends at i,
     run the DiT over it, MSE against the v-target of frame i; returns (mean loss over the target frames (1,), v_pred, v_target) of the LAST
     target frame.  The shipped dataset has ONE target frame (5-frame clips): then the draws are plain tensors — target_noise_idx /
     ctx_noise_idx (B,), ctx_noise (B, W - 1, C, h, w), noise (B, 1, C, h, w).  Longer clips pass one entry per target frame (lists, or
     (n, B) index tensors); the window of target frame i holds min(i + 1, max_frames) frames.
     keep_activations: run the DiT through forward_train so that dit.backward_(v_pred, v_target) can follow; on_frame(k, v_pred, v_target)
-    is called after target frame k's forward (the trainer differentiates each frame's loss right there, train_dit.py:679-680)."""
+    is called after target frame k's forward (the trainer differentiates each frame's loss right there, train_dit.py:679-680).
+    rng (a gtav_amd.rng.NoiseSource) in place of the four draws, which must then be None: every target frame takes one draw number of it, target index in
+    [1, noise_steps], context index in [1, ctx_max_noise_idx] (required; config.ctx_max_noise_idx of the reference) capped by the target index, the window's
+    noise from slots 0 .. W - 1 of that draw (DESIGN.md "Noise streams")."""
+    _rng.check_exclusive(rng, "forward_loss", target_noise_idx=target_noise_idx, ctx_noise_idx=ctx_noise_idx, ctx_noise=ctx_noise, noise=noise)
+    if rng is not None and ctx_max_noise_idx is None:
+        raise ValueError("forward_loss: rng= needs ctx_max_noise_idx (the upper end of the context noise index, config.ctx_max_noise_idx)")
     B, total = latents.shape[:2]
     n_iter = total - n_prompt_frames
     assert n_iter >= 1, "forward_loss: no target frame behind the prompt frames"
-    tgts, ctxs = _per_frame(target_noise_idx, n_iter, "target_noise_idx"), _per_frame(ctx_noise_idx, n_iter, "ctx_noise_idx")
-    cns, nzs = _per_frame(ctx_noise, n_iter, "ctx_noise"), _per_frame(noise, n_iter, "noise")
+    if rng is None:
+        tgts, ctxs = _per_frame(target_noise_idx, n_iter, "target_noise_idx"), _per_frame(ctx_noise_idx, n_iter, "ctx_noise_idx")
+        cns, nzs = _per_frame(ctx_noise, n_iter, "ctx_noise"), _per_frame(noise, n_iter, "noise")
     nr = torch.linspace(0, 999, noise_steps + 1).long()                                 # train_dit.py:309-315
     ac = _alphas_cumprod(clamp_min)
     total_loss = None
     for k, i in enumerate(range(n_prompt_frames, total)):
-        loss, v_pred, v_target = _frame_step(dit, latents, actions, i, tgts[k].cpu().tolist(), ctxs[k].cpu().tolist(), cns[k], nzs[k], nr, ac,
-                                             noise_abs_max, keep_activations)
+        if rng is None:
+            loss, v_pred, v_target = _frame_step(dit, latents, actions, i, tgts[k].cpu().tolist(), ctxs[k].cpu().tolist(), cns[k], nzs[k], nr, ac,
+                                                 noise_abs_max, keep_activations)
+        else:
+            loss, v_pred, v_target = _frame_step(dit, latents, actions, i, None, None, None, None, nr, ac, noise_abs_max, keep_activations, rng,
+                                                 int(noise_steps), int(ctx_max_noise_idx))
         if on_frame is not None:
             on_frame(k, v_pred, v_target)
         if total_loss is None:
@@ -123,14 +149,15 @@ def decode_frames(vae, latents: torch.Tensor) -> torch.Tensor:
 
 
 @torch.inference_mode()
-def predict(dit, vae, frames: torch.Tensor, actions: Optional[torch.Tensor], new_frame_noise: torch.Tensor, num_frames: int = 32,
+def predict(dit, vae, frames: torch.Tensor, actions: Optional[torch.Tensor], new_frame_noise: Optional[torch.Tensor] = None, num_frames: int = 32,
             n_prompt_frames: int = 4, ddim_noise_steps: int = 50, ddim_noise_steps_inference: int = 50, noise_abs_max: float = 20.0,
-            decode: bool = True):
+            decode: bool = True, rng=None):
     """train_dit.py:370-466 `predict`: first sample of the batch, prompt = its first n_prompt_frames, actions padded with "W"
     (index 3) up to num_frames, autoregressive generation with the trainer's constants.  new_frame_noise (1, num_frames -
-    n_prompt_frames, C, h, w): the standard-normal draw of every generated frame.  Returns (latents (1, num_frames, C, h, w), uint8
-    video (1, num_frames, H, W, 3) or None)."""
+    n_prompt_frames, C, h, w): the standard-normal draw of every generated frame, or rng= (a NoiseSource: one draw number, made on the device
+    as in generate_latents) in its place.  Returns (latents (1, num_frames, C, h, w), uint8 video (1, num_frames, H, W, 3) or None)."""
     from .generate import generate_latents
+    _rng.check_exclusive(rng, "predict", new_frame_noise=new_frame_noise)
     frames = frames[:1, :n_prompt_frames]
     act = None
     if actions is not None:
@@ -141,21 +168,28 @@ def predict(dit, vae, frames: torch.Tensor, actions: Optional[torch.Tensor], new
             act = torch.cat([act, pad], dim=1)
     x = encode_frames(vae, frames.to(vae.device))
     lat = generate_latents(dit, x, num_frames, ddim_noise_steps_inference, new_frame_noise, act,
-                           stabilization_level=stabilization_level(ddim_noise_steps), noise_abs_max=noise_abs_max, clamp_min=1e-6)
+                           stabilization_level=stabilization_level(ddim_noise_steps), noise_abs_max=noise_abs_max, clamp_min=1e-6, rng=rng)
     return lat, (decode_frames(vae, lat) if decode else None)
 
 
 @torch.inference_mode()
-def predict_noise(dit, vae, frames: torch.Tensor, actions: Optional[torch.Tensor], ctx_noise: torch.Tensor, new_frame_noise: torch.Tensor,
-                  ddim_noise_steps: int = 50, ddim_noise_steps_inference: int = 50, noise_abs_max: float = 20.0):
+def predict_noise(dit, vae, frames: torch.Tensor, actions: Optional[torch.Tensor], ctx_noise: Optional[torch.Tensor] = None,
+                  new_frame_noise: Optional[torch.Tensor] = None, ddim_noise_steps: int = 50, ddim_noise_steps_inference: int = 50,
+                  noise_abs_max: float = 20.0, rng=None):
     """train_dit.py:468-552 `predict_noise`: encode every frame of the first clip, noise the context frames at level
     stabilization_level - 1 (train_dit.py:498), replace the last frame by clamped noise and denoise it.
-    ctx_noise (1, n - 1, C, h, w), new_frame_noise (1, 1, C, h, w).  Returns (latents, x_noisy before denoising, x after)."""
+    ctx_noise (1, n - 1, C, h, w), new_frame_noise (1, 1, C, h, w), or rng= (a NoiseSource) in their place: one draw number for the clip, frame f is
+    slot f.  Returns (latents, x_noisy before denoising, x after)."""
     from .generate import generate_latents
+    _rng.check_exclusive(rng, "predict_noise", ctx_noise=ctx_noise, new_frame_noise=new_frame_noise)
     dev = dit.device
     L = _lib.load()
     latents = encode_frames(vae, frames[:1].to(vae.device)).to(dev)
     n = latents.shape[1]
+    if rng is not None:
+        draw = rng.next_draw()
+        ctx_noise = rng.normal(1, n - 1, latents.shape[2:], draw, 0, dev, noise_abs_max)
+        new_frame_noise = rng.normal(1, 1, latents.shape[2:], draw, n - 1, dev, noise_abs_max)
     lvl = stabilization_level(ddim_noise_steps)
     ac = _alphas_cumprod(1e-6)
     ctx = latents[:, :-1].contiguous()
@@ -270,13 +304,19 @@ def backward_overlapped(dit, v_pred, v_target, world_size: int, comm_stream=None
 
 
 @torch.inference_mode()
-def training_step(dit, latents: torch.Tensor, actions: Optional[torch.Tensor], target_noise_idx, ctx_noise_idx, ctx_noise, noise, lr: float,
-                  weight_decay: float = 0.0, max_grad_norm: float = 1.0, world_size: int = 1, noise_steps: int = 50, n_prompt_frames: int = 4,
-                  noise_abs_max: float = 20.0, clamp_min: float = 1e-6, overlap_all_reduce: bool = True, comm_stream=None, all_reduce=None,
-                  bucket_timings=None):
+def training_step(dit, latents: torch.Tensor, actions: Optional[torch.Tensor], target_noise_idx=None, ctx_noise_idx=None, ctx_noise=None, noise=None,
+                  lr: float = None, weight_decay: float = 0.0, max_grad_norm: float = 1.0, world_size: int = 1, noise_steps: int = 50,
+                  n_prompt_frames: int = 4, noise_abs_max: float = 20.0, clamp_min: float = 1e-6, overlap_all_reduce: bool = True, comm_stream=None,
+                  all_reduce=None, bucket_timings=None, rng=None, ctx_max_noise_idx: Optional[int] = None):
     """One optimisation step on a batch of latent clips: for every target frame forward + loss and its backward (train_dit.py:590-680: each
     frame's loss is differentiated inside the frame loop, the gradients add up), gradient all-reduce (bucketed and overlapped with the LAST
-    frame's backward pass when world_size > 1), clip, AdamW.  Returns the mean loss over the target frames, a (1,) tensor."""
+    frame's backward pass when world_size > 1), clip, AdamW.  Returns the mean loss over the target frames, a (1,) tensor.
+    rng / ctx_max_noise_idx: as forward_loss — the step draws its own noise indices and noise, the four draw arguments stay None."""
+    _rng.check_exclusive(rng, "training_step", target_noise_idx=target_noise_idx, ctx_noise_idx=ctx_noise_idx, ctx_noise=ctx_noise, noise=noise)
+    if rng is not None and ctx_max_noise_idx is None:
+        raise ValueError("training_step: rng= needs ctx_max_noise_idx (the upper end of the context noise index, config.ctx_max_noise_idx)")
+    if lr is None:
+        raise TypeError("training_step: lr is required")
     dit.zero_grad()
     n_iter = latents.shape[1] - n_prompt_frames
     overlap = world_size > 1 and overlap_all_reduce
@@ -288,7 +328,7 @@ def training_step(dit, latents: torch.Tensor, actions: Optional[torch.Tensor], t
             dit.backward_(v_pred, v_target)
 
     loss, _, _ = forward_loss(dit, latents, actions, target_noise_idx, ctx_noise_idx, ctx_noise, noise, noise_steps, n_prompt_frames,
-                              noise_abs_max, clamp_min, keep_activations=True, on_frame=on_frame)
+                              noise_abs_max, clamp_min, keep_activations=True, on_frame=on_frame, rng=rng, ctx_max_noise_idx=ctx_max_noise_idx)
     if not overlap:
         all_reduce_gradients(dit, world_size)
     dit.adamw_step(lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
@@ -354,9 +394,10 @@ def _operand_dtype_name(dit) -> str:
     return "bf16" if getattr(dit, "train_dtype", torch.float16) == torch.bfloat16 else "fp16"
 
 
-def save_state(dit, ckpt_dir: str, global_step: int, epoch: int, extra: Optional[dict] = None):
+def save_state(dit, ckpt_dir: str, global_step: int, epoch: int, extra: Optional[dict] = None, rng=None):
     """train_dit.py:765-800 `save_checkpoint`: <dir>/model.safetensors (fp32 masters), <dir>/optimizer.safetensors (AdamW moments + step
-    counters), <dir>/step.json {"step", "epoch", "loss_scale", "operand_dtype", ...}.  Rank 0 writes; the caller barriers around it like the reference."""
+    counters), <dir>/step.json {"step", "epoch", "loss_scale", "operand_dtype", ...}.  Rank 0 writes; the caller barriers around it like the reference.
+    rng (a NoiseSource): its {"seed", "draw"} goes into step.json as "rng" — the whole noise stream of the resumed run."""
     import json
     import os
     from safetensors.torch import save_file
@@ -365,14 +406,17 @@ def save_state(dit, ckpt_dir: str, global_step: int, epoch: int, extra: Optional
     save_file({k: v.contiguous() for k, v in dit.opt_state_dict().items()}, os.path.join(ckpt_dir, "optimizer.safetensors"))
     state = {"step": int(global_step), "epoch": int(epoch), "loss_scale": float(dit.loss_scale), "operand_dtype": _operand_dtype_name(dit)}
     state.update(extra or {})
+    if rng is not None:
+        state["rng"] = rng.state_dict()
     with open(os.path.join(ckpt_dir, "step.json"), "w") as f:
         json.dump(state, f)
 
 
-def load_state(dit, ckpt_dir: str, steps_per_epoch: Optional[int] = None, gradient_accumulation_steps: int = 1) -> dict:
+def load_state(dit, ckpt_dir: str, steps_per_epoch: Optional[int] = None, gradient_accumulation_steps: int = 1, rng=None) -> dict:
     """train_dit.py:802-849 `load_checkpoint`: restores weights, AdamW state and the loss scale into `dit` (trainable=True) and returns
     step.json's dict plus "skip_iter" = (step % steps_per_epoch) * gradient_accumulation_steps, the number of batches of the current
-    epoch the resumed loop has to skip (train_dit.py:841-843), when steps_per_epoch is given."""
+    epoch the resumed loop has to skip (train_dit.py:841-843), when steps_per_epoch is given.  rng (a NoiseSource) is set to the checkpoint's
+    "rng" entry; a checkpoint without one leaves it untouched."""
     import json
     import os
     from safetensors.torch import load_file
@@ -385,6 +429,8 @@ def load_state(dit, ckpt_dir: str, steps_per_epoch: Optional[int] = None, gradie
     # only into a handle of the same type (a checkpoint without "operand_dtype" is fp16).  The masters and moments are fp32 and load either way.
     if "loss_scale" in state and state.get("operand_dtype", "fp16") == _operand_dtype_name(dit):
         dit.loss_scale = float(state["loss_scale"])
+    if rng is not None and "rng" in state:
+        rng.load_state_dict(state["rng"])
     if steps_per_epoch:
         state["skip_iter"] = (state["step"] % int(steps_per_epoch)) * int(gradient_accumulation_steps)
     return state

@@ -327,6 +327,24 @@ int gtav_add_noise(const float* x_dev, const float* noise_dev, const float* alph
 /* train_dit.py:643-645: v_target = sqrt(a)*clamp(noise) - sqrt(1-a)*x. */
 int gtav_vtarget(const float* x_dev, const float* noise_dev, const float* alpha_dev, float* vt_dev, int32_t rows,
                  int32_t n, float clamp_abs, void* stream);
+/* Counter-based noise (DESIGN.md "Noise streams"): Philox4x32-10 keyed by (seed & 0xffffffff, seed >> 32); element e of a row of n floats (n % 4 == 0) is
+ * component e & 3 of the generator's output at counter (e >> 2, slot, sample, draw) after the Box-Muller transform, so a draw depends on no launch geometry,
+ * batch split or call history.  Row r of a call: sample = sample0 + r / slots_per_sample, slot = slot0 + r % slots_per_sample.  |N| <= 5.768 by construction.
+ * All pointers 16-byte aligned.
+ *
+ * train_dit.py:625-628,637-638 / generate.py:201-202 `torch.randn_like` + `clamp_`: out <- clamp(N(0,1), +-clamp_abs) (INFINITY: no clamp) for `rows` rows of n
+ * floats; the rows of one sample are contiguous and samples are sample_stride floats apart (the sampler fills x[:, n_prompt:] of (B, total, n) in place with
+ * sample_stride = total * n, slot0 = n_prompt, slots_per_sample = total - n_prompt). */
+int gtav_rng_normal(float* out_dev, int64_t sample_stride, int32_t rows, int32_t n, uint64_t seed, uint32_t draw, uint32_t sample0,
+                    uint32_t slot0, uint32_t slots_per_sample, float clamp_abs, void* stream);
+/* train_dit.py:625-645 in one launch, the noise drawn inside it and never stored: x (B, W, n), alpha (B, W) -> x_noisy (B, W, n) = gtav_add_noise and
+ * v_target (B, n) = gtav_vtarget of the last slot, bit for bit what those two give on gtav_rng_normal's noise of (sample0 + b, slot w). */
+int gtav_noise_window_rng(const float* x_dev, const float* alpha_dev, float* x_noisy_dev, float* v_target_dev, int32_t B, int32_t W, int32_t n,
+                          uint64_t seed, uint32_t draw, uint32_t sample0, float clamp_abs, void* stream);
+/* model/vae.py:36-39 `DiagonalGaussianDistribution.sample`: moments (frames, tokens, 2 * latent_dim) -> z (frames, tokens, latent_dim) =
+ * mean + exp(0.5 * clamp(logvar, -30, 20)) * N(0,1); a row of the stream is one frame's tokens * latent_dim block (latent_dim % 4 == 0). */
+int gtav_vae_posterior_sample(const float* moments_dev, float* z_dev, int32_t frames, int32_t tokens, int32_t latent_dim, uint64_t seed,
+                              uint32_t draw, uint32_t sample0, uint32_t slot0, uint32_t slots_per_sample, void* stream);
 /* y[i] += alpha * x[i] (x may alias y): the trainer's `total_loss += loss` / `total_loss / n` on device scalars (train_dit.py:676,682). */
 int gtav_axpy_f32(float* y_dev, const float* x_dev, float alpha, int64_t n, void* stream);
 /* train_dit.py:650 mse_loss: out[0] = mean((a-b)^2) over rows x n; a,b rows are a_stride / b_stride floats apart.
@@ -366,6 +384,9 @@ int gtav_op_gemm_qkv(const void* x_f16_dev, int32_t ldx, const void* w_f16_dev, 
                      int32_t D, int32_t mode, void* q_dev, void* k_dev, void* v_dev, int32_t S, int32_t Tq, int32_t t0,
                      int32_t Tmax, const float* rope_cs_dev, void* stream);
 int gtav_op_rope_interleave(const float* cos_dev, const float* sin_dev, float* cs_dev, int32_t npos, void* stream);
+/* the raw generator words of the noise stream above (before the normal transform): out (rows, n) uint32, rows contiguous */
+int gtav_op_rng_bits(uint32_t* out_dev, int32_t rows, int32_t n, uint64_t seed, uint32_t draw, uint32_t sample0, uint32_t slot0,
+                     uint32_t slots_per_sample, void* stream);
 int gtav_op_skinny_f32(const float* x_dev, int32_t ldx, const float* w_dev, const float* bias_dev, float* y_dev,
                        int32_t ldy, int32_t M, int32_t N, int32_t K, int32_t act_silu, void* stream);
 int gtav_op_ln_modulate(const float* x_dev, void* out_f16_dev, int32_t M, int32_t D, const float* shift_dev,
