@@ -143,7 +143,11 @@ struct DitPrefetch {
         const int pf_max_m = 1536;   // (above: measured slower, the persistent large-M kernels lose more than their successors gain)
         static const int pf_min_m = GTAV_ENV_INT("GTAV_PF_MIN_M", 256);   // 320 tokens (window step of the 256 x 256-frame preset): -2.1 %; 144 (cached step): +1.5 %; experiments build: A/B
         on = h->w_prefetch && M >= pf_min_m && M <= pf_max_m;
+        fill_on = M <= pf_max_m;     // the token range of the loader-wave kernels: nobody else reads GemmParams::wfill
     }
+    bool fill_on;
+    // GemmParams::wfill of the launch of class `cls` (gtav_dit::w_fill_cls: 0 out-proj, 1 fc1, 2 fc2, 3 to_qkv)
+    int fill(int cls) const { return fill_on ? h->w_fill_cls[cls] : 0; }
     // what the GEMM launch at position `pos` of half-block `hb` (launch order: 0 to_qkv, 1 out-proj, 2 fc1, 3 fc2) prefetches: the weight of the next GEMM launch of
     // the step, nothing past the last half-block.  (One more launch of lead — the weight of the GEMM after the next — was measured in round 5 and gained nothing on
     // either kind of GPU: profiles/round5/prefetch_box_survey.txt.)
@@ -206,7 +210,7 @@ static int dit_forward_core(gtav_dit* h, const float* x_src, const int* frame_in
         if (fused_t) rd.permute_rows(Tq, P);
         if (!folded_in) RET_IF(ln(ops, mb, mb + D, ef));
         GemmParams g = gemm_params(h->xn, D, fused_t || fused_s ? w.w_qkv_hm : w.w_qkv, M, 3 * D, D);
-        g.D = D; g.S = P; g.err_flag = ef; g.pf = pf.after(hb, 0);
+        g.D = D; g.S = P; g.err_flag = ef; g.pf = pf.after(hb, 0); g.wfill = pf.fill(3);
         if (folded_in) fold_consumer(h, g, 2 * hb, 3 * D, mod_rows, ctab);
         if (hf == 0) { g.qkv_mode = QKV_SPATIAL; g.rope_cs = h->rope_s.cs_dev; }
         else { g.qkv_mode = QKV_TEMPORAL; g.k = h->kvcache[l]; g.v = h->kvcache[l]; g.Tq = Tq; g.t0 = t0; g.Tmax = h->maxT; g.rope_cs = h->rope_t.cs_dev; }
@@ -224,14 +228,14 @@ static int dit_forward_core(gtav_dit* h, const float* x_src, const int* frame_in
         }
         folded_in = false;
         GemmParams fc1 = gemm_params(h->xn, D, w.w_fc1, M, h->Hm, D);
-        fc1.bias = w.b_fc1; fc1.out = h->hbuf; fc1.ldo = h->Hm_pad; fc1.err_flag = ef; fc1.pf = pf.after(hb, 2);
+        fc1.bias = w.b_fc1; fc1.out = h->hbuf; fc1.ldo = h->Hm_pad; fc1.err_flag = ef; fc1.pf = pf.after(hb, 2); fc1.wfill = pf.fill(1);
         if (fold_a) {
             // seam A: out-proj updates the residual in place and emits fc1's operand + row statistics; fc1 normalises in its epilogue
             RET_IF(fold_producer(h, PC_OUT, h->ao, w.w_out, M, D, w.b_out, gate(mb + 2 * D), mb + 4 * D, s));
             fold_consumer(h, fc1, 2 * hb + 1, h->Hm, mod_rows, ctab);
             PROF(h, PC_FC1, s, launch_gemm(fc1, EPI_GELU_TANH_FOLD, s));
         } else {
-            RET_IF(rd.gemm(ops, PC_OUT, h->ao, D, w.w_out, D, w.b_out, gate(mb + 2 * D), dit_resid_inplace(h, M, D), pf.after(hb, 1)));
+            RET_IF(rd.gemm(ops, PC_OUT, h->ao, D, w.w_out, D, w.b_out, gate(mb + 2 * D), dit_resid_inplace(h, M, D), pf.after(hb, 1), nullptr, nullptr, pf.fill(0)));
             RET_IF(ln(ops, mb + 3 * D, mb + 4 * D, ef));
             PROF(h, PC_FC1, s, ops.gemm(fc1, EPI_GELU_TANH, s));
         }
@@ -241,7 +245,7 @@ static int dit_forward_core(gtav_dit* h, const float* x_src, const int* frame_in
             RET_IF(fold_producer(h, PC_FC2, h->hbuf, w.w_fc2, M, h->Hm_pad, w.b_fc2, gate(mb + 5 * D), next_scale, s));
             folded_in = true;
         } else {
-            RET_IF(rd.gemm(ops, PC_FC2, h->hbuf, h->Hm_pad, w.w_fc2, h->Hm_pad, w.b_fc2, gate(mb + 5 * D), dit_resid_inplace(h, M, h->Hm_pad), pf.after(hb, 3)));
+            RET_IF(rd.gemm(ops, PC_FC2, h->hbuf, h->Hm_pad, w.w_fc2, h->Hm_pad, w.b_fc2, gate(mb + 5 * D), dit_resid_inplace(h, M, h->Hm_pad), pf.after(hb, 3), nullptr, nullptr, pf.fill(2)));
         }
     }
     const float* mf = mod + (size_t)h->L * 12 * D;
@@ -598,6 +602,18 @@ int gtav_dit_set_weight_prefetch(gtav_dit* h, int32_t enable) {
     if (h->w_prefetch != on || memcmp(cls, h->w_prefetch_cls, sizeof(cls))) h->drop_graphs();   // captured sampler steps carry the other kernel parameters
     h->w_prefetch = on;
     memcpy(h->w_prefetch_cls, cls, sizeof(cls));
+    return 0;
+}
+
+int gtav_dit_set_weight_fill_policy(gtav_dit* h, int32_t mode) {
+    GTAV_REQUIRE(h, "dit_set_weight_fill_policy: null handle");
+    GTAV_REQUIRE((mode & ~0x1111) == 0,
+                 "dit_set_weight_fill_policy: mode %d (one nibble per class: bits 0-3 out-proj's weight, 4-7 fc1's, 8-11 fc2's, 12-15 to_qkv's; "
+                 "nibble 0 = default cache policy, 1 = non-temporal fills)", mode);
+    int cls[4];
+    for (int c = 0; c < 4; ++c) cls[c] = (mode >> (4 * c)) & 15;
+    if (memcmp(cls, h->w_fill_cls, sizeof(cls))) h->drop_graphs();   // captured sampler steps carry the other kernel parameters
+    memcpy(h->w_fill_cls, cls, sizeof(cls));
     return 0;
 }
 

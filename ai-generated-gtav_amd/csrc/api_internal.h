@@ -284,11 +284,11 @@ struct DeferredResid {
     LnPending pend;
     bool pending = false;
     // x += gate * (X W^T + bias): `inplace` = in the GEMM's EPI_RESID epilogue (the caller's large-M predicate), else as slabs left to the next LayerNorm.  pf: L2
-    // prefetch of the next weight (DiT); x_out / y_save: LnPending's, the training forward's.
+    // prefetch of the next weight (DiT); x_out / y_save: LnPending's, the training forward's; wfill: GemmParams::wfill (DiT).
     int gemm(const OperandOps& ops, int cls, const f16* X, int ldx, const f16* W, int K, const float* bias, const ResidGate& gt, bool inplace,
-             const PrefetchDesc& pf = kNoPrefetch, float* x_out = nullptr, f16* y_save = nullptr) {
+             const PrefetchDesc& pf = kNoPrefetch, float* x_out = nullptr, f16* y_save = nullptr, int wfill = 0) {
         GemmParams q = gemm_params(X, ldx, W, M, N, K);
-        q.out = parts; q.ldo = N; q.pf = pf;
+        q.out = parts; q.ldo = N; q.pf = pf; q.wfill = wfill;
         if (inplace) {
             q.out = resid; q.bias = bias; q.gate = gt.gate; q.gate_stride = gt.stride; q.gate_rows = gt.rows; q.rows_per_gate = gt.rows_per_gate;
         } else {
@@ -407,6 +407,9 @@ struct gtav_dit {
     // setting that was never slower than no prefetch on any GPU of the round-5 survey (-2 ... -5 % per batch-1 step on every one of them); prefetching every
     // weight whole is 7-12 % faster on some GPUs and 2-16 % slower on others: generate.tune_weight_prefetch finds it where it pays.
     int w_prefetch_cls[4] = {1, 4, 4, 1};
+    // cache policy of the loader-wave kernels' W fills per class (same order): 0 default, 1 non-temporal (GemmParams::wfill; gtav_dit_set_weight_fill_policy;
+    // docs/LABNOTES.md 13.2).  All default: whether nt pays is a property of the GPU and of the prefetch setting, so generate.tune_weight_prefetch measures it.
+    int w_fill_cls[4] = {0, 0, 0, 0};
     int resid_inplace_min_m = GTAV_ENV_INT("GTAV_RESID_INPLACE_MIN_M", 1 << 30);   // experiments build only
     // ---- LayerNorm fold (docs/LABNOTES.md 4.7; gemm.h EPI_*_FOLD): the LayerNorm + modulate between a residual GEMM and its consumer runs inside the
     // two GEMM epilogues.  Seam A = out-proj -> fc1, seam B = fc2 -> next to_qkv / final projection.  Per-frame c1 / c2 tables for every

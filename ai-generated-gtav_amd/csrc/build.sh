@@ -13,6 +13,7 @@ if [ "$1" = "exp" ]; then
   OUT=../libgtav_amd_exp.so
   DEFS="-DGTAV_EXPERIMENTS"
 fi
+PRELOAD="-mllvm -amdgpu-kernarg-preload-count=16"
 BUILD=$(mktemp -d "${TMPDIR:-/tmp}/gtav_build.XXXXXX")
 trap 'rm -rf "$BUILD"' EXIT
 pids=()
@@ -21,6 +22,9 @@ for f in gemm skinny elementwise attention train comm api api_dit api_train api_
   # attention: keep MFMA accumulators in VGPRs — the softmax works on them every key block, and the AGPR form costs 56
   # v_accvgpr moves per 16 MFMAs there (the GEMMs touch their accumulators only in the epilogue and keep the default)
   [ $f = attention ] && extra="-mllvm -amdgpu-mfma-vgpr-form"
+  # the kernels of a batch-1 step: leading scalar / pointer kernel arguments arrive in SGPRs with the wave instead of by scalar loads from a cold cache
+  # (gemm.hip "launch head"; tools/kernel_resources.py prints what each kernel got; firmware without the feature runs the compiler's fallback prologue)
+  case $f in gemm|elementwise|attention) extra="$extra $PRELOAD";; esac
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -Wno-pass-failed $DEFS $extra "$@" -c $f.hip -o "$BUILD/$f.o" &
   pids+=($!)
 done
@@ -29,6 +33,7 @@ done
 for f in gemm elementwise attention train; do
   extra=""
   [ $f = attention ] && extra="-mllvm -amdgpu-mfma-vgpr-form"
+  case $f in gemm|elementwise|attention) extra="$extra $PRELOAD";; esac
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -Wno-pass-failed -DGTAV_BF16_OPERANDS -Dgtav=gtav_bf16 $extra "$@" -c $f.hip -o "$BUILD/${f}_bf16.o" &
   pids+=($!)
 done

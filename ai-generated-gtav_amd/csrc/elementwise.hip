@@ -99,11 +99,17 @@ __global__ __launch_bounds__(256) void ln_wave_row_kernel(const float* __restric
 // KS: where the shift K of the statistics comes from (LnPending::k_save / k_load): 0 = the row's first element, 1 = the same and kept in pd.k_save[m],
 // 2 = pd.k_load[m] (the re-run of a launch that applied a pending update, from the updated row: same K, same sums, same bits)
 template <int MODE, bool PEND, int KS = 0>
-__global__ __launch_bounds__(512) void ln_row_block_kernel(float* __restrict__ x, int ldx, f16* __restrict__ out, int M, int D,
+__global__ __launch_bounds__(512) void ln_row_block_kernel(float* __restrict__ x, int ldx, int D, const float* __restrict__ h_parts, size_t h_slab_stride, int h_ld,
+                                                           int h_nsplit, int h_flags, int rows_per_mod, f16* __restrict__ out, int M,
                                                            const float* __restrict__ p0, const float* __restrict__ p1,
-                                                           int mod_stride, const int* __restrict__ rows, int rows_per_mod,
+                                                           int mod_stride, const int* __restrict__ rows,
                                                            LnPending pd) {
     __shared__ float red[16];
+    // Argument order = order of first use: the first 14 dwords (x .. out) arrive in SGPRs with the wave (kernel-argument preload, build.sh), and they are what the
+    // first loads need — the residual row and the split-K slabs.  The slab descriptor lives in LnPending, whose fields cannot be preloaded (a by-value struct), so
+    // the launcher passes those five a second time, flat (h_*), and they replace the struct's copies here: no scalar load is left in front of the first request
+    // (docs/LABNOTES.md 13.2).  The per-frame table arguments, needed later, follow.
+    pd.parts = h_parts; pd.slab_stride = h_slab_stride; pd.ld = h_ld; pd.nsplit = h_nsplit; pd.flags = h_flags;
     // A block lives ~3 us and most of it is latency, so the head is laid out by hand (round 3): the loads that come from memory / the Infinity Cache —
     // the residual row and the split-K slabs — are requested FIRST (they need five kernel arguments); the block-uniform table indices and the statistics'
     // shift follow as SCALAR loads (their own counter: in flight beside the vector loads); the per-frame vectors (L2 hits) are requested last, as soon as
@@ -801,6 +807,8 @@ static int g_ln_wave_row_min = GTAV_ENV_INT("GTAV_LN_WAVE_ROW_MIN", 0);
 
 #define LN_WAVE_ROW_(MODE, NV, P0, P1, STRIDE, ROWS, RPM) \
     GTAV_LAUNCH((ln_wave_row_kernel<MODE, NV>), dim3(cdiv(M, 4)), dim3(256), 0, stream, x, ldx, out, M, D, P0, P1, STRIDE, ROWS, RPM, pd_.flags, err_flag)   /* (GTAV_LAUNCH: the profiler's events ride on the dispatch) */
+// ln_row_block_kernel: the slab descriptor of the pending update flat in front (its argument list says why)
+#define LN_ROW_BLOCK_ARGS_(P0, P1, STRIDE, ROWS, RPM) x, ldx, D, pd_.parts, pd_.slab_stride, pd_.ld, pd_.nsplit, pd_.flags, RPM, out, M, P0, P1, STRIDE, ROWS, pd_
 #define LN_DISPATCH(MODE, P0, P1, STRIDE, ROWS, RPM)                                                     \
     do {                                                                                                  \
         LnPending pd_;                                                                                    \
@@ -814,8 +822,8 @@ static int g_ln_wave_row_min = GTAV_ENV_INT("GTAV_LN_WAVE_ROW_MIN", 0);
         GTAV_REQUIRE(!pd_.k_load || !upd_, "ln: k_load excludes a pending update");                                                            \
         if (pd_.k_save || pd_.k_load) { /* the statistics' shift kept / given: always one block per row (LnPending::k_save) */                 \
             const dim3 g_(M), b_(round_up(D / 4, 64));                                                    \
-            if (pd_.k_save) GTAV_LAUNCH((ln_row_block_kernel<MODE, true, 1>), g_, b_, 0, stream, x, ldx, out, M, D, P0, P1, STRIDE, ROWS, RPM, pd_); \
-            else GTAV_LAUNCH((ln_row_block_kernel<MODE, false, 2>), g_, b_, 0, stream, x, ldx, out, M, D, P0, P1, STRIDE, ROWS, RPM, pd_);      \
+            if (pd_.k_save) GTAV_LAUNCH((ln_row_block_kernel<MODE, true, 1>), g_, b_, 0, stream, LN_ROW_BLOCK_ARGS_(P0, P1, STRIDE, ROWS, RPM)); \
+            else GTAV_LAUNCH((ln_row_block_kernel<MODE, false, 2>), g_, b_, 0, stream, LN_ROW_BLOCK_ARGS_(P0, P1, STRIDE, ROWS, RPM));      \
         } else if (!upd_ && pd_.tperm_T == 0 && M >= g_ln_wave_row_min && (D == 256 || D == 512 || D == 1024 || D == 2048)) { \
             if (D == 256) LN_WAVE_ROW_(MODE, 1, P0, P1, STRIDE, ROWS, RPM);                               \
             else if (D == 512) LN_WAVE_ROW_(MODE, 2, P0, P1, STRIDE, ROWS, RPM);                          \
@@ -823,8 +831,8 @@ static int g_ln_wave_row_min = GTAV_ENV_INT("GTAV_LN_WAVE_ROW_MIN", 0);
             else LN_WAVE_ROW_(MODE, 8, P0, P1, STRIDE, ROWS, RPM);                                        \
         } else { /* one block per row */                                                                  \
             const dim3 g_(M), b_(round_up(D / 4, 64));                                                    \
-            if (upd_) GTAV_LAUNCH((ln_row_block_kernel<MODE, true>), g_, b_, 0, stream, x, ldx, out, M, D, P0, P1, STRIDE, ROWS, RPM, pd_); \
-            else GTAV_LAUNCH((ln_row_block_kernel<MODE, false>), g_, b_, 0, stream, x, ldx, out, M, D, P0, P1, STRIDE, ROWS, RPM, pd_);     \
+            if (upd_) GTAV_LAUNCH((ln_row_block_kernel<MODE, true>), g_, b_, 0, stream, LN_ROW_BLOCK_ARGS_(P0, P1, STRIDE, ROWS, RPM)); \
+            else GTAV_LAUNCH((ln_row_block_kernel<MODE, false>), g_, b_, 0, stream, LN_ROW_BLOCK_ARGS_(P0, P1, STRIDE, ROWS, RPM));     \
         }                                                                                                 \
     } while (0)
 

@@ -50,6 +50,13 @@ __device__ __forceinline__ void glds16_s(const void* sbase, unsigned voff, unsig
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_addr) : "memory");
 }
+// The same load with the non-temporal cache policy (aux = 2): for weight bytes that the step reads once and that arrive from HBM anyway
+// (GemmParams::wfill; docs/LABNOTES.md 13.2).  Weight fills only: never on the X operand or on anything another launch reads back from L2.
+__device__ __forceinline__ void glds16_s_nt(const void* sbase, unsigned voff, unsigned lds_addr) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 nt\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_addr) : "memory");
+}
 // 16-byte store at a wave-uniform base + a 32-bit per-lane offset (no 64-bit per-lane address in VGPRs)
 __device__ __forceinline__ void store16_soff(const void* sbase, unsigned voff, u32x4 v) {
     asm volatile("global_store_dwordx4 %0, %1, %2" : : "v"(voff), "v"(v), "s"(sbase) : "memory");
@@ -672,10 +679,11 @@ __device__ __forceinline__ void tile_map(const GemmParams& p, int& n0, int& m0, 
 
 // The same map from host-precomputed constants (GemmParams::tm, filled by launch_l): no run-time integer division.
 __device__ __forceinline__ int div_rcp(int a, unsigned rcp) { return rcp ? (int)__umulhi((unsigned)a, rcp) : a; }   // rcp == 0 encodes a divisor of 1
+// nwg: the grid size where the caller has it in a register already (the launch-head arguments below); gridDim.x is one more scalar load, from the hidden arguments
 template <bool SPLITK, int TNB, int TMB>
-__device__ __forceinline__ void tile_map_fast(const GemmParams& p, int& n0, int& m0, int& ks, int& kt0, int& nkt) {
+__device__ __forceinline__ void tile_map_fast(const GemmParams& p, int& n0, int& m0, int& ks, int& kt0, int& nkt, int nwg = (int)gridDim.x) {
     const GemmParams::TileMap& tm = p.tm;
-    const int nwg = gridDim.x, bid = blockIdx.x;
+    const int bid = blockIdx.x;
     const int xcd = bid & 7, qq = nwg >> 3, rr = nwg & 7;
     const int swz = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
     int tile_id = swz;
@@ -694,6 +702,27 @@ __device__ __forceinline__ void tile_map_fast(const GemmParams& p, int& n0, int&
     n0 = tile_n * TNB;
     m0 = tile_m * TMB;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Launch head of the loader-wave kernels (gemm_l_kernel and the two fused to_qkv + attention kernels; docs/LABNOTES.md 13.2).  Nothing can be filled before the block
+// knows its tile and its operands, and every one of those values used to come from GemmParams: a batch of scalar loads from a cold scalar cache and their wait in
+// front of the first fill of every block of every launch.  gfx950 preloads the first kernel-argument dwords into SGPRs while the wave is launched (build.sh:
+// -amdgpu-kernarg-preload-count), but only leading arguments that are scalars or pointers, never the fields of a by-value struct.  So exactly what the loaders need
+// for their first fill is passed a second time, flat, in front of GemmParams, in the order of first use and packed into 14 dwords (16 user SGPRs less the
+// kernel-argument pointer); the kernel writes them over the struct's fields first thing, so that every later read of those fields is a register and not a load.
+//   h_gn_tn = tm.gn | tm.tiles_n << 16,  h_tiles_sk = tm.tiles | splitk << 16 | wfill << 24   (tiles * splitk < 65536: fill_tile_map; splitk < 256: launch_l)
+// ---------------------------------------------------------------------------------------------------------------------
+#define GTAV_HEAD_PARAMS unsigned h_rcp_group, int h_group, unsigned h_gn_tn, unsigned h_rcp_gn, unsigned h_rcp_gnlast, unsigned h_rcp_tiles, \
+                         const f16* h_W, const f16* h_X, int h_K, int h_N, int h_M, unsigned h_tiles_sk
+#define GTAV_HEAD_VALUES(q) (q).tm.rcp_group, (q).tm.group, (unsigned)(q).tm.gn | (unsigned)(q).tm.tiles_n << 16, (q).tm.rcp_gn, (q).tm.rcp_gnlast, (q).tm.rcp_tiles, \
+                            (q).W, (q).X, (q).K, (q).N, (q).M, (unsigned)(q).tm.tiles | (unsigned)(q).splitk << 16 | (unsigned)((q).wfill != 0) << 24
+#define GTAV_HEAD_APPLY(p)                                                                                                            \
+    do {                                                                                                                              \
+        (p).tm.rcp_group = h_rcp_group; (p).tm.group = h_group; (p).tm.gn = (int)(h_gn_tn & 0xFFFFu); (p).tm.tiles_n = (int)(h_gn_tn >> 16); \
+        (p).tm.rcp_gn = h_rcp_gn; (p).tm.rcp_gnlast = h_rcp_gnlast; (p).tm.rcp_tiles = h_rcp_tiles;                                   \
+        (p).W = h_W; (p).X = h_X; (p).K = h_K; (p).N = h_N; (p).M = h_M;                                                              \
+        (p).tm.tiles = (int)(h_tiles_sk & 0xFFFFu); (p).splitk = (int)(h_tiles_sk >> 16 & 0xFFu); (p).wfill = (int)(h_tiles_sk >> 24 & 1u); \
+    } while (0)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // LayerNorm fold, consumer side (EPI_*_FOLD; docs/LABNOTES.md 4.7).  The X operand is A[m][k] = x[m][k] (1 + scale[f][k]) of the residual row x
@@ -1888,11 +1917,13 @@ __device__ __forceinline__ void mainloop_l(const GemmParams& p, char* smem, int 
         const unsigned smem0 = lds_offset(smem);
         const char* sb[G];
         unsigned ldso[G];
+        unsigned wmask = 0;                                  // bit i: piece i of this wave is a W piece (the nt loop's policy choice)
 #pragma unroll
         for (int i = 0; i < G; ++i) {
             int q = lw * G + i;
             q = q < NP ? q : NP - 1;                         // the last wave repeats the final piece (same bytes, same place)
             const bool isw = q < WPC;
+            wmask |= (unsigned)isw << i;
             const int row = isw ? n0 + 8 * q : m0 + 8 * (q - WPC);
             int rt = row >> 7;
             const int lim = isw ? last_wt : last_rt;
@@ -1908,6 +1939,28 @@ __device__ __forceinline__ void mainloop_l(const GemmParams& p, char* smem, int 
         };
         const int npro = nkt < NS - 1 ? nkt : NS - 1;
         GTAV_STAMP_SLOT(lw == 0 && lane == 0, 7);   // first loader: first fill issued now
+        if (p.wfill) {
+            // Non-temporal W fills (GemmParams::wfill): the same fills in the same order behind the same counted waits, a loop of its own so that the default
+            // loop below stays instruction for instruction what it was.  The policy is chosen per piece (wave-uniform: a loader wave may carry both operands).
+            auto stage_nt = [&](int t) {
+                const unsigned so = (unsigned)(t % NS) * STAGE_BYTES;
+                const size_t go = (size_t)t * TILE_BYTES;
+#pragma unroll
+                for (int i = 0; i < G; ++i) {
+                    if (wmask >> i & 1) glds16_s_nt(sb[i] + go, voff, ldso[i] + so);
+                    else glds16_s(sb[i] + go, voff, ldso[i] + so);
+                }
+            };
+            for (int t = 0; t < npro; ++t) stage_nt(t);
+            for (int t = 0; t < nkt; ++t) {
+                wait_vm_ring<NS, G>(nkt - 1 - t);
+                GTAV_STAMP_SLOT_HI(t == 0 && lw == 0 && lane == 0, 6);
+                wg_barrier();
+                if (t == 0) GTAV_STAMP(bs.t[1]);
+                if (t + NS - 1 < nkt) stage_nt(t + NS - 1);
+            }
+            return;
+        }
         for (int t = 0; t < npro; ++t) stage(t);
         for (int t = 0; t < nkt; ++t) {
             wait_vm_ring<NS, G>(nkt - 1 - t);                // this wave's share of tile t has landed
@@ -2030,7 +2083,7 @@ __device__ __forceinline__ void mainloop_l(const GemmParams& p, char* smem, int 
 }
 
 template <int EPIX, int NS, int FI, int FJ, int WN, int WM, int NL>
-__global__ __launch_bounds__(64 * (WN * WM + NL), 1) void gemm_l_kernel(GemmParams p) {
+__global__ __launch_bounds__(64 * (WN * WM + NL), 1) void gemm_l_kernel(GTAV_HEAD_PARAMS, GemmParams p) {
     constexpr int EPI = epi_base(EPIX);
     constexpr int TNB = 16 * FI * WN, TM = 16 * FJ * WM;
     constexpr int STAGE = (2 * FI * WN + 2 * FJ * WM) * 1024;
@@ -2040,20 +2093,17 @@ __global__ __launch_bounds__(64 * (WN * WM + NL), 1) void gemm_l_kernel(GemmPara
     extern __shared__ __attribute__((aligned(16))) char smem_l[];
     static_assert(NS * STAGE >= EPIB, "the ring must cover the epilogue's LDS image");
     char* smem = smem_l;
-    // Every kernel argument the prologue needs is fetched HERE, in one batch of scalar loads behind one wait.  Left to itself hipcc
-    // loads GemmParams field by field in the basic blocks that use them: five to six dependent s_load / s_waitcnt lgkmcnt(0) round
-    // trips (100-200 ns each from a cold scalar cache) in front of the loaders' first fill (first fill 0.5-0.6 us after block entry,
-    // profiles/round2 stamps).  The empty asm statements are uses that pin the loads to this point.
-#define GTAV_PIN_S(x) asm volatile("" ::"s"(x))
-    GTAV_PIN_S(p.X); GTAV_PIN_S(p.W); GTAV_PIN_S(p.M); GTAV_PIN_S(p.N); GTAV_PIN_S(p.K); GTAV_PIN_S(p.splitk);
-    GTAV_PIN_S(p.tm.tiles_m); GTAV_PIN_S(p.tm.tiles_n); GTAV_PIN_S(p.tm.gn); GTAV_PIN_S(p.tm.group); GTAV_PIN_S(p.tm.tiles);
-    GTAV_PIN_S(p.tm.rcp_tiles); GTAV_PIN_S(p.tm.rcp_group); GTAV_PIN_S(p.tm.rcp_gn); GTAV_PIN_S(p.tm.rcp_gnlast);
-    GTAV_PIN_S(p.bias); GTAV_PIN_S(p.out); GTAV_PIN_S(p.ldo); GTAV_PIN_S(p.qkv_mode); GTAV_PIN_S(p.D);
-#undef GTAV_PIN_S
+    // What the loaders need for their first fill arrives in SGPRs with the wave (launch-head arguments, above): a loader wave reaches its first fill without a
+    // scalar load.  Every OTHER kernel argument the prologue needs is fetched by the compute waves in one batch of scalar loads behind one wait (pin_args, first
+    // thing in after_prologue, beside the loaders' first fills).  Left to itself hipcc loads GemmParams field by field in the basic blocks that use them: five to
+    // six dependent s_load / s_waitcnt lgkmcnt(0) round trips (100-200 ns each from a cold scalar cache; with everything pinned at the kernel head the first fill
+    // was issued 0.3-0.5 us after block entry, profiles/launch_head stamps).  The empty asm statement is a use that pins the loads to that point.
+    GTAV_HEAD_APPLY(p);
+    auto pin_args = [&]() { asm volatile("" ::"s"(p.bias), "s"(p.out), "s"(p.ldo), "s"(p.qkv_mode), "s"(p.D)); };
     BlockStamps bs;
     bs.begin(p);
     int n0, m0, ks, kt0, nkt;
-    tile_map_fast<EPI == EPI_PARTIAL, TNB, TM>(p, n0, m0, ks, kt0, nkt);
+    tile_map_fast<EPI == EPI_PARTIAL, TNB, TM>(p, n0, m0, ks, kt0, nkt, EPI == EPI_PARTIAL ? p.tm.tiles * p.splitk : p.tm.tiles);
     f32x4 acc[FI][FJ];
 #pragma unroll
     for (int i = 0; i < FI; ++i)
@@ -2075,6 +2125,7 @@ __global__ __launch_bounds__(64 * (WN * WM + NL), 1) void gemm_l_kernel(GemmPara
         tr = (p.qkv_mode == QKV_SPATIAL) && (n0 >= 2 * p.D);
         f32x4 prope[FI][FJ];
         auto pfq = [&]() {
+            pin_args();
             prefetch_bias<EPI, FI, WM, WN, NL>(p, n0, pbias);
             prefetch_rope<FI, FJ, WM, WN, NL>(p, n0, m0, prope);
             pff();
@@ -2085,7 +2136,7 @@ __global__ __launch_bounds__(64 * (WN * WM + NL), 1) void gemm_l_kernel(GemmPara
         epilogue<EPIX, FI, FJ, WM, WN, NL, true>(p, acc, pbias, smem, n0, m0, ks, tr, prope, ft);
     } else if constexpr (EPI == EPI_QKV) {
         tr = (p.qkv_mode == QKV_SPATIAL) && (n0 >= 2 * p.D);
-        auto pf = [&]() { prefetch_bias<EPI, FI, WM, WN, NL>(p, n0, pbias); pff(); };
+        auto pf = [&]() { pin_args(); prefetch_bias<EPI, FI, WM, WN, NL>(p, n0, pbias); pff(); };
         if (tr) mainloop_l<true, NS, FI, FJ, WN, WM, NL>(p, smem, n0, m0, kt0, nkt, acc, bs, pf);
         else mainloop_l<false, NS, FI, FJ, WN, WM, NL>(p, smem, n0, m0, kt0, nkt, acc, bs, pf);
         GTAV_STAMP(bs.t[2]);
@@ -2094,12 +2145,12 @@ __global__ __launch_bounds__(64 * (WN * WM + NL), 1) void gemm_l_kernel(GemmPara
         f32x4 xpre[FI][FJ];
         // (compute waves of the loader-wave kernel issue no other vector-memory operation in the K loop and never wait on vmcnt there: the whole
         // residual tile can be requested up front)
-        auto pf = [&]() { prefetch_bias<EPI, FI, WM, WN, NL>(p, n0, pbias); prefetch_resid<FI, FJ, WM, WN, NL>(p, n0, m0, xpre, 0, FI * FJ); };
+        auto pf = [&]() { pin_args(); prefetch_bias<EPI, FI, WM, WN, NL>(p, n0, pbias); prefetch_resid<FI, FJ, WM, WN, NL>(p, n0, m0, xpre, 0, FI * FJ); };
         mainloop_l<false, NS, FI, FJ, WN, WM, NL>(p, smem, n0, m0, kt0, nkt, acc, bs, pf);
         GTAV_STAMP(bs.t[2]);
         epilogue<EPIX, FI, FJ, WM, WN, NL, true>(p, acc, pbias, smem, n0, m0, ks, tr, xpre, ft);
     } else {
-        auto pf = [&]() { prefetch_bias<EPI, FI, WM, WN, NL>(p, n0, pbias); pff(); };
+        auto pf = [&]() { pin_args(); prefetch_bias<EPI, FI, WM, WN, NL>(p, n0, pbias); pff(); };
         mainloop_l<false, NS, FI, FJ, WN, WM, NL>(p, smem, n0, m0, kt0, nkt, acc, bs, pf);
         GTAV_STAMP(bs.t[2]);
         epilogue<EPIX, FI, FJ, WM, WN, NL, false>(p, acc, pbias, smem, n0, m0, ks, tr, acc, ft);
@@ -2125,21 +2176,17 @@ __global__ __launch_bounds__(64 * (WN * WM + NL), 1) void gemm_l_kernel(GemmPara
 // of one-block-per-CU tiles lose to the two-blocks-per-CU QKV GEMM there).
 // ---------------------------------------------------------------------------------------------------------------------
 template <int NS>
-__global__ __launch_bounds__(512, 1) void gemm_qkvt_attn_kernel(GemmParams p) {
+__global__ __launch_bounds__(512, 1) void gemm_qkvt_attn_kernel(GTAV_HEAD_PARAMS, GemmParams p) {
     constexpr int FI = 3, FJ = 5, WN = 4, WM = 1, NL = 4, TNB = 192, TM = 80, TMAX = 5;
     constexpr int PN = 384;   // LDS bytes per token row of the q | k | v image: 24 16-byte chunks, XOR-swizzled inside groups of 8
     extern __shared__ __attribute__((aligned(16))) char smem_l[];
     static_assert(NS * (2 * FI * WN + 2 * FJ * WM) * 1024 >= TM * PN, "the ring must cover the epilogue's LDS image");
     char* smem = smem_l;
-#define GTAV_PIN_S(x) asm volatile("" ::"s"(x))
-    GTAV_PIN_S(p.X); GTAV_PIN_S(p.W); GTAV_PIN_S(p.M); GTAV_PIN_S(p.N); GTAV_PIN_S(p.K);
-    GTAV_PIN_S(p.tm.tiles_m); GTAV_PIN_S(p.tm.tiles_n); GTAV_PIN_S(p.tm.gn); GTAV_PIN_S(p.tm.group); GTAV_PIN_S(p.tm.tiles);
-    GTAV_PIN_S(p.tm.rcp_group); GTAV_PIN_S(p.tm.rcp_gn); GTAV_PIN_S(p.tm.rcp_gnlast);
-#undef GTAV_PIN_S
+    GTAV_HEAD_APPLY(p);   // the loaders' operands and tile map arrive in SGPRs with the wave (launch-head arguments)
     BlockStamps bs;
     bs.begin(p);
     int n0, m0, ks, kt0, nkt;
-    tile_map_fast<false, TNB, TM>(p, n0, m0, ks, kt0, nkt);
+    tile_map_fast<false, TNB, TM>(p, n0, m0, ks, kt0, nkt, p.tm.tiles);
     f32x4 acc[FI][FJ];
 #pragma unroll
     for (int i = 0; i < FI; ++i)
@@ -2260,7 +2307,7 @@ __global__ __launch_bounds__(512, 1) void gemm_qkvt_attn_kernel(GemmParams p) {
 // fragment reads + 44 KB of fills per step against 0.42 us of MFMA issue per SIMD.
 // ---------------------------------------------------------------------------------------------------------------------
 template <int NS>
-__global__ __launch_bounds__(768, 1) void gemm_qkvs_attn_kernel(GemmParams p) {
+__global__ __launch_bounds__(768, 1) void gemm_qkvs_attn_kernel(GTAV_HEAD_PARAMS, GemmParams p) {
     // 4 loader + 8 compute waves (4 along the features x 2 along the tokens, 48 x 80 each): the X tile is 160 rows — the frame's 144 tokens and 16 rows of whatever
     // follows, computed and dropped — so that the tokens divide over two waves per SIMD (with ONE compute wave per SIMD, 48 x 144, a fragment read stuck behind the
     // LDS port held that SIMD's MFMA issue too: K loop 10.0 us for 6.0 us of MFMA issue, profiles/round6/fused_spatial_*_block_stamps*.txt)
@@ -2271,15 +2318,11 @@ __global__ __launch_bounds__(768, 1) void gemm_qkvs_attn_kernel(GemmParams p) {
     static_assert(NS * (2 * FI * WN + 2 * FJ * WM) * 1024 >= IMG, "the ring must cover the epilogue's LDS image");
     static_assert(16 * FJ * WM >= TM && 16 * FJ * WM == S_pad, "two token halves cover the frame");
     char* smem = smem_l;
-#define GTAV_PIN_S(x) asm volatile("" ::"s"(x))
-    GTAV_PIN_S(p.X); GTAV_PIN_S(p.W); GTAV_PIN_S(p.M); GTAV_PIN_S(p.N); GTAV_PIN_S(p.K);
-    GTAV_PIN_S(p.tm.tiles_m); GTAV_PIN_S(p.tm.tiles_n); GTAV_PIN_S(p.tm.gn); GTAV_PIN_S(p.tm.group); GTAV_PIN_S(p.tm.tiles);
-    GTAV_PIN_S(p.tm.rcp_group); GTAV_PIN_S(p.tm.rcp_gn); GTAV_PIN_S(p.tm.rcp_gnlast);
-#undef GTAV_PIN_S
+    GTAV_HEAD_APPLY(p);   // the loaders' operands and tile map arrive in SGPRs with the wave (launch-head arguments)
     BlockStamps bs;
     bs.begin(p);
     int n0, m0, ks, kt0, nkt;
-    tile_map_fast<false, TNB, TM>(p, n0, m0, ks, kt0, nkt);   // tiles step by the frame's 144 rows; the main loop reads 160 from m0 (past the last frame: a valid tile again, dropped)
+    tile_map_fast<false, TNB, TM>(p, n0, m0, ks, kt0, nkt, p.tm.tiles);   // tiles step by the frame's 144 rows; the main loop reads 160 from m0 (past the last frame: a valid tile again, dropped)
     const int tid = threadIdx.x, lane = tid & 63, wraw = tid >> 6, w = wraw - NL, li = lane & 15, g = lane >> 4;
     const int wn = w & (WN - 1), wm = w >> 2;   // compute waves: feature quarter, token half
     f32x4 acc[FI][FJ];
@@ -2592,7 +2635,8 @@ __global__ __launch_bounds__(768, 1) void gemm_lp_kernel(GemmParams p) {
 static thread_local int g_force_stages = 0, g_force_wm = GTAV_ENV_INT("GTAV_GEMM_SHAPE", 0);
 static int g_debug = GTAV_ENV_INT("GTAV_GEMM_DEBUG", 0);
 void gemm_set_stages(int ns) { g_force_stages = ns; }
-void gemm_set_wm(int wm) { g_force_wm = wm; }
+static thread_local int g_force_wfill = 0;   // tests: W fills of every loader-wave launch of this thread non-temporal (GemmParams::wfill)
+void gemm_set_wm(int wm) { g_force_wm = wm & 0xFF; g_force_wfill = wm >> 8 & 1; }
 #ifdef GTAV_EXPERIMENTS
 void gemm_set_debug(int bits) { g_debug = bits; }
 static unsigned long long* g_stamps = nullptr;
@@ -2733,8 +2777,9 @@ static int launch_l(const GemmParams& p, int splitk, hipStream_t stream) {
     }
     GemmParams q = p;
     if (int rc_ = fill_tile_map(q.tm, p.M, p.N, p.K, 16 * FJ * WM, 16 * FI * WN, splitk)) return rc_;
+    GTAV_REQUIRE(q.splitk >= 0 && q.splitk < 256, "gemm: %d K slices do not fit the launch-head arguments", q.splitk);
     const dim3 grid(q.tm.tiles * splitk);
-    GTAV_LAUNCH((gemm_l_kernel<EPI, NS, FI, FJ, WN, WM, NL>), grid, dim3(64 * (WN * WM + NL)), LDS, stream, q);
+    GTAV_LAUNCH((gemm_l_kernel<EPI, NS, FI, FJ, WN, WM, NL>), grid, dim3(64 * (WN * WM + NL)), LDS, stream, GTAV_HEAD_VALUES(q), q);
     GTAV_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -2884,8 +2929,9 @@ int launch_gemm_qkvt_attn(const GemmParams& p_in, hipStream_t stream) {
 #endif
     q.out_sc1 = 1;
     q.splitk = 1;
+    if (g_force_wfill) q.wfill = 1;
     if (int rc_ = fill_tile_map(q.tm, q.M, q.N, q.K, 80, 192, 1)) return rc_;
-    GTAV_LAUNCH((gemm_qkvt_attn_kernel<NS>), dim3(q.tm.tiles), dim3(512), LDS, stream, q);
+    GTAV_LAUNCH((gemm_qkvt_attn_kernel<NS>), dim3(q.tm.tiles), dim3(512), LDS, stream, GTAV_HEAD_VALUES(q), q);
     GTAV_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -2915,11 +2961,12 @@ int launch_gemm_qkvs_attn(const GemmParams& p_in, hipStream_t stream) {
     q.stamps = g_stamps;
 #endif
     q.splitk = 1;
+    if (g_force_wfill) q.wfill = 1;
     q.qkv_mode = QKV_SPATIAL;
     if (int rc_ = fill_tile_map(q.tm, q.M, q.N, q.K, 144, 192, 1)) return rc_;
     // (Two blocks per (frame, head) on grids of at most half the chip — both run the whole projection, each walks half of the query tiles in one round of its eight
     // waves — was measured and is not kept: 19.2 -> 19.4 us at 80 blocks, 19.8 -> 20.9 at 128.)
-    GTAV_LAUNCH((gemm_qkvs_attn_kernel<NS>), dim3(q.tm.tiles), dim3(768), LDS, stream, q);
+    GTAV_LAUNCH((gemm_qkvs_attn_kernel<NS>), dim3(q.tm.tiles), dim3(768), LDS, stream, GTAV_HEAD_VALUES(q), q);
     GTAV_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -3029,6 +3076,7 @@ int launch_gemm(const GemmParams& p_in, int epi_x, hipStream_t stream) {
     // frames/s) and back-to-back (profiles/round1/v13_gemm_sc1_stores_microbench.txt).  8-byte sc1 stores are SLOWER (one
     // fabric write each), so the unstaged epilogues keep plain stores.  Debug bit 3 turns it off (experiments).
     p.out_sc1 = (g_debug & 8) ? 0 : 1;
+    if (g_force_wfill) p.wfill = 1;
     GTAV_REQUIRE(prefetch_desc_ok(p.pf), "gemm: bad prefetch descriptor (row tiles %d, K tiles %d, K slices %d)", p.pf.rt, p.pf.nkt, p.pf.splitk);
     if (g_debug & 0x800000) p.pf.next = nullptr;   // experiments build: A/B
     GTAV_REQUIRE(p.K > 0 && p.K % TK == 0, "gemm: K=%d must be a positive multiple of %d", p.K, TK);

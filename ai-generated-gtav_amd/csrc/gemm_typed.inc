@@ -5,6 +5,8 @@
 struct GemmParams {
     const f16* X;  // tile-major [round_up(M,128)][K]
     int ldx;       // unused (kept for ABI stability of the struct users): K is the logical row length
+    int wfill;     // loader-wave kernels (mainloop_l): 1 = their W fills carry the non-temporal cache policy, 0 = default.  Same bytes, same order: the result does
+                   // not depend on it (gtav_dit_set_weight_fill_policy; tests: bit 8 of gemm_set_wm).  It sits in what used to be padding: the size is unchanged.
     const f16* W;  // tile-major [round_up(N,128)][K]
     int M, N, K;   // K % 64 == 0
     int debug;     // -DGTAV_EXPERIMENTS builds only: bit 0 = skip the LDS fills after the prologue, bit 1 = skip LDS reads + MFMA
@@ -102,5 +104,6 @@ int launch_gemm_tn(const GemmParams& p, hipStream_t stream);
 // Test overrides, thread_local in gemm.hip and therefore one pair per operand type (the twin's are gtav_bf16::gemm_set_*): gtav_op_gemm_set_stages / _set_wm set both.
 // Pipeline depth override (0 = heuristic, else 2 or 4 LDS stages).
 void gemm_set_stages(int ns);
-// Block shape override (0 = heuristic; shape numbers in gemm.hip launch_epi).  Every shape computes the same result.
+// Block shape override (0 = heuristic; shape numbers in gemm.hip launch_epi).  Every shape computes the same result.  Bit 8 (+ 0x100, with any shape or with 0):
+// every loader-wave launch of the thread fills its W operand non-temporally (GemmParams::wfill), whatever the caller's params say.  The same result again.
 void gemm_set_wm(int wm);

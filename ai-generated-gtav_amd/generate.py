@@ -120,9 +120,17 @@ def prefetch_mode(cls) -> int:
     return 0x10000 | cls[0] | cls[1] << 4 | cls[2] << 8 | cls[3] << 12
 
 
+def fill_policy_mode(cls) -> int:
+    """(out, fc1, fc2, qkv) values (0 = that weight is filled with the default cache policy, 1 = non-temporal) -> the mode word of
+    gtav_dit_set_weight_fill_policy (include/gtav_amd.h)."""
+    if any(v not in (0, 1) for v in cls) or len(cls) != 4:
+        raise ValueError(f"fill_policy_mode: {cls!r} is not four values of 0 / 1")
+    return cls[0] | cls[1] << 4 | cls[2] << 8 | cls[3] << 12
+
+
 @torch.inference_mode()
 def tune_weight_prefetch(model, B: int = 1, window: Optional[int] = None, steps: int = 24, rounds: int = 2, use_actions: bool = False,
-                         latent_hw=None, per_class: bool = True, fused_temporal: bool = True, fused_spatial: bool = True) -> dict:
+                         latent_hw=None, per_class: bool = True, fused_temporal: bool = True, fused_spatial: bool = True, fill_policy: bool = True) -> dict:
     """Times the captured full-window sampler step of batch B under different settings of the next-weight L2 prefetch (docs/LABNOTES.md 4.10) and leaves
     the model on the fastest.  The results are bit-identical under every setting, only the speed differs, and what pays depends on the GPU: on some
     MI355X GPUs prefetching every weight takes 7-12 % off the step; on the others that costs 1-8 % (the prefetched lines are gone before their consumer
@@ -131,8 +139,10 @@ def tune_weight_prefetch(model, B: int = 1, window: Optional[int] = None, steps:
     capture per switch); then, with `per_class`, from the fastest of them one pass over the four weight classes (fc2, fc1, out-proj, to_qkv) trying skip / first 4 K tiles / whole
     slice for each while the others stay.  About 0.5 s + 2.5 s at batch 1; synthetic latents.
     With `fused_temporal` / `fused_spatial` the fused to_qkv + attention launches are timed the same way afterwards (eligible windows only) and kept where faster.
+    Last, with `fill_policy`, the cache policy of the weight fills (gtav_dit_set_weight_fill_policy; steps of at most 1 536 tokens): one greedy pass over the four
+    classes on the same captured step, non-temporal against what is kept so far, alternating; a class keeps non-temporal fills only where they are decisively faster.
     Returns {"on_ms", "off_ms", "chosen": "on" | "off" | "per-class", "classes": {...}, "mode", "tuned_ms", "fused_temporal_qkv_attention": {...} | None,
-    "fused_spatial_qkv_attention": {...} | None}
+    "fused_spatial_qkv_attention": {...} | None, "weight_fill_policy": {"classes": {...}, "mode", "ms": {class: [kept_ms, nt_ms]}} | None}
     (milliseconds per step)."""
     dev = model.device
     T = int(window or model.max_frames)
@@ -211,9 +221,28 @@ def tune_weight_prefetch(model, B: int = 1, window: Optional[int] = None, steps:
         timed(cur)
         fused_s = {"on_ms": round(t_on, 4), "off_ms": round(t_off, 4), "chosen": "on" if keep else "off", "was": was}
         cur_ms = min(cur_ms, t_on) if keep else cur_ms
+    # The cache policy of the weight fills (docs/LABNOTES.md 13.2): like the prefetch a property of the GPU, and of the prefetch setting just chosen (a weight
+    # whose lines the prefetch left in L2 has little to gain), so it is timed last.  A tie means default.
+    fill = None
+    if fill_policy and B * T * (h // model.patch_size) * (w // model.patch_size) <= 1536:
+        fcur, fms = [0, 0, 0, 0], {}
+        for c in (2, 1, 0, 3):
+            t_keep = t_nt = float("inf")
+            cand = fcur[:c] + [1] + fcur[c + 1:]
+            for _ in range(rounds):
+                model.set_weight_fill_policy(fill_policy_mode(fcur))
+                t_keep = min(t_keep, timed(cur))
+                model.set_weight_fill_policy(fill_policy_mode(cand))
+                t_nt = min(t_nt, timed(cur))
+            fms[PREFETCH_CLASSES[c]] = [round(t_keep, 4), round(t_nt, 4)]
+            if t_nt < t_keep * 0.997:
+                fcur, cur_ms = cand, min(cur_ms, t_nt)
+        model.set_weight_fill_policy(fill_policy_mode(fcur))
+        timed(cur)                                            # leaves the handle warmed up (and its step captured) under the kept setting
+        fill = {"classes": dict(zip(PREFETCH_CLASSES, fcur)), "mode": fill_policy_mode(fcur), "ms": fms}
     model.check()
     chosen = "on" if cur == on else "off" if cur == off else "per-class"
-    return {"on_ms": round(best[on], 4), "off_ms": round(best[off], 4), "chosen": chosen, "classes": dict(zip(PREFETCH_CLASSES, cur)),
+    return {"weight_fill_policy": fill, "on_ms": round(best[on], 4), "off_ms": round(best[off], 4), "chosen": chosen, "classes": dict(zip(PREFETCH_CLASSES, cur)),
             "mode": prefetch_mode(cur), "tuned_ms": round(cur_ms, 4), "fused_temporal_qkv_attention": fused, "fused_spatial_qkv_attention": fused_s}
 
 

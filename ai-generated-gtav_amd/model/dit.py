@@ -293,6 +293,8 @@ class DiT(_HipModule):
                     _lib.check(L.gtav_dit_set_fold(self._handle, *self._fold))
                 if getattr(self, "_weight_prefetch", None) is not None:
                     _lib.check(L.gtav_dit_set_weight_prefetch(self._handle, int(self._weight_prefetch)))
+                if getattr(self, "_weight_fill_policy", None) is not None:
+                    _lib.check(L.gtav_dit_set_weight_fill_policy(self._handle, int(self._weight_fill_policy)))
                 for g in sorted(self._bf16_groups):                      # a re-created handle keeps the operand types chosen before
                     _lib.check(L.gtav_dit_set_operand_dtype(self._handle, g, 1))
                 if self._trainable:
@@ -589,6 +591,16 @@ class DiT(_HipModule):
         self._weight_prefetch = mode
         if self._handle:
             _lib.check(_lib.load().gtav_dit_set_weight_prefetch(self._handle, mode))
+
+    def set_weight_fill_policy(self, mode: int):
+        """Cache policy of the small-M GEMMs' weight fills per class (gtav_dit_set_weight_fill_policy; all default when never called; bit-identical results under
+        every word): a per-class word from gtav_amd.generate.fill_policy_mode, nibble 0 = default policy, 1 = non-temporal."""
+        mode = int(mode)
+        if mode & ~0x1111:
+            raise ValueError(f"set_weight_fill_policy: mode {mode:#x} is not a per-class word of nibbles 0 / 1 (gtav_amd.generate.fill_policy_mode)")
+        self._weight_fill_policy = mode
+        if self._handle:
+            _lib.check(_lib.load().gtav_dit_set_weight_fill_policy(self._handle, mode))
 
     def set_fold(self, mode: int, min_tokens_a: int = -1, min_tokens_b: int = -1):
         """EXPERIMENTS BUILD ONLY (gtav_amd.lib.load_experiments(), tools/fold_bench.py): the LayerNorm fold of round 3 (gtav_dit_set_fold, csrc/experiments.h) —

@@ -147,6 +147,15 @@ int gtav_dit_fused_launches(gtav_dit* h, int32_t B, int32_t T, int32_t t0);
  * graphs of the handle. */
 int gtav_dit_set_weight_prefetch(gtav_dit* h, int32_t mode);
 
+/* Cache policy of the weight fills of the small-M GEMM launches (steps of up to 1536 tokens: the loader-wave kernels, the two fused to_qkv + attention launches
+ * included; docs/LABNOTES.md 13.2).  A step reads more weight bytes than the last-level cache holds, so every launch streams its weight from HBM; with the
+ * non-temporal policy on those loads (weights only, never activations) the bytes land sooner on some GPUs and cost L2 hits of neighbouring row tiles on others
+ * (profiles/launch_head/).  It changes no arithmetic: the same bytes in the same order, bit-identical results under every setting.  mode: one nibble per class,
+ * laid out like gtav_dit_set_weight_prefetch's — bits 0-3 the out-projection's weight, 4-7 fc1's, 8-11 fc2's, 12-15 to_qkv's — with nibble 0 = default policy,
+ * 1 = non-temporal; anything else is refused.  Default 0.  gtav_amd.generate.tune_weight_prefetch times it per class on the captured step and keeps non-temporal
+ * fills only where they are decisively faster.  Every call that changes the setting drops the captured graphs of the handle. */
+int gtav_dit_set_weight_fill_policy(gtav_dit* h, int32_t mode);
+
 /* In-situ kernel timing for bench.py's roofline line: when enabled, every kernel of a forward is bracketed by
  * HIP events on the launch stream and the forward synchronises at its end (measurement passes only).
  * Classes: 0 LN+modulate, 1 QKV GEMM, 2 spatial attention, 3 temporal attention, 4 out-proj GEMM, 5 fc1 GEMM,

@@ -6,7 +6,10 @@
  *   gtav_op_gemm_set_stages   LDS ring depth of the 128 x 128 tiles: 2 or 4
  *   gtav_op_gemm_set_wm       block shape: 2, 3 (128 x 128, 4 / 8 waves), 7 (256 x 256), 11 (64 x 48), 12 (128 x 192), 13 (128 x 96, 4 waves), 14 (64 x 96),
  *                             20 / 24 / 26 (loader-wave kernel, 128 x 96 / 64 x 48 / 64 x 96 tiles), 31 (persistent loader-wave kernel, 128 x 192 tiles, 3-stage ring; its 4-stage / 256 x 128 / 128 x 256 forms 30 / 32 / 33 exist in the experiments build only)
- *                             — csrc/gemm.hip launch_epi
+ *                             — csrc/gemm.hip launch_epi.  Plus GTAV_GEMM_WM_NT_WEIGHT_FILLS (0x100; with a shape or with 0 = heuristic): every loader-wave
+ *                             launch of the thread (shapes 20 / 24 / 26 / 29 and the two fused to_qkv + attention launches) fills its weight operand with the
+ *                             non-temporal cache policy (GemmParams::wfill, the kernel side of gtav_dit_set_weight_fill_policy): the same bits again
+ *                             (tests/test_gpu_launch_head.py)
  *
  * gtav_op_set_operand_dtype   operand type of the kernel-level entry points (gtav_op_*) that have no _bf16 sibling: GTAV_OPERAND_F16 (0, the default) or
  *                             GTAV_OPERAND_BF16 (1), PER THREAD like the two above.  With bf16 set, gtav_op_gemm_f16, gtav_op_gemm_qkv, gtav_op_ln_modulate,
@@ -25,6 +28,8 @@
 #define GTAV_AMD_TESTING_H
 
 #include <stdint.h>
+
+#define GTAV_GEMM_WM_NT_WEIGHT_FILLS 0x100
 
 #ifdef __cplusplus
 extern "C" {
