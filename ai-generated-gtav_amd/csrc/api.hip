@@ -330,13 +330,18 @@ int gtav_op_rope_interleave(const float* cos_t, const float* sin_t, float* cs, i
 }
 int gtav_op_gemm_choose_splitk(int32_t M, int32_t N, int32_t K) { return gemm_choose_splitk(M, N, K); }
 int gtav_op_gemm_resid_inplace(int32_t M, int32_t N, int32_t K) { return gemm_resid_inplace_ok(M, N, K, 0) ? 1 : 0; }
-// the forced ring depth / block shape are thread_locals of gemm.hip, one pair per operand type: both are set, so a forced shape reaches the twin too
-void gtav_op_gemm_set_stages(int32_t ns) { gemm_set_stages(ns); gtav_bf16::gemm_set_stages(ns); }
+int gtav_op_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t qkv_mode, int32_t S, int32_t splitk, int32_t rows_per_gate, int32_t* plan8) {
+    static_assert(sizeof(gtav_shared::GemmPlan) == 8 * sizeof(int32_t), "plan8 is the GemmPlan");
+    GTAV_REQUIRE(plan8, "op_gemm_plan: null argument");
+    return gtav_shared::gemm_plan(gtav_shared::GemmProblem{M, N, K, epilogue, qkv_mode, S, splitk, rows_per_gate}, (gtav_shared::GemmPlan*)plan8);
+}
+// the forced ring depth / block shape are thread_locals of the planner (gemm_plan.hip), one set for both operand types
+void gtav_op_gemm_set_stages(int32_t ns) { gtav_shared::gemm_set_stages(ns); }
 #ifdef GTAV_EXPERIMENTS
-void gtav_op_gemm_set_debug(int32_t bits) { gemm_set_debug(bits); }   // libgtav_amd_exp.so only (csrc/experiments.h)
+void gtav_op_gemm_set_debug(int32_t bits) { gtav_shared::gemm_set_debug(bits); }   // libgtav_amd_exp.so only (csrc/experiments.h)
 void gtav_op_gemm_set_stamps(void* buf_dev, int32_t max_blocks) { gemm_set_stamps((unsigned long long*)buf_dev, max_blocks); }
 #endif
-void gtav_op_gemm_set_wm(int32_t wm) { gemm_set_wm(wm); gtav_bf16::gemm_set_wm(wm); }
+void gtav_op_gemm_set_wm(int32_t wm) { gtav_shared::gemm_set_wm(wm); }
 void gtav_op_set_operand_dtype(int32_t dtype) { g_op_bf16 = dtype == GTAV_OPERAND_BF16; }
 
 // Calibration of the in-situ profiler (gtav_dit_profile / gtav_vae_profile): `reps` launches of a one-wave kernel that spins `spin_us` microseconds on the

@@ -110,9 +110,11 @@ using gtav_shared::last_error;
 #ifdef GTAV_EXPERIMENTS
 #define GTAV_ENV_INT(name, dflt) (getenv(name) ? atoi(getenv(name)) : (dflt))
 #define GTAV_DBG(p, bits) ((p).debug & (bits))
+#define GTAV_LAB_BUILD true
 #else
 #define GTAV_ENV_INT(name, dflt) (dflt)
 #define GTAV_DBG(p, bits) false
+#define GTAV_LAB_BUILD false
 #endif
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }

@@ -3,6 +3,7 @@
 // common.h `tiled_off` (rows padded to 128, K to 64).  fp16 outputs that feed another GEMM are written tile-major too.
 #pragma once
 #include "common.h"
+#include "gemm_plan.h"
 
 namespace gtav {
 
@@ -39,17 +40,9 @@ constexpr size_t gemm_sk_flag_bytes() { return (size_t)GEMM_SK_MAX_SPLIT * 4; }
 
 // GemmParams, GemmGroup, GemmDwGroup and the launchers that take them: the declarations that name `f16` (one text for both operand types)
 #include "gemm_typed.inc"
-// True when launch_gemm would run this shape on the persistent ping-pong kernel (large M): residual GEMMs then use the in-place
-// EPI_RESID epilogue (hidden under the other wave group's main loop) instead of split-K slabs.
-bool gemm_pp_ok(int M, int N, int K, int epi);
-// True when launch_gemm runs a residual GEMM of this shape on the persistent loader-wave kernel (shape 31, large M), whose in-place gated residual epilogue
-// (EPI_RESID: the residual tile is requested at the head of the tile's K loop) replaces slab + LayerNorm reduction.
-bool gemm_resid_inplace_ok(int M, int N, int K, int rows_per_gate);
-// Split-K factor used for a residual GEMM of this shape (1 = no split): fills the 256 CUs when M is small.
-int gemm_choose_splitk(int M, int N, int K);
-// (gemm_set_stages / gemm_set_wm, the forced ring depth and block shape of the tests, are per operand type: gemm_typed.inc)
+// Which block shape a launch runs on, its K slices and tile-group width: the planner (gemm_plan.h, namespace gtav_shared — ONE copy for both operand types).
+using gtav_shared::gemm_pp_ok, gtav_shared::gemm_resid_inplace_ok, gtav_shared::gemm_choose_splitk;
 #ifdef GTAV_EXPERIMENTS
-void gemm_set_debug(int bits);   // timing experiments, WRONG results
 // per-block timeline: 8 x u64 per block {s_memtime at entry, first K-tile landed, main loop done, epilogue done (end);
 // s_memrealtime at entry and end (100 MHz); XCC id; 0}; buf must hold 8 * grid u64 (null switches it off)
 void gemm_set_stamps(unsigned long long* buf, int max_blocks);

@@ -11,7 +11,8 @@
 //   gemm256_kernel  256 x 256 tile, K-tile in four quadrant phases                             mainloop256
 //   gemm_l_kernel   loader-wave tiles (small and medium M: 128 x 96, 64 x 48 / 96, 128 x 144)   mainloop_l
 //   gemm_lp_kernel  persistent loader-wave kernel, 128 x 192 tiles (large-M residual GEMMs, in-place residual epilogue)
-// launch_gemm() picks the shape per launch from a cost model / measured thresholds (bottom of this file).  Kernels, launchers and block shapes that only
+// launch_gemm() (bottom of this file) validates, asks the planner which block shape runs — gemm_plan.h: the shape table GEMM_SHAPES and the measured rules, host
+// code compiled once for both operand types — and dispatches to the kernel instantiated from that shape's row.  Kernels, launchers and block shapes that only
 // ever measured slower live in gemm_experiments.inc, which only `build.sh exp` compiles.
 //
 // Orientation: the MFMA "A" operand is the W tile and "B" the X tile, so D[row = feature][col = token]:
@@ -28,6 +29,7 @@
 #include <hip/hip_ext.h>
 
 namespace gtav {
+using namespace gtav_shared;   // the shape table, the plan and the test / laboratory overrides (gemm_plan.h)
 
 namespace {
 
@@ -650,7 +652,7 @@ __device__ __forceinline__ void mainloop_g(const GemmParams& p, char* smem, int 
 // row-tiles as well as W panels in that XCD's 4 MiB L2.  With m fastest, X (11.8 MB at M = 5760) was re-streamed from the
 // fabric once per n-panel: rocprofv3 FETCH_SIZE 301 MB per fc1 launch against 20 MB algorithmic (profiles/round1/pmc).
 // Split-K: the K slice is the slowest index, so the slices of one W panel stay on one XCD.  gn is chosen on the host
-// (choose_gn): round 1 fixed it at tiles_n / 8 — every XCD then owns an eighth of the n-panels and streams ALL of X, which for
+// (gemm_plan.hip gemm_choose_gn): round 1 fixed it at tiles_n / 8 — every XCD then owns an eighth of the n-panels and streams ALL of X, which for
 // the N = 1024 GEMMs at large M is 8 x X from the fabric (fc2 at M = 5760: 385 MB per launch against 55 MB algorithmic).
 template <bool SPLITK, int TNB, int TMB>
 __device__ __forceinline__ void tile_map(const GemmParams& p, int& n0, int& m0, int& ks, int& kt0, int& nkt) {
@@ -667,7 +669,7 @@ __device__ __forceinline__ void tile_map(const GemmParams& p, int& n0, int& m0, 
         nkt = nkt / p.splitk;
         kt0 = ks * nkt;
     }
-    int gn = p.tm.gn;                                      // host: choose_gn() (every launcher fills it)
+    int gn = p.tm.gn;                                      // host: gemm_choose_gn() (every launcher fills it)
     const int group = tiles_m * gn;
     const int ng = tile_id / group, rem = tile_id - ng * group;
     const int n_first = ng * gn;
@@ -2628,63 +2630,23 @@ __global__ __launch_bounds__(768, 1) void gemm_lp_kernel(GemmParams p) {
 
 }  // namespace
 
-// Shape / ring-depth overrides: they select among kernels that all compute the same result (the parity tests force every
-// shape through them).  The debug bits (skip fills / skip MFMA: WRONG results, timing only) exist only in the
-// -DGTAV_EXPERIMENTS build, which also reads GTAV_GEMM_DEBUG / GTAV_GEMM_SHAPE for whole-bench A/B runs.
-// (per THREAD, like the handles: a test that forces a shape does not change what another thread's handle launches)
-static thread_local int g_force_stages = 0, g_force_wm = GTAV_ENV_INT("GTAV_GEMM_SHAPE", 0);
-static int g_debug = GTAV_ENV_INT("GTAV_GEMM_DEBUG", 0);
-void gemm_set_stages(int ns) { g_force_stages = ns; }
-static thread_local int g_force_wfill = 0;   // tests: W fills of every loader-wave launch of this thread non-temporal (GemmParams::wfill)
-void gemm_set_wm(int wm) { g_force_wm = wm & 0xFF; g_force_wfill = wm >> 8 & 1; }
 #ifdef GTAV_EXPERIMENTS
-void gemm_set_debug(int bits) { g_debug = bits; }
 static unsigned long long* g_stamps = nullptr;
-static int g_stamp_blocks = 0;
-void gemm_set_stamps(unsigned long long* buf, int max_blocks) { g_stamps = buf; g_stamp_blocks = max_blocks; }
+void gemm_set_stamps(unsigned long long* buf, int) { g_stamps = buf; }   // (max_blocks: the tool sizes the buffer for the largest grid it launches)
 #endif
-
-// The persistent loader-wave kernel (shape 31) takes the narrow residual GEMMs (N <= 2048: out-proj, fc2) in ONE K slice once its 128 x 192 tiles cover
-// most of the chip (>= 160 tiles): measured against the heuristic's own choice, split-K included (profiles/round3/persistent_loader_kernel_vs_heuristic_*.txt) —
-// M = 4320: out-proj 17.2 -> 13.2 us, fc2 47.1 -> 36.3 us; M = 5760: 17.5 -> 14.3, 51.0 -> 45.1; M = 8640: 27.5 -> 24.0, 78.6 -> 75.0; M = 11 520: 27.9 -> 25.1,
-// 87.6 -> 84.5; at 120 tiles (M = 2880) it loses (12.0 -> 12.8, 31.7 -> 34.0) and the split-K shapes stay.  One slab also halves what the LayerNorm behind fc2 reads.
-static int g_lp_enable = GTAV_ENV_INT("GTAV_LP", 1);   // experiments build: 0 = round-2 selection, for A/B runs
-static int g_resid_inplace = GTAV_ENV_INT("GTAV_RESID_INPLACE", 1);   // experiments build: 0 = slab + LayerNorm reduction at every M (A/B runs)
-static bool lp_takes(int M, int N, int K) { return g_lp_enable && N <= 2048 && N % 8 == 0 && K >= 512 && cdiv(M, 192) * cdiv(N, 128) >= 160; }
-// (rows_per_gate: tokens per gate vector — the persistent kernel stages at most LP_MAXF gate rows per 192-token tile; 0 = no gate.  A forced block shape
-// other than 31 (tests) runs the one-shot kernels, where the in-place epilogue was measured slower than slab + LayerNorm: keep the slabs then.)
-bool gemm_resid_inplace_ok(int M, int N, int K, int rows_per_gate) {
-    return g_resid_inplace && lp_takes(M, N, K) && (rows_per_gate == 0 || rows_per_gate >= 32) && (g_force_wm == 0 || g_force_wm == 31);
-}
-int gemm_choose_splitk(int M, int N, int K) {
-    if (lp_takes(M, N, K)) return 1;
+// what the overrides pass to the kernels of every launcher: the tests' non-temporal weight fills (read by the loader-wave kernels), and from the laboratory
+// the debug bits the kernel knows (`mask`) and the stamp buffer.  Product: 0 and null.
+static void lab_fields(GemmParams& q, int mask) {
+    if (gemm_forced_wfill()) q.wfill = 1;
+    q.debug = gemm_debug() & mask;
+    q.stamps = nullptr;
 #ifdef GTAV_EXPERIMENTS
-    if (g_debug & 256) return 1;   // A/B with GTAV_RESID_INPLACE_MIN_M=1: full-K residual GEMMs on 64 x 48 tiles + in-place epilogue (measured slower, profiles/round2/forward_ab_B1_inplace_fullK.txt)
+    q.stamps = g_stamps;
 #endif
-    const int tiles = cdiv(M, 128) * cdiv(N, TN);
-    int s = 1;
-    // Every slab is one more 16-byte load per thread in the LayerNorm behind the GEMM (~0.4 us per slab and launch at M = 720) and 3 MB more through the L2s that
-    // hold the next GEMM's prefetched weight: from 48 tiles on (the batch-1 window step) a K slice is at least 512 deep — out-proj in two slices instead of four:
-    // GEMM unchanged (6.7-7.0 us), LayerNorm 5.45 -> 4.7 us, forward -1.3 ... -3 % (profiles/round3/forward_ab_B1_splitk_slices.txt); fc2 keeps four slices of 1024
-    // (two: +1.6 us).  Below 48 tiles (the 144-token cached step) the CUs matter more: 256 as before.
-    static const int old_rule = GTAV_ENV_INT("GTAV_SPLITK_OLD", 0);   // experiments build: A/B
-    const int min_slice = (tiles >= 48 && !old_rule) ? 512 : 256;
-    while (tiles * s < 192 && s < 8 && (K / TK) % (s * 2) == 0 && K / (s * 2) >= min_slice) s *= 2;
-    // long-K GEMMs whose 128 x 192 grid would fill the 512 block slots unevenly (160-320 tiles): two K slices make it
-    // 320-640 blocks of half the length — fc2 at M = 5760: 69.5 -> 57.6 us, for one more slab (+5 us) in the next LayerNorm
-    if (s == 1 && K >= 4096 && (K / TK) % 2 == 0) {
-        const int t192 = cdiv(M, 192) * cdiv(N, TN);
-        if (t192 >= 160 && t192 < 320) s = 2;
-    }
-    return s;
 }
 
 #define GEMM_LAUNCH(kern, grid, block) GTAV_LAUNCH(kern, grid, block, 0, stream, p)
 
-// shape: 2 = 128x128 / 4 waves, 3 = 128x128 / 8 waves, 7 = 256x256 / 8 waves, phased K-tile (mainloop256),
-//        8 = 96x96 / 6 waves, 9 = 128x96 / 6 waves, 11 = 64x48 / 6 waves, 14 = 64x96 / 6 waves (piece-granular mainloop_g; small M),
-//        12 = 128x192 / 8 waves, two blocks per CU (mainloop_g; large M).
-// (Shapes 4, 5, 6, 10 of round 1 — 128x256, loader-wave variants, 4-wave 128x192 — measured slower and were removed.)
 // CU count of the current device, asked once per device (the persistent kernels size their grids by it; the launchers that opt in to large dynamic LDS key
 // their per-device flag by *dev_out)
 static int g_num_cus[64] = {0};
@@ -2699,59 +2661,29 @@ static int device_cus(int* dev_out) {
     }
     return g_num_cus[dev & 63];
 }
-static int g_l_for_8 = GTAV_ENV_INT("GTAV_L_FOR_8", 1);   // experiments build: 0 keeps the 96 x 96 tile (shape 8) where the cost model picks it
-#ifndef GTAV_EXPERIMENTS
-bool gemm_pp_ok(int, int, int, int) { return false; }   // the ping-pong kernel (shape 16) is compiled into the experiments build only (gemm_experiments.inc)
-#endif
 
-// Width (in n-panels) of the tile groups of the block -> tile map (tile_map): the linear tile order is (K slice, group of gn
-// n-panels, m-tile, panel in group) and every XCD takes a contiguous eighth of it.  One pass over a group streams the K slice of X
-// once (its co-resident blocks share X row-tiles and W panels in the XCD's L2), so with G = tiles_n / gn groups and C = 8 / splitk
-// XCDs per K slice the fabric sees  G x X  +  max(1, C / G) x W  bytes per slice: narrow groups re-stream X, wide groups make
-// several XCDs fetch the same W panels.  Pick the minimum, with the W panels of a group capped at 2 MiB (they must survive in the
-// 4 MiB L2 while the group's m-tiles sweep past).  Round 1's fixed gn = tiles_n / 8 is the G = 8 corner: right at M = 720 (X is
-// small), 3.5x too much traffic for the N = 1024 GEMMs at M = 5760.
-static int g_force_gn = GTAV_ENV_INT("GTAV_GEMM_GN", 0);   // experiments build: > 0 forces the group width, < 0 = round-1 rule (A/B runs)
-static int choose_gn(int M, int N, int K, int tmb, int tnb, int splitk) {
-    const int tiles_n = cdiv(N, tnb);
-#ifdef GTAV_EXPERIMENTS
-    if (g_debug & 1024) return tiles_n >= 8 ? tiles_n >> 3 : 1;   // debug bit 10: round-1 rule, for A/B runs in one process
-#endif
-    if (g_force_gn < 0) return tiles_n >= 8 ? tiles_n >> 3 : 1;
-    if (g_force_gn > 0) return g_force_gn < tiles_n ? g_force_gn : tiles_n;
-    const double ks = (double)K / (splitk > 0 ? splitk : 1);
-    const double xs = 2.0 * M * ks, ws = 2.0 * N * ks, wpanel = 2.0 * tnb * ks;
-    const double c = splitk >= 8 ? 1.0 : 8.0 / (splitk > 0 ? splitk : 1);
-    auto cost_of = [&](int gn) {
-        const int g = cdiv(tiles_n, gn);
-        return g * xs + ws * (c > g ? c / g : 1.0);
-    };
-    int best = 1;
-    double best_cost = 1e300;
-    // the 2 MiB cap protects W panels that must SURVIVE in L2 while further m-tiles of the group sweep past; a grid that is resident all at
-    // once (<= 512 block slots) has no sweep — its blocks walk K in step and share the current K window only — so the cap does not apply
-    // (weight gradients of the training step, K = 11 520 tokens: a 2.9 MB W panel forced gn = 1 = every XCD streaming ALL of the 94 MB X
-    // operand, 778 MB per launch at 7 TB/s; uncapped gn = 4: 282 MB)
-    const bool one_round = (long long)cdiv(M, tmb) * tiles_n * (splitk > 0 ? splitk : 1) <= 512;
-    for (int gn = 1; gn <= tiles_n; ++gn) {
-        if (!one_round && gn > 1 && gn * wpanel > 2.0 * 1024 * 1024) break;
-        const double cost = cost_of(gn);
-        if (cost < best_cost * 0.999) best_cost = cost, best = gn;   // ties keep the narrower group (more XCD-local W)
+// Dynamic LDS above 64 KiB needs a per-device opt-in (hipFuncSetAttribute is a per-device setting), once per kernel instantiation: KERNEL is the template
+// argument so that every instantiation has its own word of per-device flags.  *cus (optional) = CU count of the current device.
+template <auto KERNEL>
+static int lds_opt_in(int lds, int* cus = nullptr) {
+    static unsigned long long devs = 0;
+    int dev = 0;
+    const int n = device_cus(&dev);
+    GTAV_REQUIRE(n > 0, "gemm: no current device");
+    if (!(devs >> (dev & 63) & 1)) {
+        GTAV_CHECK_HIP(hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        devs |= 1ull << (dev & 63);
     }
-    // The model ignores how the groups line up with the XCDs' runs of tiles: where it predicts less than a 20 % saving keep round 1's
-    // eighth-of-the-panels groups, which do line up (fc1 at M = 720: gn = 5 instead of 4 was predicted 1 % better and measured
-    // 34.1 MB per launch against 27.4 MB)
-    const int gn1 = tiles_n >= 8 ? tiles_n >> 3 : 1;
-    if (best_cost > 0.8 * cost_of(gn1)) best = gn1;
-    return best;
+    if (cus) *cus = n;
+    return 0;
 }
 
-// block -> tile map constants of the loader-wave kernels (tile_map_fast)
-static int fill_tile_map(GemmParams::TileMap& tm, int M, int N, int K, int tmb, int tnb, int splitk) {
+// block -> tile map constants of the loader-wave kernels (tile_map_fast); gn: the planner's group width for this tile (gemm_plan.h)
+static int fill_tile_map(GemmParams::TileMap& tm, int M, int N, int tmb, int tnb, int splitk, int gn) {
     tm.tiles_m = cdiv(M, tmb);
     tm.tiles_n = cdiv(N, tnb);
     tm.tiles = tm.tiles_m * tm.tiles_n;
-    tm.gn = choose_gn(M, N, K, tmb, tnb, splitk);
+    tm.gn = gn;
     tm.group = tm.tiles_m * tm.gn;
     const int gnlast = tm.tiles_n % tm.gn ? tm.tiles_n % tm.gn : tm.gn;
     auto rcp = [](int d) { return (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); };   // ceil(2^32 / d), d >= 2
@@ -2764,46 +2696,52 @@ static int fill_tile_map(GemmParams::TileMap& tm, int M, int N, int K, int tmb, 
     return 0;
 }
 
-// loader-wave kernels: dynamic LDS above 64 KiB needs the per-device opt-in once per instantiation
-template <int EPI, int NS, int FI, int FJ, int WN, int WM, int NL>
-static int launch_l(const GemmParams& p, int splitk, hipStream_t stream) {
-    constexpr int LDS = NS * (2 * FI * WN + 2 * FJ * WM) * 1024;
-    static unsigned long long attr_devs = 0;
-    int dev = 0;
-    GTAV_REQUIRE(device_cus(&dev) > 0, "gemm: no current device");
-    if (!(attr_devs >> (dev & 63) & 1)) {
-        GTAV_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_l_kernel<EPI, NS, FI, FJ, WN, WM, NL>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        attr_devs |= 1ull << (dev & 63);
-    }
+// ---- one launcher per kernel family: the kernel's template arguments, tile, thread count and LDS ring all come from the shape's row (gemm_plan.h GEMM_SHAPES) ----
+template <int EPI, int SHAPE>
+static int launch_plain(const GemmParams& p, const GemmPlan& plan, hipStream_t stream) {   // the kernels whose LDS is static: gemm_kernel, gemm_g_kernel, gemm256_kernel
+    constexpr GemmShape R = *gemm_shape(SHAPE);
+    static_assert(R.wn == 2 && (R.family == GF_G || R.family == GF_T256 || (R.family == GF_K128 && R.features() == TN)), "two waves along the features");
+    const dim3 grid(plan.blocks), block(R.threads());
+    if constexpr (R.family == GF_G) GEMM_LAUNCH((gemm_g_kernel<EPI, R.ns, R.fi, R.fj, R.wm>), grid, block);
+    else if constexpr (R.family == GF_T256) GEMM_LAUNCH((gemm256_kernel<EPI>), grid, block);
+    else if (plan.ns <= 2) GEMM_LAUNCH((gemm_kernel<EPI, 2, R.wm, R.fj>), grid, block);
+    else GEMM_LAUNCH((gemm_kernel<EPI, 4, R.wm, R.fj>), grid, block);
+    GTAV_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+// loader-wave kernels
+template <int EPI, int SHAPE>
+static int launch_l(const GemmParams& p, const GemmPlan& plan, hipStream_t stream) {
+    constexpr GemmShape R = *gemm_shape(SHAPE);
+    static_assert(R.family == GF_L, "gemm_l_kernel");
+    if (int rc_ = lds_opt_in<gemm_l_kernel<EPI, R.ns, R.fi, R.fj, R.wn, R.wm, R.nl>>(R.ring_bytes())) return rc_;
     GemmParams q = p;
-    if (int rc_ = fill_tile_map(q.tm, p.M, p.N, p.K, 16 * FJ * WM, 16 * FI * WN, splitk)) return rc_;
+    if (int rc_ = fill_tile_map(q.tm, p.M, p.N, R.tokens(), R.features(), plan.splitk, plan.gn)) return rc_;
     GTAV_REQUIRE(q.splitk >= 0 && q.splitk < 256, "gemm: %d K slices do not fit the launch-head arguments", q.splitk);
-    const dim3 grid(q.tm.tiles * splitk);
-    GTAV_LAUNCH((gemm_l_kernel<EPI, NS, FI, FJ, WN, WM, NL>), grid, dim3(64 * (WN * WM + NL)), LDS, stream, GTAV_HEAD_VALUES(q), q);
+    GTAV_LAUNCH((gemm_l_kernel<EPI, R.ns, R.fi, R.fj, R.wn, R.wm, R.nl>), dim3(plan.blocks), dim3(R.threads()), R.ring_bytes(), stream, GTAV_HEAD_VALUES(q), q);
     GTAV_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
-// persistent loader-wave kernel (shape 30): one block per CU, dynamic LDS = ring of NS x 40 KiB
-template <int EPI, int NS, int FI = 4, int FJ = 3, int WN = 2, int WM = 4>
-static int launch_lp(const GemmParams& p, hipStream_t stream) {
-    constexpr int TNB = 16 * FI * WN, TM = 16 * FJ * WM;
-    constexpr int LDS = NS * (TNB + TM) * 128 + (EPI == EPI_RESID ? 2 * (LP_MAXF + 1) * TNB * 4 : 0);   // + the staged bias / gate rows, two tile parities
-    if constexpr (EPI == EPI_RESID) GTAV_REQUIRE(!p.gate || (p.rows_per_gate > 0 && (TM - 1) / p.rows_per_gate + 2 <= LP_MAXF), "gemm/resid on the persistent kernel: %d tokens per gate row are too few (a tile may touch at most %d rows)", p.rows_per_gate, LP_MAXF);
-    static unsigned long long attr_devs = 0;
-    int dev = 0;
-    const int cus = device_cus(&dev);
-    GTAV_REQUIRE(cus > 0, "gemm: no current device");
-    if (!(attr_devs >> (dev & 63) & 1)) {
-        GTAV_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_lp_kernel<EPI, NS, FI, FJ, WN, WM>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        attr_devs |= 1ull << (dev & 63);
+// persistent loader-wave kernel: one block per CU, dynamic LDS = ring of NS x 40 KiB (128 x 192 tiles)
+template <int EPI, int SHAPE>
+static int launch_lp(const GemmParams& p, const GemmPlan& plan, hipStream_t stream) {
+    constexpr GemmShape R = *gemm_shape(SHAPE);
+    static_assert(R.family == GF_LP, "gemm_lp_kernel");
+    if constexpr (!(EPI == EPI_GELU_TANH || EPI == EPI_PARTIAL || EPI == EPI_F16_TILED || EPI == EPI_RESID)) {   // its four epilogues: no other instantiation
+        GTAV_REQUIRE(false, "gemm: the persistent loader-wave kernel (shape %d) has no epilogue %d", SHAPE, (int)EPI);
+    } else {
+        constexpr int TNB = R.features(), TM = R.tokens();
+        constexpr int LDS = R.ns * (TNB + TM) * 128 + (EPI == EPI_RESID ? 2 * (LP_MAXF + 1) * TNB * 4 : 0);   // + the staged bias / gate rows, two tile parities
+        GTAV_REQUIRE(plan.splitk == 1 && p.N % 8 == 0, "gemm: the persistent loader-wave kernel runs the whole K in one slice (N %% 8 == 0)");
+        if constexpr (EPI == EPI_RESID) GTAV_REQUIRE(!p.gate || (p.rows_per_gate > 0 && (TM - 1) / p.rows_per_gate + 2 <= LP_MAXF), "gemm/resid on the persistent kernel: %d tokens per gate row are too few (a tile may touch at most %d rows)", p.rows_per_gate, LP_MAXF);
+        int cus = 0;
+        if (int rc_ = lds_opt_in<gemm_lp_kernel<EPI, R.ns, R.fi, R.fj, R.wn, R.wm>>(LDS, &cus)) return rc_;
+        GemmParams q = p;
+        if (EPI == EPI_RESID && !q.gate) q.rows_per_gate = 1 << 30;   // no gate: one staged row of ones
+        GTAV_LAUNCH((gemm_lp_kernel<EPI, R.ns, R.fi, R.fj, R.wn, R.wm>), dim3(plan.blocks < cus ? plan.blocks : cus), dim3(R.threads()), LDS, stream, q);
+        GTAV_CHECK_HIP(hipGetLastError());
     }
-    GemmParams q = p;
-    if (EPI == EPI_RESID && !q.gate) q.rows_per_gate = 1 << 30;   // no gate: one staged row of ones
-    const int T = cdiv(p.M, TM) * cdiv(p.N, TNB);
-    q.tm.gn = choose_gn(p.M, p.N, p.K, TM, TNB, 1);
-    GTAV_LAUNCH((gemm_lp_kernel<EPI, NS, FI, FJ, WN, WM>), dim3(T < cus ? T : cus), dim3(768), LDS, stream, q);
-    GTAV_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
@@ -2811,41 +2749,20 @@ static int launch_lp(const GemmParams& p, hipStream_t stream) {
 #include "gemm_experiments.inc"   // laboratory: kernels, launchers and block shapes that measured slower than what the heuristic picks (tools/ only)
 #endif
 
+// p.tm.gn is the plan's already (launch_gemm).  Combinations of shape and epilogue without a kernel are refused by name: they have no instantiation.
 template <int EPI>
-static int launch_epi(const GemmParams& p_in, int ns, int shape, int splitk, hipStream_t stream) {
-    GemmParams p = p_in;
-    auto set_gn = [&](int tmb, int tnb) { p.tm.gn = choose_gn(p.M, p.N, p.K, tmb, tnb, splitk); };
+static int launch_epi(const GemmParams& p, const GemmPlan& plan, hipStream_t stream) {
+    const int shape = plan.shape;
     // the LayerNorm-fold epilogues are instantiated for the shapes the heuristic can pick for them (2, 3, 11, 12, 14, 20)
     constexpr bool FOLDISH = EPI == EPI_RESID_FOLD || epi_is_fold_consumer(EPI);
     if constexpr (FOLDISH) GTAV_REQUIRE(shape == 2 || shape == 3 || shape == 11 || shape == 12 || shape == 13 || shape == 14 || shape == 20 || shape == 24 || shape == 26 || shape == 27 || shape == 28,
                                         "gemm: block shape %d has no LayerNorm-fold epilogue", shape);
-    if (shape == 20) return launch_l<EPI, 4, 2, 3, 4, 2, 4>(p, splitk, stream);   // 128 x 96, 8 compute + 4 loader waves
-    if (shape == 24) return launch_l<EPI, 4, 2, 1, 2, 3, 2>(p, splitk, stream);   // 64 x 48, 6 compute + 2 loader waves (the skinny shape 11 on the loader-wave kernel)
-    if (shape == 26) return launch_l<EPI, 4, 2, 2, 2, 3, 2>(p, splitk, stream);   // 64 x 96, 6 compute + 2 loader waves (shape 14 likewise)
-#ifdef GTAV_EXPERIMENTS
-    {   // the shapes the product refuses below: gemm_experiments.inc
-        bool handled = false;
-        const int rc_ = launch_experiment_shape<EPI>(p, ns, shape, splitk, stream, handled);
-        if (handled) return rc_;
-    }
-#else
-    GTAV_REQUIRE(shape != 8 && shape != 9 && shape != 16 && shape != 17 && shape != 18 && shape != 21 && shape != 22 && shape != 23 && shape != 25 && shape != 27 && shape != 28 &&
-                 shape != 30 && shape != 32 && shape != 33 && shape != 40 && shape != 41 && shape != 42, "gemm: block shape %d exists only in the experiments build (csrc/build.sh exp)", shape);
-#endif
+    if (shape == 20) return launch_l<EPI, 20>(p, plan, stream);
+    if (shape == 24) return launch_l<EPI, 24>(p, plan, stream);
+    if (shape == 26) return launch_l<EPI, 26>(p, plan, stream);
     GTAV_REQUIRE(!p.out2 || (EPI == EPI_F16_TILED && shape != 31), "gemm: a second output image (out2) exists for EPI_F16_TILED on the staged epilogue only (epilogue %d, block shape %d)", (int)EPI, shape);
-    if (shape == 31) {   // persistent loader-wave kernel: 128 x 192 tiles, 3-stage ring
-        if constexpr (EPI == EPI_GELU_TANH || EPI == EPI_PARTIAL || EPI == EPI_F16_TILED || EPI == EPI_RESID) {
-            GTAV_REQUIRE(splitk == 1 && p.N % 8 == 0, "gemm: the persistent loader-wave kernel runs the whole K in one slice (N %% 8 == 0)");
-            return launch_lp<EPI, 3>(p, stream);   // (30 / 32 / 33 — 4-stage ring, 256 x 128 / 128 x 256 tiles — were handled above in the experiments build)
-        } else {
-            GTAV_REQUIRE(false, "gemm: the persistent loader-wave kernel (shape %d) has no epilogue %d", shape, (int)EPI);
-        }
-    }
-    if constexpr (!FOLDISH) {
-    // 128 x 144 (nine 16-token groups: one 144-token frame per row tile), 12 compute waves of 32 x 48 + 4 loader waves (round 4): M = 1152, the context-cached
-    // step at batch 8, is 8 x 32 = 256 tiles for fc1 / 4-slice fc2 where the 128 x 128 grid has 288 (1.1 rounds)
-    if (shape == 29) return launch_l<EPI, 4, 2, 3, 4, 3, 4>(p, splitk, stream);
-    }
+    if (shape == 31) return launch_lp<EPI, 31>(p, plan, stream);   // (30 / 32 / 33 — 4-stage ring, 256 x 128 / 128 x 256 tiles: experiments build, below)
+    if constexpr (!FOLDISH) if (shape == 29) return launch_l<EPI, 29>(p, plan, stream);
     // (round 5: a 128 x 144 two-blocks-per-CU tile — shape 12 with three token groups, 6 waves — to turn to_qkv's 720 tiles at M = 5760 (2 rounds at 70 %) into
     // 960 (94 %): correct, race-clean and 40 % SLOWER at every M from 2880 to 11 520 (66 against 47 us; six-wave blocks do not pair up on the SIMDs):
     // profiles/round5/gemm_128x144_two_blocks_per_cu.txt; a 128 x 160 tile of 4 waves of 64 x 80 (864 tiles): 61.5 against 56-58 us on another box; both removed again)
@@ -2855,51 +2772,24 @@ static int launch_epi(const GemmParams& p_in, int ns, int shape, int splitk, hip
     // 256 x 144 with 8 / 6 waves of 128 x 48 / 96 x 48 — and the 256 x 128 loader-wave tile, shape 21: all correct, all 5-30 %
     // SLOWER than the two-blocks-per-CU 128 x 192 tile at M = 5760 / 11 520, profiles/round2/gemm_large_tile_*.txt: without a
     // co-resident block the prologue and epilogue of every tile are exposed.  The 1-block shapes 30-32 were removed again.)
-    if (shape == 14) {         // 64 features x 96 tokens, 6 waves: a few hundred tokens (M = 288-320)
-        set_gn(96, 64);
-        const dim3 grid(cdiv(p.M, 96) * cdiv(p.N, 64) * splitk);
-        GEMM_LAUNCH((gemm_g_kernel<EPI, 4, 2, 2, 3>), grid, dim3(384));
-    } else if (shape == 13) {  // 128 features x 96 tokens, 4 waves of 64 x 48, two-stage ring, two blocks per CU: long-K N = 1024 GEMMs at a few thousand
-                               // tokens in ONE K slice (480 tiles at M = 5760 fill the 512 block slots; 128 x 128 has 360, 128 x 192 only 240)
-        set_gn(96, 128);
-        const dim3 grid(cdiv(p.M, 96) * cdiv(p.N, 128) * splitk);
-        GEMM_LAUNCH((gemm_g_kernel<EPI, 2, 4, 3, 2>), grid, dim3(256));
-    } else if (shape == 12) {  // 128 features x 192 tokens, 8 waves of 64 x 48, two blocks per CU (4 waves per SIMD)
-        set_gn(192, 128);
-        const dim3 grid(cdiv(p.M, 192) * cdiv(p.N, 128) * splitk);
-        GEMM_LAUNCH((gemm_g_kernel<EPI, 2, 4, 3, 4>), grid, dim3(512));
-    } else if (shape == 11) {  // 64 features x 48 tokens, 6 waves: skinny M (context-cached sampling, M = 144)
-        set_gn(48, 64);
-        const dim3 grid(cdiv(p.M, 48) * cdiv(p.N, 64) * splitk);
-        GEMM_LAUNCH((gemm_g_kernel<EPI, 4, 2, 1, 3>), grid, dim3(384));   // 6 stages measured 6-8 % slower
-    } else if (shape == 7) {
+    if (shape == 14) return launch_plain<EPI, 14>(p, plan, stream);
+    if (shape == 13) return launch_plain<EPI, 13>(p, plan, stream);
+    if (shape == 12) return launch_plain<EPI, 12>(p, plan, stream);
+    if (shape == 11) return launch_plain<EPI, 11>(p, plan, stream);
+    if (shape == 3) return launch_plain<EPI, 3>(p, plan, stream);
+    if (shape == 2) return launch_plain<EPI, 2>(p, plan, stream);
+    if (shape == 7) {
 #ifndef GTAV_EXPERIMENTS
         if constexpr (EPI == EPI_QKV) {   // 15 spilled registers and never selected by the heuristic
             GTAV_REQUIRE(false, "gemm: the 256 x 256 tile has no QKV epilogue in the product build");
         } else
 #endif
-        if constexpr (!FOLDISH) {
-            set_gn(256, 256);
-            // A narrow output with far more activations than weights (the VAE's fc2 at M = 46 080: X 377 MB, W 8 MB): keep ALL n-tiles of an m-tile on one XCD,
-            // beyond choose_gn's 2 MiB cap — X then crosses the fabric once and W, which stays in the Infinity Cache, is what gets re-read: 1.94 GB -> less per
-            // launch by the PMC counters (profiles/traffic.json vae_fc2), 426 -> 408 us (profiles/round5/gemm_tile_group_width_large_M.txt)
-            if (!g_force_gn && splitk == 1 && p.N <= 1024 && (size_t)p.M >= 8 * (size_t)p.N) p.tm.gn = cdiv(p.N, 256);
-            const dim3 grid(cdiv(p.M, 256) * cdiv(p.N, 256) * splitk);
-            GEMM_LAUNCH((gemm256_kernel<EPI>), grid, dim3(512));
-        }
-    } else if (shape == 3) {
-        set_gn(128, TN);
-        const dim3 grid(cdiv(p.M, 128) * cdiv(p.N, TN) * splitk);
-        if (ns <= 2) GEMM_LAUNCH((gemm_kernel<EPI, 2, 4, 2>), grid, dim3(512));
-        else GEMM_LAUNCH((gemm_kernel<EPI, 4, 4, 2>), grid, dim3(512));
-    } else {
-        GTAV_REQUIRE(shape == 2, "gemm: unknown block shape %d", shape);
-        set_gn(128, TN);
-        const dim3 grid(cdiv(p.M, 128) * cdiv(p.N, TN) * splitk);
-        if (ns <= 2) GEMM_LAUNCH((gemm_kernel<EPI, 2, 2, 4>), grid, dim3(256));
-        else GEMM_LAUNCH((gemm_kernel<EPI, 4, 2, 4>), grid, dim3(256));
+        if constexpr (!FOLDISH) return launch_plain<EPI, 7>(p, plan, stream);
     }
-    GTAV_CHECK_HIP(hipGetLastError());
+#ifdef GTAV_EXPERIMENTS
+    return launch_experiment_shape<EPI>(p, plan, stream);   // the shapes the product's planner refuses: gemm_experiments.inc
+#endif
+    GTAV_REQUIRE(false, "gemm: block shape %d has no kernel for epilogue %d", shape, (int)EPI);
     return 0;
 }
 
@@ -2916,21 +2806,11 @@ int launch_gemm_qkvt_attn(const GemmParams& p_in, hipStream_t stream) {
     GTAV_REQUIRE(q.N == 3 * q.D && q.K % TK == 0 && q.k && q.out && q.rope_cs && q.Tmax >= q.Tq, "gemm/qkvt_attn: missing buffers");
     GTAV_REQUIRE(((uintptr_t)q.X & 15) == 0 && ((uintptr_t)q.W & 15) == 0, "gemm: operands must be 16-byte aligned");
     constexpr int NS = 4, LDS = NS * 34 * 1024;
-    static unsigned long long attr_devs = 0;
-    int dev = 0;
-    GTAV_REQUIRE(device_cus(&dev) > 0, "gemm: no current device");
-    if (!(attr_devs >> (dev & 63) & 1)) {
-        GTAV_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_qkvt_attn_kernel<NS>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        attr_devs |= 1ull << (dev & 63);
-    }
-#ifdef GTAV_EXPERIMENTS
-    q.debug = g_debug & (3 | 32 | 512);
-    q.stamps = g_stamps;
-#endif
+    if (int rc_ = lds_opt_in<gemm_qkvt_attn_kernel<NS>>(LDS)) return rc_;
+    lab_fields(q, 3 | 32 | 512);
     q.out_sc1 = 1;
     q.splitk = 1;
-    if (g_force_wfill) q.wfill = 1;
-    if (int rc_ = fill_tile_map(q.tm, q.M, q.N, q.K, 80, 192, 1)) return rc_;
+    if (int rc_ = fill_tile_map(q.tm, q.M, q.N, 80, 192, 1, gemm_choose_gn(q.M, q.N, q.K, 80, 192, 1))) return rc_;
     GTAV_LAUNCH((gemm_qkvt_attn_kernel<NS>), dim3(q.tm.tiles), dim3(512), LDS, stream, GTAV_HEAD_VALUES(q), q);
     GTAV_CHECK_HIP(hipGetLastError());
     return 0;
@@ -2949,21 +2829,11 @@ int launch_gemm_qkvs_attn(const GemmParams& p_in, hipStream_t stream) {
     GTAV_REQUIRE(q.N == 3 * q.D && q.K % TK == 0 && q.out && q.rope_cs && !q.rope_cs_q && !q.bias, "gemm/qkvs_attn: missing buffers (or a bias / a separate q table)");
     GTAV_REQUIRE(((uintptr_t)q.X & 15) == 0 && ((uintptr_t)q.W & 15) == 0, "gemm: operands must be 16-byte aligned");
     constexpr int NS = 3, LDS = NS * 44 * 1024;
-    static unsigned long long attr_devs = 0;
-    int dev = 0;
-    GTAV_REQUIRE(device_cus(&dev) > 0, "gemm: no current device");
-    if (!(attr_devs >> (dev & 63) & 1)) {
-        GTAV_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_qkvs_attn_kernel<NS>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        attr_devs |= 1ull << (dev & 63);
-    }
-#ifdef GTAV_EXPERIMENTS
-    q.debug = g_debug & (3 | 32 | 64);
-    q.stamps = g_stamps;
-#endif
+    if (int rc_ = lds_opt_in<gemm_qkvs_attn_kernel<NS>>(LDS)) return rc_;
+    lab_fields(q, 3 | 32 | 64);
     q.splitk = 1;
-    if (g_force_wfill) q.wfill = 1;
     q.qkv_mode = QKV_SPATIAL;
-    if (int rc_ = fill_tile_map(q.tm, q.M, q.N, q.K, 144, 192, 1)) return rc_;
+    if (int rc_ = fill_tile_map(q.tm, q.M, q.N, 144, 192, 1, gemm_choose_gn(q.M, q.N, q.K, 144, 192, 1))) return rc_;
     // (Two blocks per (frame, head) on grids of at most half the chip — both run the whole projection, each walks half of the query tiles in one round of its eight
     // waves — was measured and is not kept: 19.2 -> 19.4 us at 80 blocks, 19.8 -> 20.9 at 128.)
     GTAV_LAUNCH((gemm_qkvs_attn_kernel<NS>), dim3(q.tm.tiles), dim3(768), LDS, stream, GTAV_HEAD_VALUES(q), q);
@@ -2981,13 +2851,10 @@ int launch_gemm_tn(const GemmParams& p_in, hipStream_t stream) {
     GTAV_REQUIRE(gemm_tn_ok(p.M, p.N, p.K), "gemm_tn: M=%d, N=%d must be multiples of 128 and K=%d of 64", p.M, p.N, p.K);
     GTAV_REQUIRE(p.out && p.ldo >= p.N && p.ldo % 4 == 0, "gemm_tn: bad output ldo=%d", p.ldo);
     GTAV_REQUIRE(((uintptr_t)p.X & 15) == 0 && ((uintptr_t)p.W & 15) == 0, "gemm_tn: operands must be 16-byte aligned");
-#ifdef GTAV_EXPERIMENTS
-    p.debug = 0;
-    p.stamps = g_stamps;
-#endif
+    lab_fields(p, 0);
     p.splitk = 1;
     p.bias = nullptr; p.gate = nullptr;
-    p.tm.gn = choose_gn(p.M, p.N, p.K, 128, 128, 1);
+    p.tm.gn = gemm_choose_gn(p.M, p.N, p.K, 128, 128, 1);
     const dim3 grid((p.M / 128) * (p.N / 128));
     GTAV_LAUNCH((gemm_tn_kernel<4>), grid, dim3(512), 0, stream, p);
     GTAV_CHECK_HIP(hipGetLastError());
@@ -3024,9 +2891,7 @@ int launch_gemm_dw_grouped(const GemmDwGroup* g, int n, int K, int* err_flag, hi
     GemmParams p;
     memset(&p, 0, sizeof(p));
     p.K = K; p.splitk = 1; p.err_flag = err_flag; p.rows_per_gate = 1;
-#ifdef GTAV_EXPERIMENTS
-    p.stamps = g_stamps;
-#endif
+    lab_fields(p, 0);
     if (tn) {   // operands tile-major [tokens][features]: K tokens in whole 128-row tiles (the pad rows of a ragged last tile are not zero)
         GTAV_REQUIRE(K % 128 == 0, "gemm_dw_grouped: the transpose-free form contracts over whole 128-token row tiles (K=%d)", K);
         GTAV_LAUNCH(gemm256_dw_grouped_kernel<true>, dim3(gs.first[n]), dim3(512), 0, stream, p, gs);
@@ -3065,24 +2930,10 @@ int launch_gemm(const GemmParams& p_in, int epi_x, hipStream_t stream) {
                          "gemm/fold: producer needs gate, next scale, statistics and operand buffers, N %% 64 == 0");
         }
     }
-    p.debug = g_debug & (3 | 16 | 32 | 2048 | 8192 | 16384 | 0x1F0000);   // 0x10000.. : pieces of the fold producer epilogue off (timing, experiments build)   // bit 4: direct (unstaged) QKV epilogue; bit 5 (experiments): per-K-step stamps of the loader-wave kernels
-    p.stamps = nullptr;
-#ifdef GTAV_EXPERIMENTS
-    p.stamps = g_stamps;            // the tool sizes the buffer for the largest grid it launches (g_stamp_blocks)
-#endif
-    // The 16-byte output stores of the split-K slabs, the tile-major GELU output and the staged QKV epilogue go out
-    // write-through-and-drop (sc1): nothing is left dirty in L2 for the end-of-kernel write-back, and the output does not
-    // evict operand tiles.  Measured in situ at B = 1 (every GEMM class 3-9 % shorter, consumers unchanged: 3.94 -> 4.10
-    // frames/s) and back-to-back (profiles/round1/v13_gemm_sc1_stores_microbench.txt).  8-byte sc1 stores are SLOWER (one
-    // fabric write each), so the unstaged epilogues keep plain stores.  Debug bit 3 turns it off (experiments).
-    p.out_sc1 = (g_debug & 8) ? 0 : 1;
-    if (g_force_wfill) p.wfill = 1;
     GTAV_REQUIRE(prefetch_desc_ok(p.pf), "gemm: bad prefetch descriptor (row tiles %d, K tiles %d, K slices %d)", p.pf.rt, p.pf.nkt, p.pf.splitk);
-    if (g_debug & 0x800000) p.pf.next = nullptr;   // experiments build: A/B
     GTAV_REQUIRE(p.K > 0 && p.K % TK == 0, "gemm: K=%d must be a positive multiple of %d", p.K, TK);
     GTAV_REQUIRE(p.M > 0 && p.N > 0 && p.N % 4 == 0, "gemm: bad M=%d N=%d", p.M, p.N);
     GTAV_REQUIRE(((uintptr_t)p.X & 15) == 0 && ((uintptr_t)p.W & 15) == 0, "gemm: operands must be 16-byte aligned");
-    int splitk = 1;
     if (epi == EPI_QKV) {
         GTAV_REQUIRE(p.N == 3 * p.D && p.D % 128 == 0, "gemm/qkv: N=%d must equal 3*D, D=%d %% 128 == 0", p.N, p.D);
         GTAV_REQUIRE(p.S > 0 && p.q && p.k && p.rope_cs, "gemm/qkv: missing buffers");
@@ -3096,118 +2947,45 @@ int launch_gemm(const GemmParams& p_in, int epi_x, hipStream_t stream) {
         if (epi == EPI_RESID && p.gate) GTAV_REQUIRE(p.rows_per_gate > 0, "gemm/resid: rows_per_gate");
         if (epi == EPI_GELU_TANH || epi == EPI_GELU_ERF || epi == EPI_F16_TILED) GTAV_REQUIRE(p.ldo % 64 == 0, "gemm/gelu: tile-major output needs ldo %% 64 == 0");
         if (fold_p) GTAV_REQUIRE(p.splitk <= 1, "gemm/fold: the producer epilogue needs the complete sum (no split-K)");
-        if (epi == EPI_PARTIAL) {
-            splitk = p.splitk;
-            GTAV_REQUIRE(splitk >= 1 && (p.K / TK) % splitk == 0, "gemm/partial: splitk=%d must divide K/64=%d", splitk, p.K / TK);
-        }
+        if (epi == EPI_PARTIAL) GTAV_REQUIRE(p.splitk >= 1 && (p.K / TK) % p.splitk == 0, "gemm/partial: splitk=%d must divide K/64=%d", p.splitk, p.K / TK);
     }
-    // Block shape (measured, profiles/round1/v6_gemm_shapes_microbench.txt):
-    //   grid < 256 blocks of 128 x 128 (one block per CU at most): 8 waves per block (two staggered waves per SIMD),
-    //     4-stage ring — 17-25 % faster than 4 waves at M = 720;
-    //   larger grids: 4 waves, 2-stage ring, two co-resident blocks per CU; the 128 x 256 / 8-wave tile (shape 4) ties it.
-    const int blocks128 = cdiv(p.M, 128) * cdiv(p.N, TN) * splitk;
-    const bool foldish = fold_c || fold_p;
-    int wm = g_force_wm ? g_force_wm : (blocks128 <= 256 ? 3 : 2);
-    if (!g_force_wm && blocks128 <= 256) {
-        // small M: every block is bound by its own L2->LDS fill (~65 GB/s per CU), i.e. by (TN + TM) x K bytes, and the grid
-        // by how many of the 256 CUs it covers.  Candidates: 128 x 128 (shape 3), 128 x 96 (shape 9), 96 x 96 (shape 8).
-        auto cost = [&](int tn, int tm) { return cdiv(cdiv(p.M, tm) * cdiv(p.N, tn) * splitk, 256) * (tn + tm); };
-        int best = cost(128, 128);
-        if (cost(128, 96) < best) best = cost(128, 96), wm = 9;
-        const bool ok96 = p.N % 96 == 0 && epi != EPI_GELU_TANH && epi != EPI_GELU_ERF && epi != EPI_F16_TILED && !(epi == EPI_QKV && p.qkv_mode == QKV_SPATIAL);
-        if (ok96 && cost(96, 96) < best) best = cost(96, 96), wm = 8;
-        // skinny M (M = 144: the context-cached sampler step): 64 x 48 tiles put 144-192 blocks of 224 KB where the
-        // 128 x 96 grid has 48-64 blocks of 448 KB
-        if (cost(64, 96) < best) best = cost(64, 96), wm = 14;   // M = 288-320 (g256 window step, batch-2 cached step)
-        if (cost(64, 48) < best) best = cost(64, 48), wm = 11;
-    }
-    // Round 2: the 128 x 96 tile runs on the loader-wave kernel (shape 20: 4 loader + 8 compute waves, fills and MFMAs overlap by
-    // construction): QKV 14.1 -> 10.7 us, fc1 13.3 -> 10.9, fc2 12.0 -> 10.2, out-proj 6.6 -> 6.1 at M = 720 (profiles/round2).
-    if (!g_force_wm && !(g_debug & 64) && (wm == 9 || (wm == 8 && g_l_for_8))) wm = (g_debug & 128) ? 25 : 20;   // debug bit 6 (experiments build): round-1 shapes, for A/B runs in one process
-#ifdef GTAV_EXPERIMENTS
-    // round 6 A/B (debug bit 24): the 128 x 96 loader-wave tile with the weight operand straight into registers (shape 22) wherever the heuristic picks shape 20
-    if (!g_force_wm && wm == 20 && (g_debug & 0x1000000) && !foldish && (p.K / TK / (splitk > 0 ? splitk : 1)) % 4 == 0) wm = 22;
-    if (!g_force_wm && wm == 20 && (g_debug & 0x2000000) && !foldish && (p.K / TK / (splitk > 0 ? splitk : 1)) % 8 == 0) wm = 18;   // debug bit 25: shape 18
-#endif
-    // Round 3: the skinny tiles on the loader-wave kernel too (6 compute + 2 loader waves): M = 144 QKV 8.45 -> 7.34 us, fc1 7.75 -> 6.83, out-proj 5.00 -> 4.68;
-    // M = 288 QKV 10.3 -> 8.4, fc1 9.7 -> 8.4 (profiles/round3/skinny_loader_wave_shapes_M144_M288.txt); their compute waves carry the next-weight L2 prefetch.
-    // The 8-slice fc2 at M = 288 stays on the all-waves-fill kernel (7.4 against 8.3 us).
-    if (!g_force_wm && !(g_debug & 64)) {
-        if (wm == 11) wm = 24;
-        else if (wm == 14 && !(epi_x == EPI_PARTIAL && splitk >= 8)) wm = 26;
-    }
-    // Round 4: a little over a thousand tokens (M = 1152: the context-cached step at batch 8) sits between the small-M tiles (128 x 96: 12 row tiles, 1.1-1.5
-    // rounds of one-block-per-CU tiles) and the large-M ones (128 x 128, two blocks per CU: 216-288 blocks on 512 slots).  128 x 144 tiles on the loader-wave
-    // kernel (shape 29) are one round there: to_qkv 192, fc1 256, four-slice fc2 256 tiles (profiles/round4/step_B8_cached_*.json: to_qkv 14.9, fc1 18.5, fc2 19.7 us before).
-    bool frame_tile = false;
-    if (!g_force_wm && !foldish && !(g_debug & 64)) {
-        const int t29 = cdiv(p.M, 144) * cdiv(p.N, 128) * splitk, t20 = cdiv(p.M, 96) * cdiv(p.N, 128) * splitk;
-        if (t29 > 128 && t29 <= 256 && t20 > 256 && blocks128 <= 320) wm = 29, frame_tile = true;
-    }
-    if (!g_force_wm && wm == 2 && cdiv(p.M, 192) * cdiv(p.N, 128) * splitk >= 320) {
-        // large M: 128 x 192 tiles (4 waves of 64 x 96, still two blocks per CU) move 17 % fewer fill bytes per FLOP than
-        // 128 x 128: QKV 62.6 -> 55.5 us, fc1 63.8 -> 61.1 us at M = 5760 (profiles/round1/v17_gemm_128x192_microbench.txt);
-        // below ~320 tiles the 512 block slots are too unevenly filled (fc2 at M = 5760: 240 tiles, 65.7 -> 73.1 us).
-        wm = 12;   // 8 waves of 64 x 48 (four per SIMD with the co-resident block): QKV 60.3 -> 54.8, fc1 62.1 -> 59.4 vs the 4-wave form (shape 10)
-    }
-    // Narrow outputs (the N = 1024 residual GEMMs) at a few thousand tokens: both two-blocks-per-CU tiles, 128 x 192 (shape 12) and 128 x 96
-    // (shape 13), run a grid that FILLS the 512 block slots once faster than 128 x 128 runs 360-720 blocks: out-proj at M = 5760 20.6 -> 16.8 us
-    // (shape 13: 480 tiles), at M = 11 520 33.4 -> 30.8 us and fc2 97.6 -> 90.2 us (shape 12: 480 tiles; the 256 x 256 tile lost to it),
-    // M = 2880 out-proj 13.7 -> 11.4 us, fc2 34.6 -> 27.9 us (shape 13, two K slices) — profiles/round3/gemm_shapes_*.txt.  The LayerNorm-fold
-    // producer takes the larger tile whenever its grid is more than half full (27.2 us against 33.5 us at M = 5760).
-    bool narrow_pick = false;
-    if (!g_force_wm && !frame_tile && blocks128 > 256 && p.N <= 2048 && epi != EPI_QKV) {
-        const int t12 = cdiv(p.M, 192) * cdiv(p.N, 128) * splitk, t13 = cdiv(p.M, 96) * cdiv(p.N, 128) * splitk;
-        if (t12 > 256 && t12 <= 512) wm = 12, narrow_pick = true;
-        else if (t13 > 256 && t13 <= 512 && !fold_p) wm = 13, narrow_pick = true;
-        else if (fold_p && t12 > 128) wm = 12, narrow_pick = true;
-    }
-    if (!g_force_wm && splitk == 1 && ((epi_x == EPI_PARTIAL && lp_takes(p.M, p.N, p.K)) || (epi_x == EPI_RESID && gemm_resid_inplace_ok(p.M, p.N, p.K, p.gate ? p.rows_per_gate : 0)))) wm = 31, narrow_pick = true;
-    // Tens of thousands of tokens (the VAE encode of a training batch: M = 46 080): the in-place residual GEMMs on whole rounds of 256 x 256 tiles
-    // (>= 2 rounds, >= 90 % full) beat the persistent 128 x 192 kernel — fc2 453 -> 399 us, attention projection 182 -> 164 us back to back
-    // (profiles/round5/gemm_vae_shapes_M23040_M46080.txt); at M = 23 040 (1.4 rounds) they lose (240 against 223 us) and shape 31 stays
-    if (!g_force_wm && wm == 31 && epi_x == EPI_RESID && p.N % 256 == 0 && p.N <= 1024 && p.K >= 1024) {
-        const int t256 = cdiv(p.M, 256) * (p.N / 256), rounds = cdiv(t256, 256);
-        if (rounds >= 2 && t256 * 10 >= rounds * 256 * 9) wm = 7;
-    }
-#ifdef GTAV_EXPERIMENTS
-    if (!g_force_wm && epi_x == EPI_GELU_TANH && (g_debug & 0x600000) && cdiv(p.M, 128) * cdiv(p.N, 256) >= 512) wm = (g_debug & 0x200000) ? 33 : 32;   // A/B of the persistent 128 x 256 / 256 x 128 tiles for fc1 (debug bits 21 / 22)
-#endif
-    // large M: the persistent ping-pong kernel (epilogue and next tile's prologue under the other wave group's MFMAs)
-    if (!g_force_wm && splitk == 1 && gemm_pp_ok(p.M, p.N, p.K, epi) && !(epi == EPI_QKV && p.qkv_mode == QKV_SPATIAL && p.S % 8 != 0)) wm = 16;
-    GTAV_REQUIRE(!(wm == 8 && epi == EPI_QKV && p.qkv_mode == QKV_SPATIAL), "gemm: 96-feature tiles straddle the K / V boundary (spatial QKV)");
-    // 256 x 256 tiles (shape 7) halve the fill bytes per FLOP but run one block per CU, so a tile's epilogue (a 32 MB
-    // store burst per round of 256 tiles) is not hidden by a co-resident block: they win only where the K loop is long
-    // relative to the output and the grid is one well-filled round — the N = 1024 residual GEMMs at M >= 11 520
-    // (profiles/round1/v12_gemm_256tile_microbench.txt: fc2 129 -> 98 us, out-proj 40 -> 35 us).
-    if (!g_force_wm && splitk == 1 && epi != EPI_QKV && !foldish && !narrow_pick && p.N % 256 == 0 && p.N <= 1024 && p.K >= 1024) {
-        const int t256 = cdiv(p.M, 256) * (p.N / 256), rounds = cdiv(t256, 256);
-        if (t256 * 10 >= rounds * 256 * 7) wm = 7;
-    }
-    int ns = g_force_stages ? g_force_stages : ((wm == 12 || wm == 13) ? 2 : wm >= 8 ? 4 : wm == 3 ? 4 : 2);   // (shapes 20+ carry their ring depth in the template)
+    // ---- which block shape, how many K slices, which tile-group width: the planner (gemm_plan.hip holds the measured rules) ----
+    GemmPlan plan;
+    if (int rc_ = gemm_plan(GemmProblem{p.M, p.N, p.K, epi_x, p.qkv_mode, p.S, p.splitk, p.gate ? p.rows_per_gate : 0}, &plan)) return rc_;
     // a wave's token span (16 FJ) must not exceed a frame: the skinny 64 x 48 / 64 x 96 tiles span 16 / 32 tokens, the others 48-64
-    if (foldish) {
-        const int span = wm == 2 ? 64 : (wm == 3 || wm == 14 || wm == 26) ? 32 : (wm == 11 || wm == 24) ? 16 : 48;   // (12, 13, 20: 48)
-        GTAV_REQUIRE(p.f_P >= span, "gemm/fold: frames of %d tokens are shorter than the token span (%d) of a wave of block shape %d", p.f_P, span, wm);
+    if (fold_c || fold_p) {
+        const int span = gemm_shape(plan.shape)->span();
+        GTAV_REQUIRE(p.f_P >= span, "gemm/fold: frames of %d tokens are shorter than the token span (%d) of a wave of block shape %d", p.f_P, span, plan.shape);
     }
+    // ---- what the kernels read besides the caller's arguments ----
+    const int dbg = gemm_debug();
+    p.tm.gn = plan.gn;
+    lab_fields(p, 3 | 16 | 32 | 2048 | 8192 | 16384 | 0x1F0000);   // 0x10000.. : pieces of the fold producer epilogue off (timing, experiments build)   // bit 4: direct (unstaged) QKV epilogue; bit 5 (experiments): per-K-step stamps of the loader-wave kernels
+    // The 16-byte output stores of the split-K slabs, the tile-major GELU output and the staged QKV epilogue go out
+    // write-through-and-drop (sc1): nothing is left dirty in L2 for the end-of-kernel write-back, and the output does not
+    // evict operand tiles.  Measured in situ at B = 1 (every GEMM class 3-9 % shorter, consumers unchanged: 3.94 -> 4.10
+    // frames/s) and back-to-back (profiles/round1/v13_gemm_sc1_stores_microbench.txt).  8-byte sc1 stores are SLOWER (one
+    // fabric write each), so the unstaged epilogues keep plain stores.  Debug bit 3 turns it off (experiments).
+    p.out_sc1 = (dbg & 8) ? 0 : 1;
+    if (dbg & 0x800000) p.pf.next = nullptr;   // experiments build: A/B
     switch (epi_x) {
 #ifdef GTAV_EXPERIMENTS   // the LayerNorm fold (round 3: correct, measured slower at every size) is compiled into the experiments build only
-        case EPI_RESID_FOLD: return launch_epi<EPI_RESID_FOLD>(p, ns, wm, splitk, stream);
-        case EPI_QKV_FOLD: return launch_epi<EPI_QKV_FOLD>(p, ns, wm, splitk, stream);
-        case EPI_GELU_TANH_FOLD: return launch_epi<EPI_GELU_TANH_FOLD>(p, ns, wm, splitk, stream);
-        case EPI_F32_FOLD: return launch_epi<EPI_F32_FOLD>(p, ns, wm, splitk, stream);
+        case EPI_RESID_FOLD: return launch_epi<EPI_RESID_FOLD>(p, plan, stream);
+        case EPI_QKV_FOLD: return launch_epi<EPI_QKV_FOLD>(p, plan, stream);
+        case EPI_GELU_TANH_FOLD: return launch_epi<EPI_GELU_TANH_FOLD>(p, plan, stream);
+        case EPI_F32_FOLD: return launch_epi<EPI_F32_FOLD>(p, plan, stream);
 #else
         case EPI_RESID_FOLD: case EPI_QKV_FOLD: case EPI_GELU_TANH_FOLD: case EPI_F32_FOLD:
             GTAV_REQUIRE(false, "gemm: the LayerNorm-fold epilogues exist only in the experiments build (csrc/build.sh exp)");
 #endif
-        case EPI_F32: return launch_epi<EPI_F32>(p, ns, wm, splitk, stream);
-        case EPI_F16: return launch_epi<EPI_F16>(p, ns, wm, splitk, stream);
-        case EPI_GELU_TANH: return launch_epi<EPI_GELU_TANH>(p, ns, wm, splitk, stream);
-        case EPI_GELU_ERF: return launch_epi<EPI_GELU_ERF>(p, ns, wm, splitk, stream);
-        case EPI_RESID: return launch_epi<EPI_RESID>(p, ns, wm, splitk, stream);
-        case EPI_QKV: return launch_epi<EPI_QKV>(p, ns, wm, splitk, stream);
-        case EPI_PARTIAL: return launch_epi<EPI_PARTIAL>(p, ns, wm, splitk, stream);
-        case EPI_F16_TILED: return launch_epi<EPI_F16_TILED>(p, ns, wm, splitk, stream);
+        case EPI_F32: return launch_epi<EPI_F32>(p, plan, stream);
+        case EPI_F16: return launch_epi<EPI_F16>(p, plan, stream);
+        case EPI_GELU_TANH: return launch_epi<EPI_GELU_TANH>(p, plan, stream);
+        case EPI_GELU_ERF: return launch_epi<EPI_GELU_ERF>(p, plan, stream);
+        case EPI_RESID: return launch_epi<EPI_RESID>(p, plan, stream);
+        case EPI_QKV: return launch_epi<EPI_QKV>(p, plan, stream);
+        case EPI_PARTIAL: return launch_epi<EPI_PARTIAL>(p, plan, stream);
+        case EPI_F16_TILED: return launch_epi<EPI_F16_TILED>(p, plan, stream);
         default: GTAV_REQUIRE(false, "gemm: unknown epilogue %d", epi_x);
     }
     return 0;

@@ -446,7 +446,7 @@ __device__ __forceinline__ void pp_tile_of(const GemmParams& p, int v, int tiles
     const int T = tiles_m * tiles_n;
     const int xcd = v & 7, qq = T >> 3, rr = T & 7;
     const int tile_id = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (v >> 3);
-    int gn = p.tm.gn;                                      // host: choose_gn() (every launcher fills it)
+    int gn = p.tm.gn;                                      // host: gemm_choose_gn() (every launcher fills it)
     const int group = tiles_m * gn;
     const int ng = tile_id / group, rem = tile_id - ng * group;
     const int n_first = ng * gn;
@@ -740,30 +740,12 @@ __global__ __launch_bounds__(1024, 1) void gemm_pp_kernel(GemmParams p) {
 
 } // namespace
 // ---- launcher of the ping-pong kernel ----
-// Round-2 measurement (profiles/round2/pp_stamps_v1.txt): correct and bit-identical to the one-shot kernels, the overlap works (MAIN
-// phases run back to back), but with only 8 of the 16 waves computing, a K-step costs 1.15-1.25 us against 0.68 us of fill time: the
-// barrier-synchronised waves serialise into fill / read / MFMA phases, where two independent co-resident blocks interleave them.
-// fc1 at M = 5760: 71-76 us against 57 us for shape 12.  Not selected by the heuristic (GTAV_PP=1 in the experiments build or a
-// forced shape 16 run it); the de-phased shape 12 above gets the same overlap with 16 computing waves.
-static int g_pp_enable = GTAV_ENV_INT("GTAV_PP", 0);
-bool gemm_pp_ok(int M, int N, int K, int epi) {
-    if (!(epi == EPI_GELU_TANH || epi == EPI_GELU_ERF || epi == EPI_QKV || epi == EPI_RESID)) return false;
-    if (K % TK != 0 || K / TK < 14 || M % 8 != 0 || N % 8 != 0) return false;
-    // worth it when most CUs get a tile and, beyond one tile per CU, the epilogue of one tile hides under the next tile's main
-    // loop (otherwise the one-shot kernels with smaller tiles cover the chip better)
-    return g_pp_enable && cdiv(M, PP_TM) * cdiv(N, PP_TN) >= 224;
-}
+// (what it measured, and gemm_pp_ok: gemm_plan.hip)
 template <int EPI>
 static int launch_pp(const GemmParams& p, hipStream_t stream) {
     constexpr int NS = 3;
-    static unsigned long long attr_devs = 0;   // per instantiation, per device (hipFuncSetAttribute is a per-device setting)
-    int dev = 0;
-    const int cus = device_cus(&dev);
-    GTAV_REQUIRE(cus > 0, "gemm: no current device");
-    if (!(attr_devs >> (dev & 63) & 1)) {
-        GTAV_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_pp_kernel<EPI, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, NS * PP_STAGE));
-        attr_devs |= 1ull << (dev & 63);
-    }
+    int cus = 0;
+    if (int rc_ = lds_opt_in<gemm_pp_kernel<EPI, NS>>(NS * PP_STAGE, &cus)) return rc_;
     const int T = cdiv(p.M, PP_TM) * cdiv(p.N, PP_TN);
     const dim3 grid(T < cus ? T : cus);
     GemmParams q = p;
@@ -1062,33 +1044,32 @@ __global__ __launch_bounds__(1024, 1) void gemm_s16_kernel(GemmParams p) {
     if constexpr (EPI == EPI_GELU_TANH || EPI == EPI_F16_TILED) sat_report(amax, p.err_flag);
 }
 
+// The persistent 256-token-tile kernels (shapes 40 / 41 / 42): whole rounds of the T tiles + a two-way K split of a remainder of <= grid / 2 tiles (q.sk_dp / q.sk_r)
+static int p256_units(GemmParams& q, int T, int cus, int* grid) {
+    GTAV_REQUIRE((size_t)round_up(q.M, 128) * q.K * 2 < (1ull << 32) && (size_t)round_up(q.N, 128) * q.K * 2 < (1ull << 32),
+                 "gemm: the persistent 256-token-tile kernels address their operands with 32-bit offsets (M=%d N=%d K=%d)", q.M, q.N, q.K);
+    GTAV_REQUIRE(cdiv(T, cus) + 1 <= P256_MAXU, "gemm: %d tiles are more than %d rounds of the persistent 256-token-tile kernel", T, P256_MAXU - 1);
+    const int full = T / cus, rem = T - full * cus;
+    *grid = T < cus ? T : cus;
+    q.sk_dp = T;
+    q.sk_r = 0;
+    if (rem > 0 && 2 * rem <= cus && rem <= GEMM_SK_MAX_SPLIT && q.sk_ws && q.sk_flags && q.K / TK >= 4) {
+        q.sk_dp = T - rem;
+        q.sk_r = rem;
+        if (full == 0) *grid = 2 * rem;
+    }
+    return 0;
+}
+
 template <int EPI>
 static int launch_s16(const GemmParams& p, hipStream_t stream) {
     using C = S16;
-    static unsigned long long attr_devs = 0;
-    int dev = 0;
-    const int cus = device_cus(&dev);
-    GTAV_REQUIRE(cus > 0, "gemm: no current device");
-    if (!(attr_devs >> (dev & 63) & 1)) {
-        GTAV_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_s16_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
-        attr_devs |= 1ull << (dev & 63);
-    }
+    int cus = 0;
+    if (int rc_ = lds_opt_in<gemm_s16_kernel<EPI>>(C::LDS, &cus)) return rc_;
     GemmParams q = p;
-    GTAV_REQUIRE((size_t)round_up(p.M, 128) * p.K * 2 < (1ull << 32) && (size_t)round_up(p.N, 128) * p.K * 2 < (1ull << 32),
-                 "gemm: the persistent 256-token-tile kernels address their operands with 32-bit offsets (M=%d N=%d K=%d)", p.M, p.N, p.K);
     GTAV_REQUIRE((size_t)round_up(p.M, 128) * (size_t)p.ldo * 4 < (1ull << 32), "gemm: the sixteen-wave persistent kernel addresses its output with 32-bit offsets (M=%d ldo=%d)", p.M, p.ldo);
-    const int T = cdiv(p.M, 256) * cdiv(p.N, 256), nkt = p.K / TK;
-    GTAV_REQUIRE(cdiv(T, cus) + 1 <= P256_MAXU, "gemm: %d tiles are more than %d rounds of the persistent 256-token-tile kernel", T, P256_MAXU - 1);
-    const int full = T / cus, rem = T - full * cus;
-    int grid = T < cus ? T : cus;
-    q.sk_dp = T;
-    q.sk_r = 0;
-    if (rem > 0 && 2 * rem <= cus && rem <= GEMM_SK_MAX_SPLIT && q.sk_ws && q.sk_flags && nkt >= 4) {
-        q.sk_dp = T - rem;
-        q.sk_r = rem;
-        if (full == 0) grid = 2 * rem;
-    }
-    q.tm.gn = choose_gn(p.M, p.N, p.K, 256, 256, 1);
+    int grid = 0;
+    if (int rc_ = p256_units(q, cdiv(p.M, 256) * cdiv(p.N, 256), cus, &grid)) return rc_;
     GTAV_LAUNCH((gemm_s16_kernel<EPI>), dim3(grid), dim3(1024), C::LDS, stream, q);
     GTAV_CHECK_HIP(hipGetLastError());
     return 0;
@@ -1501,25 +1482,21 @@ __global__ __launch_bounds__(64 * (WN * WM + NL), 1) void gemm_lw_kernel(GemmPar
 }
 
 // loader-wave kernel with the weight operand straight into registers (shape 22): dynamic LDS = the X ring, or the epilogue's image if that is larger
-template <int EPI, int NS, int FI, int FJ, int WN, int WM, int NL, int D>
+template <int EPI, int SHAPE, int D>
 static int launch_lw(const GemmParams& p, int splitk, hipStream_t stream) {
-    constexpr int TNB = 16 * FI * WN, TM = 16 * FJ * WM;
+    constexpr GemmShape R = *gemm_shape(SHAPE);
+    static_assert(R.family == GF_LW, "gemm_lw_kernel");
+    constexpr int NS = R.ns, FI = R.fi, FJ = R.fj, WN = R.wn, WM = R.wm, NL = R.nl, TNB = R.features(), TM = R.tokens();
     constexpr int RING = NS * 2 * FJ * WM * 1024;
     constexpr int PNB = (TNB / 8 + 7) / 8 * 8 * 16, PTB = (TM / 8 + 7) / 8 * 8 * 16;
     constexpr int EPIB = (TM * PNB > TNB * PTB ? TM * PNB : TNB * PTB) + TM * 8;      // qkv_staged's pitched image + token table (gemm_l_kernel)
     constexpr int GELUB = (TNB / 64 > 0 ? TNB / 64 : 1) * TM * 128;                     // the tile-major GELU image
     constexpr int LDS = RING > EPIB ? (RING > GELUB ? RING : GELUB) : (EPIB > GELUB ? EPIB : GELUB);
-    static unsigned long long attr_devs = 0;
-    int dev = 0;
-    GTAV_REQUIRE(device_cus(&dev) > 0, "gemm: no current device");
-    if (!(attr_devs >> (dev & 63) & 1)) {
-        GTAV_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_lw_kernel<EPI, NS, FI, FJ, WN, WM, NL, D>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        attr_devs |= 1ull << (dev & 63);
-    }
+    if (int rc_ = lds_opt_in<gemm_lw_kernel<EPI, NS, FI, FJ, WN, WM, NL, D>>(LDS)) return rc_;
     GemmParams q = p;
-    if (int rc_ = fill_tile_map(q.tm, p.M, p.N, p.K, TM, TNB, splitk)) return rc_;
+    if (int rc_ = fill_tile_map(q.tm, p.M, p.N, TM, TNB, splitk, p.tm.gn)) return rc_;
     const dim3 grid(q.tm.tiles * splitk);
-    GTAV_LAUNCH((gemm_lw_kernel<EPI, NS, FI, FJ, WN, WM, NL, D>), grid, dim3(64 * (WN * WM + NL)), LDS, stream, q);
+    GTAV_LAUNCH((gemm_lw_kernel<EPI, NS, FI, FJ, WN, WM, NL, D>), grid, dim3(R.threads()), LDS, stream, q);
     GTAV_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -1528,113 +1505,65 @@ static int launch_lw(const GemmParams& p, int splitk, hipStream_t stream) {
 template <int EPI, int FI>
 static int launch_p256(const GemmParams& p, hipStream_t stream) {
     using C = P256<FI>;
-    static unsigned long long attr_devs = 0;
-    int dev = 0;
-    const int cus = device_cus(&dev);
-    GTAV_REQUIRE(cus > 0, "gemm: no current device");
-    if (!(attr_devs >> (dev & 63) & 1)) {
-        GTAV_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_p256_kernel<EPI, FI>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
-        attr_devs |= 1ull << (dev & 63);
-    }
+    int cus = 0;
+    if (int rc_ = lds_opt_in<gemm_p256_kernel<EPI, FI>>(C::LDS, &cus)) return rc_;
     GemmParams q = p;
-    GTAV_REQUIRE((size_t)round_up(p.M, 128) * p.K * 2 < (1ull << 32) && (size_t)round_up(p.N, 128) * p.K * 2 < (1ull << 32),
-                 "gemm: the persistent 256-token-tile kernel addresses its operands with 32-bit offsets (M=%d N=%d K=%d)", p.M, p.N, p.K);
-    const int T = cdiv(p.M, 256) * cdiv(p.N, C::TNB), nkt = p.K / TK;
-    GTAV_REQUIRE(nkt % 2 == 0, "gemm: the persistent 256-token-tile kernel walks K in pairs of K-tiles (K = %d is not a multiple of 128)", p.K);
-    GTAV_REQUIRE(cdiv(T, cus) + 1 <= P256_MAXU, "gemm: %d tiles are more than %d rounds of the persistent 256-token-tile kernel", T, P256_MAXU - 1);
-    const int full = T / cus, rem = T - full * cus;
-    int grid = T < cus ? T : cus;
-    q.sk_dp = T;
-    q.sk_r = 0;
-    if (rem > 0 && 2 * rem <= cus && rem <= GEMM_SK_MAX_SPLIT && q.sk_ws && q.sk_flags && nkt >= 4) {
-        q.sk_dp = T - rem;
-        q.sk_r = rem;
-        if (full == 0) grid = 2 * rem;
-    }
-    q.tm.gn = choose_gn(p.M, p.N, p.K, 256, C::TNB, 1);
+    GTAV_REQUIRE(p.K / TK % 2 == 0, "gemm: the persistent 256-token-tile kernel walks K in pairs of K-tiles (K = %d is not a multiple of 128)", p.K);
+    int grid = 0;
+    if (int rc_ = p256_units(q, cdiv(p.M, 256) * cdiv(p.N, C::TNB), cus, &grid)) return rc_;
     GTAV_LAUNCH((gemm_p256_kernel<EPI, FI>), dim3(grid), dim3(512), C::LDS, stream, q);
     GTAV_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
-// Block shapes of the experiments build.  `handled` = the shape was one of them (rc is the launch's status).
+// Block shapes of the experiments build (tiles, thread counts and grids: the plan / the table, gemm_plan.h): what launch_epi ends with there.
 template <int EPI>
-static int launch_experiment_shape(GemmParams& p, int ns, int shape, int splitk, hipStream_t stream, bool& handled) {
-    (void)ns;
+static int launch_experiment_shape(const GemmParams& p, const GemmPlan& plan, hipStream_t stream) {
     constexpr bool FOLDISH = EPI == EPI_RESID_FOLD || epi_is_fold_consumer(EPI);
-    auto set_gn = [&](int tmb, int tnb) { p.tm.gn = choose_gn(p.M, p.N, p.K, tmb, tnb, splitk); };
-    handled = true;
-    if (shape == 27) return launch_l<EPI, 8, 2, 1, 2, 3, 2>(p, splitk, stream);   // shape 24 with an 8-stage ring (112 KiB): seven K-steps of W in flight per CU
-    if (shape == 28) return launch_l<EPI, 8, 2, 1, 2, 3, 4>(p, splitk, stream);   // ... and four loader waves
-    if (shape == 42) {   // persistent 256 x 256 tiles on sixteen waves in two staggered groups (round 4)
+    const int shape = plan.shape, splitk = plan.splitk;
+    if (shape == 27) return launch_l<EPI, 27>(p, plan, stream);
+    if (shape == 28) return launch_l<EPI, 28>(p, plan, stream);
+    if (shape == 42 || shape == 41 || shape == 40) {
+        // 42: persistent 256 x 256 tiles on sixteen waves in two staggered groups (round 4); 41: persistent 256-token tiles (round 4), 192 x 256 (N x M);
+        // 40: persistent 256 x 256 tiles, 128 accumulator registers — hipcc spills inside the K loop at the 256-register cap (117 us for fc1 at M = 5760)
         if constexpr (EPI == EPI_F32 || EPI == EPI_GELU_TANH || EPI == EPI_PARTIAL || EPI == EPI_F16_TILED) {
             GTAV_REQUIRE(splitk == 1 && p.N % 8 == 0, "gemm: the persistent 256-token-tile kernels split K themselves (one slab, N %% 8 == 0)");
-            return launch_s16<EPI>(p, stream);
-        } else {
-            GTAV_REQUIRE(false, "gemm: block shape 42 has no epilogue %d", EPI);
-        }
-    }
-    if (shape == 41) {   // persistent 256-token tiles (round 4): 192 x 256 (N x M)
-        handled = true;
-        if constexpr (EPI == EPI_F32 || EPI == EPI_GELU_TANH || EPI == EPI_PARTIAL || EPI == EPI_F16_TILED) {
-            GTAV_REQUIRE(splitk == 1 && p.N % 8 == 0, "gemm: the persistent 256-token-tile kernel splits K itself (one slab, N %% 8 == 0)");
-            return launch_p256<EPI, 6>(p, stream);
+            if (shape == 42) return launch_s16<EPI>(p, stream);
+            if (shape == 41) return launch_p256<EPI, gemm_shape(41)->fi>(p, stream);
+            return launch_p256<EPI, gemm_shape(40)->fi>(p, stream);
         } else {
             GTAV_REQUIRE(false, "gemm: the persistent 256-token-tile kernel (shape %d) has no epilogue %d", shape, (int)EPI);
-        }
-    }
-    if (shape == 40) {   // persistent 256 x 256 tiles: 128 accumulator registers — hipcc spills inside the K loop at the 256-register cap (117 us for fc1 at M = 5760)
-        if constexpr (EPI == EPI_F32 || EPI == EPI_GELU_TANH || EPI == EPI_PARTIAL || EPI == EPI_F16_TILED) {
-            GTAV_REQUIRE(splitk == 1 && p.N % 8 == 0, "gemm: the persistent 256-token-tile kernel splits K itself (one slab, N %% 8 == 0)");
-            return launch_p256<EPI, 8>(p, stream);
-        } else {
-            GTAV_REQUIRE(false, "gemm: the persistent 256-token-tile kernel (shape 40) has no epilogue %d", (int)EPI);
         }
     }
     if (shape == 30 || shape == 32 || shape == 33) {
         // persistent loader-wave kernel variants, measured against shape 31 / the two-blocks-per-CU shapes (docs/LABNOTES.md 4.9): 30 (4-stage ring) ties 31; 32 / 33
         // (256 x 128 / 128 x 256) win back to back on cold operands (fc1 at M = 5760 67 -> 57 us) and LOSE inside the forward (54 -> 59-60 us)
-        if constexpr (EPI == EPI_GELU_TANH || EPI == EPI_PARTIAL || EPI == EPI_F16_TILED || EPI == EPI_RESID) {
-            GTAV_REQUIRE(splitk == 1 && p.N % 8 == 0, "gemm: the persistent loader-wave kernel runs the whole K in one slice (N %% 8 == 0)");
-            if (shape == 30) return launch_lp<EPI, 4>(p, stream);
-            if (shape == 32) return launch_lp<EPI, 3, 4, 4, 4, 2>(p, stream);
-            return launch_lp<EPI, 3, 4, 4, 2, 4>(p, stream);
-        } else {
-            GTAV_REQUIRE(false, "gemm: the persistent loader-wave kernel (shape %d) has no epilogue %d", shape, (int)EPI);
-        }
+        if (shape == 30) return launch_lp<EPI, 30>(p, plan, stream);
+        if (shape == 32) return launch_lp<EPI, 32>(p, plan, stream);
+        return launch_lp<EPI, 33>(p, plan, stream);
     }
     if constexpr (!FOLDISH) {
         // Round 6, measured SLOWER (profiles/round6/weight_operand_straight_into_registers_shapes_22_18.txt): the captured batch-1 step 2.05 -> 2.26 ms
         // (shape 22) / 2.12 -> 2.23 ms (shape 18), bit-identical results.  More weight bytes in flight per CU (128 KiB in registers against 48 KiB of the LDS ring) buy
         // nothing at M = 720: the K-step of the loader-wave kernel is not waiting for the weight.
         // shape 20's tile, the weight operand straight into registers 4 K-steps ahead (its K loop is written for K-steps per slice that are a multiple of 4: else shape 20)
-        if (shape == 22) {
-            if ((p.K / TK / (splitk > 0 ? splitk : 1)) % 4 == 0) return launch_lw<EPI, 4, 2, 3, 4, 2, 4, 4>(p, splitk, stream);
-            return launch_l<EPI, 4, 2, 3, 4, 2, 4>(p, splitk, stream);
-        }
+        if (shape == 22) return (p.K / TK / splitk) % 4 == 0 ? launch_lw<EPI, 22, 4>(p, splitk, stream) : launch_l<EPI, 20>(p, plan, stream);
         // ... and with the eight compute waves side by side along the features (16 features x all 96 tokens each): every W fragment is loaded by exactly one wave,
         // 8 K-steps ahead
-        if (shape == 18) {
-            if ((p.K / TK / (splitk > 0 ? splitk : 1)) % 8 == 0) return launch_lw<EPI, 4, 1, 6, 8, 1, 4, 8>(p, splitk, stream);
-            return launch_l<EPI, 4, 2, 3, 4, 2, 4>(p, splitk, stream);
-        }
-        // Shape 7 (launch_epi: its grid, group width and narrow-output rule) with the two wave groups of a block in antiphase (gemm256_pp_kernel).  Round 6: correct,
+        if (shape == 18) return (p.K / TK / splitk) % 8 == 0 ? launch_lw<EPI, 18, 8>(p, splitk, stream) : launch_l<EPI, 20>(p, plan, stream);
+        // Shape 7 (its grid, group width and narrow-output rule: the planner) with the two wave groups of a block in antiphase (gemm256_pp_kernel).  Round 6: correct,
         // race-screened (profiles/round6/race_screen_shape17.txt) and within +-1 % of shape 7 on the shapes that select it (fc2 / projection at M >= 11 520, fc1 -7 % at
         // M = 11 520 where shape 12 is still ahead of both at the model level): the K-tile is bound by how many fill bytes a CU keeps in flight, not by how its two
         // waves per SIMD interleave reads and MFMAs (profiles/round6/antiphase_256x256_main_loop_shape17_vs_shape7_vs_heuristic.txt: main loop 26.9 vs 27.2 us)
         if (shape == 17) {
-            GTAV_REQUIRE(!p.out2 || EPI == EPI_F16_TILED, "gemm: a second output image (out2) exists for EPI_F16_TILED on the staged epilogue only (epilogue %d, block shape %d)", (int)EPI, shape);
-            set_gn(256, 256);
-            if (!g_force_gn && splitk == 1 && p.N <= 1024 && (size_t)p.M >= 8 * (size_t)p.N) p.tm.gn = cdiv(p.N, 256);
-            const dim3 grid(cdiv(p.M, 256) * cdiv(p.N, 256) * splitk);
-            GEMM_LAUNCH((gemm256_pp_kernel<EPI>), grid, dim3(512));
+            GEMM_LAUNCH((gemm256_pp_kernel<EPI>), dim3(plan.blocks), dim3(plan.threads));
             GTAV_CHECK_HIP(hipGetLastError());
             return 0;
         }
         // measured slower than the shapes the heuristic picks (docs/LABNOTES.md 4.1.1)
-        if (shape == 21) return launch_l<EPI, 3, 4, 4, 4, 2, 4>(p, splitk, stream);   // 256 x 128, 8 compute + 4 loader waves
-        if (shape == 23) return launch_l<EPI, 4, 4, 3, 2, 2, 4>(p, splitk, stream);   // 128 x 96, 4 compute waves of 64 x 48 + 4 loader waves
-        if (shape == 25) return launch_l<EPI, 5, 2, 3, 4, 2, 4>(p, splitk, stream);   // shape 20 with a 5-stage ring (140 KiB)
+        if (shape == 21) return launch_l<EPI, 21>(p, plan, stream);
+        if (shape == 23) return launch_l<EPI, 23>(p, plan, stream);
+        if (shape == 25) return launch_l<EPI, 25>(p, plan, stream);
         if (shape == 16) {
             if constexpr (EPI == EPI_GELU_TANH || EPI == EPI_GELU_ERF || EPI == EPI_QKV || EPI == EPI_RESID) {
                 GTAV_REQUIRE(gemm_pp_ok(p.M, p.N, p.K, EPI) || (p.K / TK >= 12 && p.M % 8 == 0 && p.N % 8 == 0),
@@ -1644,26 +1573,16 @@ static int launch_experiment_shape(GemmParams& p, int ns, int shape, int splitk,
                 GTAV_REQUIRE(false, "gemm: the ping-pong kernel (shape 16) has no epilogue %d", (int)EPI);
             }
         }
-        if (shape == 9) {   // 128 features x 96 tokens, 6 waves (mainloop_g)
-            set_gn(96, 128);
-            const dim3 grid(cdiv(p.M, 96) * cdiv(p.N, 128) * splitk);
-            GEMM_LAUNCH((gemm_g_kernel<EPI, 4, 4, 2, 3>), grid, dim3(384));   // 3 stages 1-3 % and 5 stages 4-5 % slower
-            GTAV_CHECK_HIP(hipGetLastError());
-            return 0;
-        }
-        if (shape == 8) {   // 96 x 96, 6 waves
+        if (shape == 9) return launch_plain<EPI, 9>(p, plan, stream);
+        if (shape == 8) {
             if constexpr (EPI == EPI_GELU_TANH || EPI == EPI_GELU_ERF || EPI == EPI_F16_TILED) {
                 GTAV_REQUIRE(false, "gemm: the 96-feature tile has no tile-major (GELU) epilogue");
             } else {
-                set_gn(96, 96);
-                const dim3 grid(cdiv(p.M, 96) * cdiv(p.N, 96) * splitk);
-                GEMM_LAUNCH((gemm_g_kernel<EPI, 4, 3, 2, 3>), grid, dim3(384));
-                GTAV_CHECK_HIP(hipGetLastError());
-                return 0;
+                return launch_plain<EPI, 8>(p, plan, stream);
             }
         }
     }
-    handled = false;
+    GTAV_REQUIRE(false, "gemm: block shape %d has no kernel for epilogue %d", shape, (int)EPI);
     return 0;
 }
 

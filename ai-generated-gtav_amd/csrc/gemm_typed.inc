@@ -100,10 +100,3 @@ int launch_gemm_qkvs_attn(const GemmParams& p, hipStream_t stream);
 bool gemm_tn_ok(int M, int N, int K);
 bool gemm_tn_pays(int M, int N, int K);
 int launch_gemm_tn(const GemmParams& p, hipStream_t stream);
-
-// Test overrides, thread_local in gemm.hip and therefore one pair per operand type (the twin's are gtav_bf16::gemm_set_*): gtav_op_gemm_set_stages / _set_wm set both.
-// Pipeline depth override (0 = heuristic, else 2 or 4 LDS stages).
-void gemm_set_stages(int ns);
-// Block shape override (0 = heuristic; shape numbers in gemm.hip launch_epi).  Every shape computes the same result.  Bit 8 (+ 0x100, with any shape or with 0):
-// every loader-wave launch of the thread fills its W operand non-temporally (GemmParams::wfill), whatever the caller's params say.  The same result again.
-void gemm_set_wm(int wm);

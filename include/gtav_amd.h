@@ -461,8 +461,14 @@ int gtav_op_gemm_splitk_ln(const void* x_f16_dev, int32_t ldx, const void* w_f16
                            int32_t gate_stride, int32_t rows_per_gate, void* out_f16_dev, const float* shift_dev,
                            const float* scale_dev, int32_t mod_stride, void* stream);
 int gtav_op_gemm_choose_splitk(int32_t M, int32_t N, int32_t K);
+/* What a GEMM launch of this problem would run, without touching a device (the function the launch itself asks: csrc/gemm_plan.h).  epilogue: 0-7 as
+ * gtav_op_gemm_f16's (the experiments library also knows the LayerNorm-fold codes 8-11); qkv_mode / S: epilogue 5; splitk: the caller's K slices (epilogue 6);
+ * rows_per_gate: epilogue 4, 0 = no gate.  plan8 = {block shape id, ring depth, K slices, tile-group width, tile tokens, tile features, blocks, threads}.
+ * Honours the calling thread's forced shape / stages (gtav_amd_testing.h); non-zero with gtav_last_error set for a shape id that does not exist, or exists
+ * in the experiments build only. */
+int gtav_op_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t qkv_mode, int32_t S, int32_t splitk, int32_t rows_per_gate, int32_t* plan8);
 /* 1 when the model runs a residual GEMM of this shape (out-proj, fc2) with the in-place gated residual epilogue (epilogue 4) instead of split-K slabs
- * reduced by the following LayerNorm: large M on the persistent loader-wave kernel (csrc/gemm.h gemm_resid_inplace_ok). */
+ * reduced by the following LayerNorm: large M on the persistent loader-wave kernel (csrc/gemm_plan.h gemm_resid_inplace_ok). */
 int gtav_op_gemm_resid_inplace(int32_t M, int32_t N, int32_t K);
 /* (The per-thread hooks the parity tests use to force a GEMM block shape / pipeline depth are declared in gtav_amd_testing.h: they are
  * not part of the product interface.) */

@@ -1,12 +1,26 @@
 /* gtav_amd — test hooks of libgtav_amd.so.  NOT part of the product interface (include/gtav_amd.h): nothing in a binding of the
  * reference's API needs them.  tests/ use them to run every GEMM block shape the launch heuristic can pick through every epilogue.
  *
- * All settings are PER THREAD (thread_local in csrc/gemm.hip), like the handles: forcing a shape on one thread never changes what
- * another thread's handle launches.  Every choice computes the same result.  0 restores the heuristic.
+ * All settings are PER THREAD (thread_local in csrc/gemm_plan.hip, one set for both operand types), like the handles: forcing a shape on one thread never
+ * changes what another thread's handle launches.  Every choice computes the same result.  0 restores the heuristic.
  *   gtav_op_gemm_set_stages   LDS ring depth of the 128 x 128 tiles: 2 or 4
- *   gtav_op_gemm_set_wm       block shape: 2, 3 (128 x 128, 4 / 8 waves), 7 (256 x 256), 11 (64 x 48), 12 (128 x 192), 13 (128 x 96, 4 waves), 14 (64 x 96),
- *                             20 / 24 / 26 (loader-wave kernel, 128 x 96 / 64 x 48 / 64 x 96 tiles), 31 (persistent loader-wave kernel, 128 x 192 tiles, 3-stage ring; its 4-stage / 256 x 128 / 128 x 256 forms 30 / 32 / 33 exist in the experiments build only)
- *                             — csrc/gemm.hip launch_epi.  Plus GTAV_GEMM_WM_NT_WEIGHT_FILLS (0x100; with a shape or with 0 = heuristic): every loader-wave
+ *   gtav_op_gemm_set_wm       block shape, an id of the shape table GEMM_SHAPES in csrc/gemm_plan.h — the ONE place where a shape's tile, waves and ring are
+ *                             defined; gtav_op_gemm_plan (gtav_amd.h) reports them, and tests/test_host_gemm_plan.py holds this list against the table:
+ *                                id   features x tokens   compute [+ loader] waves
+ *     2     128 x 128     4 waves
+ *     3     128 x 128     8 waves
+ *     7     256 x 256     8 waves
+ *     11    64 x 48       6 waves
+ *     12    128 x 192     8 waves
+ *     13    128 x 96      4 waves
+ *     14    64 x 96       6 waves
+ *     20    128 x 96      8 + 4 waves   (loader-wave kernel, as 24 / 26 / 29)
+ *     24    64 x 48       6 + 2 waves
+ *     26    64 x 96       6 + 2 waves
+ *     29    128 x 144     12 + 4 waves
+ *     31    128 x 192     8 + 4 waves   (persistent loader-wave kernel, 3-stage ring; its 4-stage / 256 x 128 / 128 x 256 forms 30 / 32 / 33 and the
+ *                             other laboratory shapes exist in the experiments build only: a product library refuses them by name)
+ *                             Plus GTAV_GEMM_WM_NT_WEIGHT_FILLS (0x100; with a shape or with 0 = heuristic): every loader-wave
  *                             launch of the thread (shapes 20 / 24 / 26 / 29 and the two fused to_qkv + attention launches) fills its weight operand with the
  *                             non-temporal cache policy (GemmParams::wfill, the kernel side of gtav_dit_set_weight_fill_policy): the same bits again
  *                             (tests/test_gpu_launch_head.py)
