@@ -688,7 +688,7 @@ int gtav_dit_check(gtav_dit* h, void* stream) {
     GTAV_REQUIRE(h, "dit_check: null handle");
     std::vector<int> w;
     RET_IF(dit_read_err_words(h, w, (hipStream_t)stream));
-    int flag = w[0];
+    int flag = w[0] | w[1];   // (word 1: bits of the group words that gtav_dit_zero_grad set aside on a mixed-capable training handle; zero on every other)
     for (int g = 0; g < h->n_groups; ++g) flag |= w[4 + g];
     return report_err_flag(flag, "DiT");
 }
@@ -705,6 +705,9 @@ int gtav_dit_set_operand_dtype(gtav_dit* h, int32_t group, int32_t dtype) {
     int changed = 0;
     for (int g = (group < 0 ? 0 : group); g < (group < 0 ? h->n_groups : group + 1); ++g) {
         if ((h->grp_bf16[g] != 0) == (dtype == GTAV_OPERAND_BF16)) continue;
+        // (a mixed-capable training handle changes a group's type in place, from its fp32 masters; this call would un-set the weights)
+        GTAV_REQUIRE(!(h->tr.on && h->tr.mixed), "dit_set_operand_dtype: group %d of this training handle has the other type; a training handle changes it with "
+                     "gtav_dit_train_set_group_dtype", g);
         h->grp_bf16[g] = dtype == GTAV_OPERAND_BF16;
         changed += 1 + h->wt.set_dtype(g, dtype == GTAV_OPERAND_BF16);
     }

@@ -74,6 +74,9 @@ struct WeightTable {
     // clamped by the conversion AND raises ERR_F16_SAT there, so that check() reports it and gtav_dit_autorange moves the group to bf16
     int* err_words = nullptr;
     bool err_per_group = false;
+    // a mixed-capable training handle (gtav_dit::Train::range_words): a clamped GEMM weight of group g is a range problem of that group, which bf16 operands cure like
+    // a saturated activation — it goes straight to the group's sticky word, where gtav_dit_train_autorange finds it (the image is then remade from the fp32 master)
+    int* range_words = nullptr;
     // lookups that never insert (slots[n] on a misspelt name would make a blank Slot, whose null pointers the next launch writes through)
     Slot* find(const std::string& n) { auto it = slots.find(n); return it == slots.end() ? nullptr : &it->second; }
     bool is_set(const std::string& n) { const Slot* sl = find(n); return sl && sl->set; }
@@ -106,6 +109,7 @@ struct WeightTable {
                      (long long)numel, sl.R, sl.C);
         if (sl.kind == SLOT_F16_PAD) {
             int* ef = err_words ? err_words + (err_per_group && sl.group >= 0 ? 4 + sl.group : 0) : nullptr;
+            if (range_words && sl.group >= 0) ef = range_words + sl.group;
             RET_IF(operand_ops(sl.bf16).convert_pad(src, sl.C, sl.R, sl.C, (f16*)sl.dst, sl.Rp, sl.Cp, 1.0f, 1, s, ef));
         }
         else RET_IF(launch_copy_f32(src, sl.C, sl.R, sl.C, (float*)sl.dst, sl.Cp, sl.c0, s));
@@ -361,7 +365,8 @@ struct gtav_dit {
     std::vector<f16*> kvcache;  // [L]
     float *resid, *fo, *vout, *E, *HC, *Sc, *mod, *parts;
     size_t parts_rows = 0;
-    // device error words: [0] the handle's (bad timestep, non-finite input, training-side saturation), [4 + g] one per operand group g — the fp16 stores of group
+    // device error words: [0] the handle's (bad timestep, non-finite input, training-side saturation), [1] what gtav_dit_zero_grad found in the group words of a
+    // mixed-capable training handle (an inference forward's bits, kept for gtav_dit_check), [4 + g] one per operand group g — the fp16 stores of group
     // g's kernels raise ERR_F16_SAT THERE, so that gtav_dit_autorange can move exactly the saturated layers to bf16 operands
     int* err_flag = nullptr;
     // operand groups: g = 2 l + (0 spatial | 1 temporal) half of block l, 2 L = patch embedding, 2 L + 1 = final layer.  grp_bf16[g]: the group's 2-byte tensors
@@ -448,6 +453,13 @@ struct gtav_dit {
     struct Train {
         bool on = false, have_fwd = false, have_actions = false;
         bool bf16 = false;                  // every operand group bf16 (gtav_dit_train_enable_typed): no group may change its type while training is on
+        // Mixed operand types (gtav_dit_train_allow_mixed): the groups of an enabled handle may change their type one by one (gtav_dit_train_set_group_dtype,
+        // gtav_dit_train_autorange); `bf16` is then the type the handle STARTED on.  The training forward raises its bits in the group's error word (err_of(g)),
+        // launch_err_fold moves them into word 0 and into range_words[g], which stay until read: which fp16 group saturated in a training forward.
+        bool mixed = false;
+        int* range_words = nullptr;         // [n_groups] device words (mixed handles only)
+        std::vector<AdamItem> adam_items_host;   // (mixed handles only) the work items in parameter order: a type switch re-partitions the device list
+        int adam_n[2] = {0, 0};             // the device list holds adam_n[0] items of fp16 groups (and the fp32 parameters), then adam_n[1] items of bf16 groups
         int window = 8;                     // frames a training handle may be sized for (gtav_dit_train_allow_window raises it to at most 32)
         // Activation recomputation (gtav_dit_train_set_recompute): the forward keeps the L + 1 block-input states and ONE block's worth of everything else,
         // the backward re-runs a block's forward just before differentiating it.  res / hb keep their 4 L + 1 / 2 L entries, as aliases: res[k], k % 4 != 0, is

@@ -119,6 +119,12 @@ static int train_enable_body(gtav_dit* h, float* grad_arena_dev, int64_t grad_ar
         GTAV_CHECK_HIP(hipMemcpy(t.adam_params, ap.data(), ap.size() * sizeof(AdamParam), hipMemcpyHostToDevice));
         GTAV_CHECK_HIP(hipMemcpy(t.adam_items, ai.data(), ai.size() * sizeof(AdamItem), hipMemcpyHostToDevice));
         t.adam_n_items = (int)ai.size();
+        t.adam_n[t.bf16 ? 1 : 0] = t.adam_n_items;   // one operand type: one launch over the whole list (gtav_dit_adamw_step)
+        if (t.mixed) {
+            t.adam_items_host = ai;
+            RET_IF(a.alloc_t(&t.range_words, (size_t)h->n_groups));
+            h->wt.range_words = t.range_words;   // (a clamped GEMM weight: api_internal.h WeightTable::range_words)
+        }
     }
     const size_t Mx = round_up(h->Mmax, 128), Mp = round_up(h->Mmax, 64), Mm = h->Mmax;
     // saved activations (counted: gtav_dit_train_saved_bytes).  Recompute mode: the block inputs r_0, r_4, .. r_4L, three ring states for the ones inside a block,
@@ -199,6 +205,14 @@ int gtav_dit_train_set_recompute(gtav_dit* h, int32_t enable) {
     return 0;
 }
 
+// Opt-in to operand groups of both types on one training handle (api_internal.h Train::mixed): between create and train_enable only, like the two above.
+int gtav_dit_train_allow_mixed(gtav_dit* h, int32_t enable) {
+    GTAV_REQUIRE(h, "train_allow_mixed: null handle");
+    GTAV_REQUIRE(!h->tr.on, "train_allow_mixed: training is already enabled on this handle (call it between gtav_dit_create and gtav_dit_train_enable)");
+    h->tr.mixed = enable != 0;
+    return 0;
+}
+
 int gtav_dit_train_saved_bytes(gtav_dit* h, int64_t* bytes) {
     GTAV_REQUIRE(h && bytes, "train_saved_bytes: null argument");
     GTAV_REQUIRE(h->tr.on, "train_saved_bytes: training is not enabled");
@@ -234,6 +248,21 @@ int gtav_dit_train_enable_typed(gtav_dit* h, float* grad_arena_dev, int64_t grad
 
 }  // extern "C"
 
+// Where a launch of the training forward raises its saturation bits: on a mixed-capable handle (gtav_dit_train_allow_mixed) in its operand group's word, which
+// launch_err_fold moves into word 0 and the group's sticky word; on every other handle in word 0, as ever.
+static int* train_fwd_err(const gtav_dit* h, int g) { return h->tr.mixed ? h->err_of(g) : h->err_flag; }
+
+// The one 2-byte tensor that crosses a group boundary: the branch image y2 of a half-block's fc2 (LnPending::y_save) is written by the LayerNorm launch that
+// applies the pending update, which belongs to the NEXT group (the next half-block's, or the final layer's), and read by the producer's gate backward on the
+// producer's launcher set.  Where the two groups differ in type the producer's set writes it here, with the LayerNorm kernel's sum, and the LayerNorm keeps none.
+static int train_branch_seam(gtav_dit* h, int producer, int consumer, DeferredResid& rd, hipStream_t s) {
+    if (!rd.pending || !rd.pend.y_save || h->grp_bf16[producer] == h->grp_bf16[consumer]) return 0;
+    RET_IF(h->ops(producer).branch_rows(rd.pend.parts, rd.pend.nsplit, rd.pend.slab_stride, rd.pend.ld, rd.pend.bias, rd.pend.y_save, rd.M, rd.N,
+                                        train_fwd_err(h, producer), s));
+    rd.pend.y_save = nullptr;
+    return 0;
+}
+
 // Both half-blocks of block l of the training forward (gtav_dit_train_forward runs it for l = 0 .. L - 1).  Every residual GEMM stores split-K slabs and leaves
 // the update to the next LayerNorm launch (`rd`): on return the block's last fc2 branch is still pending, and the first LayerNorm of block l + 1 (or the final
 // layer's) applies it, writes r_{4l+4} and the branch image y2.
@@ -248,23 +277,25 @@ static int train_block_forward(gtav_dit* h, int l, int B, int T, bool rerun, Def
         gtav_dit::Train::HB& b = tr.hb[i];
         const float* mb = h->mod + (size_t)i * 6 * D;
         const OperandOps& o = h->ops(i);
+        int* const ef = train_fwd_err(h, i);
         auto gate = [&](const float* g) { return ResidGate{g, h->MODW, nullptr, P}; };
         // LN1 normalises r_{2i} (= r_{2i-1} + gate (fc2 of the previous half-block), written to res[2i] by this launch)
         const bool from_stored = rerun && hf == 0 && l > 0;
         if (from_stored) RET_IF(rd.load_shift(tr.kshift[l]));
         else if (tr.recompute && hf == 0 && l > 0) rd.save_shift(tr.kshift[l]);   // (l > 0: the previous block's fc2 is pending)
-        RET_IF(o.ln_modulate(from_stored ? tr.res[2 * i] : i == 0 ? tr.res[0] : tr.res[2 * i - 1], D, b.xnA, D, M, D, mb, mb + D, h->MODW, nullptr, P, rd.take(), h->err_flag, s));
+        if (i > 0 && !from_stored) RET_IF(train_branch_seam(h, i - 1, i, rd, s));
+        RET_IF(o.ln_modulate(from_stored ? tr.res[2 * i] : i == 0 ? tr.res[0] : tr.res[2 * i - 1], D, b.xnA, D, M, D, mb, mb + D, h->MODW, nullptr, P, rd.take(), ef, s));
         GemmParams g = gemm_params(b.xnA, D, w.w_qkv, M, 3 * D, D);
-        g.D = D; g.S = P; g.err_flag = h->err_flag;
+        g.D = D; g.S = P; g.err_flag = ef;
         if (hf == 0) { g.qkv_mode = QKV_SPATIAL; g.q = b.q; g.k = b.k; g.v = b.v; g.rope_cs = h->rope_s.cs_dev; }
         else { g.qkv_mode = QKV_TEMPORAL; g.q = b.q; g.k = b.k; g.v = b.k; g.Tq = T; g.t0 = 0; g.Tmax = h->maxT; g.rope_cs = h->rope_t.cs_dev; }
         RET_IF(o.gemm(g, EPI_QKV, s));
         if (hf == 0) RET_IF(o.attn_spatial(b.q, b.k, b.v, b.ao, NB, h->heads, P, s, false));
         else RET_IF(o.attn_temporal(b.q, b.k, b.ao, B, P, D, T, 0, h->maxT, s));
         RET_IF(rd.gemm(o, PC_OUT, b.ao, D, w.w_out, D, w.b_out, gate(mb + 2 * D), false, kNoPrefetch, tr.res[2 * i + 1], b.y1));
-        RET_IF(o.ln_modulate(tr.res[2 * i], D, b.xnB, D, M, D, mb + 3 * D, mb + 4 * D, h->MODW, nullptr, P, rd.take(), h->err_flag, s));
+        RET_IF(o.ln_modulate(tr.res[2 * i], D, b.xnB, D, M, D, mb + 3 * D, mb + 4 * D, h->MODW, nullptr, P, rd.take(), ef, s));
         GemmParams fc1 = gemm_params(b.xnB, D, w.w_fc1, M, h->Hm, D);
-        fc1.bias = w.b_fc1; fc1.out = b.u; fc1.ldo = h->Hm_pad; fc1.err_flag = h->err_flag;
+        fc1.bias = w.b_fc1; fc1.out = b.u; fc1.ldo = h->Hm_pad; fc1.err_flag = ef;
         if (g_fuse_gelu_fwd) fc1.out2 = b.hh;             // h = GELU(u) as a second image of the same epilogue (gemm.h out2)
         RET_IF(o.gemm(fc1, EPI_F16_TILED, s));            // the pre-activation is kept: gelu'(u) in the backward pass
         if (!g_fuse_gelu_fwd) RET_IF(h->ops(i).gelu_tiled(b.u, b.hh, (size_t)round_up(M, 128) * h->Hm_pad, s));
@@ -288,7 +319,9 @@ static int train_rerun_block(gtav_dit* h, int l, hipStream_t s) {
     const float* mb = h->mod + (size_t)i * 6 * D;   // (i = 2 L: the final layer's shift and scale)
     const bool last = l == L - 1;   // (then 2 i - 1 = 4 L - 1, and the launch is the final layer's)
     if (!last) rd.save_shift(tr.kshift[l + 1]);
-    RET_IF(h->ops(last ? 2 * L + 1 : i).ln_modulate(tr.res[2 * i - 1], D, last ? tr.xnF : tr.g_d, D, tr.M, D, mb, mb + D, h->MODW, nullptr, h->P, rd.take(), h->err_flag, s));
+    const int gn = last ? 2 * L + 1 : i;   // the group of that launch
+    RET_IF(train_branch_seam(h, i - 1, gn, rd, s));
+    RET_IF(h->ops(gn).ln_modulate(tr.res[2 * i - 1], D, last ? tr.xnF : tr.g_d, D, tr.M, D, mb, mb + D, h->MODW, nullptr, h->P, rd.take(), train_fwd_err(h, gn), s));
     tr.rc_block = l;
     return 0;
 }
@@ -322,6 +355,9 @@ int gtav_dit_zero_grad(gtav_dit* h, void* stream) {
     RET_IF(launch_fill_f32(h->tr.grad_arena, h->tr.grad_count, 0.f, (hipStream_t)stream));
     // a training step starts here: saturation / non-finite bits raised by an earlier forward on this handle (validation, predict) are not this step's
     // overflow — clear them so that only the step's own stores can make the optimizer skip (gtav_dit_check reports inference saturation before that)
+    // (a mixed-capable handle's training forward raises its bits in the group words, where an inference forward raises its own: those are set aside in word 1
+    // — neither a skip nor a type switch, and still reported by gtav_dit_check; the sticky words are not touched)
+    if (h->tr.mixed) RET_IF(launch_err_fold(h->err_flag, nullptr, 1, h->n_groups, (hipStream_t)stream));
     return launch_err_clear(h->err_flag, ERR_F16_SAT | ERR_NONFINITE, (hipStream_t)stream);
 }
 
@@ -355,18 +391,21 @@ int gtav_dit_train_forward(gtav_dit* h, const float* x, const int64_t* t64, cons
     RET_IF(launch_skinny_f32(h->Sc, D, h->w_ada, h->b_ada, h->mod, h->MODW, rows, h->MODW, D, 0, s));
     const float* mod = h->mod;
     const OperandOps& oe = h->ops(2 * L), &ofin = h->ops(2 * L + 1);   // patch embedding, final layer (the half-blocks: h->ops(i) below)
-    RET_IF(oe.patchify(x, nullptr, NB, h->C, h->H, h->W, h->p, tr.xp, h->Kpe, 1.f, 0.f, h->err_flag, s));
+    RET_IF(oe.patchify(x, nullptr, NB, h->C, h->H, h->W, h->p, tr.xp, h->Kpe, 1.f, 0.f, train_fwd_err(h, 2 * L), s));
     GemmParams g = gemm_params(tr.xp, h->Kpe, h->w_pe, M, D, h->Kpe);
     g.bias = h->b_pe; g.out = tr.res[0]; g.ldo = D;
     RET_IF(oe.gemm(g, EPI_F32, s));
     DeferredResid rd{h->parts, h->parts_rows * (size_t)D, nullptr, M, D, nullptr, s};   // no in-place target (the backward pass needs every state and branch), no profiler
     for (int l = 0; l < L; ++l) RET_IF(train_block_forward(h, l, B, T, false, rd, s));
     const float* mf = mod + (size_t)L * 12 * D;
-    RET_IF(ofin.ln_modulate(tr.res[4 * L - 1], D, tr.xnF, D, M, D, mf, mf + D, h->MODW, nullptr, P, rd.take(), h->err_flag, s));
+    RET_IF(train_branch_seam(h, 2 * L - 1, 2 * L + 1, rd, s));
+    RET_IF(ofin.ln_modulate(tr.res[4 * L - 1], D, tr.xnF, D, M, D, mf, mf + D, h->MODW, nullptr, P, rd.take(), train_fwd_err(h, 2 * L + 1), s));
     g = gemm_params(tr.xnF, D, h->w_final, M, h->Nfin, D);
     g.bias = h->b_final; g.out = h->fo; g.ldo = h->Nfin;
     RET_IF(ofin.gemm(g, EPI_F32, s));
     RET_IF(launch_unpatchify(h->fo, h->Nfin, out, NB, h->C, h->H, h->W, h->p, 0, 1.f, 0.f, s));
+    // (mixed-capable handles) the groups' bits of this forward into word 0, where the backward's publish and the optimizer look, and into the sticky words
+    if (tr.mixed) RET_IF(launch_err_fold(h->err_flag, tr.range_words, 0, h->n_groups, s));
     tr.B = B; tr.T = T; tr.M = M; tr.Mp = round_up(M, 64); tr.rows = rows; tr.have_actions = actions != nullptr; tr.have_fwd = true;
     tr.rc_block = L - 1;   // (recompute mode: the ring states and the two image sets hold the last block)
     return 0;
@@ -630,16 +669,134 @@ int gtav_dit_adamw_step(gtav_dit* h, float lr, float beta1, float beta2, float e
     GTAV_REQUIRE(h && h->tr.on, "adamw_step: training is not enabled");
     hipStream_t s = (hipStream_t)stream;
     gtav_dit::Train& tr = h->tr;
+    if (tr.mixed) RET_IF(launch_err_fold(h->err_flag, tr.range_words, 0, h->n_groups, s));   // (the bits of recompute mode's re-runs, raised after the forward's fold)
     RET_IF(launch_sumsq(tr.grad_arena, tr.grad_count, tr.sumsq_part, s));
     // overflow (non-finite norm, or a saturated fp16 gradient / activation recorded in the error word) skips the step on the device; the
     // Adam step count and its bias corrections live in ctl[4..6] and advance only with applied steps
     RET_IF(launch_clip_coef(tr.ctl, tr.sumsq_part, sumsq_parts(tr.grad_count), 1.0f / (tr.loss_scale * tr.grad_div), max_grad_norm, beta1, beta2, h->err_flag, s));
-    // one launch: AdamW on every parameter + the 2-byte W / W^T operands of the GEMM weights rewritten from the updated masters (in the handle's operand type)
-    RET_IF(operand_ops(tr.bf16).adamw_multi(tr.adam_params, tr.adam_items, tr.adam_n_items, tr.ctl, lr, beta1, beta2, eps, weight_decay, s));
+    // one launch per operand type in use (one, unless a mixed-capable handle has groups of both): AdamW on every parameter + the 2-byte W / W^T operands of the
+    // GEMM weights rewritten from the updated masters in their group's type.  The work items are independent, so the split changes no bit.
+    for (int ty = 0; ty < 2; ++ty)
+        if (tr.adam_n[ty])
+            RET_IF(operand_ops(ty != 0).adamw_multi(tr.adam_params, tr.adam_items + (ty ? tr.adam_n[0] : 0), tr.adam_n[ty], tr.ctl, lr, beta1, beta2, eps, weight_decay, s));
     RET_IF(launch_add_f32(h->b_t2, h->b_ext, h->b_t2a, h->D, s));   // fused bias of c when actions are given (gtav_dit_finalize)
     h->prepared.valid = false;
     h->kvrec.valid = false;
     return 0;
+}
+
+}  // extern "C"
+
+// ---- mixed operand types on a training handle (gtav_dit_train_allow_mixed) ----
+// The device list of AdamW work items, partitioned by the type their launch runs on: the items of fp16 groups' GEMM weights first, then those of bf16 groups'.
+// The fp32 parameters have no 2-byte image and give the same bits on either twin: they ride with the fp16 part, or with the bf16 part when no group is fp16.
+static int train_partition_items(gtav_dit* h) {
+    gtav_dit::Train& tr = h->tr;
+    bool any_f16 = false;
+    for (unsigned char b : h->grp_bf16) any_f16 |= b == 0;
+    std::vector<AdamItem> part[2];
+    for (const AdamItem& it : tr.adam_items_host) {
+        const Slot* sl = tr.params[it.param];
+        part[sl->kind == SLOT_F16_PAD ? (sl->bf16 ? 1 : 0) : (any_f16 ? 0 : 1)].push_back(it);
+    }
+    tr.adam_n[0] = (int)part[0].size(); tr.adam_n[1] = (int)part[1].size();
+    part[0].insert(part[0].end(), part[1].begin(), part[1].end());
+    GTAV_REQUIRE((int)part[0].size() == tr.adam_n_items, "train_set_group_dtype: the optimizer's work items do not add up");
+    GTAV_CHECK_HIP(hipMemcpy(tr.adam_items, part[0].data(), part[0].size() * sizeof(AdamItem), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// groups [g0, g1) of an enabled mixed-capable handle to `bf16`: launcher sets, W / W^T images from the fp32 masters, optimizer partition.  Returns the number changed.
+static int train_switch_groups(gtav_dit* h, int g0, int g1, bool bf16, hipStream_t s, int* n_changed) {
+    int changed = 0;
+    for (int g = g0; g < g1; ++g) {
+        if ((h->grp_bf16[g] != 0) == bf16) continue;
+        h->grp_bf16[g] = bf16;
+        ++changed;
+        for (auto& kv : h->wt.slots) {
+            Slot& sl = kv.second;
+            if (sl.kind != SLOT_F16_PAD || sl.group != g) continue;
+            sl.bf16 = bf16;
+            if (!sl.set) continue;   // (no weight sent yet: gtav_dit_set_weight converts into the slot's type)
+            GTAV_REQUIRE(sl.master, "train_set_group_dtype: '%s' has no fp32 master", kv.first.c_str());
+            // what WeightTable::set does with the caller's fp32 tensor, from the master (contiguous [R][C])
+            RET_IF(operand_ops(bf16).convert_pad(sl.master, sl.C, sl.R, sl.C, (f16*)sl.dst, sl.Rp, sl.Cp, 1.0f, 1, s, h->tr.range_words + g));
+            if (sl.wT) RET_IF(operand_ops(bf16).convert_T(sl.master, sl.C, sl.R, sl.C, sl.wT, s));
+        }
+    }
+    *n_changed = changed;
+    if (!changed) return 0;
+    h->any_bf16 = false;
+    for (unsigned char b : h->grp_bf16) h->any_bf16 |= b != 0;
+    // the saved activations of the last forward are of the old type, and so are the temporal K/V caches and whatever a captured step holds
+    h->tr.have_fwd = false;
+    h->tr.rc_block = -1;
+    h->prepared.valid = false;
+    h->kvrec.valid = false;
+    h->drop_graphs();
+    GTAV_CHECK_HIP(hipStreamSynchronize(s));   // (the re-partition below is a synchronous copy over a list an optimizer step in flight may still read)
+    return train_partition_items(h);
+}
+
+static int train_mixed_handle(gtav_dit* h, const char* who) {
+    GTAV_REQUIRE(h, "%s: null handle", who);
+    GTAV_REQUIRE(h->tr.on, "%s: training is not enabled", who);
+    GTAV_REQUIRE(h->tr.mixed, "%s: this training handle has one operand type for every group; opt in with gtav_dit_train_allow_mixed between gtav_dit_create and "
+                 "gtav_dit_train_enable", who);
+    return 0;
+}
+
+extern "C" {
+
+int gtav_dit_train_set_group_dtype(gtav_dit* h, int32_t group, int32_t dtype, void* stream) {
+    RET_IF(train_mixed_handle(h, "train_set_group_dtype"));
+    GTAV_REQUIRE(dtype == GTAV_OPERAND_F16 || dtype == GTAV_OPERAND_BF16, "train_set_group_dtype: dtype %d (0 = fp16, 1 = bf16)", dtype);
+    GTAV_REQUIRE(group >= -1 && group < h->n_groups, "train_set_group_dtype: group %d outside [-1, %d)", group, h->n_groups);
+    int n = 0;
+    return train_switch_groups(h, group < 0 ? 0 : group, group < 0 ? h->n_groups : group + 1, dtype == GTAV_OPERAND_BF16, (hipStream_t)stream, &n);
+}
+
+// the sticky words: copied back, cleared on the device
+int gtav_dit_train_range_words(gtav_dit* h, int32_t* words_host, void* stream) {
+    RET_IF(train_mixed_handle(h, "train_range_words"));
+    GTAV_REQUIRE(words_host, "train_range_words: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    static_assert(sizeof(int32_t) == sizeof(int), "the error words are 32-bit");
+    GTAV_CHECK_HIP(hipMemcpyAsync(words_host, h->tr.range_words, (size_t)h->n_groups * sizeof(int), hipMemcpyDeviceToHost, s));
+    GTAV_CHECK_HIP(hipStreamSynchronize(s));
+    GTAV_CHECK_HIP(hipMemsetAsync(h->tr.range_words, 0, (size_t)h->n_groups * sizeof(int), s));
+    return 0;
+}
+
+// Switch first, report afterwards: *n_switched and gtav_dit_get_operand_dtype are final when the call returns, with or without an error, so a caller that
+// reads the types back after EVERY return agrees with the handle.  (Reporting first would clear the words and return before the switch: the host would hold
+// an error, the handle its old types, and the saturation would come back with the next step.)
+int gtav_dit_train_autorange(gtav_dit* h, const int32_t* merged_words_host, int32_t* n_switched, void* stream) {
+    RET_IF(train_mixed_handle(h, "train_autorange"));
+    GTAV_REQUIRE(n_switched, "train_autorange: null argument");
+    *n_switched = 0;
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int32_t> sticky(h->n_groups, 0);
+    if (merged_words_host) sticky.assign(merged_words_host, merged_words_host + h->n_groups);
+    else RET_IF(gtav_dit_train_range_words(h, sticky.data(), stream));
+    // every other word, as gtav_dit_check reads them: the handle's, the inference bits gtav_dit_zero_grad set aside, the group words
+    std::vector<int> w(4 + h->n_groups, 0);
+    GTAV_CHECK_HIP(hipMemcpyAsync(w.data(), h->err_flag, w.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+    GTAV_CHECK_HIP(hipStreamSynchronize(s));
+    GTAV_CHECK_HIP(hipMemsetAsync(h->err_flag, 0, w.size() * sizeof(int), s));
+    int other = w[0] | w[1];
+    for (int g = 0; g < h->n_groups; ++g) {
+        other |= w[4 + g];
+        const bool switch_it = (sticky[g] & ERR_F16_SAT) && !h->grp_bf16[g];
+        // a saturation bit of a group that is bf16 already is a fault (the twins never raise it for a finite value), not something to drop
+        other |= switch_it ? sticky[g] & ~ERR_F16_SAT : sticky[g];
+        if (switch_it) {
+            int n = 0;
+            RET_IF(train_switch_groups(h, g, g + 1, true, s, &n));
+            *n_switched += n;
+        }
+    }
+    return report_err_flag(other, "DiT training");
 }
 
 // ctl: [0] sum of squares of the scaled gradients, [1] step coefficient (0 = the step was skipped), [2] skipped steps so far,

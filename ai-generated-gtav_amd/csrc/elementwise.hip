@@ -223,6 +223,26 @@ __global__ __launch_bounds__(512) void ln_row_block_kernel(float* __restrict__ x
     sat_report(amax, pd.err_flag);
 }
 
+// The branch image y = sum_s parts[s] + bias of a pending residual update as 2-byte rows, in THIS build's operand type: what ln_row_block_kernel keeps in
+// pd.y_save, with the same adds in the same order (bias, slab 0, slab 1, ..) and the same clamp, so the same bits.  A training handle with mixed operand
+// types runs it on the launcher set of the group that PRODUCED the branch where the LayerNorm that applies the update belongs to a group of the other type
+// (api_train.hip train_branch_seam); that LayerNorm then gets y_save = nullptr.  One thread per four columns; n4 = M * N / 4 of them.
+__global__ __launch_bounds__(256) void branch_rows_kernel(const float* __restrict__ parts, int nsplit, size_t slab_stride, int ld, const float* __restrict__ bias,
+                                                          f16* __restrict__ y, int N, size_t n4, int* err_flag) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    float am = 0.f;
+    if (i < n4) {
+        const int per_row = N >> 2;
+        const size_t m = i / per_row;
+        const int c = (int)(i - m * per_row) * 4;
+        const float* pp = parts + m * ld + c;
+        f32x4 acc = bias ? *(const f32x4*)(bias + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int sp = 0; sp < nsplit; ++sp) acc = acc + *(const f32x4*)(pp + (size_t)sp * slab_stride);
+        *(f16x4*)(y + m * ld + c) = sat4(acc[0], acc[1], acc[2], acc[3], am);
+    }
+    sat_report(am, err_flag);
+}
+
 // ------------------------------------------------------------------------------------------
 __global__ void patchify_kernel(const float* __restrict__ img, const int* __restrict__ frame_index, int NB, int C, int H,
                                 int W, int p, f16* __restrict__ out, int ldo, float a, float b, int* err_flag) {
@@ -857,6 +877,15 @@ int launch_ln_affine(float* x, int ldx, f16* out, int ldo, int M, int D, const f
 }
 #undef LN_DISPATCH
 #undef LN_WAVE_ROW_
+
+int launch_branch_rows(const float* parts, int nsplit, size_t slab_stride, int ld, const float* bias, f16* y, int M, int N, int* err_flag, hipStream_t stream) {
+    GTAV_REQUIRE(parts && y && nsplit >= 1 && nsplit <= 8 && M > 0 && N > 0 && N % 4 == 0 && ld % 4 == 0 && N <= ld && slab_stride >= (size_t)M * ld,
+                 "branch_rows: bad slabs (nsplit=%d, M=%d, N=%d, ld=%d)", nsplit, M, N, ld);
+    const size_t n4 = (size_t)M * (N / 4);
+    hipLaunchKernelGGL(branch_rows_kernel, dim3((unsigned)cdiv((long long)n4, 256)), dim3(256), 0, stream, parts, nsplit, slab_stride, ld, bias, y, N, n4, err_flag);
+    GTAV_CHECK_HIP(hipGetLastError());
+    return 0;
+}
 
 int launch_patchify(const float* img, const int* frame_index, int NB, int C, int H, int W, int p, f16* out, int ldo,
                     float a, float b, int* err_flag, hipStream_t stream) {

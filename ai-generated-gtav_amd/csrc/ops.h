@@ -140,6 +140,12 @@ int launch_sumsq(const float* g, size_t n, float* part, hipStream_t stream);
 int launch_overflow_publish(const int* err_flag, float* g, hipStream_t stream);
 // clears `bits` of the device error word (stream-ordered)
 int launch_err_clear(int* err_flag, int bits, hipStream_t stream);
+// Mixed-type training handles (gtav_dit_train_allow_mixed): moves the bits of the per-group error words words[4 .. 4 + n_groups) (stream-ordered) into
+// words[dst_word] and, where `sticky` is given, into sticky[g] as well; the group words are cleared.  (sticky, 0) is the fold at the end of a training forward:
+// the optimizer's skip decision and launch_overflow_publish see in word 0 what they see on a default handle, and the sticky words remember WHICH group
+// saturated until gtav_dit_train_range_words / gtav_dit_train_autorange read them.  (nullptr, 1) is gtav_dit_zero_grad's: bits an inference forward left in
+// the group words are not this step's, and wait in word 1 for gtav_dit_check.
+int launch_err_fold(int* words, int* sticky, int dst_word, int n_groups, hipStream_t stream);
 int launch_clip_coef(float* ctl, const float* part, int nparts, float inv_scale, float max_norm, float beta1, float beta2, int* err_flag, hipStream_t stream);
 int launch_adamw(float* p, int ldp, int R, int C, const float* g, float* m, float* v, const float* ctl, float lr, float beta1, float beta2, float eps,
                  float wd, hipStream_t stream);

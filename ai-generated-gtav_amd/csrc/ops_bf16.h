@@ -41,7 +41,8 @@ namespace gtav {
     F(mse_bwd_patch, launch_mse_bwd_patch)                  \
     F(attn_spatial_bwd, launch_attn_spatial_bwd)            \
     F(attn_temporal_bwd, launch_attn_temporal_bwd)          \
-    F(adamw_multi, launch_adamw_multi)
+    F(adamw_multi, launch_adamw_multi)                      \
+    F(branch_rows, launch_branch_rows)
 
 // One set of launchers per operand type; the signatures are the fp16 ones (the bf16 set casts 2-byte pointers and parameter structs: api.hip twin_call).
 struct OperandOps {

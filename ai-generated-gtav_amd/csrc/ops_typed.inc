@@ -49,6 +49,9 @@ int launch_ln_modulate(float* x, int ldx, f16* out, int ldo, int M, int D, const
 // LayerNorm(eps=1e-6) with affine weight/bias -> fp16   (model/vae.py:139,146,174)
 int launch_ln_affine(float* x, int ldx, f16* out, int ldo, int M, int D, const float* gamma, const float* beta,
                      const LnPending* pend, int* err_flag, hipStream_t stream);
+// The branch image of a pending update, y[m] = sum_s parts[s][m] + bias as 2-byte rows of ld elements: LnPending::y_save written by a launch of its own, in the
+// operand type of the set it is called on, bit for bit what the LayerNorm launch would have kept (mixed-type training handles: api_train.hip train_branch_seam)
+int launch_branch_rows(const float* parts, int nsplit, size_t slab_stride, int ld, const float* bias, f16* y, int M, int N, int* err_flag, hipStream_t stream);
 
 // Non-overlapping patch gather (im2col of a k = s = p conv):  img (NB, C, H, W) f32 -> A fp16 TILE-MAJOR, logical [M][ldo],
 // token m = (nb, gh, gw), column k = (c, ph, pw); value = a * img + b.  Columns [C p p, ldo) are zeroed.

@@ -1868,6 +1868,21 @@ int launch_err_clear(int* err_flag, int bits, hipStream_t stream) {
     GTAV_CHECK_HIP(hipGetLastError());
     return 0;
 }
+__global__ void err_fold_kernel(int* words, int* sticky, int dst_word, int n_groups) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_groups) return;
+    const int bits = words[4 + g];
+    if (!bits) return;
+    if (sticky) atomicOr(sticky + g, bits);
+    atomicOr(words + dst_word, bits);
+    atomicAnd(words + 4 + g, ~bits);
+}
+int launch_err_fold(int* words, int* sticky, int dst_word, int n_groups, hipStream_t stream) {
+    GTAV_REQUIRE(words && n_groups > 0 && dst_word >= 0 && dst_word < 4, "err_fold: bad argument");
+    hipLaunchKernelGGL(err_fold_kernel, dim3(cdiv(n_groups, 64)), dim3(64), 0, stream, words, sticky, dst_word, n_groups);
+    GTAV_CHECK_HIP(hipGetLastError());
+    return 0;
+}
 int launch_overflow_publish(const int* err_flag, float* g, hipStream_t stream) {
     if (!err_flag || !g) return 0;
     hipLaunchKernelGGL(overflow_publish_kernel, dim3(1), dim3(1), 0, stream, err_flag, g);

@@ -74,6 +74,10 @@ SIGNATURES = {
     "gtav_dit_train_allow_window": [_p, _i],
     "gtav_dit_train_set_recompute": [_p, _i],
     "gtav_dit_train_saved_bytes": [_p, C.POINTER(C.c_int64)],
+    "gtav_dit_train_allow_mixed": [_p, _i],
+    "gtav_dit_train_set_group_dtype": [_p, _i, _i, _p],
+    "gtav_dit_train_range_words": [_p, C.POINTER(C.c_int32), _p],
+    "gtav_dit_train_autorange": [_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _p],
     "gtav_dit_train_enable": [_p, _p, _l],
     "gtav_dit_train_enable_typed": [_p, _p, _l, _i],
     "gtav_dit_set_loss_scale": [_p, _f],

@@ -149,7 +149,7 @@ class DiT(_HipModule):
 
     def __init__(self, input_h=18, input_w=32, patch_size=2, in_channels=16, hidden_size=1024, depth=12, num_heads=16,
                  mlp_ratio=4.0, external_cond_dim=25, max_frames=5, *, max_batch=1, init_weights=True, trainable=False, range_policy="report",
-                 train_dtype=torch.float16, train_max_frames=None, train_recompute=False):
+                 train_dtype=torch.float16, train_max_frames=None, train_recompute=False, train_range_policy="report"):
         super().__init__()
         self._trainable = bool(trainable)    # keyword-only, not in the reference: keeps fp32 masters, gradients and AdamW state on the GPU
         # opt-in to training windows of up to train_max_frames frames (include/gtav_amd.h gtav_dit_train_allow_window); None: TRAIN_MAX_FRAMES.  The saved
@@ -174,6 +174,15 @@ class DiT(_HipModule):
         if train_dtype == torch.bfloat16 and not self._trainable:
             raise ValueError("train_dtype=torch.bfloat16 needs trainable=True (an inference model picks its operand type with set_operand_dtype)")
         self._train_bf16 = self._trainable and train_dtype == torch.bfloat16
+        # opt-in to operand groups of both types on the training handle (include/gtav_amd.h gtav_dit_train_allow_mixed): "auto" lets train_autorange() /
+        # train_set_group_dtype() move single layer groups to bf16 while the run goes on; train_dtype is then the type every group starts on.  "report" (default):
+        # one type for every group, a saturating forward skips every step (train_stats) and nothing switches
+        if train_range_policy not in ("report", "auto"):
+            raise ValueError("train_range_policy must be 'report' (one operand type for every layer group) or 'auto' (train_autorange() moves the layer groups "
+                             "whose training forward saturated to bf16 operands)")
+        if train_range_policy == "auto" and not self._trainable:
+            raise ValueError("train_range_policy='auto' needs trainable=True (an inference model has range_policy)")
+        self.train_range_policy = train_range_policy
         self._grads = None
         self._loss_scale = 1.0 if self._train_bf16 else 65536.0
         self.in_channels = in_channels
@@ -295,8 +304,9 @@ class DiT(_HipModule):
                     _lib.check(L.gtav_dit_set_weight_prefetch(self._handle, int(self._weight_prefetch)))
                 if getattr(self, "_weight_fill_policy", None) is not None:
                     _lib.check(L.gtav_dit_set_weight_fill_policy(self._handle, int(self._weight_fill_policy)))
-                for g in sorted(self._bf16_groups):                      # a re-created handle keeps the operand types chosen before
-                    _lib.check(L.gtav_dit_set_operand_dtype(self._handle, g, 1))
+                if not self._train_mixed:
+                    for g in sorted(self._bf16_groups):                  # a re-created handle keeps the operand types chosen before
+                        _lib.check(L.gtav_dit_set_operand_dtype(self._handle, g, 1))
                 if self._trainable:
                     n = C.c_int64(0)
                     _lib.check(L.gtav_dit_train_param_count(self._handle, C.byref(n)))
@@ -306,10 +316,16 @@ class DiT(_HipModule):
                         _lib.check(L.gtav_dit_train_allow_window(self._handle, self._train_max_frames))
                     if self._train_recompute:
                         _lib.check(L.gtav_dit_train_set_recompute(self._handle, 1))
+                    if self._train_mixed:
+                        _lib.check(L.gtav_dit_train_allow_mixed(self._handle, 1))
                     if self._train_bf16:
                         _lib.check(L.gtav_dit_train_enable_typed(self._handle, self._grads.data_ptr(), n.value, 1))
                     else:
                         _lib.check(L.gtav_dit_train_enable(self._handle, self._grads.data_ptr(), n.value))
+                    if self._train_mixed:                                # a re-created handle keeps the per-group types (no weight is set yet: nothing to convert)
+                        start = set(range(self.n_operand_groups)) if self._train_bf16 else set()
+                        for g in sorted(self._bf16_groups ^ start):
+                            _lib.check(L.gtav_dit_train_set_group_dtype(self._handle, g, 1 if g in self._bf16_groups else 0, _lib.current_stream()))
                     _lib.check(L.gtav_dit_set_loss_scale(self._handle, self._loss_scale))
                     if self.grad_divisor != 1.0:
                         _lib.check(L.gtav_dit_set_grad_divisor(self._handle, self.grad_divisor))
@@ -406,6 +422,84 @@ class DiT(_HipModule):
     def train_dtype(self):
         """Operand type of the training step: torch.bfloat16 (train_dtype=torch.bfloat16) or torch.float16."""
         return torch.bfloat16 if self._train_bf16 else torch.float16
+
+    @property
+    def _train_mixed(self) -> bool:
+        return self._trainable and self.train_range_policy == "auto"
+
+    def _read_group_dtypes(self):
+        """_bf16_groups from the handle (gtav_dit_get_operand_dtype): the handle is the truth after a call that may have switched groups and failed."""
+        L, d, new = _lib.load(), C.c_int32(0), set()
+        for g in range(self.n_operand_groups):
+            _lib.check(L.gtav_dit_get_operand_dtype(self._handle, g, C.byref(d)))
+            if d.value == 1:
+                new.add(g)
+        switched = sorted(new ^ self._bf16_groups)
+        self._bf16_groups = new
+        return switched
+
+    def _mixed_handle(self, who):
+        assert self._trainable, "construct the model with trainable=True"
+        if not self._train_mixed:
+            raise _lib.GtavError(f"{who}: this trainable DiT has one operand type for every layer group; construct it with train_range_policy='auto'")
+        if not self._handle:
+            self._ensure(self._capacity_b, self._capacity_t)
+
+    def train_set_group_dtype(self, dtype, groups=None):
+        """torch.float16 / torch.bfloat16 for the layer groups `groups` (None = all) of a train_range_policy="auto" model, in place (gtav_dit_train_set_group_dtype):
+        the groups' kernels and the 2-byte images of their GEMM weights change type, the fp32 masters and the AdamW state on the GPU stay as they are."""
+        if dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError(f"train_set_group_dtype: {dtype} (torch.float16 or torch.bfloat16)")
+        self._mixed_handle("train_set_group_dtype")
+        gs = range(self.n_operand_groups) if groups is None else [int(g) for g in groups]
+        L = _lib.load()
+        try:
+            with torch.cuda.device(self.device):
+                for g in gs:
+                    _lib.check(L.gtav_dit_train_set_group_dtype(self._handle, g, 1 if dtype == torch.bfloat16 else 0, _lib.current_stream()))
+        finally:
+            self._read_group_dtypes()
+
+    def train_range_words(self):
+        """The sticky per-group saturation words of the training forwards since the last read (gtav_dit_train_range_words; synchronises, clears them): a list
+        of n_operand_groups ints, what gtav_amd.train.autorange_step merges over the ranks."""
+        self._mixed_handle("train_range_words")
+        buf = (C.c_int32 * self.n_operand_groups)()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().gtav_dit_train_range_words(self._handle, buf, _lib.current_stream()))
+        return list(buf)
+
+    def train_autorange(self, merged_words=None):
+        """Between two optimisation steps: moves the fp16 layer groups whose training forward saturated since the last call to bf16 operands
+        (gtav_dit_train_autorange; synchronises) and returns their numbers.  merged_words: the words to act on in place of the handle's own (the data-parallel
+        merge of train_range_words()).  Anything else in the error words raises as check() raises it — after the switch, and operand_dtypes() is right either way."""
+        self._mixed_handle("train_autorange")
+        n = C.c_int32(0)
+        words = None if merged_words is None else (C.c_int32 * self.n_operand_groups)(*[int(w) for w in merged_words])
+        try:
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.load().gtav_dit_train_autorange(self._handle, words, C.byref(n), _lib.current_stream()))
+        finally:
+            switched = self._read_group_dtypes()
+        assert len(switched) == n.value, (switched, n.value)
+        return switched
+
+    def restore_operand_groups(self, bf16_groups):
+        """The bf16 layer groups of a checkpoint (step.json "bf16_groups", gtav_amd.train.load_state) onto this model, before its weights are sent: needs
+        train_range_policy="auto" unless they are the groups the model has anyway."""
+        new = {int(g) for g in bf16_groups}
+        if any(g < 0 or g >= self.n_operand_groups for g in new):
+            raise ValueError(f"restore_operand_groups: groups {sorted(new)} outside [0, {self.n_operand_groups})")
+        if new == self._bf16_groups:
+            return
+        if not self._train_mixed:
+            raise _lib.GtavError(f"restore_operand_groups: the checkpoint trains the layer groups {sorted(new)} on bf16 operands and the others on fp16; this model "
+                                 "has one operand type for every layer group (construct it with trainable=True, train_range_policy='auto')")
+        if self._handle:
+            self.train_set_group_dtype(torch.bfloat16, sorted(new - self._bf16_groups))
+            self.train_set_group_dtype(torch.float16, sorted(self._bf16_groups - new))
+        else:
+            self._bf16_groups = new                # (_ensure applies them to the handle it builds)
 
     @property
     def train_recompute(self) -> bool:
@@ -632,6 +726,8 @@ class DiT(_HipModule):
         new = (self._bf16_groups | gs) if dtype == torch.bfloat16 else (self._bf16_groups - gs)
         if new == self._bf16_groups:
             return
+        if self._train_mixed:
+            raise _lib.GtavError("set_operand_dtype: a trainable DiT changes the type of a layer group with train_set_group_dtype (train_range_policy='auto')")
         if self._handle:
             L = _lib.load()
             for g in sorted(new ^ self._bf16_groups):
@@ -640,7 +736,7 @@ class DiT(_HipModule):
         self._bf16_groups = new
 
     def operand_dtypes(self):
-        """torch dtype of every operand group, in group order."""
+        """torch dtype of every operand group, in group order (a train_range_policy="auto" model: as train_autorange / train_set_group_dtype left them)."""
         return [torch.bfloat16 if g in self._bf16_groups else torch.float16 for g in range(self.n_operand_groups)]
 
     def check(self):

@@ -335,14 +335,46 @@ def training_step(dit, latents: torch.Tensor, actions: Optional[torch.Tensor], t
     return loss
 
 
+ERR_F16_SAT = 2      # csrc/common.h: the saturation bit of a device error word
+
+
+def merge_range_words(words, world_size: int = 1, all_reduce=None):
+    """The data-parallel merge of the sticky saturation words (DiT.train_range_words(), one per layer group): the element-wise maximum over the ranks of whether
+    the group saturated, so that every rank derives the SAME list of groups to switch — the union of the ranks' lists — as every rank takes the same overflow skip.
+    Pure host code: `all_reduce(tensor)` reduces an int32 CPU tensor in place with MAX (default: torch.distributed.all_reduce(op=MAX), which gloo serves).
+    Returns (merged words as a list of ints, the groups whose saturation bit is set)."""
+    t = torch.tensor([1 if int(w) & ERR_F16_SAT else 0 for w in words], dtype=torch.int32)
+    rest = torch.tensor([int(w) & ~ERR_F16_SAT for w in words], dtype=torch.int32)      # other bits stay this rank's: they are reported, not acted on
+    if world_size > 1:
+        if all_reduce is None:
+            import torch.distributed as dist
+            all_reduce = lambda x: dist.all_reduce(x, op=dist.ReduceOp.MAX)
+        all_reduce(t)
+    merged = [int(r) | (ERR_F16_SAT if int(v) else 0) for v, r in zip(t.tolist(), rest.tolist())]
+    return merged, [g for g, v in enumerate(t.tolist()) if v]
+
+
+def autorange_step(dit, world_size: int = 1, all_reduce=None):
+    """Between two optimisation steps of a DiT(trainable=True, train_range_policy="auto"): reads this rank's sticky words, merges them over the ranks
+    (merge_range_words) and switches the fp16 layer groups that saturated in a training forward on ANY rank to bf16 operands.  Returns the switched groups,
+    the same list on every rank.  Raises what DiT.train_autorange raises (after the switch)."""
+    merged, _ = merge_range_words(dit.train_range_words(), world_size, all_reduce)
+    return dit.train_autorange(merged)
+
+
 class LossScaler:
     """Dynamic loss scale for the fp16 backward pass (the reference trains under bf16 autocast and needs none).  The optimizer step skips
     itself on the device when a gradient overflowed (non-finite norm or a saturated fp16 store: gtav_dit_adamw_step); every `check_every`
     steps this reads the skip counter (one synchronisation) and halves the scale if steps were skipped since the last check, or doubles it
-    after `growth_interval` clean steps — torch.cuda.amp.GradScaler's policy at a coarser cadence."""
+    after `growth_interval` clean steps — torch.cuda.amp.GradScaler's policy at a coarser cadence.
+    On a train_range_policy="auto" model skipped steps are first put to autorange_step (world_size / all_reduce: its data-parallel arguments): when a layer
+    group switched to bf16 the skips were a range problem of the forward, which no loss scale cures, and the scale is left alone for that interval."""
 
-    def __init__(self, dit, check_every: int = 50, growth_interval: int = 2000, min_scale: float = 1.0, max_scale: float = 2.0 ** 24):
+    def __init__(self, dit, check_every: int = 50, growth_interval: int = 2000, min_scale: float = 1.0, max_scale: float = 2.0 ** 24, world_size: int = 1,
+                 all_reduce=None):
         self.dit, self.check_every, self.growth_interval = dit, int(check_every), int(growth_interval)
+        self.world_size, self.all_reduce = int(world_size), all_reduce
+        self.switched = []                   # the groups the last update() moved to bf16
         self.min_scale, self.max_scale = float(min_scale), float(max_scale)
         self._calls = 0
         self._clean = 0
@@ -364,7 +396,12 @@ class LossScaler:
             # say nothing about the restored loss scale
             self._skipped_seen = skipped
             return self.dit.loss_scale
-        if skipped > self._skipped_seen:
+        self.switched = []
+        if skipped > self._skipped_seen and getattr(self.dit, "train_range_policy", "report") == "auto":
+            self.switched = autorange_step(self.dit, self.world_size, self.all_reduce)
+        if self.switched:
+            self._clean = 0
+        elif skipped > self._skipped_seen:
             self.dit.loss_scale = max(self.min_scale, self.dit.loss_scale * 0.5)
             self._clean = 0
         else:
@@ -394,9 +431,27 @@ def _operand_dtype_name(dit) -> str:
     return "bf16" if getattr(dit, "train_dtype", torch.float16) == torch.bfloat16 else "fp16"
 
 
+def _step_state(dit, global_step: int, epoch: int) -> dict:
+    """step.json's own fields: "operand_dtype" is the type the training handle started on, "bf16_groups" the layer groups that run on bf16 operands now (all of
+    them on a bf16 handle, none on an fp16 one, some after train_autorange / train_set_group_dtype on a train_range_policy="auto" model)."""
+    bf16 = [g for g, d in enumerate(dit.operand_dtypes()) if d == torch.bfloat16] if hasattr(dit, "operand_dtypes") else []
+    return {"step": int(global_step), "epoch": int(epoch), "loss_scale": float(dit.loss_scale), "operand_dtype": _operand_dtype_name(dit), "bf16_groups": bf16}
+
+
+def _restore_groups(dit, state: dict):
+    """load_state, before any weight reaches the handle: a checkpoint with SOME groups on bf16 needs a model that can hold them (DiT.restore_operand_groups
+    raises by name on one that cannot); a train_range_policy="auto" model takes the checkpoint's groups whatever they are."""
+    groups = state.get("bf16_groups")
+    if groups is None:
+        return
+    n = getattr(dit, "n_operand_groups", len(groups))
+    if 0 < len(groups) < n or getattr(dit, "train_range_policy", "report") == "auto":
+        dit.restore_operand_groups(groups)
+
+
 def save_state(dit, ckpt_dir: str, global_step: int, epoch: int, extra: Optional[dict] = None, rng=None):
     """train_dit.py:765-800 `save_checkpoint`: <dir>/model.safetensors (fp32 masters), <dir>/optimizer.safetensors (AdamW moments + step
-    counters), <dir>/step.json {"step", "epoch", "loss_scale", "operand_dtype", ...}.  Rank 0 writes; the caller barriers around it like the reference.
+    counters), <dir>/step.json {"step", "epoch", "loss_scale", "operand_dtype", "bf16_groups", ...}.  Rank 0 writes; the caller barriers around it like the reference.
     rng (a NoiseSource): its {"seed", "draw"} goes into step.json as "rng" — the whole noise stream of the resumed run."""
     import json
     import os
@@ -404,7 +459,7 @@ def save_state(dit, ckpt_dir: str, global_step: int, epoch: int, extra: Optional
     os.makedirs(ckpt_dir, exist_ok=True)
     save_model(dit, os.path.join(ckpt_dir, "model.safetensors"))
     save_file({k: v.contiguous() for k, v in dit.opt_state_dict().items()}, os.path.join(ckpt_dir, "optimizer.safetensors"))
-    state = {"step": int(global_step), "epoch": int(epoch), "loss_scale": float(dit.loss_scale), "operand_dtype": _operand_dtype_name(dit)}
+    state = _step_state(dit, global_step, epoch)
     state.update(extra or {})
     if rng is not None:
         state["rng"] = rng.state_dict()
@@ -421,10 +476,11 @@ def load_state(dit, ckpt_dir: str, steps_per_epoch: Optional[int] = None, gradie
     import os
     from safetensors.torch import load_file
     from . import weights as _w
-    dit.load_state_dict(_w.load_state_dict_file(os.path.join(ckpt_dir, "model.safetensors")))
-    dit.load_opt_state_dict(load_file(os.path.join(ckpt_dir, "optimizer.safetensors")))
     with open(os.path.join(ckpt_dir, "step.json")) as f:
         state = json.load(f)
+    _restore_groups(dit, state)              # (first: the masters below are converted into each group's type as they are sent)
+    dit.load_state_dict(_w.load_state_dict_file(os.path.join(ckpt_dir, "model.safetensors")))
+    dit.load_opt_state_dict(load_file(os.path.join(ckpt_dir, "optimizer.safetensors")))
     # the loss scale belongs to the operand type it was found for: a bf16 run's scale (1 by default) would let an fp16 backward underflow, so it is restored
     # only into a handle of the same type (a checkpoint without "operand_dtype" is fp16).  The masters and moments are fp32 and load either way.
     if "loss_scale" in state and state.get("operand_dtype", "fp16") == _operand_dtype_name(dit):

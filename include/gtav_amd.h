@@ -28,6 +28,9 @@
  *   gtav_dit_train_enable    hipMalloc + hipMemset of masters, optimizer state, saved-activation and backward workspace, two small
  *                            synchronous hipMemcpy (the multi-tensor AdamW tables)
  *   gtav_dit_train_stats     copies four floats back and synchronises `stream`
+ *   gtav_dit_train_range_words / gtav_dit_train_autorange   copy the device error words back and synchronise `stream`
+ *   gtav_dit_train_set_group_dtype (and gtav_dit_train_autorange when it switches a group)   synchronises `stream`, then a synchronous hipMemcpy of the
+ *                            optimizer's re-partitioned work-item list
  *   gtav_dit_get_opt_step / gtav_dit_set_opt_step   copy the optimizer's control words and synchronise `stream`
  *   gtav_comm_unique_id / gtav_comm_init / gtav_comm_destroy   dlopen of librccl.so on first use; RCCL's own bootstrap (blocking)
  * The library reads no environment variables (RCCL, once loaded, reads its own NCCL_* / RCCL_* variables).
@@ -208,9 +211,30 @@ int gtav_timer_calibrate(int32_t spin_us, int32_t reps, double* event_us_mean, d
  * DESIGN.md 7) and time (measured at batch 16 x 5 frames x 144 tokens: 0.96 of the forward's time more per step, 48.5 -> 62.7 ms).  gtav_dit_train_get_residual then serves k % 4 == 0 only (the other states do not outlive their
  * block).  The call itself allocates nothing; it combines with gtav_dit_train_allow_window, both operand types and every frame size.
  * gtav_dit_train_saved_bytes: bytes of the saved-activation buffers of an enabled training handle in either mode (the residual states, the per-half-block images,
- * the final LayerNorm's output, the patch matrix and, in recompute mode, 4 bytes per token and block of LayerNorm statistics' shifts). */
+ * the final LayerNorm's output, the patch matrix and, in recompute mode, 4 bytes per token and block of LayerNorm statistics' shifts).
+ * Mixed operand types: gtav_dit_train_allow_mixed(h, 1), called between gtav_dit_create and gtav_dit_train_enable[_typed] (it fails afterwards; it allocates
+ * nothing), lets the operand groups of the enabled handle change their type one by one.  gtav_dit_train_enable_typed's dtype is then the type every group STARTS
+ * on, and the loss scale keeps that type's default.  With no group switched the handle gives the bits of a handle without the opt-in.
+ *   gtav_dit_train_set_group_dtype(h, group, dtype, stream)   group -1 = every group.  In place: the group's launches move to the other type's kernels, the W / W^T
+ *       images of its GEMM weights are converted again from the fp32 masters IN the handle (no gtav_dit_set_weight / gtav_dit_finalize), its AdamW work items move
+ *       to the other type's launch.  Masters, gradients, moments and step counters are untouched; the saved forward is dropped (run gtav_dit_train_forward again).
+ *   Attribution: the launches of the training FORWARD raise their saturation bits in the group's error word; at the end of gtav_dit_train_forward and at the head
+ *       of gtav_dit_adamw_step one small launch ORs the group words into word 0 (so the step is skipped, and published to the other ranks, as on every handle)
+ *       and into one STICKY word per group, and clears them.  The backward raises word 0 directly: a saturated gradient store is the loss scale's business.
+ *       gtav_dit_zero_grad sets aside what an inference forward left in the group words (still reported by gtav_dit_check; neither a skip nor a switch).
+ *   gtav_dit_train_range_words(h, words_host, stream)   the sticky words, one int32 per group, copied back and cleared: what a data-parallel caller merges over
+ *       the ranks (element-wise OR / MAX) before every rank applies the same switches.
+ *   gtav_dit_train_autorange(h, merged_words_host, &n, stream)   call it between steps (after gtav_dit_adamw_step).  merged_words_host NULL: reads and clears the
+ *       handle's own sticky words; else uses the n_groups words given.  Every fp16 group whose word holds the saturation bit is switched to bf16 (*n of them);
+ *       THEN everything else in the error words — a saturation bit of a group that is bf16 already included — is reported as gtav_dit_check reports it.  The
+ *       switches are done when the call fails: read the types back (gtav_dit_get_operand_dtype) after every return.
+ *   gtav_dit_set_operand_dtype refuses on such a handle whatever would change a group.  All three calls fail by name on a handle without the opt-in. */
 int gtav_dit_train_allow_window(gtav_dit* h, int32_t max_frames);
 int gtav_dit_train_set_recompute(gtav_dit* h, int32_t enable);
+int gtav_dit_train_allow_mixed(gtav_dit* h, int32_t enable);
+int gtav_dit_train_set_group_dtype(gtav_dit* h, int32_t group, int32_t dtype, void* stream);
+int gtav_dit_train_range_words(gtav_dit* h, int32_t* words_host, void* stream);
+int gtav_dit_train_autorange(gtav_dit* h, const int32_t* merged_words_host, int32_t* n_switched, void* stream);
 int gtav_dit_train_saved_bytes(gtav_dit* h, int64_t* bytes);
 int gtav_dit_train_param_count(gtav_dit* h, int64_t* numel);
 int gtav_dit_train_enable(gtav_dit* h, float* grad_arena_dev, int64_t grad_arena_numel);
@@ -270,7 +294,8 @@ int gtav_dit_check(gtav_dit* h, void* stream);
  *   groups of a DiT handle: 2 l = spatial half of block l, 2 l + 1 = its temporal half, 2 depth = the patch embedding, 2 depth + 1 = the final layer
  *   gtav_dit_set_operand_dtype(h, group, dtype)   group -1 = every group.  The fp16 / bf16 images of the changed groups' GEMM weights become stale: send those weights
  *       again with gtav_dit_set_weight (any weight may be re-sent) and call gtav_dit_finalize.  Drops the captured graphs and the cached context.  Training handles
- *       keep the operand type they were enabled with (gtav_dit_train_enable: fp16; gtav_dit_train_enable_typed: fp16 or bf16 for every group).
+ *       keep the operand type they were enabled with (gtav_dit_train_enable: fp16; gtav_dit_train_enable_typed: fp16 or bf16 for every group); one that opted in
+ *       with gtav_dit_train_allow_mixed changes a group's type with gtav_dit_train_set_group_dtype / gtav_dit_train_autorange, never with this call.
  *   gtav_dit_autorange(h, &n, stream)   gtav_dit_check that RECOVERS: every fp16 group whose stores saturated since the last check is switched to bf16
  *       (*n_switched of them; weights to be re-sent as above, results since the last check to be recomputed); other errors are reported like gtav_dit_check.
  * The VAE handle has one type for all its layers. */

@@ -7,7 +7,9 @@ A/B of profiles/round7/train_step_bf16_ab.txt.
 (profiles/long_window_train/: batch 8 x 8, 4 x 16 and 2 x 32 frames, 9 216 tokens each).
 --recompute: DiT(train_recompute=True), the activation recomputation of DESIGN.md 7 (product library: give --dtype).  Every run reports the handle's saved-activation
 bytes (train_saved_bytes) and the device's free memory before and after the training handle was built.  --forward-only times gtav_dit_train_forward alone on the
-same inputs (the yardstick of the recompute mode's extra time: it re-runs L - 1 of the L blocks' forwards)."""
+same inputs (the yardstick of the recompute mode's extra time: it re-runs L - 1 of the L blocks' forwards).
+--mixed none | one | alternating: DiT(train_range_policy="auto"), the mixed operand types of DESIGN.md 7 (product library: give --dtype, the type every group starts
+on) with no group switched, with group 1 on the other type, or with every even group on it (profiles/train_mixed/)."""
 import argparse
 import json
 import os
@@ -29,9 +31,10 @@ def main():
     ap.add_argument("--dtype", choices=("fp16", "bf16"), default=None, help="operand type of the training step, on the product library")
     ap.add_argument("--recompute", action="store_true", help="DiT(train_recompute=True): recompute each block's activations in the backward pass")
     ap.add_argument("--forward-only", action="store_true", help="time the training forward (forward_train) alone instead of the optimisation step")
+    ap.add_argument("--mixed", choices=("none", "one", "alternating"), default=None, help="DiT(train_range_policy='auto') and which groups run on the other type")
     a = ap.parse_args()
-    if a.recompute and a.dtype is None:
-        ap.error("--recompute runs on the product library: give --dtype fp16 or bf16")
+    if (a.recompute or a.mixed) and a.dtype is None:
+        ap.error("--recompute / --mixed run on the product library: give --dtype fp16 or bf16")
     if a.dtype is None:
         L.load_experiments()
     else:
@@ -46,7 +49,8 @@ def main():
     F = a.frames
     from gtav_amd.model.dit import DiT
     dit = DiT(input_h=LH, input_w=LW, patch_size=2, hidden_size=1024, depth=16, num_heads=16, max_frames=F, init_weights=False, max_batch=B, trainable=True,
-              train_dtype=train_dtype, train_max_frames=F if F > 8 else None, train_recompute=a.recompute)   # DiT-S/2 at the given latent size
+              train_dtype=train_dtype, train_max_frames=F if F > 8 else None, train_recompute=a.recompute,
+              **({"train_range_policy": "auto"} if a.mixed else {}))   # DiT-S/2 at the given latent size
     dit.load_state_dict(W.synth_state_dict(W.dit_param_shapes(depth=16, input_h=LH, input_w=LW), seed=0))
     with torch.cuda.device(dev):
         torch.cuda.synchronize()
@@ -54,6 +58,9 @@ def main():
         saved = dit.train_saved_bytes()               # builds the handle: gtav_dit_create + train_enable
         torch.cuda.synchronize()
         free_after = torch.cuda.mem_get_info()[0]
+    if a.mixed in ("one", "alternating"):
+        other = torch.float16 if a.dtype == "bf16" else torch.bfloat16
+        dit.train_set_group_dtype(other, [1] if a.mixed == "one" else range(0, dit.n_operand_groups, 2))
     g = torch.Generator().manual_seed(7)
     lat = (torch.randn(B, F, 16, LH, LW, generator=g) * 0.5).to(dev)
     actions = torch.zeros(B, F, 25, device=dev)
@@ -83,7 +90,8 @@ def main():
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / a.steps * 1e3
     applied, skipped, gnorm = dit.train_stats()
-    print(json.dumps({"batch": B, "frames": F, "latent_hw": [LH, LW], "dtype": a.dtype or "fp16 (experiments library)", "recompute": a.recompute,
+    print(json.dumps({"batch": B, "frames": F, "latent_hw": [LH, LW], "dtype": a.dtype or "fp16 (experiments library)", "recompute": a.recompute, "mixed": a.mixed,
+                      "bf16_groups": [i for i, d in enumerate(dit.operand_dtypes()) if d == torch.bfloat16],
                       "what": "train_forward" if a.forward_only else "optimisation step", "ms_per_step": round(ms, 3), "loss": float(loss), "grad_norm": gnorm, "skipped": skipped,
                       "saved_bytes": saved, "free_before_enable": free_before, "free_after_enable": free_after, "handle_bytes": free_before - free_after,
                       "env": {k: v for k, v in os.environ.items() if k.startswith("GTAV_")}}))
