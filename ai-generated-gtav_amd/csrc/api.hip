@@ -387,4 +387,115 @@ int gtav_op_convert_f16(const float* src, int32_t lds, int32_t R, int32_t C, voi
     return op_ops().convert_pad(src, lds, R, C, (f16*)dst, Rp, Cp, 1.0f, tiled, (hipStream_t)stream, nullptr);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Test hooks over the backward-only training launchers (include/gtav_amd_testing.h gtav_op_train_*): what api_train.hip launches, one launcher (or the fused /
+// unfused group of them) per hook.  The caller owns every buffer; nothing is allocated and nothing synchronises.  A workspace that is too small is refused by name.
+// ------------------------------------------------------------------------------------------------
+#define GTAV_OP_WS(name, ws, have, need)                                                                                                         \
+    GTAV_REQUIRE((ws) && (have) >= (int64_t)(need), name ": workspace of %lld floats, %lld needed", (long long)((ws) ? (have) : 0), (long long)(need))
+int gtav_op_train_ln_mod_bwd(int32_t fused, const float* dxn, const float* x, const float* scale, int32_t mod_stride, int32_t frames, int32_t P, int32_t D,
+                             float* dres, int32_t accumulate, float* dshift, float* dscale, float* ws, int64_t ws_floats, void* stream) {
+    GTAV_REQUIRE(dxn && x && scale && dres && dshift && dscale, "op_train_ln_mod_bwd: null argument");
+    GTAV_REQUIRE(frames >= 1 && P >= 1 && D >= 4 && D % 4 == 0 && D <= 2048 && mod_stride >= D && mod_stride % 4 == 0 && aligned16(scale) && aligned16(dxn) &&
+                     aligned16(x) && aligned16(dres),
+                 "op_train_ln_mod_bwd: frames=%d P=%d D=%d mod_stride=%d (D a multiple of 4 up to 2048, rows read as aligned 16-byte vectors)", frames, P, D, mod_stride);
+    if (fused) {
+        GTAV_REQUIRE(ln_bwd_fused_ok(D), "op_train_ln_mod_bwd: the fused launch exists at D = 256, 512, 1024 and 2048 only, not at D=%d", D);
+        GTAV_OP_WS("op_train_ln_mod_bwd (fused)", ws, ws_floats, ln_bwd_fused_workspace(frames, P, D));
+        return launch_ln_mod_bwd_fused(dxn, x, scale, mod_stride, frames, P, D, dres, accumulate, dshift, dscale, ws, (hipStream_t)stream);
+    }
+    GTAV_OP_WS("op_train_ln_mod_bwd (row statistics)", ws, ws_floats, (int64_t)2 * frames * P);
+    RET_IF(launch_ln_mod_bwd(dxn, x, scale, mod_stride, P, frames * P, D, dres, accumulate, ws, (hipStream_t)stream));
+    return launch_frame_reduce_ln(dxn, x, ws, frames, P, D, dshift, dscale, mod_stride, (hipStream_t)stream);
+}
+int gtav_op_train_gate_bwd(int32_t fused, const float* dres, const void* y, const float* gate, int32_t mod_stride, int32_t frames, int32_t P, int32_t D,
+                           void* dy_tiled, float* dgate, float* db, float* ws, int64_t ws_floats, int32_t* err, void* stream) {
+    GTAV_REQUIRE(dres && y && dy_tiled && dgate, "op_train_gate_bwd: null argument");
+    GTAV_REQUIRE(frames >= 1 && P >= 1 && D >= 64 && D % 64 == 0 && mod_stride >= D && mod_stride % 4 == 0 && aligned16(dres) && (!gate || aligned16(gate)),
+                 "op_train_gate_bwd: frames=%d P=%d D=%d mod_stride=%d", frames, P, D, mod_stride);
+    const int M = frames * P;
+    if (fused) {
+        GTAV_OP_WS("op_train_gate_bwd (fused)", ws, ws_floats, (int64_t)frames * D);
+        return op_ops().gate_bwd_fused(dres, (const f16*)y, gate, mod_stride, frames, P, D, (f16*)dy_tiled, dgate, db, ws, err, (hipStream_t)stream);
+    }
+    GTAV_REQUIRE(db, "op_train_gate_bwd: the unfused form adds its column sums to db, which is null");
+    GTAV_OP_WS("op_train_gate_bwd (column sums)", ws, ws_floats, colsum_workspace(M, D));
+    RET_IF(op_ops().gate_bwd(dres, gate, mod_stride, P, M, D, (f16*)dy_tiled, err, (hipStream_t)stream));
+    RET_IF(op_ops().frame_reduce_gate(dres, (const f16*)y, frames, P, D, dgate, mod_stride, (hipStream_t)stream));
+    return op_ops().colsum_tiled((const f16*)dy_tiled, M, D, db, ws, (hipStream_t)stream);
+}
+int gtav_op_train_gelu_bwd(int32_t fused, const void* dh, const void* u, void* du, int32_t M, int32_t N, float* db, float* ws, int64_t ws_floats, int32_t* err,
+                           void* stream) {
+    GTAV_REQUIRE(dh && u && du && M >= 1 && N >= 64 && N % 64 == 0, "op_train_gelu_bwd: M=%d N=%d (N a multiple of 64)", M, N);
+    if (fused) {
+        GTAV_OP_WS("op_train_gelu_bwd (fused)", ws, ws_floats, (int64_t)gelu_bwd_colsum_splits(M) * N);
+        return op_ops().gelu_bwd_tiled_colsum((const f16*)dh, (const f16*)u, (f16*)du, M, N, db, ws, err, (hipStream_t)stream);
+    }
+    GTAV_REQUIRE(db, "op_train_gelu_bwd: the unfused form adds its column sums to db, which is null");
+    GTAV_OP_WS("op_train_gelu_bwd (column sums)", ws, ws_floats, colsum_workspace(M, N));
+    RET_IF(op_ops().gelu_bwd_tiled((const f16*)dh, (const f16*)u, (f16*)du, (size_t)round_up(M, 128) * N, err, (hipStream_t)stream));
+    return op_ops().colsum_tiled((const f16*)du, M, N, db, ws, (hipStream_t)stream);
+}
+int gtav_op_train_colsum_tiled(const void* dy, int32_t M, int32_t N, float* db, float* ws, int64_t ws_floats, void* stream) {
+    GTAV_REQUIRE(dy && db && M >= 1 && N >= 64, "op_train_colsum_tiled: M=%d N=%d", M, N);
+    GTAV_OP_WS("op_train_colsum_tiled", ws, ws_floats, colsum_workspace(M, N));
+    return op_ops().colsum_tiled((const f16*)dy, M, N, db, ws, (hipStream_t)stream);
+}
+int gtav_op_train_colsum_f32(const float* a, int32_t lda, int32_t M, int32_t N, float* db, float* ws, int64_t ws_floats, void* stream) {
+    GTAV_REQUIRE(a && db && M >= 1 && N >= 1 && lda >= N, "op_train_colsum_f32: M=%d N=%d lda=%d", M, N, lda);
+    GTAV_OP_WS("op_train_colsum_f32", ws, ws_floats, colsum_workspace(M, N));
+    return launch_colsum_f32(a, lda, M, N, db, ws, (hipStream_t)stream);
+}
+int gtav_op_train_colsum_reduce_multi(const float* const* ws, float* const* db, const int32_t* splits, const int32_t* N, int32_t njobs, void* stream) {
+    GTAV_REQUIRE(ws && db && splits && N, "op_train_colsum_reduce_multi: null argument");
+    GTAV_REQUIRE(njobs >= 1 && njobs <= 4, "op_train_colsum_reduce_multi: %d jobs (1 .. 4)", njobs);
+    for (int j = 0; j < njobs; ++j)
+        GTAV_REQUIRE(ws[j] && db[j] && splits[j] >= 1 && N[j] >= 1, "op_train_colsum_reduce_multi: job %d: splits=%d N=%d or a null pointer", j, splits[j], N[j]);
+    return launch_colsum_reduce_multi(ws, db, splits, N, njobs, (hipStream_t)stream);
+}
+int gtav_op_train_mse_bwd_patch(const float* vpred, const float* vtarget, int32_t B, int32_t T, int32_t C, int32_t H, int32_t W, int32_t p, float scale, void* dfo,
+                                int32_t ldf, int32_t* err, void* stream) {
+    GTAV_REQUIRE(vpred && vtarget && dfo && B >= 1 && T >= 1 && C >= 1 && p >= 1 && H >= p && W >= p && H % p == 0 && W % p == 0,
+                 "op_train_mse_bwd_patch: B=%d T=%d C=%d H=%d W=%d p=%d", B, T, C, H, W, p);
+    return op_ops().mse_bwd_patch(vpred, vtarget, B, T, C, H, W, p, scale, (f16*)dfo, ldf, err, (hipStream_t)stream);
+}
+int gtav_op_train_to_tiled(const float* a, int32_t M, int32_t D, void* out, int32_t* err, void* stream) {
+    GTAV_REQUIRE(a && out && M >= 1 && D >= 64 && aligned16(a), "op_train_to_tiled: M=%d D=%d", M, D);
+    return op_ops().to_tiled(a, M, D, (f16*)out, err, (hipStream_t)stream);
+}
+int gtav_op_train_transpose_tiled(const void* src, int32_t R, int32_t C, void* dst, void* stream) {
+    GTAV_REQUIRE(src && dst, "op_train_transpose_tiled: null argument");
+    return op_ops().transpose_tiled((const f16*)src, R, C, (f16*)dst, (hipStream_t)stream);
+}
+int gtav_op_train_convert_t(const float* src, int32_t lds, int32_t R, int32_t C, void* dst, void* stream) {
+    GTAV_REQUIRE(src && dst && R >= 1 && C >= 1 && lds >= C, "op_train_convert_T: R=%d C=%d lds=%d", R, C, lds);
+    return op_ops().convert_T(src, lds, R, C, (f16*)dst, (hipStream_t)stream);
+}
+int gtav_op_train_silu(const float* x, int32_t ldx, float* y, int32_t ldy, int32_t R, int32_t C, void* stream) {
+    GTAV_REQUIRE(x && y && R >= 1 && C >= 1 && ldx >= C && ldy >= C, "op_train_silu: R=%d C=%d ldx=%d ldy=%d", R, C, ldx, ldy);
+    return launch_silu(x, ldx, y, ldy, R, C, (hipStream_t)stream);
+}
+int gtav_op_train_silu_bwd(const float* dy, int32_t lddy, const float* x, int32_t ldx, float* dx, int32_t lddx, int32_t R, int32_t C, void* stream) {
+    GTAV_REQUIRE(dy && x && dx && R >= 1 && C >= 1 && lddy >= C && ldx >= C && lddx >= C, "op_train_silu_bwd: R=%d C=%d lddy=%d ldx=%d lddx=%d", R, C, lddy, ldx, lddx);
+    return launch_silu_bwd(dy, lddy, x, ldx, dx, lddx, R, C, (hipStream_t)stream);
+}
+int gtav_op_train_gemm_tn_f32(const float* dY, int32_t lddy, const float* X, int32_t ldx, int32_t R, int32_t N, int32_t K, float* dW, int32_t lddw, void* stream) {
+    GTAV_REQUIRE(dY && X && dW && R >= 1 && N >= 1 && K >= 1 && lddy >= N && ldx >= K && lddw >= K, "op_train_gemm_tn_f32: R=%d N=%d K=%d lddy=%d ldx=%d lddw=%d", R, N, K,
+                 lddy, ldx, lddw);
+    // the matrix-core kernel (N % 64 == 0 and K % 64 == 0) updates dW by 16-byte vectors
+    GTAV_REQUIRE(N % 64 || K % 64 || (lddw % 4 == 0 && aligned16(dW)), "op_train_gemm_tn_f32: dW rows must be 16-byte aligned at N=%d K=%d (lddw=%d)", N, K, lddw);
+    return launch_gemm_tn_f32(dY, lddy, X, ldx, R, N, K, dW, lddw, (hipStream_t)stream);
+}
+int gtav_op_train_gemm_nn_f32(const float* dY, int32_t lddy, const float* W, int32_t ldw, int32_t R, int32_t N, int32_t K, float* dX, int32_t lddx, void* stream) {
+    GTAV_REQUIRE(dY && W && dX && R >= 1 && N >= 1 && K >= 1 && lddy >= N && ldw >= K && lddx >= K && aligned16(dY), "op_train_gemm_nn_f32: R=%d N=%d K=%d lddy=%d ldw=%d lddx=%d",
+                 R, N, K, lddy, ldw, lddx);
+    return launch_gemm_nn_f32(dY, lddy, W, ldw, R, N, K, dX, lddx, (hipStream_t)stream);
+}
+int gtav_op_train_ada_bwd_dx(const float* dmod, int32_t MODW, const float* W, int32_t D, int32_t R, float* dSc, float* part, int64_t part_floats, void* stream) {
+    GTAV_REQUIRE(dmod && W && dSc && MODW >= 1 && D >= 1 && R >= 1, "op_train_ada_bwd_dx: MODW=%d D=%d R=%d", MODW, D, R);
+    GTAV_OP_WS("op_train_ada_bwd_dx", part, part_floats, ada_bwd_dx_workspace(MODW, D, R));
+    return launch_ada_bwd_dx(dmod, MODW, W, D, R, dSc, part, (hipStream_t)stream);
+}
+#undef GTAV_OP_WS
+
 }  // extern "C"

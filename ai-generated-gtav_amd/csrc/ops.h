@@ -114,7 +114,7 @@ int launch_frame_reduce_ln(const float* dxn, const float* x, const float* stats,
                            hipStream_t stream);
 int gelu_bwd_colsum_splits(int M);
 int launch_colsum_reduce_multi(const float* const* ws, float* const* db, const int* splits, const int* N, int njobs, hipStream_t stream);
-// launch_ln_mod_bwd + launch_frame_reduce_ln in one pass over dxn and x (M = frames x P rows)
+// launch_ln_mod_bwd + launch_frame_reduce_ln in one pass over dxn and x (M = frames x P rows); ln_bwd_fused_ok: D = 256, 512, 1024 or 2048
 bool ln_bwd_fused_ok(int D);
 size_t ln_bwd_fused_workspace(int frames, int P, int D);
 int launch_ln_mod_bwd_fused(const float* dxn, const float* x, const float* scale, int mod_stride, int frames, int P, int D, float* dres, int accumulate,
@@ -126,10 +126,11 @@ int launch_silu(const float* x, int ldx, float* y, int ldy, int R, int C, hipStr
 int launch_silu_bwd(const float* dy, int lddy, const float* x, int ldx, float* dx, int lddx, int R, int C, hipStream_t stream);
 int launch_gemm_tn_f32(const float* dY, int lddy, const float* X, int ldx, int R, int N, int K, float* dW, int lddw, hipStream_t stream);   // dW += dY^T X
 int launch_gemm_nn_f32(const float* dY, int lddy, const float* W, int ldw, int R, int N, int K, float* dX, int lddx, hipStream_t stream);   // dX = dY W
-// dSc [R][D] = dmod [R][MODW] x W_ada [MODW][D].  `part` = workspace of ada_bwd_dx_workspace(MODW, D, R) floats (fp32 MFMA path: per-chunk partial
-// sums reduced in a fixed order); nullptr selects the VALU kernel, which accumulates with atomics.  dSc is overwritten.
+// dSc [R][D] = dmod [R][MODW] x W_ada [MODW][D].  `part` = workspace of ada_bwd_dx_workspace(MODW, D, R) floats, REQUIRED (nullptr is refused by name): both
+// kernels store per-chunk partial sums there and a second launch adds the chunks in a fixed order.  The fp32 MFMA kernel runs where D % 64 == 0, D <= 1024 and
+// R <= 80; every other shape takes the VALU kernel.  No atomics on either path.  dSc is overwritten.
 size_t ada_bwd_dx_workspace(int MODW, int D, int R);
-int launch_ada_bwd_dx(const float* dmod, int MODW, const float* W, int D, int R, float* dSc, float* part, hipStream_t stream);                         // dSc += dmod W_ada
+int launch_ada_bwd_dx(const float* dmod, int MODW, const float* W, int D, int R, float* dSc, float* part, hipStream_t stream);                         // dSc = dmod W_ada
 int sumsq_parts(size_t n);                                                         // per-block partial sums written by launch_sumsq
 int launch_sumsq(const float* g, size_t n, float* part, hipStream_t stream);
 // adds the partial sums in order (ctl[0]); err_flag (optional): ERR_F16_SAT / ERR_NONFINITE in the handle's error word count as overflow

@@ -98,6 +98,9 @@ __global__ void gelu_bwd_tiled_kernel(const f16* __restrict__ dh, const f16* __r
 // LayerNorm (eps 1e-6, no affine) + modulate backward, one block per token row (D / 4 threads):
 //   xhat = (x - mean) rstd,  g = dxn (1 + scale + 1e-6),  dx = rstd (g - mean(g) - xhat mean(g xhat))
 //   dres[m] = (accumulate ? dres[m] : 0) + dx;   stats[m] = (mean, rstd) for the per-frame reductions
+// The row is centred as (x - K) - mean(x - K), K = its first element, like the forward LayerNorm (elementwise.hip): x - fl(mean x) rounds the mean to an ulp of
+// |x| first, which on a row of 300 +- 0.02 is 7.6e-4 of the standard deviation — xhat, and dscale with it, left the project's LayerNorm bound there
+// (tests/test_gpu_ops_train.py test_ln_mod_bwd_large_mean_rows).  stats[m].mean is the mean of x - K; frame_reduce_ln_kernel subtracts the same K.
 // The adaLN gradients are sums over the P tokens of a frame: dshift = sum dxn, dscale = sum dxn xhat (frame_reduce_ln_kernel).
 // ------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(512) void ln_mod_bwd_kernel(const float* __restrict__ dxn, const float* __restrict__ x, const float* __restrict__ scale,
@@ -108,8 +111,9 @@ __global__ __launch_bounds__(512) void ln_mod_bwd_kernel(const float* __restrict
     const bool act = c < D;
     const float* sc = scale + (size_t)(m / rows_per_mod) * mod_stride;
     f32x4 xv = f32x4{0.f, 0.f, 0.f, 0.f}, gv = xv, sv = xv;
+    const float K = x[(size_t)m * D];
     if (act) {
-        xv = *(const f32x4*)(x + (size_t)m * D + c);
+        xv = *(const f32x4*)(x + (size_t)m * D + c) - K;
         gv = *(const f32x4*)(dxn + (size_t)m * D + c);
         sv = *(const f32x4*)(sc + c);
     }
@@ -145,7 +149,7 @@ __global__ __launch_bounds__(256) void frame_reduce_ln_kernel(const float* __res
             const size_t m = (size_t)f * P + t;
             const float g = dxn[m * D + d];
             a += g;
-            b += g * (x[m * D + d] - stats[2 * m]) * stats[2 * m + 1];
+            b += g * ((x[m * D + d] - x[m * D]) - stats[2 * m]) * stats[2 * m + 1];
         }
     ra[tg][dl] = a;
     rb[tg][dl] = b;
@@ -183,9 +187,13 @@ __global__ __launch_bounds__(256) void ln_mod_bwd_fused_kernel(const float* __re
             xv[q] = *(const f32x4*)(x + m * D + 4 * (lane + 64 * q));
             gv[q] = *(const f32x4*)(dxn + m * D + 4 * (lane + 64 * q));
         }
+        const float K = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, xv[0][0])));   // the row's first element (ln_mod_bwd_kernel)
         float s = 0.f;
 #pragma unroll
-        for (int q = 0; q < NV; ++q) s += (xv[q][0] + xv[q][1]) + (xv[q][2] + xv[q][3]);
+        for (int q = 0; q < NV; ++q) {
+            xv[q] = xv[q] - K;
+            s += (xv[q][0] + xv[q][1]) + (xv[q][2] + xv[q][3]);
+        }
         const float mean = wave_sum_dpp(s) / (float)D;
         s = 0.f;
 #pragma unroll
@@ -1656,7 +1664,7 @@ int launch_ln_mod_bwd(const float* dxn, const float* x, const float* scale, int 
     GTAV_CHECK_HIP(hipGetLastError());
     return 0;
 }
-// fused form of launch_ln_mod_bwd + launch_frame_reduce_ln (D = 1024 or 2048; part: ln_bwd_fused_workspace(frames, P, D) floats)
+// fused form of launch_ln_mod_bwd + launch_frame_reduce_ln (D = 256, 512, 1024 or 2048; part: ln_bwd_fused_workspace(frames, P, D) floats)
 bool ln_bwd_fused_ok(int D) { return D == 1024 || D == 2048 || D == 512 || D == 256; }
 size_t ln_bwd_fused_workspace(int frames, int P, int D) { return (size_t)frames * (size_t)cdiv(P, 16) * 2 * (size_t)D; }
 int launch_ln_mod_bwd_fused(const float* dxn, const float* x, const float* scale, int mod_stride, int frames, int P, int D, float* dres, int accumulate,

@@ -164,6 +164,22 @@ SIGNATURES = {
     "gtav_op_gemm_set_wm": [_i],
     "gtav_op_set_operand_dtype": [_i],
     "gtav_op_attn_spatial_prescaled": [_p, _p, _p, _p, _i, _i, _i, _p],
+    # test hooks over the backward-only training launchers (include/gtav_amd_testing.h)
+    "gtav_op_train_ln_mod_bwd": [_i, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p, _p, _p, _l, _p],
+    "gtav_op_train_gate_bwd": [_i, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _l, _p, _p],
+    "gtav_op_train_gelu_bwd": [_i, _p, _p, _p, _i, _i, _p, _p, _l, _p, _p],
+    "gtav_op_train_colsum_tiled": [_p, _i, _i, _p, _p, _l, _p],
+    "gtav_op_train_colsum_f32": [_p, _i, _i, _i, _p, _p, _l, _p],
+    "gtav_op_train_colsum_reduce_multi": [C.POINTER(_p), C.POINTER(_p), C.POINTER(_i), C.POINTER(_i), _i, _p],
+    "gtav_op_train_mse_bwd_patch": [_p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _i, _p, _p],
+    "gtav_op_train_to_tiled": [_p, _i, _i, _p, _p, _p],
+    "gtav_op_train_transpose_tiled": [_p, _i, _i, _p, _p],
+    "gtav_op_train_convert_t": [_p, _i, _i, _i, _p, _p],
+    "gtav_op_train_silu": [_p, _i, _p, _i, _i, _i, _p],
+    "gtav_op_train_silu_bwd": [_p, _i, _p, _i, _p, _i, _i, _i, _p],
+    "gtav_op_train_gemm_tn_f32": [_p, _i, _p, _i, _i, _i, _i, _p, _i, _p],
+    "gtav_op_train_gemm_nn_f32": [_p, _i, _p, _i, _i, _i, _i, _p, _i, _p],
+    "gtav_op_train_ada_bwd_dx": [_p, _i, _p, _i, _i, _p, _p, _l, _p],
 }
 _RESTYPES = {"gtav_last_error": C.c_char_p, "gtav_dit_destroy": None, "gtav_vae_destroy": None, "gtav_op_gemm_set_stages": None,
              "gtav_op_gemm_set_wm": None, "gtav_op_set_operand_dtype": None}

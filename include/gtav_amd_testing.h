@@ -36,6 +36,23 @@
  * gtav_op_attn_spatial_prescaled   gtav_op_attn_spatial on a q that already carries 1/8 log2 e (the form the VAE's flash attention runs, GemmParams::rope_cs_q);
  *                             refused at the sequence lengths whose kernel takes plain q.  Honours the operand type above.
  * tests/test_gpu_ops_typed.py runs every one of these in both operand types against fp64 math with per-element bounds.
+ *
+ * gtav_op_train_*             the backward-only kernels of the training step (csrc/train.hip), each a thin call of the launcher(s) a training handle runs.  The 2-byte
+ *                             ones dispatch per gtav_op_set_operand_dtype like gtav_op_gemm_tn (with bf16 set, every 2-byte buffer holds bf16); the fp32 conditioning
+ *                             path (colsum_f32, colsum_reduce_multi, silu, silu_bwd, gemm_tn_f32, gemm_nn_f32, ada_bwd_dx) ignores it.  The caller owns EVERY
+ *                             buffer — workspaces and the device error word `err` (may be null) included; a hook allocates nothing and never synchronises.  A
+ *                             workspace comes with its size in floats and the hook refuses by name when the launcher's own *_workspace / *_splits function asks
+ *                             for more.  `fused` picks between the one-pass launch a handle normally runs (1) and the separate launches it replaces (0):
+ *   ln_mod_bwd            1: launch_ln_mod_bwd_fused (D = 256 / 512 / 1024 / 2048, ws = ln_bwd_fused_workspace(frames, P, D));  0: launch_ln_mod_bwd +
+ *                             launch_frame_reduce_ln (any D % 4 == 0 up to 2048, ws = the 2 frames P floats of row statistics)
+ *   gate_bwd              1: launch_gate_bwd_fused (ws = frames x D; db null leaves the per-frame bias partial sums in ws for colsum_reduce_multi);
+ *                             0: launch_gate_bwd + launch_frame_reduce_gate + launch_colsum_tiled_f16 (ws = colsum_workspace(frames P, D), db required)
+ *   gelu_bwd              1: launch_gelu_bwd_tiled_colsum (ws = gelu_bwd_colsum_splits(M) x N; db null leaves the per-split partial sums in ws);
+ *                             0: launch_gelu_bwd_tiled over the whole 128-row-padded image + launch_colsum_tiled_f16 (ws = colsum_workspace(M, N), db required)
+ *   colsum_tiled, colsum_f32   db[n] += column sums (ws = colsum_workspace(M, N));  colsum_reduce_multi: 1 .. 4 jobs, host arrays of device pointers
+ *   mse_bwd_patch, to_tiled, transpose_tiled, convert_t (launch_convert_T_f16)   the loss gradient and the layout converters
+ *   silu, silu_bwd, gemm_tn_f32 (dW += dY^T X), gemm_nn_f32 (dX = dY W), ada_bwd_dx (part = ada_bwd_dx_workspace(MODW, D, R))
+ * tests/test_gpu_ops_train.py runs them against fp64 math with the bounds of tests/parity_bounds.py.
  * (Timing experiments that change results, and the block shapes that measured slower than these, exist only in the separate
  * -DGTAV_EXPERIMENTS build: csrc/build.sh exp -> libgtav_amd_exp.so, loaded by tools/ only.) */
 #ifndef GTAV_AMD_TESTING_H
@@ -53,6 +70,27 @@ void gtav_op_gemm_set_stages(int32_t ns);
 void gtav_op_gemm_set_wm(int32_t wm);
 void gtav_op_set_operand_dtype(int32_t dtype);   /* GTAV_OPERAND_F16 (default) / GTAV_OPERAND_BF16, per thread */
 int gtav_op_attn_spatial_prescaled(const void* q, const void* k, const void* vt, void* o, int32_t NB, int32_t heads, int32_t S, void* stream);
+
+/* ---- backward-only training kernels (see above); M = frames x P token rows, 2-byte buffers in the thread's operand type ---- */
+int gtav_op_train_ln_mod_bwd(int32_t fused, const float* dxn, const float* x, const float* scale, int32_t mod_stride, int32_t frames, int32_t P, int32_t D,
+                             float* dres, int32_t accumulate, float* dshift, float* dscale, float* ws, int64_t ws_floats, void* stream);
+int gtav_op_train_gate_bwd(int32_t fused, const float* dres, const void* y, const float* gate, int32_t mod_stride, int32_t frames, int32_t P, int32_t D,
+                           void* dy_tiled, float* dgate, float* db, float* ws, int64_t ws_floats, int32_t* err, void* stream);
+int gtav_op_train_gelu_bwd(int32_t fused, const void* dh, const void* u, void* du, int32_t M, int32_t N, float* db, float* ws, int64_t ws_floats, int32_t* err,
+                           void* stream);
+int gtav_op_train_colsum_tiled(const void* dy, int32_t M, int32_t N, float* db, float* ws, int64_t ws_floats, void* stream);
+int gtav_op_train_colsum_f32(const float* a, int32_t lda, int32_t M, int32_t N, float* db, float* ws, int64_t ws_floats, void* stream);
+int gtav_op_train_colsum_reduce_multi(const float* const* ws, float* const* db, const int32_t* splits, const int32_t* N, int32_t njobs, void* stream);
+int gtav_op_train_mse_bwd_patch(const float* vpred, const float* vtarget, int32_t B, int32_t T, int32_t C, int32_t H, int32_t W, int32_t p, float scale, void* dfo,
+                                int32_t ldf, int32_t* err, void* stream);
+int gtav_op_train_to_tiled(const float* a, int32_t M, int32_t D, void* out, int32_t* err, void* stream);
+int gtav_op_train_transpose_tiled(const void* src, int32_t R, int32_t C, void* dst, void* stream);
+int gtav_op_train_convert_t(const float* src, int32_t lds, int32_t R, int32_t C, void* dst, void* stream);
+int gtav_op_train_silu(const float* x, int32_t ldx, float* y, int32_t ldy, int32_t R, int32_t C, void* stream);
+int gtav_op_train_silu_bwd(const float* dy, int32_t lddy, const float* x, int32_t ldx, float* dx, int32_t lddx, int32_t R, int32_t C, void* stream);
+int gtav_op_train_gemm_tn_f32(const float* dY, int32_t lddy, const float* X, int32_t ldx, int32_t R, int32_t N, int32_t K, float* dW, int32_t lddw, void* stream);
+int gtav_op_train_gemm_nn_f32(const float* dY, int32_t lddy, const float* W, int32_t ldw, int32_t R, int32_t N, int32_t K, float* dX, int32_t lddx, void* stream);
+int gtav_op_train_ada_bwd_dx(const float* dmod, int32_t MODW, const float* W, int32_t D, int32_t R, float* dSc, float* part, int64_t part_floats, void* stream);
 
 #ifdef __cplusplus
 }

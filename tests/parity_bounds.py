@@ -1,5 +1,6 @@
 """Inputs, fp64 references, error bounds and fp32 emulations of the operand-typed kernels, shared by tests/test_gpu_ops_typed.py (the kernels, on a GPU) and
-tests/test_host_parity_bounds.py (the bounds themselves, on the CPU).  Pure torch: nothing here loads the library.
+tests/test_host_parity_bounds.py (the bounds themselves, on the CPU).  Pure torch: nothing here loads the library.  The second half of the file holds the same
+for the backward-only training kernels (tests/test_gpu_ops_train.py), with its own head comment.
 
 None of the bounds is taken from the code under test.  u is the unit roundoff of the operand type, 2^-11 for fp16 and 2^-8 for bf16.
 
@@ -365,3 +366,408 @@ class TemporalCase:
 @functools.lru_cache(maxsize=None)
 def temporal_case(B, P, D, Tq, t0, Tmax, dtype):
     return TemporalCase(B, P, D, Tq, t0, Tmax, dtype)
+
+
+# =======================================================================================================================================================
+# The backward-only training kernels (csrc/train.hip): inputs, fp64 references, bounds and fp32 emulations shared by tests/test_gpu_ops_train.py (GPU) and
+# tests/test_host_parity_bounds.py (CPU).  eps = 2^-24 is the unit roundoff of fp32.  Every figure below is a count of roundings or a project constant.
+#
+# An fp32 sum of n terms (frame sums, bias sums, column sums, the fp32 conditioning GEMMs):
+#     |got - ref| <= (n + 2) eps sum |term|          (acc_term's convention: n terms added in ANY order pass n - 1 additions, + the rounding of the product in
+#   front and of the `+=` behind; doubled where an fp32 MFMA adds, whose internal rounding is not documented).  |term| includes the old value of an
+#   accumulating output.
+# Bias sums: the FUSED launches (gate_bwd_fused, gelu_bwd_tiled_colsum) add the UNROUNDED fp32 products; the unfused forms add the 2-byte dy / du the first
+#   launch stored, each off by u |term| (one round to nearest) + half a subnormal step — an intended difference of the two forms, so the unfused bound is the
+#   fused one + u sum |term| + n subnormal steps.
+# A value rounded once to 2 bytes from a short fp32 expression: store_bound(ref, acc, dtype), acc = the fp32 roundings of the expression (2 eps |ref| for a
+#   product of two or three factors) and, for GELU', the error of its own fp32 evaluation (gelu_grad_eval_error).
+# =======================================================================================================================================================
+EPS32 = 2.0 ** -24
+ERR_F16_SAT = 2               # csrc/common.h
+F16_MAX = 65504.0
+
+
+def sum_bound(n, mag, mfma=False):
+    return (2.0 if mfma else 1.0) * (n + 2) * EPS32 * mag
+
+
+def frame_sum(v, frames, P, drop_last=False):
+    """[frames P][D] -> [frames][D], the sum over a frame's tokens.  drop_last: the WRONG sum that leaves out the last token of every frame (the last row of the
+    last, partial 16-row chunk of the fused kernels)"""
+    v = v.reshape(frames, P, -1)
+    return (v[:, :P - 1] if drop_last else v).sum(1)
+
+
+# ---- LayerNorm + modulate backward (fp32 only) -----------------------------------------------------------------------------------------------------------
+LN_BWD_SHAPES = [(256, 3, 24), (512, 2, 16), (1024, 2, 40), (2048, 1, 17), (384, 2, 24), (100, 1, 5)]      # (D, frames, P); the last two: no fused kernel
+LN_BWD_FUSED_D = (256, 512, 1024, 2048)
+
+
+class LnBwdCase:
+    """dres = (accumulate ? old : 0) + rstd (g - mean g - xhat mean(g xhat)), g = dxn (1 + scale + 1e-6); dshift = sum_t dxn, dscale = sum_t dxn xhat.
+    scale / dshift / dscale live in tables of row length 3 D + 64 at the column offsets SC / SH / DS (multiples of 4: the kernels read scale as 16-byte vectors).
+
+    Forward error of the fp32 evaluation, per element (first order in eps; every count is the number of roundings the value passes, + 2 as in sum_bound):
+      a = x - K, K = the row's first element (what the kernels centre on, like the forward LayerNorm): eps |a|
+      mean a   e_m  = (D + 3) eps mean|a|
+      d = a - mean a:  e_d = e_m + eps (|a| + |d|)
+      variance e_v  = e_m^2 + (D + 4) eps var        (the mean's error enters at second order only: sum d = 0)
+      rstd     rho  = e_v / (2 (var + 1e-6)) + 3 eps   (relative: the addition, the square root, the division)
+      xhat     e_xh = e_d rstd + |xhat| (rho + eps)
+      g        3 eps |g|;   s1 = mean g: e_s1 = (D + 5) eps mean|g|;   s2 = mean(g xhat): e_s2 = (D + 6) eps mean|g xhat| + mean(|g| e_xh)
+      dx       e_dx = rstd (6 eps |g| + e_s1 + 3 eps |s1| + e_xh |s2| + |xhat| (e_s2 + 3 eps |s2|)) + (rho + eps) rstd (|g| + |s1| + |xhat s2|)
+      dres     e_dx + eps (|old| + |dx|)  with accumulate
+      dshift   sum_bound(P, sum_t |dxn|);   dscale: sum_bound(P, sum_t |dxn xhat|) + sum_t |dxn| e_xh
+    large_mean (rows of 300 +- 0.02, as ln_large_mean_case): because the bound follows the CENTRED arithmetic it stays sharp there (|a| is 0.03, not 300); a kernel
+    that forms x - fl(mean x) instead is off by half an ulp of 300 = 1.5e-5 in the mean at least, 7.6e-4 of the standard deviation, and leaves it.  The tests hold
+    dres and dscale of that set to the per-ROW relative L2 LN_TOL (the project's LayerNorm figure) as well."""
+
+    def __init__(self, D, frames, P, large_mean=False):
+        self.D, self.frames, self.P, self.M = D, frames, P, frames * P
+        M = self.M
+        self.stride, self.SC, self.SH, self.DS = 3 * D + 64, D + 32, 32, 2 * D + 64
+        self.x = (300.0 + 0.02 * rand(M, D, seed=5)) if large_mean else rand(M, D, seed=1) * 3 + 0.5
+        self.dxn = rand(M, D, seed=2)
+        self.mod = rand(frames, self.stride, seed=3)
+        self.old = rand(M, D, seed=4)
+        x, dxn = self.x.double(), self.dxn.double()
+        sc = self.mod[:, self.SC:self.SC + D].double().repeat_interleave(P, 0)
+        mu = x.mean(-1, keepdim=True)
+        d = x - mu
+        var = (d * d).mean(-1, keepdim=True)
+        r = 1.0 / torch.sqrt(var + 1e-6)
+        xh = d * r
+        g = dxn * (1.0 + (sc + 1e-6))
+        s1, s2 = g.mean(-1, keepdim=True), (g * xh).mean(-1, keepdim=True)
+        self.ref_dx = r * (g - s1 - xh * s2)
+        self.ref_dshift, self.ref_dscale = frame_sum(dxn, frames, P), frame_sum(dxn * xh, frames, P)
+        e = EPS32
+        a = x - x[:, :1]
+        e_m = (D + 3) * e * a.abs().mean(-1, keepdim=True)
+        e_d = e_m + e * (a.abs() + d.abs())
+        e_v = e_m ** 2 + (D + 4) * e * var
+        rho = e_v / (2 * (var + 1e-6)) + 3 * e
+        e_xh = e_d * r + xh.abs() * (rho + e)
+        e_s1 = (D + 5) * e * g.abs().mean(-1, keepdim=True)
+        e_s2 = (D + 6) * e * (g * xh).abs().mean(-1, keepdim=True) + (g.abs() * e_xh).mean(-1, keepdim=True)
+        self.tol_dx = r * (6 * e * g.abs() + e_s1 + 3 * e * s1.abs() + e_xh * s2.abs() + xh.abs() * (e_s2 + 3 * e * s2.abs())) + \
+            (rho + e) * r * (g.abs() + s1.abs() + (xh * s2).abs())
+        self.tol_dshift = sum_bound(P, frame_sum(dxn.abs(), frames, P))
+        self.tol_dscale = sum_bound(P, frame_sum((dxn * xh).abs(), frames, P)) + frame_sum(dxn.abs() * e_xh, frames, P)
+
+    def ref_dres(self, accumulate):
+        return self.ref_dx + self.old.double() if accumulate else self.ref_dx
+
+    def tol_dres(self, accumulate):
+        return self.tol_dx + EPS32 * (self.old.double().abs() + self.ref_dx.abs()) if accumulate else self.tol_dx
+
+    def emulate(self, accumulate, wrong=None):
+        """the kernels' arithmetic in fp32 (sums in torch's order) -> dres, dshift, dscale.  wrong: "scale0" = the scale row of frame 0 for every frame,
+        "noacc" = accumulate ignored, "var" = variance over D - 1, "drop" = the frame sums without the last token, "plain" = x - fl(mean x) without the
+        centring on the row's first element"""
+        D, P, frames = self.D, self.P, self.frames
+        x, dxn = self.x, self.dxn
+        sc = self.mod[:, self.SC:self.SC + D]
+        sc = sc[:1].expand(frames, D) if wrong == "scale0" else sc
+        sc = sc.repeat_interleave(P, 0)
+        a = x if wrong == "plain" else x - x[:, :1]
+        d = a - a.sum(-1, keepdim=True) / D
+        var = (d * d).sum(-1, keepdim=True) / (D - 1 if wrong == "var" else D)
+        r = 1.0 / torch.sqrt(var + 1e-6)
+        xh = d * r
+        g = dxn * (1.0 + (sc + 1e-6))
+        s1, s2 = g.sum(-1, keepdim=True) / D, (g * xh).sum(-1, keepdim=True) / D
+        dx = r * (g - s1 - xh * s2)
+        if accumulate and wrong != "noacc":
+            dx = dx + self.old
+        return dx, frame_sum(dxn, frames, P, wrong == "drop"), frame_sum(dxn * xh, frames, P, wrong == "drop")
+
+
+@functools.lru_cache(maxsize=None)
+def ln_bwd_case(D, frames, P, large_mean=False):
+    return LnBwdCase(D, frames, P, large_mean)
+
+
+# ---- gate backward (2-byte dy, fp32 dgate and bias sums) ------------------------------------------------------------------------------------------------------
+GATE_BWD_SHAPES = [(256, 3, 24), (128, 2, 5), (1024, 1, 144)]      # (D, frames, P)
+
+
+class GateBwdCase:
+    """dy = gate dres rounded to 2 bytes (gate None: 1); dgate[f] = sum_t dres y; db += sum_m dy.  gate sits at column offset G of a table of row length 3 D + 64,
+    dgate goes to the same columns of a table of its own.  sat: ONE product is 70000, beyond fp16 — fp16 stores +-65504 there and raises ERR_F16_SAT, bf16 stores
+    the rounded value.
+      dy      store_bound(ref, 2 eps |ref|)            one product (no product at all without a gate)
+      dgate   sum_bound(P, sum_t |dres y|)
+      db      fused: sum_bound(M, sum_m |dy| + |old|);  unfused: + u sum_m |dy| + M subnormal steps (see the head of this section)"""
+
+    def __init__(self, D, frames, P, dtype, gated=True, sat=False):
+        self.D, self.frames, self.P, self.M, self.dtype = D, frames, P, frames * P, dtype
+        M = self.M
+        self.stride, self.G = 3 * D + 64, 2 * D + 32
+        self.dres = rand(M, D, seed=1)
+        self.y = rand(M, D, seed=2).to(dtype)
+        self.mod = rand(frames, self.stride, seed=3)
+        self.db0 = rand(D, seed=4)
+        self.sat_at = None
+        if sat:
+            m0, d0 = M - 2, D - 3
+            gv = self.mod[m0 // P, self.G + d0].item() if gated else 1.0
+            self.dres[m0, d0] = 70000.0 / gv
+            self.sat_at = (m0, d0)
+        self.gate = self.mod[:, self.G:self.G + D] if gated else None
+        gr = self.gate.double().repeat_interleave(P, 0) if gated else torch.ones(M, D, dtype=torch.float64)
+        dres, y = self.dres.double(), self.y.double()
+        self.ref_dy = gr * dres
+        self.tol_dy = store_bound(self.ref_dy, 2 * EPS32 * self.ref_dy.abs(), dtype)
+        self.ref_dgate = frame_sum(dres * y, frames, P)
+        self.tol_dgate = sum_bound(P, frame_sum((dres * y).abs(), frames, P))
+        mag = self.ref_dy.abs().sum(0)
+        self.ref_db = self.db0.double() + self.ref_dy.sum(0)
+        self.tol_db_fused = sum_bound(M, mag + self.db0.double().abs())
+        self.tol_db_unfused = self.tol_db_fused + U[dtype] * mag + M * SUBNORMAL[dtype]
+
+    def tol_db(self, fused):
+        return self.tol_db_fused if fused else self.tol_db_unfused
+
+    def emulate(self, fused, store=store_rne, drop=False, assign=False):
+        """fp32 arithmetic -> dy (2 bytes), dgate, db.  drop: frame sums without the last token; assign: db = in place of db +="""
+        D, P, frames = self.D, self.P, self.frames
+        gr = self.gate.repeat_interleave(P, 0) if self.gate is not None else None
+        dy32 = self.dres * gr if gr is not None else self.dres.clone()
+        dy = store(dy32, self.dtype)
+        dgate = frame_sum(self.dres * self.y.float(), frames, P, drop)
+        if fused:
+            parts = frame_sum(self.dres, frames, P, drop)
+            s = (parts * self.gate if self.gate is not None else parts).sum(0)
+        else:
+            s = dy.float().sum(0)
+        return dy, dgate, (s if assign else self.db0 + s)
+
+
+@functools.lru_cache(maxsize=None)
+def gate_bwd_case(D, frames, P, dtype, gated=True, sat=False):
+    return GateBwdCase(D, frames, P, dtype, gated, sat)
+
+
+# ---- GELU(tanh) backward with the fc1 bias sums ------------------------------------------------------------------------------------------------------------
+GELU_BWD_SHAPES = [(100, 128), (512, 64), (513, 256), (1100, 128)]     # (M, N): 1, 1, 2 and 3 row splits of the 128-padded image
+GELU_K, GELU_C = math.sqrt(2.0 / math.pi), 0.044715
+
+
+def gelu_grad64(u):
+    """d/du GELU_tanh(u) = s + T (1 - s), s = sigmoid(2 k (u + c u^3)), T = u s 2 k (1 + 3 c u^2) -> (value, s, 1 - s, T), 1 - s without cancellation"""
+    u = u.double()
+    w = 2.0 * GELU_K * (u + GELU_C * u ** 3)
+    s, s1 = torch.sigmoid(w), torch.sigmoid(-w)
+    T = u * s * 2.0 * GELU_K * (1.0 + 3.0 * GELU_C * u * u)
+    return s + T * s1, s, s1, T
+
+
+def gelu_grad_eval_error(u):
+    """Error of common.h gelu_tanh_grad_f2 in fp32, first order (eps = 2^-24), over the magnitudes of its terms:
+      arg = u fma(u^2, b, a), a = -2 log2(e) k, b = a c (constants rounded to fp32, a few roundings each): |d arg| <= 6 eps A, A = |u| (|a| + |b| u^2)
+      e = exp2(arg) (1 ulp = 2 eps), s = rcp(1 + e) (eps + 2 eps):  relative error of s  rho = (1 - s) (6 ln2 A + 2) eps + 3 eps
+      T = (u s) fma(u^2, 6 k c, 2 k): rho + 6 eps;  1 - s is formed from the ROUNDED s: absolute error s rho + eps (1 - s)
+      value = fma(T, 1 - s, s):  |T| (1 - s) (rho + 7 eps) + (1 + |T|) s rho + eps (s + |T| (1 - s))
+    The middle term is the cancellation in 1 - s where s is close to 1 (u > 3): |T| reaches 170 at u = 9."""
+    u = u.double()
+    _, s, s1, T = gelu_grad64(u)
+    a = 2.0 * LOG2E * GELU_K
+    A = u.abs() * (a + a * GELU_C * u * u)
+    rho = s1 * (6 * math.log(2.0) * A + 2) * EPS32 + 3 * EPS32
+    return T.abs() * s1 * (rho + 7 * EPS32) + (1 + T.abs()) * s * rho + EPS32 * (s + T.abs() * s1)
+
+
+def gelu_grad_emulate(u):
+    """gelu_tanh_grad_f2 in fp32 arithmetic (the fused multiply-adds as a multiply and an add)"""
+    v = u.float()
+    f = lambda c: torch.tensor(c, dtype=torch.float32)
+    k, c = f(0.7978845608028654), f(0.044715)
+    a = f(-2.0) * f(1.4426950408889634) * k
+    b, k2, k6 = a * c, f(2.0) * k, f(6.0) * k * c
+    z = v * v
+    s = 1.0 / (torch.exp2(v * (z * b + a)) + 1.0)
+    t = (v * s) * (z * k6 + k2)
+    return t * (1.0 - s) + s
+
+
+class GeluBwdCase:
+    """du = dh gelu'(u) rounded to 2 bytes, db += sum over the M real rows of du.  sweep: u covers [-9, 9] in the operand type (row m: the gelu_sweep value, column
+    n: + a multiple of 2^-10); else u = 2 N(0, 1).  sat: one product beyond fp16 (dh = 65000 at u = 3, gelu' = 1.012).
+      du   store_bound(ref, |dh| gelu_grad_eval_error(u) + 2 eps |ref|)
+      db   fused: sum_bound(M, sum |du| + |old|) + sum_m |dh| eval error (the terms are the unrounded fp32 products);  unfused: + u sum |du| + M subnormal steps"""
+
+    def __init__(self, M, N, dtype, sweep, sat=False):
+        self.M, self.N, self.dtype = M, N, dtype
+        if sweep:
+            u = torch.linspace(-9.0, 9.0, M)[:, None] + ((torch.arange(N, dtype=torch.float32) - N / 2) / 1024)[None, :]
+        else:
+            u = rand(M, N, seed=1, scale=2.0)
+        self.u = u.to(dtype)
+        self.dh = rand(M, N, seed=2).to(dtype)
+        self.db0 = rand(N, seed=3)
+        self.sat_at = None
+        if sat:
+            self.sat_at = (M - 1, N - 5)
+            self.u[self.sat_at] = 3.0
+            self.dh[self.sat_at] = 65000.0
+        dh, g = self.dh.double(), gelu_grad64(self.u)[0]
+        self.ref_du = dh * g
+        ev = dh.abs() * gelu_grad_eval_error(self.u)
+        self.tol_du = store_bound(self.ref_du, ev + 2 * EPS32 * self.ref_du.abs(), dtype)
+        mag = self.ref_du.abs().sum(0)
+        self.ref_db = self.db0.double() + self.ref_du.sum(0)
+        self.tol_db_fused = sum_bound(M, mag + self.db0.double().abs()) + ev.sum(0)
+        self.tol_db_unfused = self.tol_db_fused + U[dtype] * mag + M * SUBNORMAL[dtype]
+
+    def tol_db(self, fused):
+        return self.tol_db_fused if fused else self.tol_db_unfused
+
+    def emulate(self, fused, store=store_rne, pad_row=None, assign=False):
+        """fp32 arithmetic -> du (2 bytes), db.  pad_row: a row of fp32 products behind row M that the WRONG sum includes; assign: db = in place of db +="""
+        du32 = self.dh.float() * gelu_grad_emulate(self.u)
+        du = store(du32, self.dtype)
+        terms = du32 if fused else du.float()
+        s = terms.sum(0)
+        if pad_row is not None:
+            s = s + pad_row
+        return du, (s if assign else self.db0 + s)
+
+
+@functools.lru_cache(maxsize=None)
+def gelu_bwd_case(M, N, dtype, sweep, sat=False):
+    return GeluBwdCase(M, N, dtype, sweep, sat)
+
+
+# ---- column sums ----------------------------------------------------------------------------------------------------------------------------------------------
+COLSUM_TILED_M, COLSUM_TILED_N = (1, 511, 512, 513, 1300), (64, 192)
+COLSUM_F32_M, COLSUM_F32_N = (1, 255, 256, 257, 700), (50, 300)
+COLSUM_MULTI_SPLITS = (1, 7, 8, 9, 17)
+
+
+class ColsumCase:
+    """db += sum_m a[m][n], launched `launches` times on the same a: ref = old + launches sum, bound sum_bound(launches M, |old| + launches sum |a|)"""
+
+    def __init__(self, M, N, dtype=None, launches=1):
+        self.M, self.N, self.launches = M, N, launches
+        self.a = rand(M, N, seed=1) if dtype is None else rand(M, N, seed=1).to(dtype)
+        self.db0 = rand(N, seed=2)
+        a = self.a.double()
+        self.ref = self.db0.double() + launches * a.sum(0)
+        self.tol = sum_bound(launches * M, self.db0.double().abs() + launches * a.abs().sum(0))
+
+    def emulate(self, assign=False):
+        db = self.db0.clone()
+        for _ in range(self.launches):
+            s = self.a.float().sum(0)
+            db = s if assign else db + s
+        return db
+
+
+@functools.lru_cache(maxsize=None)
+def colsum_case(M, N, dtype=None, launches=1):
+    return ColsumCase(M, N, dtype, launches)
+
+
+# ---- the loss gradient ----------------------------------------------------------------------------------------------------------------------------------------
+MSE_BWD_SHAPES = [(2, 3, 16, 8, 16, 2, 64), (1, 1, 3, 4, 6, 2, 64)]      # (B, T, C, H, W, p, ldf): F = C p p = 64 = ldf and 12 < ldf
+
+
+class MseBwdCase:
+    """dv[b][T - 1] = scale (vpred[b][T - 1] - vtarget[b]) as an image, zero in every other frame; the launch stores its patch tokens dfo[m][(ph, pw, c)] —
+    the inverse of DiT.unpatchify — rounded to 2 bytes.  Two fp32 roundings (the difference, the product): store_bound(ref, 2 eps |ref|).  sat: one difference
+    that `scale` carries beyond fp16."""
+
+    def __init__(self, B, T, C, H, W, p, ldf, dtype, sat=False):
+        self.shape, self.dtype, self.ldf = (B, T, C, H, W, p), dtype, ldf
+        self.vpred, self.vtarget = rand(B, T, C, H, W, seed=1), rand(B, C, H, W, seed=2)
+        self.scale = 3.0
+        self.sat_at = None
+        if sat:
+            self.sat_at = (B - 1, C - 1, H - 1, W - 2)
+            self.vpred[B - 1, T - 1, C - 1, H - 1, W - 2] = self.vtarget[self.sat_at] + 30000.0
+        self.ref = torch.zeros(B, T, C, H, W, dtype=torch.float64)
+        self.ref[:, T - 1] = float(self.scale) * (self.vpred[:, T - 1].double() - self.vtarget.double())
+        self.tol = store_bound(self.ref, 2 * EPS32 * self.ref.abs(), dtype)
+
+    def emulate(self, store=store_rne, every_frame=False):
+        """fp32 arithmetic -> the gradient image (B, T, C, H, W) in 2 bytes.  every_frame: the WRONG kernel that writes the gradient for the frame in front of the
+        last as well"""
+        B, T = self.shape[:2]
+        out = torch.zeros(self.vpred.shape)
+        for t in ([T - 1] if not every_frame else range(max(T - 2, 0), T)):
+            out[:, t] = torch.tensor(self.scale, dtype=torch.float32) * (self.vpred[:, t] - self.vtarget)
+        return store(out, self.dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def mse_bwd_case(B, T, C, H, W, p, ldf, dtype, sat=False):
+    return MseBwdCase(B, T, C, H, W, p, ldf, dtype, sat)
+
+
+# ---- the fp32 conditioning path -------------------------------------------------------------------------------------------------------------------------------
+SILU_SPECIAL = (0.0, 20.0, -20.0, 90.0, -90.0)
+# expf(-v) overflows at -v > 88.73: the kernels then return 0 where the true value is as large as 88.73 x 2^-128 (SiLU) or |dy| 87.73 x 2^-128 (its derivative),
+# both below 2^-121
+SILU_ABS = 2.0 ** -121
+
+
+class SiluCase:
+    """y = x sigmoid(x); dx = dy s (1 + x (1 - s)), s = sigmoid(x).  s from expf (2 ulp), an addition and a division: 8 eps relative, generous.
+      silu      10 eps |ref| + SILU_ABS
+      silu_bwd  16 eps |dy| s (1 + |x|) + SILU_ABS max(1, |dy|)      (magnitudes, not the value: 1 + x (1 - s) cancels at x = -1.28, and 1 - s is formed from the
+                rounded s, an absolute error of 8 eps s that x multiplies)"""
+
+    def __init__(self, R=7, C=100):
+        self.R, self.C = R, C
+        self.x = rand(R, C, seed=1, scale=4.0)
+        self.x[0, :len(SILU_SPECIAL)] = torch.tensor(SILU_SPECIAL)
+        self.dy = rand(R, C, seed=2)
+        x, dy = self.x.double(), self.dy.double()
+        s, s1 = torch.sigmoid(x), torch.sigmoid(-x)
+        self.ref_y = x * s
+        self.tol_y = 10 * EPS32 * self.ref_y.abs() + SILU_ABS
+        self.ref_dx = dy * s * (1.0 + x * s1)
+        self.tol_dx = 16 * EPS32 * dy.abs() * s * (1.0 + x.abs()) + SILU_ABS * dy.abs().clamp_min(1.0)
+
+    def emulate(self):
+        x, dy = self.x, self.dy
+        s = 1.0 / (1.0 + torch.exp(-x))
+        return x / (1.0 + torch.exp(-x)), dy * s * (1.0 + x * (1.0 - s))
+
+
+@functools.lru_cache(maxsize=None)
+def silu_case():
+    return SiluCase()
+
+
+class GemmF32Case:
+    """out[i][j] (+)= sum_t a[t][i] b[t][j] over `n` terms in fp32: a [n][I], b [n][J], old [I][J] (None: the output is overwritten).
+    gemm_tn_f32: a = dY [R][N], b = X [R][K], n = R, accumulating.  gemm_nn_f32: a = dY^T [N][R], b = W [N][K], n = N.  ada_bwd_dx: a = dmod^T [MODW][R],
+    b = W_ada [MODW][D], n = MODW.  Bound: sum_bound(n, sum |a b| + |old|), doubled on the fp32 matrix cores."""
+
+    def __init__(self, n, I, J, accumulate, mfma, seed=0, scale=1.0):
+        self.n, self.I, self.J = n, I, J
+        self.a, self.b = rand(n, I, seed=seed + 1), rand(n, J, seed=seed + 2, scale=scale)
+        self.old = rand(I, J, seed=seed + 3) if accumulate else None
+        a, b = self.a.double(), self.b.double()
+        self.ref, mag = a.t() @ b, a.abs().t() @ b.abs()
+        if accumulate:
+            self.ref, mag = self.ref + self.old.double(), mag + self.old.double().abs()
+        self.tol = sum_bound(n, mag, mfma)
+
+    def emulate(self, assign=False):
+        s = self.a.t() @ self.b
+        return s if (self.old is None or assign) else self.old + s
+
+
+@functools.lru_cache(maxsize=None)
+def gemm_f32_case(n, I, J, accumulate, mfma, seed=0, scale=1.0):
+    return GemmF32Case(n, I, J, accumulate, mfma, seed, scale)
+
+
+GEMM_TN_F32_MFMA = [(5, 64, 64), (17, 256, 128), (80, 128, 64)]                 # (R, N, K)
+GEMM_TN_F32_VALU = [(16, 64, 25, "full"), (5, 30, 25, "odd lddy"), (5, 64, 25, "dY offset")]
+GEMM_NN_F32 = [(R, N, K) for N in (256, 2048, 4096) for R in (1, 17) for K in (64, 100)]
+ADA_BWD_MFMA = [(3584, 256, 6), (1024 + 192, 64, 80), (2048, 1024, 17)]         # (MODW, D, R)
+ADA_BWD_VALU = [(3584, 256, 81), (1024 + 192, 100, 6)]                          # more than 80 conditioning rows; D % 64 != 0

@@ -1,4 +1,4 @@
-"""The bounds of tests/test_gpu_ops_typed.py, checked on the CPU (no library, no GPU): a bound is only worth asserting if a correct kernel stays inside it and a
+"""The bounds of tests/test_gpu_ops_typed.py and (second half) of tests/test_gpu_ops_train.py, checked on the CPU (no library, no GPU): a bound is only worth asserting if a correct kernel stays inside it and a
 subtly wrong one does not.  For every per-element bound, an emulation in fp32 arithmetic with a round-to-nearest-even 2-byte store must leave NO element
 outside, and the same emulation with a TRUNCATING store (a dropped guard bit, a wrong pack instruction) must put at least 1 % of the elements outside.  For
 every per-row bound, the fp64 reference rounded to the operand type — the best any kernel can return — must stay below 0.6 of the bound in its worst row.
@@ -163,3 +163,179 @@ def test_spatial_attention_jump_row_bound(jump):
     ctl = c.control()
     for (b, h, row) in c.dominated:
         assert PB.rel_l2(ctl[b, h, row], c.ref4[b, h, row]) < 0.6 * PB.ATTN_DOMINATED_TOL * PB.FACTOR[PB.BF16]
+
+
+# ======================================================================================================================================================
+# The bounds of tests/test_gpu_ops_train.py (the backward-only training kernels).  For every bound: the fp32 emulation leaves NO element outside, and each
+# wrong variant puts at least 1 % of the elements it affects outside (a per-row bound: it is exceeded in the worst affected row).
+# ======================================================================================================================================================
+def _inside(name, got, ref, tol):
+    f, w = PB.outside((got.double() - ref).abs(), tol)
+    print(f"[bound control {name}] fp32 emulation: {100 * f:.2f} % outside, worst ratio {w:.3f}")
+    assert f == 0.0, (name, f, w)
+
+
+def _caught(name, what, got, ref, tol, affected=None):
+    err, tol = (got.double() - ref).abs(), tol.expand_as(ref) if tol.dim() else tol
+    if affected is not None:
+        err, tol = err[affected], tol[affected]
+    f, w = PB.outside(err, tol)
+    print(f"[bound control {name}] WRONG ({what}): {100 * f:.2f} % of the affected elements outside, worst ratio {w:.3g}")
+    assert f >= 0.01, (name, what, f)
+
+
+def _store_control(name, dtype, c_emulate, ref, tol):
+    """c_emulate(store) -> the 2-byte output under the given store"""
+    _inside(f"{name} {PB.NAME[dtype]}", c_emulate(PB.store_rne), ref, tol)
+    _caught(f"{name} {PB.NAME[dtype]}", "truncating store", c_emulate(PB.store_trunc), ref, tol)
+
+
+@pytest.mark.parametrize("accumulate", [0, 1])
+@pytest.mark.parametrize("D,frames,P", PB.LN_BWD_SHAPES)
+def test_ln_mod_bwd_bounds(D, frames, P, accumulate):
+    c = PB.ln_bwd_case(D, frames, P)
+    name = f"ln_mod_bwd D={D} frames={frames} P={P} accumulate={accumulate}"
+    ref, tol = c.ref_dres(accumulate), c.tol_dres(accumulate)
+    dres, dshift, dscale = c.emulate(accumulate)
+    _inside(name + " dres", dres, ref, tol)
+    _inside(name + " dshift", dshift, c.ref_dshift, c.tol_dshift)
+    _inside(name + " dscale", dscale, c.ref_dscale, c.tol_dscale)
+    if frames > 1:
+        later = torch.arange(c.M) >= P                                           # the rows of every frame but the first
+        _caught(name + " dres", "scale row of frame 0 for every frame", c.emulate(accumulate, "scale0")[0], ref, tol, later)
+    if accumulate:
+        _caught(name + " dres", "accumulate ignored", c.emulate(accumulate, "noacc")[0], ref, tol)
+    if D <= 1024:
+        _caught(name + " dres", "variance over D - 1", c.emulate(accumulate, "var")[0], ref, tol)
+    _, dshift, dscale = c.emulate(accumulate, "drop")
+    _caught(name + " dshift", "last token left out", dshift, c.ref_dshift, c.tol_dshift)
+    _caught(name + " dscale", "last token left out", dscale, c.ref_dscale, c.tol_dscale)
+
+
+@pytest.mark.parametrize("D", [256, 1024])
+def test_ln_mod_bwd_large_mean_needs_the_centred_difference(D):
+    """rows of 300 +- 0.02.  Centred on the row's first element, as the kernels do it, the fp32 emulation stays inside the per-element bounds and far inside the
+    per-row LN_TOL of dres and dscale.  With x - fl(mean x) the mean is off by an ulp of 300, 7.6e-4 of the standard deviation: dscale leaves both its bounds —
+    the form the kernels had until the GPU twin of this test found it (dres barely moves: a constant shift of xhat meets the small means of g there)."""
+    c = PB.ln_bwd_case(D, 2, 24, True)
+    name = f"ln_mod_bwd large mean D={D}"
+    ref = c.ref_dres(0)
+    dres, dshift, dscale = c.emulate(0)
+    _inside(name + " dres", dres, ref, c.tol_dres(0))
+    _inside(name + " dshift", dshift, c.ref_dshift, c.tol_dshift)
+    _inside(name + " dscale", dscale, c.ref_dscale, c.tol_dscale)
+    good = (PB.row_rel_l2(dres, ref) / PB.LN_TOL, PB.row_rel_l2(dscale, c.ref_dscale) / PB.LN_TOL)
+    pres, _, pscale = c.emulate(0, "plain")
+    bad = (PB.row_rel_l2(pres, ref) / PB.LN_TOL, PB.row_rel_l2(pscale, c.ref_dscale) / PB.LN_TOL)
+    print(f"[bound control {name}] of the per-row bound (dres, dscale): centred {good[0]:.2e}, {good[1]:.2e}; x - fl(mean x): {bad[0]:.3f}, {bad[1]:.3f}")
+    assert max(good) < 0.6
+    assert bad[1] > 1.0
+    _caught(name + " dscale", "x - fl(mean x)", pscale, c.ref_dscale, c.tol_dscale)
+    var = PB.row_rel_l2(c.emulate(0, "var")[0], ref) / PB.LN_TOL
+    sc0 = PB.row_rel_l2(c.emulate(0, "scale0")[0][c.P:], ref[c.P:]) / PB.LN_TOL
+    print(f"[bound control {name}] dres rows: variance over D - 1: {var:.3f} of the per-row bound; scale row of frame 0: {sc0:.3g}")
+    assert sc0 > 1.0
+    if D == 256:
+        assert var > 1.0        # (D = 1024: the relative change of rstd is 1 / 2046 = 4.9e-4, inside LN_TOL — the per-element bound catches it, below)
+    _caught(name + " dres", "variance over D - 1", c.emulate(0, "var")[0], ref, c.tol_dres(0))
+
+
+@DTYPES
+@pytest.mark.parametrize("gated", [True, False])
+@pytest.mark.parametrize("D,frames,P", PB.GATE_BWD_SHAPES)
+def test_gate_bwd_bounds(D, frames, P, gated, dtype):
+    c = PB.gate_bwd_case(D, frames, P, dtype, gated)
+    name = f"gate_bwd D={D} frames={frames} P={P} gate={'yes' if gated else 'null'}"
+    if gated:           # (without a gate dy is the rounded dres itself: both stores of an fp32 value are checked by the gated form)
+        _store_control(name + " dy", dtype, lambda st: c.emulate(True, st)[0], c.ref_dy, c.tol_dy)
+    for fused in (True, False):
+        tag = f"{name} {'fused' if fused else 'unfused'} {PB.NAME[dtype]}"
+        dy, dgate, db = c.emulate(fused)
+        _inside(tag + " dy", dy, c.ref_dy, c.tol_dy)
+        _inside(tag + " dgate", dgate, c.ref_dgate, c.tol_dgate)
+        _inside(tag + " db", db, c.ref_db, c.tol_db(fused))
+        _caught(tag + " db", "= in place of +=", c.emulate(fused, assign=True)[2], c.ref_db, c.tol_db(fused))
+    _, dgate, db = c.emulate(True, drop=True)
+    _caught(name + " dgate", "last token left out", dgate, c.ref_dgate, c.tol_dgate)
+    _caught(name + " fused bias parts", "last token left out", db, c.ref_db, c.tol_db(True))
+
+
+@DTYPES
+@pytest.mark.parametrize("sweep", [True, False], ids=["sweep", "random"])
+@pytest.mark.parametrize("M,N", PB.GELU_BWD_SHAPES)
+def test_gelu_bwd_bounds(M, N, sweep, dtype):
+    c = PB.gelu_bwd_case(M, N, dtype, sweep)
+    name = f"gelu_bwd {M}x{N} {'sweep' if sweep else 'random'}"
+    _store_control(name + " du", dtype, lambda st: c.emulate(True, st)[0], c.ref_du, c.tol_du)
+    pad = PB.rand(N, seed=9)                                                     # a pad row of ordinary magnitude
+    for fused in (True, False):
+        tag = f"{name} {'fused' if fused else 'unfused'} {PB.NAME[dtype]}"
+        _inside(tag + " db", c.emulate(fused)[1], c.ref_db, c.tol_db(fused))
+        _caught(tag + " db", "one pad row included", c.emulate(fused, pad_row=pad)[1], c.ref_db, c.tol_db(fused))
+        _caught(tag + " db", "= in place of +=", c.emulate(fused, assign=True)[1], c.ref_db, c.tol_db(fused))
+
+
+def test_gelu_grad_reference_and_evaluation_error():
+    """gelu_grad64 against torch's autograd of GELU(tanh) in fp64, and the fp32 evaluation inside gelu_grad_eval_error over the whole sweep, fp32 grid included"""
+    u = torch.linspace(-9.0, 9.0, 200001, dtype=torch.float64).requires_grad_(True)
+    torch.nn.functional.gelu(u, approximate="tanh").sum().backward()
+    g = PB.gelu_grad64(u.detach())[0]
+    assert (g - u.grad).abs().max().item() < 1e-14
+    u32 = u.detach().float()
+    f, w = PB.outside((PB.gelu_grad_emulate(u32).double() - PB.gelu_grad64(u32)[0]).abs(), PB.gelu_grad_eval_error(u32))
+    print(f"[bound control gelu' evaluation] fp32 emulation: {100 * f:.2f} % outside, worst ratio {w:.3f}")
+    assert f == 0.0
+
+
+@pytest.mark.parametrize("N", PB.COLSUM_TILED_N)
+@pytest.mark.parametrize("M", PB.COLSUM_TILED_M)
+@DTYPES
+def test_colsum_tiled_bound(M, N, dtype):
+    c = PB.colsum_case(M, N, dtype, 2)
+    _inside(f"colsum_tiled {M}x{N} {PB.NAME[dtype]}", c.emulate(), c.ref, c.tol)
+    _caught(f"colsum_tiled {M}x{N} {PB.NAME[dtype]}", "= in place of +=", c.emulate(assign=True), c.ref, c.tol)
+
+
+@pytest.mark.parametrize("N", PB.COLSUM_F32_N)
+@pytest.mark.parametrize("M", PB.COLSUM_F32_M + PB.COLSUM_MULTI_SPLITS)
+def test_colsum_f32_bound(M, N):
+    """launch_colsum_f32 and (M = the number of splits) a job of launch_colsum_reduce_multi"""
+    c = PB.colsum_case(M, N)
+    _inside(f"colsum_f32 {M}x{N}", c.emulate(), c.ref, c.tol)
+    _caught(f"colsum_f32 {M}x{N}", "= in place of +=", c.emulate(assign=True), c.ref, c.tol)
+
+
+@DTYPES
+def test_mse_bwd_patch_bound(dtype):
+    for shape in PB.MSE_BWD_SHAPES:
+        c = PB.mse_bwd_case(*shape, dtype)
+        name = f"mse_bwd_patch {shape}"
+        last = c.ref[:, -1]
+        _store_control(name, dtype, lambda st: c.emulate(st)[:, -1], last, c.tol[:, -1])
+        _inside(name + " all frames", c.emulate(), c.ref, c.tol)
+        if shape[1] > 1:
+            _caught(name, "gradient also written for the frame in front of the last", c.emulate(every_frame=True)[:, -2], c.ref[:, -2], c.tol[:, -2])
+
+
+def test_silu_bounds():
+    c = PB.silu_case()
+    y, dx = c.emulate()
+    _inside("silu", y, c.ref_y, c.tol_y)
+    _inside("silu_bwd", dx, c.ref_dx, c.tol_dx)
+    # the derivative without its second term, x (1 - s): what a kernel that returned dy s would give
+    _caught("silu_bwd", "dy sigmoid(x) alone", c.dy * torch.sigmoid(c.x), c.ref_dx, c.tol_dx)
+    assert c.emulate()[0][0, 4].item() == 0.0 and abs(c.ref_y[0, 4].item()) > 2.0 ** -126      # x = -90: the flushed value SILU_ABS exists for
+
+
+@pytest.mark.parametrize("n,I,J,accumulate,mfma", [(R, N, K, True, True) for (R, N, K) in PB.GEMM_TN_F32_MFMA] + [(R, N, K, True, False) for (R, N, K, _) in PB.GEMM_TN_F32_VALU] +
+                         [(N, R, K, False, False) for (R, N, K) in PB.GEMM_NN_F32] + [(MODW, R, D, False, True) for (MODW, D, R) in PB.ADA_BWD_MFMA] +
+                         [(MODW, R, D, False, False) for (MODW, D, R) in PB.ADA_BWD_VALU])
+def test_gemm_f32_bounds(n, I, J, accumulate, mfma):
+    """gemm_tn_f32 (accumulating), gemm_nn_f32 and ada_bwd_dx at the shapes of the GPU tests"""
+    c = PB.gemm_f32_case(n, I, J, accumulate, mfma)
+    name = f"gemm f32 {n} terms {I}x{J}{' mfma' if mfma else ''}"
+    _inside(name, c.emulate(), c.ref, c.tol)
+    if accumulate:
+        _caught(name, "= in place of +=", c.emulate(assign=True), c.ref, c.tol)
+    drop = (c.a[:-1].t() @ c.b[:-1]) + (c.old if accumulate else 0.0)            # the last term of every sum left out
+    _caught(name, "last term left out", drop, c.ref, c.tol)
