@@ -325,6 +325,25 @@ int gtav_op_gemm_splitk_ln(const void* x, int32_t ldx, const void* w, const floa
     pd.gate_stride = gate_stride; pd.rows_per_gate = rows_per_gate;
     return op_ops().ln_modulate(resid, N, (f16*)out_f16, N, M, N, shift, scale, mod_stride, nullptr, rows_per_gate, &pd, nullptr, (hipStream_t)stream);
 }
+// Test hooks (include/gtav_amd_testing.h): ONE launch_ln_modulate (mode 0: p0 = shift, p1 = scale) or launch_ln_affine (mode 1: p0 = gamma, p1 = beta; rows,
+// rows_per_mod and mod_stride unused) with every LnPending field passed flat, and launch_branch_rows.  Nothing is validated here: the launchers' own
+// refusals are what the tests hold.
+int gtav_op_ln_pending(int32_t mode, float* x, int32_t ldx, void* out, int32_t M, int32_t D, const float* p0, const float* p1, int32_t mod_stride,
+                       const int32_t* rows, int32_t rows_per_mod, const float* parts, int32_t nsplit, int64_t slab_stride, int32_t ld,
+                       const float* bias, const float* gate, int32_t gate_stride, const int32_t* gate_rows, int32_t rows_per_gate, float* x_out, void* y_save,
+                       int32_t tperm_T, int32_t tperm_P, float* k_save, const float* k_load, int32_t* err, void* stream) {
+    LnPending pd;
+    memset(&pd, 0, sizeof(pd));
+    pd.parts = parts; pd.nsplit = nsplit; pd.slab_stride = (size_t)slab_stride; pd.ld = ld; pd.bias = bias; pd.gate = gate;
+    pd.gate_stride = gate_stride; pd.gate_rows = gate_rows; pd.rows_per_gate = rows_per_gate; pd.x_out = x_out; pd.y_save = (f16*)y_save;
+    pd.tperm_T = tperm_T; pd.tperm_P = tperm_P; pd.k_save = k_save; pd.k_load = k_load;
+    if (mode == 0) return op_ops().ln_modulate(x, ldx, (f16*)out, D, M, D, p0, p1, mod_stride, rows, rows_per_mod, &pd, err, (hipStream_t)stream);
+    return op_ops().ln_affine(x, ldx, (f16*)out, D, M, D, p0, p1, &pd, err, (hipStream_t)stream);
+}
+int gtav_op_branch_rows(const float* parts, int32_t nsplit, int64_t slab_stride, int32_t ld, const float* bias, void* y, int32_t M, int32_t N, int32_t* err,
+                        void* stream) {
+    return op_ops().branch_rows(parts, nsplit, (size_t)slab_stride, ld, bias, (f16*)y, M, N, err, (hipStream_t)stream);
+}
 int gtav_op_rope_interleave(const float* cos_t, const float* sin_t, float* cs, int32_t npos, void* stream) {
     return launch_rope_interleave(cos_t, sin_t, cs, npos, (hipStream_t)stream);
 }

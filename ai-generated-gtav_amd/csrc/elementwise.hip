@@ -172,6 +172,7 @@ __global__ __launch_bounds__(512) void ln_row_block_kernel(float* __restrict__ x
         if (pd.y_save) {   // training forward: the branch output before the gate (d gate needs it)
             float am = 0.f;
             *(f16x4*)(pd.y_save + (size_t)m * pd.ld + c) = sat4(y[0], y[1], y[2], y[3], am);
+            sat_report(am, pd.err_flag);   // a clamped branch image is a wrong gate gradient: reported like branch_rows_kernel's (it was clamped in silence)
         }
         if (pd.gate) y = y * g4;
         v = v + y;
@@ -924,7 +925,10 @@ int launch_convert_pad_f16(const float* src, int lds, int R, int C, f16* dst, in
 
 int launch_qkv_head_major(const f16* src, f16* dst, int D, hipStream_t stream, int mode) {
     GTAV_REQUIRE(D % 128 == 0 && (mode == 0 || mode == 1), "qkv_head_major: D=%d must be a multiple of 128, mode=%d 0 or 1", D, mode);
-    hipLaunchKernelGGL(qkv_head_major_kernel, dim3(grid_for((size_t)3 * D * (D / 8))), dim3(256), 0, stream, src, dst, D, mode);
+    // one thread per 16-byte chunk and no grid-stride loop in the kernel: the grid covers every chunk (grid_for's cap of 4096 blocks left the rows from
+    // 4096 on unwritten at D = 2048 and those from 4681 on at D = 1792: tests/test_gpu_ops.py::test_qkv_head_major_every_hidden_size)
+    const size_t total = (size_t)3 * D * (D / 8);
+    hipLaunchKernelGGL(qkv_head_major_kernel, dim3((unsigned)cdiv((long long)total, 256)), dim3(256), 0, stream, src, dst, D, mode);
     GTAV_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -122,7 +122,7 @@ int skinny_init() {
     int devid = 0;
     GTAV_CHECK_HIP(hipGetDevice(&devid));
     if (done_devs >> (devid & 63) & 1) return 0;
-#define GTAV_SKINNY_ATTR(A, F, R) GTAV_CHECK_HIP(hipFuncSetAttribute((const void*)skinny_f32_kernel<A, F, R>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+#define GTAV_SKINNY_ATTR(A, F, R) GTAV_CHECK_HIP(hipFuncSetAttribute((const void*)skinny_f32_kernel<A, F, R>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));   // (launch_skinny_f32: SKINNY_LDS)
     GTAV_SKINNY_VARIANTS(GTAV_SKINNY_ATTR)
 #undef GTAV_SKINNY_ATTR
 #define GTAV_SKINNY_ATTR_C(R) GTAV_CHECK_HIP(hipFuncSetAttribute((const void*)skinny_f32_kernel<0, 4, R, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -135,7 +135,11 @@ int skinny_init() {
 int launch_skinny_f32(const float* X, int ldx, const float* W, const float* bias, float* Y, int ldy, int M, int N,
                       int K, int act_silu, hipStream_t stream) {
     GTAV_REQUIRE(M > 0 && N > 0 && N % 4 == 0, "skinny: bad M=%d N=%d", M, N);
-    GTAV_REQUIRE(K > 0 && K % 32 == 0 && K <= 2048, "skinny: K=%d must be a multiple of 32 and <= 2048", K);
+    // the bound on K is the LDS of ONE 16-row slab of X (the attribute skinny_init sets), not a round number: the second projection of the conditioning MLP reads
+    // hidden + the padded action columns, 2080 at hidden 2048 — K <= 2048 refused every forward of that width with actions
+    // (tests/test_gpu_models.py::test_hidden_2048_dit_forward_and_fused_spatial_switch)
+    constexpr int SKINNY_LDS = 160 * 1024, SKINNY_MAX_K = (SKINNY_LDS / (16 * (int)sizeof(float)) - 8) / 32 * 32;   // 2528
+    GTAV_REQUIRE(K > 0 && K % 32 == 0 && K <= SKINNY_MAX_K, "skinny: K=%d must be a multiple of 32 and <= %d", K, SKINNY_MAX_K);
     GTAV_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0 && ldx >= K && ldy >= N, "skinny: bad leading dims");
     // four (eight) feature tiles per wave where that still leaves the chip full, 32-row slabs as soon as there are two of them: the adaLN table of a frame
     // 1.52 -> 0.92 ms at 101 rows (batch 1), 11.3 -> 5.0 ms at 808 rows (batch 8)

@@ -180,6 +180,9 @@ SIGNATURES = {
     "gtav_op_train_gemm_tn_f32": [_p, _i, _p, _i, _i, _i, _i, _p, _i, _p],
     "gtav_op_train_gemm_nn_f32": [_p, _i, _p, _i, _i, _i, _i, _p, _i, _p],
     "gtav_op_train_ada_bwd_dx": [_p, _i, _p, _i, _i, _p, _p, _l, _p],
+    # the deferred-residual LayerNorm with every LnPending field flat, and the branch image launch (include/gtav_amd_testing.h)
+    "gtav_op_ln_pending": [_i, _p, _i, _p, _i, _i, _p, _p, _i, _p, _i, _p, _i, _l, _i, _p, _p, _i, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p],
+    "gtav_op_branch_rows": [_p, _i, _l, _i, _p, _p, _i, _i, _p, _p],
 }
 _RESTYPES = {"gtav_last_error": C.c_char_p, "gtav_dit_destroy": None, "gtav_vae_destroy": None, "gtav_op_gemm_set_stages": None,
              "gtav_op_gemm_set_wm": None, "gtav_op_set_operand_dtype": None}

@@ -53,6 +53,15 @@
  *   mse_bwd_patch, to_tiled, transpose_tiled, convert_t (launch_convert_T_f16)   the loss gradient and the layout converters
  *   silu, silu_bwd, gemm_tn_f32 (dW += dY^T X), gemm_nn_f32 (dX = dY W), ada_bwd_dx (part = ada_bwd_dx_workspace(MODW, D, R))
  * tests/test_gpu_ops_train.py runs them against fp64 math with the bounds of tests/parity_bounds.py.
+ *
+ * gtav_op_ln_pending          ONE launch_ln_modulate (mode 0: p0 = shift, p1 = scale tables of row length mod_stride, indexed by rows / rows_per_mod) or
+ *                             launch_ln_affine (mode 1: p0 = gamma, p1 = beta; rows, rows_per_mod and mod_stride unused) with a deferred residual update
+ *                             (csrc/ops_typed.inc LnPending) whose EVERY field is an argument: parts .. k_load.  x has the leading dimension ldx, out is the
+ *                             tile-major 2-byte operand of row length D.  Dispatches per gtav_op_set_operand_dtype (out and y_save then hold bf16).
+ * gtav_op_branch_rows         launch_branch_rows, the launch of its own that writes what LnPending::y_save keeps, in the thread's operand type.
+ *                             Both: the caller owns every buffer and the device error word `err` (may be null); the hooks allocate nothing, never synchronise and
+ *                             validate NOTHING themselves — a bad descriptor meets the launchers' own refusals, which is what tests/test_gpu_ops_ln_pending.py
+ *                             holds, next to the fp64 references and bounds of tests/parity_bounds.py.
  * (Timing experiments that change results, and the block shapes that measured slower than these, exist only in the separate
  * -DGTAV_EXPERIMENTS build: csrc/build.sh exp -> libgtav_amd_exp.so, loaded by tools/ only.) */
 #ifndef GTAV_AMD_TESTING_H
@@ -91,6 +100,14 @@ int gtav_op_train_silu_bwd(const float* dy, int32_t lddy, const float* x, int32_
 int gtav_op_train_gemm_tn_f32(const float* dY, int32_t lddy, const float* X, int32_t ldx, int32_t R, int32_t N, int32_t K, float* dW, int32_t lddw, void* stream);
 int gtav_op_train_gemm_nn_f32(const float* dY, int32_t lddy, const float* W, int32_t ldw, int32_t R, int32_t N, int32_t K, float* dX, int32_t lddx, void* stream);
 int gtav_op_train_ada_bwd_dx(const float* dmod, int32_t MODW, const float* W, int32_t D, int32_t R, float* dSc, float* part, int64_t part_floats, void* stream);
+
+/* ---- the deferred-residual LayerNorm (see above) ---- */
+int gtav_op_ln_pending(int32_t mode, float* x, int32_t ldx, void* out, int32_t M, int32_t D, const float* p0, const float* p1, int32_t mod_stride,
+                       const int32_t* rows, int32_t rows_per_mod, const float* parts, int32_t nsplit, int64_t slab_stride, int32_t ld, const float* bias,
+                       const float* gate, int32_t gate_stride, const int32_t* gate_rows, int32_t rows_per_gate, float* x_out, void* y_save, int32_t tperm_T,
+                       int32_t tperm_P, float* k_save, const float* k_load, int32_t* err, void* stream);
+int gtav_op_branch_rows(const float* parts, int32_t nsplit, int64_t slab_stride, int32_t ld, const float* bias, void* y, int32_t M, int32_t N, int32_t* err,
+                        void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,7 @@
 """Inputs, fp64 references, error bounds and fp32 emulations of the operand-typed kernels, shared by tests/test_gpu_ops_typed.py (the kernels, on a GPU) and
 tests/test_host_parity_bounds.py (the bounds themselves, on the CPU).  Pure torch: nothing here loads the library.  The second half of the file holds the same
-for the backward-only training kernels (tests/test_gpu_ops_train.py), with its own head comment.
+for the backward-only training kernels (tests/test_gpu_ops_train.py) and the last part for the deferred-residual LayerNorm (tests/test_gpu_ops_ln_pending.py),
+each with its own head comment.
 
 None of the bounds is taken from the code under test.  u is the unit roundoff of the operand type, 2^-11 for fp16 and 2^-8 for bf16.
 
@@ -213,7 +214,7 @@ def qkv_temporal_case(dtype):
 
 
 # ---- LayerNorm ----------------------------------------------------------------------------------------------------------------------------------------
-LN_SHAPES = [(128, 96), (256, 96), (1024, 1027), (2048, 160)]      # (D, M)
+LN_SHAPES = [(128, 96), (256, 96), (1024, 1027), (2048, 160), (1280, 96), (1792, 33)]      # (D, M); the last two: blocks of 5 and 7 waves
 LN_TOL = 5e-4
 
 
@@ -399,7 +400,7 @@ def frame_sum(v, frames, P, drop_last=False):
 
 
 # ---- LayerNorm + modulate backward (fp32 only) -----------------------------------------------------------------------------------------------------------
-LN_BWD_SHAPES = [(256, 3, 24), (512, 2, 16), (1024, 2, 40), (2048, 1, 17), (384, 2, 24), (100, 1, 5)]      # (D, frames, P); the last two: no fused kernel
+LN_BWD_SHAPES = [(256, 3, 24), (512, 2, 16), (1024, 2, 40), (2048, 1, 17), (384, 2, 24), (100, 1, 5), (1792, 1, 17)]      # (D, frames, P); the last three: no fused kernel
 LN_BWD_FUSED_D = (256, 512, 1024, 2048)
 
 
@@ -770,4 +771,166 @@ GEMM_TN_F32_MFMA = [(5, 64, 64), (17, 256, 128), (80, 128, 64)]                 
 GEMM_TN_F32_VALU = [(16, 64, 25, "full"), (5, 30, 25, "odd lddy"), (5, 64, 25, "dY offset")]
 GEMM_NN_F32 = [(R, N, K) for N in (256, 2048, 4096) for R in (1, 17) for K in (64, 100)]
 ADA_BWD_MFMA = [(3584, 256, 6), (1024 + 192, 64, 80), (2048, 1024, 17)]         # (MODW, D, R)
-ADA_BWD_VALU = [(3584, 256, 81), (1024 + 192, 100, 6)]                          # more than 80 conditioning rows; D % 64 != 0
+ADA_BWD_VALU = [(3584, 256, 81), (1024 + 192, 100, 6), (14 * 2048, 2048, 6)]        # more than 80 conditioning rows; D % 64 != 0; what a depth-1 hidden-2048 handle calls
+
+
+# =======================================================================================================================================================
+# The deferred-residual LayerNorm (csrc/elementwise.hip ln_row_block_kernel, csrc/ops_typed.inc LnPending): x += gate[frame] (bias + sum_k slab_k), then
+# LayerNorm + modulate / affine of the updated row into the 2-byte operand.  Shared by tests/test_gpu_ops_ln_pending.py and tests/test_host_parity_bounds.py.
+#
+#   1  updated residual, per element:  |got - ref| <= (nsplit + 2) eps (|x| + |g| (|b| + sum_k |s_k|))  = sum_bound(nsplit, ..): nsplit additions (the bias
+#      and the slabs), one product and one addition, each off by eps relative at most (a fused multiply-add only drops one of them)
+#   2  the branch image y_save / launch_branch_rows: bit for bit the operand-type store (round to nearest even, clamped to the largest finite fp16 in fp16) of
+#      the fp32 sum bias + s_0 + s_1 + .. in THAT order — additions only, so no contraction can move a bit
+#   3  the 2-byte operand: relative L2 LN_TOL FACTOR[dtype] against the fp64 LayerNorm of the fp64-updated row, per row and globally (the criterion of the
+#      LayerNorm cases above)
+# Slabs, bias and gates are N(0, 1), so a dropped slab, a slab added twice, another frame's gate or a bias behind the gate move the residual by the order of 1,
+# 2^20 times the bound.  Rows 0 .. 63 of the D = 1024, M = 300 case hold ln_large_mean_case's 300 +- 0.02 with slabs of 1 / 32 the size.
+# =======================================================================================================================================================
+class LnPendCase:
+    """mode 0: modulate with a table [R][3 D] = [gate | shift | scale] (stride 3 D), frame f of P rows -> table row rows[f] (LayerNorm) / gate_rows[f] (gate),
+    the identity without `indirect`;  mode 1: affine (gamma, beta), never gated.  nsplit 0: a descriptor without slabs.  tperm (T, P16): the output row order of
+    the fused temporal launch.  ld: row length of the slabs and of y_save (>= D)."""
+
+    def __init__(self, name, D, M, nsplit, mode, gate=True, bias=True, P=1, indirect=False, tperm=None, large_mean=0, ld=None):
+        self.name, self.D, self.M, self.nsplit, self.mode, self.P, self.tperm = name, D, M, nsplit, mode, P, tperm
+        self.ld = ld or D
+        frames = M // P
+        assert frames * P == M and not (mode == 1 and gate)
+        self.frames = frames
+        self.x = rand(M, D, seed=11) * 3 + 0.5
+        self.slabs = rand(max(nsplit, 1), M, self.ld, seed=12)[:nsplit]
+        if large_mean:
+            self.x[:large_mean] = ln_large_mean_case(D)[0][:large_mean]
+            self.slabs[:, :large_mean] *= 1.0 / 32
+        self.bias = rand(D, seed=13) if bias and nsplit else None
+        self.R = frames + 2 if indirect else frames
+        self.mod = rand(self.R, 3 * D, seed=14)
+        self.gamma, self.beta = rand(D, seed=15) * 0.1 + 1, rand(D, seed=16) * 0.1
+        if indirect:     # non-monotone, one table row used by two frames, two table rows unused; the gate's list is another one
+            self.rows = torch.tensor([(7 * f + 3) % self.R for f in range(frames)], dtype=torch.int32)
+            self.rows[frames - 1] = self.rows[1]
+            self.gate_rows = torch.tensor([(5 * f + 1) % self.R for f in range(frames)], dtype=torch.int32)
+            self.gate_rows[frames - 2] = self.gate_rows[0]
+        else:
+            self.rows = self.gate_rows = None
+        self.gated = gate and nsplit > 0
+        # ---- fp64 references ----
+        x = self.x.double()
+        self.ref_new, self.tol_new = x, torch.zeros_like(x)
+        if nsplit:
+            y = self.slabs[:, :, :D].double().sum(0)
+            mag = self.slabs[:, :, :D].double().abs().sum(0)
+            if self.bias is not None:
+                y, mag = y + self.bias.double(), mag + self.bias.double().abs()
+            if self.gated:
+                g = self._table(self.gate_rows, 0, torch.float64)
+                y, mag = g * y, g.abs() * mag
+            self.ref_new = x + y
+            self.tol_new = sum_bound(nsplit, x.abs() + mag)
+        xh = ln64(self.ref_new)
+        if mode == 0:
+            shift, scale = self._table(self.rows, 1, torch.float64), self._table(self.rows, 2, torch.float64)
+            self.ref_operand = xh * (1 + (scale + 1e-6)) + shift
+        else:
+            self.ref_operand = xh * self.gamma.double() + self.beta.double()
+
+    def _table(self, rows, part, ft, shift_frames=0):
+        """[M][D]: columns part D .. of the table row of every token's frame"""
+        f = (torch.arange(self.frames) + shift_frames) % self.frames
+        r = rows.long()[f] if rows is not None else f
+        D = self.D
+        return self.mod[r, part * D:(part + 1) * D].to(ft).repeat_interleave(self.P, 0)
+
+    def out_rows(self, swapped=False):
+        """row of the 2-byte operand that token row m is written to (LnPending::tperm_*): (b, t, p) -> (b, p / 16, t, p % 16).  swapped: the WRONG order
+        with the two parts of p exchanged, (b, p % (P / 16), t, p / (P / 16))"""
+        m = torch.arange(self.M)
+        if not self.tperm:
+            return m
+        T, P = self.tperm
+        fr, pp = m // P, m % P
+        bb, tt = fr // T, fr % T
+        hi, lo = (pp % (P // 16), pp // (P // 16)) if swapped else (pp // 16, pp % 16)
+        return ((bb * (P // 16) + hi) * T + tt) * 16 + lo
+
+    def branch32(self, wrong=None):
+        """bias + s_0 + s_1 + .. in fp32, in the kernels' order.  wrong: "drop" = without the last slab, "again" = slab 0 once more where the load chunk
+        (1 / 2 / 4 / 8 slots) has an unused slot"""
+        D = self.D
+        y = self.bias.clone().expand(self.M, D) if self.bias is not None else torch.zeros(self.M, D)
+        n = self.nsplit - 1 if wrong == "drop" else self.nsplit
+        for k in range(n):
+            y = y + self.slabs[k, :, :D]
+        if wrong == "again" and self.nsplit not in (1, 2, 4, 8):
+            y = y + self.slabs[0, :, :D]
+        return y
+
+    def y_save(self, dtype):
+        return store_clamped(self.branch32(), dtype)
+
+    def emulate(self, dtype, wrong=None):
+        """the row-block kernel's arithmetic in fp32 -> (updated residual, the 2-byte operand in the launch's OUTPUT row order).  wrong: branch32's, "gate" = the
+        gate of the next frame, "bias" = the bias added behind the gate, "tperm" = out_rows(swapped)"""
+        D, x = self.D, self.x
+        v = x
+        if self.nsplit:
+            if wrong == "bias" and self.bias is not None:
+                y = torch.zeros(self.M, D)
+                for k in range(self.nsplit):
+                    y = y + self.slabs[k, :, :D]
+            else:
+                y = self.branch32(wrong)
+            if self.gated:
+                y = y * self._table(self.gate_rows, 0, torch.float32, 1 if wrong == "gate" else 0)
+            if wrong == "bias" and self.bias is not None:
+                y = y + self.bias
+            v = x + y
+        a = v - x[:, :1]                                  # K = the row's first element BEFORE the update
+        m1 = a.sum(-1, keepdim=True) / D
+        var = ((a * a).sum(-1, keepdim=True) / D - m1 * m1).clamp_min(0.0)
+        xh = (a - m1) * (1.0 / torch.sqrt(var + 1e-6))
+        if self.mode == 0:
+            o = xh * (1.0 + (self._table(self.rows, 2, torch.float32) + 1e-6)) + self._table(self.rows, 1, torch.float32)
+        else:
+            o = xh * self.gamma + self.beta
+        out = torch.empty(self.M, D, dtype=dtype)
+        out[self.out_rows(wrong == "tperm")] = store_rne(o, dtype)
+        return v, out
+
+
+def store_clamped(x, dtype):
+    """common.h sat4: fp32 -> 2 bytes, round to nearest even behind a clamp to the largest finite fp16 (bf16: fp32's own range, no clamp)"""
+    x = x.float()
+    return store_rne(x.clamp(-F16_MAX, F16_MAX) if dtype is F16 else x, dtype)
+
+
+# name -> constructor arguments; tests/test_gpu_ops_ln_pending.py says which buffers (x_out, y_save, k_save) each launch gets
+LN_PEND_CASES = {
+    "d64": dict(D=64, M=40, nsplit=1, mode=0, P=8),                                               # one wave, nw = 1
+    "d192": dict(D=192, M=33, nsplit=2, mode=1, gate=False, bias=False, ld=200),                  # the VAE's form; 48 of 64 threads active; ld > D
+    "d256_rows": dict(D=256, M=160, nsplit=3, mode=0, P=16, indirect=True, tperm=(5, 16)),        # B 2, T 5, P 16
+    "d256_tperm": dict(D=256, M=144, nsplit=0, mode=0, P=48, tperm=(3, 48)),                      # a descriptor without slabs
+    "d1024_train": dict(D=1024, M=300, nsplit=4, mode=0, P=60, large_mean=64),                    # x_out + y_save + k_save, then the k_load re-run
+    "d1280": dict(D=1280, M=96, nsplit=5, mode=0, P=32),                                          # 5 waves
+    "d1280_tperm": dict(D=1280, M=96, nsplit=5, mode=0, P=32, tperm=(3, 32)),                     # (P = 16 above makes the order the identity: here it is not)
+    "d1792": dict(D=1792, M=33, nsplit=8, mode=1, gate=False),                                    # 7 waves
+    "d2048": dict(D=2048, M=130, nsplit=8, mode=0, P=26),
+    "d1024_step": dict(D=1024, M=720, nsplit=4, mode=0, P=144),                                   # the batch-1 step's launch, in place, repeated
+}
+LN_PEND_WRONG = ("drop", "again", "gate", "bias", "tperm")
+
+
+@functools.lru_cache(maxsize=None)
+def ln_pend_case(name):
+    return LnPendCase(name, **LN_PEND_CASES[name])
+
+
+@functools.lru_cache(maxsize=None)
+def ln_pend_sat_case():
+    """D = 64, 8 rows, two slabs whose sum leaves fp16 in two elements (+80000, -70000.5): fp16 stores +-65504 and raises ERR_F16_SAT, bf16 rounds the value."""
+    c = LnPendCase("sat", D=64, M=8, nsplit=2, mode=0, P=8)
+    c.bias = torch.zeros(64)
+    c.slabs[0, 3, 5], c.slabs[1, 3, 5] = 40000.0, 40000.0
+    c.slabs[0, 6, 60], c.slabs[1, 6, 60] = -30000.5, -40000.0
+    return c

@@ -85,6 +85,37 @@ def test_full_dit_forward_b1_t5(full_dit):
     assert e < 1e-3
 
 
+def test_hidden_2048_dit_forward_and_fused_spatial_switch():
+    """The widest hidden size a handle accepts (hidden_size % 256 == 0, <= 2048), one block, B = 1, T = 5 frames of 144 tokens with actions: the forward at the
+    bound of test_full_dit_forward_b1_t5, and gtav_dit_set_fused_spatial off / on bit-identical as at hidden 1024.  The fused spatial launch reads the to_qkv
+    weight in the head-major order launch_qkv_head_major writes at finalize and at the switch: rows it left unwritten (heads 21 .. 31 at this width, before
+    the launch covered every chunk) show here as a forward that differs from the two-kernel path."""
+    kw = dict(input_h=18, input_w=32, hidden_size=2048, num_heads=32, depth=1)
+    m, sd, cfg = _mk_dit(kw, seed=4, max_batch=1)
+    g = torch.Generator().manual_seed(0)
+    x = torch.randn(1, 5, 16, 18, 32, generator=g)
+    t = torch.tensor([[15, 15, 15, 15, 500]])
+    a = torch.zeros(1, 5, 25)
+    a[:, :, 3] = 1
+    with torch.no_grad():
+        ref = O.dit_forward(sd, cfg, x, t, a)
+    try:
+        assert m.fused_launches(1, 5) & 1, "the fused spatial launch is this geometry's default"
+        fused = m(x, t, a).clone()
+        m.set_fused_spatial(False)
+        assert m.fused_launches(1, 5) == 0
+        split = m(x, t, a).clone()
+        m.set_fused_spatial(True)
+        again = m(x, t, a).clone()
+        m.check()
+    finally:
+        m.set_fused_spatial(True)
+    e_split, e_fused = rel_l2(split, ref), rel_l2(fused, ref)
+    print(f"hidden-2048 DiT B=1 T=5 rel-L2: two-kernel path {e_split:.3e}, fused spatial {e_fused:.3e}")
+    assert torch.isfinite(fused).all() and e_split < 1e-3 and e_fused < 1e-3
+    assert torch.equal(fused, split) and torch.equal(again, split)
+
+
 def test_full_dit_forward_b2_t3_no_actions(full_dit):
     m, sd, cfg = full_dit
     x, t, _ = _inputs(cfg, 2, 3, seed=5, actions=False)

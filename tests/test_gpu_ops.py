@@ -8,7 +8,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from helpers import dev, gemm, pad_weight_f16, rel_l2, stream, to_tiled_f16, untile  # noqa: E402
+from helpers import dev, gemm, pad_weight_f16, rel_l2, stream, tiled_index, to_tiled_f16, untile  # noqa: E402
 from gtav_amd import lib as L  # noqa: E402
 
 
@@ -288,7 +288,7 @@ def test_attention_temporal(Tq, t0):
     assert rel_l2(untile(o, B * Tq * P, D).float(), ref) < 6e-4
 
 
-@pytest.mark.parametrize("NB,D", [(5, 1024), (1, 256), (7, 512), (16, 1024)])
+@pytest.mark.parametrize("NB,D", [(5, 1024), (1, 256), (7, 512), (16, 1024), (5, 1792), (5, 2048)])
 def test_fused_spatial_qkv_attention_equals_the_two_kernel_path(NB, D):
     """gemm_qkvs_attn_kernel (to_qkv projection + RoPE + spatial attention of 144-token frames in one launch; the q / k / v^T images stay in LDS) against
     gtav_op_gemm_qkv (spatial mode) + gtav_op_attn_spatial on the same operands: a BIT-EQUAL attention output (same fp16 q / k / v, the same tile body —
@@ -334,6 +334,38 @@ def test_fused_spatial_qkv_attention_equals_the_two_kernel_path(NB, D):
     assert rel_l2(untile(first, M, D).float(), ref) < 1.5e-3
 
 
+@pytest.mark.parametrize("D", list(range(128, 2048 + 1, 128)))
+def test_qkv_head_major_every_hidden_size(D):
+    """launch_qkv_head_major at every hidden size a handle accepts, both row orders, bit for bit against the row permutation the kernel documents:
+    mode 0 (fused temporal launch) row hd 192 + which 64 + d, mode 1 (fused spatial launch) row hd 192 + w 48 + which 16 + e with d = 16 w + e, both <- source row
+    which D + hd 64 + d; chunks keep their place inside the tile-major row.  The destination starts as a sentinel no source element holds, so a row the launch
+    never wrote shows.  (It found the launch capped at 4096 blocks of 256 chunks with no grid-stride loop in the kernel: at D = 1792 the rows from 4681 on,
+    at D = 2048 those from 4096 on — heads 21 .. 31 — kept the sentinel.)"""
+    lib = L.load()
+    R = 3 * D
+    src = torch.randint(0, 30000, (R, D), generator=torch.Generator().manual_seed(D), dtype=torch.int16)
+    idx = tiled_index(R, D).reshape(-1)                      # R % 128 == 0 and D % 64 == 0: the image has exactly R D elements
+    image = torch.empty(R * D, dtype=torch.int16)
+    image[idx] = src.reshape(-1)
+    sd = image.to(dev())
+    nd = torch.arange(R)
+    hd, rem = nd // 192, nd % 192
+    rows = {0: (rem // 64) * D + hd * 64 + rem % 64,
+            1: ((rem % 48) // 16) * D + hd * 64 + 16 * (rem // 48) + rem % 16}
+    for mode, fn in ((0, lib.gtav_op_qkv_head_major), (1, lib.gtav_op_qkv_head_major_spatial)):
+        assert sorted(rows[mode].tolist()) == list(range(R))
+        dst = torch.full((R * D,), 0x7B7B, dtype=torch.int16, device=dev())
+        L.check(fn(sd.data_ptr(), dst.data_ptr(), D, stream()))
+        torch.cuda.synchronize()
+        got = dst.cpu()
+        want = torch.empty(R * D, dtype=torch.int16)
+        want[idx] = src[rows[mode]].reshape(-1)
+        unwritten = (got == 0x7B7B).sum().item()
+        assert unwritten == 0, f"D={D} mode {mode}: {unwritten} of {R * D} elements never written (first logical row {(got[idx].reshape(R, D) == 0x7B7B).any(1).nonzero()[0].item()})"
+        assert torch.equal(got, want), f"D={D} mode {mode}"
+    assert torch.equal(sd.cpu(), image)
+
+
 def test_fused_spatial_qkv_attention_refuses_other_geometries():
     lib = L.load()
     z = torch.zeros(1 << 16, device=dev(), dtype=torch.float16)
@@ -343,7 +375,7 @@ def test_fused_spatial_qkv_attention_refuses_other_geometries():
             L.check(lib.gtav_op_gemm_qkvs_attn(z.data_ptr(), z.data_ptr(), M, D, P, cs.data_ptr(), z.data_ptr(), stream()))
 
 
-@pytest.mark.parametrize("B,P,D", [(1, 144, 1024), (2, 32, 256), (3, 16, 256)])
+@pytest.mark.parametrize("B,P,D", [(1, 144, 1024), (2, 32, 256), (3, 16, 256), (1, 16, 2048)])
 def test_fused_temporal_qkv_attention_equals_the_two_kernel_path(B, P, D):
     """gemm_qkvt_attn_kernel (to_qkv projection + RoPE + causal temporal attention + K/V cache rows in one launch) against
     gtav_op_gemm_qkv + gtav_op_attn_temporal on the same operands: BIT-EQUAL cache rows and attention output (same fp16 q / k / v,

@@ -694,7 +694,8 @@ def test_ada_bwd_dx_needs_its_workspace():
 
 
 # ---- 8. whole-model gradients at the hidden sizes whose training step runs the other kernels -------------------------------------------------------------------------
-# hidden 512: ln_mod_bwd_fused_kernel<2>; hidden 768 (a multiple of 256 without a fused kernel): the two-kernel LayerNorm backward.  Bounds: GRAD_TOL of
+# hidden 512: ln_mod_bwd_fused_kernel<2>; hidden 768 (a multiple of 256 without a fused kernel): the two-kernel LayerNorm backward; 1280 and 2048: the widths
+# above 1024 (LayerNorm blocks of 5 and 8 waves, ln_mod_bwd_fused_kernel<8>).  Bounds: GRAD_TOL of
 # tests/test_gpu_train.py in fp16, 8 x that in bf16 (tests/test_gpu_train_bf16.py GRAD_TOL_BF16).
 GRAD_TOL = {torch.float16: 4.5e-3, torch.bfloat16: 8 * 4.5e-3}
 
@@ -723,7 +724,7 @@ def _toy_reference(hidden, heads):
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["fp16", "bf16"])
-@pytest.mark.parametrize("hidden,heads", [(512, 8), (768, 12)])
+@pytest.mark.parametrize("hidden,heads", [(512, 8), (768, 12), (1280, 20), (2048, 32)])
 def test_model_gradients_at_other_hidden_sizes(hidden, heads, dtype):
     from gtav_amd.model.dit import DiT
     sd, (x, t, a, vt), v_ref, grads = _toy_reference(hidden, heads)

@@ -337,5 +337,57 @@ def test_gemm_f32_bounds(n, I, J, accumulate, mfma):
     _inside(name, c.emulate(), c.ref, c.tol)
     if accumulate:
         _caught(name, "= in place of +=", c.emulate(assign=True), c.ref, c.tol)
-    drop = (c.a[:-1].t() @ c.b[:-1]) + (c.old if accumulate else 0.0)            # the last term of every sum left out
-    _caught(name, "last term left out", drop, c.ref, c.tol)
+    # the last term of every sum left out.  The bound grows with n^2 (n + 2 roundings of a sum of n magnitudes) and one term with n: from about 8192 terms on
+    # a single one disappears in it (0.21 of the bound at the 28672 of a hidden-2048 ada_bwd_dx), so there the wrong sum leaves out the last 1024 terms — one
+    # split of ada_bwd_dx's workspace, the part a wrong split count loses
+    k = 1 if n < 8192 else 1024
+    drop = (c.a[:-k].t() @ c.b[:-k]) + (c.old if accumulate else 0.0)
+    _caught(name, f"last {k} term(s) left out", drop, c.ref, c.tol)
+
+
+# ---- the deferred-residual LayerNorm (tests/test_gpu_ops_ln_pending.py) ------------------------------------------------------------------------------------
+def _ln_pend_margins(c, dtype, wrong=None):
+    """(worst ratio of bound 1, worst row / global relative L2 as a fraction of bound 3) of the fp32 emulation; the operand is read back through the DOCUMENTED
+    output row order, as the GPU test reads the kernel's"""
+    v, out = c.emulate(dtype, wrong)
+    w1 = PB.outside((v.double() - c.ref_new).abs(), c.tol_new)[1] if c.nsplit else 0.0
+    nat, tol = out[c.out_rows()], PB.LN_TOL * PB.FACTOR[dtype]
+    return w1, max(PB.row_rel_l2(nat, c.ref_operand), PB.rel_l2(nat, c.ref_operand)) / tol
+
+
+@DTYPES
+@pytest.mark.parametrize("name", list(PB.LN_PEND_CASES))
+def test_ln_pending_emulation_is_inside(name, dtype):
+    c = PB.ln_pend_case(name)
+    w1, w3 = _ln_pend_margins(c, dtype)
+    print(f"[bound control ln_pending {name} {PB.NAME[dtype]}] fp32 emulation: residual {w1:.3f} of bound 1, operand {w3:.3f} of bound 3")
+    assert w1 <= 1.0 and w3 < 1.0
+    # the branch image is a clamped round to nearest of a sum the bound of assertion 1 also covers (without gate and residual)
+    if c.nsplit:
+        y64 = c.slabs[:, :, :c.D].double().sum(0) + (c.bias.double() if c.bias is not None else 0.0)
+        assert (c.y_save(dtype).double() - y64).abs().max() <= 2 * PB.U[dtype] * y64.abs().max()
+
+
+@DTYPES
+@pytest.mark.parametrize("wrong", PB.LN_PEND_WRONG)
+def test_ln_pending_wrong_variants_are_outside(wrong, dtype):
+    """every wrong variant leaves bound 1 or bound 3 on at least one case; `caught` names them"""
+    caught = []
+    for name in PB.LN_PEND_CASES:
+        w1, w3 = _ln_pend_margins(PB.ln_pend_case(name), dtype, wrong)
+        if w1 > 1.0 or w3 >= 1.0:
+            caught.append(f"{name} ({w1:.3g} / {w3:.3g})")
+    print(f"[bound control ln_pending {PB.NAME[dtype]}] WRONG ({wrong}) outside on: {', '.join(caught) or 'nothing'}")
+    assert caught, wrong
+    # and each where it should be: a slab added again only where the load chunk has an unused slot, the exchanged permutation only where P > 16
+    expect = {"again": {"d256_rows", "d1280", "d1280_tperm"}, "tperm": {"d256_tperm", "d1280_tperm"}}.get(wrong)
+    if expect:
+        assert {s.split()[0] for s in caught} == expect, caught
+
+
+def test_ln_pending_saturating_branch_image():
+    c = PB.ln_pend_sat_case()
+    y16, ybf = c.y_save(PB.F16), c.y_save(PB.BF16)
+    assert y16[3, 5].item() == PB.F16_MAX and y16[6, 60].item() == -PB.F16_MAX and torch.isfinite(y16.float()).all()
+    assert ybf[3, 5].item() == 79872.0 and ybf[6, 60].item() == -70144.0                   # bf16's grid around 80000 / 70000.5 has steps of 512
+    assert (c.branch32().abs() > PB.F16_MAX).sum().item() == 2
