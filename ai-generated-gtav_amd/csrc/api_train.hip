@@ -1,6 +1,8 @@
 // C-ABI of the DiT training step (include/gtav_amd.h): forward with saved activations, backward, AdamW, optimizer state.
 #include "api_internal.h"
 
+#include <algorithm>
+
 static int g_dw_grouped = GTAV_ENV_INT("GTAV_DW_GROUPED", 1);   // experiments build: 0 = one launch per weight gradient (A/B runs)
 static int g_fuse_gelu_fwd = GTAV_ENV_INT("GTAV_FUSE_GELU_FWD", 1); // experiments build: 0 = h = GELU(u) by the flat elementwise kernel behind fc1 (A/B runs)
 static int g_fuse_gelu = GTAV_ENV_INT("GTAV_FUSE_GELU_BWD", 1); // experiments build: 0 = gelu_bwd and the fc1 bias column sums as two launches (A/B runs)
@@ -56,7 +58,14 @@ static int train_enable_body(gtav_dit* h, float* grad_arena_dev, int64_t grad_ar
     gtav_dit::Train& t = h->tr;
     Arena& a = h->arena;
     const int D = h->D, L = h->L, Hp = h->Hm_pad;
-    GTAV_REQUIRE(h->Hm == h->Hm_pad && h->Kpe == h->C * h->p * h->p, "train_enable: padded MLP width / patch size are not implemented for training");
+    // Every patch width F = C p^2 the forward takes, but for two refusals.  The patch embedding contracts over Kpe = round_up(F, 64) columns whose pad is zero in
+    // both operands (patchify, the weight image), the final projection's gradient dfo is Nf = round_up(F, 64) wide with zero pad columns (mse_bwd_patch).
+    const int F = h->C * h->p * h->p, Nf = round_up(h->Nfin, 64);
+    GTAV_REQUIRE(h->Hm == h->Hm_pad, "train_enable: a padded MLP width (mlp_ratio * hidden_size = %d, padded to %d) is not implemented for training", h->Hm, h->Hm_pad);
+    GTAV_REQUIRE(F % 4 == 0, "train_enable: a patch of in_channels * patch_size^2 = %d features is not implemented for training (the weight-gradient GEMM writes "
+                 "multiples of 4 columns)", F);
+    GTAV_REQUIRE((size_t)Nf <= (size_t)h->max_rows * D, "train_enable: the final projection's %d features do not fit the bias-gradient scratch (%d x %d)", Nf,
+                 h->max_rows, D);
     size_t count = 0;
     std::vector<std::string> names;
     for (auto& kv : h->wt.slots) {
@@ -92,7 +101,7 @@ static int train_enable_body(gtav_dit* h, float* grad_arena_dev, int64_t grad_ar
     }
     RET_IF(a.alloc_t(&t.ctl, 8));
     RET_IF(train_resolve_slots(h));
-    t.red_ws_floats = colsum_workspace(h->Mmax > h->max_rows ? h->Mmax : h->max_rows, h->Hm_pad > 6 * D ? h->Hm_pad : 6 * D);
+    t.red_ws_floats = colsum_workspace(h->Mmax > h->max_rows ? h->Mmax : h->max_rows, std::max(std::max(h->Hm_pad, 6 * D), Nf));
     RET_IF(a.alloc_t(&t.red_ws, t.red_ws_floats));
     RET_IF(a.alloc_t(&t.sumsq_part, (size_t)sumsq_parts(count)));
     {
@@ -166,8 +175,9 @@ static int train_enable_body(gtav_dit* h, float* grad_arena_dev, int64_t grad_ar
     RET_IF(a.alloc_t(&t.dmod, R * h->MODW)); RET_IF(a.alloc_t(&t.dSc, R * D)); RET_IF(a.alloc_t(&t.ada_part, ada_bwd_dx_workspace(h->MODW, D, (int)R))); RET_IF(a.alloc_t(&t.dc, R * D)); RET_IF(a.alloc_t(&t.dh0, R * D));
     RET_IF(a.alloc_t(&t.dz0, R * D));
     RET_IF(a.alloc_t(&t.g_d, Mx * D)); RET_IF(a.alloc_t(&t.g_d2, Mx * D)); RET_IF(a.alloc_t(&t.g_h, Mx * Hp)); RET_IF(a.alloc_t(&t.g_u, Mx * Hp)); RET_IF(a.alloc_t(&t.g_qkv, Mx * 3 * D));
-    RET_IF(a.alloc_t(&t.dao, Mm * D)); RET_IF(a.alloc_t(&t.dfo, Mx * 64));
-    const size_t widest = (size_t)(Hp > 3 * D ? Hp : 3 * D);
+    RET_IF(a.alloc_t(&t.dao, Mm * D)); RET_IF(a.alloc_t(&t.dfo, Mx * Nf));
+    // (rows of the transposed images, padded to the GEMM's 128-row tiles: dfo^T has Nf rows, xp^T has Kpe)
+    const size_t widest = (size_t)std::max(std::max(Hp, 3 * D), std::max(round_up(Nf, 128), round_up(h->Kpe, 128)));
     RET_IF(a.alloc_t(&t.tA, widest * Mp)); RET_IF(a.alloc_t(&t.tB, widest * Mp));
     if (D % 256 == 0 && Hp % 256 == 0) {   // (rows of the transposed images: fc2 dY / X, fc1, out-proj, QKV)
         const size_t ra[4] = {(size_t)D, (size_t)Hp, (size_t)D, (size_t)3 * D}, rb[4] = {(size_t)Hp, (size_t)D, (size_t)D, (size_t)D};
@@ -470,7 +480,16 @@ struct TrainBackward {
     }
     // dW[n][k] += sum_m dY[m][n] X[m][k]: both operands transposed to [.][Mp] (tokens are the contraction), accumulating epilogue; slot_i >= 0: one of the four of a
     // half-block (fc2, fc1, out-proj, QKV), deferred into its grouped launch where that is on
-    int gemm_dw(const f16* dY, int N, const f16* X, int K, float* grad, int slot_i = -1) {
+    // Kv < K (the patch embedding at C p^2 % 64 != 0): X carries K - Kv zero pad columns which the gradient, contiguous [N][Kv], has no room for: the
+    // transposed-operand GEMM writes the first Kv of its K features with ldo = Kv (the other forms write whole 128 / 256-column tiles)
+    int gemm_dw(const f16* dY, int N, const f16* X, int K, float* grad, int slot_i = -1, int Kv = 0) {
+        if (Kv > 0 && Kv < K) {
+            RET_IF(op->transpose_tiled(dY, M, N, tr.tA, s));
+            RET_IF(op->transpose_tiled(X, M, K, tr.tB, s));
+            GemmParams q = gemm_params(tr.tA, Mp, tr.tB, N, Kv, Mp);
+            q.out = grad; q.ldo = Kv;
+            return op->gemm(q, EPI_RESID, s);
+        }
         if (tn_dw && slot_i >= 0) {
             dwg[ndw++] = GemmDwGroup{dY, X, grad, N, K, K};
             return 0;
@@ -519,19 +538,20 @@ struct TrainBackward {
 int TrainBackward::final_layer(const float* v_pred, const float* v_target) {
     const float scale = 2.0f * tr.loss_scale / ((float)B * (float)(h->C * h->H * h->W));
     op = &h->ops(2 * L + 1);
-    RET_IF(op->mse_bwd_patch(v_pred, v_target, B, T, h->C, h->H, h->W, h->p, scale, tr.dfo, 64, h->err_flag, s));
-    // db: column sums over the 64-wide (zero-padded) dfo, only the first Nfin belong to the bias: sum into a scratch row first
-    GTAV_CHECK_HIP(hipMemsetAsync(tr.dSc, 0, 64 * sizeof(float), s));
-    RET_IF(op->colsum_tiled(tr.dfo, M, 64, tr.dSc, tr.red_ws, s));
+    const int Nf = round_up(h->Nfin, 64);   // width of dfo: the final projection's features padded to whole 64-column tiles (zeros: mse_bwd_patch)
+    RET_IF(op->mse_bwd_patch(v_pred, v_target, B, T, h->C, h->H, h->W, h->p, scale, tr.dfo, Nf, h->err_flag, s));
+    // db: column sums over the Nf-wide (zero-padded) dfo, only the first Nfin belong to the bias: sum into a scratch row first
+    GTAV_CHECK_HIP(hipMemsetAsync(tr.dSc, 0, Nf * sizeof(float), s));
+    RET_IF(op->colsum_tiled(tr.dfo, M, Nf, tr.dSc, tr.red_ws, s));
     RET_IF(launch_add_f32(tr.fin.b->grad, tr.dSc, tr.fin.b->grad, h->Nfin, s));
-    // dW_final [Nfin][D] += dfo^T xnF   (M = Nfin rows of the 64-row transposed operand)
-    RET_IF(op->transpose_tiled(tr.dfo, M, 64, tr.tA, s));
+    // dW_final [Nfin][D] += dfo^T xnF   (M = Nfin rows of the Nf-row transposed operand)
+    RET_IF(op->transpose_tiled(tr.dfo, M, Nf, tr.tA, s));
     RET_IF(op->transpose_tiled(tr.xnF, M, D, tr.tB, s));
     GemmParams q = gemm_params(tr.tA, Mp, tr.tB, h->Nfin, D, Mp);
     q.out = tr.fin.w->grad; q.ldo = D;
     RET_IF(op->gemm(q, EPI_RESID, s));
     // d xnF = dfo W_final  -> fp32 [M][D]
-    RET_IF(gemm_dx(tr.dfo, tr.fin.w->wT, D, 64, EPI_F32, tr.dtmp, D));
+    RET_IF(gemm_dx(tr.dfo, tr.fin.w->wT, D, Nf, EPI_F32, tr.dtmp, D));
     const float* mf = h->mod + (size_t)L * 12 * D;
     float* dmf = tr.dmod + (size_t)L * 12 * D;
     RET_IF(ln_bwd(tr.dtmp, tr.res[4 * L], mf + D, 0, dmf, dmf + D));
@@ -588,8 +608,8 @@ int TrainBackward::embedders() {
     op = &h->ops(2 * L);
     RET_IF(launch_colsum_f32(tr.dres, D, M, D, tr.pe.b->grad, tr.red_ws, s));
     RET_IF(op->to_tiled(tr.dres, M, D, tr.g_d, h->err_flag, s));
-    GTAV_REQUIRE(tr.pe.w->C == h->Kpe, "train_backward: a patch embedding with padded K (%d of %d) is not implemented", tr.pe.w->C, h->Kpe);
-    RET_IF(gemm_dw(tr.g_d, D, tr.xp, h->Kpe, tr.pe.w->grad));
+    // dW_pe [D][F]: xp keeps its Kpe - F zero pad columns, the gradient (and with it the master and the moments) has none
+    RET_IF(gemm_dw(tr.g_d, D, tr.xp, h->Kpe, tr.pe.w->grad, -1, tr.pe.w->C));
     // ---- the shared conditioning path (fp32, `rows` = B T rows): c = W_2 SiLU(W_0 e + b_0) + b_2 (+ W_ext a + b_ext), SiLU(c) feeds every adaLN
     // projection (their own gradients were taken block by block above) ----
     RET_IF(launch_ada_bwd_dx(tr.dmod, MODW, h->w_ada, D, rows, tr.dSc, tr.ada_part, s));
@@ -622,7 +642,6 @@ int gtav_dit_train_backward_phases(gtav_dit* h, const float* v_pred, const float
     GTAV_REQUIRE(h->tr.on && h->tr.have_fwd, "train_backward: no saved forward (gtav_dit_train_forward)");
     GTAV_REQUIRE(phase_begin >= 0 && phase_begin <= phase_end && phase_end <= h->L + 2, "train_backward: phases [%d, %d) outside [0, %d]", phase_begin, phase_end,
                  h->L + 2);
-    GTAV_REQUIRE(h->Nfin <= 64, "train_backward: a final projection wider than 64 features is not implemented");
     TrainBackward bw(h, (hipStream_t)stream);
     const int L = h->L;
     if (phase_begin <= 0 && 0 < phase_end) RET_IF(bw.final_layer(v_pred, v_target));

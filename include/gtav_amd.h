@@ -190,6 +190,10 @@ int gtav_timer_calibrate(int32_t spin_us, int32_t reps, double* event_us_mean, d
  * caller-owned device buffer of gtav_dit_train_param_count floats that receives all gradients contiguously, parameters in the
  * lexicographic order of their state-dict names (NULL: the handle allocates it).  These calls allocate (enable) or synchronise
  * (train_stats); forward / backward / adamw_step only enqueue.
+ * Accepted geometry: gtav_dit_train_enable[_typed] takes every patch_size / in_channels gtav_dit_create takes (F = in_channels * patch_size^2 features per
+ * patch, any input_h x input_w with tokens per frame % 8 == 0), with two refusals by name: F % 4 != 0, and an MLP width mlp_ratio * hidden_size that is not a
+ * multiple of 128 (a padded MLP width).  Where F is not a multiple of 64 the patch embedding and the final projection work on operands padded with zero columns
+ * to the next multiple of 64; gradients, masters and optimizer state keep the state-dict shapes (gtav_dit_train_param_count counts no pad).  DESIGN.md 7.
  * gtav_dit_train_enable_typed picks the operand type of the whole training step (the reference's `--mixed_precision bf16`):
  *   GTAV_OPERAND_F16    exactly gtav_dit_train_enable (which refuses a handle with any bf16 operand group).
  *   GTAV_OPERAND_BF16   every operand group is set to bf16, then training is enabled (a handle whose groups are all bf16 already is accepted, one with

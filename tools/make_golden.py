@@ -3,7 +3,7 @@
 Run in the build container only:   PYTHONDONTWRITEBYTECODE=1 python tools/make_golden.py
 g0_constants and g1_ops_dit, which tests compare bit for bit or nearly so, were recorded with MKL_CBWR=COMPATIBLE, the MKL branch
 tests/conftest.py pins (torch's CPU sin / cos differ in the last bits between MKL's branches); the other files, compared within
-tolerances, come from MKL's AVX-512 branch.
+tolerances, come from MKL's AVX-512 branch (g14_geometry among them; `--only-g14` writes it alone).
 The reference is imported through tools/ref_shim.py (stubs for the absent third-party packages); its
 modules are loaded with this repo's deterministic synthetic weights (gtav_amd.weights.synth_state_dict, every
 matrix non-zero — the reference's own init zeroes the adaLN gates, which would make every block the identity).
@@ -295,6 +295,52 @@ def g12_long_window(rd, ref_denoise_step, ref_schedule):
     save("g13_long_window_steps.safetensors", g13)
 
 
+G14_GEOMETRIES = {"p4c4": dict(input_h=16, input_w=32, patch_size=4, in_channels=4), "p2c8": dict(input_h=8, input_w=16, patch_size=2, in_channels=8)}
+
+
+def g14_sel(name, v):
+    """Gradient elements G14 keeps: complete tensors of up to 512 elements; every 97th element of the two weights whose shape follows the patch geometry; every
+    997th of the other large ones (G8 keeps every 97th of all of them at one geometry: two geometries at that rate would be 400 KB of gradients alone)."""
+    if v.numel() <= 512:
+        return v.reshape(-1).clone()
+    return v.reshape(-1)[::97 if name in ("x_embedder.proj.weight", "final_layer.linear.weight") else 997].clone()
+
+
+def g14_geometry(rd, ref_denoise_step, ref_schedule):
+    """G14: the reference's own DiT at two patch geometries other than (patch 2, 16 channels) — patch 4 on 4-channel 16 x 32 latents (64 features per patch,
+    the (ph, pw, c) order at a patch other than 2) and patch 2 on 8-channel 8 x 16 latents (32 features: the patch embedding contracts over zero-padded columns).
+    Small width (hidden 256, depth 2, seed 3), B = 2, T = 3, actions on.  Per geometry: inputs, v_pred, loss, the gradient norm of EVERY parameter (sorted by
+    name), the g14_sel selection of every gradient, and the last frame of one `denoise_step` at noise index 50 of 50 on the same buffer.  Own generators."""
+    out = {}
+    ac = torch.cumprod(1.0 - ref_schedule(1000).float(), dim=0)[:, None, None, None]
+    nr = torch.linspace(0, 999, 51)
+    for gi, (tag, geo) in enumerate(G14_GEOMETRIES.items()):
+        kw = dict(SMALL_DIT, **geo)
+        C, h, w = kw["in_channels"], kw["input_h"], kw["input_w"]
+        sd = W.synth_state_dict(W.dit_param_shapes(**kw), seed=3)
+        m = load_into(rd.DiT(**kw), sd).train()
+        g = torch.Generator().manual_seed(141 + gi)
+        x = torch.randn(2, 3, C, h, w, generator=g)
+        t = torch.randint(0, 1000, (2, 3), generator=g)
+        a = one_hot_actions(2, 3, g)
+        vt = torch.randn(2, 1, C, h, w, generator=g)
+        params = {k: p for k, p in m.named_parameters() if p.requires_grad}
+        v_pred = m(x, t, a)
+        loss = torch.nn.functional.mse_loss(v_pred[:, -1:], vt)
+        loss.backward()
+        names = sorted(k for k in params if params[k].grad is not None)
+        out.update({f"{tag}.x": x, f"{tag}.t": t, f"{tag}.actions": a, f"{tag}.v_target": vt, f"{tag}.v_pred": v_pred.detach(), f"{tag}.loss": loss.detach().reshape(1),
+                    f"{tag}.grad_norms": torch.stack([params[k].grad.norm() for k in names]), f"{tag}.names_check": torch.tensor([len(names)])})
+        for k in names:
+            out[f"{tag}.grad.{k}"] = g14_sel(k, params[k].grad)
+        with torch.no_grad():
+            xp, _ = ref_denoise_step(m.eval(), x, a, 50, 15, nr, ac, start_frame=0, dtype=torch.bfloat16)
+        out[f"{tag}.x_pred_last_50"] = xp[:, -1:].clone()
+    save("g14_geometry.safetensors", out)
+    size = os.path.getsize(os.path.join(OUT, "g14_geometry.safetensors"))
+    assert size < 300 * 1024, f"g14_geometry.safetensors is {size} bytes"
+
+
 def resize_probe_image(H, W):
     """A deterministic uint8 image (H, W, 3) from integer arithmetic only (no RNG: the tests rebuild it bit for bit): smooth ramps + a fine texture."""
     y = torch.arange(H).view(H, 1, 1)
@@ -331,6 +377,8 @@ def main():
     rd, rv, ref_denoise_step, ref_schedule = ref_shim.import_reference()
     if "--only-g12" in sys.argv:
         return g12_long_window(rd, ref_denoise_step, ref_schedule)
+    if "--only-g14" in sys.argv:
+        return g14_geometry(rd, ref_denoise_step, ref_schedule)
     g11_resize()
     if "--only-g9-g10" in sys.argv:
         g10_frame_loop(rd, ref_schedule)
@@ -494,6 +542,7 @@ def main():
     g1_per_op(rd, rv)
     g8_training(rd)
     g12_long_window(rd, ref_denoise_step, ref_schedule)
+    g14_geometry(rd, ref_denoise_step, ref_schedule)
     save("g3_full_vae.safetensors", {"mean": post.mean, "logvar": post.logvar, "z": z, "decoded_stride4": dec[:, :, ::4, ::4].clone(),
                                      "decoded_row100": dec[:, :, 100].clone()})
 

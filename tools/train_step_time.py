@@ -9,7 +9,8 @@ A/B of profiles/round7/train_step_bf16_ab.txt.
 bytes (train_saved_bytes) and the device's free memory before and after the training handle was built.  --forward-only times gtav_dit_train_forward alone on the
 same inputs (the yardstick of the recompute mode's extra time: it re-runs L - 1 of the L blocks' forwards).
 --mixed none | one | alternating: DiT(train_range_policy="auto"), the mixed operand types of DESIGN.md 7 (product library: give --dtype, the type every group starts
-on) with no group switched, with group 1 on the other type, or with every even group on it (profiles/train_mixed/)."""
+on) with no group switched, with group 1 on the other type, or with every even group on it (profiles/train_mixed/).
+--in-channels C --patch-size p: another patch geometry than (2, 16) (profiles/geometry/)."""
 import argparse
 import json
 import os
@@ -32,6 +33,8 @@ def main():
     ap.add_argument("--recompute", action="store_true", help="DiT(train_recompute=True): recompute each block's activations in the backward pass")
     ap.add_argument("--forward-only", action="store_true", help="time the training forward (forward_train) alone instead of the optimisation step")
     ap.add_argument("--mixed", choices=("none", "one", "alternating"), default=None, help="DiT(train_range_policy='auto') and which groups run on the other type")
+    ap.add_argument("--in-channels", type=int, default=16, help="latent channels (profiles/geometry/: 4 at patch 2 = 16 features per patch, padded to 64)")
+    ap.add_argument("--patch-size", type=int, default=2)
     a = ap.parse_args()
     if (a.recompute or a.mixed) and a.dtype is None:
         ap.error("--recompute / --mixed run on the product library: give --dtype fp16 or bf16")
@@ -47,11 +50,12 @@ def main():
     train_dtype = torch.bfloat16 if a.dtype == "bf16" else torch.float16
     LH, LW = a.latent_hw
     F = a.frames
+    C_ = a.in_channels
     from gtav_amd.model.dit import DiT
-    dit = DiT(input_h=LH, input_w=LW, patch_size=2, hidden_size=1024, depth=16, num_heads=16, max_frames=F, init_weights=False, max_batch=B, trainable=True,
+    dit = DiT(input_h=LH, input_w=LW, patch_size=a.patch_size, in_channels=C_, hidden_size=1024, depth=16, num_heads=16, max_frames=F, init_weights=False, max_batch=B, trainable=True,
               train_dtype=train_dtype, train_max_frames=F if F > 8 else None, train_recompute=a.recompute,
               **({"train_range_policy": "auto"} if a.mixed else {}))   # DiT-S/2 at the given latent size
-    dit.load_state_dict(W.synth_state_dict(W.dit_param_shapes(depth=16, input_h=LH, input_w=LW), seed=0))
+    dit.load_state_dict(W.synth_state_dict(W.dit_param_shapes(depth=16, input_h=LH, input_w=LW, patch_size=a.patch_size, in_channels=C_), seed=0))
     with torch.cuda.device(dev):
         torch.cuda.synchronize()
         free_before = torch.cuda.mem_get_info()[0]
@@ -62,13 +66,13 @@ def main():
         other = torch.float16 if a.dtype == "bf16" else torch.bfloat16
         dit.train_set_group_dtype(other, [1] if a.mixed == "one" else range(0, dit.n_operand_groups, 2))
     g = torch.Generator().manual_seed(7)
-    lat = (torch.randn(B, F, 16, LH, LW, generator=g) * 0.5).to(dev)
+    lat = (torch.randn(B, F, C_, LH, LW, generator=g) * 0.5).to(dev)
     actions = torch.zeros(B, F, 25, device=dev)
     actions[:, :, 3] = 1
     tgt = torch.randint(1, 51, (B,), generator=g)
     ctx = torch.randint(1, 41, (B,), generator=g)
-    ctx_noise = torch.randn(B, F - 1, 16, LH, LW, generator=g).to(dev)
-    noise = torch.randn(B, 1, 16, LH, LW, generator=g).to(dev)
+    ctx_noise = torch.randn(B, F - 1, C_, LH, LW, generator=g).to(dev)
+    noise = torch.randn(B, 1, C_, LH, LW, generator=g).to(dev)
 
     def step():
         return training_step(dit, lat, actions, tgt, ctx, ctx_noise, noise, lr=1e-5, weight_decay=0.01, max_grad_norm=1.0, world_size=1, n_prompt_frames=F - 1)
@@ -90,7 +94,7 @@ def main():
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / a.steps * 1e3
     applied, skipped, gnorm = dit.train_stats()
-    print(json.dumps({"batch": B, "frames": F, "latent_hw": [LH, LW], "dtype": a.dtype or "fp16 (experiments library)", "recompute": a.recompute, "mixed": a.mixed,
+    print(json.dumps({"batch": B, "frames": F, "latent_hw": [LH, LW], "in_channels": C_, "patch_size": a.patch_size, "dtype": a.dtype or "fp16 (experiments library)", "recompute": a.recompute, "mixed": a.mixed,
                       "bf16_groups": [i for i, d in enumerate(dit.operand_dtypes()) if d == torch.bfloat16],
                       "what": "train_forward" if a.forward_only else "optimisation step", "ms_per_step": round(ms, 3), "loss": float(loss), "grad_norm": gnorm, "skipped": skipped,
                       "saved_bytes": saved, "free_before_enable": free_before, "free_after_enable": free_after, "handle_bytes": free_before - free_after,
