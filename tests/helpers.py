@@ -1,4 +1,6 @@
 """Thin torch wrappers over the kernel-level C-ABI entry points (test infrastructure)."""
+import os
+
 import torch
 
 from gtav_amd import lib as L
@@ -15,6 +17,16 @@ def stream():
 def rel_l2(a, b):
     a, b = a.detach().double().cpu(), b.detach().double().cpu()
     return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
+
+
+def rel_l2_logged(a, b, what="", tag="rel_l2"):
+    """rel_l2 that prints the measured margin under the running test's name (`pytest -s` shows them; profiles/*/margins.txt are such printouts).  Test files import it
+    as their local rel_l2.  `what` names the compared tensor where a test compares several; the geometry files' lines (tag="geometry") always carry that field."""
+    v = rel_l2(a, b)
+    test = os.environ.get("PYTEST_CURRENT_TEST", "").split("::")[-1].split(" ")[0]
+    field = f"{what} " if what or tag != "rel_l2" else ""
+    print(f"[{tag} {test}] {field}{v:.3e}")
+    return v
 
 
 def tiled_index(R, K):

@@ -6,6 +6,7 @@ Bounds are those of tests/test_gpu_models.py for the same comparisons: TOL_SMALL
 bf16 operands 1.5e-2 (tests/test_gpu_range.py TOL_BF16).  Captured and replayed sampler steps and the context-cached step reproduce the eager window step
 bit for bit.  The posterior sample: 2^-17 std + 2^-22 |result| per element (tests/test_gpu_rng.py).  `pytest -s` prints every margin
 (profiles/geometry/margins.txt)."""
+import functools
 import os
 
 import numpy as np
@@ -15,7 +16,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from helpers import dev  # noqa: E402
-from helpers import rel_l2 as _rel_l2  # noqa: E402
+from helpers import rel_l2_logged  # noqa: E402
 from oracle import ref_cpu as O  # noqa: E402
 import gtav_amd.weights as W  # noqa: E402
 from gtav_amd import rng as R  # noqa: E402
@@ -40,10 +41,7 @@ GEOS = sorted(GEO)
 SMALL_VAE = dict(input_height=64, input_width=96, patch_size=8, enc_dim=128, enc_depth=2, enc_heads=2, dec_dim=256, dec_depth=2, dec_heads=4)   # tests/test_gpu_models.py, less latent_dim
 
 
-def rel_l2(a, b, what=""):
-    v = _rel_l2(a, b)
-    print(f"[geometry {os.environ.get('PYTEST_CURRENT_TEST', '').split('::')[-1].split(' ')[0]}] {what} {v:.3e}")
-    return v
+rel_l2 = functools.partial(rel_l2_logged, tag="geometry")       # rel_l2(a, b, what): (-s shows the measured margins)
 
 
 def _mk_dit(geo, seed, max_batch=2, **extra):

@@ -2,11 +2,10 @@
 patch from 16 to 256, where the patch embedding contracts over Kpe = round_up(F, 64) zero-padded columns and the final projection's gradient is round_up(F, 64)
 wide.  Toy model (hidden 256, depth 2, 4 heads, 25 actions), B = 2, T = 3, 32 tokens per frame at every geometry; fp16 and bf16 operands.
 
-Bounds are the project's own for the same comparisons, restated: forward 2e-3 (tests/test_gpu_train.py) / bf16 1.5e-2 (tests/test_gpu_train_bf16.py
-TOL_FWD_BF16); every gradient tensor within GRAD_TOL = 4.5e-3 relative L2 (tests/test_gpu_train.py GRAD_TOL) / bf16 8 x (tests/test_gpu_train_bf16.py
-GRAD_TOL_BF16).  x_embedder.proj.weight is the worst tensor of every training test of the project: where it ALONE exceeds GRAD_TOL at some geometry it is held
-to 1.5 x the figure the same tensor reads at (patch 2, 16 channels, 8 x 16) with the same batch and seed in the same run — the geometry every earlier test
-uses (the rule of tests/test_gpu_train_long_window.py).  `pytest -s` prints every margin (profiles/geometry/grad_errors.txt).
+Bounds are the project's own for the same comparisons (tests/train_cases.py): forward within FWD_TOL, every gradient tensor within GRAD_TOL relative L2, for
+fp16 and for bf16 operands.  x_embedder.proj.weight is the worst tensor of every training test of the project: where it ALONE exceeds GRAD_TOL at some
+geometry it is held to 1.5 x the figure the same tensor reads at (patch 2, 16 channels, 8 x 16) with the same batch and seed in the same run — the geometry
+every earlier test uses (the rule of tests/test_gpu_train_long_window.py).  `pytest -s` prints every margin (profiles/geometry/grad_errors.txt).
 
 The training handle has no hook that seeds its workspace, so rows behind M and the pad columns of xp / dfo cannot be poisoned from here; that the pad columns
 of the patch-embedding image stay exactly zero through optimizer steps is asserted through the gradients of a later step being finite and equal, bit for bit,
@@ -18,14 +17,13 @@ import os
 import pytest
 import torch
 
-from helpers import dev
+import train_cases as TC
+from helpers import dev, rel_l2_logged
 from helpers import rel_l2 as _rel_l2
+from train_cases import DTYPES, F16, FWD_TOL, GRAD_TOL
 
 pytestmark = pytest.mark.gpu
 
-F16, BF16 = torch.float16, torch.bfloat16
-GRAD_TOL = {F16: 4.5e-3, BF16: 8 * 4.5e-3}     # tests/test_gpu_train.py GRAD_TOL, tests/test_gpu_train_bf16.py GRAD_TOL_BF16
-FWD_TOL = {F16: 2e-3, BF16: 1.5e-2}            # tests/test_gpu_train.py, tests/test_gpu_train_bf16.py TOL_FWD_BF16
 PE = "x_embedder.proj.weight"
 
 SMALL = dict(hidden_size=256, depth=2, num_heads=4, external_cond_dim=25)
@@ -39,74 +37,34 @@ GEO = {   # id: geometry; F = C p^2, Kpe = round_up(F, 64)
 }
 DEFAULT = dict(input_h=8, input_w=16, patch_size=2, in_channels=16)          # the geometry of every other training test
 GEOS = sorted(GEO)
-DTYPES = pytest.mark.parametrize("dtype", [F16, BF16], ids=["fp16", "bf16"])
 STEP_KW = dict(lr=3e-4, weight_decay=0.01, max_grad_norm=1.0)
 
-
-def rel_l2(a, b, what=""):
-    v = _rel_l2(a, b)
-    print(f"[geometry {os.environ.get('PYTEST_CURRENT_TEST', '').split('::')[-1].split(' ')[0]}] {what} {v:.3e}")   # (-s shows the measured margins)
-    return v
+rel_l2 = functools.partial(rel_l2_logged, tag="geometry")       # rel_l2(a, b, what): (-s shows the measured margins)
 
 
 def _kw(geo):
     return dict(SMALL, **(DEFAULT if geo == "default" else GEO[geo]))
 
 
-@functools.lru_cache(maxsize=None)
 def _sd(geo, seed=1):
-    import gtav_amd.weights as W
-    return W.synth_state_dict(W.dit_param_shapes(**_kw(geo)), seed=seed)
+    return TC.state_dict(_kw(geo), seed)
 
 
-def _inputs(geo, actions=True, seed=0, B=2, T=3):
-    kw = _kw(geo)
-    C, h, w = kw["in_channels"], kw["input_h"], kw["input_w"]
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(B, T, C, h, w, generator=g)
-    t = torch.randint(0, 1000, (B, T), generator=g)
-    a = None
-    if actions:
-        a = torch.zeros(B, T, 25)
-        a[:, :, 3] = 1
-        a[0, T - 1, 7] = 1
-    vt = torch.randn(B, 1, C, h, w, generator=g)
-    return x, t, a, vt
+def _inputs(geo, actions=True):
+    return TC.inputs(_kw(geo), 2, 3, actions)
 
 
-@functools.lru_cache(maxsize=None)
 def _ref(geo, actions):
-    """The oracle's loss, v_pred and gradients of one geometry, computed once and shared (never modified)."""
-    from oracle import ref_cpu as O
-    x, t, a, vt = _inputs(geo, actions)
-    return O.dit_loss_and_grads(_sd(geo), O.DiTConfig(**_kw(geo)), x, t, a, vt)
+    """The oracle's loss, v_pred and gradients of one geometry (shared: never modified)."""
+    return TC.oracle(_kw(geo), 2, 3, actions)[2:]
 
 
 def _model(geo, dtype=F16, sd=None, **extra):
-    from gtav_amd.model.dit import DiT
-    m = DiT(**_kw(geo), max_batch=2, max_frames=3, init_weights=False, trainable=True, train_dtype=dtype, **extra)
-    m.load_state_dict(_sd(geo) if sd is None else sd)
-    return m
+    return TC.model(_kw(geo), 2, 3, dtype, sd, **extra)
 
 
-def _grad_errors(m, grads):
-    errs = {}
-    for k, gref in grads.items():
-        g = m.grad(k).cpu()
-        assert torch.isfinite(g).all(), k
-        if gref.norm() == 0:
-            assert g.abs().max() == 0, k                 # external_cond.* without actions: unused, gradient None upstream
-            continue
-        errs[k] = _rel_l2(g, gref)
-    return errs
-
-
-def _backward(m, x, t, a, vt):
-    v = m.forward_train(x, t, a)
-    m.zero_grad()
-    m.backward_(v, vt)
-    m.check()
-    return v
+def _backward(m, *inputs):
+    return TC.forward_backward(m, inputs)
 
 
 @functools.lru_cache(maxsize=None)
@@ -145,7 +103,7 @@ def test_gradients_match_autograd(geo, actions, dtype):
     e_loss = abs(float(loss) - float(loss_ref)) / float(loss_ref)
     print(f"[geometry {geo}] loss {float(loss):.6f} oracle {float(loss_ref):.6f} rel {e_loss:.3e}")
     assert e_loss < FWD_TOL[dtype]
-    _accept(_grad_errors(m, grads), dtype, actions, f"{geo} actions={actions} {dtype}")
+    _accept(TC.grad_errors(m, grads), dtype, actions, f"{geo} actions={actions} {dtype}")
 
 
 def _g14_sel(name, v):
@@ -210,21 +168,12 @@ def test_adamw_step_matches_reference(geo, dtype):
     _, v2_ref, grads2 = O.dit_loss_and_grads(sd2, O.DiTConfig(**_kw(geo)), x, t, a, vt)
     v2 = _backward(m, x, t, a, vt)
     assert rel_l2(v2, v2_ref, "v_pred after the step") < FWD_TOL[dtype]
-    _accept(_grad_errors(m, grads2), dtype, True, f"{geo} {dtype} after one AdamW step")
+    _accept(TC.grad_errors(m, grads2), dtype, True, f"{geo} {dtype} after one AdamW step")
 
 
 # ---- 3. the training modes: recompute, phases and buckets, checkpoints, mixed-capable handles, device noise ---------------------------------------
-def _clip(geo, seed=5, B=2):
-    kw = _kw(geo)
-    C, h, w = kw["in_channels"], kw["input_h"], kw["input_w"]
-    g = torch.Generator().manual_seed(seed)
-    lat = torch.randn(B, 3, C, h, w, generator=g) * 0.5
-    a = torch.zeros(B, 3, 25)
-    a[:, :, 3] = 1
-    tgt, ctx = torch.tensor([30, 10][:B]), torch.tensor([5, 20][:B])
-    cn = torch.randn(B, 2, C, h, w, generator=g)
-    nz = torch.randn(B, 1, C, h, w, generator=g)
-    return lat, a, tgt, ctx, cn, nz
+def _clip(geo):
+    return TC.clip(_kw(geo), F=3)
 
 
 def _masters(m):

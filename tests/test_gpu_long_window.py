@@ -14,7 +14,7 @@ from safetensors.torch import load_file
 pytestmark = pytest.mark.gpu
 
 from helpers import dev, stream, untile  # noqa: E402
-from helpers import rel_l2 as _rel_l2  # noqa: E402
+from helpers import rel_l2_logged as rel_l2  # noqa: E402
 from oracle import ref_cpu as O  # noqa: E402
 import gtav_amd.weights as W  # noqa: E402
 from gtav_amd import lib as L  # noqa: E402
@@ -29,12 +29,6 @@ TOL_ATTN_OP = 6e-4     # tests/test_gpu_ops.py test_attention_temporal
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 SMALL_DIT = dict(input_h=8, input_w=16, patch_size=2, in_channels=16, hidden_size=256, depth=2, num_heads=4, external_cond_dim=25)
 SEED = 21              # tools/make_golden.py g12_long_window
-
-
-def rel_l2(a, b):
-    v = _rel_l2(a, b)
-    print(f"[rel_l2 {os.environ.get('PYTEST_CURRENT_TEST', '').split('::')[-1].split(' ')[0]}] {v:.3e}")
-    return v
 
 
 def _rand(*shape, seed=0):

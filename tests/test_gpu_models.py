@@ -11,7 +11,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from helpers import dev  # noqa: E402
-from helpers import rel_l2 as _rel_l2  # noqa: E402
+from helpers import rel_l2_logged as rel_l2  # noqa: E402
 from oracle import ref_cpu as O  # noqa: E402
 import gtav_amd.weights as W  # noqa: E402
 from gtav_amd.model.dit import DiT, DiT_models  # noqa: E402
@@ -20,12 +20,6 @@ from gtav_amd.model.vae import AutoencoderKL, VAE_models  # noqa: E402
 TOL_FULL = 1e-3      # north-star bound: full-size DiT / VAE forwards vs the fp32 CPU reference
 TOL_SMALL = 2e-3     # toy widths (hidden 128-256): fewer terms per dot product average the fp16 operand rounding less
 TOL_ROLLOUT = 1.5e-3   # tens of chained forwards (toy and full-size models; measured <= 7e-4, pytest -s prints every margin)
-
-
-def rel_l2(a, b):
-    v = _rel_l2(a, b)
-    print(f"[rel_l2 {os.environ.get('PYTEST_CURRENT_TEST', '').split('::')[-1].split(' ')[0]}] {v:.3e}")
-    return v
 
 
 SMALL_DIT = dict(input_h=8, input_w=16, patch_size=2, in_channels=16, hidden_size=256, depth=2, num_heads=4, external_cond_dim=25)
@@ -165,7 +159,6 @@ def test_fused_temporal_qkv_attention_is_bit_identical(full_dit):
         ms.denoise_step_(xd, 0, 4, 15, 500, 400, False, as_.to(dev()), cached=True)
         outs.append(xd.clone())
     assert torch.equal(outs[0], outs[1])
-
 
 
 def test_fused_spatial_qkv_attention_is_bit_identical(full_dit):

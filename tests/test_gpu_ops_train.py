@@ -20,6 +20,7 @@ pytestmark = pytest.mark.gpu
 import parity_bounds as PB  # noqa: E402
 from helpers import dev, stream, tiled_index  # noqa: E402
 from gtav_amd import lib as L  # noqa: E402
+from train_cases import GRAD_TOL  # noqa: E402
 
 F16, BF16 = PB.F16, PB.BF16
 DTYPES = pytest.mark.parametrize("dtype", PB.DTYPES, ids=[PB.NAME[d] for d in PB.DTYPES])
@@ -696,8 +697,7 @@ def test_ada_bwd_dx_needs_its_workspace():
 # ---- 8. whole-model gradients at the hidden sizes whose training step runs the other kernels -------------------------------------------------------------------------
 # hidden 512: ln_mod_bwd_fused_kernel<2>; hidden 768 (a multiple of 256 without a fused kernel): the two-kernel LayerNorm backward; 1280 and 2048: the widths
 # above 1024 (LayerNorm blocks of 5 and 8 waves, ln_mod_bwd_fused_kernel<8>).  Bounds: GRAD_TOL of
-# tests/test_gpu_train.py in fp16, 8 x that in bf16 (tests/test_gpu_train_bf16.py GRAD_TOL_BF16).
-GRAD_TOL = {torch.float16: 4.5e-3, torch.bfloat16: 8 * 4.5e-3}
+# tests/train_cases.py (fp16, and 8 x that in bf16).
 
 
 def _toy(hidden, heads):

@@ -5,15 +5,13 @@ default is fp16 operands (1e-3 parity with the fp32 reference).  A checkpoint wi
 range_policy="auto" the layer groups that saturated move to bf16 operands — the same kernels compiled for v_mfma_f32_16x16x32_bf16 — and the recomputed
 result matches the fp32 oracle to the bf16 bound.  Tolerances: bf16 operands (8 mantissa bits) give 6-9e-3 relative L2 per full-size forward
 (measured in round 1); the bound asserted here is 1.5e-2 for an all-bf16 model and 1e-2 when only the saturated group is bf16."""
-import os
-
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
 from helpers import dev  # noqa: E402
-from helpers import rel_l2 as _rel_l2  # noqa: E402
+from helpers import rel_l2_logged as rel_l2  # noqa: E402
 from oracle import ref_cpu as O  # noqa: E402
 import gtav_amd.weights as W  # noqa: E402
 from gtav_amd.lib import GtavError, GtavRangeSwitch  # noqa: E402
@@ -26,12 +24,6 @@ TOL_SMALL = 2e-3       # the fp16 bound of the toy widths (tests/test_gpu_models
 
 SMALL_DIT = dict(input_h=8, input_w=16, patch_size=2, in_channels=16, hidden_size=256, depth=2, num_heads=4, external_cond_dim=25)
 SMALL_VAE = dict(latent_dim=16, input_height=64, input_width=96, patch_size=8, enc_dim=128, enc_depth=2, enc_heads=2, dec_dim=256, dec_depth=2, dec_heads=4)
-
-
-def rel_l2(a, b):
-    v = _rel_l2(a, b)
-    print(f"[rel_l2 {os.environ.get('PYTEST_CURRENT_TEST', '').split('::')[-1].split(' ')[0]}] {v:.3e}")
-    return v
 
 
 def _inputs(cfg, B, T, seed):

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 import torch
 
-import gtav_amd.weights as W
+import train_cases as TC
 from gtav_amd import lib as L
 from gtav_amd import rng as R
 from gtav_amd.model.dit import DiT
@@ -184,31 +184,22 @@ def test_vae_posterior_sample():
 
 
 # ---- 6: the training step -------------------------------------------------------------------------------------------------------------------
-F16, BF16 = torch.float16, torch.bfloat16
-KW = dict(input_h=8, input_w=16, patch_size=2, in_channels=16, hidden_size=256, depth=3, num_heads=4, external_cond_dim=25)   # tests/test_gpu_train_recompute.py
+KW = dict(TC.TOY_KW, depth=3)             # tests/test_gpu_train_recompute.py
 STEP_KW = dict(lr=3e-4, weight_decay=0.01, max_grad_norm=1.0)
 NOISE_STEPS, CTX_MAX = 50, 40
-_SD = {}
 
 
 def _sd():
-    if "sd" not in _SD:
-        _SD["sd"] = W.synth_state_dict(W.dit_param_shapes(**KW), seed=1)
-    return _SD["sd"]
+    return TC.state_dict(KW)
 
 
-def _model(dtype=F16, B=2):
-    m = DiT(**KW, max_batch=B, max_frames=5, init_weights=False, trainable=True, train_dtype=dtype)
-    m.load_state_dict(_sd())
-    return m
+def _model(dtype=TC.F16):
+    return TC.model(KW, 2, 5, dtype)
 
 
-def _clip(F, B=2, seed=5):
-    g = torch.Generator().manual_seed(seed)
-    lat = torch.randn(B, F, 16, 8, 16, generator=g) * 0.5
-    a = torch.zeros(B, F, 25)
-    a[:, :, 3] = 1
-    return lat, a
+def _clip(F):
+    """Latents and actions of TC.clip: the noise and the indices come from the stream under test."""
+    return TC.clip(KW, F=F)[:2]
 
 
 def _masters(m):
@@ -230,7 +221,7 @@ def _materialise(src, B, F, n_prompt, max_frames=5):
     return tgt, ctx, cn, nz
 
 
-@pytest.mark.parametrize("dtype", [F16, BF16], ids=["fp16", "bf16"])
+@TC.DTYPES
 @pytest.mark.parametrize("F,n_prompt", [(5, 4), (6, 3)], ids=["one-target", "three-targets"])
 def test_training_step_with_rng_equals_materialised_draws(F, n_prompt, dtype):
     from gtav_amd.train import training_step

@@ -7,69 +7,40 @@ import math
 import pytest
 import torch
 
-import os
-
+import train_cases as TC
 from helpers import dev
-from helpers import rel_l2 as _rel_l2
-
-
-def rel_l2(a, b):
-    v = _rel_l2(a, b)
-    print(f"[rel_l2 {os.environ.get('PYTEST_CURRENT_TEST', '').split('::')[-1].split(' ')[0]}] {v:.3e}")   # (-s shows the measured margins)
-    return v
+from helpers import rel_l2_logged as rel_l2       # (-s shows the measured margins)
+from train_cases import TOY_KW as KW
 
 pytestmark = pytest.mark.gpu
 
-GRAD_TOL = 4.5e-3   # relative L2 per gradient tensor; measured worst 3.5e-3 (toy model, B = 5) / 3.3e-3 (full size), pytest -s prints every margin
-
-KW = dict(input_h=8, input_w=16, patch_size=2, in_channels=16, hidden_size=256, depth=2, num_heads=4, external_cond_dim=25)
+GRAD_TOL, FWD_TOL = TC.GRAD_TOL[TC.F16], TC.FWD_TOL[TC.F16]
 
 
 def _setup(B=2, T=3, actions=True, seed=0):
-    import gtav_amd.weights as W
-    from gtav_amd.model.dit import DiT
-    from oracle import ref_cpu as O
-    sd = W.synth_state_dict(W.dit_param_shapes(**KW), seed=1)
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(B, T, 16, 8, 16, generator=g)
-    t = torch.randint(0, 1000, (B, T), generator=g)
-    a = None
-    if actions:
-        a = torch.zeros(B, T, 25)
-        a[:, :, 3] = 1
-        a[0, T - 1, 7] = 1
-    vt = torch.randn(B, 1, 16, 8, 16, generator=g)
-    m = DiT(**KW, max_batch=B, max_frames=T, init_weights=False, trainable=True)
-    m.load_state_dict(sd)
-    return m, sd, O.DiTConfig(**KW), x, t, a, vt
+    x, t, a, vt = TC.inputs(KW, B, T, actions, seed)
+    return TC.model(KW, B, T), TC.state_dict(KW), x, t, a, vt
 
 
 @pytest.mark.parametrize("actions", [True, False])
 def test_gradients_match_autograd(actions):
-    from oracle import ref_cpu as O
-    m, sd, cfg, x, t, a, vt = _setup(actions=actions)
-    loss_ref, v_ref, grads = O.dit_loss_and_grads(sd, cfg, x, t, a, vt)
+    _, (x, t, a, vt), _, v_ref, grads = TC.oracle(KW, 2, 3, actions)
+    m = TC.model(KW, 2, 3)
     v = m.forward_train(x, t, a)
-    assert rel_l2(v, v_ref) < 2e-3
+    assert rel_l2(v, v_ref) < FWD_TOL
     # same function as the inference forward; the MLP's GELU is applied to the fp16-rounded pre-activation (kept for gelu') instead
     # of the fp32 accumulator, hence not bit-identical (measured 4.6e-4)
     assert rel_l2(m(x, t, a), v.cpu()) < 1.5e-3
     m.zero_grad()
     m.backward_(v, vt)
     m.check()
-    worst = {}
-    for k, gref in grads.items():
-        g = m.grad(k).cpu()
-        if gref.norm() == 0:
-            assert g.abs().max() == 0, k                 # e.g. external_cond.* without actions: unused, gradient None upstream
-            continue
-        worst[k] = rel_l2(g, gref)
+    worst = TC.grad_errors(m, grads, log=True)
     bad = {k: v_ for k, v_ in worst.items() if v_ > GRAD_TOL}
     assert not bad, f"gradient mismatch: {bad}"
 
 
 def test_backward_accumulates_and_zero_grad_clears():
-    m, sd, cfg, x, t, a, vt = _setup()
+    m, sd, x, t, a, vt = _setup()
     v = m.forward_train(x, t, a)
     m.zero_grad()
     m.backward_(v, vt)
@@ -86,8 +57,8 @@ def test_adamw_step_matches_torch():
     gradients the first Adam step is sign(g) * lr per element, so a single element whose tiny gradient differs in sign dominates any
     norm: that comparison says nothing about the optimizer.)"""
     from oracle import ref_cpu as O
-    m, sd, cfg, x, t, a, vt = _setup()
-    _, _, grads = O.dit_loss_and_grads(sd, cfg, x, t, a, vt)
+    sd, (x, t, a, vt), _, _, grads = TC.oracle(KW, 2, 3, True)
+    m = TC.model(KW, 2, 3)
     params = {k: v for k, v in sd.items() if not k.endswith("freqs")}
     steps = 3
     ref, norm_ref = O.adamw_reference(params, grads, lr=1e-3, weight_decay=0.01, max_grad_norm=1.0, steps=steps)
@@ -108,9 +79,9 @@ def test_adamw_step_matches_torch():
     # the refreshed fp16 operands (W and W^T) are what the next forward / backward use: both must match the oracle at the UPDATED weights
     sd2 = dict(sd)
     sd2.update(ref)
-    _, v2_ref, grads2 = O.dit_loss_and_grads(sd2, cfg, x, t, a, vt)
+    _, v2_ref, grads2 = O.dit_loss_and_grads(sd2, O.DiTConfig(**KW), x, t, a, vt)
     v2 = m.forward_train(x, t, a)
-    assert rel_l2(v2, v2_ref) < 2e-3
+    assert rel_l2(v2, v2_ref) < FWD_TOL
     m.zero_grad()
     m.backward_(v2, vt)
     for k in ("blocks.1.t_mlp.fc1.weight", "blocks.0.s_attn.to_qkv.weight", "t_embedder.mlp.0.weight", "x_embedder.proj.weight"):
@@ -118,7 +89,7 @@ def test_adamw_step_matches_torch():
 
 
 def test_overflow_skips_the_step():
-    m, sd, cfg, x, t, a, vt = _setup()
+    m, sd, x, t, a, vt = _setup()
     v = m.forward_train(x, t, a)
     m.zero_grad()
     m.backward_(v, vt)
@@ -133,13 +104,8 @@ def test_overflow_skips_the_step():
 
 def test_training_step_reduces_the_loss():
     from gtav_amd.train import training_step
-    m, sd, cfg, x, t, a, vt = _setup(B=2, T=5)
-    g = torch.Generator().manual_seed(5)
-    lat = torch.randn(2, 5, 16, 8, 16, generator=g) * 0.5
-    tgt = torch.tensor([30, 10])
-    ctx = torch.tensor([5, 20])
-    cn = torch.randn(2, 4, 16, 8, 16, generator=g)
-    nz = torch.randn(2, 1, 16, 8, 16, generator=g)
+    m = TC.model(KW, 2, 5)
+    lat, a, tgt, ctx, cn, nz = TC.clip(KW)
     losses = [float(training_step(m, lat, a.new_zeros(2, 5, 25), tgt, ctx, cn, nz, lr=2e-4, weight_decay=0.0, max_grad_norm=1.0)) for _ in range(8)]
     assert all(math.isfinite(l) for l in losses)
     assert losses[-1] < losses[0] * 0.9, losses
@@ -262,15 +228,11 @@ def test_plain_forward_of_a_trainable_handle_at_large_m_equals_the_inference_han
 def test_gradients_other_windows(B, T):
     """Windows of 1, 2 and 5 frames (the temporal attention backward is specialised per window length; T = 1 has one key per query);
     B = 5, T = 5 gives 25 conditioning rows: two ragged 16-row tiles in the fp32-MFMA adaLN backward kernels."""
-    from oracle import ref_cpu as O
-    m, sd, cfg, x, t, a, vt = _setup(B=B, T=T)
-    _, v_ref, grads = O.dit_loss_and_grads(sd, cfg, x, t, a, vt)
-    v = m.forward_train(x, t, a)
-    assert rel_l2(v, v_ref) < 2e-3
-    m.zero_grad()
-    m.backward_(v, vt)
-    m.check()
-    worst = {k: rel_l2(m.grad(k), g) for k, g in grads.items() if g.norm() > 0}
+    _, inp, _, v_ref, grads = TC.oracle(KW, B, T, True)
+    m = TC.model(KW, B, T)
+    v = TC.forward_backward(m, inp)
+    assert rel_l2(v, v_ref) < FWD_TOL
+    worst = TC.grad_errors(m, grads, log=True)
     assert max(worst.values()) < GRAD_TOL, {k: v_ for k, v_ in worst.items() if v_ > GRAD_TOL}
 
 
@@ -278,7 +240,7 @@ def test_loss_scale_is_transparent_and_micro_batches_accumulate():
     """(1) The unscaled gradients do not depend on the loss scale (256 vs 65536) beyond fp16 rounding.  (2) Two micro-batches with
     per-micro-batch mean losses accumulate to twice the gradient of... each its own loss: g(b0) + g(b1) equals the sum of separate runs
     (what gradient_accumulation_steps relies on, train_dit.py:676-680)."""
-    m, sd, cfg, x, t, a, vt = _setup(B=2, T=3)
+    m, sd, x, t, a, vt = _setup(B=2, T=3)
     key = "blocks.1.s_mlp.fc1.weight"
     v = m.forward_train(x, t, a)
     m.zero_grad()
@@ -312,14 +274,11 @@ def test_gradients_match_reference_fixture_g8():
     gradient within 1e-2 relative L2, the global (clipping) norm within 0.5 %."""
     import os
     from safetensors.torch import load_file
-    import gtav_amd.weights as W
-    from gtav_amd.model.dit import DiT
     g = load_file(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g8_training.safetensors"))
-    sd = W.synth_state_dict(W.dit_param_shapes(**KW), seed=3)
-    m = DiT(**KW, max_batch=2, max_frames=3, init_weights=False, trainable=True)
-    m.load_state_dict(sd)
+    sd = TC.state_dict(KW, 3)
+    m = TC.model(KW, 2, 3, sd=sd)
     v = m.forward_train(g["x"], g["t"], g["actions"])
-    assert rel_l2(v, g["v_pred"]) < 2e-3
+    assert rel_l2(v, g["v_pred"]) < FWD_TOL
     m.zero_grad()
     m.backward_(v, g["v_target"])
     m.check()
@@ -340,12 +299,8 @@ def test_per_block_residual_taps_match_reference_fixture_g2():
     tests/golden/g2_small_dit.safetensors): per-block parity, not only end-to-end."""
     import os
     from safetensors.torch import load_file
-    import gtav_amd.weights as W
-    from gtav_amd.model.dit import DiT
     g = load_file(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g2_small_dit.safetensors"))
-    sd = W.synth_state_dict(W.dit_param_shapes(**KW), seed=3)
-    m = DiT(**KW, max_batch=2, max_frames=3, init_weights=False, trainable=True)
-    m.load_state_dict(sd)
+    m = TC.model(KW, 2, 3, sd=TC.state_dict(KW, 3))
     v = m.forward_train(g["x"], g["t"], g["actions"])
     assert rel_l2(v, g["out_actions"]) < 1e-3
     for i in range(2):
@@ -358,7 +313,7 @@ def test_phased_backward_equals_monolithic_and_buckets_cover_the_arena():
     (final layer, one per block in reverse, embedders) are disjoint, contiguous and cover the arena; each bucket's gradients are final
     after the phase it is attached to (later phases do not touch them)."""
     from gtav_amd.train import gradient_buckets
-    m, sd, cfg, x, t, a, vt = _setup()
+    m, sd, x, t, a, vt = _setup()
     v = m.forward_train(x, t, a)
     m.zero_grad()
     m.backward_(v, vt)
@@ -383,7 +338,7 @@ def test_overlapped_all_reduce_path_single_rank_process_group():
     import os
     import torch.distributed as dist
     from gtav_amd.train import backward_overlapped
-    m, sd, cfg, x, t, a, vt = _setup()
+    m, sd, x, t, a, vt = _setup()
     v = m.forward_train(x, t, a)
     m.zero_grad()
     m.backward_(v, vt)
@@ -411,38 +366,20 @@ def test_overlapped_all_reduce_path_single_rank_process_group():
 # ------------------------------------------------------------------------------------------------------------------------
 # round 3: checkpoint / resume (train_dit.py:765-849), overflow by fp16 saturation, the general frame loop
 # ------------------------------------------------------------------------------------------------------------------------
-def _step_inputs(B=2, seed=5):
-    g = torch.Generator().manual_seed(seed)
-    lat = torch.randn(B, 5, 16, 8, 16, generator=g) * 0.5
-    a = torch.zeros(B, 5, 25)
-    a[:, :, 3] = 1
-    tgt, ctx = torch.tensor([30, 10][:B]), torch.tensor([5, 20][:B])
-    cn = torch.randn(B, 4, 16, 8, 16, generator=g)
-    nz = torch.randn(B, 1, 16, 8, 16, generator=g)
-    return lat, a, tgt, ctx, cn, nz
-
-
 def test_save_state_load_state_resumes_bit_exactly(tmp_path):
     """accelerator.save_state / load_state (train_dit.py:765-849): three optimisation steps straight == two steps, save_state, a FRESH
     model (new handle: masters, AdamW moments, step counters, loss scale restored through the C-ABI), load_state, one more step — the
     weights must be EQUAL bit for bit, and step.json carries step / epoch / skip_iter like the reference's load_checkpoint."""
-    import gtav_amd.weights as W
     from gtav_amd.model.dit import DiT
     from gtav_amd.train import load_state, save_state, training_step
-    lat, a, tgt, ctx, cn, nz = _step_inputs()
+    lat, a, tgt, ctx, cn, nz = TC.clip(KW)
     kw = dict(lr=3e-4, weight_decay=0.01, max_grad_norm=1.0)
-    sd = W.synth_state_dict(W.dit_param_shapes(**KW), seed=1)
-
-    def fresh():
-        m = DiT(**KW, max_batch=2, max_frames=5, init_weights=False, trainable=True)
-        m.load_state_dict(sd)
-        return m
-    m1 = fresh()
+    m1 = TC.model(KW, 2, 5)
     for _ in range(3):
         training_step(m1, lat, a, tgt, ctx, cn, nz, **kw)
     m1.pull_weights()
     straight = {k: v.clone() for k, v in m1._sd.items()}
-    m2 = fresh()
+    m2 = TC.model(KW, 2, 5)
     for _ in range(2):
         training_step(m2, lat, a, tgt, ctx, cn, nz, **kw)
     ck = str(tmp_path / "train_checkpoints" / "dit_last")
@@ -467,8 +404,8 @@ def test_fp16_saturation_skips_the_step_and_loss_scaler_backs_off():
     gradients: the step is skipped on the device (weights, moments, Adam step count untouched), the bit is consumed (check() is clean),
     and LossScaler halves the scale until steps apply again."""
     from gtav_amd.train import LossScaler, training_step
-    m, sd, cfg, x, t, a, vt = _setup(B=2, T=5)
-    lat, a5, tgt, ctx, cn, nz = _step_inputs()
+    m, sd, x, t, a, vt = _setup(B=2, T=5)
+    lat, a5, tgt, ctx, cn, nz = TC.clip(KW)
     m.loss_scale = 2.0 ** 40
     training_step(m, lat, a5, tgt, ctx, cn, nz, lr=1e-3)
     applied, skipped, gnorm = m.train_stats()
@@ -494,16 +431,9 @@ def test_overflow_on_one_rank_skips_the_step_on_every_rank():
     identical weights, the all-reduce SUM done by hand on the two gradient arenas): only replica A's inputs saturate its fp16 gradient stores.
     Its backward pass publishes the overflow as +inf in its arena, so after the "all-reduce" BOTH replicas see a non-finite norm and skip: weights
     bit-equal afterwards, Adam step counts equal, both skip counters 1.  (Round 3 tested the saturation bit per rank: A skipped, B stepped.)"""
-    import gtav_amd.weights as W
-    from gtav_amd.model.dit import DiT
     from gtav_amd.train import forward_loss
-    lat, a5, tgt, ctx, cn, nz = _step_inputs()
-    sd = W.synth_state_dict(W.dit_param_shapes(**KW), seed=1)
-    reps = []
-    for _ in range(2):
-        m = DiT(**KW, max_batch=2, max_frames=5, init_weights=False, trainable=True)
-        m.load_state_dict(sd)
-        reps.append(m)
+    lat, a5, tgt, ctx, cn, nz = TC.clip(KW)
+    reps = [TC.model(KW, 2, 5) for _ in range(2)]
     lats = [lat * 3e4, lat]            # replica A: latents far outside the fp16 range of the activation gradients at the default loss scale
     for m, l in zip(reps, lats):
         m.zero_grad()
@@ -541,13 +471,9 @@ def test_frame_loop_three_target_frames_vs_reference_fixture_g10():
     the returned mean loss; and training_step differentiates every frame's loss (gradients add up over the frame loop)."""
     import os
     from safetensors.torch import load_file
-    import gtav_amd.weights as W
-    from gtav_amd.model.dit import DiT
     from gtav_amd.train import forward_loss, training_step
     g = load_file(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g10_frame_loop.safetensors"))
-    sd = W.synth_state_dict(W.dit_param_shapes(**KW), seed=17)
-    m = DiT(**KW, max_batch=2, max_frames=5, init_weights=False, trainable=True)
-    m.load_state_dict(sd)
+    m = TC.model(KW, 2, 5, sd=TC.state_dict(KW, 17))
     seen = {}
 
     def on_frame(k, v_pred, v_target):
@@ -557,7 +483,7 @@ def test_frame_loop_three_target_frames_vs_reference_fixture_g10():
     assert sorted(seen) == [0, 1, 2]
     for k in range(3):
         assert rel_l2(seen[k][1], g[f"v_target{k}"]) < 1e-6
-        assert rel_l2(seen[k][0], g[f"v_pred{k}"]) < 2e-3
+        assert rel_l2(seen[k][0], g[f"v_pred{k}"]) < FWD_TOL
     assert abs(float(loss) - float(g["mean_loss"])) / float(g["mean_loss"]) < 2e-3
     # gradients of the three frames add up: one training_step == three backward passes accumulated
     m.zero_grad()
@@ -574,8 +500,8 @@ def test_trainable_model_refuses_to_grow_before_destroying_its_state():
     """a trainable DiT that would have to grow its workspace (predict on the training model with more conditioning rows than
     reserved) must raise BEFORE the handle — the only home of the fp32 masters and the AdamW state — is destroyed, and stay usable."""
     from gtav_amd.train import training_step
-    m, sd, cfg, x, t, a, vt = _setup(B=2, T=5)
-    lat, a5, tgt, ctx, cn, nz = _step_inputs()
+    m, sd, x, t, a, vt = _setup(B=2, T=5)
+    lat, a5, tgt, ctx, cn, nz = TC.clip(KW)
     training_step(m, lat, a5, tgt, ctx, cn, nz, lr=1e-4)
     with pytest.raises(RuntimeError, match="cannot grow"):
         m.reserve(4, 5, noise_steps=50)
@@ -591,7 +517,7 @@ def test_comm_from_torch_distributed_and_bucket_order_single_rank():
     on a one-rank RCCL communicator; the arena afterwards equals the plain backward's."""
     from gtav_amd.comm import Comm
     from gtav_amd.train import backward_overlapped, gradient_buckets
-    m, sd, cfg, x, t, a, vt = _setup()
+    m, sd, x, t, a, vt = _setup()
     v = m.forward_train(x, t, a)
     m.zero_grad()
     m.backward_(v, vt)

@@ -2,7 +2,7 @@
 own `--mixed_precision bf16` (train_dit.py:190-198).  Forward, backward and the optimizer's operand rewrite run on the bf16 twins of the training kernels.
 
 Tolerances: bf16 keeps 3 fewer mantissa bits than fp16, and all-bf16 forwards measure 5-7e-3 against the fp32 oracle where fp16 gives <= 1e-3
-(tests/test_gpu_range.py).  The forward bound is that file's TOL_BF16 (1.5e-2); gradients are held to 8 x the fp16 GRAD_TOL of tests/test_gpu_train.py,
+(tests/test_gpu_range.py).  The forward bound is that file's TOL_BF16 (1.5e-2); gradients are held to 8 x the fp16 GRAD_TOL (tests/train_cases.py),
 3.6e-2 relative L2 per tensor.  `pytest -s` prints every measured margin."""
 import json
 import math
@@ -11,91 +11,44 @@ import os
 import pytest
 import torch
 
+import train_cases as TC
 from helpers import rel_l2 as _rel_l2
+from helpers import rel_l2_logged as rel_l2       # (-s shows the measured margins)
+from train_cases import BF16, F16
+from train_cases import TOY_KW as KW
 
 pytestmark = pytest.mark.gpu
 
-TOL_FWD_BF16 = 1.5e-2
-GRAD_TOL_F16 = 4.5e-3
-GRAD_TOL_BF16 = 8 * GRAD_TOL_F16      # 3.6e-2
-
-KW = dict(input_h=8, input_w=16, patch_size=2, in_channels=16, hidden_size=256, depth=2, num_heads=4, external_cond_dim=25)
-BF16 = torch.bfloat16
-
-
-def rel_l2(a, b):
-    v = _rel_l2(a, b)
-    print(f"[rel_l2 {os.environ.get('PYTEST_CURRENT_TEST', '').split('::')[-1].split(' ')[0]}] {v:.3e}")   # (-s shows the measured margins)
-    return v
+TOL_FWD_BF16, GRAD_TOL_BF16 = TC.FWD_TOL[BF16], TC.GRAD_TOL[BF16]
 
 
 def _model(sd, B, T, dtype=BF16, **kw):
-    from gtav_amd.model.dit import DiT
-    m = DiT(**KW, max_batch=B, max_frames=T, init_weights=False, trainable=True, train_dtype=dtype, **kw)
-    m.load_state_dict(sd)
-    return m
+    return TC.model(KW, B, T, dtype, sd, **kw)
 
 
 def _inputs(B=2, T=3, actions=True, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(B, T, 16, 8, 16, generator=g)
-    t = torch.randint(0, 1000, (B, T), generator=g)
-    a = None
-    if actions:
-        a = torch.zeros(B, T, 25)
-        a[:, :, 3] = 1
-        a[0, T - 1, 7] = 1
-    vt = torch.randn(B, 1, 16, 8, 16, generator=g)
-    return x, t, a, vt
-
-
-def _step_inputs(B=2, seed=5):
-    g = torch.Generator().manual_seed(seed)
-    lat = torch.randn(B, 5, 16, 8, 16, generator=g) * 0.5
-    a = torch.zeros(B, 5, 25)
-    a[:, :, 3] = 1
-    tgt, ctx = torch.tensor([30, 10][:B]), torch.tensor([5, 20][:B])
-    cn = torch.randn(B, 4, 16, 8, 16, generator=g)
-    nz = torch.randn(B, 1, 16, 8, 16, generator=g)
-    return lat, a, tgt, ctx, cn, nz
+    return TC.inputs(KW, B, T, actions, seed)
 
 
 def _grad_errors(m, grads, keys=None):
-    worst = {}
-    for k in (keys or grads):
-        gref = grads[k]
-        g = m.grad(k).cpu()
-        assert torch.isfinite(g).all(), k
-        if gref.norm() == 0:
-            assert g.abs().max() == 0, k              # unused upstream (external_cond.* without actions)
-            continue
-        worst[k] = rel_l2(g, gref)
-    return worst
+    return TC.grad_errors(m, grads, keys, log=True)
 
 
 # ---- 1. toy DiT against the fp32 oracle -------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("actions", [True, False])
 def test_bf16_gradients_match_autograd(actions):
-    import gtav_amd.weights as W
-    from oracle import ref_cpu as O
-    sd = W.synth_state_dict(W.dit_param_shapes(**KW), seed=1)
-    x, t, a, vt = _inputs(actions=actions)
-    _, v_ref, grads = O.dit_loss_and_grads(sd, O.DiTConfig(**KW), x, t, a, vt)
+    sd, inp, _, v_ref, grads = TC.oracle(KW, 2, 3, actions)
     worst = {}
-    for dtype in (torch.float16, BF16):
+    for dtype in (F16, BF16):
         m = _model(sd, 2, 3, dtype)
         assert m.train_dtype == dtype
-        v = m.forward_train(x, t, a)
-        e_fwd = rel_l2(v, v_ref)
-        assert e_fwd < (2e-3 if dtype == torch.float16 else TOL_FWD_BF16)
-        m.zero_grad()
-        m.backward_(v, vt)
-        m.check()
+        v = TC.forward_backward(m, inp)
+        assert rel_l2(v, v_ref) < TC.FWD_TOL[dtype]
         worst[dtype] = _grad_errors(m, grads)
         del m
     bad = {k: e for k, e in worst[BF16].items() if e > GRAD_TOL_BF16}
     assert not bad, f"bf16 gradient mismatch: {bad}"
-    w16, wbf = max(worst[torch.float16].values()), max(worst[BF16].values())
+    w16, wbf = max(worst[F16].values()), max(worst[BF16].values())
     print(f"worst gradient error: fp16 {w16:.3e}, bf16 {wbf:.3e} (bound {GRAD_TOL_BF16:.1e})")
     assert wbf > w16                                   # the bf16 mode really ran
 
@@ -146,9 +99,8 @@ def test_bf16_full_size_gradients(B, T):
 # ---- 3. fixture G8: autograd through the reference's own module -------------------------------------------------------------------------
 def test_bf16_gradients_match_reference_fixture_g8():
     from safetensors.torch import load_file
-    import gtav_amd.weights as W
     g = load_file(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g8_training.safetensors"))
-    sd = W.synth_state_dict(W.dit_param_shapes(**KW), seed=3)
+    sd = TC.state_dict(KW, 3)
     m = _model(sd, 2, 3)
     v = m.forward_train(g["x"], g["t"], g["actions"])
     assert rel_l2(v, g["v_pred"]) < TOL_FWD_BF16
@@ -172,8 +124,7 @@ def test_bf16_gradients_match_reference_fixture_g8():
 
 # ---- 4. the outlier checkpoint: fp16 cannot train it, bf16 can --------------------------------------------------------------------------
 def _outlier_sd():
-    import gtav_amd.weights as W
-    sd = W.synth_state_dict(W.dit_param_shapes(**KW), seed=3)
+    sd = TC.state_dict(KW, 3)
     big = dict(sd)
     big["blocks.0.s_mlp.fc1.weight"] = sd["blocks.0.s_mlp.fc1.weight"] * 3e5     # the x3e5 outlier of tests/test_gpu_range.py
     return big
@@ -182,9 +133,9 @@ def _outlier_sd():
 def test_outlier_checkpoint_fp16_training_step_is_skipped():
     """The gap this mode closes: every saturating fp16 activation store raises the saturation bit, and the optimizer skips the step at any loss scale."""
     from gtav_amd.train import training_step
-    m = _model(_outlier_sd(), 2, 5, torch.float16)
+    m = _model(_outlier_sd(), 2, 5, F16)
     m.loss_scale = 1.0
-    lat, a, tgt, ctx, cn, nz = _step_inputs()
+    lat, a, tgt, ctx, cn, nz = TC.clip(KW)
     training_step(m, lat, a, tgt, ctx, cn, nz, lr=1e-4)
     applied, skipped, _ = m.train_stats()
     assert not applied and skipped == 1
@@ -221,7 +172,7 @@ def test_outlier_checkpoint_trains_on_bf16_operands():
         print(f"{k}: bf16 training {e:.3e}, fp32 oracle on bf16-rounded weights {sens:.3e}")
         assert e < 1.5 * sens, (k, e, sens)
     # eight optimisation steps through the training loop: every one applies (the Adam step count reaches 8), the loss stays finite
-    lat, a5, tgt, ctx, cn, nz = _step_inputs()
+    lat, a5, tgt, ctx, cn, nz = TC.clip(KW)
     losses = []
     for _ in range(8):
         losses.append(float(training_step(m, lat, a5, tgt, ctx, cn, nz, lr=1e-4)))
@@ -234,10 +185,9 @@ def test_outlier_checkpoint_trains_on_bf16_operands():
 
 
 def test_bf16_training_step_reduces_the_loss():
-    import gtav_amd.weights as W
     from gtav_amd.train import training_step
-    m = _model(W.synth_state_dict(W.dit_param_shapes(**KW), seed=1), 2, 5)
-    lat, a, tgt, ctx, cn, nz = _step_inputs()
+    m = _model(TC.state_dict(KW, 1), 2, 5)
+    lat, a, tgt, ctx, cn, nz = TC.clip(KW)
     losses = [float(training_step(m, lat, a.new_zeros(2, 5, 25), tgt, ctx, cn, nz, lr=2e-4, weight_decay=0.0, max_grad_norm=1.0)) for _ in range(8)]
     print("losses:", losses)
     assert all(math.isfinite(l) for l in losses)
@@ -249,11 +199,10 @@ def test_bf16_training_step_reduces_the_loss():
 def test_bf16_adamw_rewrites_the_operands_like_a_fresh_inference_handle():
     """After two steps the W / W^T images the optimizer wrote from the updated masters are the bf16 conversion of those masters: a fresh bf16 INFERENCE handle
     loaded with the pulled weights returns the trained handle's plain forward bit for bit."""
-    import gtav_amd.weights as W
     from gtav_amd.model.dit import DiT
     from gtav_amd.train import training_step
-    m = _model(W.synth_state_dict(W.dit_param_shapes(**KW), seed=1), 2, 5)
-    lat, a, tgt, ctx, cn, nz = _step_inputs()
+    m = _model(TC.state_dict(KW, 1), 2, 5)
+    lat, a, tgt, ctx, cn, nz = TC.clip(KW)
     for _ in range(2):
         training_step(m, lat, a, tgt, ctx, cn, nz, lr=1e-3, weight_decay=0.01)
     assert int(m.opt_state_dict()["step"][0]) == 2
@@ -271,8 +220,7 @@ def test_bf16_adamw_rewrites_the_operands_like_a_fresh_inference_handle():
 
 # ---- 6. phases, overflow ------------------------------------------------------------------------------------------------------------------
 def test_bf16_phased_backward_equals_monolithic():
-    import gtav_amd.weights as W
-    m = _model(W.synth_state_dict(W.dit_param_shapes(**KW), seed=1), 2, 3)
+    m = _model(TC.state_dict(KW, 1), 2, 3)
     x, t, a, vt = _inputs()
     v = m.forward_train(x, t, a)
     m.zero_grad()
@@ -285,8 +233,7 @@ def test_bf16_phased_backward_equals_monolithic():
 
 
 def test_bf16_overflow_skips_the_step():
-    import gtav_amd.weights as W
-    sd = W.synth_state_dict(W.dit_param_shapes(**KW), seed=1)
+    sd = TC.state_dict(KW, 1)
     m = _model(sd, 2, 3)
     x, t, a, vt = _inputs()
     v = m.forward_train(x, t, a)
@@ -303,11 +250,10 @@ def test_bf16_overflow_skips_the_step():
 
 # ---- 7. checkpoint / resume -----------------------------------------------------------------------------------------------------------------
 def test_bf16_save_state_load_state_resumes_bit_exactly(tmp_path):
-    import gtav_amd.weights as W
     from gtav_amd.train import load_state, save_state, training_step
-    lat, a, tgt, ctx, cn, nz = _step_inputs()
+    lat, a, tgt, ctx, cn, nz = TC.clip(KW)
     kw = dict(lr=3e-4, weight_decay=0.01, max_grad_norm=1.0)
-    sd = W.synth_state_dict(W.dit_param_shapes(**KW), seed=1)
+    sd = TC.state_dict(KW, 1)
     m1 = _model(sd, 2, 5)
     for _ in range(3):
         training_step(m1, lat, a, tgt, ctx, cn, nz, **kw)
@@ -341,19 +287,18 @@ def test_bf16_save_state_load_state_resumes_bit_exactly(tmp_path):
 
 # ---- 8. interface -------------------------------------------------------------------------------------------------------------------------
 def test_bf16_trainable_model_operand_dtype_interface():
-    import gtav_amd.weights as W
     from gtav_amd.lib import GtavError
     from gtav_amd.model.dit import DiT, DiT_models
-    m = _model(W.synth_state_dict(W.dit_param_shapes(**KW), seed=1), 1, 2)
+    m = _model(TC.state_dict(KW, 1), 1, 2)
     assert m.loss_scale == 1.0 and all(d == BF16 for d in m.operand_dtypes())
     m.set_operand_dtype(BF16)                            # no-op
     with pytest.raises(GtavError, match="bf16 operands"):
-        m.set_operand_dtype(torch.float16)
+        m.set_operand_dtype(F16)
     x, t, a, vt = _inputs(B=1, T=2)
     m.forward_train(x, t, a)                             # builds the handle
     m.set_operand_dtype(BF16)
     with pytest.raises(GtavError, match="bf16 operands"):
-        m.set_operand_dtype(torch.float16)
+        m.set_operand_dtype(F16)
     assert all(d == BF16 for d in m.operand_dtypes())
     m2 = DiT_models["DiT-S/2"](init_weights=False, trainable=True, train_dtype=BF16)
     assert m2.train_dtype == BF16 and m2.loss_scale == 1.0

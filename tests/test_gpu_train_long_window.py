@@ -3,76 +3,33 @@ streaming temporal attention backward (csrc/train.hip attn_temporal_bwd_stream_k
 frame loop of train.py — against torch autograd on the CPU oracle, and the properties the 5-frame step is held to (tests/test_gpu_train.py,
 test_gpu_train_bf16.py): phases, resume, loss going down, limits.
 
-Bounds are the project's own for the same comparisons: forward 2e-3 (bf16 1.5e-2), every gradient tensor within GRAD_TOL = 4.5e-3 relative L2 (bf16 8 x),
+Bounds are the project's own for the same comparisons (tests/train_cases.py): forward within FWD_TOL, every gradient tensor within GRAD_TOL relative L2,
 a trainable-vs-inference forward 1.5e-3.  Where a gradient tensor of a long window exceeds GRAD_TOL it is held to 1.5 x the worst tensor of the T = 8 step of the
 same batch, measured in the same run (_gradient_case).  `pytest -s` prints every measured margin."""
 import ctypes as C
 import math
-import os
 
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
-from helpers import rel_l2 as _rel_l2  # noqa: E402
-from oracle import ref_cpu as O  # noqa: E402
-import gtav_amd.weights as W  # noqa: E402
+import train_cases as TC  # noqa: E402
+from helpers import rel_l2_logged as rel_l2  # noqa: E402
 from gtav_amd import lib as L  # noqa: E402
 from gtav_amd.model.dit import DiT  # noqa: E402
+from train_cases import DTYPES, F16, FWD_TOL, GRAD_TOL  # noqa: E402
+from train_cases import TOY_KW as KW  # noqa: E402
 
-F16, BF16 = torch.float16, torch.bfloat16
-GRAD_TOL = {F16: 4.5e-3, BF16: 8 * 4.5e-3}     # tests/test_gpu_train.py GRAD_TOL, tests/test_gpu_train_bf16.py GRAD_TOL_BF16
-FWD_TOL = {F16: 2e-3, BF16: 1.5e-2}            # tests/test_gpu_train.py, tests/test_gpu_train_bf16.py TOL_FWD_BF16
-DTYPES = pytest.mark.parametrize("dtype", [F16, BF16], ids=["fp16", "bf16"])
-
-KW = dict(input_h=8, input_w=16, patch_size=2, in_channels=16, hidden_size=256, depth=2, num_heads=4, external_cond_dim=25)
 KW_WIDE = dict(KW, hidden_size=1024, num_heads=16, depth=1)
 
 
-def rel_l2(a, b):
-    v = _rel_l2(a, b)
-    print(f"[rel_l2 {os.environ.get('PYTEST_CURRENT_TEST', '').split('::')[-1].split(' ')[0]}] {v:.3e}")
-    return v
+def _inputs(B, T, actions=True):
+    return TC.inputs(KW, B, T, actions)
 
 
-_SD, _REF = {}, {}
-
-
-def _sd(kw=KW, seed=1):
-    key = (tuple(sorted(kw.items())), seed)
-    if key not in _SD:
-        _SD[key] = W.synth_state_dict(W.dit_param_shapes(**kw), seed=seed)
-    return _SD[key]
-
-
-def _inputs(B, T, actions=True, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(B, T, 16, 8, 16, generator=g)
-    t = torch.randint(0, 1000, (B, T), generator=g)
-    a = None
-    if actions:
-        a = torch.zeros(B, T, 25)
-        a[:, :, 3] = 1
-        a[0, T - 1, 7] = 1
-    vt = torch.randn(B, 1, 16, 8, 16, generator=g)
-    return x, t, a, vt
-
-
-def _reference(B, T, actions, kw=KW):
-    """(v_pred, gradients) of torch autograd on the CPU oracle: computed once per case, shared by the operand types, never modified."""
-    key = (B, T, actions, tuple(sorted(kw.items())))
-    if key not in _REF:
-        x, t, a, vt = _inputs(B, T, actions)
-        _, v_ref, grads = O.dit_loss_and_grads(_sd(kw), O.DiTConfig(**kw), x, t, a, vt)
-        _REF[key] = (v_ref, grads)
-    return _REF[key]
-
-
-def _model(B, T, dtype=F16, kw=KW, window=None, sd=None, **extra):
-    m = DiT(**kw, max_batch=B, max_frames=T, init_weights=False, trainable=True, train_dtype=dtype, train_max_frames=window or max(T, 8), **extra)
-    m.load_state_dict(sd or _sd(kw))
-    return m
+def _model(B, T, dtype=F16, kw=KW):
+    return TC.model(kw, B, T, dtype, train_max_frames=max(T, 8))
 
 
 def _all_grads(m):
@@ -81,22 +38,10 @@ def _all_grads(m):
 
 def _grad_errors(B, T, actions, dtype, kw=KW):
     """Forward error and the relative L2 error of every gradient tensor of one (B, T) step against torch autograd; tensors that are zero upstream must be zero."""
-    v_ref, grads = _reference(B, T, actions, kw)
-    x, t, a, vt = _inputs(B, T, actions)
+    _, inp, _, v_ref, grads = TC.oracle(kw, B, T, actions)
     m = _model(B, T, dtype, kw)
-    v = m.forward_train(x, t, a)
-    fwd = rel_l2(v, v_ref)
-    m.zero_grad()
-    m.backward_(v, vt)
-    m.check()
-    errs = {}
-    for k, gref in grads.items():
-        g = m.grad(k).cpu()
-        if gref.norm() == 0:
-            assert g.abs().max() == 0, k          # unused upstream (external_cond.* without actions): exactly zero
-            continue
-        errs[k] = _rel_l2(g, gref)
-    return fwd, errs
+    v = TC.forward_backward(m, inp)
+    return rel_l2(v, v_ref), TC.grad_errors(m, grads)
 
 
 _T8 = {}
@@ -153,13 +98,8 @@ def test_short_windows_keep_their_bits_on_an_opted_in_handle():
     """A (2, 5) step on DiT(max_frames=16, train_max_frames=16) runs the kernels of the default DiT(max_frames=5): every gradient is equal bit for bit."""
     x, t, a, vt = _inputs(2, 5)
     got = []
-    for m in (DiT(**KW, max_batch=2, max_frames=16, train_max_frames=16, init_weights=False, trainable=True),
-              DiT(**KW, max_batch=2, max_frames=5, init_weights=False, trainable=True)):
-        m.load_state_dict(_sd())
-        v = m.forward_train(x, t, a)
-        m.zero_grad()
-        m.backward_(v, vt)
-        m.check()
+    for m in (TC.model(KW, 2, 16, train_max_frames=16), TC.model(KW, 2, 5)):
+        v = TC.forward_backward(m, (x, t, a, vt))
         got.append((v.clone(), _all_grads(m)))
     assert torch.equal(got[0][0], got[1][0])
     for k in got[0][1]:
@@ -169,8 +109,8 @@ def test_short_windows_keep_their_bits_on_an_opted_in_handle():
 # ------------------------------------------------------------------------------------------------------------------------
 # training behaviour at a 12-frame window (the 5-frame tests of tests/test_gpu_train.py / test_gpu_train_bf16.py)
 # ------------------------------------------------------------------------------------------------------------------------
-def _step_inputs(B=2, F=12, n_target=1, seed=5):
-    """A clip of F + n_target - 1 latent frames whose every target frame sees a window of F frames."""
+def _multi_target_clip(n_target, B=2, F=12, seed=5):
+    """A clip of F + n_target - 1 latent frames whose every target frame sees a window of F frames (one target frame: TC.clip(KW, B, F))."""
     g = torch.Generator().manual_seed(seed)
     total = F + n_target - 1
     lat = torch.randn(B, total, 16, 8, 16, generator=g) * 0.5
@@ -180,8 +120,6 @@ def _step_inputs(B=2, F=12, n_target=1, seed=5):
     ctx = torch.tensor([[5, 20], [7, 2], [9, 30]][:n_target])[:, :B]
     cn = [torch.randn(B, F - 1, 16, 8, 16, generator=g) for _ in range(n_target)]
     nz = [torch.randn(B, 1, 16, 8, 16, generator=g) for _ in range(n_target)]
-    if n_target == 1:
-        return lat, a, tgt[0], ctx[0], cn[0], nz[0]
     return lat, a, tgt, ctx, cn, nz
 
 
@@ -189,7 +127,7 @@ def _step_inputs(B=2, F=12, n_target=1, seed=5):
 def test_training_steps_reduce_the_loss_at_12_frames(dtype):
     from gtav_amd.train import training_step
     m = _model(2, 12, dtype)
-    lat, a, tgt, ctx, cn, nz = _step_inputs()
+    lat, a, tgt, ctx, cn, nz = TC.clip(KW, F=12)
     losses = [float(training_step(m, lat, a, tgt, ctx, cn, nz, lr=2e-4, weight_decay=0.0, max_grad_norm=1.0, n_prompt_frames=11)) for _ in range(8)]
     print("losses:", " ".join(f"{l:.4f}" for l in losses))
     assert all(math.isfinite(l) for l in losses)
@@ -217,7 +155,7 @@ def test_phased_backward_equals_monolithic_at_12_frames(dtype):
 def test_save_state_load_state_resumes_bit_exactly_at_12_frames(dtype, tmp_path):
     """Three steps straight == two steps, save_state, a fresh model, load_state, one more step: equal weights bit for bit (no atomics anywhere in the step)."""
     from gtav_amd.train import load_state, save_state, training_step
-    lat, a, tgt, ctx, cn, nz = _step_inputs()
+    lat, a, tgt, ctx, cn, nz = TC.clip(KW, F=12)
     kw = dict(lr=3e-4, weight_decay=0.01, max_grad_norm=1.0, n_prompt_frames=11)
     m1 = _model(2, 12, dtype)
     for _ in range(3):
@@ -245,7 +183,7 @@ def test_training_step_over_a_14_frame_clip_with_12_frame_windows():
     """n_prompt_frames = 11, max_frames = 12: target frames 11, 12, 13 each see a 12-frame window (the last two after the window slid).  The step is applied
     and its loss equals forward_loss of an inference model with the same weights (the project's trainable-vs-inference forward figure, 1.5e-3)."""
     from gtav_amd.train import forward_loss, training_step
-    lat, a, tgt, ctx, cn, nz = _step_inputs(F=12, n_target=3)
+    lat, a, tgt, ctx, cn, nz = _multi_target_clip(3)
     assert lat.shape[1] == 14
     m = _model(2, 12)
     seen = []
@@ -256,7 +194,7 @@ def test_training_step_over_a_14_frame_clip_with_12_frame_windows():
     applied, skipped, gnorm = m.train_stats()
     assert math.isfinite(loss) and applied and skipped == 0 and math.isfinite(gnorm) and gnorm > 0
     mi = DiT(**KW, max_batch=2, max_frames=12, init_weights=False)
-    mi.load_state_dict(_sd())
+    mi.load_state_dict(TC.state_dict(KW))
     ref = float(forward_loss(mi, lat, a, tgt, ctx, cn, nz, n_prompt_frames=11)[0])
     print(f"[14-frame clip] training_step loss {loss:.6f}, inference forward_loss {ref:.6f}, rel {abs(loss - ref) / ref:.3e}")
     assert abs(loss - ref) / ref < 1.5e-3

@@ -2,8 +2,8 @@
 the opt-in costs no bits, a handle with every group switched is the bf16 handle, every boundary between two groups of different types computes the right
 gradients, and a checkpoint with one outlier layer — which skips every fp16 step — trains again after train_autorange() moved the saturated groups to bf16.
 
-Toy geometry and bounds of tests/test_gpu_train_bf16.py: hidden 256, 4 heads, 8 x 16 latents, patch 2 (32 tokens per frame); GRAD_TOL_F16 = 4.5e-3,
-GRAD_TOL_BF16 = 8 x that, TOL_FWD_BF16 = 1.5e-2.  `pytest -s` prints every measured margin.
+Toy geometry and bounds of tests/train_cases.py: hidden 256, 4 heads, 8 x 16 latents, patch 2 (32 tokens per frame); the bf16 GRAD_TOL (8 x the fp16 one) and
+FWD_TOL.  `pytest -s` prints every measured margin.
 
 Depth: the bit-for-bit tests of recompute mode and of the phased backward run at depth 3, where a middle block exists — in recompute mode it is the only block
 whose re-run both starts from a stored shift and ends by re-saving the next block's.  The tests against the fp32 oracle run at depth 2, the depth GRAD_TOL_BF16 was
@@ -17,108 +17,40 @@ import os
 import pytest
 import torch
 
-from helpers import rel_l2 as _rel_l2
+import train_cases as TC
+from helpers import rel_l2_logged as rel_l2       # (-s shows the measured margins)
+from train_cases import BF16, F16
+from train_cases import TOY_KW as KW
 
 pytestmark = pytest.mark.gpu
 
-TOL_FWD_BF16 = 1.5e-2
-GRAD_TOL_F16 = 4.5e-3
-GRAD_TOL_BF16 = 8 * GRAD_TOL_F16      # 3.6e-2
+TOL_FWD_BF16, GRAD_TOL_BF16 = TC.FWD_TOL[BF16], TC.GRAD_TOL[BF16]
 
-KW = dict(input_h=8, input_w=16, patch_size=2, in_channels=16, hidden_size=256, depth=2, num_heads=4, external_cond_dim=25)
 KW3 = dict(KW, depth=3)
-F16, BF16 = torch.float16, torch.bfloat16
 # layer groups of the depth-2 model: 0 .. 3 the half-blocks, 4 the patch embedding, 5 the final layer.  Even / odd: every boundary between two half-blocks changes
 # type; the last pattern also changes type between the last half-block (3) and the final layer (5), whose LayerNorm applies that half-block's pending branch
 PATTERNS = {"even_bf16": [0, 2, 4], "odd_bf16": [1, 3, 5], "final_seam": [1, 2, 5]}
 
 
-def rel_l2(a, b):
-    v = _rel_l2(a, b)
-    print(f"[rel_l2 {os.environ.get('PYTEST_CURRENT_TEST', '').split('::')[-1].split(' ')[0]}] {v:.3e}")   # (-s shows the measured margins)
-    return v
-
-
-def _sd(kw=KW, seed=1):
-    import gtav_amd.weights as W
-    return W.synth_state_dict(W.dit_param_shapes(**kw), seed=seed)
-
-
 def _outlier_sd():
-    sd = _sd(KW, 3)
+    sd = TC.state_dict(KW, 3)
     big = dict(sd)
     big["blocks.0.s_mlp.fc1.weight"] = sd["blocks.0.s_mlp.fc1.weight"] * 3e5     # the x3e5 outlier of tests/test_gpu_range.py
     return big
 
 
 def _model(sd, B, T, dtype=F16, policy="auto", kw=KW, **extra):
-    from gtav_amd.model.dit import DiT
-    m = DiT(**kw, max_batch=B, max_frames=T, init_weights=False, trainable=True, train_dtype=dtype, train_range_policy=policy, **extra)
-    m.load_state_dict(sd)
-    return m
+    return TC.model(kw, B, T, dtype, sd, train_range_policy=policy, **extra)
 
 
-def _inputs(B=2, T=3, actions=True, seed=0, h=8, w=16):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(B, T, 16, h, w, generator=g)
-    t = torch.randint(0, 1000, (B, T), generator=g)
-    a = None
-    if actions:
-        a = torch.zeros(B, T, 25)
-        a[:, :, 3] = 1
-        a[0, T - 1, 7] = 1
-    vt = torch.randn(B, 1, 16, h, w, generator=g)
-    return x, t, a, vt
-
-
-def _step_inputs(B=2, seed=5):
-    g = torch.Generator().manual_seed(seed)
-    lat = torch.randn(B, 5, 16, 8, 16, generator=g) * 0.5
-    a = torch.zeros(B, 5, 25)
-    a[:, :, 3] = 1
-    tgt, ctx = torch.tensor([30, 10][:B]), torch.tensor([5, 20][:B])
-    cn = torch.randn(B, 4, 16, 8, 16, generator=g)
-    nz = torch.randn(B, 1, 16, 8, 16, generator=g)
-    return lat, a, tgt, ctx, cn, nz
-
-
-_ORACLE = {}
-
-
-def _oracle(kw, sd, sd_key, B, T, actions, seed=0):
-    """(inputs, oracle v_pred, oracle gradients) of one case: computed once, shared by the tests that need it, never modified."""
-    key = (tuple(sorted(kw.items())), sd_key, B, T, actions, seed)
-    if key not in _ORACLE:
-        from oracle import ref_cpu as O
-        inp = _inputs(B, T, actions, seed, kw["input_h"], kw["input_w"])
-        torch.set_num_threads(16)
-        _, v_ref, grads = O.dit_loss_and_grads(sd, O.DiTConfig(**kw), *inp)
-        _ORACLE[key] = (inp, v_ref, grads)
-    return _ORACLE[key]
-
-
-def _grad_errors(m, grads, keys=None):
-    worst = {}
-    for k in (keys or grads):
-        gref = grads[k]
-        g = m.grad(k).cpu()
-        assert torch.isfinite(g).all(), k
-        if gref.norm() == 0:
-            assert g.abs().max() == 0, k              # unused upstream (external_cond.* without actions)
-            continue
-        worst[k] = _rel_l2(g, gref)
-    return worst
+def _inputs(B=2, T=3, actions=True, seed=0):
+    return TC.inputs(KW, B, T, actions, seed)
 
 
 def _forward_backward(m, inp, v_ref, grads, keys=None):
     """One forward + backward against the oracle: (forward error, per-tensor gradient errors); nothing may be left in the error words."""
-    x, t, a, vt = inp
-    v = m.forward_train(x, t, a)
-    e_fwd = rel_l2(v, v_ref)
-    m.zero_grad()
-    m.backward_(v, vt)
-    m.check()
-    return e_fwd, _grad_errors(m, grads, keys)
+    v = TC.forward_backward(m, inp)
+    return rel_l2(v, v_ref), TC.grad_errors(m, grads, keys)
 
 
 def _print_table(title, cols):
@@ -144,7 +76,7 @@ def _snapshot(m, probe):
 
 def _run(m, n_steps, probe, **kw):
     from gtav_amd.train import training_step
-    lat, a, tgt, ctx, cn, nz = _step_inputs()
+    lat, a, tgt, ctx, cn, nz = TC.clip(KW)
     losses = [training_step(m, lat, a, tgt, ctx, cn, nz, lr=1e-3, weight_decay=0.01, **kw).clone() for _ in range(n_steps)]
     snap = _snapshot(m, probe)
     snap["losses"] = torch.cat(losses)
@@ -158,9 +90,9 @@ def _assert_same(a, b):
 
 
 # ---- 1. the opt-in costs no bits ----------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("dtype", [F16, BF16], ids=["fp16", "bf16"])
+@TC.DTYPES
 def test_mixed_capable_handle_with_no_group_switched_equals_the_default_handle(dtype):
-    sd, probe = _sd(), _inputs(B=2, T=5, seed=9)
+    sd, probe = TC.state_dict(KW), _inputs(B=2, T=5, seed=9)
     plain = _run(_model(sd, 2, 5, dtype, "report"), 3, probe)
     m = _model(sd, 2, 5, dtype, "auto")
     opted = _run(m, 3, probe)
@@ -173,7 +105,7 @@ def test_mixed_capable_handle_with_no_group_switched_equals_the_default_handle(d
 # ---- 2. every group switched = the bf16 twin ------------------------------------------------------------------------------------------------
 def test_all_groups_switched_equals_the_bf16_handle():
     """The images train_set_group_dtype remakes from the masters in the handle are set_weight's, and no launch stays on the fp16 kernels."""
-    sd, probe = _sd(), _inputs(B=2, T=5, seed=9)
+    sd, probe = TC.state_dict(KW), _inputs(B=2, T=5, seed=9)
     twin = _run(_model(sd, 2, 5, BF16, "report"), 3, probe)
     m = _model(sd, 2, 5, F16, "auto")
     m.forward_train(*probe[:3])                    # the weights are in the handle as fp16 images ...
@@ -187,8 +119,7 @@ def test_all_groups_switched_equals_the_bf16_handle():
 @pytest.mark.parametrize("actions", [True, False], ids=["actions", "noactions"])
 @pytest.mark.parametrize("pattern", list(PATTERNS))
 def test_alternating_types_match_autograd(pattern, actions):
-    sd = _sd()
-    inp, v_ref, grads = _oracle(KW, sd, "synth1", 2, 3, actions)
+    sd, inp, _, v_ref, grads = TC.oracle(KW, 2, 3, actions)
     m = _model(sd, 2, 3)
     m.train_set_group_dtype(BF16, PATTERNS[pattern])
     assert [d == BF16 for d in m.operand_dtypes()] == [g in PATTERNS[pattern] for g in range(6)]
@@ -203,8 +134,7 @@ def test_alternating_types_match_autograd(pattern, actions):
 def test_one_group_switched_keeps_every_gradient_in_the_bf16_bound():
     """Group 1 (block 0, temporal half) on bf16, everything else fp16.  Whether the tensors of the fp16 groups stay at their fp16 error is printed per tensor
     beside the all-fp16 and the all-bf16 handle (profiles/train_mixed/grad_errors.txt is this table), not asserted."""
-    sd = _sd()
-    inp, v_ref, grads = _oracle(KW, sd, "synth1", 2, 3, True)
+    sd, inp, _, v_ref, grads = TC.oracle(KW, 2, 3, True)
     cols = {}
     for name, dtype, groups in (("fp16", F16, []), ("group1", F16, [1]), ("bf16", BF16, [])):
         m = _model(sd, 2, 3, dtype)
@@ -228,7 +158,7 @@ def _outlier_switch(m):
     """The skipped first step of the outlier checkpoint and the switch: returns the switched groups."""
     from gtav_amd.train import training_step
     m.loss_scale = 1.0
-    lat, a, tgt, ctx, cn, nz = _step_inputs()
+    lat, a, tgt, ctx, cn, nz = TC.clip(KW)
     training_step(m, lat, a, tgt, ctx, cn, nz, lr=1e-4)
     applied, skipped, _ = m.train_stats()
     assert not applied and skipped == 1
@@ -245,7 +175,7 @@ def test_outlier_checkpoint_recovers_after_train_autorange():
     big = _outlier_sd()
     m = _model(big, 2, 5)
     _outlier_switch(m)
-    lat, a, tgt, ctx, cn, nz = _step_inputs()
+    lat, a, tgt, ctx, cn, nz = TC.clip(KW)
     losses = []
     for _ in range(8):
         losses.append(float(training_step(m, lat, a, tgt, ctx, cn, nz, lr=1e-4)))
@@ -260,7 +190,9 @@ def test_outlier_checkpoint_recovers_after_train_autorange():
 
 def test_outlier_checkpoint_gradients_after_the_switch():
     big = _outlier_sd()
-    inp, v_ref, grads = _oracle(KW, big, "outlier3", 2, 3, True, seed=4)
+    from oracle import ref_cpu as O
+    inp = _inputs(seed=4)
+    _, v_ref, grads = O.dit_loss_and_grads(big, O.DiTConfig(**KW), *inp)
     m = _model(big, 2, 5)
     _outlier_switch(m)
     # The groups that stayed fp16 need their loss scale back: at scale 1 their gradient stores underflow (block 1's gradients come out as zeros).  Which scale is
@@ -283,11 +215,11 @@ def test_outlier_checkpoint_gradients_after_the_switch():
 # ---- 6. forward saturation switches, backward saturation halves the loss scale ----------------------------------------------------------------
 def test_gradient_overflow_switches_nothing_and_halves_the_scale():
     from gtav_amd.train import LossScaler, training_step
-    m = _model(_sd(), 2, 5)
+    m = _model(TC.state_dict(KW), 2, 5)
     m.zero_grad()                                   # builds the handle: the scaler reads the skip counter it starts from
     sc = LossScaler(m, check_every=1)
     m.loss_scale = 2.0 ** 40                        # every fp16 gradient store saturates; the forward does not know the scale
-    lat, a, tgt, ctx, cn, nz = _step_inputs()
+    lat, a, tgt, ctx, cn, nz = TC.clip(KW)
     training_step(m, lat, a, tgt, ctx, cn, nz, lr=1e-4)
     applied, skipped, _ = m.train_stats()
     assert not applied and skipped == 1
@@ -305,7 +237,7 @@ def test_forward_saturation_switches_groups_and_leaves_the_scale():
     m.zero_grad()
     sc = LossScaler(m, check_every=1)
     m.loss_scale = 1.0
-    lat, a, tgt, ctx, cn, nz = _step_inputs()
+    lat, a, tgt, ctx, cn, nz = TC.clip(KW)
     training_step(m, lat, a, tgt, ctx, cn, nz, lr=1e-4)
     assert m.train_stats()[1] == 1
     assert sc.update() == 1.0 and 0 in sc.switched
@@ -323,7 +255,7 @@ def _alternating(sd, B, T, kw=KW3, **extra):
 
 
 def test_recompute_mode_equals_plain_mode_on_alternating_types():
-    sd, probe = _sd(KW3), _inputs(B=2, T=5, seed=9)
+    sd, probe = TC.state_dict(KW3), _inputs(B=2, T=5, seed=9)
     plain = _run(_alternating(sd, 2, 5), 2, probe)
     rc = _run(_alternating(sd, 2, 5, train_recompute=True), 2, probe)
     assert int(plain["opt.step"][0]) == 2
@@ -331,7 +263,7 @@ def test_recompute_mode_equals_plain_mode_on_alternating_types():
 
 
 def test_phased_backward_equals_monolithic_on_alternating_types():
-    m = _alternating(_sd(KW3), 2, 3)
+    m = _alternating(TC.state_dict(KW3), 2, 3)
     x, t, a, vt = _inputs()
     v = m.forward_train(x, t, a)
     m.zero_grad()
@@ -346,8 +278,7 @@ def test_phased_backward_equals_monolithic_on_alternating_types():
 @pytest.mark.parametrize("case", ["9frames", "200tok"])
 def test_alternating_types_on_a_long_window_and_a_long_frame(case):
     kw, B, T, extra = (KW, 2, 9, dict(train_max_frames=9)) if case == "9frames" else (dict(KW, input_h=20, input_w=40), 2, 3, {})
-    sd = _sd(kw)
-    inp, v_ref, grads = _oracle(kw, sd, "synth1", B, T, True)
+    sd, inp, _, v_ref, grads = TC.oracle(kw, B, T, True)
     e_fwd, worst = _forward_backward(_alternating(sd, B, T, kw, **extra), inp, v_ref, grads)
     _print_table(f"test 7 {case}: forward {e_fwd:.3e}", {"rel_l2": worst})
     assert e_fwd < TOL_FWD_BF16
@@ -360,7 +291,7 @@ def test_save_state_load_state_resumes_a_switched_run_bit_exactly(tmp_path):
     from gtav_amd.lib import GtavError
     from gtav_amd.model.dit import DiT
     from gtav_amd.train import load_state, save_state, training_step
-    lat, a, tgt, ctx, cn, nz = _step_inputs()
+    lat, a, tgt, ctx, cn, nz = TC.clip(KW)
     kw = dict(lr=1e-4, weight_decay=0.01, max_grad_norm=1.0)
     m1 = _model(_outlier_sd(), 2, 5)
     switched = _outlier_switch(m1)
@@ -401,7 +332,7 @@ def test_mixed_type_calls_are_refused_by_name():
         return lib.gtav_last_error().decode()
     n = C.c_int32(0)
     words = (C.c_int32 * 8)()
-    plain = _model(_sd(), 1, 2, policy="report")
+    plain = _model(TC.state_dict(KW), 1, 2, policy="report")
     plain.zero_grad()
     h = plain._handle
     assert "already enabled" in err(lib.gtav_dit_train_allow_mixed(h, 1))
@@ -413,7 +344,7 @@ def test_mixed_type_calls_are_refused_by_name():
             call()
     with pytest.raises(GtavError, match="keeps fp16 operands"):       # as on every fp16 training handle
         plain.set_operand_dtype(BF16)
-    m = _model(_sd(), 1, 2)
+    m = _model(TC.state_dict(KW), 1, 2)
     m.zero_grad()
     h = m._handle
     assert "already enabled" in err(lib.gtav_dit_train_allow_mixed(h, 1))
@@ -438,7 +369,7 @@ def test_autorange_switches_before_it_reports():
     from gtav_amd.train import training_step
     m = _model(_outlier_sd(), 2, 5)
     m.loss_scale = 1.0
-    lat, a, tgt, ctx, cn, nz = _step_inputs()
+    lat, a, tgt, ctx, cn, nz = TC.clip(KW)
     training_step(m, lat, a, tgt, ctx, cn, nz, lr=1e-4)
     x, t, a3, _ = _inputs(B=2, T=3)
     m.forward_train(x, torch.full_like(t, 1000), a3)
@@ -459,11 +390,11 @@ def test_autorange_switches_before_it_reports():
 def test_a_saturating_validation_forward_neither_skips_nor_switches():
     from gtav_amd.lib import GtavError
     from gtav_amd.train import training_step
-    m = _model(_sd(), 2, 5)
+    m = _model(TC.state_dict(KW), 2, 5)
     x, t, a3, _ = _inputs(B=2, T=5, seed=9)
     out = m(x * 1e7, t, a3)                         # inference forward on the training handle: the patch embedding's operand saturates
     assert torch.isfinite(out).all()
-    lat, a, tgt, ctx, cn, nz = _step_inputs()
+    lat, a, tgt, ctx, cn, nz = TC.clip(KW)
     training_step(m, lat, a, tgt, ctx, cn, nz, lr=1e-4)
     applied, skipped, _ = m.train_stats()
     assert applied and skipped == 0

@@ -11,45 +11,25 @@ import math
 import pytest
 import torch
 
-import gtav_amd.weights as W
+import train_cases as TC
 from gtav_amd import lib as L
 from gtav_amd.model.dit import DiT
+from train_cases import BF16, DTYPES, F16
 
 pytestmark = pytest.mark.gpu
 
-F16, BF16 = torch.float16, torch.bfloat16
-DTYPES = [F16, BF16]
 DEPTH = 3
-KW = dict(input_h=8, input_w=16, patch_size=2, in_channels=16, hidden_size=256, depth=DEPTH, num_heads=4, external_cond_dim=25)
+KW = dict(TC.TOY_KW, depth=DEPTH)
 
-_SD, _PLAIN = {}, {}
-
-
-def _sd(kw=KW, seed=1):
-    key = (tuple(sorted(kw.items())), seed)
-    if key not in _SD:
-        _SD[key] = W.synth_state_dict(W.dit_param_shapes(**kw), seed=seed)
-    return _SD[key]
+_PLAIN = {}
 
 
 def _inputs(B, T, actions=True, kw=KW, seed=0):
-    h, w = kw["input_h"], kw["input_w"]
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(B, T, 16, h, w, generator=g)
-    t = torch.randint(0, 1000, (B, T), generator=g)
-    a = None
-    if actions:
-        a = torch.zeros(B, T, 25)
-        a[:, :, 3] = 1
-        a[0, T - 1, 7] = 1
-    vt = torch.randn(B, 1, 16, h, w, generator=g)
-    return x, t, a, vt
+    return TC.inputs(kw, B, T, actions, seed)
 
 
-def _model(B, T, dtype=F16, recompute=False, kw=KW, window=None, sd=None):
-    m = DiT(**kw, max_batch=B, max_frames=T, init_weights=False, trainable=True, train_dtype=dtype, train_max_frames=window, train_recompute=recompute)
-    m.load_state_dict(sd or _sd(kw))
-    return m
+def _model(B, T, dtype=F16, recompute=False, kw=KW, window=None):
+    return TC.model(kw, B, T, dtype, train_max_frames=window, train_recompute=recompute)
 
 
 def _loss(m, v, vt):
@@ -89,7 +69,7 @@ def _assert_same(got, want):
 
 
 # ---- 1 / 2: one step, bit for bit ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("dtype", DTYPES, ids=["fp16", "bf16"])
+@DTYPES
 @pytest.mark.parametrize("actions", [True, False], ids=["actions", "noactions"])
 @pytest.mark.parametrize("B,T", [(2, 3), (1, 5)])
 def test_step_is_bit_equal_to_the_plain_handle(B, T, actions, dtype):
@@ -100,14 +80,14 @@ def test_step_is_bit_equal_to_the_plain_handle(B, T, actions, dtype):
     m.check()          # the error words too: nothing was raised that the plain step does not raise
 
 
-@pytest.mark.parametrize("dtype", DTYPES, ids=["fp16", "bf16"])
+@DTYPES
 def test_bit_equal_on_a_9_frame_window(dtype):
     """train_max_frames=9, (B, T) = (1, 9): the streaming temporal attention forward and backward."""
     m = _model(1, 9, dtype, True, window=9)
     _assert_same(_one_pass(m, *_inputs(1, 9, True)), _plain(1, 9, True, dtype, window=9))
 
 
-@pytest.mark.parametrize("dtype", DTYPES, ids=["fp16", "bf16"])
+@DTYPES
 def test_bit_equal_on_200_token_frames(dtype):
     """20 x 40 latents = 200 tokens per frame, the smallest long-frame geometry of tests/test_gpu_train_long_frames.py, at (1, 2): the streaming spatial
     attention backward."""
@@ -145,13 +125,12 @@ def test_phased_backward_equals_the_plain_monolithic_backward():
 
 
 # ---- 4: optimisation steps, checkpoints across the modes ----------------------------------------------------------------------------------
-def _step_inputs(B=2, F=5, n_target=1, seed=5):
+def _multi_target_clip(n_target, B=2, F=5, seed=5):
+    """TC.clip's latents and actions with n_target target frames: the index draws come before the noise draws."""
     g = torch.Generator().manual_seed(seed)
     lat = torch.randn(B, F, 16, 8, 16, generator=g) * 0.5
     a = torch.zeros(B, F, 25)
     a[:, :, 3] = 1
-    if n_target == 1:
-        return lat, a, torch.tensor([30, 10][:B]), torch.tensor([5, 20][:B]), torch.randn(B, F - 1, 16, 8, 16, generator=g), torch.randn(B, 1, 16, 8, 16, generator=g)
     tgt = [torch.randint(1, 51, (B,), generator=g) for _ in range(n_target)]
     ctx = [torch.randint(1, 41, (B,), generator=g) for _ in range(n_target)]
     first = F - n_target
@@ -175,7 +154,7 @@ def _assert_state_equal(a, b):
 
 def test_three_optimisation_steps_and_checkpoints_across_the_modes(tmp_path):
     from gtav_amd.train import load_state, save_state, training_step
-    ins = _step_inputs()
+    ins = TC.clip(KW)
     kw = dict(lr=3e-4, weight_decay=0.01, max_grad_norm=1.0)
     plain, rc = _model(2, 5, F16, False), _model(2, 5, F16, True)
     for step in range(3):
@@ -202,7 +181,7 @@ def test_three_optimisation_steps_and_checkpoints_across_the_modes(tmp_path):
 def test_frame_loop_with_three_target_frames():
     """A 5-frame clip with n_prompt_frames=2: target frames 2, 3, 4 see windows of 3, 4 and 5 frames, each differentiated inside the loop (training_step)."""
     from gtav_amd.train import training_step
-    ins = _step_inputs(n_target=3)
+    ins = _multi_target_clip(3)
     out = []
     for recompute in (False, True):
         m = _model(2, 5, F16, recompute)
@@ -238,7 +217,7 @@ def test_fp16_saturation_skips_the_step_in_both_modes():
     """A loss scale of 2^40 saturates the fp16 activation gradients (tests/test_gpu_train.py test_fp16_saturation_skips_the_step_and_loss_scaler_backs_off): the
     step is skipped on the device with the same statistics, the weights stay, and the error word was consumed."""
     from gtav_amd.train import training_step
-    ins = _step_inputs()
+    ins = TC.clip(KW)
     stats = []
     for recompute in (False, True):
         m = _model(2, 5, F16, recompute)
@@ -248,7 +227,7 @@ def test_fp16_saturation_skips_the_step_in_both_modes():
         assert not applied and skipped == 1 and math.isinf(gnorm)
         assert int(m.opt_state_dict()["step"][0]) == 0
         m.pull_weights()
-        assert torch.equal(m._sd["blocks.1.s_mlp.fc1.weight"], _sd()["blocks.1.s_mlp.fc1.weight"])
+        assert torch.equal(m._sd["blocks.1.s_mlp.fc1.weight"], TC.state_dict(KW)["blocks.1.s_mlp.fc1.weight"])
         m.check()
         stats.append((applied, skipped, gnorm))
     assert stats[0] == stats[1]
