@@ -33,6 +33,8 @@ GTAV_TWIN_STRUCT(LnPending)
 GTAV_TWIN_STRUCT(GemmDwGroup)
 GTAV_TWIN_STRUCT(AdamParam)
 GTAV_TWIN_STRUCT(AdamItem)
+GTAV_TWIN_STRUCT(LoraMergeParam)
+GTAV_TWIN_STRUCT(LoraMergeItem)
 #undef GTAV_TWIN_STRUCT
 // twin_call<fp16 signature, twin's signature, twin>::call has the fp16 signature and calls the twin with every argument cast to the type the twin declares.
 // A twin whose signature is not the mapped fp16 one does not compile.
@@ -489,6 +491,23 @@ int gtav_op_train_transpose_tiled(const void* src, int32_t R, int32_t C, void* d
 int gtav_op_train_convert_t(const float* src, int32_t lds, int32_t R, int32_t C, void* dst, void* stream) {
     GTAV_REQUIRE(src && dst && R >= 1 && C >= 1 && lds >= C, "op_train_convert_T: R=%d C=%d lds=%d", R, C, lds);
     return op_ops().convert_T(src, lds, R, C, (f16*)dst, (hipStream_t)stream);
+}
+// Low-rank adapters, kernel level (include/gtav_amd.h): the gradient of one Linear as a LoRA training handle launches it, and the merge of one Linear (both images,
+// then the fp32 sum where w_f32 is given).  The launchers validate the shapes and the workspace by name.
+int gtav_op_lora_grads(const void* x, const void* dy, const float* a_f32, const float* b_f32, int32_t M, int32_t N, int32_t K, int32_t r, float s, float* dA,
+                       float* dB, float* ws, int64_t ws_floats, int32_t* err, void* stream) {
+    GTAV_REQUIRE(ws_floats >= 0, "op_lora_grads: ws_floats=%lld", (long long)ws_floats);
+    return op_ops().lora_grads((const f16*)x, (const f16*)dy, a_f32, b_f32, M, N, K, r, s, dA, dB, ws, (size_t)ws_floats, err, (hipStream_t)stream);
+}
+int gtav_op_lora_merge(const float* w0_f32, const float* a_f32, const float* b_f32, int32_t N, int32_t K, int32_t r, float s, void* w_img, void* wT_img,
+                       float* w_f32, void* stream) {
+    GTAV_REQUIRE(w_img, "op_lora_merge: null image");
+    LoraMergeParam P;
+    memset(&P, 0, sizeof(P));
+    P.w0 = w0_f32; P.a = a_f32; P.b = b_f32; P.N = N; P.K = K; P.r = r; P.s = s;
+    P.w16 = (f16*)w_img; P.Cp16 = K; P.wT = (f16*)wT_img; P.RpT = round_up(N, 64); P.w32 = w_f32;
+    RET_IF(op_ops().lora_merge_one(P, 0, (hipStream_t)stream));
+    return w_f32 ? op_ops().lora_merge_one(P, 1, (hipStream_t)stream) : 0;
 }
 int gtav_op_train_silu(const float* x, int32_t ldx, float* y, int32_t ldy, int32_t R, int32_t C, void* stream) {
     GTAV_REQUIRE(x && y && R >= 1 && C >= 1 && ldx >= C && ldy >= C, "op_train_silu: R=%d C=%d ldx=%d ldy=%d", R, C, ldx, ldy);

@@ -386,7 +386,8 @@ int gtav_dit_set_weight(gtav_dit* h, const char* name, const float* src, int64_t
         n = spatial ? "spatial_rotary_emb.freqs" : "temporal_rotary_emb.freqs";
     }
     h->finalized = false;
-    return h->wt.set(n.c_str(), src, numel, (hipStream_t)stream);
+    RET_IF(h->wt.set(n.c_str(), src, numel, (hipStream_t)stream));
+    return train_lora_after_set(h, n, (hipStream_t)stream);   // (a LoRA training handle: the Linear's images stay merged)
 }
 
 int gtav_dit_get_weight(gtav_dit* h, const char* name, float* dst, int64_t numel, void* stream) {
@@ -434,6 +435,7 @@ int gtav_dit_finalize(gtav_dit* h, void* stream) {
         }
         RET_IF(upload(h->sincos, tab));
     }
+    if (h->tr.lora.rank && h->tr.on) RET_IF(train_lora_merge_all(h, s));   // (a LoRA training handle: W0 + s B A into every adapted weight's images)
     for (size_t hb = 0; hb < h->halves.size(); ++hb) {
         gtav_dit::Half& w = h->halves[hb];
         if (w.w_qkv_hm) RET_IF(launch_qkv_head_major(w.w_qkv, w.w_qkv_hm, D, s, (hb & 1) ? 0 : 1));

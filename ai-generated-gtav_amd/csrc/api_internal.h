@@ -1,6 +1,6 @@
 // Internals shared by the C-ABI translation units (api.hip: error plumbing, operand-type launcher tables, elementwise / kernel-level entry points, timer
 // calibration; api_dit.hip: the DiT handle — create, weights, forward, sampler step, profile, check / operand type; api_train.hip: the DiT training step;
-// api_vae.hip: the VAE handle).  Everything here is inline / header-only: handle bookkeeping (Arena, WeightTable), host-side table builders, the in-situ
+// api_vae.hip: the VAE handle).  Everything here is inline / header-only but the two LoRA helpers declared at the end: handle bookkeeping (Arena, WeightTable), host-side table builders, the in-situ
 // profiler and the DiT handle itself, which the inference and the training file both work on.
 #pragma once
 #include "../../include/gtav_amd.h"
@@ -475,7 +475,25 @@ struct gtav_dit {
         std::vector<Slot*> params;          // trainable slots in a fixed (sorted-by-name) order
         // the slots the backward pass writes gradients of, resolved by name once (train_enable): per half-block (to_qkv has no bias), final layer, embedders;
         // ext: null without external_cond
-        struct Linear { Slot *w = nullptr, *b = nullptr; };
+        // Low-rank adapters (gtav_dit_train_set_lora; DESIGN.md 7 "Low-rank adapters"): rank 0 = off.  The only trainable slots are then the adapter pairs
+        // "<linear>.lora_A.weight" [r][K] / "<linear>.lora_B.weight" [N][r] of the four GEMM Linears of every half-block; every other slot is frozen (the GEMM
+        // weights keep master and wT, nothing but the adapters has grad / am / av).  The 2-byte images hold clamp(W0 + s B A), s = alpha / rank, rewritten by
+        // ONE launch over merge_items after every optimizer step and by finalize; linears[4 i + j] is Linear j (to_qkv, to_out, fc1, fc2) of half-block i,
+        // whose tiles are items [first_item, first_item + n_items).
+        struct Lora {
+            int rank = 0;
+            float alpha = 0.f, s = 0.f;
+            struct Lin { std::string name; Slot *w = nullptr, *a = nullptr, *b = nullptr; LoraMergeParam p; int first_item = 0, n_items = 0; };
+            std::vector<Lin> linears;
+            LoraMergeParam* params_dev = nullptr;
+            LoraMergeItem* items_dev = nullptr;
+            int n_items = 0;
+            float* ws = nullptr;            // workspace of the gradient launches (ops.h lora_grads_workspace at the handle's largest M, N + K)
+            size_t ws_floats = 0;
+            bool trainable_name(const std::string& n) const { return n.find(".lora_") != std::string::npos; }
+        } lora;
+        // la / lb: the Linear's adapter pair on a LoRA handle (then w has no gradient and b is not resolved)
+        struct Linear { Slot *w = nullptr, *b = nullptr, *la = nullptr, *lb = nullptr; };
         struct HalfSlots { Linear qkv, out, fc1, fc2, ada; };
         std::vector<HalfSlots> hs;          // [2 L]
         Linear fin, fin_ada, pe, t0, t2, ext;
@@ -501,3 +519,6 @@ struct gtav_dit {
     } tr;
 };
 
+// Low-rank adapters (api_train.hip): the merge of every adapted weight's images, and of the one Linear a weight upload touched
+int train_lora_merge_all(gtav_dit* h, hipStream_t s);
+int train_lora_after_set(gtav_dit* h, const std::string& name, hipStream_t s);

@@ -52,12 +52,85 @@ static int train_resolve_slots(gtav_dit* h) {
     return h->A > 0 ? train_linear(h, "external_cond", &t.ext) : 0;
 }
 
+// ... on a LoRA handle (gtav_dit_train_set_lora): the four GEMM Linears of every half-block with their adapter pairs, and the final projection, whose W^T the dX
+// chain starts from.  Nothing else is differentiated with respect to its parameters.
+static int train_resolve_lora(gtav_dit* h) {
+    gtav_dit::Train& t = h->tr;
+    t.hs.resize(2 * h->L);
+    t.lora.linears.clear();
+    static const char* const kLin[4] = {"attn.to_qkv", "attn.to_out", "mlp.fc1", "mlp.fc2"};
+    for (int i = 0; i < 2 * h->L; ++i) {
+        char pre[64];
+        snprintf(pre, sizeof(pre), "blocks.%d.%c_", i / 2, i % 2 == 0 ? 's' : 't');
+        gtav_dit::Train::Linear* const lin[4] = {&t.hs[i].qkv, &t.hs[i].out, &t.hs[i].fc1, &t.hs[i].fc2};
+        for (int j = 0; j < 4; ++j) {
+            const std::string n = std::string(pre) + kLin[j];
+            gtav_dit::Train::Linear& l = *lin[j];
+            l.w = h->wt.find(n + ".weight"); l.la = h->wt.find(n + ".lora_A.weight"); l.lb = h->wt.find(n + ".lora_B.weight");
+            GTAV_REQUIRE(l.w && l.w->master && l.w->wT && l.la && l.la->grad && l.lb && l.lb->grad, "train_enable: the model has no adapted Linear '%s'", n.c_str());
+            gtav_dit::Train::Lora::Lin L;
+            L.name = n + ".weight"; L.w = l.w; L.a = l.la; L.b = l.lb;
+            memset(&L.p, 0, sizeof(L.p));
+            L.p.w0 = l.w->master; L.p.a = l.la->master; L.p.b = l.lb->master; L.p.N = l.w->R; L.p.K = l.w->C; L.p.r = t.lora.rank; L.p.s = t.lora.s;
+            L.p.w16 = (f16*)l.w->dst; L.p.Cp16 = l.w->Cp; L.p.wT = l.w->wT; L.p.RpT = round_up(l.w->R, 64);
+            t.lora.linears.push_back(L);
+        }
+    }
+    t.fin.w = h->wt.find("final_layer.linear.weight");
+    GTAV_REQUIRE(t.fin.w && t.fin.w->wT, "train_enable: the model has no final projection");
+    return 0;
+}
+// the device tables of the merge launch (one item per 64 x 64 tile of every adapted weight) and the workspace of the gradient launches
+static int train_lora_tables(gtav_dit* h) {
+    gtav_dit::Train::Lora& lo = h->tr.lora;
+    std::vector<LoraMergeParam> mp;
+    std::vector<LoraMergeItem> mi;
+    size_t ws = 0;
+    for (size_t k = 0; k < lo.linears.size(); ++k) {
+        auto& L = lo.linears[k];
+        mp.push_back(L.p);
+        L.first_item = (int)mi.size();
+        L.n_items = (L.p.N / 64) * (L.p.K / 64);
+        for (int i = 0; i < L.n_items; ++i) mi.push_back(LoraMergeItem{(int)k, (unsigned)i});
+        ws = std::max(ws, lora_grads_workspace_upto(h->Mmax, L.p.N, L.p.K, lo.rank));
+    }
+    RET_IF(h->arena.alloc_t(&lo.params_dev, mp.size()));
+    RET_IF(h->arena.alloc_t(&lo.items_dev, mi.size()));
+    GTAV_CHECK_HIP(hipMemcpy(lo.params_dev, mp.data(), mp.size() * sizeof(LoraMergeParam), hipMemcpyHostToDevice));
+    GTAV_CHECK_HIP(hipMemcpy(lo.items_dev, mi.data(), mi.size() * sizeof(LoraMergeItem), hipMemcpyHostToDevice));
+    lo.n_items = (int)mi.size();
+    lo.ws_floats = ws;
+    return h->arena.alloc_t(&lo.ws, ws);
+}
+
+// every adapted weight's images from its master and its adapters (gtav_dit_finalize, gtav_dit_adamw_step)
+int train_lora_merge_all(gtav_dit* h, hipStream_t s) {
+    const gtav_dit::Train::Lora& lo = h->tr.lora;
+    GTAV_REQUIRE(lo.rank && h->tr.on && lo.n_items, "lora_merge: not a LoRA training handle");
+    return operand_ops(h->tr.bf16).lora_merge(lo.params_dev, lo.items_dev, lo.n_items, s);
+}
+// gtav_dit_set_weight of an adapter or of an adapted base weight: once all three tensors of that Linear have arrived its images are merged again, so the
+// order of the uploads does not matter (an upload of the base alone wrote the plain images: WeightTable::set)
+int train_lora_after_set(gtav_dit* h, const std::string& name, hipStream_t s) {
+    if (!h->tr.lora.rank || !h->tr.on) return 0;
+    for (const auto& L : h->tr.lora.linears) {
+        const Slot* sl = h->wt.find(name);
+        if (sl != L.w && sl != L.a && sl != L.b) continue;
+        if (L.w->set && L.a->set && L.b->set) return operand_ops(h->tr.bf16).lora_merge_one(L.p, 0, s);
+        return 0;
+    }
+    return 0;
+}
+
 // gtav_dit_train_enable after its operand-type checks: trainable slots, fp32 masters, AdamW state, saved-activation and backward workspace
 static int train_enable_body(gtav_dit* h, float* grad_arena_dev, int64_t grad_arena_numel) {
     for (auto& kv : h->wt.slots) GTAV_REQUIRE(!kv.second.set, "train_enable: call it before any gtav_dit_set_weight (the fp32 masters are filled by set_weight)");
     gtav_dit::Train& t = h->tr;
     Arena& a = h->arena;
     const int D = h->D, L = h->L, Hp = h->Hm_pad;
+    const bool lora = t.lora.rank > 0;     // (gtav_dit_train_set_lora): the adapters are the only trainable slots
+    GTAV_REQUIRE(!(lora && t.mixed), "train_enable: gtav_dit_train_allow_mixed together with gtav_dit_train_set_lora is not implemented (a type switch remakes the "
+                 "2-byte images from the fp32 masters, without the adapters)");
     // Every patch width F = C p^2 the forward takes, but for two refusals.  The patch embedding contracts over Kpe = round_up(F, 64) columns whose pad is zero in
     // both operands (patchify, the weight image), the final projection's gradient dfo is Nf = round_up(F, 64) wide with zero pad columns (mse_bwd_patch).
     const int F = h->C * h->p * h->p, Nf = round_up(h->Nfin, 64);
@@ -69,7 +142,7 @@ static int train_enable_body(gtav_dit* h, float* grad_arena_dev, int64_t grad_ar
     size_t count = 0;
     std::vector<std::string> names;
     for (auto& kv : h->wt.slots) {
-        if (!WeightTable::trainable_name(kv.first)) continue;
+        if (!(lora ? t.lora.trainable_name(kv.first) : WeightTable::trainable_name(kv.first))) continue;
         kv.second.trainable = true;
         t.params.push_back(&kv.second);
         names.push_back(kv.first);
@@ -99,8 +172,17 @@ static int train_enable_body(gtav_dit* h, float* grad_arena_dev, int64_t grad_ar
             sl->master = (float*)sl->dst + sl->c0;
         }
     }
+    if (lora) {   // the frozen GEMM weights: the fp32 master the merge starts from (and get_weight returns), W^T for dX; no gradient, no moments
+        for (auto& kv : h->wt.slots) {
+            Slot& sl = kv.second;
+            if (sl.kind != SLOT_F16_PAD) continue;
+            RET_IF(a.alloc_t(&sl.master, (size_t)sl.R * sl.C));
+            if (kv.first != "x_embedder.proj.weight") RET_IF(a.alloc_t(&sl.wT, (size_t)round_up(sl.C, 128) * round_up(sl.R, 64)));
+        }
+    }
     RET_IF(a.alloc_t(&t.ctl, 8));
-    RET_IF(train_resolve_slots(h));
+    RET_IF(lora ? train_resolve_lora(h) : train_resolve_slots(h));
+    if (lora) RET_IF(train_lora_tables(h));
     t.red_ws_floats = colsum_workspace(h->Mmax > h->max_rows ? h->Mmax : h->max_rows, std::max(std::max(h->Hm_pad, 6 * D), Nf));
     RET_IF(a.alloc_t(&t.red_ws, t.red_ws_floats));
     RET_IF(a.alloc_t(&t.sumsq_part, (size_t)sumsq_parts(count)));
@@ -177,9 +259,10 @@ static int train_enable_body(gtav_dit* h, float* grad_arena_dev, int64_t grad_ar
     RET_IF(a.alloc_t(&t.g_d, Mx * D)); RET_IF(a.alloc_t(&t.g_d2, Mx * D)); RET_IF(a.alloc_t(&t.g_h, Mx * Hp)); RET_IF(a.alloc_t(&t.g_u, Mx * Hp)); RET_IF(a.alloc_t(&t.g_qkv, Mx * 3 * D));
     RET_IF(a.alloc_t(&t.dao, Mm * D)); RET_IF(a.alloc_t(&t.dfo, Mx * Nf));
     // (rows of the transposed images, padded to the GEMM's 128-row tiles: dfo^T has Nf rows, xp^T has Kpe)
+    // (a LoRA handle runs no dW GEMM: none of the transposed operand buffers)
     const size_t widest = (size_t)std::max(std::max(Hp, 3 * D), std::max(round_up(Nf, 128), round_up(h->Kpe, 128)));
-    RET_IF(a.alloc_t(&t.tA, widest * Mp)); RET_IF(a.alloc_t(&t.tB, widest * Mp));
-    if (D % 256 == 0 && Hp % 256 == 0) {   // (rows of the transposed images: fc2 dY / X, fc1, out-proj, QKV)
+    if (!lora) { RET_IF(a.alloc_t(&t.tA, widest * Mp)); RET_IF(a.alloc_t(&t.tB, widest * Mp)); }
+    if (!lora && D % 256 == 0 && Hp % 256 == 0) {   // (rows of the transposed images: fc2 dY / X, fc1, out-proj, QKV)
         const size_t ra[4] = {(size_t)D, (size_t)Hp, (size_t)D, (size_t)3 * D}, rb[4] = {(size_t)Hp, (size_t)D, (size_t)D, (size_t)D};
         for (int i = 0; i < 4; ++i) { RET_IF(a.alloc_t(&t.tAg[i], ra[i] * Mp)); RET_IF(a.alloc_t(&t.tBg[i], rb[i] * Mp)); }
     }
@@ -219,7 +302,52 @@ int gtav_dit_train_set_recompute(gtav_dit* h, int32_t enable) {
 int gtav_dit_train_allow_mixed(gtav_dit* h, int32_t enable) {
     GTAV_REQUIRE(h, "train_allow_mixed: null handle");
     GTAV_REQUIRE(!h->tr.on, "train_allow_mixed: training is already enabled on this handle (call it between gtav_dit_create and gtav_dit_train_enable)");
+    GTAV_REQUIRE(!(enable && h->tr.lora.rank), "train_allow_mixed: mixed operand groups together with low-rank adapters (gtav_dit_train_set_lora) are not implemented");
     h->tr.mixed = enable != 0;
+    return 0;
+}
+
+// Opt-in to low-rank adapter training (api_internal.h Train::Lora; DESIGN.md 7 "Low-rank adapters"): between create and train_enable only, like the three above.
+// Adds the adapter pairs of the four GEMM Linears of every half-block to the weight table as fp32 slots.
+int gtav_dit_train_set_lora(gtav_dit* h, int32_t rank, float alpha) {
+    GTAV_REQUIRE(h, "train_set_lora: null handle");
+    GTAV_REQUIRE(!h->tr.on, "train_set_lora: training is already enabled on this handle (call it between gtav_dit_create and gtav_dit_train_enable)");
+    GTAV_REQUIRE(lora_rank_ok(rank), "train_set_lora: rank %d (the adapters fill whole MFMA tiles: 16, 32 or 64)", rank);
+    GTAV_REQUIRE(alpha > 0.f && std::isfinite(alpha), "train_set_lora: alpha=%g must be a positive number", (double)alpha);
+    GTAV_REQUIRE(!h->tr.mixed, "train_set_lora: low-rank adapters together with mixed operand groups (gtav_dit_train_allow_mixed) are not implemented");
+    GTAV_REQUIRE(h->tr.lora.rank == 0, "train_set_lora: the adapters of this handle exist already (rank %d)", h->tr.lora.rank);
+    GTAV_REQUIRE(h->D % 64 == 0 && h->Hm % 64 == 0 && h->Hm == h->Hm_pad, "train_set_lora: hidden_size=%d and the MLP width %d must be multiples of 64 (the merge works "
+                 "on 64 x 64 tiles)", h->D, h->Hm);
+    static const char* const kLin[4] = {"attn.to_qkv", "attn.to_out", "mlp.fc1", "mlp.fc2"};
+    const int D = h->D, NK[4][2] = {{3 * D, D}, {D, D}, {h->Hm, D}, {D, h->Hm}};
+    for (int i = 0; i < 2 * h->L; ++i)
+        for (int j = 0; j < 4; ++j) {
+            char pre[96];
+            snprintf(pre, sizeof(pre), "blocks.%d.%c_%s", i / 2, i % 2 == 0 ? 's' : 't', kLin[j]);
+            float *pa = nullptr, *pb = nullptr;
+            RET_IF(h->arena.alloc_t(&pa, (size_t)rank * NK[j][1]));
+            RET_IF(h->arena.alloc_t(&pb, (size_t)NK[j][0] * rank));
+            h->wt.add_f32(std::string(pre) + ".lora_A.weight", rank, NK[j][1], pa, NK[j][1]);
+            h->wt.add_f32(std::string(pre) + ".lora_B.weight", NK[j][0], rank, pb, rank);
+        }
+    h->tr.lora.rank = rank; h->tr.lora.alpha = alpha; h->tr.lora.s = alpha / (float)rank;
+    h->finalized = false;
+    return 0;
+}
+
+// fp32 W0 + s B A of one adapted weight, torch layout: what the merge launch casts into the images (the same device function)
+int gtav_dit_lora_get_merged(gtav_dit* h, const char* name, float* dst, int64_t numel, void* stream) {
+    GTAV_REQUIRE(h && name && dst, "lora_get_merged: null argument");
+    GTAV_REQUIRE(h->tr.lora.rank && h->tr.on, "lora_get_merged: not a LoRA training handle (gtav_dit_train_set_lora, gtav_dit_train_enable)");
+    for (const auto& L : h->tr.lora.linears) {
+        if (L.name != name) continue;
+        GTAV_REQUIRE(numel == (int64_t)L.p.N * L.p.K, "lora_get_merged: '%s' has %d x %d elements, got %lld", name, L.p.N, L.p.K, (long long)numel);
+        GTAV_REQUIRE(L.w->set && L.a->set && L.b->set, "lora_get_merged: '%s' or its adapters were not set", name);
+        LoraMergeParam P = L.p;
+        P.w32 = dst;
+        return operand_ops(h->tr.bf16).lora_merge_one(P, 1, (hipStream_t)stream);
+    }
+    GTAV_REQUIRE(false, "lora_get_merged: '%s' is not an adapted weight (the to_qkv, to_out, fc1 and fc2 weights of the blocks are)", name);
     return 0;
 }
 
@@ -343,7 +471,7 @@ int gtav_dit_train_param_count(gtav_dit* h, int64_t* numel) {
     GTAV_REQUIRE(h && numel, "train_param_count: null argument");
     int64_t c = 0;
     for (auto& kv : h->wt.slots)
-        if (WeightTable::trainable_name(kv.first)) c += (int64_t)kv.second.R * kv.second.C;
+        if (h->tr.lora.rank ? h->tr.lora.trainable_name(kv.first) : WeightTable::trainable_name(kv.first)) c += (int64_t)kv.second.R * kv.second.C;
     *numel = c;
     return 0;
 }
@@ -444,11 +572,12 @@ struct TrainBackward {
     const int D, P, L, B, T, M, Mp, NB, rows, Hp, MODW;
     const OperandOps* op;   // launcher set of the operand group being differentiated (final layer, half-block i, patch embedding): set where each part begins
     bool defer_dw = false, tn_dw, fuse_ln, fuse_gate, defer_bias;   // which fusions the shapes of this step allow (the constructor says when)
+    const bool lora;        // a LoRA handle (Train::Lora): adapter gradients in place of dW, no bias / adaLN / final-layer / embedder parameter gradients
     GemmDwGroup dwg[GEMM_DW_MAX_GROUPS];   // the pending grouped weight gradients
     int ndw = 0;
 
     TrainBackward(gtav_dit* h_, hipStream_t s_)
-        : h(h_), tr(h_->tr), s(s_), D(h->D), P(h->P), L(h->L), B(tr.B), T(tr.T), M(tr.M), Mp(tr.Mp), NB(B * T), rows(tr.rows), Hp(h->Hm_pad), MODW(h->MODW), op(&h->ops(2 * L + 1)) {
+        : h(h_), tr(h_->tr), s(s_), D(h->D), P(h->P), L(h->L), B(tr.B), T(tr.T), M(tr.M), Mp(tr.Mp), NB(B * T), rows(tr.rows), Hp(h->Hm_pad), MODW(h->MODW), op(&h->ops(2 * L + 1)), lora(h_->tr.lora.rank > 0) {
         // Half-blocks of production widths defer their four dW GEMMs into ONE grouped launch of 256 x 256 tiles (flush_dw; gemm.h)
         if (tr.tAg[0] && g_dw_grouped) {
             const GemmDwGroup probe[4] = {{tr.tAg[0], tr.tBg[0], tr.dres, D, Hp, Hp}, {tr.tAg[1], tr.tBg[1], tr.dres, Hp, D, D}, {tr.tAg[2], tr.tBg[2], tr.dres, D, D, D},
@@ -483,6 +612,7 @@ struct TrainBackward {
     // Kv < K (the patch embedding at C p^2 % 64 != 0): X carries K - Kv zero pad columns which the gradient, contiguous [N][Kv], has no room for: the
     // transposed-operand GEMM writes the first Kv of its K features with ldo = Kv (the other forms write whole 128 / 256-column tiles)
     int gemm_dw(const f16* dY, int N, const f16* X, int K, float* grad, int slot_i = -1, int Kv = 0) {
+        GTAV_REQUIRE(!lora, "train_backward: a LoRA handle computes no full weight gradient");
         if (Kv > 0 && Kv < K) {
             RET_IF(op->transpose_tiled(dY, M, N, tr.tA, s));
             RET_IF(op->transpose_tiled(X, M, K, tr.tB, s));
@@ -511,6 +641,13 @@ struct TrainBackward {
         q.out = grad; q.ldo = K;
         return op->gemm(q, EPI_RESID, s);
     }
+    // the weight gradient of one of a half-block's four Linears: the full dW, or on a LoRA handle the gradients of its adapter pair (train.hip launch_lora_grads:
+    // three launches at once, nothing deferred, so dY and X need not outlive the call)
+    int linear_dw(const gtav_dit::Train::Linear& l, const f16* dY, int N, const f16* X, int K, int slot_i) {
+        if (!lora) return gemm_dw(dY, N, X, K, l.w->grad, slot_i);
+        return op->lora_grads(X, dY, l.la->master, l.lb->master, M, N, K, tr.lora.rank, tr.lora.s, l.la->grad, l.lb->grad, tr.lora.ws, tr.lora.ws_floats, h->err_flag, s);
+    }
+    static float* bias_grad(const gtav_dit::Train::Linear& l) { return l.b ? l.b->grad : nullptr; }   // (null on a LoRA handle: the biases are frozen)
     int ln_bwd(const float* dxn, const float* x, const float* scale, int accumulate, float* dshift, float* dscale) {
         if (fuse_ln) return launch_ln_mod_bwd_fused(dxn, x, scale, MODW, NB, P, D, tr.dres, accumulate, dshift, dscale, tr.ln_part, s);
         RET_IF(launch_ln_mod_bwd(dxn, x, scale, MODW, P, M, D, tr.dres, accumulate, tr.stats, s));
@@ -527,7 +664,7 @@ struct TrainBackward {
         if (fuse_gate) return op->gate_bwd_fused(tr.dres, y, gate, MODW, NB, P, D, g_out, dgate, defer_bias ? nullptr : dbias, ws, h->err_flag, s);
         RET_IF(op->gate_bwd(tr.dres, gate, MODW, P, M, D, g_out, h->err_flag, s));
         RET_IF(op->frame_reduce_gate(tr.dres, y, NB, P, D, dgate, MODW, s));
-        return op->colsum_tiled(g_out, M, D, dbias, tr.red_ws, s);
+        return dbias ? op->colsum_tiled(g_out, M, D, dbias, tr.red_ws, s) : 0;   // (dbias null: a LoRA handle, whose biases are frozen)
     }
     int final_layer(const float* v_pred, const float* v_target);
     int half_block(int i);
@@ -540,6 +677,11 @@ int TrainBackward::final_layer(const float* v_pred, const float* v_target) {
     op = &h->ops(2 * L + 1);
     const int Nf = round_up(h->Nfin, 64);   // width of dfo: the final projection's features padded to whole 64-column tiles (zeros: mse_bwd_patch)
     RET_IF(op->mse_bwd_patch(v_pred, v_target, B, T, h->C, h->H, h->W, h->p, scale, tr.dfo, Nf, h->err_flag, s));
+    if (lora) {   // the final layer is frozen: the dX chain alone (the LayerNorm backward still fills its dmod chunks, which nothing reads)
+        RET_IF(gemm_dx(tr.dfo, tr.fin.w->wT, D, Nf, EPI_F32, tr.dtmp, D));
+        float* dmf = tr.dmod + (size_t)L * 12 * D;
+        return ln_bwd(tr.dtmp, tr.res[4 * L], h->mod + (size_t)L * 12 * D + D, 0, dmf, dmf + D);
+    }
     // db: column sums over the Nf-wide (zero-padded) dfo, only the first Nfin belong to the bias: sum into a scratch row first
     GTAV_CHECK_HIP(hipMemsetAsync(tr.dSc, 0, Nf * sizeof(float), s));
     RET_IF(op->colsum_tiled(tr.dfo, M, Nf, tr.dSc, tr.red_ws, s));
@@ -567,29 +709,29 @@ int TrainBackward::half_block(int i) {
     op = &h->ops(i);
     // r_{2i+2} = r_{2i+1} + gate_mlp y2
     float* const ws_fc2 = tr.red_ws, *const ws_out = tr.red_ws + (defer_bias ? (size_t)NB * D : 0), *const ws_fc1 = tr.red_ws + (defer_bias ? (size_t)2 * NB * D : 0);   // (not deferred: every reduction follows its partial sums at once and the regions may coincide)
-    RET_IF(gate_bwd(b.y2, mb + 5 * D, dmb + 5 * D, tr.g_d, p.fc2.b->grad, ws_fc2));
-    RET_IF(gemm_dw(tr.g_d, D, b.hh, Hp, p.fc2.w->grad, 0));
+    RET_IF(gate_bwd(b.y2, mb + 5 * D, dmb + 5 * D, tr.g_d, bias_grad(p.fc2), ws_fc2));
+    RET_IF(linear_dw(p.fc2, tr.g_d, D, b.hh, Hp, 0));
     RET_IF(gemm_dx(tr.g_d, p.fc2.w->wT, Hp, D, EPI_F16_TILED, tr.g_h, Hp));
     if (defer_bias) {
         RET_IF(op->gelu_bwd_tiled_colsum(tr.g_h, b.u, tr.g_u, M, Hp, nullptr, ws_fc1, h->err_flag, s));
     } else if (g_fuse_gelu && colsum_workspace(round_up(M, 128), Hp) <= tr.red_ws_floats) {
-        RET_IF(op->gelu_bwd_tiled_colsum(tr.g_h, b.u, tr.g_u, M, Hp, p.fc1.b->grad, tr.red_ws, h->err_flag, s));
+        RET_IF(op->gelu_bwd_tiled_colsum(tr.g_h, b.u, tr.g_u, M, Hp, bias_grad(p.fc1), tr.red_ws, h->err_flag, s));   // (LoRA: null, the partial sums stay unread)
     } else {
         RET_IF(op->gelu_bwd_tiled(tr.g_h, b.u, tr.g_u, (size_t)round_up(M, 128) * Hp, h->err_flag, s));
-        RET_IF(op->colsum_tiled(tr.g_u, M, Hp, p.fc1.b->grad, tr.red_ws, s));
+        if (!lora) RET_IF(op->colsum_tiled(tr.g_u, M, Hp, p.fc1.b->grad, tr.red_ws, s));
     }
-    RET_IF(gemm_dw(tr.g_u, Hp, b.xnB, D, p.fc1.w->grad, 1));
+    RET_IF(linear_dw(p.fc1, tr.g_u, Hp, b.xnB, D, 1));
     RET_IF(gemm_dx(tr.g_u, p.fc1.w->wT, D, Hp, EPI_F32, tr.dtmp, D));
     RET_IF(ln_bwd(tr.dtmp, tr.res[2 * i + 1], mb + 4 * D, 1, dmb + 3 * D, dmb + 4 * D));
     // r_{2i+1} = r_{2i} + gate_msa y1
     f16* const g_o = tn_dw ? tr.g_d2 : tr.g_d;   // (the fc2 weight gradient above still reads g_d when the grouped launch is deferred without copies)
-    RET_IF(gate_bwd(b.y1, mb + 2 * D, dmb + 2 * D, g_o, p.out.b->grad, ws_out));
-    RET_IF(gemm_dw(g_o, D, b.ao, D, p.out.w->grad, 2));
+    RET_IF(gate_bwd(b.y1, mb + 2 * D, dmb + 2 * D, g_o, bias_grad(p.out), ws_out));
+    RET_IF(linear_dw(p.out, g_o, D, b.ao, D, 2));
     RET_IF(gemm_dx(g_o, p.out.w->wT, D, D, EPI_F16, tr.dao, D));
     if (i % 2 == 0) RET_IF(op->attn_spatial_bwd(b.q, b.k, b.v, tr.dao, NB, h->heads, P, D, h->rope_s.cs_dev, tr.g_qkv, h->err_flag, s));
     else RET_IF(op->attn_temporal_bwd(b.q, b.k, tr.dao, B, P, D, T, h->maxT, h->rope_t.cs_dev, tr.g_qkv, h->err_flag, s));
-    RET_IF(gemm_dw(tr.g_qkv, 3 * D, b.xnA, D, p.qkv.w->grad, 3));
-    if (defer_bias) {
+    RET_IF(linear_dw(p.qkv, tr.g_qkv, 3 * D, b.xnA, D, 3));
+    if (defer_bias && !lora) {
         const float* wsv[3] = {ws_fc2, ws_out, ws_fc1};
         float* dbv[3] = {p.fc2.b->grad, p.out.b->grad, p.fc1.b->grad};
         const int spv[3] = {NB, NB, gelu_bwd_colsum_splits(M)}, nv[3] = {D, D, Hp};
@@ -598,12 +740,16 @@ int TrainBackward::half_block(int i) {
     RET_IF(flush_dw());
     RET_IF(gemm_dx(tr.g_qkv, p.qkv.w->wT, D, 3 * D, EPI_F32, tr.dtmp, D));
     RET_IF(ln_bwd(tr.dtmp, tr.res[2 * i], mb + D, 1, dmb, dmb + D));
+    // a LoRA handle: the adaLN projections are frozen, and block 0 is the last bucket the data-parallel harness reduces (train.gradient_buckets), so the
+    // overflow publish of the backward pass lands here, in a blocks.0 adapter gradient, at the end of the last half-block differentiated
+    if (lora) return i == 0 ? launch_overflow_publish(h->err_flag, p.qkv.la->grad, s) : 0;
     // all six dmod chunks of this half-block are in place: its adaLN projection's gradients
     return ada_grads((size_t)i * 6 * D, 6 * D, p.ada.w, p.ada.b);
 }
 
 // ---- phase L + 1: patch embedding: r_0 = xp W_pe^T + b_pe ----
 int TrainBackward::embedders() {
+    if (lora) return 0;   // the patch embedding and the conditioning path are frozen (the overflow publish: half_block(0))
     const int ldhc = D + h->Apad;
     op = &h->ops(2 * L);
     RET_IF(launch_colsum_f32(tr.dres, D, M, D, tr.pe.b->grad, tr.red_ws, s));
@@ -676,6 +822,7 @@ int gtav_dit_train_param_range(gtav_dit* h, const char* prefix, int64_t* offset,
         last_end = o + n;
         cnt += n;
     }
+    if (off < 0 && h->tr.lora.rank) { *offset = 0; *count = 0; return 0; }   // a frozen prefix of a LoRA handle ("final_layer.", the embedders): an empty bucket
     GTAV_REQUIRE(off >= 0, "train_param_range: no trainable parameter starts with '%s'", prefix);
     *offset = off;
     *count = cnt;
@@ -698,6 +845,8 @@ int gtav_dit_adamw_step(gtav_dit* h, float lr, float beta1, float beta2, float e
     for (int ty = 0; ty < 2; ++ty)
         if (tr.adam_n[ty])
             RET_IF(operand_ops(ty != 0).adamw_multi(tr.adam_params, tr.adam_items + (ty ? tr.adam_n[0] : 0), tr.adam_n[ty], tr.ctl, lr, beta1, beta2, eps, weight_decay, s));
+    // a LoRA handle: the step moved the adapters only; every adapted weight's two images = clamp(W0 + s B A) again, one launch over all their tiles
+    if (tr.lora.rank) RET_IF(train_lora_merge_all(h, s));
     RET_IF(launch_add_f32(h->b_t2, h->b_ext, h->b_t2a, h->D, s));   // fused bias of c when actions are given (gtav_dit_finalize)
     h->prepared.valid = false;
     h->kvrec.valid = false;

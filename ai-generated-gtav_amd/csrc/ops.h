@@ -150,6 +150,23 @@ int launch_err_fold(int* words, int* sticky, int dst_word, int n_groups, hipStre
 int launch_clip_coef(float* ctl, const float* part, int nparts, float inv_scale, float max_norm, float beta1, float beta2, int* err_flag, hipStream_t stream);
 int launch_adamw(float* p, int ldp, int R, int C, const float* g, float* m, float* v, const float* ctl, float lr, float beta1, float beta2, float eps,
                  float wd, hipStream_t stream);
+// Low-rank adapters (ops_typed.inc launch_lora_grads): the planning of the gradient launches, pure host arithmetic.  The contraction over the M token rows is
+// cut into at most LORA_MAX_SPLITS runs of whole 128-row tiles; every run stores a partial [N + K][r] result which a second pass adds in run order.
+// Workspace, in floats: t^T and u^T as 2-byte [r][round_up(M, 128)] each (r * round_up(M, 128) floats together), the adapters rounded to the operand type, A^ [r][K]
+// and B^^T [r][N] (r (N + K) / 2 floats), then splits x (N + K) x r partial sums.
+constexpr int LORA_MAX_SPLITS = 16;
+inline bool lora_rank_ok(int r) { return r == 16 || r == 32 || r == 64; }
+inline int lora_grads_splits(int M) {
+    const int tiles = cdiv(M, 128), s0 = tiles < LORA_MAX_SPLITS ? tiles : LORA_MAX_SPLITS;
+    return cdiv(tiles, cdiv(tiles, s0));   // (no run is empty)
+}
+inline size_t lora_grads_workspace(int M, int N, int K, int r) {
+    return (size_t)r * round_up(M, 128) + (size_t)r * (N + K) / 2 + (size_t)lora_grads_splits(M) * (size_t)(N + K) * r;
+}
+// ... of a handle that serves every M <= Mmax (the run count is not monotonic in M: 16 tiles are 16 runs, 17 tiles 6 runs of 3)
+inline size_t lora_grads_workspace_upto(int Mmax, int N, int K, int r) {
+    return (size_t)r * round_up(Mmax, 128) + (size_t)r * (N + K) / 2 + (size_t)LORA_MAX_SPLITS * (size_t)(N + K) * r;
+}
 
 // ---- attention.hip -----------------------------------------------------------------------
 bool attn_spatial_wants_prescaled_q(int S);

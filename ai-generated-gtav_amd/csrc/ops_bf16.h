@@ -42,6 +42,9 @@ namespace gtav {
     F(attn_spatial_bwd, launch_attn_spatial_bwd)            \
     F(attn_temporal_bwd, launch_attn_temporal_bwd)          \
     F(adamw_multi, launch_adamw_multi)                      \
+    F(lora_merge, launch_lora_merge)                        \
+    F(lora_merge_one, launch_lora_merge_one)                \
+    F(lora_grads, launch_lora_grads)                        \
     F(branch_rows, launch_branch_rows)
 
 // One set of launchers per operand type; the signatures are the fp16 ones (the bf16 set casts 2-byte pointers and parameter structs: api.hip twin_call).

@@ -108,6 +108,25 @@ static_assert(sizeof(AdamItem) == 8, "AdamItem: every build and both operand typ
 // norm, [4] applied steps (the Adam step count), [5] / [6] bias corrections of the step being applied (written by clip_coef on the device)
 int launch_adamw_multi(const AdamParam* params, const AdamItem* items, int n_items, const float* ctl, float lr, float beta1, float beta2, float eps, float wd,
                        hipStream_t stream);
+// Low-rank adapters (train.hip, DESIGN.md 7 "Low-rank adapters"): W = W0 + s B A for every adapted Linear, one work item per 64 x 64 tile of W (N, K % 64 == 0).
+struct LoraMergeParam {
+    const float* w0; const float* a; const float* b;   // frozen fp32 master [N][K], A [r][K], B [N][r]
+    int N, K, r; float s;
+    f16* w16; int Cp16;                    // tile-major 2-byte W (logical row length Cp16)
+    f16* wT; int RpT;                      // tile-major 2-byte W^T (logical row length RpT = round_up(N, 64)), or null
+    float* w32;                            // launch_lora_merge_one(export_f32): the fp32 sum itself, contiguous [N][K]
+};
+static_assert(sizeof(LoraMergeParam) == 80, "LoraMergeParam: every build and both operand types must see the same struct");
+struct LoraMergeItem { int param; unsigned tile; };   // tile index, row-major over 64 x 64 tiles
+static_assert(sizeof(LoraMergeItem) == 8, "LoraMergeItem: every build and both operand types must see the same struct");
+// (f16)clamp(W0 + s B A) into both images of every item's tile / the fp32 sum into w32: one device function, the same fp32 value (train.hip has the contract)
+int launch_lora_merge(const LoraMergeParam* params, const LoraMergeItem* items, int n_items, hipStream_t stream);
+// one Linear by value: its two images (export_f32 == 0) or the fp32 sum into P.w32
+int launch_lora_merge_one(const LoraMergeParam& P, int export_f32, hipStream_t stream);
+// dB [N][r] += s dY^T (X A^T), dA [r][K] += s (dY B)^T X over the M token rows of the tile-major X [M][K], dY [M][N] (pad rows up to 128 are never used);
+// ws: lora_grads_workspace(M, N, K, r) floats (ops.h).  Fixed-order sums, no atomics; err_flag: ERR_F16_SAT when t = X A^T or u = dY B saturated.
+int launch_lora_grads(const f16* X, const f16* dY, const float* A, const float* B, int M, int N, int K, int r, float s, float* dA, float* dB, float* ws,
+                      size_t ws_floats, int* err_flag, hipStream_t stream);
 
 // ---- attention.hip -----------------------------------------------------------------------
 // Full (non-causal) attention over S tokens per (nb, head), head_dim 64 (model/attention.py:127-129, model/vae.py:101).

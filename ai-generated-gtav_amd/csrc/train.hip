@@ -1618,6 +1618,233 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamParam* __res
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------------
+// Low-rank adapters (DESIGN.md 7 "Low-rank adapters"): every adapted Linear computes with W = W0 + s B A, W0 [N][K] frozen, A [r][K] and B [N][r] trained in
+// fp32, r = 16 / 32 / 64.  The forward and the dX GEMMs read the 2-byte images of W only, so the adapters reach them by rewriting those images (the merge, a
+// twin of the GEMM-weight branch of adamw_multi_kernel) and cost the forward nothing.
+//
+// Merge contract, per element: acc = 0; for k = 0 .. r - 1 ascending: acc = fmaf(B[n][k], A[k][c], acc); w = fmaf(s, acc, W0[n][c]) in fp32.  The image entry
+// stores (f16)fmed3(w, +-max) exactly as set_weight / AdamW do; the export entry stores w itself.  Both are this ONE device function, so an fp32 export sent
+// through set_weight of another handle gives that handle the same image bits.
+// One block = one 64 x 64 tile (N % 64 == 0 and K % 64 == 0: every tile is interior).  Every global load of a thread (4 float4 of W0, r / 16 float4 of each of
+// A and B) comes before its first global store (adamw_multi_kernel's rule: a load behind a store waits for the store's round trip).
+// ------------------------------------------------------------------------------------------------------------------------
+template <bool EXPORT>
+__device__ __forceinline__ void lora_merge_tile(const LoraMergeParam& P, unsigned tile) {
+    __shared__ float sB[64][65];           // B rows r0 .. r0 + 63 (pitch 65: the four rows a wave reads per k fall into different banks)
+    __shared__ __attribute__((aligned(16))) float sA[64][64];   // A columns c0 .. c0 + 63
+    __shared__ __attribute__((aligned(16))) f16 t[64][72];
+    const int tiles_c = P.K >> 6, r = P.r, nq = r >> 4;   // nq float4 of A and of B per thread
+    const int r0 = (int)(tile / tiles_c) * 64, c0 = (int)(tile % tiles_c) * 64;
+    f32x4 w4[4], a4[4], b4[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int q = threadIdx.x + 256 * k, row = q >> 4, c4 = (q & 15) * 4;
+        w4[k] = *(const f32x4*)(P.w0 + (size_t)(r0 + row) * P.K + c0 + c4);
+        if (k < nq) {
+            a4[k] = *(const f32x4*)(P.a + (size_t)row * P.K + c0 + c4);          // A[row][c0 + c4 ..], row < 16 nq = r
+            b4[k] = *(const f32x4*)(P.b + (size_t)r0 * r + (size_t)q * 4);       // the 64 rows of B are one contiguous run of 64 r floats
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (k < nq) {
+            const int q = threadIdx.x + 256 * k, row = q >> 4, c4 = (q & 15) * 4;
+            *(f32x4*)&sA[row][c4] = a4[k];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { const int i = q * 4 + e; sB[i / r][i % r] = b4[k][e]; }
+        }
+    }
+    __syncthreads();
+    f32x4 acc[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int row0 = threadIdx.x >> 4, c4 = (threadIdx.x & 15) * 4;
+    for (int kk = 0; kk < r; ++kk) {       // k ascending, one fmaf per term: the contract
+        const f32x4 av = *(const f32x4*)&sA[kk][c4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float bv = sB[row0 + 16 * k][kk];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[k][e] = __builtin_fmaf(bv, av[e], acc[k][e]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int row = row0 + 16 * k;
+        f32x4 w;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) w[e] = __builtin_fmaf(P.s, acc[k][e], w4[k][e]);
+        if constexpr (EXPORT) {
+            *(f32x4*)(P.w32 + (size_t)(r0 + row) * P.K + c0 + c4) = w;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) t[row][c4 + e] = (f16)__builtin_amdgcn_fmed3f(w[e], -F16_MAX, F16_MAX);
+        }
+    }
+    if constexpr (!EXPORT) {
+        __syncthreads();
+        for (int q = threadIdx.x; q < 512; q += 256) {     // the two images, as adamw_multi_kernel writes them
+            const int a = q >> 3, ch = q & 7;
+            *(uint4*)(P.w16 + tiled_off(r0 + a, c0 + 8 * ch, P.Cp16)) = *(const uint4*)&t[a][8 * ch];
+            if (P.wT) {
+                union { f16 h[8]; uint4 u; } o;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) o.h[i] = t[8 * ch + i][a];
+                *(uint4*)(P.wT + tiled_off(c0 + a, r0 + 8 * ch, P.RpT)) = o.u;
+            }
+        }
+    }
+}
+__global__ __launch_bounds__(256) void lora_merge_kernel(const LoraMergeParam* __restrict__ params, const LoraMergeItem* __restrict__ items) {
+    const LoraMergeItem it = items[blockIdx.x];
+    lora_merge_tile<false>(params[it.param], it.tile);
+}
+// one Linear, descriptor by value, blockIdx.x = tile: a weight upload that re-merges its Linear, and the fp32 export (EXPORT)
+template <bool EXPORT>
+__global__ __launch_bounds__(256) void lora_merge_one_kernel(const LoraMergeParam P) { lora_merge_tile<EXPORT>(P, blockIdx.x); }
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Low-rank gradient of one Linear, four launches (lora_grads_workspace in ops.h lays out the workspace):
+//   0. lora_prep_kernel    A [r][K] and B [N][r] rounded to nearest into the operand type as A^ [r][K] and B^^T [r][N]: both row-major along the contraction of
+//                          the next launch, which reads them as 16-byte MFMA fragments straight from memory (they stay in L2: at most 640 KB).
+//   1. lora_tu_kernel      t = X A^^T and u = dY B^, [M][r] each, fp32 accumulation on the K = 32 MFMA, stored ONCE as 2-byte values (round to nearest,
+//                          saturate and flag) TRANSPOSED, [r][LDt] with LDt = round_up(M, 128), so that the next launch reads them along the token rows.
+//                          A block takes 32 token rows; its four waves take every fourth 64-column step of the contraction (no barrier in the loop, four times
+//                          the waves in flight of a block that owns its rows alone: the launch is bound by the latency of streaming X / dY) and their partial
+//                          accumulators are added through LDS in wave order.  blockIdx.y picks t or u.  Rows >= M are stored as zeros, whatever their
+//                          (undefined) inputs gave.
+//   2. lora_grad_kernel    G[c][j] = sum_m Z[m][c] tu[m][j] for the N + K columns c of Z = [dY | X] (tu = t under dY: dB; u under X: dA^T) — the contraction
+//                          over the token rows, with the K = 16 MFMA.  A block takes 64 columns and one of `splits` runs of 128-row tiles; a tile (16 KiB,
+//                          contiguous in the tile-major image) is copied into LDS as it lies, rows >= M as zeros, and the A operand (16 columns x 16 rows) is a
+//                          transposing LDS read of it.  Each block stores its partial G with plain stores: no float atomics.
+//   3. lora_reduce_kernel  adds the partials of every element in split order, multiplies by s and ADDS to dB [N][r] / dA [r][K].
+// ------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void lora_prep_kernel(const float* __restrict__ A, const float* __restrict__ B, int N, int K, int r, f16* __restrict__ Ah,
+                                                        f16* __restrict__ BhT) {
+    const int nA = r * K, total = nA + r * N;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+        const int i = idx - nA;
+        const float v = idx < nA ? A[idx] : B[(size_t)(i % N) * r + i / N];         // B^^T[j][n] = B[n][j]
+        const f16 h = (f16)__builtin_amdgcn_fmed3f(v, -F16_MAX, F16_MAX);
+        if (idx < nA) Ah[idx] = h;
+        else BhT[i] = h;
+    }
+}
+
+template <int R16>
+__global__ __launch_bounds__(256) void lora_tu_kernel(const f16* __restrict__ X, const f16* __restrict__ dY, const f16* __restrict__ Ah, const f16* __restrict__ BhT,
+                                                      int M, int N, int K, int LDt, f16* __restrict__ tT, f16* __restrict__ uT, int* err_flag) {
+    __shared__ f32x4 red[4][2 * R16][64];  // the four waves' partial accumulators
+    const bool is_u = blockIdx.y != 0;
+    const f16* Z = is_u ? dY : X;
+    const f16* Wh = is_u ? BhT : Ah;       // [r][Cz]
+    const int Cz = is_u ? N : K;
+    f16* out = is_u ? uT : tT;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
+    const int m0 = blockIdx.x * 32;
+    f32x4 acc[2][R16];
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+        for (int jt = 0; jt < R16; ++jt) acc[rt][jt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 2
+    for (int kt = w; kt < (Cz >> 6); kt += 4) {
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            const int k0 = 64 * kt + 32 * ks + 8 * g;
+            f16x8 za[2];
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt) za[rt] = *(const f16x8*)(Z + tiled_off(m0 + 16 * rt + c, k0, Cz));
+#pragma unroll
+            for (int jt = 0; jt < R16; ++jt) {
+                const f16x8 wb = *(const f16x8*)(Wh + (size_t)(16 * jt + c) * Cz + k0);
+#pragma unroll
+                for (int rt = 0; rt < 2; ++rt) acc[rt][jt] = mfma16(za[rt], wb, acc[rt][jt], 0, 0, 0);
+            }
+        }
+    }
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+        for (int jt = 0; jt < R16; ++jt) red[w][rt * R16 + jt][lane] = acc[rt][jt];
+    __syncthreads();
+    float amax = 0.f;
+    for (int id = threadIdx.x; id < 2 * R16 * 64; id += 256) {
+        const int q = id >> 6, l = id & 63, rt = q / R16, jt = q % R16;
+        const f32x4 v4 = ((red[0][q][l] + red[1][q][l]) + red[2][q][l]) + red[3][q][l];   // wave order: fixed
+        const int row = m0 + 16 * rt + 4 * (l >> 4);   // accumulator layout: rows row .. row + 3 of column j = 16 jt + (l & 15)
+        float v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = row + e < M ? v4[e] : 0.f;
+        *(f16x4*)(out + (size_t)(16 * jt + (l & 15)) * LDt + row) = sat4(v[0], v[1], v[2], v[3], amax);
+    }
+    sat_report(amax, err_flag);
+}
+
+template <int R16>
+__global__ __launch_bounds__(256) void lora_grad_kernel(const f16* __restrict__ X, const f16* __restrict__ dY, const f16* __restrict__ tT, const f16* __restrict__ uT,
+                                                        int M, int N, int K, int LDt, int tiles_per_split, float* __restrict__ part) {
+    constexpr int r = 16 * R16;
+    __shared__ __attribute__((aligned(16))) f16 sZ[128 * 64];   // one tile of the tile-major image, as it lies (chunk ch of row m at ch ^ (m & 7))
+    const int cb = blockIdx.x, nbY = N >> 6;
+    const bool is_x = cb >= nbY;
+    const f16* Z = is_x ? X : dY;
+    const f16* tu = is_x ? uT : tT;
+    const int Cz = is_x ? K : N, ct = is_x ? cb - nbY : cb;    // column tile inside Z
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
+    const int ntiles = LDt >> 7, t_begin = blockIdx.y * tiles_per_split, t_end = t_begin + tiles_per_split < ntiles ? t_begin + tiles_per_split : ntiles;
+    f32x4 acc[R16];
+#pragma unroll
+    for (int jt = 0; jt < R16; ++jt) acc[jt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // transposing read of the swizzled tile: lane 4 q + p' of a 16-lane group passes row 4 g + q, columns 16 w + 4 p' .. of the 16-row step
+    const int trow = 4 * g + (c >> 2), tcol = 16 * w + 4 * (c & 3);
+    uint4 stage[4];
+    auto load_tile = [&](int tile) {
+        const uint4* src = (const uint4*)(Z + ((size_t)tile * (Cz >> 6) + ct) * 8192);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int i = threadIdx.x + 256 * k;               // 16-byte chunk i of the tile: row i >> 3
+            stage[k] = tile * 128 + (i >> 3) < M ? src[i] : uint4{0, 0, 0, 0};
+        }
+    };
+    if (t_begin < t_end) load_tile(t_begin);
+    for (int tile = t_begin; tile < t_end; ++tile) {
+        __syncthreads();                   // the previous tile's reads are done
+#pragma unroll
+        for (int k = 0; k < 4; ++k) ((uint4*)sZ)[threadIdx.x + 256 * k] = stage[k];
+        __syncthreads();
+        if (tile + 1 < t_end) load_tile(tile + 1);
+#pragma unroll
+        for (int ms = 0; ms < 8; ++ms) {
+            const int m = 16 * ms + trow;
+            const f16x4 za = lds_read_tr(sZ + m * 64 + ((((tcol >> 3) & 7) ^ (m & 7)) << 3) + (tcol & 7));   // A[row = column 16 w + c][k = token row 16 ms + 4 g + e]
+#pragma unroll
+            for (int jt = 0; jt < R16; ++jt) {
+                const f16x4 tb = *(const f16x4*)(tu + (size_t)(16 * jt + c) * LDt + tile * 128 + 16 * ms + 4 * g);   // B[k = token row ..][col = j]
+                acc[jt] = mfma16k16(za, tb, acc[jt]);
+            }
+        }
+    }
+    // partial G of this split: rows = columns of Z (cb * 64 + 16 w + 4 g + e), column j = 16 jt + c
+    float* dst = part + ((size_t)blockIdx.y * (N + K) + (size_t)cb * 64 + 16 * w + 4 * g) * r;
+#pragma unroll
+    for (int jt = 0; jt < R16; ++jt)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) dst[(size_t)e * r + 16 * jt + c] = acc[jt][e];
+}
+
+__global__ __launch_bounds__(256) void lora_reduce_kernel(const float* __restrict__ part, int splits, int N, int K, int r, float s, float* __restrict__ dA,
+                                                          float* __restrict__ dB) {
+    const size_t total = (size_t)(N + K) * r, idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    float sum = 0.f;
+    for (int sp = 0; sp < splits; ++sp) sum += part[(size_t)sp * total + idx];   // split order: fixed
+    const int cg = (int)(idx / r), j = (int)(idx % r);
+    if (cg < N) dB[idx] += s * sum;                                            // dB [N][r]
+    else dA[(size_t)j * K + (cg - N)] += s * sum;                              // dA [r][K] (G holds its transpose)
+}
+
 static int grid_for(size_t n, int block = 256) { return (int)((n + block - 1) / block < 4096 ? (n + block - 1) / block : 4096); }
 
 }  // namespace
@@ -1908,6 +2135,54 @@ int launch_adamw_multi(const AdamParam* params, const AdamItem* items, int n_ite
     GTAV_CHECK_HIP(hipGetLastError());
     return 0;
 }
+// ---- low-rank adapters (the kernels' comments above; ops.h lora_grads_*) ----
+static int lora_merge_check(const LoraMergeParam& P) {
+    GTAV_REQUIRE(P.w0 && P.a && P.b && lora_rank_ok(P.r) && P.N >= 64 && P.K >= 64 && P.N % 64 == 0 && P.K % 64 == 0,
+                 "lora_merge: N=%d K=%d rank %d (N and K multiples of 64, rank 16, 32 or 64)", P.N, P.K, P.r);
+    return 0;
+}
+int launch_lora_merge(const LoraMergeParam* params, const LoraMergeItem* items, int n_items, hipStream_t stream) {
+    GTAV_REQUIRE(params && items && n_items >= 1, "lora_merge: %d work items", n_items);
+    hipLaunchKernelGGL(lora_merge_kernel, dim3(n_items), dim3(256), 0, stream, params, items);
+    GTAV_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+int launch_lora_merge_one(const LoraMergeParam& P, int export_f32, hipStream_t stream) {
+    if (int rc = lora_merge_check(P)) return rc;
+    GTAV_REQUIRE(export_f32 ? P.w32 != nullptr : P.w16 != nullptr, "lora_merge_one: null destination");
+    const dim3 grid((unsigned)((P.N >> 6) * (P.K >> 6)));
+    if (export_f32) hipLaunchKernelGGL(lora_merge_one_kernel<true>, grid, dim3(256), 0, stream, P);
+    else hipLaunchKernelGGL(lora_merge_one_kernel<false>, grid, dim3(256), 0, stream, P);
+    GTAV_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+int launch_lora_grads(const f16* X, const f16* dY, const float* A, const float* B, int M, int N, int K, int r, float s, float* dA, float* dB, float* ws,
+                      size_t ws_floats, int* err_flag, hipStream_t stream) {
+    GTAV_REQUIRE(X && dY && A && B && dA && dB && ws, "lora_grads: null argument");
+    GTAV_REQUIRE(lora_rank_ok(r), "lora_grads: rank %d (16, 32 or 64)", r);
+    GTAV_REQUIRE(M >= 1 && N >= 64 && K >= 64 && N % 64 == 0 && K % 64 == 0, "lora_grads: M=%d N=%d K=%d (N and K multiples of 64)", M, N, K);
+    GTAV_REQUIRE(ws_floats >= lora_grads_workspace(M, N, K, r), "lora_grads: the workspace holds %zu floats, M=%d N=%d K=%d rank %d needs %zu", ws_floats, M, N, K, r,
+                 lora_grads_workspace(M, N, K, r));
+    const int LDt = round_up(M, 128), splits = lora_grads_splits(M), tps = cdiv(LDt / 128, splits);
+    f16* tT = (f16*)ws;                    // (ops.h lora_grads_workspace: t^T, u^T, A^, B^^T as 2-byte values, then the partial sums)
+    f16* uT = tT + (size_t)r * LDt;
+    f16* Ah = uT + (size_t)r * LDt;
+    f16* BhT = Ah + (size_t)r * K;
+    float* part = ws + (size_t)r * LDt + (size_t)r * (N + K) / 2;
+    const dim3 g1(LDt / 32, 2), g2((N + K) / 64, splits);
+    hipLaunchKernelGGL(lora_prep_kernel, dim3((unsigned)cdiv(r * (N + K), 1024)), dim3(256), 0, stream, A, B, N, K, r, Ah, BhT);
+#define GTAV_LORA_R(R16)                                                                                                                              \
+    case 16 * R16:                                                                                                                                    \
+        hipLaunchKernelGGL(lora_tu_kernel<R16>, g1, dim3(256), 0, stream, X, dY, (const f16*)Ah, (const f16*)BhT, M, N, K, LDt, tT, uT, err_flag);   \
+        hipLaunchKernelGGL(lora_grad_kernel<R16>, g2, dim3(256), 0, stream, X, dY, (const f16*)tT, (const f16*)uT, M, N, K, LDt, tps, part);         \
+        break
+    switch (r) { GTAV_LORA_R(1); GTAV_LORA_R(2); GTAV_LORA_R(4); }
+#undef GTAV_LORA_R
+    hipLaunchKernelGGL(lora_reduce_kernel, dim3((unsigned)cdiv((N + K) * r, 256)), dim3(256), 0, stream, (const float*)part, splits, N, K, r, s, dA, dB);
+    GTAV_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 int launch_adamw(float* p, int ldp, int R, int C, const float* g, float* m, float* v, const float* ctl, float lr, float beta1, float beta2, float eps,
                  float wd, hipStream_t stream) {
     hipLaunchKernelGGL(adamw_kernel, dim3(grid_for((size_t)R * C)), dim3(256), 0, stream, p, ldp, R, C, g, m, v, ctl, lr, beta1, beta2, eps, wd);

@@ -75,6 +75,8 @@ SIGNATURES = {
     "gtav_dit_train_set_recompute": [_p, _i],
     "gtav_dit_train_saved_bytes": [_p, C.POINTER(C.c_int64)],
     "gtav_dit_train_allow_mixed": [_p, _i],
+    "gtav_dit_train_set_lora": [_p, _i, _f],
+    "gtav_dit_lora_get_merged": [_p, C.c_char_p, _p, _l, _p],
     "gtav_dit_train_set_group_dtype": [_p, _i, _i, _p],
     "gtav_dit_train_range_words": [_p, C.POINTER(C.c_int32), _p],
     "gtav_dit_train_autorange": [_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _p],
@@ -183,6 +185,9 @@ SIGNATURES = {
     # the deferred-residual LayerNorm with every LnPending field flat, and the branch image launch (include/gtav_amd_testing.h)
     "gtav_op_ln_pending": [_i, _p, _i, _p, _i, _i, _p, _p, _i, _p, _i, _p, _i, _l, _i, _p, _p, _i, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p],
     "gtav_op_branch_rows": [_p, _i, _l, _i, _p, _p, _i, _i, _p, _p],
+    # low-rank adapters: the gradient of one Linear and the merge of one Linear (kernel-level entry points of include/gtav_amd.h)
+    "gtav_op_lora_grads": [_p, _p, _p, _p, _i, _i, _i, _i, _f, _p, _p, _p, _l, _p, _p],
+    "gtav_op_lora_merge": [_p, _p, _p, _i, _i, _i, _f, _p, _p, _p, _p],
 }
 _RESTYPES = {"gtav_last_error": C.c_char_p, "gtav_dit_destroy": None, "gtav_vae_destroy": None, "gtav_op_gemm_set_stages": None,
              "gtav_op_gemm_set_wm": None, "gtav_op_set_operand_dtype": None}

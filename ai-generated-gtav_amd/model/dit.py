@@ -149,7 +149,8 @@ class DiT(_HipModule):
 
     def __init__(self, input_h=18, input_w=32, patch_size=2, in_channels=16, hidden_size=1024, depth=12, num_heads=16,
                  mlp_ratio=4.0, external_cond_dim=25, max_frames=5, *, max_batch=1, init_weights=True, trainable=False, range_policy="report",
-                 train_dtype=torch.float16, train_max_frames=None, train_recompute=False, train_range_policy="report"):
+                 train_dtype=torch.float16, train_max_frames=None, train_recompute=False, train_range_policy="report", train_lora_rank=None,
+                 train_lora_alpha=None):
         super().__init__()
         self._trainable = bool(trainable)    # keyword-only, not in the reference: keeps fp32 masters, gradients and AdamW state on the GPU
         # opt-in to training windows of up to train_max_frames frames (include/gtav_amd.h gtav_dit_train_allow_window); None: TRAIN_MAX_FRAMES.  The saved
@@ -183,6 +184,27 @@ class DiT(_HipModule):
         if train_range_policy == "auto" and not self._trainable:
             raise ValueError("train_range_policy='auto' needs trainable=True (an inference model has range_policy)")
         self.train_range_policy = train_range_policy
+        # opt-in to low-rank adapter training on a frozen backbone (include/gtav_amd.h gtav_dit_train_set_lora): every half-block's to_qkv / to_out / fc1 / fc2 computes
+        # with W0 + (alpha / rank) B A, the adapter pairs lora_A (rank, K) / lora_B (N, rank) are the only trainable parameters (grad, param_range, grad_arena and the
+        # optimizer state see them alone); state_dict() / load_state_dict() mean the frozen base, lora_state_dict() / load_lora_state_dict() the adapters,
+        # merged_state_dict() the reference-layout weights with the adapters folded in.  alpha defaults to the rank (scale 1)
+        if train_lora_rank is None and train_lora_alpha is not None:
+            raise ValueError("train_lora_alpha needs train_lora_rank")
+        if train_lora_rank is not None:
+            if not self._trainable:
+                raise ValueError("train_lora_rank needs trainable=True (the adapters exist for the training step; run inference from merged_state_dict())")
+            if int(train_lora_rank) != train_lora_rank or int(train_lora_rank) not in _w.LORA_RANKS:
+                raise ValueError(f"train_lora_rank={train_lora_rank}: the adapters fill whole MFMA tiles, rank must be one of {_w.LORA_RANKS}")
+            if train_range_policy == "auto":
+                raise ValueError("train_lora_rank together with train_range_policy='auto' is not implemented (a type switch remakes the weight images from the "
+                                 "fp32 masters, without the adapters)")
+            train_lora_alpha = float(train_lora_rank if train_lora_alpha is None else train_lora_alpha)
+            if not (train_lora_alpha > 0.0 and math.isfinite(train_lora_alpha)):
+                raise ValueError(f"train_lora_alpha={train_lora_alpha}: a positive number")
+        self._lora_rank = None if train_lora_rank is None else int(train_lora_rank)
+        self._lora_alpha = train_lora_alpha
+        self._lora_sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+        self._lora_host_fresh = True         # the host copies of the adapters are the truth (until an optimizer step moves the handle's)
         self._grads = None
         self._loss_scale = 1.0 if self._train_bf16 else 65536.0
         self.in_channels = in_channels
@@ -213,6 +235,8 @@ class DiT(_HipModule):
                              "layers to bf16 operands and raises GtavRangeSwitch: recompute)")
         if init_weights:
             self.initialize_weights()
+        if self._lora_rank:
+            self.init_lora()
 
     @property
     def _train_window(self):
@@ -238,6 +262,13 @@ class DiT(_HipModule):
 
     def _shapes(self):
         return _w.dit_param_shapes(**self._cfg_kwargs)
+
+    def _lora_shapes(self):
+        return _w.lora_param_shapes(self._lora_rank, **self._cfg_kwargs)
+
+    def _train_shapes(self):
+        """The trainable parameters: every parameter, or on a LoRA model the adapters alone."""
+        return self._lora_shapes() if self._lora_rank else self._shapes()
 
     def _extra_state(self):
         # same de-duplicated aliases the reference's own writer keeps (train_dit.py:758-762)
@@ -308,6 +339,8 @@ class DiT(_HipModule):
                     for g in sorted(self._bf16_groups):                  # a re-created handle keeps the operand types chosen before
                         _lib.check(L.gtav_dit_set_operand_dtype(self._handle, g, 1))
                 if self._trainable:
+                    if self._lora_rank:                                  # (first: the adapters are then what train_param_count counts)
+                        _lib.check(L.gtav_dit_train_set_lora(self._handle, self._lora_rank, self._lora_alpha))
                     n = C.c_int64(0)
                     _lib.check(L.gtav_dit_train_param_count(self._handle, C.byref(n)))
                     # one contiguous fp32 gradient arena owned by torch: a single all-reduce covers the whole model (train.py)
@@ -330,13 +363,18 @@ class DiT(_HipModule):
                     if self.grad_divisor != 1.0:
                         _lib.check(L.gtav_dit_set_grad_divisor(self._handle, self.grad_divisor))
             self._dirty = True
+            self._lora_host_fresh = True     # (a new handle holds no adapters yet: the host copies are all there is)
         if self._dirty:
+            if self._lora_rank and not self._lora_host_fresh:            # the re-upload below sends the adapters too: the trained ones, not the stale host copies
+                self._pull_lora()
             gh, gw = self.input_h // self.patch_size, self.input_w // self.patch_size
             sc, ss = _rope_tables_axial(self._spatial_freqs, gh, gw)
             tc, ts = _rope_tables_temporal(self._temporal_freqs, self._capacity_t)
             extra = {"tables.timestep_sincos": _timestep_table(), "tables.rope_spatial_cos": sc, "tables.rope_spatial_sin": ss,
                      "tables.rope_temporal_cos": tc, "tables.rope_temporal_sin": ts}
+            extra.update(self._lora_sd)
             self._upload(extra)
+            self._lora_host_fresh = True
             if self._schedule is not None:
                 self.set_schedule(self._schedule)
 
@@ -523,8 +561,11 @@ class DiT(_HipModule):
             _lib.check(_lib.load().gtav_dit_set_loss_scale(self._handle, self._loss_scale))
 
     def grad(self, name: str) -> torch.Tensor:
-        """Unscaled gradient of one parameter in its state-dict shape."""
-        shp = self._shapes()[name]
+        """Unscaled gradient of one trainable parameter in its state-dict shape (a LoRA model: of an adapter; the base is frozen and refused by name)."""
+        shapes = self._train_shapes()
+        if name not in shapes:
+            raise _lib.GtavError(f"grad: '{name}' is not a trainable parameter" + (" (a LoRA model trains its lora_A / lora_B adapters only)" if self._lora_rank else ""))
+        shp = shapes[name]
         out = torch.empty(shp, device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().gtav_dit_get_grad(self._handle, name.encode(), out.data_ptr(), out.numel(), _lib.current_stream()))
@@ -544,6 +585,7 @@ class DiT(_HipModule):
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().gtav_dit_adamw_step(self._handle, float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
                                                        float(max_grad_norm), _lib.current_stream()))
+        self._lora_host_fresh = False
 
     def train_stats(self):
         """(step applied?, skipped steps so far, unscaled global gradient norm of the last step); synchronises."""
@@ -559,7 +601,7 @@ class DiT(_HipModule):
         L = _lib.load()
         out = {}
         with torch.cuda.device(self.device):
-            for k, shp in self._shapes().items():
+            for k, shp in self._train_shapes().items():
                 m = torch.empty(shp, device=self.device, dtype=torch.float32)
                 v = torch.empty_like(m)
                 _lib.check(L.gtav_dit_get_opt_state(self._handle, k.encode(), m.data_ptr(), v.data_ptr(), m.numel(), _lib.current_stream()))
@@ -575,7 +617,7 @@ class DiT(_HipModule):
         self._ensure(self._capacity_b, self._capacity_t)
         L = _lib.load()
         with torch.cuda.device(self.device):
-            for k, shp in self._shapes().items():
+            for k, shp in self._train_shapes().items():
                 m = state["m." + k].to(self.device, torch.float32).contiguous()
                 v = state["v." + k].to(self.device, torch.float32).contiguous()
                 if tuple(m.shape) != tuple(shp) or tuple(v.shape) != tuple(shp):
@@ -604,6 +646,99 @@ class DiT(_HipModule):
                 out = torch.empty(shp, device=self.device, dtype=torch.float32)
                 _lib.check(L.gtav_dit_get_weight(self._handle, k.encode(), out.data_ptr(), out.numel(), _lib.current_stream()))
                 self._sd[k] = out.cpu()
+
+    # ------------------------------------------------------------------------------------------
+    # low-rank adapters (train_lora_rank=...; include/gtav_amd.h gtav_dit_train_set_lora)
+    # ------------------------------------------------------------------------------------------
+    @property
+    def lora_rank(self):
+        """Rank of the adapters, None on a model without them."""
+        return self._lora_rank
+
+    @property
+    def lora_alpha(self):
+        return self._lora_alpha
+
+    def _need_lora(self, who):
+        if not self._lora_rank:
+            raise _lib.GtavError(f"{who}: this DiT has no adapters (construct it with trainable=True, train_lora_rank=16 / 32 / 64)")
+
+    def init_lora(self, seed: int = 0):
+        """The default adapters: lora_A ~ U(-1 / sqrt(K), 1 / sqrt(K)) from a CPU generator seeded with `seed` (drawn in name order), lora_B = 0, so that the
+        model starts as its base."""
+        self._need_lora("init_lora")
+        g = torch.Generator(device="cpu").manual_seed(int(seed))
+        sd = OrderedDict()
+        for k, shp in self._lora_shapes().items():
+            if k.endswith(".lora_A.weight"):
+                bound = 1.0 / math.sqrt(shp[1])
+                sd[k] = (torch.rand(shp, generator=g, dtype=torch.float32) * 2.0 - 1.0) * bound
+            else:
+                sd[k] = torch.zeros(shp, dtype=torch.float32)
+        self._set_lora(sd)
+
+    def _set_lora(self, sd):
+        """New host copies of the adapters; a handle whose other weights are in place takes them at once (the library re-merges the images)."""
+        self._lora_sd = OrderedDict((k, sd[k]) for k in self._lora_shapes())
+        self._lora_host_fresh = True
+        if self._handle and not self._dirty:
+            L, stream = _lib.load(), _lib.current_stream()
+            with torch.cuda.device(self.device):
+                for k, v in self._lora_sd.items():
+                    d = v.to(self.device, torch.float32).contiguous()
+                    _lib.check(L.gtav_dit_set_weight(self._handle, k.encode(), d.data_ptr(), d.numel(), stream))
+                _lib.check(L.gtav_dit_finalize(self._handle, stream))
+                torch.cuda.synchronize()
+
+    def _pull_lora(self):
+        L = _lib.load()
+        with torch.cuda.device(self.device):
+            for k, shp in self._lora_shapes().items():
+                out = torch.empty(shp, device=self.device, dtype=torch.float32)
+                _lib.check(L.gtav_dit_get_weight(self._handle, k.encode(), out.data_ptr(), out.numel(), _lib.current_stream()))
+                self._lora_sd[k] = out.cpu()
+        self._lora_host_fresh = True
+
+    def lora_state_dict(self) -> "OrderedDict[str, torch.Tensor]":
+        """The adapters as CPU tensors (the trained ones, copied back from the GPU when an optimizer step moved them)."""
+        self._need_lora("lora_state_dict")
+        if self._handle and not self._lora_host_fresh:
+            self._pull_lora()
+        return OrderedDict(self._lora_sd)
+
+    def load_lora_state_dict(self, sd: Dict[str, torch.Tensor]):
+        """Inverse of lora_state_dict: every adapter, nothing else, in its shape."""
+        self._need_lora("load_lora_state_dict")
+        shapes = self._lora_shapes()
+        missing = [k for k in shapes if k not in sd]
+        unexpected = [k for k in sd if k not in shapes]
+        if missing or unexpected:
+            raise RuntimeError(f"load_lora_state_dict: missing keys {missing[:5]}{'...' if len(missing) > 5 else ''}, unexpected keys "
+                               f"{unexpected[:5]}{'...' if len(unexpected) > 5 else ''}")
+        new = {}
+        for k, shp in shapes.items():
+            v = sd[k].detach().to("cpu", torch.float32).contiguous()
+            if tuple(v.shape) != tuple(shp):
+                raise RuntimeError(f"load_lora_state_dict: {k} has shape {tuple(v.shape)}, expected {tuple(shp)} (rank {self._lora_rank})")
+            new[k] = v
+        self._set_lora(new)
+
+    def merged_state_dict(self) -> "OrderedDict[str, torch.Tensor]":
+        """The reference's key layout with the adapters folded in: every adapted weight is the fp32 W0 + (alpha / rank) B A that the GPU casts into its
+        weight images (gtav_dit_lora_get_merged), everything else the frozen base.  Loaded into any DiT it computes what this model computes."""
+        self._need_lora("merged_state_dict")
+        self._ensure(self._capacity_b, self._capacity_t)
+        sd = self.state_dict()
+        L = _lib.load()
+        with torch.cuda.device(self.device):
+            for k in self._lora_shapes():
+                if not k.endswith(".lora_A.weight"):
+                    continue
+                name = k[: -len(".lora_A.weight")] + ".weight"
+                out = torch.empty(self._shapes()[name], device=self.device, dtype=torch.float32)
+                _lib.check(L.gtav_dit_lora_get_merged(self._handle, name.encode(), out.data_ptr(), out.numel(), _lib.current_stream()))
+                sd[name] = out.cpu()
+        return sd
 
     # ------------------------------------------------------------------------------------------
     # fused sampler entry (train_dit.denoise_step + generate.py:220), used by gtav_amd.generate

@@ -426,6 +426,21 @@ def save_model(dit, path: str):
     _w.save_state_dict_file(dit.state_dict(), path)
 
 
+def _lora_meta(dit):
+    """{"rank", "alpha"} of a LoRA model (DiT(train_lora_rank=...)), None for any other."""
+    rank = getattr(dit, "lora_rank", None)
+    return {"rank": int(rank), "alpha": float(dit.lora_alpha)} if rank else None
+
+
+def save_lora(dit, path: str):
+    """The adapters of a LoRA model alone as one .safetensors (a few MB beside the caller's frozen checkpoint); metadata {"rank", "alpha"}, as strings."""
+    from safetensors.torch import save_file
+    meta = _lora_meta(dit)
+    if meta is None:
+        raise _lib.GtavError("save_lora: this DiT has no adapters (construct it with trainable=True, train_lora_rank=...)")
+    save_file({k: v.contiguous() for k, v in dit.lora_state_dict().items()}, path, metadata={k: repr(v) for k, v in meta.items()})
+
+
 def _operand_dtype_name(dit) -> str:
     """step.json's "operand_dtype": the training step's operand type ("bf16" for DiT(train_dtype=torch.bfloat16), else "fp16")."""
     return "bf16" if getattr(dit, "train_dtype", torch.float16) == torch.bfloat16 else "fp16"
@@ -450,14 +465,23 @@ def _restore_groups(dit, state: dict):
 
 
 def save_state(dit, ckpt_dir: str, global_step: int, epoch: int, extra: Optional[dict] = None, rng=None):
-    """train_dit.py:765-800 `save_checkpoint`: <dir>/model.safetensors (fp32 masters), <dir>/optimizer.safetensors (AdamW moments + step
+    """A LoRA model (DiT(train_lora_rank=...)) writes <dir>/lora.safetensors (the adapters; no model.safetensors: the base is the caller's frozen checkpoint), the
+    adapters' moments and step.json with "lora": {"rank", "alpha"}; load_state restores the three into a LoRA model of the same rank, onto whatever base it holds.
+    train_dit.py:765-800 `save_checkpoint`: <dir>/model.safetensors (fp32 masters), <dir>/optimizer.safetensors (AdamW moments + step
     counters), <dir>/step.json {"step", "epoch", "loss_scale", "operand_dtype", "bf16_groups", ...}.  Rank 0 writes; the caller barriers around it like the reference.
     rng (a NoiseSource): its {"seed", "draw"} goes into step.json as "rng" — the whole noise stream of the resumed run."""
     import json
     import os
     from safetensors.torch import save_file
     os.makedirs(ckpt_dir, exist_ok=True)
-    save_model(dit, os.path.join(ckpt_dir, "model.safetensors"))
+    lora = _lora_meta(dit)
+    # a LoRA model: lora.safetensors (the adapters) in place of model.safetensors — the base is the caller's frozen checkpoint —, the adapters' moments, and
+    # step.json's "lora": {"rank", "alpha"}
+    if lora is not None:
+        save_lora(dit, os.path.join(ckpt_dir, "lora.safetensors"))
+        extra = dict(extra or {}, lora=lora)
+    else:
+        save_model(dit, os.path.join(ckpt_dir, "model.safetensors"))
     save_file({k: v.contiguous() for k, v in dit.opt_state_dict().items()}, os.path.join(ckpt_dir, "optimizer.safetensors"))
     state = _step_state(dit, global_step, epoch)
     state.update(extra or {})
@@ -478,8 +502,20 @@ def load_state(dit, ckpt_dir: str, steps_per_epoch: Optional[int] = None, gradie
     from . import weights as _w
     with open(os.path.join(ckpt_dir, "step.json")) as f:
         state = json.load(f)
+    lora, ck = _lora_meta(dit), state.get("lora")
+    if lora is not None and ck is None:
+        raise _lib.GtavError(f"load_state: {ckpt_dir} is a full checkpoint (model.safetensors, every parameter's moments) and this DiT trains rank-{lora['rank']} "
+                             "adapters on a frozen base: load its model.safetensors with load_state_dict and start the adapters afresh")
+    if lora is None and ck is not None:
+        raise _lib.GtavError(f"load_state: {ckpt_dir} is a LoRA checkpoint (rank {ck['rank']} adapters, no base weights) and this DiT trains every parameter: "
+                             f"construct it with trainable=True, train_lora_rank={ck['rank']}")
+    if lora is not None and int(ck["rank"]) != lora["rank"]:
+        raise _lib.GtavError(f"load_state: the checkpoint's adapters have rank {ck['rank']}, this DiT's rank {lora['rank']}")
     _restore_groups(dit, state)              # (first: the masters below are converted into each group's type as they are sent)
-    dit.load_state_dict(_w.load_state_dict_file(os.path.join(ckpt_dir, "model.safetensors")))
+    if lora is not None:
+        dit.load_lora_state_dict(_w.load_state_dict_file(os.path.join(ckpt_dir, "lora.safetensors")))
+    else:
+        dit.load_state_dict(_w.load_state_dict_file(os.path.join(ckpt_dir, "model.safetensors")))
     dit.load_opt_state_dict(load_file(os.path.join(ckpt_dir, "optimizer.safetensors")))
     # the loss scale belongs to the operand type it was found for: a bf16 run's scale (1 by default) would let an fp16 backward underflow, so it is restored
     # only into a handle of the same type (a checkpoint without "operand_dtype" is fp16).  The masters and moments are fp32 and load either way.

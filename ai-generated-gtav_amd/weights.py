@@ -62,6 +62,24 @@ def dit_param_shapes(input_h=18, input_w=32, patch_size=2, in_channels=16, hidde
     return s
 
 
+LORA_RANKS = (16, 32, 64)                      # whole MFMA tiles (include/gtav_amd.h gtav_dit_train_set_lora)
+LORA_LINEARS = ("attn.to_qkv", "attn.to_out", "mlp.fc1", "mlp.fc2")
+
+
+def lora_param_shapes(rank: int, **cfg_kwargs) -> Shapes:
+    """The adapter pairs of DiT(train_lora_rank=rank): for each of the four GEMM Linears of every half-block (weight (N, K)) "<linear>.lora_A.weight"
+    (rank, K) and "<linear>.lora_B.weight" (N, rank), in the lexicographic name order of the gradient arena."""
+    if int(rank) not in LORA_RANKS:
+        raise ValueError(f"lora rank {rank}: one of {LORA_RANKS}")
+    base = dit_param_shapes(**cfg_kwargs)
+    out = {}
+    for k, (n, kk) in ((k, v) for k, v in base.items() if k.startswith("blocks.") and any(k.endswith(l + ".weight") for l in LORA_LINEARS)):
+        stem = k[: -len(".weight")]
+        out[stem + ".lora_A.weight"] = (int(rank), kk)
+        out[stem + ".lora_B.weight"] = (n, int(rank))
+    return OrderedDict((k, out[k]) for k in sorted(out))
+
+
 def dit_freq_alias_names(depth: int) -> Iterable[str]:
     """The 2 + 2*depth aliases of the two shared rotary `freqs` parameters (model/dit.py:259-262)."""
     yield "spatial_rotary_emb.freqs"

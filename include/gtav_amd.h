@@ -232,7 +232,22 @@ int gtav_timer_calibrate(int32_t spin_us, int32_t reps, double* event_us_mean, d
  *       handle's own sticky words; else uses the n_groups words given.  Every fp16 group whose word holds the saturation bit is switched to bf16 (*n of them);
  *       THEN everything else in the error words — a saturation bit of a group that is bf16 already included — is reported as gtav_dit_check reports it.  The
  *       switches are done when the call fails: read the types back (gtav_dit_get_operand_dtype) after every return.
- *   gtav_dit_set_operand_dtype refuses on such a handle whatever would change a group.  All three calls fail by name on a handle without the opt-in. */
+ *   gtav_dit_set_operand_dtype refuses on such a handle whatever would change a group.  All three calls fail by name on a handle without the opt-in.
+ * Low-rank adapters (LoRA fine-tuning on a frozen backbone; DESIGN.md 7 "Low-rank adapters"): gtav_dit_train_set_lora(h, rank, alpha), called between
+ * gtav_dit_create and gtav_dit_train_enable[_typed] (it fails afterwards), adds to every half-block's four GEMM Linears (attn.to_qkv, attn.to_out, mlp.fc1,
+ * mlp.fc2; weight W0 [N][K]) the fp32 parameters "<linear>.lora_A.weight" [rank][K] and "<linear>.lora_B.weight" [N][rank].  The Linear computes with
+ * W = W0 + (alpha / rank) B A.  rank is 16, 32 or 64, alpha > 0; hidden_size and the MLP width must be multiples of 64; refused together with
+ * gtav_dit_train_allow_mixed.  On such a handle the adapters are the ONLY trainable parameters: gtav_dit_train_param_count, the gradient arena (lexicographic
+ * name order as ever), gtav_dit_train_param_range (a frozen prefix gives count 0), the AdamW moments and gtav_dit_get_grad / get_opt_state / set_opt_state
+ * (which refuse a frozen parameter by name) cover them alone; the backward pass computes the adapters' gradients in place of the weight gradients and no bias,
+ * adaLN, final-layer or embedder gradient.  gtav_dit_set_weight takes the base weights and the adapters in any order (all are required by gtav_dit_finalize);
+ * finalize, every gtav_dit_adamw_step and a later set_weight of an adapter or an adapted weight leave the 2-byte images of the adapted weights equal to
+ * clamp(W0 + s B A), so the forward costs what it costs without adapters.  gtav_dit_get_weight keeps its meaning (the frozen fp32 base, or the adapter);
+ * gtav_dit_lora_get_merged(h, "<linear>.weight", dst_dev, numel, stream) writes the fp32 W0 + s B A of one adapted weight in torch layout — sent to any other
+ * handle with gtav_dit_set_weight it gives that handle the adapted weight's image bits.  Recomputation, longer windows, both operand types, long frames and
+ * every patch geometry combine with it unchanged. */
+int gtav_dit_train_set_lora(gtav_dit* h, int32_t rank, float alpha);
+int gtav_dit_lora_get_merged(gtav_dit* h, const char* name, float* dst_dev, int64_t numel, void* stream);
 int gtav_dit_train_allow_window(gtav_dit* h, int32_t max_frames);
 int gtav_dit_train_set_recompute(gtav_dit* h, int32_t enable);
 int gtav_dit_train_allow_mixed(gtav_dit* h, int32_t enable);
@@ -489,6 +504,18 @@ int gtav_op_gemm_splitk_ln(const void* x_f16_dev, int32_t ldx, const void* w_f16
                            int32_t N, int32_t K, int32_t splitk, float* parts_dev, float* resid_dev, const float* gate_dev,
                            int32_t gate_stride, int32_t rows_per_gate, void* out_f16_dev, const float* shift_dev,
                            const float* scale_dev, int32_t mod_stride, void* stream);
+/* Low-rank adapters (csrc/train.hip; DESIGN.md 7 "Low-rank adapters"), kernel level: what a LoRA training handle launches per Linear.  Both dispatch per
+ * gtav_op_set_operand_dtype (gtav_amd_testing.h) like gtav_op_gemm_tn; the caller owns every buffer, nothing is allocated and nothing synchronises.
+ * gtav_op_lora_grads   dB [N][r] += s dY^T (X A^T), dA [r][K] += s (dY B)^T X: x / dy tile-major 2-byte [round_up(M, 128)][K] / [..][N] whose rows >= M are
+ *                      never used, a_f32 [r][K] and b_f32 [N][r] fp32 (rounded to the operand type inside), N and K multiples of 64, r 16 / 32 / 64;
+ *                      ws_floats >= r round_up(M, 128) + r (N + K) / 2 + splits (N + K) r with splits = the runs of 128-row tiles (at most 16; csrc/ops.h
+ *                      lora_grads_workspace), refused by name otherwise.  err: ERR_F16_SAT when t = X A^T or u = dY B saturated (may be null).
+ * gtav_op_lora_merge   w_img (tile-major [N][K]) and wT_img (tile-major [K][N], may be null) = the operand type's clamp + cast of W0 + s B A, and w_f32
+ *                      (contiguous [N][K], may be null) = that fp32 sum itself, from the one device function a handle's merge launch runs. */
+int gtav_op_lora_grads(const void* x, const void* dy, const float* a_f32, const float* b_f32, int32_t M, int32_t N, int32_t K, int32_t r, float s, float* dA,
+                       float* dB, float* ws, int64_t ws_floats, int32_t* err, void* stream);
+int gtav_op_lora_merge(const float* w0_f32, const float* a_f32, const float* b_f32, int32_t N, int32_t K, int32_t r, float s, void* w_img, void* wT_img,
+                       float* w_f32, void* stream);
 int gtav_op_gemm_choose_splitk(int32_t M, int32_t N, int32_t K);
 /* What a GEMM launch of this problem would run, without touching a device (the function the launch itself asks: csrc/gemm_plan.h).  epilogue: 0-7 as
  * gtav_op_gemm_f16's (the experiments library also knows the LayerNorm-fold codes 8-11); qkv_mode / S: epilogue 5; splitk: the caller's K slices (epilogue 6);
