@@ -110,19 +110,26 @@ static int fold_producer(gtav_dit* h, int cls, const f16* X, const f16* Wt, int 
 }
 
 // the conditioning MLP over `rows` rows of E / HC (launch_cond_inputs*): timestep embedding -> c (+ actions) -> the modulation table h->mod
-static int dit_cond_mlp(gtav_dit* h, int rows, bool have_actions, hipStream_t s) {
-    const int ldhc = h->D + h->Apad;
+// The last `rows_uncond` rows (guided sampling: the unconditional half) are the external_cond=None branch of model/dit.py:359-366: their action columns of HC
+// are zero and their bias is b_t2, without b_ext — the bits an actions = NULL call computes for them; the rows in front keep the fused b_t2a.  Two launches
+// of the same kernel over the two row ranges (per output the same fma chain at any row count, skinny.hip); rows_uncond = 0 is the one launch it always was.
+static int dit_cond_mlp(gtav_dit* h, int rows, bool have_actions, int rows_uncond, hipStream_t s) {
+    const int ldhc = h->D + h->Apad, rc = rows - rows_uncond;
     RET_IF(launch_skinny_f32(h->E, 256, h->w_t0, h->b_t0, h->HC, ldhc, rows, h->D, 256, 1, s));
-    RET_IF(launch_skinny_f32(h->HC, ldhc, h->w_t2cat, have_actions ? h->b_t2a : h->b_t2, h->Sc, h->D, rows, h->D, ldhc, 1, s));
+    if (rc > 0) RET_IF(launch_skinny_f32(h->HC, ldhc, h->w_t2cat, have_actions ? h->b_t2a : h->b_t2, h->Sc, h->D, rc, h->D, ldhc, 1, s));
+    if (rows_uncond > 0)
+        RET_IF(launch_skinny_f32(h->HC + (size_t)rc * ldhc, ldhc, h->w_t2cat, h->b_t2, h->Sc + (size_t)rc * h->D, h->D, rows_uncond, h->D, ldhc, 1, s));
     return launch_skinny_f32(h->Sc, h->D, h->w_ada, h->b_ada, h->mod, h->MODW, rows, h->MODW, h->D, 0, s);
 }
 
+// rows = outer x Tq; outer indices from n_cond_outer on are unconditional (guided step: outer = 2 B samples, n_cond_outer = B)
 static int dit_cond(gtav_dit* h, const int64_t* t64, int rows, int Tq, const StepParams* sp, int use_cur, const float* actions,
-                    int64_t act_outer, int64_t act_inner, hipStream_t s) {
-    GTAV_REQUIRE(rows <= h->max_rows, "conditioning rows %d exceed max_cond_rows %d", rows, h->max_rows);
-    RET_IF(launch_cond_inputs(t64, rows, Tq, sp, use_cur, h->sincos, h->E, actions, act_outer, act_inner, h->A, h->HC, h->D + h->Apad,
+                    int64_t act_outer, int64_t act_inner, int n_cond_outer, hipStream_t s) {
+    GTAV_REQUIRE(rows <= h->max_rows, "conditioning rows %d exceed max_cond_rows %d%s", rows, h->max_rows,
+                 n_cond_outer * Tq < rows ? " (a guided step conditions 2 B samples)" : "");
+    RET_IF(launch_cond_inputs(t64, rows, Tq, sp, use_cur, h->sincos, h->E, actions, act_outer, act_inner, n_cond_outer, h->A, h->HC, h->D + h->Apad,
                               h->D, h->Apad, h->err_flag, s));
-    RET_IF(dit_cond_mlp(h, rows, actions != nullptr, s));
+    RET_IF(dit_cond_mlp(h, rows, actions != nullptr, rows - (n_cond_outer * Tq < rows ? n_cond_outer * Tq : rows), s));
     bool fa, fb;
     fold_policy(h, rows * h->P, fa, fb);     // one forward over these rows' frames: the LayerNorm-fold tables of the seams it will fold
     return dit_fold_tables(h, rows, fa, fb, s);
@@ -458,7 +465,7 @@ int gtav_dit_forward(gtav_dit* h, const float* x, const int64_t* t, const float*
     // at t0 = 0: a table prepared by gtav_dit_prepare_frame and the context cached by a window step are gone after it
     h->prepared.valid = false;
     h->kvrec.valid = false;
-    RET_IF(dit_cond(h, t, B * T, 1, nullptr, 0, actions, h->A, 0, s));
+    RET_IF(dit_cond(h, t, B * T, 1, nullptr, 0, actions, h->A, 0, B * T, s));
     return dit_forward_core(h, x, nullptr, B, T, 0, h->mod, nullptr, h->fold.ctab, out, s);
 }
 
@@ -474,10 +481,14 @@ static int denoise_step_body(gtav_dit* h, float* x, int B, int F, int T, const f
                              bool prepared, hipStream_t s) {
     const size_t fsz = (size_t)h->C * h->H * h->W;
     const int Tq = mode == 1 ? 1 : T, t0 = mode == 1 ? T - 1 : 0;
-    if (!prepared) RET_IF(dit_cond(h, nullptr, B * Tq, Tq, h->step_dev, mode == 1, actions, (int64_t)F * h->A, h->A, s));
-    RET_IF(dit_forward_core(h, x, h->frame_idx, B, Tq, t0, prepared ? h->mod_cur : h->mod, nullptr, prepared ? h->fold.ctab_cur : h->fold.ctab, h->vout, s));
+    // guided (gtav_dit_set_guidance): ONE forward over 2 B internal samples — [0, B) conditional, [B, 2 B) unconditional on the same frames (frame_idx, no copy of x)
+    const int Bi = h->guided ? 2 * B : B;
+    if (!prepared) RET_IF(dit_cond(h, nullptr, Bi * Tq, Tq, h->step_dev, mode == 1, actions, (int64_t)F * h->A, h->A, B, s));
+    RET_IF(dit_forward_core(h, x, h->frame_idx, Bi, Tq, t0, prepared ? h->mod_cur : h->mod, nullptr, prepared ? h->fold.ctab_cur : h->fold.ctab, h->vout, s));
     // DDIM update of frame `cur` (train_dit.py:110-125, generate.py:220)
     const float* vlast = h->vout + (size_t)(Tq - 1) * fsz;
+    if (h->guided)   // v_c = row b, v_u = row B + b of the forward; v_out is written by the same launch
+        return launch_ddim_update_guided_step(x, F, vlast, vlast + (size_t)B * Tq * fsz, (size_t)Tq * fsz, B, (int)fsz, h->step_dev, v_out, s);
     RET_IF(launch_ddim_update_step(x, F, vlast, (size_t)Tq * fsz, B, (int)fsz, h->step_dev, s));
     if (v_out) RET_IF(launch_copy_rows_f32(vlast, (size_t)Tq * fsz, v_out, fsz, B, fsz, s));
     return 0;
@@ -491,19 +502,25 @@ int gtav_dit_prepare_frame(gtav_dit* h, int32_t B, int32_t F, int32_t start, int
     GTAV_REQUIRE(start >= 0 && cur < F && T >= 1 && T <= h->maxT && B >= 1 && B <= h->maxB && n_steps >= 1 && n_steps <= 1024,
                  "prepare_frame: bad window [%d, %d] / steps %d", start, cur, n_steps);
     GTAV_REQUIRE(!actions || h->A > 0, "prepare_frame: model has no external_cond");
-    const int rows = B * (T - 1) + n_steps * B;
-    GTAV_REQUIRE(rows <= h->max_rows, "prepare_frame: %d conditioning rows exceed max_cond_rows %d", rows, h->max_rows);
+    // guided: the table doubles — rows [0, rows_cond) as always, rows [rows_cond, 2 rows_cond) the same (frame, step) rows of the unconditional branch
+    const int rows_cond = B * (T - 1) + n_steps * B, rows = h->guided ? 2 * rows_cond : rows_cond, Bi = h->guided ? 2 * B : B;
+    if (h->guided) {
+        GTAV_REQUIRE(actions, "prepare_frame: guidance is on and actions == NULL (the unconditional branch is built here; call gtav_dit_set_guidance(h, 0, 1) for an unguided frame)");
+        GTAV_REQUIRE(2 * B <= h->maxB, "prepare_frame: a guided step of batch %d runs 2 B = %d internal samples, max_batch is %d", B, 2 * B, h->maxB);
+    }
+    GTAV_REQUIRE(rows <= h->max_rows, "prepare_frame: %d conditioning rows exceed max_cond_rows %d%s", rows, h->max_rows,
+                 h->guided ? " (guidance doubles the table: 2 B (window - 1 + steps) rows)" : "");
     hipStream_t s = (hipStream_t)stream;
     // the host array may be freed by the caller after this call returns: synchronous copy (once per generated frame)
     GTAV_CHECK_HIP(hipStreamSynchronize(s));
     GTAV_CHECK_HIP(hipMemcpy(h->t_steps_dev, t_steps_host, n_steps * sizeof(int), hipMemcpyHostToDevice));
-    RET_IF(launch_cond_inputs_frame(rows, B, T, F, start, cur, t_ctx, h->t_steps_dev, h->sincos, h->E, actions, h->A, h->HC, h->D + h->Apad,
+    RET_IF(launch_cond_inputs_frame(rows, rows_cond, B, T, F, start, cur, t_ctx, h->t_steps_dev, h->sincos, h->E, actions, h->A, h->HC, h->D + h->Apad,
                                     h->D, h->Apad, h->err_flag, s));
-    RET_IF(dit_cond_mlp(h, rows, actions != nullptr, s));
+    RET_IF(dit_cond_mlp(h, rows, actions != nullptr, rows - rows_cond, s));
     {   // LayerNorm-fold tables of every row, for the seams a full-window step (B T P tokens) or a context-cached step (B P tokens) folds
         bool fa, fb, fa1, fb1;
-        fold_policy(h, B * T * h->P, fa, fb);
-        fold_policy(h, B * h->P, fa1, fb1);
+        fold_policy(h, Bi * T * h->P, fa, fb);
+        fold_policy(h, Bi * h->P, fa1, fb1);
         RET_IF(dit_fold_tables(h, rows, fa || fa1, fb || fb1, s));
         h->prepared.fold_tables = fa || fa1 || fb || fb1;
     }
@@ -518,7 +535,7 @@ int gtav_dit_prepare_frame(gtav_dit* h, int32_t B, int32_t F, int32_t start, int
 // or capture is not available here, and then use_graph goes off for good.  A step body that fails inside the capture returns its own code.
 static int dit_step_graph(gtav_dit* h, float* x, int B, int F, int T, const float* actions, int mode, float* v_out, bool prepared, hipGraphExec_t* out) {
     *out = nullptr;
-    const gtav_dit::GraphKey key{B, F, T, mode * 2 + (prepared ? 1 : 0), x, actions, v_out};
+    const gtav_dit::GraphKey key{B, F, T, mode * 2 + (prepared ? 1 : 0), x, actions, v_out, h->guided ? 1 : 0};   // (the guidance scale is read from step_dev: not in the key)
     auto it = h->graphs.find(key);
     if (it == h->graphs.end()) {
         if (h->graphs.size() > 64) h->drop_graphs();
@@ -557,6 +574,11 @@ int gtav_dit_denoise_step(gtav_dit* h, float* x, int32_t B, int32_t F, int32_t s
     GTAV_REQUIRE(t_cur >= 0 && t_cur < 1000 && t_next >= 0 && t_next < 1000 && t_ctx >= 0 && t_ctx < 1000, "denoise_step: timestep out of range");
     GTAV_REQUIRE(!actions || h->A > 0, "denoise_step: model has no external_cond");
     GTAV_REQUIRE(mode == 0 || mode == 1, "denoise_step: mode %d", mode);
+    if (h->guided) {
+        GTAV_REQUIRE(actions, "denoise_step: guidance is on and actions == NULL (there is nothing to guide towards; call gtav_dit_set_guidance(h, 0, 1) for an unguided step)");
+        GTAV_REQUIRE(2 * B <= h->maxB, "denoise_step: a guided step of batch %d runs 2 B = %d internal samples, max_batch is %d", B, 2 * B, h->maxB);
+    }
+    const int Bi = h->guided ? 2 * B : B;
     const bool prepared = cond_step >= 0;
     if (prepared)
         GTAV_REQUIRE(h->prepared.valid && h->prepared.B == B && h->prepared.F == F && h->prepared.start == start &&
@@ -576,9 +598,11 @@ int gtav_dit_denoise_step(gtav_dit* h, float* x, int32_t B, int32_t F, int32_t s
     StepParams sp;
     sp.first = start; sp.cur = cur; sp.t_ctx = t_ctx; sp.t_cur = t_cur; sp.is_final = is_final != 0;
     sp.alpha_t = h->ac_host[t_cur]; sp.alpha_next = h->ac_host[t_next]; sp.cond_step = cond_step;
-    RET_IF(launch_step_setup(h->step_dev, sp, h->frame_idx, h->mod_rows_dev, prepared ? h->mod_last : nullptr, h->mod_changed, B, mode == 1 ? 1 : T, T, F,
-                             mode == 1, s));
-    if (prepared) RET_IF(launch_gather_rows(h->mod, h->mod_rows_dev, h->mod_changed, h->mod_cur, B * (mode == 1 ? 1 : T), h->MODW,
+    sp.guidance = h->guide_scale;
+    // (guided + prepared: the unconditional half of the table starts where prepare_frame put it, after the B (T - 1 + n_steps) conditional rows)
+    RET_IF(launch_step_setup(h->step_dev, sp, h->frame_idx, h->mod_rows_dev, prepared ? h->mod_last : nullptr, h->mod_changed, Bi, mode == 1 ? 1 : T, T, F,
+                             mode == 1, B, prepared ? B * (T - 1 + h->prepared.n_steps) : 0, s));
+    if (prepared) RET_IF(launch_gather_rows(h->mod, h->mod_rows_dev, h->mod_changed, h->mod_cur, Bi * (mode == 1 ? 1 : T), h->MODW,
                                             h->prepared.fold_tables ? h->fold.ctab : nullptr, h->fold.ctab_cur, h->fold.CTW, s));
     hipGraphExec_t exec = nullptr;
     if (h->use_graph && !h->prof.on) RET_IF(dit_step_graph(h, x, B, F, T, actions, mode, v_out, prepared, &exec));
@@ -590,6 +614,22 @@ int gtav_dit_denoise_step(gtav_dit* h, float* x, int32_t B, int32_t F, int32_t s
 int gtav_dit_set_graph(gtav_dit* h, int32_t enable) {
     GTAV_REQUIRE(h, "dit_set_graph: null handle");
     h->use_graph = enable != 0;
+    return 0;
+}
+
+int gtav_dit_set_guidance(gtav_dit* h, int32_t enable, float scale) {
+    GTAV_REQUIRE(h, "dit_set_guidance: null handle");
+    GTAV_REQUIRE(enable == 0 || enable == 1, "dit_set_guidance: enable %d (0 off, 1 on)", enable);
+    GTAV_REQUIRE(!enable || std::isfinite(scale), "dit_set_guidance: the scale is not finite");
+    GTAV_REQUIRE(!enable || h->A > 0, "dit_set_guidance: model has no external_cond (nothing to guide towards)");
+    GTAV_REQUIRE(!enable || 2 <= h->maxB, "dit_set_guidance: a guided step of batch B runs 2 B internal samples, max_batch is %d", h->maxB);
+    if ((enable != 0) != h->guided) {
+        // the other mode's conditioning table and temporal K/V caches have another row / sample layout (captured steps stay: the key carries the flag)
+        h->prepared.valid = false;
+        h->kvrec.valid = false;
+    }
+    h->guided = enable != 0;
+    if (enable) h->guide_scale = scale;
     return 0;
 }
 

@@ -388,12 +388,18 @@ struct gtav_dit {
     // which window the per-layer temporal K/V caches currently describe: written by a full-window (mode 0) sampler step,
     // required by a context-cached (mode 1) step, invalidated by anything else that writes the caches (gtav_dit_forward)
     struct { bool valid = false; int B = 0, F = 0, start = 0, cur = 0; const void* x = nullptr; } kvrec;
-    // captured hipGraphs of the fused sampler step, keyed by (shape, mode, buffers)
+    // classifier-free guidance (gtav_dit_set_guidance): the sampler step and prepare_frame run 2 B internal samples — [0, B) with the actions, [B, 2 B) as the
+    // external_cond=None branch on the same frames — and frame `cur` is updated from v_c + (s - 1)(v_c - v_u).  Switching `guided` invalidates `prepared`
+    // and `kvrec` (the table and the caches of the other mode have another row / sample layout); the scale alone invalidates nothing.
+    bool guided = false;
+    float guide_scale = 1.f;
+    // captured hipGraphs of the fused sampler step, keyed by (shape, mode, buffers, guided)
     struct GraphKey {
         int B, F, T, mode;
         const void *x, *actions, *vout;
+        int guided;
         bool operator<(const GraphKey& o) const {
-            return std::tie(B, F, T, mode, x, actions, vout) < std::tie(o.B, o.F, o.T, o.mode, o.x, o.actions, o.vout);
+            return std::tie(B, F, T, mode, x, actions, vout, guided) < std::tie(o.B, o.F, o.T, o.mode, o.x, o.actions, o.vout, o.guided);
         }
     };
     std::map<GraphKey, hipGraphExec_t> graphs;   // nullptr value = shape seen once (eager warm-up done), not yet captured
@@ -452,6 +458,10 @@ struct gtav_dit {
     // ---- training: saved activations of the last training forward, backward workspace, optimizer state ----
     struct Train {
         bool on = false, have_fwd = false, have_actions = false;
+        // per-sample action dropout of the saved forward (gtav_dit_train_forward_keep): keep[b] == 0 conditioned sample b as external_cond=None; the backward
+        // sums external_cond.bias over the kept rows only
+        bool have_keep = false;
+        int* keep = nullptr;                // [maxB], device
         bool bf16 = false;                  // every operand group bf16 (gtav_dit_train_enable_typed): no group may change its type while training is on
         // Mixed operand types (gtav_dit_train_allow_mixed): the groups of an enabled handle may change their type one by one (gtav_dit_train_set_group_dtype,
         // gtav_dit_train_autorange); `bf16` is then the type the handle STARTED on.  The training forward raises its bits in the group's error word (err_of(g)),

@@ -181,6 +181,7 @@ static int train_enable_body(gtav_dit* h, float* grad_arena_dev, int64_t grad_ar
         }
     }
     RET_IF(a.alloc_t(&t.ctl, 8));
+    RET_IF(a.alloc_t(&t.keep, (size_t)h->maxB));
     RET_IF(lora ? train_resolve_lora(h) : train_resolve_slots(h));
     if (lora) RET_IF(train_lora_tables(h));
     t.red_ws_floats = colsum_workspace(h->Mmax > h->max_rows ? h->Mmax : h->max_rows, std::max(std::max(h->Hm_pad, 6 * D), Nf));
@@ -509,7 +510,22 @@ int gtav_dit_get_grad(gtav_dit* h, const char* name, float* dst, int64_t numel, 
     return 0;
 }
 
+static int train_forward_impl(gtav_dit* h, const float* x, const int64_t* t64, const float* actions, const int32_t* keep, float* out, int32_t B, int32_t T, void* stream);
+
 int gtav_dit_train_forward(gtav_dit* h, const float* x, const int64_t* t64, const float* actions, float* out, int32_t B, int32_t T, void* stream) {
+    return train_forward_impl(h, x, t64, actions, nullptr, out, B, T, stream);
+}
+
+int gtav_dit_train_forward_keep(gtav_dit* h, const float* x, const int64_t* t64, const float* actions, const int32_t* keep, float* out, int32_t B, int32_t T,
+                                void* stream) {
+    GTAV_REQUIRE(!keep || actions, "train_forward_keep: a keep mask without actions (there is nothing to drop)");
+    return train_forward_impl(h, x, t64, actions, keep, out, B, T, stream);
+}
+
+}  // extern "C"
+
+// keep (device, B flags, optional): sample b with keep[b] == 0 is conditioned as external_cond=None for all its frames (gtav_dit_train_forward_keep)
+static int train_forward_impl(gtav_dit* h, const float* x, const int64_t* t64, const float* actions, const int32_t* keep, float* out, int32_t B, int32_t T, void* stream) {
     GTAV_REQUIRE(h && x && t64 && out, "train_forward: null argument");
     GTAV_REQUIRE(h->tr.on && h->finalized, "train_forward: call gtav_dit_train_enable, load the weights and finalize first");
     GTAV_REQUIRE(B >= 1 && B <= h->maxB && T >= 1 && T <= h->maxT, "train_forward: B=%d T=%d outside capacity (%d, %d)", B, T, h->maxB, h->maxT);
@@ -521,10 +537,19 @@ int gtav_dit_train_forward(gtav_dit* h, const float* x, const int64_t* t64, cons
     h->kvrec.valid = false;
     tr.rc_block = -1;   // (recompute mode: this forward overwrites the ring states and the image sets; if it fails partway, no block is in place)
     // conditioning path with its pre-activations kept (dit_cond applies SiLU inside the skinny GEMM)
-    RET_IF(launch_cond_inputs(t64, rows, 1, nullptr, 0, h->sincos, h->E, actions, h->A, 0, h->A, h->HC, ldhc, D, h->Apad, h->err_flag, s));
+    RET_IF(launch_cond_inputs(t64, rows, 1, nullptr, 0, h->sincos, h->E, actions, h->A, 0, rows, h->A, h->HC, ldhc, D, h->Apad, h->err_flag, s));
     RET_IF(launch_skinny_f32(h->E, 256, h->w_t0, h->b_t0, tr.z0, D, rows, D, 256, 0, s));
     RET_IF(launch_silu(tr.z0, D, h->HC, ldhc, rows, D, s));
-    RET_IF(launch_skinny_f32(h->HC, ldhc, h->w_t2cat, actions ? h->b_t2a : h->b_t2, tr.cpre, D, rows, D, ldhc, 0, s));
+    if (keep) {
+        // per-sample action dropout: a dropped sample's rows lose their action columns, and every row gets ITS bias — b_t2a (kept) or b_t2 (dropped) — by the one
+        // fp32 add the GEMM epilogue would have made: all ones is the plain forward with actions bit for bit, all zeros the forward with actions = NULL
+        GTAV_CHECK_HIP(hipMemcpyAsync(tr.keep, keep, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+        RET_IF(launch_keep_mask_cols(h->HC + D, ldhc, rows, h->Apad, T, tr.keep, s));
+        RET_IF(launch_skinny_f32(h->HC, ldhc, h->w_t2cat, nullptr, tr.cpre, D, rows, D, ldhc, 0, s));
+        RET_IF(launch_keep_add_bias(tr.cpre, D, rows, D, T, tr.keep, h->b_t2a, h->b_t2, s));
+    } else {
+        RET_IF(launch_skinny_f32(h->HC, ldhc, h->w_t2cat, actions ? h->b_t2a : h->b_t2, tr.cpre, D, rows, D, ldhc, 0, s));
+    }
     RET_IF(launch_silu(tr.cpre, D, h->Sc, D, rows, D, s));
     RET_IF(launch_skinny_f32(h->Sc, D, h->w_ada, h->b_ada, h->mod, h->MODW, rows, h->MODW, D, 0, s));
     const float* mod = h->mod;
@@ -545,9 +570,12 @@ int gtav_dit_train_forward(gtav_dit* h, const float* x, const int64_t* t64, cons
     // (mixed-capable handles) the groups' bits of this forward into word 0, where the backward's publish and the optimizer look, and into the sticky words
     if (tr.mixed) RET_IF(launch_err_fold(h->err_flag, tr.range_words, 0, h->n_groups, s));
     tr.B = B; tr.T = T; tr.M = M; tr.Mp = round_up(M, 64); tr.rows = rows; tr.have_actions = actions != nullptr; tr.have_fwd = true;
+    tr.have_keep = keep != nullptr;
     tr.rc_block = L - 1;   // (recompute mode: the ring states and the two image sets hold the last block)
     return 0;
 }
+
+extern "C" {
 
 // Residual stream of the last training forward after k branch additions (every block adds four branches: spatial attention, spatial
 // MLP, temporal attention, temporal MLP): k = 0 is the patch embedding output, k = 4 (l + 1) the output of block l, k = 4 L the input of
@@ -763,7 +791,9 @@ int TrainBackward::embedders() {
     RET_IF(launch_colsum_f32(tr.dc, D, rows, D, tr.t2.b->grad, tr.red_ws, s));
     RET_IF(launch_gemm_tn_f32(tr.dc, D, h->HC, ldhc, rows, D, D, tr.t2.w->grad, D, s));
     if (tr.have_actions) {
-        RET_IF(launch_colsum_f32(tr.dc, D, rows, D, tr.ext.b->grad, tr.red_ws, s));
+        // (action dropout: b_ext reached the kept rows only; W_ext's gradient is right by itself, the dropped rows' action columns of HC are zero)
+        if (tr.have_keep) RET_IF(launch_colsum_f32_keep(tr.dc, D, rows, D, tr.keep, T, tr.ext.b->grad, tr.red_ws, s));
+        else RET_IF(launch_colsum_f32(tr.dc, D, rows, D, tr.ext.b->grad, tr.red_ws, s));
         RET_IF(launch_gemm_tn_f32(tr.dc, D, h->HC + D, ldhc, rows, D, h->A, tr.ext.w->grad, h->A, s));
     }
     RET_IF(launch_gemm_nn_f32(tr.dc, D, h->w_t2cat, ldhc, rows, D, D, tr.dh0, D, s));

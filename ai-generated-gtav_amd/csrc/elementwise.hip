@@ -361,15 +361,16 @@ __global__ void add_f32_kernel(const float* a, const float* b, float* out, size_
 }
 
 __global__ void step_setup_kernel(StepParams* dst, StepParams v, int* frame_idx, int* mod_rows, int* last_rows, int* changed, int B, int Tq, int T,
-                                  int F, int use_cur) {
+                                  int F, int use_cur, int Bc, int uncond_row0) {
     if (threadIdx.x == 0) *dst = v;
     const int first = use_cur ? v.cur : v.first;
     for (int i = threadIdx.x; i < B * Tq; i += blockDim.x) {
-        const int b = i / Tq, tl = i - b * Tq;
+        const int bi = i / Tq, tl = i - bi * Tq;
+        const int uncond = bi >= Bc, b = uncond ? bi - Bc : bi;   // guided step: internal sample Bc + b reads the frames of sample b
         frame_idx[i] = b * F + first + tl;
         if (v.cond_step >= 0) {
             const int tw = use_cur ? T - 1 : tl;   // position inside the window
-            const int r = tw < T - 1 ? b * (T - 1) + tw : B * (T - 1) + v.cond_step * B + b;
+            const int r = (tw < T - 1 ? b * (T - 1) + tw : Bc * (T - 1) + v.cond_step * Bc + b) + (uncond ? uncond_row0 : 0);
             mod_rows[i] = r;
             if (last_rows) {      // which slots of the current-step table (gather_rows_kernel) hold another row than this step needs
                 changed[i] = last_rows[i] != r;
@@ -429,20 +430,22 @@ __global__ __launch_bounds__(256) void ctab_inputs_kernel(const float* __restric
     *(u32x4*)(sx + (size_t)g * group_stride + tiled_off(r, k, D)) = o.u;
 }
 
-__global__ void cond_inputs_frame_kernel(int rows, int B, int T, int F, int start, int cur, int t_ctx, const int* __restrict__ t_steps,
+__global__ void cond_inputs_frame_kernel(int rows, int rows_cond, int B, int T, int F, int start, int cur, int t_ctx, const int* __restrict__ t_steps,
                                          const float* __restrict__ sincos, float* __restrict__ E,
                                          const float* __restrict__ actions, int A, float* __restrict__ HC, int ldhc, int D,
                                          int Apad, int* err_flag) {
     const int r = blockIdx.x;
     if (r >= rows) return;
+    const int rc = r >= rows_cond ? r - rows_cond : r;    // (guided: the unconditional half repeats the rows without actions)
+    if (r >= rows_cond) actions = nullptr;
     const int nctx = B * (T - 1);
     int t, b, frame;
-    if (r < nctx) {
-        b = r / (T - 1);
-        frame = start + (r - b * (T - 1));
+    if (rc < nctx) {
+        b = rc / (T - 1);
+        frame = start + (rc - b * (T - 1));
         t = t_ctx;
     } else {
-        const int q = r - nctx;
+        const int q = rc - nctx;
         const int sidx = q / B;
         b = q - sidx * B;
         frame = cur;
@@ -459,11 +462,12 @@ __global__ void cond_inputs_frame_kernel(int rows, int B, int T, int F, int star
 
 __global__ void cond_inputs_kernel(const int64_t* __restrict__ t64, int rows, int Tq, const StepParams* __restrict__ sp, int use_cur,
                                    const float* __restrict__ sincos, float* __restrict__ E, const float* __restrict__ actions,
-                                   long long act_outer, long long act_inner, int A, float* __restrict__ HC, int ldhc, int D,
+                                   long long act_outer, long long act_inner, int n_cond_outer, int A, float* __restrict__ HC, int ldhc, int D,
                                    int Apad, int* err_flag) {
     const int r = blockIdx.x;
     if (r >= rows) return;
     const int ro = r / Tq, ri = r - ro * Tq;
+    if (ro >= n_cond_outer) actions = nullptr;
     long long t;
     int frame0 = 0;
     if (t64) {
@@ -506,6 +510,28 @@ __global__ void ddim_update_step_kernel(float* __restrict__ x, size_t frames_per
     float* xf = x + ((size_t)b * frames_per_sample + sp->cur) * n;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
         xf[i] = ddim_one(xf[i], v[b * v_stride + i], at, an, fin);
+}
+
+// Classifier-free guidance on one element: d = v_c - v_u, m = (s - 1) d, v_g = v_c + m, each rounded to fp32 on its own.  Contraction is OFF: fused into an fma
+// the last bit would differ from the three-operation numpy float32 expression the tests compare against, and s = 1 would not return v_c itself.
+__device__ __forceinline__ float guided_v(float vc, float vu, float s) {
+#pragma clang fp contract(off)
+    const float d = vc - vu;
+    const float m = (s - 1.0f) * d;
+    return vc + m;
+}
+
+__global__ void ddim_update_guided_step_kernel(float* __restrict__ x, size_t frames_per_sample, const float* __restrict__ v_c, const float* __restrict__ v_u,
+                                               size_t v_stride, int n, const StepParams* __restrict__ sp, float* __restrict__ v_out) {
+    const int b = blockIdx.y;
+    const float at = sp->alpha_t, an = sp->alpha_next, s = sp->guidance;
+    const int fin = sp->is_final;
+    float* xf = x + ((size_t)b * frames_per_sample + sp->cur) * n;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const float vg = guided_v(v_c[b * v_stride + i], v_u[b * v_stride + i], s);
+        xf[i] = ddim_one(xf[i], vg, at, an, fin);
+        if (v_out) v_out[(size_t)b * n + i] = vg;
+    }
 }
 
 // The noising and the v-target of one element (train_dit.py:625-645), shared by the kernels that read their noise from memory and by the one that draws it
@@ -970,8 +996,9 @@ int launch_add_f32(const float* a, const float* b, float* out, size_t n, hipStre
 }
 
 int launch_step_setup(StepParams* dst, const StepParams& v, int* frame_idx, int* mod_rows, int* last_rows, int* changed, int B, int Tq, int T, int F,
-                      int use_cur, hipStream_t stream) {
-    hipLaunchKernelGGL(step_setup_kernel, dim3(1), dim3(64), 0, stream, dst, v, frame_idx, mod_rows, last_rows, changed, B, Tq, T, F, use_cur);
+                      int use_cur, int Bc, int uncond_row0, hipStream_t stream) {
+    GTAV_REQUIRE(Bc == B || (2 * Bc == B && uncond_row0 >= 0), "step_setup: %d internal samples for %d conditional ones", B, Bc);
+    hipLaunchKernelGGL(step_setup_kernel, dim3(1), dim3(64), 0, stream, dst, v, frame_idx, mod_rows, last_rows, changed, B, Tq, T, F, use_cur, Bc, uncond_row0);
     GTAV_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -995,21 +1022,22 @@ int launch_ctab_inputs(const float* mod, int MODW, int R, int Rp, int D, const i
     return 0;
 }
 
-int launch_cond_inputs_frame(int rows, int B, int T, int F, int start, int cur, int t_ctx, const int* t_steps, const float* sincos,
+int launch_cond_inputs_frame(int rows, int rows_cond, int B, int T, int F, int start, int cur, int t_ctx, const int* t_steps, const float* sincos,
                              float* E, const float* actions, int A, float* HC, int ldhc, int D, int Apad, int* err_flag,
                              hipStream_t stream) {
-    hipLaunchKernelGGL(cond_inputs_frame_kernel, dim3(rows), dim3(256), 0, stream, rows, B, T, F, start, cur, t_ctx, t_steps, sincos,
+    GTAV_REQUIRE(rows_cond == rows || 2 * rows_cond == rows, "cond_inputs_frame: %d rows for %d conditional ones", rows, rows_cond);
+    hipLaunchKernelGGL(cond_inputs_frame_kernel, dim3(rows), dim3(256), 0, stream, rows, rows_cond, B, T, F, start, cur, t_ctx, t_steps, sincos,
                        E, actions, A, HC, ldhc, D, Apad, err_flag);
     GTAV_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
 int launch_cond_inputs(const int64_t* t64, int rows, int Tq, const StepParams* sp, int use_cur, const float* sincos, float* E,
-                       const float* actions, int64_t act_outer, int64_t act_inner, int A, float* HC, int ldhc, int D, int Apad,
+                       const float* actions, int64_t act_outer, int64_t act_inner, int n_cond_outer, int A, float* HC, int ldhc, int D, int Apad,
                        int* err_flag, hipStream_t stream) {
     GTAV_REQUIRE(rows > 0 && Tq > 0 && (t64 || sp), "cond_inputs: bad rows/Tq/timesteps");
     hipLaunchKernelGGL(cond_inputs_kernel, dim3(rows), dim3(256), 0, stream, t64, rows, Tq, sp, use_cur, sincos, E, actions,
-                       (long long)act_outer, (long long)act_inner, A, HC, ldhc, D, Apad, err_flag);
+                       (long long)act_outer, (long long)act_inner, n_cond_outer, A, HC, ldhc, D, Apad, err_flag);
     GTAV_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -1026,6 +1054,14 @@ int launch_ddim_update_step(float* x, size_t frames_per_sample, const float* v, 
                             const StepParams* sp, hipStream_t stream) {
     hipLaunchKernelGGL(ddim_update_step_kernel, dim3(cdiv(n, 256), B), dim3(256), 0, stream, x, frames_per_sample, v, v_stride,
                        n, sp);
+    GTAV_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_ddim_update_guided_step(float* x, size_t frames_per_sample, const float* v_c, const float* v_u, size_t v_stride, int B, int n,
+                                   const StepParams* sp, float* v_out, hipStream_t stream) {
+    hipLaunchKernelGGL(ddim_update_guided_step_kernel, dim3(cdiv(n, 256), B), dim3(256), 0, stream, x, frames_per_sample, v_c, v_u, v_stride,
+                       n, sp, v_out);
     GTAV_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -24,18 +24,22 @@ struct StepParams {
     int is_final;   // noise_idx == 0: return x_start (train_dit.py:119-120)
     float alpha_t, alpha_next;
     int cond_step;  // >= 0: row set of the per-frame conditioning table prepared by gtav_dit_prepare_frame; -1: inline
+    float guidance; // classifier-free guidance scale s of a guided step (gtav_dit_set_guidance): on the device, so one captured step replays for any s
 };
 // One launch ahead of the (possibly graph-replayed) step: *dst = v, frame_idx[b*Tq+tl] = b*F + first + tl
 // (first = use_cur ? v.cur : v.first) and, when v.cond_step >= 0, the conditioning-table row of every processed frame:
 // context frame (b, tl < T-1) -> b*(T-1)+tl, frame `cur` of sample b -> B*(T-1) + cond_step*B + b.
+// Guided step (Bc < B, B = 2 Bc internal samples): sample Bc + b is the unconditional twin of sample b — the same frames of x (no copy), and the same row
+// numbers over Bc samples plus `uncond_row0`, where the unconditional half of the prepared table starts.  Bc == B: today's numbering, uncond_row0 unused.
 int launch_step_setup(StepParams* dst, const StepParams& v, int* frame_idx, int* mod_rows, int* last_rows, int* changed, int B, int Tq, int T, int F,
-                      int use_cur, hipStream_t stream);
+                      int use_cur, int Bc, int uncond_row0, hipStream_t stream);
 // current-step conditioning table: cur[slot] <- table[rows[slot]] (W floats) for the slots step_setup flagged in `changed`
 // (table2 / cur2 / W2: optional second table gathered by the same launch — the c1 / c2 tables of the LayerNorm fold)
 int launch_gather_rows(const float* table, const int* rows, const int* changed, float* cur, int slots, int W, const float* table2, float* cur2, int W2,
                        hipStream_t stream);
-// Conditioning inputs for a whole generated frame (rows laid out as above, n_steps row sets for frame `cur`).
-int launch_cond_inputs_frame(int rows, int B, int T, int F, int start, int cur, int t_ctx, const int* t_steps, const float* sincos,
+// Conditioning inputs for a whole generated frame (rows laid out as above, n_steps row sets for frame `cur`).  rows_cond < rows (guided: rows = 2 rows_cond):
+// row rows_cond + r repeats row r without its actions (zero action columns).
+int launch_cond_inputs_frame(int rows, int rows_cond, int B, int T, int F, int start, int cur, int t_ctx, const int* t_steps, const float* sincos,
                              float* E, const float* actions, int A, float* HC, int ldhc, int D, int Apad, int* err_flag,
                              hipStream_t stream);
 
@@ -69,8 +73,9 @@ int launch_axpy_f32(float* y, const float* x, float alpha, size_t n, hipStream_t
 //   HC[r][D : D+Apad] = actions[(r / Tq) * act_outer + (r % Tq) * act_inner + 0:A]  (zeros when actions == nullptr)
 // With `sp` (sampler step): t_ctx / t_cur come from *sp and the action row of (b, tl) is
 // actions[b * act_outer + ((use_cur ? sp->cur : sp->first) + tl) * act_inner].
+// Outer indices from `n_cond_outer` on (the unconditional half of a guided step) get zero action columns.
 int launch_cond_inputs(const int64_t* t64, int rows, int Tq, const StepParams* sp, int use_cur, const float* sincos /*[1000][256]*/,
-                       float* E, const float* actions, int64_t act_outer, int64_t act_inner, int A, float* HC, int ldhc,
+                       float* E, const float* actions, int64_t act_outer, int64_t act_inner, int n_cond_outer, int A, float* HC, int ldhc,
                        int D, int Apad, int* err_flag, hipStream_t stream);
 
 // DDIM-style v-prediction update of the newest frame (train_dit.py:110-125), per sample b:
@@ -82,6 +87,11 @@ int launch_ddim_update(const float* x, size_t x_stride, const float* v, size_t v
 // sampler form: frame sp->cur of x (B, F, n) is updated in place from v (row stride v_stride); alphas / is_final from *sp
 int launch_ddim_update_step(float* x, size_t frames_per_sample, const float* v, size_t v_stride, int B, int n,
                             const StepParams* sp, hipStream_t stream);
+// guided sampler form: v_g = v_c + (s - 1) (v_c - v_u) with s = sp->guidance, as three separately rounded fp32 operations (d = v_c - v_u, m = (s - 1) d,
+// v_g = v_c + m: never an fma, so numpy float32 gives the same bits and s = 1 gives v_c itself); frame sp->cur of x is updated from v_g, and v_out
+// (B, n; optional) receives v_g.  v_c / v_u: row b at b * v_stride.
+int launch_ddim_update_guided_step(float* x, size_t frames_per_sample, const float* v_c, const float* v_u, size_t v_stride, int B, int n,
+                                   const StepParams* sp, float* v_out, hipStream_t stream);
 
 // Training-side noising, v-target and squared-error partial sums (train_dit.py:621-650).
 int launch_add_noise(const float* x, const float* noise, const float* alpha /*[rows]*/, float* out, int rows, int n,
@@ -122,6 +132,10 @@ int launch_ln_mod_bwd_fused(const float* dxn, const float* x, const float* scale
 // column sums in a fixed order (no float atomics): ws = colsum_workspace(M, N) floats of scratch for the per-row-split partial sums
 size_t colsum_workspace(int M, int N);
 int launch_colsum_f32(const float* a, int lda, int M, int N, float* db, float* ws, hipStream_t stream);   // db[n] += sum_m a[m][n]
+// per-sample action dropout of the training forward (gtav_dit_train_forward_keep): row m belongs to sample m / rows_per_keep, keep[sample] == 0 = dropped
+int launch_colsum_f32_keep(const float* a, int lda, int M, int N, const int* keep, int rows_per_keep, float* db, float* ws, hipStream_t stream);   // db[n] += sum over kept rows
+int launch_keep_mask_cols(float* a, int lda, int M, int C, int rows_per_keep, const int* keep, hipStream_t stream);   // a[m][0:C] = 0 in dropped rows
+int launch_keep_add_bias(float* y, int ldy, int M, int N, int rows_per_keep, const int* keep, const float* bias_keep, const float* bias_drop, hipStream_t stream);
 int launch_silu(const float* x, int ldx, float* y, int ldy, int R, int C, hipStream_t stream);
 int launch_silu_bwd(const float* dy, int lddy, const float* x, int ldx, float* dx, int lddx, int R, int C, hipStream_t stream);
 int launch_gemm_tn_f32(const float* dY, int lddy, const float* X, int ldx, int R, int N, int K, float* dW, int lddw, hipStream_t stream);   // dW += dY^T X

@@ -440,6 +440,45 @@ __global__ __launch_bounds__(256) void colsum_f32_kernel(const float* __restrict
     else db[n] += s;
 }
 
+// Per-sample action dropout (gtav_dit_train_forward_keep; reference train_dit.py:704-705, commented out there).  Row m belongs to sample m / rows_per_keep.
+// colsum_f32_kernel over the rows of kept samples: the same chains, splits and order with +0 in a dropped row's place, so all-ones is launch_colsum_f32 bit for bit.
+__global__ __launch_bounds__(256) void colsum_f32_keep_kernel(const float* __restrict__ a, int lda, int M, int N, const int* __restrict__ keep, int rows_per_keep,
+                                                              float* __restrict__ db, int rows_per_block, float* __restrict__ ws) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    const int r_begin = blockIdx.y * rows_per_block, r_end = min(M, r_begin + rows_per_block);
+    auto at = [&](int r) { return keep[r / rows_per_keep] ? a[(size_t)r * lda + n] : 0.f; };
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    int r = r_begin;
+    for (; r + 4 <= r_end; r += 4) {
+        s0 += at(r);
+        s1 += at(r + 1);
+        s2 += at(r + 2);
+        s3 += at(r + 3);
+    }
+    for (; r < r_end; ++r) s0 += at(r);
+    const float s = (s0 + s1) + (s2 + s3);
+    if (ws) ws[(size_t)blockIdx.y * N + n] = s;
+    else db[n] += s;
+}
+// columns [0, C) of the rows of dropped samples <- 0 (the action columns of the conditioning MLP's operand)
+__global__ void keep_mask_cols_kernel(float* __restrict__ a, int lda, int M, int C, int rows_per_keep, const int* __restrict__ keep) {
+    const size_t total = (size_t)M * C;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+        const int r = (int)(idx / C), c = (int)(idx - (size_t)r * C);
+        if (!keep[r / rows_per_keep]) a[(size_t)r * lda + c] = 0.f;
+    }
+}
+// y[m][n] += (kept row ? bias_keep : bias_drop)[n]: the bias add of the GEMM epilogue, one fp32 add, with the bias chosen per row
+__global__ void keep_add_bias_kernel(float* __restrict__ y, int ldy, int M, int N, int rows_per_keep, const int* __restrict__ keep,
+                                     const float* __restrict__ bias_keep, const float* __restrict__ bias_drop) {
+    const size_t total = (size_t)M * N;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+        const int r = (int)(idx / N), n = (int)(idx - (size_t)r * N);
+        y[(size_t)r * ldy + n] = y[(size_t)r * ldy + n] + (keep[r / rows_per_keep] ? bias_keep[n] : bias_drop[n]);
+    }
+}
+
 // fp32 row-major [M][D] -> fp16 tile-major (the patch-embedding gradient as a dW operand)
 __global__ void to_tiled_f16_kernel(const float* __restrict__ a, int M, int D, f16* __restrict__ out, int* err_flag) {
     const size_t total = (size_t)M * (D / 4);
@@ -1959,6 +1998,28 @@ int launch_colsum_f32(const float* a, int lda, int M, int N, float* db, float* w
     GTAV_REQUIRE(splits == 1 || ws, "colsum: %d row splits need the partial-sum workspace", splits);
     hipLaunchKernelGGL(colsum_f32_kernel, dim3(cdiv(N, 256), splits), dim3(256), 0, stream, a, lda, M, N, db, cdiv(M, splits), splits > 1 ? ws : nullptr);
     if (splits > 1) hipLaunchKernelGGL(colsum_reduce_kernel, dim3(cdiv(N, 32)), dim3(256), 0, stream, ws, splits, N, db);
+    GTAV_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+int launch_colsum_f32_keep(const float* a, int lda, int M, int N, const int* keep, int rows_per_keep, float* db, float* ws, hipStream_t stream) {
+    const int splits = cdiv(M, 256);
+    GTAV_REQUIRE(keep && rows_per_keep > 0 && M % rows_per_keep == 0, "colsum_keep: %d rows in samples of %d", M, rows_per_keep);
+    GTAV_REQUIRE(splits == 1 || ws, "colsum: %d row splits need the partial-sum workspace", splits);
+    hipLaunchKernelGGL(colsum_f32_keep_kernel, dim3(cdiv(N, 256), splits), dim3(256), 0, stream, a, lda, M, N, keep, rows_per_keep, db, cdiv(M, splits),
+                       splits > 1 ? ws : nullptr);
+    if (splits > 1) hipLaunchKernelGGL(colsum_reduce_kernel, dim3(cdiv(N, 32)), dim3(256), 0, stream, ws, splits, N, db);
+    GTAV_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+int launch_keep_mask_cols(float* a, int lda, int M, int C, int rows_per_keep, const int* keep, hipStream_t stream) {
+    GTAV_REQUIRE(keep && rows_per_keep > 0 && M % rows_per_keep == 0 && C > 0 && C <= lda, "keep_mask_cols: bad shape");
+    hipLaunchKernelGGL(keep_mask_cols_kernel, dim3(grid_for((size_t)M * C)), dim3(256), 0, stream, a, lda, M, C, rows_per_keep, keep);
+    GTAV_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+int launch_keep_add_bias(float* y, int ldy, int M, int N, int rows_per_keep, const int* keep, const float* bias_keep, const float* bias_drop, hipStream_t stream) {
+    GTAV_REQUIRE(keep && rows_per_keep > 0 && M % rows_per_keep == 0 && N > 0 && N <= ldy, "keep_add_bias: bad shape");
+    hipLaunchKernelGGL(keep_add_bias_kernel, dim3(grid_for((size_t)M * N)), dim3(256), 0, stream, y, ldy, M, N, rows_per_keep, keep, bias_keep, bias_drop);
     GTAV_CHECK_HIP(hipGetLastError());
     return 0;
 }

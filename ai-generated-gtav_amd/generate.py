@@ -52,7 +52,8 @@ def vae_decode_frames(x: torch.Tensor, vae, scaling_factor: float = SCALING_FACT
 @torch.inference_mode()
 def generate_latents(model, x_prompt: torch.Tensor, total_frames: int, noise_steps: int, noise_chunks: Optional[torch.Tensor] = None,
                      actions: Optional[torch.Tensor] = None, stabilization_level: int = 15, noise_abs_max: float = 20.0,
-                     clamp_min: float = 1e-4, ctx_cache: bool = False, hoist_cond: bool = True, rng=None) -> torch.Tensor:
+                     clamp_min: float = 1e-4, ctx_cache: bool = False, hoist_cond: bool = True, rng=None,
+                     guidance_scale: Optional[float] = None) -> torch.Tensor:
     """generate.py:186-220.  x_prompt (B, n_prompt, C, h, w) latents; noise_chunks (B, total-n_prompt, C, h, w)
     standard-normal draws (clamped to +-noise_abs_max here, generate.py:201-202); actions (B, total, 25) or None.
     ctx_cache=False re-runs the whole window on every noise step exactly like the reference;
@@ -62,9 +63,22 @@ def generate_latents(model, x_prompt: torch.Tensor, total_frames: int, noise_ste
     conditioning never depends on x); False recomputes it inside every step like DiT.forward does. Same results.
     Exactly one of noise_chunks and rng (a gtav_amd.rng.NoiseSource) is given.  With rng the clip takes one draw number and the new frames are filled in
     place on the device, clamp included: frame f of sample b is slot f of sample rng.sample0 + b (DESIGN.md "Noise streams").
+    guidance_scale s: classifier-free guidance on the actions — every step updates its frame from v_c + (s - 1)(v_c - v_u), v_u being the model's
+    external_cond=None branch, both from one fused step over 2 B internal samples (DiT.set_guidance; needs actions and max_batch >= 2 B).  The model's own
+    setting comes back afterwards; None (default) leaves the model as it is.
     Returns latents (B, total_frames, C, h, w) on the model's device."""
     if (noise_chunks is None) == (rng is None):
         raise ValueError("generate_latents: give exactly one of noise_chunks and rng")
+    if guidance_scale is not None:
+        if actions is None:
+            raise ValueError("generate_latents: guidance_scale needs actions (guidance pushes the frame from the action-free prediction towards the conditioned one)")
+        was = model._guidance
+        model.set_guidance(guidance_scale)
+        try:
+            return generate_latents(model, x_prompt, total_frames, noise_steps, noise_chunks, actions, stabilization_level, noise_abs_max,
+                                    clamp_min, ctx_cache, hoist_cond, rng)
+        finally:
+            model.set_guidance(was)
     dev = model.device
     B, n_prompt = x_prompt.shape[:2]
     x = torch.empty((B, total_frames, *x_prompt.shape[2:]), device=dev, dtype=torch.float32)
@@ -268,14 +282,15 @@ def shard_inputs(global_batch: int, rank: int, world: int, n_prompt: int, total_
 
 
 def generate_clip(dit, vae, frames: torch.Tensor, noise: Optional[torch.Tensor], total_frames: int, noise_steps: int,
-                  actions: Optional[torch.Tensor] = None, ctx_cache: bool = False, to_uint8: bool = True, gather: bool = True, rng=None):
+                  actions: Optional[torch.Tensor] = None, ctx_cache: bool = False, to_uint8: bool = True, gather: bool = True, rng=None,
+                  guidance_scale: Optional[float] = None):
     """One rank's whole clip (reference generate.py:main for its shard of the batch): VAE-encode the prompt frames,
     run the denoising loop, all-gather the final latents over the ranks (the path's only collective, RCCL over xGMI
     under the nccl backend) and decode this rank's own frames.  Exactly one of noise and rng (a NoiseSource whose sample0 is the global id of this rank's
-    first sample) is given, as in generate_latents.  Returns (gathered latents, decoded local frames)."""
+    first sample) is given, as in generate_latents; guidance_scale likewise.  Returns (gathered latents, decoded local frames)."""
     n_prompt = frames.shape[1]
     x0 = vae_encode(frames.to(vae.device), vae, n_prompt)
-    x = generate_latents(dit, x0, total_frames, noise_steps, noise, actions, ctx_cache=ctx_cache, rng=rng)
+    x = generate_latents(dit, x0, total_frames, noise_steps, noise, actions, ctx_cache=ctx_cache, rng=rng, guidance_scale=guidance_scale)
     xg = all_gather_latents(x) if gather else x
     out = vae_decode_frames(x, vae, to_uint8=to_uint8)
     vae.check()

@@ -86,6 +86,7 @@ SIGNATURES = {
     "gtav_dit_set_grad_divisor": [_p, _f],
     "gtav_dit_zero_grad": [_p, _p],
     "gtav_dit_train_forward": [_p, _p, _p, _p, _p, _i, _i, _p],
+    "gtav_dit_train_forward_keep": [_p, _p, _p, _p, _p, _p, _i, _i, _p],
     "gtav_dit_train_backward": [_p, _p, _p, _p],
     "gtav_dit_train_backward_phases": [_p, _p, _p, _i, _i, _p],
     "gtav_dit_train_param_range": [_p, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
@@ -98,6 +99,7 @@ SIGNATURES = {
     "gtav_dit_get_opt_step": [_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _p],
     "gtav_dit_set_opt_step": [_p, _l, _l, _p],
     "gtav_dit_set_graph": [_p, _i],
+    "gtav_dit_set_guidance": [_p, _i, _f],
     "gtav_dit_set_fused_temporal": [_p, _i],
     "gtav_dit_set_fused_spatial": [_p, _i],
     "gtav_dit_fused_launches": [_p, _i, _i, _i],

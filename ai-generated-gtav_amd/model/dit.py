@@ -226,6 +226,7 @@ class DiT(_HipModule):
         self._spatial_freqs = _w.rope_freqs_pixel(hd // 2, 256)   # model/dit.py:259-261
         self._temporal_freqs = _w.rope_freqs_lang(hd)             # model/dit.py:262
         self._schedule = None
+        self._guidance = None                # classifier-free guidance scale of the fused sampler step (set_guidance); None: off
         # operand groups (include/gtav_amd.h "operand type"): 2 l / 2 l + 1 = spatial / temporal half of block l, 2 depth = patch embedding, 2 depth + 1 = final layer
         self.n_operand_groups = 2 * depth + 2
         self._bf16_groups = set(range(self.n_operand_groups)) if self._train_bf16 else set()
@@ -335,6 +336,8 @@ class DiT(_HipModule):
                     _lib.check(L.gtav_dit_set_weight_prefetch(self._handle, int(self._weight_prefetch)))
                 if getattr(self, "_weight_fill_policy", None) is not None:
                     _lib.check(L.gtav_dit_set_weight_fill_policy(self._handle, int(self._weight_fill_policy)))
+                if self._guidance is not None:
+                    _lib.check(L.gtav_dit_set_guidance(self._handle, 1, self._guidance))
                 if not self._train_mixed:
                     for g in sorted(self._bf16_groups):                  # a re-created handle keeps the operand types chosen before
                         _lib.check(L.gtav_dit_set_operand_dtype(self._handle, g, 1))
@@ -381,8 +384,10 @@ class DiT(_HipModule):
     def reserve(self, max_batch: int, max_frames: Optional[int] = None, noise_steps: int = 0):
         """Sizes the handle's HBM workspace once for the largest batch / window / per-frame conditioning table a run will use
         (noise_steps + 1 row sets per generated frame), so that no later call has to rebuild the handle (which re-uploads the
-        weights and drops the captured hipGraphs)."""
+        weights and drops the captured hipGraphs).  While guidance is on (set_guidance) `max_batch` counts user samples: the handle is sized for the
+        2 x max_batch internal samples and the doubled conditioning table of a guided step."""
         T = max_frames or self._capacity_t
+        max_batch *= 2 if self._guidance is not None else 1
         self._ensure(max_batch, T, cond_rows=max_batch * (T - 1 + noise_steps + 1) if noise_steps else 0)
 
     def forward(self, x: torch.Tensor, t: torch.Tensor, external_cond: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -406,8 +411,9 @@ class DiT(_HipModule):
     # ------------------------------------------------------------------------------------------
     # training step (reference: train_dit.py:649-650, :680, :232-238, :965-970)
     # ------------------------------------------------------------------------------------------
-    def forward_train(self, x: torch.Tensor, t: torch.Tensor, external_cond: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """DiT.forward keeping the activations `backward_` needs (same result as forward)."""
+    def forward_train(self, x: torch.Tensor, t: torch.Tensor, external_cond: Optional[torch.Tensor] = None, action_keep=None) -> torch.Tensor:
+        """DiT.forward keeping the activations `backward_` needs (same result as forward).  action_keep (B,) of 0 / 1 (None: everyone keeps): per-sample
+        action dropout — a sample with 0 is conditioned as external_cond=None in all its frames, and backward_ honours the mask (gtav_dit_train_forward_keep)."""
         assert self._trainable, "construct the model with trainable=True"
         B, T, Cc, H, W = x.shape
         assert H == self.input_h and W == self.input_w
@@ -417,6 +423,16 @@ class DiT(_HipModule):
         td = t.to(dev, torch.int64).contiguous()
         ad = external_cond.to(dev, torch.float32).contiguous() if torch.is_tensor(external_cond) else None
         out = torch.empty_like(xd)
+        if action_keep is not None:
+            if ad is None:
+                raise ValueError("forward_train: action_keep without external_cond (there is nothing to drop)")
+            kd = torch.as_tensor(action_keep).reshape(-1).ne(0).to(dev, torch.int32).contiguous()
+            if kd.numel() != B:
+                raise ValueError(f"forward_train: action_keep has {kd.numel()} flags for a batch of {B}")
+            with torch.cuda.device(dev):
+                _lib.check(_lib.load().gtav_dit_train_forward_keep(self._handle, xd.data_ptr(), td.data_ptr(), ad.data_ptr(), kd.data_ptr(), out.data_ptr(), B, T,
+                                                                   _lib.current_stream()))
+            return out
         with torch.cuda.device(dev):
             _lib.check(_lib.load().gtav_dit_train_forward(self._handle, xd.data_ptr(), td.data_ptr(), _lib.ptr(ad), out.data_ptr(), B, T,
                                                           _lib.current_stream()))
@@ -751,11 +767,36 @@ class DiT(_HipModule):
             arr = (C.c_float * 1000).from_buffer_copy(ac.numpy().tobytes())
             _lib.check(_lib.load().gtav_dit_set_schedule(self._handle, arr, 1000))
 
+    def set_guidance(self, scale: Optional[float]):
+        """Classifier-free guidance on the actions for the fused sampler step (gtav_dit_set_guidance): with a scale s, prepare_frame_ / denoise_step_ run the
+        conditional and the external_cond=None branch as one forward over 2 B internal samples and update frame `cur` from v_c + (s - 1)(v_c - v_u)
+        (s = 1: v_c itself, s = 0: v_u).  None switches it off (the default: today's step bit for bit).  The model needs max_batch >= 2 B.  Changing the
+        scale between steps costs nothing (one captured step serves every scale); switching on / off drops the prepared table and the context cache."""
+        if scale is not None:
+            scale = float(scale)
+            if not math.isfinite(scale):
+                raise ValueError(f"set_guidance: scale {scale} is not finite")
+            if not self.external_cond_dim or self.external_cond_dim <= 0:
+                raise ValueError("set_guidance: this model has no external_cond (external_cond_dim=0): there are no actions to guide towards")
+        self._guidance = scale
+        if self._handle:
+            _lib.check(_lib.load().gtav_dit_set_guidance(self._handle, int(scale is not None), 1.0 if scale is None else scale))
+
+    def _internal_batch(self, B: int) -> int:
+        """Samples a sampler step of batch B runs inside the handle: 2 B while guidance is on.  A guided step never grows the handle by itself."""
+        if self._guidance is None:
+            return B
+        if 2 * B > self._capacity_b:
+            raise ValueError(f"a guided sampler step of batch {B} runs 2 B = {2 * B} internal samples: this model was built with max_batch={self._capacity_b}; "
+                             f"construct it with max_batch={2 * B} (or call reserve({B}) while guidance is on)")
+        return 2 * B
+
     def prepare_frame_(self, B: int, F: int, start: int, cur: int, t_ctx: int, t_steps, actions: Optional[torch.Tensor] = None):
         """Builds the conditioning (adaLN) table for every noise step of one generated frame (gtav_dit_prepare_frame);
         step k of that frame then passes cond_step=k to denoise_step_."""
         n = len(t_steps)
-        self._ensure(B, cur - start + 1, cond_rows=B * (cur - start + n))
+        Bi = self._internal_batch(B)
+        self._ensure(Bi, cur - start + 1, cond_rows=Bi * (cur - start + n))
         arr = (C.c_int32 * n)(*[int(v) for v in t_steps])
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().gtav_dit_prepare_frame(self._handle, B, F, start, cur, int(t_ctx), arr, n, _lib.ptr(actions),
@@ -768,7 +809,7 @@ class DiT(_HipModule):
         assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
         B, F = x.shape[:2]
         if cond_step < 0:
-            self._ensure(B, cur - start + 1)
+            self._ensure(self._internal_batch(B), cur - start + 1)
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().gtav_dit_denoise_step(
                 self._handle, x.data_ptr(), B, F, start, cur, int(t_ctx), int(t_cur), int(t_next), int(bool(is_final)),

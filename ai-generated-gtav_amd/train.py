@@ -21,7 +21,7 @@ def encode_frames(vae, frames: torch.Tensor) -> torch.Tensor:
 
 
 def _frame_step(dit, latents, actions, i, target_noise_idx, ctx_noise_idx, ctx_noise, noise, nr, ac, noise_abs_max, keep_activations, rng=None,
-                noise_steps=None, ctx_max_noise_idx=None):
+                noise_steps=None, ctx_max_noise_idx=None, action_keep=None):
     """One iteration of the frame loop of `_shared_step` (train_dit.py:590-650) for target frame i: returns (loss (1,), v_pred, v_target).
     With `rng` the frame takes one draw number: the two noise indices of every sample come from the host stream (train_dit.py:574-587) and the window's noise
     (slots 0 .. W - 1 of sample rng.sample0 + b) is drawn inside the one launch that noises the window and makes the v-target."""
@@ -64,7 +64,10 @@ def _frame_step(dit, latents, actions, i, target_noise_idx, ctx_noise_idx, ctx_n
             v_target = torch.empty_like(x_last)
             _lib.check(L.gtav_vtarget(x_last.data_ptr(), nz_last.data_ptr(), a_last.data_ptr(), v_target.data_ptr(), B, n,
                                       noise_abs_max, stream))
-    v_pred = dit.forward_train(x_noisy, t, a) if keep_activations else dit(x_noisy, t, a)
+    if action_keep is not None:
+        v_pred = dit.forward_train(x_noisy, t, a, action_keep=action_keep)             # (forward_loss: the mask needs the training forward)
+    else:
+        v_pred = dit.forward_train(x_noisy, t, a) if keep_activations else dit(x_noisy, t, a)
     out = torch.empty(1 + B, device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
         vp_last = v_pred[:, -1]
@@ -87,7 +90,7 @@ def _per_frame(arg, n_iter, what):
 @torch.inference_mode()
 def forward_loss(dit, latents: torch.Tensor, actions: Optional[torch.Tensor], target_noise_idx=None, ctx_noise_idx=None, ctx_noise=None, noise=None,
                  noise_steps: int = 50, n_prompt_frames: int = 4, noise_abs_max: float = 20.0, clamp_min: float = 1e-6,
-                 keep_activations: bool = False, on_frame=None, rng=None, ctx_max_noise_idx: Optional[int] = None):
+                 keep_activations: bool = False, on_frame=None, rng=None, ctx_max_noise_idx: Optional[int] = None, action_keep=None):
     """train_dit.py:590-682 `_shared_step`: for every target frame i in [n_prompt_frames, total_frames) noise the window that ends at i,
     run the DiT over it, MSE against the v-target of frame i; returns (mean loss over the target frames (1,), v_pred, v_target) of the LAST
     target frame.  The shipped dataset has ONE target frame (5-frame clips): then the draws are plain tensors — target_noise_idx /
@@ -97,7 +100,11 @@ def forward_loss(dit, latents: torch.Tensor, actions: Optional[torch.Tensor], ta
     is called after target frame k's forward (the trainer differentiates each frame's loss right there, train_dit.py:679-680).
     rng (a gtav_amd.rng.NoiseSource) in place of the four draws, which must then be None: every target frame takes one draw number of it, target index in
     [1, noise_steps], context index in [1, ctx_max_noise_idx] (required; config.ctx_max_noise_idx of the reference) capped by the target index, the window's
-    noise from slots 0 .. W - 1 of that draw (DESIGN.md "Noise streams")."""
+    noise from slots 0 .. W - 1 of that draw (DESIGN.md "Noise streams").
+    action_keep (B,) of 0 / 1, or None: per-sample action dropout (draw_action_keep; the reference's commented-out train_dit.py:704-705) — a sample with 0 is
+    conditioned as external_cond=None in every target frame's forward.  It lives in the training forward: needs keep_activations=True and actions."""
+    if action_keep is not None and not (keep_activations and actions is not None):
+        raise ValueError("forward_loss: action_keep needs keep_activations=True (the training forward) and actions")
     _rng.check_exclusive(rng, "forward_loss", target_noise_idx=target_noise_idx, ctx_noise_idx=ctx_noise_idx, ctx_noise=ctx_noise, noise=noise)
     if rng is not None and ctx_max_noise_idx is None:
         raise ValueError("forward_loss: rng= needs ctx_max_noise_idx (the upper end of the context noise index, config.ctx_max_noise_idx)")
@@ -113,10 +120,10 @@ def forward_loss(dit, latents: torch.Tensor, actions: Optional[torch.Tensor], ta
     for k, i in enumerate(range(n_prompt_frames, total)):
         if rng is None:
             loss, v_pred, v_target = _frame_step(dit, latents, actions, i, tgts[k].cpu().tolist(), ctxs[k].cpu().tolist(), cns[k], nzs[k], nr, ac,
-                                                 noise_abs_max, keep_activations)
+                                                 noise_abs_max, keep_activations, action_keep=action_keep)
         else:
             loss, v_pred, v_target = _frame_step(dit, latents, actions, i, None, None, None, None, nr, ac, noise_abs_max, keep_activations, rng,
-                                                 int(noise_steps), int(ctx_max_noise_idx))
+                                                 int(noise_steps), int(ctx_max_noise_idx), action_keep=action_keep)
         if on_frame is not None:
             on_frame(k, v_pred, v_target)
         if total_loss is None:
@@ -151,11 +158,12 @@ def decode_frames(vae, latents: torch.Tensor) -> torch.Tensor:
 @torch.inference_mode()
 def predict(dit, vae, frames: torch.Tensor, actions: Optional[torch.Tensor], new_frame_noise: Optional[torch.Tensor] = None, num_frames: int = 32,
             n_prompt_frames: int = 4, ddim_noise_steps: int = 50, ddim_noise_steps_inference: int = 50, noise_abs_max: float = 20.0,
-            decode: bool = True, rng=None):
+            decode: bool = True, rng=None, guidance_scale: Optional[float] = None):
     """train_dit.py:370-466 `predict`: first sample of the batch, prompt = its first n_prompt_frames, actions padded with "W"
     (index 3) up to num_frames, autoregressive generation with the trainer's constants.  new_frame_noise (1, num_frames -
     n_prompt_frames, C, h, w): the standard-normal draw of every generated frame, or rng= (a NoiseSource: one draw number, made on the device
-    as in generate_latents) in its place.  Returns (latents (1, num_frames, C, h, w), uint8 video (1, num_frames, H, W, 3) or None)."""
+    as in generate_latents) in its place.  guidance_scale: classifier-free guidance on the actions, as in generate_latents (needs actions and a model with
+    max_batch >= 2).  Returns (latents (1, num_frames, C, h, w), uint8 video (1, num_frames, H, W, 3) or None)."""
     from .generate import generate_latents
     _rng.check_exclusive(rng, "predict", new_frame_noise=new_frame_noise)
     frames = frames[:1, :n_prompt_frames]
@@ -168,7 +176,7 @@ def predict(dit, vae, frames: torch.Tensor, actions: Optional[torch.Tensor], new
             act = torch.cat([act, pad], dim=1)
     x = encode_frames(vae, frames.to(vae.device))
     lat = generate_latents(dit, x, num_frames, ddim_noise_steps_inference, new_frame_noise, act,
-                           stabilization_level=stabilization_level(ddim_noise_steps), noise_abs_max=noise_abs_max, clamp_min=1e-6, rng=rng)
+                           stabilization_level=stabilization_level(ddim_noise_steps), noise_abs_max=noise_abs_max, clamp_min=1e-6, rng=rng, guidance_scale=guidance_scale)
     return lat, (decode_frames(vae, lat) if decode else None)
 
 
@@ -307,11 +315,13 @@ def backward_overlapped(dit, v_pred, v_target, world_size: int, comm_stream=None
 def training_step(dit, latents: torch.Tensor, actions: Optional[torch.Tensor], target_noise_idx=None, ctx_noise_idx=None, ctx_noise=None, noise=None,
                   lr: float = None, weight_decay: float = 0.0, max_grad_norm: float = 1.0, world_size: int = 1, noise_steps: int = 50,
                   n_prompt_frames: int = 4, noise_abs_max: float = 20.0, clamp_min: float = 1e-6, overlap_all_reduce: bool = True, comm_stream=None,
-                  all_reduce=None, bucket_timings=None, rng=None, ctx_max_noise_idx: Optional[int] = None):
+                  all_reduce=None, bucket_timings=None, rng=None, ctx_max_noise_idx: Optional[int] = None, action_keep=None):
     """One optimisation step on a batch of latent clips: for every target frame forward + loss and its backward (train_dit.py:590-680: each
     frame's loss is differentiated inside the frame loop, the gradients add up), gradient all-reduce (bucketed and overlapped with the LAST
     frame's backward pass when world_size > 1), clip, AdamW.  Returns the mean loss over the target frames, a (1,) tensor.
-    rng / ctx_max_noise_idx: as forward_loss — the step draws its own noise indices and noise, the four draw arguments stay None."""
+    rng / ctx_max_noise_idx: as forward_loss — the step draws its own noise indices and noise, the four draw arguments stay None.
+    action_keep: as forward_loss — per-sample action dropout for classifier-free guidance (each rank draws its own samples' flags with draw_action_keep:
+    nothing new is reduced across ranks)."""
     _rng.check_exclusive(rng, "training_step", target_noise_idx=target_noise_idx, ctx_noise_idx=ctx_noise_idx, ctx_noise=ctx_noise, noise=noise)
     if rng is not None and ctx_max_noise_idx is None:
         raise ValueError("training_step: rng= needs ctx_max_noise_idx (the upper end of the context noise index, config.ctx_max_noise_idx)")
@@ -328,11 +338,20 @@ def training_step(dit, latents: torch.Tensor, actions: Optional[torch.Tensor], t
             dit.backward_(v_pred, v_target)
 
     loss, _, _ = forward_loss(dit, latents, actions, target_noise_idx, ctx_noise_idx, ctx_noise, noise, noise_steps, n_prompt_frames,
-                              noise_abs_max, clamp_min, keep_activations=True, on_frame=on_frame, rng=rng, ctx_max_noise_idx=ctx_max_noise_idx)
+                              noise_abs_max, clamp_min, keep_activations=True, on_frame=on_frame, rng=rng, ctx_max_noise_idx=ctx_max_noise_idx,
+                              action_keep=action_keep)
     if not overlap:
         all_reduce_gradients(dit, world_size)
     dit.adamw_step(lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
     return loss
+
+
+def draw_action_keep(B: int, p: float = 0.1, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """The keep flags of per-sample action dropout (the reference's commented-out train_dit.py:704-705 drops the actions with probability 0.1): (B,) int32 on the
+    host, 0 with probability p.  Drawn from `generator` (a CPU torch.Generator; None: the global one), so a seeded run repeats its mask."""
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"draw_action_keep: p={p} is not a probability")
+    return (torch.rand(B, generator=generator) >= p).to(torch.int32)
 
 
 ERR_F16_SAT = 2      # csrc/common.h: the saturation bit of a device error word

@@ -115,6 +115,22 @@ int gtav_dit_denoise_step(gtav_dit* h, float* x_dev, int32_t B, int32_t F, int32
 int gtav_dit_prepare_frame(gtav_dit* h, int32_t B, int32_t F, int32_t start, int32_t cur, int32_t t_ctx,
                            const int32_t* t_steps_host, int32_t n_steps, const float* actions_dev, void* stream);
 
+/* Classifier-free guidance on the actions.  The reference conditions on c = t_emb(t) + external_cond(actions) or, with
+ * external_cond=None, on c = t_emb(t) alone (model/dit.py:359-366), and its training script carries the matching 10 % action
+ * dropout commented out (train_dit.py:704-705).  While guidance is on (default: off, today's path bit for bit), gtav_dit_denoise_step and
+ * gtav_dit_prepare_frame on this handle run guided: ONE forward over 2 B internal samples — [0, B) with the actions (v_c), [B, 2 B)
+ * the external_cond=None branch (v_u: no W_ext a and no b_ext, NOT zeroed actions) on the same frames of x — and frame `cur` is
+ * updated from
+ *     d = v_c - v_u,   m = (scale - 1) d,   v_g = v_c + m      (three separately rounded fp32 operations, never an fma:
+ *                                                               scale = 1 gives v_c itself, numpy float32 gives the same bits)
+ * through the same DDIM update; v_out receives v_g.  Mode-1 steps then cache the temporal K/V of 2 B samples, and prepare_frame
+ * builds 2 B (cur - start + n_steps) rows: first the conditional table as always, then the unconditional one.
+ * Refused: a model without external_cond, a non-finite scale, max_batch < 2 (here); actions == NULL, 2 B > max_batch, the doubled rows
+ * beyond max_cond_rows (in the step / prepare_frame).  Switching `enable` invalidates the prepared table and the recorded K/V window:
+ * a mode-1 step or a cond_step >= 0 step straight after fails as after a gtav_dit_forward.  Changing only the scale invalidates
+ * nothing — it is read from device memory, so one captured step replays under a guidance schedule.  enable == 0 ignores `scale`. */
+int gtav_dit_set_guidance(gtav_dit* h, int32_t enable, float scale);
+
 /* The fused step replays a captured hipGraph per (shape, buffers) key by default; this call switches to plain
  * launches (results are identical). */
 int gtav_dit_set_graph(gtav_dit* h, int32_t enable);
@@ -266,6 +282,17 @@ int gtav_dit_zero_grad(gtav_dit* h, void* stream);
 /* DiT.forward in training mode: same result as gtav_dit_forward, keeps the activations the backward pass needs. */
 int gtav_dit_train_forward(gtav_dit* h, const float* x_dev, const int64_t* t_dev, const float* actions_dev, float* out_dev,
                            int32_t B, int32_t T, void* stream);
+/* The same with per-sample action dropout, the training half of classifier-free guidance (the reference carries it commented out as a 10 %
+ * dropout, train_dit.py:704-705): keep_dev holds B int32 flags (device); a sample with keep[b] == 0 is conditioned for all its frames as
+ * the reference conditions external_cond=None (model/dit.py:359-366: c = t_emb(t), neither W_ext a nor b_ext).  The mask is saved with
+ * the forward and the backward entry points honour it: external_cond.bias is summed over the kept rows only, external_cond.weight sees
+ * zero action rows for the dropped ones, everything else is unchanged.  Every row gets its bias (b_t2 + b_ext or b_t2) in one add, so
+ * keep all ones is gtav_dit_train_forward with actions bit for bit, and keep all zeros is gtav_dit_train_forward with actions = NULL bit for
+ * bit, external_cond gradients exactly zero.  keep_dev == NULL is gtav_dit_train_forward; a mask needs actions.  fp16, bf16, mixed,
+ * recompute and LoRA handles alike: the conditioning path is the exact-fp32 one they share. */
+int gtav_dit_train_forward_keep(gtav_dit* h, const float* x_dev, const int64_t* t_dev, const float* actions_dev,
+                                const int32_t* keep_dev /* B, or NULL = gtav_dit_train_forward */, float* out_dev,
+                                int32_t B, int32_t T, void* stream);
 /* Adds loss_scale * d mean((v_pred[:, -1] - v_target)^2) / d theta to the gradient arena.  v_pred (B,T,C,H,W) as returned by
  * gtav_dit_train_forward, v_target (B,C,H,W). */
 int gtav_dit_train_backward(gtav_dit* h, const float* v_pred_dev, const float* v_target_dev, void* stream);
