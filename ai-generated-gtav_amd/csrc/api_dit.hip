@@ -386,6 +386,7 @@ void gtav_dit_destroy(gtav_dit* h) { delete h; }
 
 int gtav_dit_set_weight(gtav_dit* h, const char* name, const float* src, int64_t numel, void* stream) {
     GTAV_REQUIRE(h && name && src, "dit_set_weight: null argument");
+    RET_IF(train_not_swapped(h, "dit_set_weight"));
     std::string n(name);
     // any alias of the two shared rotary freqs parameters
     if (n.size() > 16 && n.compare(n.size() - 16, 16, "rotary_emb.freqs") == 0) {

@@ -60,6 +60,7 @@ struct Slot {
     // training (gtav_dit_train_enable): fp32 master copy (f16 slots; f32 slots train in place), gradient (contiguous [R][C], a
     // slice of the gradient arena), AdamW moments, and for f16 GEMM weights the tile-major copy of the TRANSPOSE (dX = dY W)
     float *master = nullptr, *grad = nullptr, *am = nullptr, *av = nullptr;
+    float* ema = nullptr;   // averaged weights of a trainable slot (gtav_dit_train_set_ema): fp32 shadow, contiguous [R][C] like am / av; null without them
     f16* wT = nullptr;
     bool trainable = false;
     // operand type of an f16 slot's device image (common.h "operand type"): the group of layers it belongs to (gtav_dit_set_operand_dtype; -1 = the handle
@@ -115,6 +116,7 @@ struct WeightTable {
         else RET_IF(launch_copy_f32(src, sl.C, sl.R, sl.C, (float*)sl.dst, sl.Cp, sl.c0, s));
         if (sl.master && sl.kind == SLOT_F16_PAD) RET_IF(launch_copy_f32(src, sl.C, sl.R, sl.C, sl.master, sl.C, 0, s));
         if (sl.wT) RET_IF(operand_ops(sl.bf16).convert_T(src, sl.C, sl.R, sl.C, sl.wT, s));
+        if (sl.ema) RET_IF(launch_copy_f32(src, sl.C, sl.R, sl.C, sl.ema, sl.C, 0, s));   // a freshly loaded model starts with its average = its weights
         sl.set = true;
         return 0;
     }
@@ -475,6 +477,11 @@ struct gtav_dit {
         // the backward re-runs a block's forward just before differentiating it.  res / hb keep their 4 L + 1 / 2 L entries, as aliases: res[k], k % 4 != 0, is
         // one of three ring states, hb[i] is image set i % 2.  rc_block: the block whose ring states and images are in place (-1: none); kshift[l], l >= 1: the
         // statistics' shift of every row in the first LayerNorm of block l (LnPending::k_save), which the re-run of that launch needs to give the same bits.
+        // Averaged weights (gtav_dit_train_set_ema; DESIGN.md 7 "Averaged weights"): ema_decay > 0 = every trainable slot has an fp32 shadow (Slot::ema) that the
+        // optimizer launch moves towards the master it just wrote.  ema_swapped: gtav_dit_train_swap_ema exchanged masters and shadow (the images are those of
+        // the average): inference runs, the training step and everything that would write either side is refused until the swap back.
+        float ema_decay = 0.f;
+        bool ema_warmup = false, ema_swapped = false;
         bool recompute = false;
         int rc_block = -1;
         std::vector<float*> kshift;
@@ -509,7 +516,7 @@ struct gtav_dit {
         Linear fin, fin_ada, pe, t0, t2, ext;
         float* grad_arena = nullptr;        // all gradients, contiguous (one all-reduce); caller-owned when passed to train_enable
         size_t grad_count = 0;
-        float* ctl = nullptr;               // [8]: sumsq, step coefficient, skipped steps, grad norm, applied steps, bias corrections
+        float* ctl = nullptr;               // [8]: sumsq, step coefficient, skipped steps, grad norm, applied steps, bias corrections, [7] the averaged weights' decay of the step being applied (ema_decay > 0 only)
         float *ln_part = nullptr;   // per-(frame, 16-row chunk) partial rows of the fused LayerNorm backward (train.hip ln_mod_bwd_fused_kernel)
         float *red_ws = nullptr, *sumsq_part = nullptr;   // partial sums of the fixed-order reductions (bias gradients, gradient norm)
         size_t red_ws_floats = 0;           // size of red_ws: what train_enable allocated is what the backward pass's fusions are bounded by
@@ -532,3 +539,5 @@ struct gtav_dit {
 // Low-rank adapters (api_train.hip): the merge of every adapted weight's images, and of the one Linear a weight upload touched
 int train_lora_merge_all(gtav_dit* h, hipStream_t s);
 int train_lora_after_set(gtav_dit* h, const std::string& name, hipStream_t s);
+// Averaged weights (api_train.hip): refuses `who` by name while the average is swapped in (gtav_dit_train_swap_ema)
+int train_not_swapped(const gtav_dit* h, const char* who);

@@ -111,6 +111,12 @@ int train_lora_merge_all(gtav_dit* h, hipStream_t s) {
 }
 // gtav_dit_set_weight of an adapter or of an adapted base weight: once all three tensors of that Linear have arrived its images are merged again, so the
 // order of the uploads does not matter (an upload of the base alone wrote the plain images: WeightTable::set)
+// While the averaged weights are swapped in the masters hold the average and the shadow the iterate: the saved activations, the optimizer and every upload belong
+// to the other weights.
+int train_not_swapped(const gtav_dit* h, const char* who) {
+    GTAV_REQUIRE(!h->tr.ema_swapped, "%s: the averaged weights are swapped in (gtav_dit_train_swap_ema); swap the trained weights back first", who);
+    return 0;
+}
 int train_lora_after_set(gtav_dit* h, const std::string& name, hipStream_t s) {
     if (!h->tr.lora.rank || !h->tr.on) return 0;
     for (const auto& L : h->tr.lora.linears) {
@@ -164,6 +170,7 @@ static int train_enable_body(gtav_dit* h, float* grad_arena_dev, int64_t grad_ar
         off += n;
         RET_IF(a.alloc_t(&sl->am, n));
         RET_IF(a.alloc_t(&sl->av, n));
+        if (t.ema_decay > 0.f) RET_IF(a.alloc_t(&sl->ema, n));   // the averaged weights: 4 bytes per trainable parameter more
         if (sl->kind == SLOT_F16_PAD) {
             RET_IF(a.alloc_t(&sl->master, n));
             if (names[pi] != "x_embedder.proj.weight")   // every GEMM weight but the patch embedding needs W^T for dX
@@ -195,7 +202,7 @@ static int train_enable_body(gtav_dit* h, float* grad_arena_dev, int64_t grad_ar
             AdamParam d;
             memset(&d, 0, sizeof(d));
             const bool f16w = sl->kind == SLOT_F16_PAD;
-            d.p = sl->master; d.ldp = f16w ? sl->C : sl->Cp; d.R = sl->R; d.C = sl->C; d.g = sl->grad; d.m = sl->am; d.v = sl->av;
+            d.p = sl->master; d.ldp = f16w ? sl->C : sl->Cp; d.R = sl->R; d.C = sl->C; d.g = sl->grad; d.m = sl->am; d.v = sl->av; d.e = sl->ema;
             if (f16w) { d.w16 = (f16*)sl->dst; d.Cp16 = sl->Cp; d.wT = sl->wT; d.RpT = round_up(sl->R, 64); }
             ap.push_back(d);
             if (f16w) {
@@ -333,6 +340,19 @@ int gtav_dit_train_set_lora(gtav_dit* h, int32_t rank, float alpha) {
         }
     h->tr.lora.rank = rank; h->tr.lora.alpha = alpha; h->tr.lora.s = alpha / (float)rank;
     h->finalized = false;
+    return 0;
+}
+
+// Opt-in to averaged weights (api_internal.h Train::ema_decay; DESIGN.md 7 "Averaged weights").  Between create and train_enable it turns the shadow on (allocated
+// by train_enable); on an enabled handle that has one it changes the decay and the warm-up of the steps to come.  The decay is checked first: a bad one is refused
+// whatever the handle.
+int gtav_dit_train_set_ema(gtav_dit* h, float decay, int32_t warmup) {
+    GTAV_REQUIRE(decay > 0.f && decay < 1.f, "train_set_ema: decay=%g outside (0, 1)", (double)decay);
+    GTAV_REQUIRE(h, "train_set_ema: null handle");
+    GTAV_REQUIRE(!h->tr.on || h->tr.ema_decay > 0.f, "train_set_ema: training is already enabled on this handle without averaged weights; the shadow is allocated by "
+                 "gtav_dit_train_enable and cannot be turned on or off afterwards (call it between gtav_dit_create and gtav_dit_train_enable)");
+    h->tr.ema_decay = decay;
+    h->tr.ema_warmup = warmup != 0;
     return 0;
 }
 
@@ -528,6 +548,7 @@ int gtav_dit_train_forward_keep(gtav_dit* h, const float* x, const int64_t* t64,
 static int train_forward_impl(gtav_dit* h, const float* x, const int64_t* t64, const float* actions, const int32_t* keep, float* out, int32_t B, int32_t T, void* stream) {
     GTAV_REQUIRE(h && x && t64 && out, "train_forward: null argument");
     GTAV_REQUIRE(h->tr.on && h->finalized, "train_forward: call gtav_dit_train_enable, load the weights and finalize first");
+    RET_IF(train_not_swapped(h, "train_forward"));
     GTAV_REQUIRE(B >= 1 && B <= h->maxB && T >= 1 && T <= h->maxT, "train_forward: B=%d T=%d outside capacity (%d, %d)", B, T, h->maxB, h->maxT);
     GTAV_REQUIRE(!actions || h->A > 0, "train_forward: model has no external_cond");
     hipStream_t s = (hipStream_t)stream;
@@ -815,6 +836,7 @@ extern "C" {
 // and the shared conditioning path (t_embedder, external_cond).  tr.dres / tr.dmod carry the state from one phase to the next.
 int gtav_dit_train_backward_phases(gtav_dit* h, const float* v_pred, const float* v_target, int32_t phase_begin, int32_t phase_end, void* stream) {
     GTAV_REQUIRE(h && v_pred && v_target, "train_backward: null argument");
+    RET_IF(train_not_swapped(h, "train_backward"));
     GTAV_REQUIRE(h->tr.on && h->tr.have_fwd, "train_backward: no saved forward (gtav_dit_train_forward)");
     GTAV_REQUIRE(phase_begin >= 0 && phase_begin <= phase_end && phase_end <= h->L + 2, "train_backward: phases [%d, %d) outside [0, %d]", phase_begin, phase_end,
                  h->L + 2);
@@ -863,18 +885,25 @@ int gtav_dit_train_param_range(gtav_dit* h, const char* prefix, int64_t* offset,
 // non-finite norm skips the step) -> AdamW -> refreshed fp16 operand copies (W and W^T) of the GEMM weights.
 int gtav_dit_adamw_step(gtav_dit* h, float lr, float beta1, float beta2, float eps, float weight_decay, float max_grad_norm, void* stream) {
     GTAV_REQUIRE(h && h->tr.on, "adamw_step: training is not enabled");
+    RET_IF(train_not_swapped(h, "adamw_step"));
     hipStream_t s = (hipStream_t)stream;
     gtav_dit::Train& tr = h->tr;
     if (tr.mixed) RET_IF(launch_err_fold(h->err_flag, tr.range_words, 0, h->n_groups, s));   // (the bits of recompute mode's re-runs, raised after the forward's fold)
     RET_IF(launch_sumsq(tr.grad_arena, tr.grad_count, tr.sumsq_part, s));
     // overflow (non-finite norm, or a saturated fp16 gradient / activation recorded in the error word) skips the step on the device; the
     // Adam step count and its bias corrections live in ctl[4..6] and advance only with applied steps
-    RET_IF(launch_clip_coef(tr.ctl, tr.sumsq_part, sumsq_parts(tr.grad_count), 1.0f / (tr.loss_scale * tr.grad_div), max_grad_norm, beta1, beta2, h->err_flag, s));
+    // (a handle with averaged weights: the decay of this applied step goes to ctl[7] beside the bias corrections)
+    RET_IF(launch_clip_coef(tr.ctl, tr.sumsq_part, sumsq_parts(tr.grad_count), 1.0f / (tr.loss_scale * tr.grad_div), max_grad_norm, beta1, beta2, tr.ema_decay,
+                            tr.ema_warmup, h->err_flag, s));
     // one launch per operand type in use (one, unless a mixed-capable handle has groups of both): AdamW on every parameter + the 2-byte W / W^T operands of the
     // GEMM weights rewritten from the updated masters in their group's type.  The work items are independent, so the split changes no bit.
+    // A handle with averaged weights runs the instantiation that also moves the shadow towards the master it just wrote (train.hip ADAM_STEP_EMA).
     for (int ty = 0; ty < 2; ++ty)
-        if (tr.adam_n[ty])
-            RET_IF(operand_ops(ty != 0).adamw_multi(tr.adam_params, tr.adam_items + (ty ? tr.adam_n[0] : 0), tr.adam_n[ty], tr.ctl, lr, beta1, beta2, eps, weight_decay, s));
+        if (tr.adam_n[ty]) {
+            const OperandOps& o = operand_ops(ty != 0);
+            RET_IF((tr.ema_decay > 0.f ? o.adamw_multi_ema : o.adamw_multi)(tr.adam_params, tr.adam_items + (ty ? tr.adam_n[0] : 0), tr.adam_n[ty], tr.ctl, lr, beta1,
+                                                                           beta2, eps, weight_decay, s));
+        }
     // a LoRA handle: the step moved the adapters only; every adapted weight's two images = clamp(W0 + s B A) again, one launch over all their tiles
     if (tr.lora.rank) RET_IF(train_lora_merge_all(h, s));
     RET_IF(launch_add_f32(h->b_t2, h->b_ext, h->b_t2a, h->D, s));   // fused bias of c when actions are given (gtav_dit_finalize)
@@ -948,6 +977,7 @@ extern "C" {
 
 int gtav_dit_train_set_group_dtype(gtav_dit* h, int32_t group, int32_t dtype, void* stream) {
     RET_IF(train_mixed_handle(h, "train_set_group_dtype"));
+    RET_IF(train_not_swapped(h, "train_set_group_dtype"));
     GTAV_REQUIRE(dtype == GTAV_OPERAND_F16 || dtype == GTAV_OPERAND_BF16, "train_set_group_dtype: dtype %d (0 = fp16, 1 = bf16)", dtype);
     GTAV_REQUIRE(group >= -1 && group < h->n_groups, "train_set_group_dtype: group %d outside [-1, %d)", group, h->n_groups);
     int n = 0;
@@ -971,6 +1001,7 @@ int gtav_dit_train_range_words(gtav_dit* h, int32_t* words_host, void* stream) {
 // an error, the handle its old types, and the saturation would come back with the next step.)
 int gtav_dit_train_autorange(gtav_dit* h, const int32_t* merged_words_host, int32_t* n_switched, void* stream) {
     RET_IF(train_mixed_handle(h, "train_autorange"));
+    RET_IF(train_not_swapped(h, "train_autorange"));
     GTAV_REQUIRE(n_switched, "train_autorange: null argument");
     *n_switched = 0;
     hipStream_t s = (hipStream_t)stream;
@@ -1024,6 +1055,51 @@ int gtav_dit_set_opt_state(gtav_dit* h, const char* name, const float* m_src, co
     GTAV_REQUIRE(m_src && v_src, "set_opt_state: null source");
     GTAV_CHECK_HIP(hipMemcpyAsync(sl->am, m_src, (size_t)numel * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     GTAV_CHECK_HIP(hipMemcpyAsync(sl->av, v_src, (size_t)numel * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+// The averaged weights of one trainable parameter, torch layout (the shadow is contiguous in the parameter's state-dict shape, like the moments).
+static int ema_slot(gtav_dit* h, const char* who, const char* name, int64_t numel, Slot** out) {
+    GTAV_REQUIRE(h && name && h->tr.on, "%s: training is not enabled", who);
+    GTAV_REQUIRE(h->tr.ema_decay > 0.f, "%s: this handle keeps no averaged weights (gtav_dit_train_set_ema before gtav_dit_train_enable)", who);
+    RET_IF(train_not_swapped(h, who));
+    auto it = h->wt.slots.find(name);
+    GTAV_REQUIRE(it != h->wt.slots.end() && it->second.trainable && it->second.ema, "%s: '%s' is not a trainable parameter", who, name);
+    GTAV_REQUIRE(numel == (int64_t)it->second.R * it->second.C, "%s: '%s' has %d x %d elements, got %lld", who, name, it->second.R, it->second.C, (long long)numel);
+    *out = &it->second;
+    return 0;
+}
+int gtav_dit_get_ema(gtav_dit* h, const char* name, float* dst, int64_t numel, void* stream) {
+    Slot* sl = nullptr;
+    RET_IF(ema_slot(h, "get_ema", name, numel, &sl));
+    GTAV_REQUIRE(dst, "get_ema: null destination");
+    GTAV_CHECK_HIP(hipMemcpyAsync(dst, sl->ema, (size_t)numel * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+int gtav_dit_set_ema(gtav_dit* h, const char* name, const float* src, int64_t numel, void* stream) {
+    Slot* sl = nullptr;
+    RET_IF(ema_slot(h, "set_ema", name, numel, &sl));
+    GTAV_REQUIRE(src, "set_ema: null source");
+    GTAV_CHECK_HIP(hipMemcpyAsync(sl->ema, src, (size_t)numel * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+// Masters <-> shadow, and the handle computes with what the masters now hold: one swap launch per operand type in use over the optimizer's own partition (the
+// 2-byte images come out as a step that had produced those masters would have written them), then what the end of gtav_dit_adamw_step does.  Calling it again
+// swaps back: the exchange moves fp32 words and the images are a function of the masters, so the handle is bit for bit where it was.
+int gtav_dit_train_swap_ema(gtav_dit* h, void* stream) {
+    GTAV_REQUIRE(h && h->tr.on, "train_swap_ema: training is not enabled");
+    gtav_dit::Train& tr = h->tr;
+    GTAV_REQUIRE(tr.ema_decay > 0.f, "train_swap_ema: this handle keeps no averaged weights (gtav_dit_train_set_ema before gtav_dit_train_enable)");
+    GTAV_REQUIRE(h->finalized, "train_swap_ema: load the weights and finalize first");
+    hipStream_t s = (hipStream_t)stream;
+    for (int ty = 0; ty < 2; ++ty)
+        if (tr.adam_n[ty]) RET_IF(operand_ops(ty != 0).adamw_swap_ema(tr.adam_params, tr.adam_items + (ty ? tr.adam_n[0] : 0), tr.adam_n[ty], s));
+    if (tr.lora.rank) RET_IF(train_lora_merge_all(h, s));   // (the adapters were swapped: every adapted weight's images = clamp(W0 + s B A) of the ones in place)
+    RET_IF(launch_add_f32(h->b_t2, h->b_ext, h->b_t2a, h->D, s));
+    h->prepared.valid = false;
+    h->kvrec.valid = false;
+    tr.have_fwd = false;   // the saved activations are those of the other weights
+    tr.rc_block = -1;
+    tr.ema_swapped = !tr.ema_swapped;
     return 0;
 }
 int gtav_dit_get_opt_step(gtav_dit* h, int64_t* applied_steps, int64_t* skipped_steps, void* stream) {

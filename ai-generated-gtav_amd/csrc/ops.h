@@ -161,7 +161,9 @@ int launch_err_clear(int* err_flag, int bits, hipStream_t stream);
 // saturated until gtav_dit_train_range_words / gtav_dit_train_autorange read them.  (nullptr, 1) is gtav_dit_zero_grad's: bits an inference forward left in
 // the group words are not this step's, and wait in word 1 for gtav_dit_check.
 int launch_err_fold(int* words, int* sticky, int dst_word, int n_groups, hipStream_t stream);
-int launch_clip_coef(float* ctl, const float* part, int nparts, float inv_scale, float max_norm, float beta1, float beta2, int* err_flag, hipStream_t stream);
+// ema_decay > 0 (a handle with averaged weights): ctl[7] = the decay of the step being applied, ema_decay or with ema_warmup min(ema_decay, (1 + t) / (10 + t))
+int launch_clip_coef(float* ctl, const float* part, int nparts, float inv_scale, float max_norm, float beta1, float beta2, float ema_decay, int ema_warmup,
+                     int* err_flag, hipStream_t stream);
 int launch_adamw(float* p, int ldp, int R, int C, const float* g, float* m, float* v, const float* ctl, float lr, float beta1, float beta2, float eps,
                  float wd, hipStream_t stream);
 // Low-rank adapters (ops_typed.inc launch_lora_grads): the planning of the gradient launches, pure host arithmetic.  The contraction over the M token rows is

@@ -42,6 +42,8 @@ namespace gtav {
     F(attn_spatial_bwd, launch_attn_spatial_bwd)            \
     F(attn_temporal_bwd, launch_attn_temporal_bwd)          \
     F(adamw_multi, launch_adamw_multi)                      \
+    F(adamw_multi_ema, launch_adamw_multi_ema)              \
+    F(adamw_swap_ema, launch_adamw_swap_ema)                \
     F(lora_merge, launch_lora_merge)                        \
     F(lora_merge_one, launch_lora_merge_one)                \
     F(lora_grads, launch_lora_grads)                        \

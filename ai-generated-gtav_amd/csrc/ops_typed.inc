@@ -98,16 +98,23 @@ int launch_attn_temporal_bwd(const f16* q, const f16* kv, const f16* dO, int B, 
 struct AdamParam {
     float* p; int ldp, R, C;               // fp32 master (GEMM weights: contiguous [R][C]; fp32 parameters: in place, leading dimension ldp)
     const float* g; float *m, *v;          // gradient (scaled), AdamW moments, contiguous [R][C]
+    float* e;                              // averaged weights (the fp32 shadow, contiguous [R][C] like m and v), or null on a handle without them
     f16* w16; int Cp16;                    // GEMM weights: tile-major fp16 W (logical row length Cp16), else null
     f16* wT; int RpT;                      // tile-major fp16 W^T (logical row length RpT = round_up(R, 64)), or null
 };
-static_assert(sizeof(AdamParam) == 80, "AdamParam: every build and both operand types must see the same struct");
+static_assert(sizeof(AdamParam) == 88, "AdamParam: every build and both operand types must see the same struct");
 struct AdamItem { int param; unsigned start; };   // GEMM weight: tile index (row-major over 64 x 64 tiles); fp32 parameter: first element
 static_assert(sizeof(AdamItem) == 8, "AdamItem: every build and both operand types must see the same struct");
 // ctl [8] floats: [0] sum of squares of the scaled gradients, [1] step coefficient (0 = step skipped), [2] skipped steps, [3] unscaled gradient
-// norm, [4] applied steps (the Adam step count), [5] / [6] bias corrections of the step being applied (written by clip_coef on the device)
+// norm, [4] applied steps (the Adam step count), [5] / [6] bias corrections of the step being applied (written by clip_coef on the device),
+// [7] decay of the averaged weights for the step being applied (handles with a shadow only)
 int launch_adamw_multi(const AdamParam* params, const AdamItem* items, int n_items, const float* ctl, float lr, float beta1, float beta2, float eps, float wd,
                        hipStream_t stream);
+// the same step, then e = fmaf(ctl[7], e, (1 - ctl[7]) * w_new) on every element's shadow (AdamParam::e, not null) in the same launch; a skipped step leaves it alone
+int launch_adamw_multi_ema(const AdamParam* params, const AdamItem* items, int n_items, const float* ctl, float lr, float beta1, float beta2, float eps, float wd,
+                           hipStream_t stream);
+// no step: w <-> e on every element, both 2-byte images of the GEMM weights rewritten from the new w as the step writes them
+int launch_adamw_swap_ema(const AdamParam* params, const AdamItem* items, int n_items, hipStream_t stream);
 // Low-rank adapters (train.hip, DESIGN.md 7 "Low-rank adapters"): W = W0 + s B A for every adapted Linear, one work item per 64 x 64 tile of W (N, K % 64 == 0).
 struct LoraMergeParam {
     const float* w0; const float* a; const float* b;   // frozen fp32 master [N][K], A [r][K], B [N][r]

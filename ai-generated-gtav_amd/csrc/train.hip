@@ -1488,6 +1488,7 @@ __global__ void ada_reduce_kernel(const float* __restrict__ part, int nchunk, si
 //   weights, moments and the Adam step count cannot drift apart between replicas (round 3 tested the bit locally only: ADVICE r3).
 //   ctl[4] = number of APPLIED steps (the Adam step count t: a skipped step does not advance it), ctl[5] / ctl[6] = the bias
 //   corrections 1 - beta1^t / 1 - beta2^t of the step being applied, computed here on the device so that m / v and t stay in step.
+//   ctl[7] = the decay d_t of the averaged weights for the step being applied (handles with a shadow only; otherwise never written).
 // ------------------------------------------------------------------------------------------------------------------------
 // (per-block partial sums, added up in block order by clip_coef_kernel: no float atomics, the norm — and with it the clip coefficient and every
 // AdamW update — is bit-reproducible from run to run)
@@ -1514,7 +1515,7 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
     if (threadIdx.x == 0) part[blockIdx.x] = t;
 }
 __global__ __launch_bounds__(256) void clip_coef_kernel(float* ctl, const float* __restrict__ part, int nparts, float inv_scale, float max_norm, float beta1, float beta2,
-                                                        int* err_flag) {
+                                                        float ema_decay, int ema_warmup, int* err_flag) {
     __shared__ float red[16];
     float a = 0.f;
     for (int i = threadIdx.x; i < nparts; i += 256) a += part[i];
@@ -1539,6 +1540,9 @@ __global__ __launch_bounds__(256) void clip_coef_kernel(float* ctl, const float*
         ctl[4] = t;
         ctl[5] = 1.0f - powf(beta1, t);
         ctl[6] = 1.0f - powf(beta2, t);
+        // averaged weights: the decay of this applied step, d or with warm-up min(d, (1 + t) / (10 + t)) — t is an exact integer, both sums are exact and
+        // the division is correctly rounded, so the host mirrors it bit for bit (train.ema_decay_at)
+        if (ema_decay > 0.f) ctl[7] = ema_warmup ? fminf(ema_decay, (1.0f + t) / (10.0f + t)) : ema_decay;
     }
     ctl[3] = norm;
 }
@@ -1567,23 +1571,48 @@ __global__ void adamw_kernel(float* __restrict__ p, int ldp, int R, int C, const
 // parameter.  A block updates its item in fp32 and, for a GEMM weight, writes the tile straight into the tile-major fp16 W (16 bytes
 // along c) and, through an LDS transpose, into the tile-major fp16 W^T (16 bytes along r): the separate convert passes (two more reads
 // of the 0.8 GB of masters, 370 launches) and 300 per-parameter AdamW launches are gone.
+//
+// MODE (DESIGN.md 7 "Averaged weights"; AdamParam::e is the fp32 shadow, contiguous [R][C] like m and v):
+//   ADAM_STEP      the step alone: P.e is never read (null on a handle without a shadow).
+//   ADAM_STEP_EMA  the step, then per element e = fmaf(d, e, (1 - d) * w_new) with d = ctl[7] (the decay of THIS applied step, written by clip_coef_kernel) and
+//                  w_new the master the step just wrote: three fp32 roundings (1 - d, the product, the fma), the explicit fmaf is the only contraction there is.
+//                  The master, moment and image arithmetic is ADAM_STEP's, operation for operation; a skipped step (ctl[1] == 0) leaves the shadow alone too.
+//                  Measured (profiles/ema/): 3.415 ms for the step alone, 4.205 ms with the average, on 608 M parameters: 32 and 40 bytes per parameter at 5.7 TB/s.
+//   ADAM_SWAP      no step: per element w <-> e, moments and gradients untouched, and both images written from the new w through the same clamp, LDS transpose and
+//                  tiled_off tail — exactly what a step that had produced those masters would have written.  ctl, lr .. wd are not read.
+enum { ADAM_STEP = 0, ADAM_STEP_EMA = 1, ADAM_SWAP = 2 };
+template <int MODE>
 __global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamParam* __restrict__ params, const AdamItem* __restrict__ items, const float* __restrict__ ctl,
                                                           float lr, float beta1, float beta2, float eps, float wd) {
-    const float coef = ctl[1];
-    if (coef == 0.f) return;               // overflow: skip the step
-    const float bc1 = ctl[5], bc2 = ctl[6];
+    float coef = 0.f, bc1 = 1.f, bc2 = 1.f, ed = 0.f, eo = 0.f;
+    if constexpr (MODE != ADAM_SWAP) {
+        coef = ctl[1];
+        if (coef == 0.f) return;           // overflow: skip the step
+        bc1 = ctl[5]; bc2 = ctl[6];
+    }
+    if constexpr (MODE == ADAM_STEP_EMA) { ed = ctl[7]; eo = 1.0f - ed; }
     const AdamItem it = items[blockIdx.x];
     const AdamParam P = params[it.param];
     const float decay = 1.0f - lr * wd, step = lr / bc1, rs2 = 1.0f / sqrtf(bc2);
     auto upd = [&](size_t idx, float* pp) -> float {
-        const float gr = P.g[idx] * coef;
-        const float mm = beta1 * P.m[idx] + (1.0f - beta1) * gr;
-        const float vv = beta2 * P.v[idx] + (1.0f - beta2) * gr * gr;
-        P.m[idx] = mm;
-        P.v[idx] = vv;
-        const float w = *pp * decay - step * mm / (sqrtf(vv) * rs2 + eps);
-        *pp = w;
-        return w;
+        if constexpr (MODE == ADAM_SWAP) {
+            const float w = P.e[idx];
+            P.e[idx] = *pp;
+            *pp = w;
+            return w;
+        } else {
+            float ev = 0.f;
+            if constexpr (MODE == ADAM_STEP_EMA) ev = P.e[idx];
+            const float gr = P.g[idx] * coef;
+            const float mm = beta1 * P.m[idx] + (1.0f - beta1) * gr;
+            const float vv = beta2 * P.v[idx] + (1.0f - beta2) * gr * gr;
+            P.m[idx] = mm;
+            P.v[idx] = vv;
+            const float w = *pp * decay - step * mm / (sqrtf(vv) * rs2 + eps);
+            *pp = w;
+            if constexpr (MODE == ADAM_STEP_EMA) P.e[idx] = __builtin_fmaf(ed, ev, eo * w);
+            return w;
+        }
     };
     if (!P.w16) {                          // fp32 parameter (trained in place, possibly a strided view): a linear run of elements
         const size_t total = (size_t)P.R * P.C;
@@ -1599,30 +1628,40 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamParam* __res
     const int tiles_c = (P.C + 63) / 64;
     const int r0 = (int)(it.start / tiles_c) * 64, c0 = (int)(it.start % tiles_c) * 64;
     if (r0 + 64 <= P.R && c0 + 64 <= P.C && (P.C & 3) == 0) {
-        // interior tile (every tile of the DiT's GEMM weights): 16-byte accesses, and ALL of the thread's loads (4 float4 of each of g, m, v, w) before its first
-        // store — a load behind a store waits for the store's round trip (vmcnt retires in order), three times per block in the element-wise loop below:
-        // 5.41 -> 3.26 ms per step for the 608 M parameters (6 TB/s)
-        f32x4 g4[4], m4[4], v4[4], w4[4];
+        // interior tile (every tile of the DiT's GEMM weights): 16-byte accesses, and ALL of the thread's loads (4 float4 of each of g, m, v, w — and of the
+        // shadow e where MODE reads it) before its first store — a load behind a store waits for the store's round trip (vmcnt retires in order), three
+        // times per block in the element-wise loop below: 5.41 -> 3.26 ms per step for the 608 M parameters (6 TB/s)
+        f32x4 g4[4], m4[4], v4[4], w4[4], e4[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int q = threadIdx.x + 256 * k, r = q >> 4, c4 = (q & 15) * 4;
             const size_t idx = (size_t)(r0 + r) * P.C + c0 + c4;
-            g4[k] = *(const f32x4*)(P.g + idx); m4[k] = *(const f32x4*)(P.m + idx); v4[k] = *(const f32x4*)(P.v + idx); w4[k] = *(const f32x4*)(P.p + idx);
+            if constexpr (MODE != ADAM_SWAP) { g4[k] = *(const f32x4*)(P.g + idx); m4[k] = *(const f32x4*)(P.m + idx); v4[k] = *(const f32x4*)(P.v + idx); }
+            w4[k] = *(const f32x4*)(P.p + idx);
+            if constexpr (MODE != ADAM_STEP) e4[k] = *(const f32x4*)(P.e + idx);
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int q = threadIdx.x + 256 * k, r = q >> 4, c4 = (q & 15) * 4;
             const size_t idx = (size_t)(r0 + r) * P.C + c0 + c4;
-            f32x4 mm, vv, ww;
+            if constexpr (MODE == ADAM_SWAP) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {   // (the same operations in the same order as upd())
-                const float gr = g4[k][e] * coef;
-                mm[e] = beta1 * m4[k][e] + (1.0f - beta1) * gr;
-                vv[e] = beta2 * v4[k][e] + (1.0f - beta2) * gr * gr;
-                ww[e] = w4[k][e] * decay - step * mm[e] / (sqrtf(vv[e]) * rs2 + eps);
-                t[r][c4 + e] = (f16)__builtin_amdgcn_fmed3f(ww[e], -F16_MAX, F16_MAX);
+                for (int e = 0; e < 4; ++e) t[r][c4 + e] = (f16)__builtin_amdgcn_fmed3f(e4[k][e], -F16_MAX, F16_MAX);
+                *(f32x4*)(P.p + idx) = e4[k]; *(f32x4*)(P.e + idx) = w4[k];
+            } else {
+                f32x4 mm, vv, ww, ee;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {   // (the same operations in the same order as upd())
+                    const float gr = g4[k][e] * coef;
+                    mm[e] = beta1 * m4[k][e] + (1.0f - beta1) * gr;
+                    vv[e] = beta2 * v4[k][e] + (1.0f - beta2) * gr * gr;
+                    ww[e] = w4[k][e] * decay - step * mm[e] / (sqrtf(vv[e]) * rs2 + eps);
+                    t[r][c4 + e] = (f16)__builtin_amdgcn_fmed3f(ww[e], -F16_MAX, F16_MAX);
+                    if constexpr (MODE == ADAM_STEP_EMA) ee[e] = __builtin_fmaf(ed, e4[k][e], eo * ww[e]);
+                }
+                *(f32x4*)(P.m + idx) = mm; *(f32x4*)(P.v + idx) = vv; *(f32x4*)(P.p + idx) = ww;
+                if constexpr (MODE == ADAM_STEP_EMA) *(f32x4*)(P.e + idx) = ee;
             }
-            *(f32x4*)(P.m + idx) = mm; *(f32x4*)(P.v + idx) = vv; *(f32x4*)(P.p + idx) = ww;
         }
     } else
     for (int q = threadIdx.x; q < 64 * 16; q += 256) {     // 64 rows x 16 float4
@@ -2185,14 +2224,26 @@ int launch_overflow_publish(const int* err_flag, float* g, hipStream_t stream) {
     GTAV_CHECK_HIP(hipGetLastError());
     return 0;
 }
-int launch_clip_coef(float* ctl, const float* part, int nparts, float inv_scale, float max_norm, float beta1, float beta2, int* err_flag, hipStream_t stream) {
-    hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, stream, ctl, part, nparts, inv_scale, max_norm, beta1, beta2, err_flag);
+int launch_clip_coef(float* ctl, const float* part, int nparts, float inv_scale, float max_norm, float beta1, float beta2, float ema_decay, int ema_warmup,
+                     int* err_flag, hipStream_t stream) {
+    hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, stream, ctl, part, nparts, inv_scale, max_norm, beta1, beta2, ema_decay, ema_warmup, err_flag);
     GTAV_CHECK_HIP(hipGetLastError());
     return 0;
 }
 int launch_adamw_multi(const AdamParam* params, const AdamItem* items, int n_items, const float* ctl, float lr, float beta1, float beta2, float eps, float wd,
                        hipStream_t stream) {
-    hipLaunchKernelGGL(adamw_multi_kernel, dim3(n_items), dim3(256), 0, stream, params, items, ctl, lr, beta1, beta2, eps, wd);
+    hipLaunchKernelGGL(adamw_multi_kernel<ADAM_STEP>, dim3(n_items), dim3(256), 0, stream, params, items, ctl, lr, beta1, beta2, eps, wd);
+    GTAV_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+int launch_adamw_multi_ema(const AdamParam* params, const AdamItem* items, int n_items, const float* ctl, float lr, float beta1, float beta2, float eps, float wd,
+                           hipStream_t stream) {
+    hipLaunchKernelGGL(adamw_multi_kernel<ADAM_STEP_EMA>, dim3(n_items), dim3(256), 0, stream, params, items, ctl, lr, beta1, beta2, eps, wd);
+    GTAV_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+int launch_adamw_swap_ema(const AdamParam* params, const AdamItem* items, int n_items, hipStream_t stream) {
+    hipLaunchKernelGGL(adamw_multi_kernel<ADAM_SWAP>, dim3(n_items), dim3(256), 0, stream, params, items, (const float*)nullptr, 0.f, 0.f, 0.f, 0.f, 0.f);
     GTAV_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -96,6 +96,10 @@ SIGNATURES = {
     "gtav_dit_train_stats": [_p, C.POINTER(C.c_float), _p],
     "gtav_dit_get_opt_state": [_p, C.c_char_p, _p, _p, _l, _p],
     "gtav_dit_set_opt_state": [_p, C.c_char_p, _p, _p, _l, _p],
+    "gtav_dit_train_set_ema": [_p, _f, _i],
+    "gtav_dit_get_ema": [_p, C.c_char_p, _p, _l, _p],
+    "gtav_dit_set_ema": [_p, C.c_char_p, _p, _l, _p],
+    "gtav_dit_train_swap_ema": [_p, _p],
     "gtav_dit_get_opt_step": [_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _p],
     "gtav_dit_set_opt_step": [_p, _l, _l, _p],
     "gtav_dit_set_graph": [_p, _i],

@@ -6,6 +6,7 @@ storage (device tensors, the fp32 master copy of the weights) and host-side cons
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 from collections import OrderedDict
@@ -150,7 +151,7 @@ class DiT(_HipModule):
     def __init__(self, input_h=18, input_w=32, patch_size=2, in_channels=16, hidden_size=1024, depth=12, num_heads=16,
                  mlp_ratio=4.0, external_cond_dim=25, max_frames=5, *, max_batch=1, init_weights=True, trainable=False, range_policy="report",
                  train_dtype=torch.float16, train_max_frames=None, train_recompute=False, train_range_policy="report", train_lora_rank=None,
-                 train_lora_alpha=None):
+                 train_lora_alpha=None, train_ema_decay=None, train_ema_warmup=False):
         super().__init__()
         self._trainable = bool(trainable)    # keyword-only, not in the reference: keeps fp32 masters, gradients and AdamW state on the GPU
         # opt-in to training windows of up to train_max_frames frames (include/gtav_amd.h gtav_dit_train_allow_window); None: TRAIN_MAX_FRAMES.  The saved
@@ -201,6 +202,20 @@ class DiT(_HipModule):
             train_lora_alpha = float(train_lora_rank if train_lora_alpha is None else train_lora_alpha)
             if not (train_lora_alpha > 0.0 and math.isfinite(train_lora_alpha)):
                 raise ValueError(f"train_lora_alpha={train_lora_alpha}: a positive number")
+        # opt-in to averaged weights (include/gtav_amd.h gtav_dit_train_set_ema): the optimizer launch keeps ema <- d_n ema + (1 - d_n) w of every trainable parameter
+        # in fp32 on the GPU, 4 bytes per trainable parameter more; d_n = train_ema_decay, or with train_ema_warmup min(decay, (1 + n) / (10 + n)) at applied step n
+        # (gtav_amd.train.ema_decay_at).  ema_state_dict() / load_ema_state_dict() move the average, `with dit.ema_weights():` computes with it
+        if train_ema_decay is None and train_ema_warmup:
+            raise ValueError("train_ema_warmup needs train_ema_decay")
+        if train_ema_decay is not None:
+            if not self._trainable:
+                raise ValueError("train_ema_decay needs trainable=True (the average is kept by the optimizer step; an inference model loads ema_state_dict())")
+            train_ema_decay = float(train_ema_decay)
+            if not 0.0 < train_ema_decay < 1.0:
+                raise ValueError(f"train_ema_decay={train_ema_decay}: the decay of the averaged weights must lie in (0, 1)")
+        self._ema_decay = train_ema_decay
+        self._ema_warmup = bool(train_ema_warmup)
+        self._ema_swapped = False
         self._lora_rank = None if train_lora_rank is None else int(train_lora_rank)
         self._lora_alpha = train_lora_alpha
         self._lora_sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
@@ -344,6 +359,8 @@ class DiT(_HipModule):
                 if self._trainable:
                     if self._lora_rank:                                  # (first: the adapters are then what train_param_count counts)
                         _lib.check(L.gtav_dit_train_set_lora(self._handle, self._lora_rank, self._lora_alpha))
+                    if self._ema_decay is not None:
+                        _lib.check(L.gtav_dit_train_set_ema(self._handle, self._ema_decay, int(self._ema_warmup)))
                     n = C.c_int64(0)
                     _lib.check(L.gtav_dit_train_param_count(self._handle, C.byref(n)))
                     # one contiguous fp32 gradient arena owned by torch: a single all-reduce covers the whole model (train.py)
@@ -367,8 +384,14 @@ class DiT(_HipModule):
                         _lib.check(L.gtav_dit_set_grad_divisor(self._handle, self.grad_divisor))
             self._dirty = True
             self._lora_host_fresh = True     # (a new handle holds no adapters yet: the host copies are all there is)
+            self._ema_swapped = False
         if self._dirty:
+            if self._ema_swapped:
+                raise _lib.GtavError("new weights while the averaged weights are swapped in (ema_weights()): leave the context first")
+            keep_ema = None
             if self._lora_rank and not self._lora_host_fresh:            # the re-upload below sends the adapters too: the trained ones, not the stale host copies
+                # (and a weight upload sets the average to the weight: the trained adapters' average is put back behind it)
+                keep_ema = self._pull_ema() if self._ema_decay is not None else None
                 self._pull_lora()
             gh, gw = self.input_h // self.patch_size, self.input_w // self.patch_size
             sc, ss = _rope_tables_axial(self._spatial_freqs, gh, gw)
@@ -378,6 +401,8 @@ class DiT(_HipModule):
             extra.update(self._lora_sd)
             self._upload(extra)
             self._lora_host_fresh = True
+            if keep_ema is not None:
+                self._push_ema(keep_ema)
             if self._schedule is not None:
                 self.set_schedule(self._schedule)
 
@@ -656,12 +681,99 @@ class DiT(_HipModule):
 
     def pull_weights(self):
         """Copies the trained fp32 masters from the GPU back into the host state dict (checkpoints, state_dict())."""
+        if self._ema_swapped:
+            raise _lib.GtavError("pull_weights: the averaged weights are swapped in (ema_weights()); the trained ones are read outside the context (the average: ema_state_dict())")
         L = _lib.load()
         with torch.cuda.device(self.device):
             for k, shp in self._shapes().items():
                 out = torch.empty(shp, device=self.device, dtype=torch.float32)
                 _lib.check(L.gtav_dit_get_weight(self._handle, k.encode(), out.data_ptr(), out.numel(), _lib.current_stream()))
                 self._sd[k] = out.cpu()
+
+    # ------------------------------------------------------------------------------------------
+    # averaged weights (train_ema_decay=...; include/gtav_amd.h gtav_dit_train_set_ema)
+    # ------------------------------------------------------------------------------------------
+    @property
+    def ema_decay(self):
+        """Decay of the averaged weights, None on a model without them; fixed at construction."""
+        return self._ema_decay
+
+    @property
+    def ema_warmup(self) -> bool:
+        return self._ema_warmup
+
+    def _need_ema(self, who):
+        if self._ema_decay is None:
+            raise _lib.GtavError(f"{who}: this DiT keeps no averaged weights (construct it with trainable=True, train_ema_decay=...)")
+
+    def _pull_ema(self):
+        L, out = _lib.load(), OrderedDict()
+        with torch.cuda.device(self.device):
+            for k, shp in self._train_shapes().items():
+                e = torch.empty(shp, device=self.device, dtype=torch.float32)
+                _lib.check(L.gtav_dit_get_ema(self._handle, k.encode(), e.data_ptr(), e.numel(), _lib.current_stream()))
+                out[k] = e.cpu()
+        return out
+
+    def _push_ema(self, sd):
+        L = _lib.load()
+        with torch.cuda.device(self.device):
+            for k in self._train_shapes():
+                d = sd[k].to(self.device, torch.float32).contiguous()
+                _lib.check(L.gtav_dit_set_ema(self._handle, k.encode(), d.data_ptr(), d.numel(), _lib.current_stream()))
+            torch.cuda.synchronize()
+
+    def ema_state_dict(self) -> "OrderedDict[str, torch.Tensor]":
+        """The averaged weights as CPU tensors in the reference's key layout: every trainable tensor from the GPU's fp32 shadow, the constants (rotary
+        frequencies) from state_dict().  A LoRA model returns the averaged ADAPTERS under the adapter keys — loaded into a LoRA model over the same base
+        (load_lora_state_dict) they give the model `with ema_weights():` computes with; note that merging averaged adapters is not the average of the merged
+        weights (B A is bilinear)."""
+        self._need_ema("ema_state_dict")
+        self._ensure(self._capacity_b, self._capacity_t)
+        ema = self._pull_ema()
+        if self._lora_rank:
+            return ema
+        sd = self.state_dict()
+        sd.update(ema)
+        return sd
+
+    def load_ema_state_dict(self, sd: Dict[str, torch.Tensor]):
+        """Inverse of ema_state_dict: every trainable tensor's average in its shape (other keys, the rotary frequencies among them, are ignored).  The weights
+        themselves: load_state_dict, which also sets the average to the weights it loads — so call this after it."""
+        self._need_ema("load_ema_state_dict")
+        shapes = self._train_shapes()
+        missing = [k for k in shapes if k not in sd]
+        if missing:
+            raise RuntimeError(f"load_ema_state_dict: missing keys {missing[:5]}{'...' if len(missing) > 5 else ''}")
+        new = {}
+        for k, shp in shapes.items():
+            v = sd[k].detach().to("cpu", torch.float32).contiguous()
+            if tuple(v.shape) != tuple(shp):
+                raise RuntimeError(f"load_ema_state_dict: {k} has shape {tuple(v.shape)}, expected {tuple(shp)}")
+            new[k] = v
+        self._ensure(self._capacity_b, self._capacity_t)
+        self._push_ema(new)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """`with dit.ema_weights():` the model computes with the averaged weights — forward / __call__, the sampler step, gtav_amd.train.predict, state via
+        gtav_dit_get_weight — and with the trained ones again afterwards, bit for bit (gtav_dit_train_swap_ema: masters and shadow change places on the GPU, the
+        2-byte weight images are remade; nothing is copied to the host).  Inside, forward_train / backward_ / adamw_step and weight uploads raise GtavError;
+        nesting raises."""
+        self._need_ema("ema_weights")
+        if self._ema_swapped:
+            raise _lib.GtavError("ema_weights: the averaged weights are swapped in already (the context does not nest)")
+        self._ensure(self._capacity_b, self._capacity_t)
+        L = _lib.load()
+        with torch.cuda.device(self.device):
+            _lib.check(L.gtav_dit_train_swap_ema(self._handle, _lib.current_stream()))
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            with torch.cuda.device(self.device):
+                _lib.check(L.gtav_dit_train_swap_ema(self._handle, _lib.current_stream()))
+            self._ema_swapped = False
 
     # ------------------------------------------------------------------------------------------
     # low-rank adapters (train_lora_rank=...; include/gtav_amd.h gtav_dit_train_set_lora)
@@ -707,6 +819,8 @@ class DiT(_HipModule):
                 torch.cuda.synchronize()
 
     def _pull_lora(self):
+        if self._ema_swapped:
+            raise _lib.GtavError("the averaged adapters are swapped in (ema_weights()); the trained ones are read outside the context (the average: ema_state_dict())")
         L = _lib.load()
         with torch.cuda.device(self.device):
             for k, shp in self._lora_shapes().items():

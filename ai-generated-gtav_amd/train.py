@@ -437,9 +437,30 @@ class LossScaler:
 # names (train_dit.py:758-762); `save_checkpoint` = accelerator.save_state (model + optimizer) + step.json {step, epoch}; `load_checkpoint`
 # = load_state + step.json, then the caller skips `steps_in_epoch * gradient_accumulation_steps` batches (train_dit.py:841-843).
 # ------------------------------------------------------------------------------------------------------------------------
-def save_model(dit, path: str):
-    """train_dit.py:746-763: weights only, safetensors, reference key names (incl. the de-duplicated rotary `freqs`)."""
+def ema_decay_at(n: int, decay: float, warmup: bool = False) -> float:
+    """The decay d_n the optimizer launch applies to the averaged weights at applied step n >= 1 (DiT(train_ema_decay=decay, train_ema_warmup=warmup)): `decay`
+    rounded to float32, or with warm-up min(decay, (1 + n) / (10 + n)) — computed in float32 exactly as the device computes it (both sums are exact integers,
+    the division is correctly rounded), returned as a Python float holding that float32 value."""
+    import numpy as np
+    if int(n) < 1 or int(n) >= 1 << 24:
+        raise ValueError(f"ema_decay_at: applied step n={n} (the first applied step is 1; the device keeps the count as an exact fp32 integer, below 2^24)")
+    d = np.float32(decay)
+    if not 0.0 < float(d) < 1.0:
+        raise ValueError(f"ema_decay_at: decay={decay} outside (0, 1)")
+    if warmup:
+        d = min(d, np.float32(1 + int(n)) / np.float32(10 + int(n)))
+    return float(d)
+
+
+def save_model(dit, path: str, ema: bool = False):
+    """train_dit.py:746-763: weights only, safetensors, reference key names (incl. the de-duplicated rotary `freqs`).  ema=True: the averaged weights of a
+    DiT(train_ema_decay=...) in the same layout — the file an inference model loads to sample from the average."""
     from . import weights as _w
+    if ema:
+        if getattr(dit, "lora_rank", None):
+            raise _lib.GtavError("save_model(ema=True): this DiT averages its low-rank adapters, not the weights; save them with save_lora(dit, path, ema=True)")
+        _w.save_state_dict_file(dit.ema_state_dict(), path)
+        return
     if getattr(dit, "_trainable", False) and dit._handle:
         dit.pull_weights()
     _w.save_state_dict_file(dit.state_dict(), path)
@@ -451,13 +472,15 @@ def _lora_meta(dit):
     return {"rank": int(rank), "alpha": float(dit.lora_alpha)} if rank else None
 
 
-def save_lora(dit, path: str):
-    """The adapters of a LoRA model alone as one .safetensors (a few MB beside the caller's frozen checkpoint); metadata {"rank", "alpha"}, as strings."""
+def save_lora(dit, path: str, ema: bool = False):
+    """The adapters of a LoRA model alone as one .safetensors (a few MB beside the caller's frozen checkpoint); metadata {"rank", "alpha"}, as strings.
+    ema=True: the averaged adapters of a DiT(train_lora_rank=..., train_ema_decay=...) under the same keys."""
     from safetensors.torch import save_file
     meta = _lora_meta(dit)
     if meta is None:
         raise _lib.GtavError("save_lora: this DiT has no adapters (construct it with trainable=True, train_lora_rank=...)")
-    save_file({k: v.contiguous() for k, v in dit.lora_state_dict().items()}, path, metadata={k: repr(v) for k, v in meta.items()})
+    sd = dit.ema_state_dict() if ema else dit.lora_state_dict()
+    save_file({k: v.contiguous() for k, v in sd.items()}, path, metadata={k: repr(v) for k, v in meta.items()})
 
 
 def _operand_dtype_name(dit) -> str:
@@ -486,6 +509,8 @@ def _restore_groups(dit, state: dict):
 def save_state(dit, ckpt_dir: str, global_step: int, epoch: int, extra: Optional[dict] = None, rng=None):
     """A LoRA model (DiT(train_lora_rank=...)) writes <dir>/lora.safetensors (the adapters; no model.safetensors: the base is the caller's frozen checkpoint), the
     adapters' moments and step.json with "lora": {"rank", "alpha"}; load_state restores the three into a LoRA model of the same rank, onto whatever base it holds.
+    A model with averaged weights (DiT(train_ema_decay=...)) also writes <dir>/ema.safetensors and step.json's "ema": {"decay", "warmup"}; load_state restores the
+    average after the weights, leaves it equal to the loaded weights when the checkpoint has none, and ignores the file on a model without a shadow.
     train_dit.py:765-800 `save_checkpoint`: <dir>/model.safetensors (fp32 masters), <dir>/optimizer.safetensors (AdamW moments + step
     counters), <dir>/step.json {"step", "epoch", "loss_scale", "operand_dtype", "bf16_groups", ...}.  Rank 0 writes; the caller barriers around it like the reference.
     rng (a NoiseSource): its {"seed", "draw"} goes into step.json as "rng" — the whole noise stream of the resumed run."""
@@ -502,6 +527,11 @@ def save_state(dit, ckpt_dir: str, global_step: int, epoch: int, extra: Optional
     else:
         save_model(dit, os.path.join(ckpt_dir, "model.safetensors"))
     save_file({k: v.contiguous() for k, v in dit.opt_state_dict().items()}, os.path.join(ckpt_dir, "optimizer.safetensors"))
+    # a model with averaged weights: ema.safetensors (the trainable tensors' fp32 shadow) and step.json's "ema": {"decay", "warmup"}
+    if getattr(dit, "ema_decay", None) is not None:
+        shapes = dit._train_shapes()
+        save_file({k: v.contiguous() for k, v in dit.ema_state_dict().items() if k in shapes}, os.path.join(ckpt_dir, "ema.safetensors"))
+        extra = dict(extra or {}, ema={"decay": float(dit.ema_decay), "warmup": bool(dit.ema_warmup)})
     state = _step_state(dit, global_step, epoch)
     state.update(extra or {})
     if rng is not None:
@@ -536,6 +566,10 @@ def load_state(dit, ckpt_dir: str, steps_per_epoch: Optional[int] = None, gradie
     else:
         dit.load_state_dict(_w.load_state_dict_file(os.path.join(ckpt_dir, "model.safetensors")))
     dit.load_opt_state_dict(load_file(os.path.join(ckpt_dir, "optimizer.safetensors")))
+    # the averaged weights, after the weights (whose upload set the average to them: what a checkpoint without ema.safetensors leaves); a model without a
+    # shadow ignores the file
+    if getattr(dit, "ema_decay", None) is not None and os.path.exists(os.path.join(ckpt_dir, "ema.safetensors")):
+        dit.load_ema_state_dict(load_file(os.path.join(ckpt_dir, "ema.safetensors")))
     # the loss scale belongs to the operand type it was found for: a bf16 run's scale (1 by default) would let an fp16 backward underflow, so it is restored
     # only into a handle of the same type (a checkpoint without "operand_dtype" is fp16).  The masters and moments are fp32 and load either way.
     if "loss_scale" in state and state.get("operand_dtype", "fp16") == _operand_dtype_name(dit):

@@ -324,6 +324,26 @@ int gtav_dit_get_opt_state(gtav_dit* h, const char* name, float* m_dst_dev, floa
 int gtav_dit_set_opt_state(gtav_dit* h, const char* name, const float* m_src_dev, const float* v_src_dev, int64_t numel, void* stream);
 int gtav_dit_get_opt_step(gtav_dit* h, int64_t* applied_steps, int64_t* skipped_steps, void* stream);
 int gtav_dit_set_opt_step(gtav_dit* h, int64_t applied_steps, int64_t skipped_steps, void* stream);
+/* Averaged weights (an exponential moving average of the fp32 masters, kept inside the optimizer launch; DESIGN.md 7 "Averaged weights").
+ * gtav_dit_train_set_ema(h, decay, warmup) between gtav_dit_create and gtav_dit_train_enable[_typed] turns the shadow on: train_enable allocates 4 bytes per
+ * trainable parameter more, and every APPLIED gtav_dit_adamw_step then ends, per element and in the same launch, with
+ *     ema = fmaf(d_n, ema, (1 - d_n) * w_new)         (fp32; w_new = the master the step just wrote)
+ * where n counts the applied steps including this one and d_n = decay, or with warmup != 0 min(decay, (1 + n) / (10 + n)).  A skipped step leaves the shadow
+ * untouched and does not advance n.  On an enabled handle that has a shadow the call changes decay and warm-up for the steps to come; on one that has none it
+ * is refused (the shadow cannot be turned on or off after enable).  decay outside (0, 1) is refused.  Nothing is communicated between ranks: the average is
+ * a function of the masters, which are identical across ranks.  On a LoRA handle the trainable parameters, and so the averaged ones, are the adapters (the
+ * merge of averaged adapters is NOT the average of the merged weights: B A is bilinear).
+ * gtav_dit_set_weight of a trainable parameter writes the master AND the shadow (a freshly loaded model starts with ema = weights); gtav_dit_set_ema writes the
+ * shadow alone, gtav_dit_get_ema reads it (torch layout, the checks of gtav_dit_get_opt_state).
+ * gtav_dit_train_swap_ema(h, stream) exchanges masters and shadow and remakes the 2-byte images of the GEMM weights (a LoRA handle: merges again): the handle
+ * then COMPUTES with the average — gtav_dit_forward, the sampler step, gtav_dit_get_weight and gtav_dit_lora_get_merged see it — until the same call swaps
+ * back, which restores every bit.  While swapped, gtav_dit_train_forward*, gtav_dit_train_backward*, gtav_dit_adamw_step, gtav_dit_set_weight,
+ * gtav_dit_set_ema / get_ema, gtav_dit_train_set_group_dtype and gtav_dit_train_autorange are refused by name: the saved activations and the optimizer state
+ * belong to the other weights. */
+int gtav_dit_train_set_ema(gtav_dit* h, float decay, int32_t warmup);
+int gtav_dit_get_ema(gtav_dit* h, const char* name, float* dst_dev, int64_t numel, void* stream);
+int gtav_dit_set_ema(gtav_dit* h, const char* name, const float* src_dev, int64_t numel, void* stream);
+int gtav_dit_train_swap_ema(gtav_dit* h, void* stream);
 
 /* Reads and clears the handle's device error word (synchronises): fails if, since the last call, a timestep was outside
  * [0, 999], an input held a NaN/inf, or an fp16 activation store saturated (|x| > 65504 is clamped to +-65504, never
