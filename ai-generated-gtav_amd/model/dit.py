@@ -46,10 +46,35 @@ def _timestep_table() -> torch.Tensor:
     return torch.cat([torch.cos(args), torch.sin(args)], dim=-1).contiguous()
 
 
+def _checked_tensors(sd, shapes, who, *, strict=True, allow_unexpected=False, note=""):
+    """The tensors of `sd` that the shape table names, as CPU fp32 contiguous copies in table order, each checked against its shape.  strict: a key the table
+    has and `sd` lacks raises, and (unless allow_unexpected) so does one `sd` has and the table lacks; otherwise absent keys are left out."""
+    if strict:
+        dots = lambda keys: f"{keys[:5]}{'...' if len(keys) > 5 else ''}"
+        missing = [k for k in shapes if k not in sd]
+        unexpected = [] if allow_unexpected else [k for k in sd if k not in shapes]
+        if missing or unexpected:
+            raise RuntimeError(f"{who}: missing keys {dots(missing)}" + ("" if allow_unexpected else f", unexpected keys {dots(unexpected)}"))
+    out = OrderedDict()
+    for k, shp in shapes.items():
+        if k in sd:
+            v = sd[k].detach().to("cpu", torch.float32).contiguous()
+            if tuple(v.shape) != tuple(shp):
+                raise RuntimeError(f"{who}: {k} has shape {tuple(v.shape)}, expected {tuple(shp)}{note}")
+            out[k] = v
+    return out
+
+
+_ALWAYS = object()     # a handle setting with this default is replayed onto every new handle
+
+
 class _HipModule:
     """Shared plumbing of DiT / AutoencoderKL: fp32 master weights on the host, a C-ABI handle on the GPU."""
 
     _prefix = ""  # gtav_dit / gtav_vae
+    # the settings that survive a re-created handle, in replay order: attribute -> (C setter, stage of handle creation that replays it, the default that
+    # needs no call, value -> the setter's arguments).  A public setter is: validate, _set()
+    _SETTINGS = {}
 
     def __init__(self):
         self._sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
@@ -57,6 +82,49 @@ class _HipModule:
         self._dirty = True
         self.training = False
         self.device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cuda")
+        for attr, (_, _, default, _) in self._SETTINGS.items():
+            setattr(self, attr, default)
+
+    def _set(self, attr, value):
+        """Records a handle setting and applies it to the handle if there is one."""
+        setattr(self, attr, value)
+        if self._handle:
+            symbol, _, _, args = self._SETTINGS[attr]
+            _lib.check(getattr(_lib.load(), symbol)(self._handle, *args(value)))
+
+    def _replay(self, stage):
+        """The recorded settings of one stage onto the handle, in table order."""
+        for attr, (symbol, at, default, args) in self._SETTINGS.items():
+            value = getattr(self, attr)
+            if at == stage and value != default:
+                _lib.check(getattr(_lib.load(), symbol)(self._handle, *args(value)))
+
+    def _pull(self, symbol, shapes, ptrs=1, cpu=True):
+        """name -> fp32 tensor (ptrs > 1: tuple of tensors) of the shapes in the table, each filled by `symbol(handle, name, ptr..., numel, stream)`."""
+        fn, stream, out = getattr(_lib.load(), symbol), _lib.current_stream(), OrderedDict()
+        with torch.cuda.device(self.device):
+            for k, shp in shapes.items():
+                d = [torch.empty(tuple(shp), device=self.device, dtype=torch.float32) for _ in range(ptrs)]
+                _lib.check(fn(self._handle, k.encode(), *[t.data_ptr() for t in d], d[0].numel(), stream))
+                if cpu:
+                    d = [t.cpu() for t in d]
+                out[k] = d[0] if ptrs == 1 else tuple(d)
+        return out
+
+    def _push(self, symbol, tensors, finalize=False, synchronize=True):
+        """`symbol(handle, name, ptr..., numel, stream)` for every name -> tensor (or tuple of tensors) of the mapping, copied to the device as fp32; then
+        the handle's finalize and a device synchronisation where asked."""
+        L, stream = _lib.load(), _lib.current_stream()
+        fn = getattr(L, symbol)
+        with torch.cuda.device(self.device):
+            for k, v in tensors.items():
+                d = [t.to(self.device, torch.float32).contiguous() for t in (v if isinstance(v, tuple) else (v,))]
+                _lib.check(fn(self._handle, k.encode(), *[t.data_ptr() for t in d], d[0].numel(), stream))
+                del d
+            if finalize:
+                _lib.check(getattr(L, self._prefix + "_finalize")(self._handle, stream))
+            if synchronize:
+                torch.cuda.synchronize()
 
     # --- nn.Module-like surface the reference callers use (SURVEY.md §8(b) "Attributes read") ---
     def eval(self):
@@ -100,12 +168,7 @@ class _HipModule:
         unexpected = [k for k in params if k not in shapes]
         if strict and (missing or unexpected):
             raise RuntimeError(f"load_state_dict: missing keys {missing[:5]}..., unexpected keys {unexpected[:5]}...")
-        for k, shp in shapes.items():
-            if k in params:
-                v = params[k].detach().to("cpu", torch.float32).contiguous()
-                if tuple(v.shape) != tuple(shp):
-                    raise RuntimeError(f"load_state_dict: {k} has shape {tuple(v.shape)}, expected {tuple(shp)}")
-                self._sd[k] = v
+        self._sd.update(_checked_tensors(params, shapes, "load_state_dict", strict=False))
         self._load_freqs(sf, tf)
         self._dirty = True
         return missing, unexpected
@@ -125,16 +188,7 @@ class _HipModule:
             pass
 
     def _upload(self, extra: Dict[str, torch.Tensor]):
-        L = _lib.load()
-        setw = getattr(L, self._prefix + "_set_weight")
-        stream = _lib.current_stream()
-        with torch.cuda.device(self.device):
-            for name, v in list(self._sd.items()) + list(extra.items()):
-                d = v.to(self.device, torch.float32, non_blocking=False).contiguous()
-                _lib.check(setw(self._handle, name.encode(), d.data_ptr(), d.numel(), stream))
-                del d
-            _lib.check(getattr(L, self._prefix + "_finalize")(self._handle, stream))
-            torch.cuda.synchronize()
+        self._push(self._prefix + "_set_weight", {**self._sd, **extra}, finalize=True)
         self._dirty = False
 
 
@@ -142,11 +196,86 @@ MAX_FRAMES = 32        # gtav_dit_create's range (include/gtav_amd.h gtav_dit_co
 TRAIN_MAX_FRAMES = 8   # gtav_dit_train_enable's default; DiT(train_max_frames=n) raises it to n <= MAX_FRAMES (gtav_dit_train_allow_window)
 
 
+def _train_options(trainable, max_frames, recompute, dtype, range_policy, lora_rank, lora_alpha, ema_decay, ema_warmup):
+    """The seven train_* options of DiT(), checked and normalised: (train_max_frames or None, recompute, bf16 operands?, range policy, LoRA rank or None,
+    LoRA alpha or None, EMA decay or None, EMA warm-up)."""
+    # opt-in to training windows of up to train_max_frames frames (include/gtav_amd.h gtav_dit_train_allow_window); None: TRAIN_MAX_FRAMES.  The saved
+    # activations are sized by max_batch x min(max_frames, train_max_frames): about 1.3 MB per token for DiT-S/2, 6 GB for one 32-frame sample
+    if max_frames is not None:
+        if not TRAIN_MAX_FRAMES <= int(max_frames) <= MAX_FRAMES:
+            raise ValueError(f"train_max_frames={max_frames}: the training step serves windows of {TRAIN_MAX_FRAMES} to {MAX_FRAMES} frames")
+        if not trainable:
+            raise ValueError("train_max_frames needs trainable=True (an inference model serves windows of up to max_frames as it is)")
+        max_frames = int(max_frames)
+    # opt-in to activation recomputation (include/gtav_amd.h gtav_dit_train_set_recompute): the forward keeps the block inputs only and the backward re-runs
+    # each block before differentiating it: the same bits as the default, 0.147 MB of saved activations per token instead of 1.31 for DiT-S/2, and a step
+    # that takes 0.96 of a training forward longer (DESIGN.md 7, measured at batch 16 x 5 frames: 48.5 -> 62.7 ms)
+    if recompute and not trainable:
+        raise ValueError("train_recompute=True needs trainable=True (an inference model saves no activations)")
+    # operand type of the training step (include/gtav_amd.h gtav_dit_train_enable_typed): torch.bfloat16 is the reference's `--mixed_precision bf16`
+    # (fp32 range, no loss scaling needed), torch.float16 the default (loss-scaled)
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"train_dtype: {dtype} (torch.float16 or torch.bfloat16)")
+    if dtype == torch.bfloat16 and not trainable:
+        raise ValueError("train_dtype=torch.bfloat16 needs trainable=True (an inference model picks its operand type with set_operand_dtype)")
+    # opt-in to operand groups of both types on the training handle (include/gtav_amd.h gtav_dit_train_allow_mixed): "auto" lets train_autorange() /
+    # train_set_group_dtype() move single layer groups to bf16 while the run goes on; train_dtype is then the type every group starts on.  "report" (default):
+    # one type for every group, a saturating forward skips every step (train_stats) and nothing switches
+    if range_policy not in ("report", "auto"):
+        raise ValueError("train_range_policy must be 'report' (one operand type for every layer group) or 'auto' (train_autorange() moves the layer groups "
+                         "whose training forward saturated to bf16 operands)")
+    if range_policy == "auto" and not trainable:
+        raise ValueError("train_range_policy='auto' needs trainable=True (an inference model has range_policy)")
+    # opt-in to low-rank adapter training on a frozen backbone (include/gtav_amd.h gtav_dit_train_set_lora): every half-block's to_qkv / to_out / fc1 / fc2 computes
+    # with W0 + (alpha / rank) B A, the adapter pairs lora_A (rank, K) / lora_B (N, rank) are the only trainable parameters (grad, param_range, grad_arena and the
+    # optimizer state see them alone); state_dict() / load_state_dict() mean the frozen base, lora_state_dict() / load_lora_state_dict() the adapters,
+    # merged_state_dict() the reference-layout weights with the adapters folded in.  alpha defaults to the rank (scale 1)
+    if lora_rank is None and lora_alpha is not None:
+        raise ValueError("train_lora_alpha needs train_lora_rank")
+    if lora_rank is not None:
+        if not trainable:
+            raise ValueError("train_lora_rank needs trainable=True (the adapters exist for the training step; run inference from merged_state_dict())")
+        if int(lora_rank) != lora_rank or int(lora_rank) not in _w.LORA_RANKS:
+            raise ValueError(f"train_lora_rank={lora_rank}: the adapters fill whole MFMA tiles, rank must be one of {_w.LORA_RANKS}")
+        if range_policy == "auto":
+            raise ValueError("train_lora_rank together with train_range_policy='auto' is not implemented (a type switch remakes the weight images from the "
+                             "fp32 masters, without the adapters)")
+        lora_alpha = float(lora_rank if lora_alpha is None else lora_alpha)
+        if not (lora_alpha > 0.0 and math.isfinite(lora_alpha)):
+            raise ValueError(f"train_lora_alpha={lora_alpha}: a positive number")
+        lora_rank = int(lora_rank)
+    # opt-in to averaged weights (include/gtav_amd.h gtav_dit_train_set_ema): the optimizer launch keeps ema <- d_n ema + (1 - d_n) w of every trainable parameter
+    # in fp32 on the GPU, 4 bytes per trainable parameter more; d_n = train_ema_decay, or with train_ema_warmup min(decay, (1 + n) / (10 + n)) at applied step n
+    # (gtav_amd.train.ema_decay_at).  ema_state_dict() / load_ema_state_dict() move the average, `with dit.ema_weights():` computes with it
+    if ema_decay is None and ema_warmup:
+        raise ValueError("train_ema_warmup needs train_ema_decay")
+    if ema_decay is not None:
+        if not trainable:
+            raise ValueError("train_ema_decay needs trainable=True (the average is kept by the optimizer step; an inference model loads ema_state_dict())")
+        ema_decay = float(ema_decay)
+        if not 0.0 < ema_decay < 1.0:
+            raise ValueError(f"train_ema_decay={ema_decay}: the decay of the averaged weights must lie in (0, 1)")
+    return max_frames, bool(recompute), trainable and dtype == torch.bfloat16, range_policy, lora_rank, lora_alpha, ema_decay, bool(ema_warmup)
+
+
 class DiT(_HipModule):
     """model/dit.py:228-376.  `max_batch` (keyword-only, not in the reference) pre-sizes the HBM workspace;
     it grows automatically when a larger batch arrives."""
 
     _prefix = "gtav_dit"
+    # stages: "create" right after gtav_dit_create, "train" at the end of enabling training, "weights" after every weight upload
+    _SETTINGS = {
+        "_fused_temporal": ("gtav_dit_set_fused_temporal", "create", False, lambda v: (int(v),)),
+        "_fused_spatial": ("gtav_dit_set_fused_spatial", "create", None, lambda v: (int(v),)),   # None: the library's default (on where the geometry allows)
+        "_fold": ("gtav_dit_set_fold", "create", None, lambda v: v),                             # (experiments library only)
+        "_weight_prefetch": ("gtav_dit_set_weight_prefetch", "create", None, lambda v: (v,)),
+        "_weight_fill_policy": ("gtav_dit_set_weight_fill_policy", "create", None, lambda v: (v,)),
+        # classifier-free guidance scale of the fused sampler step (set_guidance); None: off
+        "_guidance": ("gtav_dit_set_guidance", "create", None, lambda v: (int(v is not None), 1.0 if v is None else v)),
+        "_loss_scale": ("gtav_dit_set_loss_scale", "train", _ALWAYS, lambda v: (v,)),
+        "_grad_divisor": ("gtav_dit_set_grad_divisor", "train", 1.0, lambda v: (v,)),
+        "_schedule": ("gtav_dit_set_schedule", "weights", None, lambda v: (v, 1000)),            # (a C float[1000])
+    }
 
     def __init__(self, input_h=18, input_w=32, patch_size=2, in_channels=16, hidden_size=1024, depth=12, num_heads=16,
                  mlp_ratio=4.0, external_cond_dim=25, max_frames=5, *, max_batch=1, init_weights=True, trainable=False, range_policy="report",
@@ -154,70 +283,12 @@ class DiT(_HipModule):
                  train_lora_alpha=None, train_ema_decay=None, train_ema_warmup=False):
         super().__init__()
         self._trainable = bool(trainable)    # keyword-only, not in the reference: keeps fp32 masters, gradients and AdamW state on the GPU
-        # opt-in to training windows of up to train_max_frames frames (include/gtav_amd.h gtav_dit_train_allow_window); None: TRAIN_MAX_FRAMES.  The saved
-        # activations are sized by max_batch x min(max_frames, train_max_frames): about 1.3 MB per token for DiT-S/2, 6 GB for one 32-frame sample
-        if train_max_frames is not None:
-            if not TRAIN_MAX_FRAMES <= int(train_max_frames) <= MAX_FRAMES:
-                raise ValueError(f"train_max_frames={train_max_frames}: the training step serves windows of {TRAIN_MAX_FRAMES} to {MAX_FRAMES} frames")
-            if not self._trainable:
-                raise ValueError("train_max_frames needs trainable=True (an inference model serves windows of up to max_frames as it is)")
-            train_max_frames = int(train_max_frames)
-        self._train_max_frames = train_max_frames
-        # opt-in to activation recomputation (include/gtav_amd.h gtav_dit_train_set_recompute): the forward keeps the block inputs only and the backward re-runs
-        # each block before differentiating it: the same bits as the default, 0.147 MB of saved activations per token instead of 1.31 for DiT-S/2, and a step
-        # that takes 0.96 of a training forward longer (measured at batch 16 x 5 frames: 48.5 -> 62.7 ms)
-        if train_recompute and not self._trainable:
-            raise ValueError("train_recompute=True needs trainable=True (an inference model saves no activations)")
-        self._train_recompute = bool(train_recompute)
-        # operand type of the training step (include/gtav_amd.h gtav_dit_train_enable_typed): torch.bfloat16 is the reference's `--mixed_precision bf16`
-        # (fp32 range, no loss scaling needed), torch.float16 the default (loss-scaled)
-        if train_dtype not in (torch.float16, torch.bfloat16):
-            raise ValueError(f"train_dtype: {train_dtype} (torch.float16 or torch.bfloat16)")
-        if train_dtype == torch.bfloat16 and not self._trainable:
-            raise ValueError("train_dtype=torch.bfloat16 needs trainable=True (an inference model picks its operand type with set_operand_dtype)")
-        self._train_bf16 = self._trainable and train_dtype == torch.bfloat16
-        # opt-in to operand groups of both types on the training handle (include/gtav_amd.h gtav_dit_train_allow_mixed): "auto" lets train_autorange() /
-        # train_set_group_dtype() move single layer groups to bf16 while the run goes on; train_dtype is then the type every group starts on.  "report" (default):
-        # one type for every group, a saturating forward skips every step (train_stats) and nothing switches
-        if train_range_policy not in ("report", "auto"):
-            raise ValueError("train_range_policy must be 'report' (one operand type for every layer group) or 'auto' (train_autorange() moves the layer groups "
-                             "whose training forward saturated to bf16 operands)")
-        if train_range_policy == "auto" and not self._trainable:
-            raise ValueError("train_range_policy='auto' needs trainable=True (an inference model has range_policy)")
-        self.train_range_policy = train_range_policy
-        # opt-in to low-rank adapter training on a frozen backbone (include/gtav_amd.h gtav_dit_train_set_lora): every half-block's to_qkv / to_out / fc1 / fc2 computes
-        # with W0 + (alpha / rank) B A, the adapter pairs lora_A (rank, K) / lora_B (N, rank) are the only trainable parameters (grad, param_range, grad_arena and the
-        # optimizer state see them alone); state_dict() / load_state_dict() mean the frozen base, lora_state_dict() / load_lora_state_dict() the adapters,
-        # merged_state_dict() the reference-layout weights with the adapters folded in.  alpha defaults to the rank (scale 1)
-        if train_lora_rank is None and train_lora_alpha is not None:
-            raise ValueError("train_lora_alpha needs train_lora_rank")
-        if train_lora_rank is not None:
-            if not self._trainable:
-                raise ValueError("train_lora_rank needs trainable=True (the adapters exist for the training step; run inference from merged_state_dict())")
-            if int(train_lora_rank) != train_lora_rank or int(train_lora_rank) not in _w.LORA_RANKS:
-                raise ValueError(f"train_lora_rank={train_lora_rank}: the adapters fill whole MFMA tiles, rank must be one of {_w.LORA_RANKS}")
-            if train_range_policy == "auto":
-                raise ValueError("train_lora_rank together with train_range_policy='auto' is not implemented (a type switch remakes the weight images from the "
-                                 "fp32 masters, without the adapters)")
-            train_lora_alpha = float(train_lora_rank if train_lora_alpha is None else train_lora_alpha)
-            if not (train_lora_alpha > 0.0 and math.isfinite(train_lora_alpha)):
-                raise ValueError(f"train_lora_alpha={train_lora_alpha}: a positive number")
-        # opt-in to averaged weights (include/gtav_amd.h gtav_dit_train_set_ema): the optimizer launch keeps ema <- d_n ema + (1 - d_n) w of every trainable parameter
-        # in fp32 on the GPU, 4 bytes per trainable parameter more; d_n = train_ema_decay, or with train_ema_warmup min(decay, (1 + n) / (10 + n)) at applied step n
-        # (gtav_amd.train.ema_decay_at).  ema_state_dict() / load_ema_state_dict() move the average, `with dit.ema_weights():` computes with it
-        if train_ema_decay is None and train_ema_warmup:
-            raise ValueError("train_ema_warmup needs train_ema_decay")
-        if train_ema_decay is not None:
-            if not self._trainable:
-                raise ValueError("train_ema_decay needs trainable=True (the average is kept by the optimizer step; an inference model loads ema_state_dict())")
-            train_ema_decay = float(train_ema_decay)
-            if not 0.0 < train_ema_decay < 1.0:
-                raise ValueError(f"train_ema_decay={train_ema_decay}: the decay of the averaged weights must lie in (0, 1)")
-        self._ema_decay = train_ema_decay
-        self._ema_warmup = bool(train_ema_warmup)
+        (self._train_max_frames, self._train_recompute, self._train_bf16, self.train_range_policy, self._lora_rank, self._lora_alpha, self._ema_decay,
+         self._ema_warmup) = _train_options(self._trainable, train_max_frames, train_recompute, train_dtype, train_range_policy, train_lora_rank,
+                                            train_lora_alpha, train_ema_decay, train_ema_warmup)
+        # the longest window _ensure serves: a trainable handle's saved activations are sized for the training window
+        self._window_limit = self._train_window if self._trainable else MAX_FRAMES
         self._ema_swapped = False
-        self._lora_rank = None if train_lora_rank is None else int(train_lora_rank)
-        self._lora_alpha = train_lora_alpha
         self._lora_sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
         self._lora_host_fresh = True         # the host copies of the adapters are the truth (until an optimizer step moves the handle's)
         self._grads = None
@@ -235,13 +306,11 @@ class DiT(_HipModule):
                                 hidden_size=hidden_size, depth=depth, num_heads=num_heads, mlp_ratio=mlp_ratio,
                                 external_cond_dim=external_cond_dim)
         # a trainable handle is never sized beyond the window the training step implements: _ensure refuses longer ones by name
-        self._capacity_b, self._capacity_t = max_batch, min(max(max_frames, 1), self._train_window if self._trainable else MAX_FRAMES)
+        self._capacity_b, self._capacity_t = max_batch, min(max(max_frames, 1), self._window_limit)
         self._capacity_rows = 0
         hd = hidden_size // num_heads
         self._spatial_freqs = _w.rope_freqs_pixel(hd // 2, 256)   # model/dit.py:259-261
         self._temporal_freqs = _w.rope_freqs_lang(hd)             # model/dit.py:262
-        self._schedule = None
-        self._guidance = None                # classifier-free guidance scale of the fused sampler step (set_guidance); None: off
         # operand groups (include/gtav_amd.h "operand type"): 2 l / 2 l + 1 = spatial / temporal half of block l, 2 depth = patch embedding, 2 depth + 1 = final layer
         self.n_operand_groups = 2 * depth + 2
         self._bf16_groups = set(range(self.n_operand_groups)) if self._train_bf16 else set()
@@ -315,96 +384,99 @@ class DiT(_HipModule):
 
     # ------------------------------------------------------------------------------------------
     def _ensure(self, B: int, T: int, cond_rows: int = 0):
-        # window limits first, before a handle is rebuilt or destroyed
+        """A handle with room for B x T frames (and cond_rows conditioning rows) that holds the current weights.  The usual call (handle there, nothing
+        dirty, no growth) is the four tests below and nothing else."""
+        if T > self._window_limit:           # window limits first, before a handle is rebuilt or destroyed
+            self._refuse_window(T)
+        if (cond_rows > max(self._capacity_rows, self._capacity_b * self._capacity_t)) or T > self._capacity_t or B > self._capacity_b:
+            self._grow(B, T, cond_rows)
+        if not self._handle:
+            self._create_handle()
+        if self._dirty:
+            self._sync_weights()
+
+    def _refuse_window(self, T):
         if T > MAX_FRAMES:
             raise ValueError(f"a window of {T} frames: the temporal attention serves at most {MAX_FRAMES} (max_frames <= {MAX_FRAMES})")
-        if self._trainable and self._train_max_frames is not None and T > self._train_max_frames:
+        if self._train_max_frames is not None:
             raise ValueError(f"a window of {T} frames on a trainable DiT constructed with train_max_frames={self._train_max_frames}: the handle's saved "
                              f"activations are sized for at most {self._train_max_frames} frames (train_max_frames <= {MAX_FRAMES})")
-        if self._trainable and self._train_max_frames is None and T > TRAIN_MAX_FRAMES:
-            raise ValueError(f"a window of {T} frames on a trainable DiT: the training step (backward temporal attention, adaLN-gradient reduction) is "
-                             f"implemented for at most {TRAIN_MAX_FRAMES} frames; windows up to {MAX_FRAMES} need trainable=False")
-        grow = (cond_rows > max(self._capacity_rows, self._capacity_b * self._capacity_t)) or T > self._capacity_t or B > self._capacity_b
-        if grow and self._handle and self._trainable and self._grads is not None:
+        raise ValueError(f"a window of {T} frames on a trainable DiT: the training step (backward temporal attention, adaLN-gradient reduction) is "
+                         f"implemented for at most {TRAIN_MAX_FRAMES} frames; windows up to {MAX_FRAMES} need trainable=False")
+
+    def _grow(self, B, T, cond_rows):
+        """Raises the capacities to what the call needs and drops the handle, or refuses."""
+        if self._handle and self._trainable and self._grads is not None:
             # the fp32 masters and the AdamW state live only in the handle: refuse BEFORE anything is destroyed (the handle stays usable)
             raise RuntimeError(f"a trainable DiT cannot grow its workspace after training was enabled (batch {B} > {self._capacity_b}, window {T} > "
                                f"{self._capacity_t} or {cond_rows} conditioning rows > {max(self._capacity_rows, self._capacity_b * self._capacity_t)}): "
                                "size it with max_batch / max_frames / reserve() before the first step")
-        if grow:
-            self._capacity_rows = max(self._capacity_rows, cond_rows)
-            self._capacity_t = max(self._capacity_t, T)
-            self._capacity_b = max(self._capacity_b, B)
-            self._free()
-        if not self._handle:
-            L = _lib.load()
-            cfg = _lib.DitConfig(max_frames=self._capacity_t, max_batch=self._capacity_b,
-                                 max_cond_rows=max(self._capacity_b * self._capacity_t, self._capacity_rows), **self._cfg_kwargs)
-            with torch.cuda.device(self.device):
-                _lib.check(L.gtav_dit_create(C.byref(cfg), C.byref(self._handle)))
-                if getattr(self, "_fused_temporal", False):
-                    _lib.check(L.gtav_dit_set_fused_temporal(self._handle, 1))
-                if getattr(self, "_fused_spatial", None) is not None:     # None: the library's default (on where the geometry allows)
-                    _lib.check(L.gtav_dit_set_fused_spatial(self._handle, int(self._fused_spatial)))
-                if getattr(self, "_fold", None) is not None:
-                    _lib.check(L.gtav_dit_set_fold(self._handle, *self._fold))
-                if getattr(self, "_weight_prefetch", None) is not None:
-                    _lib.check(L.gtav_dit_set_weight_prefetch(self._handle, int(self._weight_prefetch)))
-                if getattr(self, "_weight_fill_policy", None) is not None:
-                    _lib.check(L.gtav_dit_set_weight_fill_policy(self._handle, int(self._weight_fill_policy)))
-                if self._guidance is not None:
-                    _lib.check(L.gtav_dit_set_guidance(self._handle, 1, self._guidance))
-                if not self._train_mixed:
-                    for g in sorted(self._bf16_groups):                  # a re-created handle keeps the operand types chosen before
-                        _lib.check(L.gtav_dit_set_operand_dtype(self._handle, g, 1))
-                if self._trainable:
-                    if self._lora_rank:                                  # (first: the adapters are then what train_param_count counts)
-                        _lib.check(L.gtav_dit_train_set_lora(self._handle, self._lora_rank, self._lora_alpha))
-                    if self._ema_decay is not None:
-                        _lib.check(L.gtav_dit_train_set_ema(self._handle, self._ema_decay, int(self._ema_warmup)))
-                    n = C.c_int64(0)
-                    _lib.check(L.gtav_dit_train_param_count(self._handle, C.byref(n)))
-                    # one contiguous fp32 gradient arena owned by torch: a single all-reduce covers the whole model (train.py)
-                    self._grads = torch.zeros(n.value, device=self.device, dtype=torch.float32)
-                    if self._train_max_frames is not None:
-                        _lib.check(L.gtav_dit_train_allow_window(self._handle, self._train_max_frames))
-                    if self._train_recompute:
-                        _lib.check(L.gtav_dit_train_set_recompute(self._handle, 1))
-                    if self._train_mixed:
-                        _lib.check(L.gtav_dit_train_allow_mixed(self._handle, 1))
-                    if self._train_bf16:
-                        _lib.check(L.gtav_dit_train_enable_typed(self._handle, self._grads.data_ptr(), n.value, 1))
-                    else:
-                        _lib.check(L.gtav_dit_train_enable(self._handle, self._grads.data_ptr(), n.value))
-                    if self._train_mixed:                                # a re-created handle keeps the per-group types (no weight is set yet: nothing to convert)
-                        start = set(range(self.n_operand_groups)) if self._train_bf16 else set()
-                        for g in sorted(self._bf16_groups ^ start):
-                            _lib.check(L.gtav_dit_train_set_group_dtype(self._handle, g, 1 if g in self._bf16_groups else 0, _lib.current_stream()))
-                    _lib.check(L.gtav_dit_set_loss_scale(self._handle, self._loss_scale))
-                    if self.grad_divisor != 1.0:
-                        _lib.check(L.gtav_dit_set_grad_divisor(self._handle, self.grad_divisor))
-            self._dirty = True
-            self._lora_host_fresh = True     # (a new handle holds no adapters yet: the host copies are all there is)
-            self._ema_swapped = False
-        if self._dirty:
-            if self._ema_swapped:
-                raise _lib.GtavError("new weights while the averaged weights are swapped in (ema_weights()): leave the context first")
-            keep_ema = None
-            if self._lora_rank and not self._lora_host_fresh:            # the re-upload below sends the adapters too: the trained ones, not the stale host copies
-                # (and a weight upload sets the average to the weight: the trained adapters' average is put back behind it)
-                keep_ema = self._pull_ema() if self._ema_decay is not None else None
-                self._pull_lora()
-            gh, gw = self.input_h // self.patch_size, self.input_w // self.patch_size
-            sc, ss = _rope_tables_axial(self._spatial_freqs, gh, gw)
-            tc, ts = _rope_tables_temporal(self._temporal_freqs, self._capacity_t)
-            extra = {"tables.timestep_sincos": _timestep_table(), "tables.rope_spatial_cos": sc, "tables.rope_spatial_sin": ss,
-                     "tables.rope_temporal_cos": tc, "tables.rope_temporal_sin": ts}
-            extra.update(self._lora_sd)
-            self._upload(extra)
-            self._lora_host_fresh = True
-            if keep_ema is not None:
-                self._push_ema(keep_ema)
-            if self._schedule is not None:
-                self.set_schedule(self._schedule)
+        self._capacity_rows = max(self._capacity_rows, cond_rows)
+        self._capacity_t = max(self._capacity_t, T)
+        self._capacity_b = max(self._capacity_b, B)
+        self._free()
+
+    def _create_handle(self):
+        L = _lib.load()
+        cfg = _lib.DitConfig(max_frames=self._capacity_t, max_batch=self._capacity_b,
+                             max_cond_rows=max(self._capacity_b * self._capacity_t, self._capacity_rows), **self._cfg_kwargs)
+        with torch.cuda.device(self.device):
+            _lib.check(L.gtav_dit_create(C.byref(cfg), C.byref(self._handle)))
+            self._replay("create")
+            if not self._train_mixed:
+                for g in sorted(self._bf16_groups):                      # a re-created handle keeps the operand types chosen before
+                    _lib.check(L.gtav_dit_set_operand_dtype(self._handle, g, 1))
+            if self._trainable:
+                self._enable_training(L)
+        self._dirty = True
+        self._lora_host_fresh = True         # (a new handle holds no adapters yet: the host copies are all there is)
+        self._ema_swapped = False
+
+    def _enable_training(self, L):
+        """Training on a new handle; the order matters."""
+        if self._lora_rank:                                              # (first: the adapters are then what train_param_count counts)
+            _lib.check(L.gtav_dit_train_set_lora(self._handle, self._lora_rank, self._lora_alpha))
+        if self._ema_decay is not None:
+            _lib.check(L.gtav_dit_train_set_ema(self._handle, self._ema_decay, int(self._ema_warmup)))
+        n = C.c_int64(0)
+        _lib.check(L.gtav_dit_train_param_count(self._handle, C.byref(n)))
+        # one contiguous fp32 gradient arena owned by torch: a single all-reduce covers the whole model (train.py)
+        self._grads = torch.zeros(n.value, device=self.device, dtype=torch.float32)
+        if self._train_max_frames is not None:
+            _lib.check(L.gtav_dit_train_allow_window(self._handle, self._train_max_frames))
+        if self._train_recompute:
+            _lib.check(L.gtav_dit_train_set_recompute(self._handle, 1))
+        if self._train_mixed:
+            _lib.check(L.gtav_dit_train_allow_mixed(self._handle, 1))
+        if self._train_bf16:
+            _lib.check(L.gtav_dit_train_enable_typed(self._handle, self._grads.data_ptr(), n.value, 1))
+        else:
+            _lib.check(L.gtav_dit_train_enable(self._handle, self._grads.data_ptr(), n.value))
+        if self._train_mixed:                                            # a re-created handle keeps the per-group types (no weight is set yet: nothing to convert)
+            start = set(range(self.n_operand_groups)) if self._train_bf16 else set()
+            for g in sorted(self._bf16_groups ^ start):
+                _lib.check(L.gtav_dit_train_set_group_dtype(self._handle, g, 1 if g in self._bf16_groups else 0, _lib.current_stream()))
+        self._replay("train")
+
+    def _sync_weights(self):
+        if self._ema_swapped:
+            raise _lib.GtavError("new weights while the averaged weights are swapped in (ema_weights()): leave the context first")
+        keep_ema = None
+        if self._lora_rank and not self._lora_host_fresh:                # the re-upload below sends the adapters too: the trained ones, not the stale host copies
+            # (and a weight upload sets the average to the weight: the trained adapters' average is put back behind it)
+            keep_ema = self._pull_ema() if self._ema_decay is not None else None
+            self._pull_lora()
+        gh, gw = self.input_h // self.patch_size, self.input_w // self.patch_size
+        sc, ss = _rope_tables_axial(self._spatial_freqs, gh, gw)
+        tc, ts = _rope_tables_temporal(self._temporal_freqs, self._capacity_t)
+        extra = {"tables.timestep_sincos": _timestep_table(), "tables.rope_spatial_cos": sc, "tables.rope_spatial_sin": ss,
+                 "tables.rope_temporal_cos": tc, "tables.rope_temporal_sin": ts}
+        extra.update(self._lora_sd)
+        self._upload(extra)
+        self._lora_host_fresh = True
+        if keep_ema is not None:
+            self._push_ema(keep_ema)
+        self._replay("weights")
 
     def reserve(self, max_batch: int, max_frames: Optional[int] = None, noise_steps: int = 0):
         """Sizes the handle's HBM workspace once for the largest batch / window / per-frame conditioning table a run will use
@@ -597,20 +669,15 @@ class DiT(_HipModule):
 
     @loss_scale.setter
     def loss_scale(self, v: float):
-        self._loss_scale = float(v)
-        if self._handle:
-            _lib.check(_lib.load().gtav_dit_set_loss_scale(self._handle, self._loss_scale))
+        self._set("_loss_scale", float(v))
 
     def grad(self, name: str) -> torch.Tensor:
         """Unscaled gradient of one trainable parameter in its state-dict shape (a LoRA model: of an adapter; the base is frozen and refused by name)."""
         shapes = self._train_shapes()
         if name not in shapes:
             raise _lib.GtavError(f"grad: '{name}' is not a trainable parameter" + (" (a LoRA model trains its lora_A / lora_B adapters only)" if self._lora_rank else ""))
-        shp = shapes[name]
-        out = torch.empty(shp, device=self.device, dtype=torch.float32)
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().gtav_dit_get_grad(self._handle, name.encode(), out.data_ptr(), out.numel(), _lib.current_stream()))
-        return out / (self._loss_scale * self.grad_divisor)
+        out = self._pull("gtav_dit_get_grad", {name: shapes[name]}, cpu=False)[name]     # (stays on the device)
+        return out / (self._loss_scale * self._grad_divisor)
 
     def residual_after(self, k: int, B: int, T: int) -> torch.Tensor:
         """Residual stream of the last forward_train after k branch additions (4 per block; k = 4 (i + 1) is the output of block i),
@@ -639,16 +706,12 @@ class DiT(_HipModule):
         """AdamW state of every trainable parameter as CPU tensors: "m.<name>" / "v.<name>" (first / second moments, state-dict shapes)
         plus "step" = [applied steps, skipped steps] — what accelerator.save_state keeps for the optimizer (train_dit.py:765-800)."""
         assert self._trainable and self._handle, "no optimizer state: construct with trainable=True and run a step (or reserve()) first"
-        L = _lib.load()
         out = {}
+        for k, (m, v) in self._pull("gtav_dit_get_opt_state", self._train_shapes(), ptrs=2).items():
+            out["m." + k], out["v." + k] = m, v
+        a, sk = C.c_int64(0), C.c_int64(0)
         with torch.cuda.device(self.device):
-            for k, shp in self._train_shapes().items():
-                m = torch.empty(shp, device=self.device, dtype=torch.float32)
-                v = torch.empty_like(m)
-                _lib.check(L.gtav_dit_get_opt_state(self._handle, k.encode(), m.data_ptr(), v.data_ptr(), m.numel(), _lib.current_stream()))
-                out["m." + k], out["v." + k] = m.cpu(), v.cpu()
-            a, sk = C.c_int64(0), C.c_int64(0)
-            _lib.check(L.gtav_dit_get_opt_step(self._handle, C.byref(a), C.byref(sk), _lib.current_stream()))
+            _lib.check(_lib.load().gtav_dit_get_opt_step(self._handle, C.byref(a), C.byref(sk), _lib.current_stream()))
         out["step"] = torch.tensor([a.value, sk.value], dtype=torch.int64)
         return out
 
@@ -656,39 +719,28 @@ class DiT(_HipModule):
         """Inverse of opt_state_dict (the weights themselves: load_state_dict).  The handle is built first if it does not exist yet."""
         assert self._trainable, "construct the model with trainable=True"
         self._ensure(self._capacity_b, self._capacity_t)
-        L = _lib.load()
+        shapes = self._train_shapes()
+        m, v = (_checked_tensors({k: state[p + k] for k in shapes}, shapes, "load_opt_state_dict") for p in ("m.", "v."))
+        self._push("gtav_dit_set_opt_state", {k: (m[k], v[k]) for k in shapes}, synchronize=False)
+        st = state["step"]
         with torch.cuda.device(self.device):
-            for k, shp in self._train_shapes().items():
-                m = state["m." + k].to(self.device, torch.float32).contiguous()
-                v = state["v." + k].to(self.device, torch.float32).contiguous()
-                if tuple(m.shape) != tuple(shp) or tuple(v.shape) != tuple(shp):
-                    raise RuntimeError(f"load_opt_state_dict: {k} has shape {tuple(m.shape)}, expected {tuple(shp)}")
-                _lib.check(L.gtav_dit_set_opt_state(self._handle, k.encode(), m.data_ptr(), v.data_ptr(), m.numel(), _lib.current_stream()))
-            st = state["step"]
-            _lib.check(L.gtav_dit_set_opt_step(self._handle, int(st[0]), int(st[1]), _lib.current_stream()))
+            _lib.check(_lib.load().gtav_dit_set_opt_step(self._handle, int(st[0]), int(st[1]), _lib.current_stream()))
             torch.cuda.synchronize()
 
     @property
     def grad_divisor(self) -> float:
-        return getattr(self, "_grad_divisor", 1.0)
+        return self._grad_divisor
 
     @grad_divisor.setter
     def grad_divisor(self, v: float):
         """The gradient arena holds the SUM over this many ranks (all-reduce SUM): the optimizer step divides, the arena is not rescaled."""
-        self._grad_divisor = float(v)
-        if self._handle:
-            _lib.check(_lib.load().gtav_dit_set_grad_divisor(self._handle, self._grad_divisor))
+        self._set("_grad_divisor", float(v))
 
     def pull_weights(self):
         """Copies the trained fp32 masters from the GPU back into the host state dict (checkpoints, state_dict())."""
         if self._ema_swapped:
             raise _lib.GtavError("pull_weights: the averaged weights are swapped in (ema_weights()); the trained ones are read outside the context (the average: ema_state_dict())")
-        L = _lib.load()
-        with torch.cuda.device(self.device):
-            for k, shp in self._shapes().items():
-                out = torch.empty(shp, device=self.device, dtype=torch.float32)
-                _lib.check(L.gtav_dit_get_weight(self._handle, k.encode(), out.data_ptr(), out.numel(), _lib.current_stream()))
-                self._sd[k] = out.cpu()
+        self._sd.update(self._pull("gtav_dit_get_weight", self._shapes()))
 
     # ------------------------------------------------------------------------------------------
     # averaged weights (train_ema_decay=...; include/gtav_amd.h gtav_dit_train_set_ema)
@@ -707,21 +759,10 @@ class DiT(_HipModule):
             raise _lib.GtavError(f"{who}: this DiT keeps no averaged weights (construct it with trainable=True, train_ema_decay=...)")
 
     def _pull_ema(self):
-        L, out = _lib.load(), OrderedDict()
-        with torch.cuda.device(self.device):
-            for k, shp in self._train_shapes().items():
-                e = torch.empty(shp, device=self.device, dtype=torch.float32)
-                _lib.check(L.gtav_dit_get_ema(self._handle, k.encode(), e.data_ptr(), e.numel(), _lib.current_stream()))
-                out[k] = e.cpu()
-        return out
+        return self._pull("gtav_dit_get_ema", self._train_shapes())
 
     def _push_ema(self, sd):
-        L = _lib.load()
-        with torch.cuda.device(self.device):
-            for k in self._train_shapes():
-                d = sd[k].to(self.device, torch.float32).contiguous()
-                _lib.check(L.gtav_dit_set_ema(self._handle, k.encode(), d.data_ptr(), d.numel(), _lib.current_stream()))
-            torch.cuda.synchronize()
+        self._push("gtav_dit_set_ema", sd)
 
     def ema_state_dict(self) -> "OrderedDict[str, torch.Tensor]":
         """The averaged weights as CPU tensors in the reference's key layout: every trainable tensor from the GPU's fp32 shadow, the constants (rotary
@@ -741,16 +782,7 @@ class DiT(_HipModule):
         """Inverse of ema_state_dict: every trainable tensor's average in its shape (other keys, the rotary frequencies among them, are ignored).  The weights
         themselves: load_state_dict, which also sets the average to the weights it loads — so call this after it."""
         self._need_ema("load_ema_state_dict")
-        shapes = self._train_shapes()
-        missing = [k for k in shapes if k not in sd]
-        if missing:
-            raise RuntimeError(f"load_ema_state_dict: missing keys {missing[:5]}{'...' if len(missing) > 5 else ''}")
-        new = {}
-        for k, shp in shapes.items():
-            v = sd[k].detach().to("cpu", torch.float32).contiguous()
-            if tuple(v.shape) != tuple(shp):
-                raise RuntimeError(f"load_ema_state_dict: {k} has shape {tuple(v.shape)}, expected {tuple(shp)}")
-            new[k] = v
+        new = _checked_tensors(sd, self._train_shapes(), "load_ema_state_dict", allow_unexpected=True)
         self._ensure(self._capacity_b, self._capacity_t)
         self._push_ema(new)
 
@@ -810,23 +842,12 @@ class DiT(_HipModule):
         self._lora_sd = OrderedDict((k, sd[k]) for k in self._lora_shapes())
         self._lora_host_fresh = True
         if self._handle and not self._dirty:
-            L, stream = _lib.load(), _lib.current_stream()
-            with torch.cuda.device(self.device):
-                for k, v in self._lora_sd.items():
-                    d = v.to(self.device, torch.float32).contiguous()
-                    _lib.check(L.gtav_dit_set_weight(self._handle, k.encode(), d.data_ptr(), d.numel(), stream))
-                _lib.check(L.gtav_dit_finalize(self._handle, stream))
-                torch.cuda.synchronize()
+            self._push("gtav_dit_set_weight", self._lora_sd, finalize=True)
 
     def _pull_lora(self):
         if self._ema_swapped:
             raise _lib.GtavError("the averaged adapters are swapped in (ema_weights()); the trained ones are read outside the context (the average: ema_state_dict())")
-        L = _lib.load()
-        with torch.cuda.device(self.device):
-            for k, shp in self._lora_shapes().items():
-                out = torch.empty(shp, device=self.device, dtype=torch.float32)
-                _lib.check(L.gtav_dit_get_weight(self._handle, k.encode(), out.data_ptr(), out.numel(), _lib.current_stream()))
-                self._lora_sd[k] = out.cpu()
+        self._lora_sd.update(self._pull("gtav_dit_get_weight", self._lora_shapes()))
         self._lora_host_fresh = True
 
     def lora_state_dict(self) -> "OrderedDict[str, torch.Tensor]":
@@ -839,35 +860,16 @@ class DiT(_HipModule):
     def load_lora_state_dict(self, sd: Dict[str, torch.Tensor]):
         """Inverse of lora_state_dict: every adapter, nothing else, in its shape."""
         self._need_lora("load_lora_state_dict")
-        shapes = self._lora_shapes()
-        missing = [k for k in shapes if k not in sd]
-        unexpected = [k for k in sd if k not in shapes]
-        if missing or unexpected:
-            raise RuntimeError(f"load_lora_state_dict: missing keys {missing[:5]}{'...' if len(missing) > 5 else ''}, unexpected keys "
-                               f"{unexpected[:5]}{'...' if len(unexpected) > 5 else ''}")
-        new = {}
-        for k, shp in shapes.items():
-            v = sd[k].detach().to("cpu", torch.float32).contiguous()
-            if tuple(v.shape) != tuple(shp):
-                raise RuntimeError(f"load_lora_state_dict: {k} has shape {tuple(v.shape)}, expected {tuple(shp)} (rank {self._lora_rank})")
-            new[k] = v
-        self._set_lora(new)
+        self._set_lora(_checked_tensors(sd, self._lora_shapes(), "load_lora_state_dict", note=f" (rank {self._lora_rank})"))
 
     def merged_state_dict(self) -> "OrderedDict[str, torch.Tensor]":
         """The reference's key layout with the adapters folded in: every adapted weight is the fp32 W0 + (alpha / rank) B A that the GPU casts into its
         weight images (gtav_dit_lora_get_merged), everything else the frozen base.  Loaded into any DiT it computes what this model computes."""
         self._need_lora("merged_state_dict")
         self._ensure(self._capacity_b, self._capacity_t)
-        sd = self.state_dict()
-        L = _lib.load()
-        with torch.cuda.device(self.device):
-            for k in self._lora_shapes():
-                if not k.endswith(".lora_A.weight"):
-                    continue
-                name = k[: -len(".lora_A.weight")] + ".weight"
-                out = torch.empty(self._shapes()[name], device=self.device, dtype=torch.float32)
-                _lib.check(L.gtav_dit_lora_get_merged(self._handle, name.encode(), out.data_ptr(), out.numel(), _lib.current_stream()))
-                sd[name] = out.cpu()
+        sd, shapes = self.state_dict(), self._shapes()
+        adapted = [k[: -len(".lora_A.weight")] + ".weight" for k in self._lora_shapes() if k.endswith(".lora_A.weight")]
+        sd.update(self._pull("gtav_dit_lora_get_merged", OrderedDict((name, shapes[name]) for name in adapted)))
         return sd
 
     # ------------------------------------------------------------------------------------------
@@ -876,10 +878,7 @@ class DiT(_HipModule):
     def set_schedule(self, alphas_cumprod: torch.Tensor):
         ac = alphas_cumprod.detach().reshape(-1).float().cpu().contiguous()
         assert ac.numel() == 1000
-        self._schedule = ac
-        if self._handle:
-            arr = (C.c_float * 1000).from_buffer_copy(ac.numpy().tobytes())
-            _lib.check(_lib.load().gtav_dit_set_schedule(self._handle, arr, 1000))
+        self._set("_schedule", (C.c_float * 1000).from_buffer_copy(ac.numpy().tobytes()))
 
     def set_guidance(self, scale: Optional[float]):
         """Classifier-free guidance on the actions for the fused sampler step (gtav_dit_set_guidance): with a scale s, prepare_frame_ / denoise_step_ run the
@@ -892,9 +891,7 @@ class DiT(_HipModule):
                 raise ValueError(f"set_guidance: scale {scale} is not finite")
             if not self.external_cond_dim or self.external_cond_dim <= 0:
                 raise ValueError("set_guidance: this model has no external_cond (external_cond_dim=0): there are no actions to guide towards")
-        self._guidance = scale
-        if self._handle:
-            _lib.check(_lib.load().gtav_dit_set_guidance(self._handle, int(scale is not None), 1.0 if scale is None else scale))
+        self._set("_guidance", scale)
 
     def _internal_batch(self, B: int) -> int:
         """Samples a sampler step of batch B runs inside the handle: 2 B while guidance is on.  A guided step never grows the handle by itself."""
@@ -933,7 +930,8 @@ class DiT(_HipModule):
                        "empty_event_pair")
 
     def profile(self, enable: bool):
-        """In-situ per-kernel-class HIP-event timing (measurement passes only; see include/gtav_amd.h)."""
+        """In-situ per-kernel-class HIP-event timing (measurement passes only; see include/gtav_amd.h).  Not one of the recorded settings: a handle that is
+        re-created (growth) comes back with it off."""
         _lib.check(_lib.load().gtav_dit_profile(self._handle, int(bool(enable))))
 
     def profile_read(self):
@@ -943,22 +941,19 @@ class DiT(_HipModule):
         return {k: (ms[i], n[i]) for i, k in enumerate(self.PROFILE_CLASSES)}
 
     def set_graph(self, enable: bool):
-        """hipGraph replay of the fused sampler step on/off (on by default)."""
+        """hipGraph replay of the fused sampler step on/off (on by default).  Not one of the recorded settings: a handle that is re-created (growth)
+        comes back with the default."""
         _lib.check(_lib.load().gtav_dit_set_graph(self._handle, int(bool(enable))))
 
     def set_fused_temporal(self, enable: bool):
         """Temporal QKV projection + temporal attention as one kernel on batch-1 full-window steps (off by default; bit-identical to the two-kernel path;
         1-2 % slower per eager forward, 1-1.6 % faster per replayed captured step: generate.tune_weight_prefetch times both and keeps the faster)."""
-        self._fused_temporal = bool(enable)
-        if self._handle:
-            _lib.check(_lib.load().gtav_dit_set_fused_temporal(self._handle, int(self._fused_temporal)))
+        self._set("_fused_temporal", bool(enable))
 
     def set_fused_spatial(self, enable: bool):
         """Spatial QKV projection + spatial attention as one kernel on steps of 5 or more frames of 144 tokens (gtav_dit_set_fused_spatial; ON by default where
         the geometry allows; bit-identical to the two-kernel path; generate.tune_weight_prefetch times both on the shape it tunes and keeps the faster)."""
-        self._fused_spatial = bool(enable)
-        if self._handle:
-            _lib.check(_lib.load().gtav_dit_set_fused_spatial(self._handle, int(self._fused_spatial)))
+        self._set("_fused_spatial", bool(enable))
 
     def fused_launches(self, B: int, T: int, t0: int = 0) -> int:
         """Bit 0: a step of B x T frames runs the fused spatial to_qkv + attention launch on this handle as it is now; bit 1: the fused temporal one
@@ -972,9 +967,7 @@ class DiT(_HipModule):
         mode = int(mode)
         if mode not in (0, 1) and (mode >> 16) != 1:
             raise ValueError(f"set_weight_prefetch: mode {mode:#x} is neither 0, 1 nor a per-class word (gtav_amd.generate.prefetch_mode)")
-        self._weight_prefetch = mode
-        if self._handle:
-            _lib.check(_lib.load().gtav_dit_set_weight_prefetch(self._handle, mode))
+        self._set("_weight_prefetch", mode)
 
     def set_weight_fill_policy(self, mode: int):
         """Cache policy of the small-M GEMMs' weight fills per class (gtav_dit_set_weight_fill_policy; all default when never called; bit-identical results under
@@ -982,9 +975,7 @@ class DiT(_HipModule):
         mode = int(mode)
         if mode & ~0x1111:
             raise ValueError(f"set_weight_fill_policy: mode {mode:#x} is not a per-class word of nibbles 0 / 1 (gtav_amd.generate.fill_policy_mode)")
-        self._weight_fill_policy = mode
-        if self._handle:
-            _lib.check(_lib.load().gtav_dit_set_weight_fill_policy(self._handle, mode))
+        self._set("_weight_fill_policy", mode)
 
     def set_fold(self, mode: int, min_tokens_a: int = -1, min_tokens_b: int = -1):
         """EXPERIMENTS BUILD ONLY (gtav_amd.lib.load_experiments(), tools/fold_bench.py): the LayerNorm fold of round 3 (gtav_dit_set_fold, csrc/experiments.h) —
@@ -992,9 +983,7 @@ class DiT(_HipModule):
         Correct, and measured slower than the LayerNorm launches at every size: the product library does not carry it."""
         if not getattr(_lib.load(), "_gtav_experiments", False):
             raise _lib.GtavError("set_fold: the LayerNorm fold exists only in the experiments build (gtav_amd.lib.load_experiments())")
-        self._fold = (int(mode), int(min_tokens_a), int(min_tokens_b))
-        if self._handle:
-            _lib.check(_lib.load().gtav_dit_set_fold(self._handle, *self._fold))
+        self._set("_fold", (int(mode), int(min_tokens_a), int(min_tokens_b)))
 
     # ------------------------------------------------------------------------------------------
     # operand type / range safety (include/gtav_amd.h "operand type"; reference: bf16 autocast, generate.py:125-127, train_dit.py:190-198)
@@ -1041,17 +1030,13 @@ class DiT(_HipModule):
                 _lib.check(L.gtav_dit_check(self._handle, _lib.current_stream()))
                 return
             n = C.c_int32(0)
-            _lib.check(L.gtav_dit_autorange(self._handle, C.byref(n), _lib.current_stream()))
+            try:
+                _lib.check(L.gtav_dit_autorange(self._handle, C.byref(n), _lib.current_stream()))
+            finally:                         # (the groups switch before another error of the same check is reported: the handle is the truth either way)
+                switched = self._read_group_dtypes()
+                if switched:
+                    self._dirty = True
             if n.value:
-                d = C.c_int32(0)
-                new = set()
-                for g in range(self.n_operand_groups):
-                    _lib.check(L.gtav_dit_get_operand_dtype(self._handle, g, C.byref(d)))
-                    if d.value == 1:
-                        new.add(g)
-                switched = sorted(new - self._bf16_groups)
-                self._bf16_groups = new
-                self._dirty = True
                 raise _lib.GtavRangeSwitch(f"DiT: an activation exceeded the fp16 range (|x| > 65504) in operand group(s) {switched}; those layers now run "
                                            "on bf16 operands (the reference's own autocast type): results since the last check are clipped — recompute them", switched)
 

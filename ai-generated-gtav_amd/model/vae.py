@@ -56,6 +56,7 @@ class AutoencoderKL(_HipModule):
     """model/vae.py:160-361."""
 
     _prefix = "gtav_vae"
+    _SETTINGS = {"_bf16": ("gtav_vae_set_operand_dtype", "create", False, lambda v: (int(v),))}
 
     def __init__(self, latent_dim, input_height=270, input_width=480, patch_size=24, enc_dim=768, enc_depth=6, enc_heads=12,
                  dec_dim=768, dec_depth=6, dec_heads=12, mlp_ratio=4.0, norm_layer=None, use_variational=True,
@@ -116,8 +117,7 @@ class AutoencoderKL(_HipModule):
             cfg = _lib.VaeConfig(max_frames_per_call=self._capacity, **self._cfg_kwargs)
             with torch.cuda.device(self.device):
                 _lib.check(_lib.load().gtav_vae_create(C.byref(cfg), C.byref(self._handle)))
-                if getattr(self, "_bf16", False):
-                    _lib.check(_lib.load().gtav_vae_set_operand_dtype(self._handle, 1))
+                self._replay("create")
             self._dirty = True
         if self._dirty:
             # model/vae.py:71-76: RotaryEmbedding(dim=head_dim // 4, pixel, max_freq=H*W).get_axial_freqs(H, W)
@@ -175,13 +175,9 @@ class AutoencoderKL(_HipModule):
         the VAE (include/gtav_amd.h "operand type"); the weights are converted again from the fp32 host copies at the next call."""
         if dtype not in (torch.float16, torch.bfloat16):
             raise ValueError(f"set_operand_dtype: {dtype} (torch.float16 or torch.bfloat16)")
-        bf = dtype == torch.bfloat16
-        if bf == getattr(self, "_bf16", False):
-            return
-        self._bf16 = bf
-        if self._handle:
-            _lib.check(_lib.load().gtav_vae_set_operand_dtype(self._handle, 1 if bf else 0))
-            self._dirty = True
+        if (dtype == torch.bfloat16) != self._bf16:
+            self._set("_bf16", dtype == torch.bfloat16)
+            self._dirty = True               # (a handle's weight images are stale)
 
     def check(self):
         """Raises if an input held NaN/inf or an fp16 activation saturated since the last call (gtav_vae_check; synchronises)."""
@@ -192,7 +188,8 @@ class AutoencoderKL(_HipModule):
     PROFILE_CLASSES = ("ln_affine", "gemm_qkv", "attn_spatial", "attn_temporal", "gemm_proj", "gemm_fc1", "gemm_fc2", "other", "empty_event_pair")
 
     def profile(self, enable: bool):
-        """In-situ per-kernel-class HIP-event timing of encode / decode (measurement passes only; include/gtav_amd.h gtav_vae_profile)."""
+        """In-situ per-kernel-class HIP-event timing of encode / decode (measurement passes only; include/gtav_amd.h gtav_vae_profile).  Not one of the
+        recorded settings: a handle that is re-created (growth) comes back with it off."""
         self._ensure(1)
         _lib.check(_lib.load().gtav_vae_profile(self._handle, int(bool(enable))))
 

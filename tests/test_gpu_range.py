@@ -5,6 +5,9 @@ default is fp16 operands (1e-3 parity with the fp32 reference).  A checkpoint wi
 range_policy="auto" the layer groups that saturated move to bf16 operands — the same kernels compiled for v_mfma_f32_16x16x32_bf16 — and the recomputed
 result matches the fp32 oracle to the bf16 bound.  Tolerances: bf16 operands (8 mantissa bits) give 6-9e-3 relative L2 per full-size forward
 (measured in round 1); the bound asserted here is 1.5e-2 for an all-bf16 model and 1e-2 when only the saturated group is bf16."""
+import ctypes
+import functools
+
 import pytest
 import torch
 
@@ -112,10 +115,9 @@ def test_bf16_operands_full_size_dit_batch8_and_cached_step():
     m.check()
 
 
-def test_autorange_moves_exactly_the_saturated_layers_to_bf16():
-    """VERDICT r5 item 5: the x3e5 outlier checkpoint of test_fp16_saturation_is_clamped_and_reported (fc1 of block 0's spatial MLP scaled so that the GELU
-    output exceeds 65504).  range_policy="report": clamped + reported, as before.  range_policy="auto": check() switches operand group 0 — that half-block
-    only — to bf16 and raises GtavRangeSwitch; the recomputed forward is clean and matches the fp32 oracle to the bf16 bound instead of returning clamped values."""
+@functools.lru_cache(maxsize=None)
+def _outlier_case():
+    """(clean weights, outlier weights, config, x, t, a, the fp32 oracle's output for the outlier weights) at B = 1, T = 2; read-only."""
     sd = W.synth_state_dict(W.dit_param_shapes(**SMALL_DIT), seed=3)
     big = dict(sd)
     big["blocks.0.s_mlp.fc1.weight"] = sd["blocks.0.s_mlp.fc1.weight"] * 3e5
@@ -123,6 +125,14 @@ def test_autorange_moves_exactly_the_saturated_layers_to_bf16():
     x, t, a = _inputs(cfg, 1, 2, seed=11)
     with torch.no_grad():
         ref = O.dit_forward(big, cfg, x, t, a)
+    return sd, big, cfg, x, t, a, ref
+
+
+def test_autorange_moves_exactly_the_saturated_layers_to_bf16():
+    """VERDICT r5 item 5: the x3e5 outlier checkpoint of test_fp16_saturation_is_clamped_and_reported (fc1 of block 0's spatial MLP scaled so that the GELU
+    output exceeds 65504).  range_policy="report": clamped + reported, as before.  range_policy="auto": check() switches operand group 0 — that half-block
+    only — to bf16 and raises GtavRangeSwitch; the recomputed forward is clean and matches the fp32 oracle to the bf16 bound instead of returning clamped values."""
+    sd, big, cfg, x, t, a, ref = _outlier_case()
     m = DiT(**SMALL_DIT, init_weights=False, max_batch=1, range_policy="auto")
     m.load_state_dict(big)
     clipped = m(x, t, a).clone()
@@ -143,6 +153,33 @@ def test_autorange_moves_exactly_the_saturated_layers_to_bf16():
     m.set_operand_dtype(torch.float16)
     assert rel_l2(m(x, t, a), ref0) < TOL_SMALL
     m.check()
+
+
+def test_autorange_that_also_reports_another_error_leaves_the_model_usable():
+    """A check() that finds a saturation AND another error: gtav_dit_autorange moves the saturated group to bf16 on the handle (which un-finalizes it) and then
+    fails with the other error, here a timestep of 1000 (clamped to 999 and flagged by the conditioning kernel; nothing is read out of range).  check() raises that
+    error, and the model has followed the handle all the same: operand_dtypes() is what gtav_dit_get_operand_dtype reports group by group, and the next forward
+    re-sends the weights, runs, and matches the fp32 oracle to the bf16 bound."""
+    from gtav_amd import lib as L
+    sd, big, cfg, x, t, a, ref = _outlier_case()
+    m = DiT(**SMALL_DIT, init_weights=False, max_batch=1, range_policy="auto")
+    m.load_state_dict(big)
+    bad = t.clone()
+    bad[0, 0] = 1000
+    m(x, bad, a)
+    with pytest.raises(GtavError, match=r"timestep outside \[0, 999\]") as ei:
+        m.check()
+    assert not isinstance(ei.value, GtavRangeSwitch)
+    d, on_handle = ctypes.c_int32(0), []
+    for g in range(m.n_operand_groups):
+        L.check(L.load().gtav_dit_get_operand_dtype(m._handle, g, ctypes.byref(d)))
+        on_handle.append(torch.bfloat16 if d.value == 1 else torch.float16)
+    assert m.operand_dtypes() == on_handle and on_handle.count(torch.bfloat16) >= 1
+    out = m(x, t, a)
+    m.check()
+    e = rel_l2(out, ref)
+    print(f"after a check() that switched and failed: {e:.3e} from the oracle, bf16 groups {[g for g, v in enumerate(on_handle) if v == torch.bfloat16]}")
+    assert e < TOL_BF16
 
 
 def test_autorange_in_the_generation_loop():
