@@ -222,7 +222,6 @@ int gtav_op_gemm_fold_consumer(const void* a, const void* w, int32_t M, int32_t 
 #endif
 int gtav_op_skinny_f32(const float* x, int32_t ldx, const float* w, const float* bias, float* y, int32_t ldy, int32_t M,
                        int32_t N, int32_t K, int32_t act_silu, void* stream) {
-    RET_IF(skinny_init());
     return launch_skinny_f32(x, ldx, w, bias, y, ldy, M, N, K, act_silu, (hipStream_t)stream);
 }
 int gtav_op_ln_modulate(const float* x, void* out, int32_t M, int32_t D, const float* shift, const float* scale,
@@ -355,6 +354,11 @@ int gtav_op_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t
     static_assert(sizeof(gtav_shared::GemmPlan) == 8 * sizeof(int32_t), "plan8 is the GemmPlan");
     GTAV_REQUIRE(plan8, "op_gemm_plan: null argument");
     return gtav_shared::gemm_plan(gtav_shared::GemmProblem{M, N, K, epilogue, qkv_mode, S, splitk, rows_per_gate}, (gtav_shared::GemmPlan*)plan8);
+}
+int gtav_op_launch_plan(int32_t kind, int32_t a0, int32_t a1, int32_t a2, int32_t a3, int32_t a4, int32_t a5, int32_t a6, int32_t* plan12) {
+    GTAV_REQUIRE(plan12 && kind >= 0 && kind <= 9, "op_launch_plan: null argument or unknown kind %d", kind);
+    const int a[7] = {a0, a1, a2, a3, a4, a5, a6};
+    return kind == 0 ? ln_launch_plan(a, plan12) : kind <= 2 ? attn_launch_plan(kind, a, plan12) : kind == 5 ? skinny_launch_plan(a, plan12) : train_launch_plan(kind, a, plan12);
 }
 // the forced ring depth / block shape are thread_locals of the planner (gemm_plan.hip), one set for both operand types
 void gtav_op_gemm_set_stages(int32_t ns) { gtav_shared::gemm_set_stages(ns); }

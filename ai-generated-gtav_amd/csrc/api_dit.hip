@@ -276,7 +276,6 @@ int gtav_dit_create(const gtav_dit_config* c, gtav_dit** out) {
                  c->input_h, c->input_w, c->patch_size);
     GTAV_REQUIRE(c->max_frames >= 1 && c->max_frames <= 32, "max_frames=%d must be in [1, 32]", c->max_frames);
     GTAV_REQUIRE(c->max_batch >= 1 && c->depth >= 1, "bad max_batch/depth");
-    RET_IF(skinny_init());
     gtav_dit* h = new gtav_dit();
     h->cfg = *c;
     h->D = c->hidden_size; h->L = c->depth; h->heads = c->num_heads; h->C = c->in_channels; h->p = c->patch_size;

@@ -16,6 +16,7 @@
 #include <cstdlib>
 
 namespace gtav {
+using namespace gtav_shared;   // the instantiation lists and the planner (launch_plan.h)
 
 namespace {
 
@@ -579,108 +580,65 @@ static int g_attn_sc1 = GTAV_ENV_INT("GTAV_ATTN_SC1", 0) | (GTAV_ENV_INT("GTAV_A
 
 bool attn_spatial_wants_prescaled_q(int S) { return S > 0 && S % 8 == 0 && round_up(S, 32) > 160; }
 
-int launch_attn_spatial(const f16* Q, const f16* K, const f16* Vt, f16* O, int NB, int heads, int S, hipStream_t stream, bool q_prescaled) {
+// what a launch of this problem runs: the launcher's own refusals, then the planner (launch_plan.hip: the one-pass / flash rules, query split and NQT tie rule)
+static int attn_spatial_check_plan(int NB, int heads, int S, bool q_prescaled, AttnSpatialPlan* plan) {
     GTAV_REQUIRE(S > 0 && S % 8 == 0, "attn_spatial: S=%d must be a positive multiple of 8", S);
     GTAV_REQUIRE(!q_prescaled || attn_spatial_wants_prescaled_q(S), "attn_spatial: S=%d runs a kernel that takes plain q", S);
-    const int S_pad = round_up(S, 32);
-    const int nqt = cdiv(S, 16);
-    static const int force_flash = GTAV_ENV_INT("GTAV_ATTN_FORCE_FLASH", 0);   // experiments build: the flash kernel for short sequences too (A/B runs)
-    if (S_pad <= 160 && !force_flash) {   // short sequences (the DiT's frames): one pass per query tile, scores in registers
-        const size_t lds = (size_t)S_pad * 128 + (size_t)64 * (S_pad + 8) * 2;
-        int devid = 0;
-        GTAV_CHECK_HIP(hipGetDevice(&devid));
-        // enough blocks to fill 256 CUs when there are few (frame, head) pairs; each block re-stages K / Vt from L2
-        int qsplit = 1;
-        const int max_split = cdiv(nqt, 4);
-        static const int blocks_target = GTAV_ENV_INT("GTAV_ATTN_S_BLOCKS", 512);
-        while (NB * heads * qsplit < blocks_target && qsplit < max_split) ++qsplit;
-        const dim3 grid(NB * heads, qsplit);
-        const int nk = S_pad / 16;
-#define GTAV_ATTN_1P(NK_)                                                                                                               \
-        do {                                                                                                                          \
-            static unsigned long long devs_ = 0;   /* hipFuncAttributeMaxDynamicSharedMemorySize is per device: one "raised" bit per ordinal */ \
-            if (!(devs_ >> (devid & 63) & 1)) {                                                                                       \
-                GTAV_CHECK_HIP(hipFuncSetAttribute((const void*)attn_spatial_1p_kernel<4, NK_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-                devs_ |= 1ull << (devid & 63);                                                                                        \
-            }                                                                                                                         \
-            GTAV_LAUNCH((attn_spatial_1p_kernel<4, NK_>), grid, dim3(256), lds, stream, Q, K, Vt, O, heads, S, qsplit, g_attn_sc1 & 1);   \
-        } while (0)
-#ifdef GTAV_EXPERIMENTS
-        // experiments build: waves per block of the one-pass kernel at NK = 10 (A/B runs: GTAV_ATTN_1P_NW = 3, 5 or 9; the product runs 4)
-        static const int nw_exp = GTAV_ENV_INT("GTAV_ATTN_1P_NW", 4);
-#define GTAV_ATTN_1P_NW(NW_)                                                                                                            \
-        do {                                                                                                                          \
-            GTAV_CHECK_HIP(hipFuncSetAttribute((const void*)attn_spatial_1p_kernel<NW_, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-            int qs_ = 1;                                                                                                              \
-            GTAV_LAUNCH((attn_spatial_1p_kernel<NW_, 10>), dim3(NB * heads, qs_), dim3(64 * NW_), lds, stream, Q, K, Vt, O, heads, S, qs_, g_attn_sc1 & 1); \
-        } while (0)
-        if (nk == 10 && nw_exp == 3) { GTAV_ATTN_1P_NW(3); GTAV_CHECK_HIP(hipGetLastError()); return 0; }
-        if (nk == 10 && nw_exp == 5) { GTAV_ATTN_1P_NW(5); GTAV_CHECK_HIP(hipGetLastError()); return 0; }
-        if (nk == 10 && nw_exp == 9) { GTAV_ATTN_1P_NW(9); GTAV_CHECK_HIP(hipGetLastError()); return 0; }
-#undef GTAV_ATTN_1P_NW
-#endif
-        if (nk == 2) GTAV_ATTN_1P(2);
-        else if (nk == 4) GTAV_ATTN_1P(4);
-        else if (nk == 6) GTAV_ATTN_1P(6);
-        else if (nk == 8) GTAV_ATTN_1P(8);
-        else GTAV_ATTN_1P(10);
-#undef GTAV_ATTN_1P
-        GTAV_CHECK_HIP(hipGetLastError());
-        return 0;
-    }
-    // long sequences (the VAE's 576 tokens): flash form, K / Vt streamed through a 3-slot LDS ring (48 KiB whatever S is), 4 waves x NQT query tiles per block.
-    // NQT by the fewest padded query tiles; on a tie the larger tile once the grid fills the chip, else the smaller (more blocks)
-    int best = 0, best_pad = 1 << 30, best_nqb = 0;
-    for (int c = 2; c <= 4; ++c) {
-        const int nqb_c = cdiv(nqt, 4 * c), pad = nqb_c * c;
-        const bool better = pad < best_pad || (pad == best_pad && NB * heads * best_nqb >= 512);
-        if (better) best = c, best_pad = pad, best_nqb = nqb_c;
-    }
-    static const int force_nqt = GTAV_ENV_INT("GTAV_ATTN_FLASH_NQT", 0), occ3 = GTAV_ENV_INT("GTAV_ATTN_FLASH_OCC3", 1);   // experiments build: A/B runs
-    if (force_nqt >= 2 && force_nqt <= 4) best = force_nqt, best_nqb = cdiv(nqt, 4 * force_nqt);
-    const int nfh = NB * heads;
-    GTAV_REQUIRE((long long)nfh * best_nqb < (1ll << 31) && (long long)S * 64 * 2 < (1ll << 31), "attn_spatial: grid / sequence too large");
-    const dim3 fgrid(nfh * best_nqb);
-#define GTAV_ATTN_FLASH_(NQT_, OCC_, RG_, PS_) GTAV_LAUNCH((attn_flash_kernel<NQT_, OCC_, RG_, PS_>), fgrid, dim3(256), 0, stream, Q, K, Vt, O, heads, S, nfh, best_nqb, g_attn_sc1)
-#define GTAV_ATTN_FLASH(NQT_, OCC_)                                                                    \
-    do {                                                                                               \
-        if (S % 64 != 0) { if (q_prescaled) GTAV_ATTN_FLASH_(NQT_, OCC_, true, true); else GTAV_ATTN_FLASH_(NQT_, OCC_, true, false); }   \
-        else { if (q_prescaled) GTAV_ATTN_FLASH_(NQT_, OCC_, false, true); else GTAV_ATTN_FLASH_(NQT_, OCC_, false, false); }             \
-    } while (0)
-    if (best == 2) GTAV_ATTN_FLASH(2, 3);
-    else if (best == 3 && occ3) GTAV_ATTN_FLASH(3, 3);
-    else if (best == 3) GTAV_ATTN_FLASH(3, 2);
-    else GTAV_ATTN_FLASH(4, 2);
-#undef GTAV_ATTN_FLASH
-#undef GTAV_ATTN_FLASH_
-    GTAV_CHECK_HIP(hipGetLastError());
+    if (int rc_ = attn_spatial_plan(AttnSpatialProblem{NB, heads, S, q_prescaled}, plan)) return rc_;
+    GTAV_REQUIRE(ATTN_SPATIAL_KERNELS[plan->kernel].family != LF_ATTN_FLASH || ((long long)NB * heads * plan->nqb < (1ll << 31) && (long long)S * 64 * 2 < (1ll << 31)),
+                 "attn_spatial: grid / sequence too large");
     return 0;
 }
-
-int launch_attn_temporal(const f16* q, const f16* kv, f16* O, int B, int P, int D, int Tq, int t0, int Tmax,
-                         hipStream_t stream) {
-    GTAV_REQUIRE(D % 256 == 0 && D <= 2048, "attn_temporal: D=%d must be a multiple of 256 and <= 2048", D);
-    GTAV_REQUIRE(Tq > 0 && t0 >= 0 && t0 + Tq <= Tmax && Tmax <= 32, "attn_temporal: window t0=%d Tq=%d Tmax=%d (max 32)", t0, Tq, Tmax);
-    GTAV_REQUIRE(P > 0 && B > 0 && (long long)B * Tq * P < (1ll << 31), "attn_temporal: B=%d P=%d Tq=%d", B, P, Tq);
-    const int tpc = D / 8, cpb = tpc >= 256 ? 1 : 256 / tpc;  // threads per column, columns per block
-    // The kernel is chosen by the number of VISIBLE frames, never by the cache stride Tmax: a window of <= 8 frames runs the same
-    // kernel, and gives the same bits, whatever capacity its handle was built for.
-    const int Tvis = t0 + Tq;
-    if (Tvis > 8) {
-        if (Tq == 1) {
-            GTAV_LAUNCH((attn_temporal_stream_kernel<1, 8>), dim3(cdiv(B * P, cpb), 1), dim3(tpc * cpb), 0, stream, q, kv, O, B * P, P, D, Tq, t0, Tmax);
+int launch_attn_spatial(const f16* Q, const f16* K, const f16* Vt, f16* O, int NB, int heads, int S, hipStream_t stream, bool q_prescaled) {
+    AttnSpatialPlan plan;
+    if (int rc_ = attn_spatial_check_plan(NB, heads, S, q_prescaled, &plan)) return rc_;
+    const dim3 grid(plan.gx, plan.gy), block(plan.block);
+    return dispatch_kernel<kernel_count(ATTN_SPATIAL_KERNELS)>(plan.kernel, [&](auto I) {
+        constexpr KernelInst R = ATTN_SPATIAL_KERNELS[decltype(I)::value];
+        if constexpr (!R.product && !GTAV_LAB_BUILD) {
+            GTAV_REQUIRE(false, "attn_spatial: this kernel exists only in the experiments build (csrc/build.sh exp)");
+        } else if constexpr (R.family == LF_ATTN_1P) {
+            if (int rc_ = lds_opt_in<attn_spatial_1p_kernel<R.a, R.b>>(LAUNCH_LDS_MAX)) return rc_;
+            GTAV_LAUNCH((attn_spatial_1p_kernel<R.a, R.b>), grid, block, plan.lds, stream, Q, K, Vt, O, heads, S, plan.qsplit, g_attn_sc1 & 1);
         } else {
-            GTAV_LAUNCH((attn_temporal_stream_kernel<8, 4>), dim3(cdiv(B * P, cpb), cdiv(Tq, 8)), dim3(tpc * cpb), 0, stream, q, kv, O, B * P, P, D, Tq, t0, Tmax);
+            GTAV_LAUNCH((attn_flash_kernel<R.a, R.b, R.c != 0, R.d != 0>), grid, block, 0, stream, Q, K, Vt, O, heads, S, NB * heads, plan.nqb, g_attn_sc1);
         }
         GTAV_CHECK_HIP(hipGetLastError());
         return 0;
+    });
+}
+
+static int attn_temporal_check_plan(int B, int P, int D, int Tq, int t0, int Tmax, AttnTemporalPlan* plan) {
+    GTAV_REQUIRE(D % 256 == 0 && D <= 2048, "attn_temporal: D=%d must be a multiple of 256 and <= 2048", D);
+    GTAV_REQUIRE(Tq > 0 && t0 >= 0 && t0 + Tq <= Tmax && Tmax <= 32, "attn_temporal: window t0=%d Tq=%d Tmax=%d (max 32)", t0, Tq, Tmax);
+    GTAV_REQUIRE(P > 0 && B > 0 && (long long)B * Tq * P < (1ll << 31), "attn_temporal: B=%d P=%d Tq=%d", B, P, Tq);
+    return attn_temporal_plan(AttnTemporalProblem{B * P, D, Tq, t0}, plan);
+}
+int launch_attn_temporal(const f16* q, const f16* kv, f16* O, int B, int P, int D, int Tq, int t0, int Tmax,
+                         hipStream_t stream) {
+    AttnTemporalPlan plan;
+    if (int rc_ = attn_temporal_check_plan(B, P, D, Tq, t0, Tmax, &plan)) return rc_;
+    const dim3 grid(plan.gx, plan.gy), block(plan.block);
+    return dispatch_kernel<kernel_count(ATTN_TEMPORAL_KERNELS)>(plan.kernel, [&](auto I) {
+        constexpr KernelInst R = ATTN_TEMPORAL_KERNELS[decltype(I)::value];
+        if constexpr (R.family == LF_ATTN_T) GTAV_LAUNCH(attn_temporal_kernel<R.a>, grid, block, 0, stream, q, kv, O, B * P, P, D, Tq, t0, Tmax, plan.split);
+        else GTAV_LAUNCH((attn_temporal_stream_kernel<R.a, R.b>), grid, block, 0, stream, q, kv, O, B * P, P, D, Tq, t0, Tmax);
+        GTAV_CHECK_HIP(hipGetLastError());
+        return 0;
+    });
+}
+
+// gtav_op_launch_plan, kinds 1 (a = NB, heads, S, q_prescaled) and 2 (a = B, P, D, Tq, t0, Tmax)
+int attn_launch_plan(int kind, const int* a, int* out12) {
+    if (kind == 1) {
+        AttnSpatialPlan plan;
+        if (int rc_ = attn_spatial_check_plan(a[0], a[1], a[2], a[3] != 0, &plan)) return rc_;
+        launch_plan_report(ATTN_SPATIAL_KERNELS[plan.kernel], plan, plan.qsplit, plan.nqb, 0, out12);
+    } else {
+        AttnTemporalPlan plan;
+        if (int rc_ = attn_temporal_check_plan(a[0], a[1], a[2], a[3], a[4], a[5], &plan)) return rc_;
+        launch_plan_report(ATTN_TEMPORAL_KERNELS[plan.kernel], plan, plan.split, 0, 0, out12);
     }
-    static const int split_max = GTAV_ENV_INT("GTAV_ATTN_T_SPLIT_MAX", 1024);
-    const int split = (Tq > 1 && B * P < split_max) ? 1 : 0;   // few columns: one block per (column group, query frame)
-    const dim3 grid(cdiv(B * P, cpb), split ? Tq : 1), block(tpc * cpb);
-    if (Tvis <= 5) GTAV_LAUNCH(attn_temporal_kernel<5>, grid, block, 0, stream, q, kv, O, B * P, P, D, Tq, t0, Tmax, split);
-    else GTAV_LAUNCH(attn_temporal_kernel<8>, grid, block, 0, stream, q, kv, O, B * P, P, D, Tq, t0, Tmax, split);
-    GTAV_CHECK_HIP(hipGetLastError());
     return 0;
 }
 

@@ -17,7 +17,7 @@ PRELOAD="-mllvm -amdgpu-kernarg-preload-count=16"
 BUILD=$(mktemp -d "${TMPDIR:-/tmp}/gtav_build.XXXXXX")
 trap 'rm -rf "$BUILD"' EXIT
 pids=()
-for f in gemm gemm_plan skinny elementwise attention train comm api api_dit api_train api_vae; do
+for f in gemm gemm_plan launch_plan skinny elementwise attention train comm api api_dit api_train api_vae; do
   extra=""
   # attention: keep MFMA accumulators in VGPRs — the softmax works on them every key block, and the AGPR form costs 56
   # v_accvgpr moves per 16 MFMAs there (the GEMMs touch their accumulators only in the epilogue and keep the default)
@@ -28,7 +28,7 @@ for f in gemm gemm_plan skinny elementwise attention train comm api api_dit api_
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -Wno-pass-failed $DEFS $extra "$@" -c $f.hip -o "$BUILD/$f.o" &
   pids+=($!)
 done
-# (gemm_plan: the GEMM planner, host code only, ONE copy for both operand types — never a twin)
+# (gemm_plan, launch_plan: the GEMM planner and the other launchers' planner, host code only, ONE copy for both operand types — never a twin)
 # the bf16-operand twins (common.h "operand type", ops_bf16.h): the same four sources with f16 = __bf16 in a namespace of their own (train: the training step of a
 # bf16 handle, gtav_dit_train_enable_typed).  Never with -DGTAV_EXPERIMENTS: the laboratory kernels exist for fp16 only.
 for f in gemm elementwise attention train; do
@@ -39,7 +39,7 @@ for f in gemm elementwise attention train; do
   pids+=($!)
 done
 for p in "${pids[@]}"; do wait $p; done
-hipcc --offload-arch=gfx950 -shared -fPIC -o "$BUILD/lib.so" "$BUILD"/{gemm,gemm_plan,skinny,elementwise,attention,train,comm,api,api_dit,api_train,api_vae,gemm_bf16,elementwise_bf16,attention_bf16,train_bf16}.o -ldl
+hipcc --offload-arch=gfx950 -shared -fPIC -o "$BUILD/lib.so" "$BUILD"/{gemm,gemm_plan,launch_plan,skinny,elementwise,attention,train,comm,api,api_dit,api_train,api_vae,gemm_bf16,elementwise_bf16,attention_bf16,train_bf16}.o -ldl
 mv -f "$BUILD/lib.so" "$OUT.tmp.$$"
 mv -f "$OUT.tmp.$$" "$OUT"
 echo "built $(realpath $OUT)"

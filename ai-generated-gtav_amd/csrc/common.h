@@ -103,6 +103,20 @@ using gtav_shared::last_error;
         }                                                                                 \
     } while (0)
 
+// Dynamic LDS above 64 KiB needs a per-device opt-in (hipFuncSetAttribute is a per-device setting), once per kernel instantiation: KERNEL is the template
+// argument so that every instantiation has its own word of per-device flags, raised before that instantiation's first launch on the device.
+template <auto KERNEL>
+static int lds_opt_in(int lds) {
+    static unsigned long long devs = 0;
+    int dev = 0;
+    GTAV_CHECK_HIP(hipGetDevice(&dev));
+    if (!(devs >> (dev & 63) & 1)) {
+        GTAV_CHECK_HIP(hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        devs |= 1ull << (dev & 63);
+    }
+    return 0;
+}
+
 // ---- experiment knobs ---------------------------------------------------------------------------
 // The shipped library (build.sh) reads NO environment variables and carries no result-changing switches.  A second
 // build with -DGTAV_EXPERIMENTS (build.sh exp -> libgtav_amd_exp.so, used by tools/ only) compiles in the timing

@@ -9,6 +9,7 @@
 #include <cstring>
 
 namespace gtav {
+using namespace gtav_shared;   // the instantiation lists and the planner (launch_plan.h)
 
 namespace {
 
@@ -847,50 +848,53 @@ __global__ void calib_spin_kernel(unsigned long long ticks, unsigned long long* 
 // -DGTAV_EXPERIMENTS builds: GTAV_LN_FLAGS (see LnPending::flags)
 static int g_ln_flags = GTAV_ENV_INT("GTAV_LN_FLAGS", 7);   // default: all stores written through (B = 1: LN 0.57 -> 0.54 ms per forward)
 
-// ln_wave_row_kernel from this many rows on when there is no pending update (every such launch: 3.4 vs 3.6 us at 720 rows, 7.1 vs 8.9 at 5 760, 45 vs 67 at 46 080)
-static int g_ln_wave_row_min = GTAV_ENV_INT("GTAV_LN_WAVE_ROW_MIN", 0);
-// (Round 2 had tried one wave per row for the batch-1 forward's launches WITH a pending update: 5.2-5.3 us per launch against 4.9 for the row-block
-// kernel at M = 720 in a one-process A/B, profiles/round2/forward_ab_B1_ln_wave_row.txt; round 5 measured the same again, see above.)
-
-#define LN_WAVE_ROW_(MODE, NV, P0, P1, STRIDE, ROWS, RPM) \
-    GTAV_LAUNCH((ln_wave_row_kernel<MODE, NV>), dim3(cdiv(M, 4)), dim3(256), 0, stream, x, ldx, out, M, D, P0, P1, STRIDE, ROWS, RPM, pd_.flags, err_flag)   /* (GTAV_LAUNCH: the profiler's events ride on the dispatch) */
-// ln_row_block_kernel: the slab descriptor of the pending update flat in front (its argument list says why)
-#define LN_ROW_BLOCK_ARGS_(P0, P1, STRIDE, ROWS, RPM) x, ldx, D, pd_.parts, pd_.slab_stride, pd_.ld, pd_.nsplit, pd_.flags, RPM, out, M, P0, P1, STRIDE, ROWS, pd_
-#define LN_DISPATCH(MODE, P0, P1, STRIDE, ROWS, RPM)                                                     \
-    do {                                                                                                  \
-        LnPending pd_;                                                                                    \
-        memset(&pd_, 0, sizeof(pd_));                                                                     \
-        if (pend) pd_ = *pend;                                                                            \
-        pd_.flags = g_ln_flags;                                                                           \
-        pd_.err_flag = err_flag;                                                                          \
-        GTAV_REQUIRE(pd_.tperm_T == 0 || (pd_.tperm_P % 16 == 0 && M % (pd_.tperm_T * pd_.tperm_P) == 0), "ln: bad output row permutation"); \
-        const bool upd_ = pend && pend->parts;   /* a LnPending without slabs carries the output row permutation only */ \
-        GTAV_REQUIRE(!pd_.k_save || (upd_ && !pd_.k_load), "ln: k_save needs a pending update and excludes k_load");                          \
-        GTAV_REQUIRE(!pd_.k_load || !upd_, "ln: k_load excludes a pending update");                                                            \
-        if (pd_.k_save || pd_.k_load) { /* the statistics' shift kept / given: always one block per row (LnPending::k_save) */                 \
-            const dim3 g_(M), b_(round_up(D / 4, 64));                                                    \
-            if (pd_.k_save) GTAV_LAUNCH((ln_row_block_kernel<MODE, true, 1>), g_, b_, 0, stream, LN_ROW_BLOCK_ARGS_(P0, P1, STRIDE, ROWS, RPM)); \
-            else GTAV_LAUNCH((ln_row_block_kernel<MODE, false, 2>), g_, b_, 0, stream, LN_ROW_BLOCK_ARGS_(P0, P1, STRIDE, ROWS, RPM));      \
-        } else if (!upd_ && pd_.tperm_T == 0 && M >= g_ln_wave_row_min && (D == 256 || D == 512 || D == 1024 || D == 2048)) { \
-            if (D == 256) LN_WAVE_ROW_(MODE, 1, P0, P1, STRIDE, ROWS, RPM);                               \
-            else if (D == 512) LN_WAVE_ROW_(MODE, 2, P0, P1, STRIDE, ROWS, RPM);                          \
-            else if (D == 1024) LN_WAVE_ROW_(MODE, 4, P0, P1, STRIDE, ROWS, RPM);                         \
-            else LN_WAVE_ROW_(MODE, 8, P0, P1, STRIDE, ROWS, RPM);                                        \
-        } else { /* one block per row */                                                                  \
-            const dim3 g_(M), b_(round_up(D / 4, 64));                                                    \
-            if (upd_) GTAV_LAUNCH((ln_row_block_kernel<MODE, true>), g_, b_, 0, stream, LN_ROW_BLOCK_ARGS_(P0, P1, STRIDE, ROWS, RPM)); \
-            else GTAV_LAUNCH((ln_row_block_kernel<MODE, false>), g_, b_, 0, stream, LN_ROW_BLOCK_ARGS_(P0, P1, STRIDE, ROWS, RPM));     \
-        }                                                                                                 \
-    } while (0)
+// One LayerNorm launch of either mode (MODE 0: p0 / p1 = shift / scale with their row map; MODE 1: gamma / beta): validate, plan (launch_plan.hip ln_plan: one wave
+// per row or one block per row), dispatch.  ln_check_plan holds the refusals that need no pointer, for the launch and for gtav_op_launch_plan alike.
+static int ln_check_plan(int mode, int M, int D, const LnPending& pd, bool upd, LaunchGeom* plan) {
+    GTAV_REQUIRE(pd.tperm_T == 0 || (pd.tperm_P % 16 == 0 && M % (pd.tperm_T * pd.tperm_P) == 0), "ln: bad output row permutation");
+    GTAV_REQUIRE(!pd.k_save || (upd && !pd.k_load), "ln: k_save needs a pending update and excludes k_load");
+    GTAV_REQUIRE(!pd.k_load || !upd, "ln: k_load excludes a pending update");
+    return ln_plan(LnProblem{mode, M, D, upd, pd.tperm_T != 0, pd.k_save != nullptr, pd.k_load != nullptr}, plan);
+}
+static int ln_launch(int mode, float* x, int ldx, f16* out, int M, int D, const float* p0, const float* p1, int stride, const int* rows, int rpm, const LnPending* pend,
+                     int* err_flag, hipStream_t stream) {
+    LnPending pd;
+    memset(&pd, 0, sizeof(pd));
+    if (pend) pd = *pend;
+    pd.flags = g_ln_flags;
+    pd.err_flag = err_flag;
+    LaunchGeom plan;
+    if (int rc_ = ln_check_plan(mode, M, D, pd, pend && pend->parts, &plan)) return rc_;   // (a LnPending without slabs carries the output row permutation only)
+    const dim3 grid(plan.gx), block(plan.block);
+    return dispatch_kernel<kernel_count(LN_KERNELS)>(plan.kernel, [&](auto I) {
+        constexpr KernelInst R = LN_KERNELS[decltype(I)::value];
+        if constexpr (R.family == LF_LN_WAVE_ROW)   // (GTAV_LAUNCH: the profiler's events ride on the dispatch)
+            GTAV_LAUNCH((ln_wave_row_kernel<R.a, R.b>), grid, block, 0, stream, x, ldx, out, M, D, p0, p1, stride, rows, rpm, pd.flags, err_flag);
+        else   // ln_row_block_kernel: the slab descriptor of the pending update flat in front (its argument list says why)
+            GTAV_LAUNCH((ln_row_block_kernel<R.a, R.b != 0, R.c>), grid, block, 0, stream, x, ldx, D, pd.parts, pd.slab_stride, pd.ld, pd.nsplit, pd.flags, rpm, out, M, p0, p1, stride,
+                        rows, pd);
+        GTAV_CHECK_HIP(hipGetLastError());
+        return 0;
+    });
+}
+// gtav_op_launch_plan, kind 0: a = mode, M, D, slabs, permutation, k_save, k_load
+int ln_launch_plan(const int* a, int* out12) {
+    LnPending pd;
+    memset(&pd, 0, sizeof(pd));
+    if (a[4]) pd.tperm_T = 1, pd.tperm_P = 16;
+    pd.k_save = a[5] ? (float*)16 : nullptr, pd.k_load = a[6] ? (const float*)16 : nullptr;
+    LaunchGeom plan;
+    if (int rc_ = ln_check_plan(a[0], a[1], a[2], pd, a[3] != 0, &plan)) return rc_;
+    launch_plan_report(LN_KERNELS[plan.kernel], plan, 0, 0, 0, out12);
+    return 0;
+}
 
 int launch_ln_modulate(float* x, int ldx, f16* out, int ldo, int M, int D, const float* shift, const float* scale,
                        int mod_stride, const int* rows, int rows_per_mod, const LnPending* pend, int* err_flag, hipStream_t stream) {
     GTAV_REQUIRE(D % 64 == 0 && D <= 2048 && rows_per_mod > 0 && ldo == D, "ln_modulate: D=%d must be %%64, <= 2048, ldo == D", D);
     GTAV_REQUIRE(!pend || !pend->parts || (pend->nsplit >= 1 && pend->nsplit <= 8 && pend->ld % 4 == 0 && (!pend->gate || pend->rows_per_gate > 0)),
                  "ln_modulate: bad pending update");
-    LN_DISPATCH(0, shift, scale, mod_stride, rows, rows_per_mod);
-    GTAV_CHECK_HIP(hipGetLastError());
-    return 0;
+    return ln_launch(0, x, ldx, out, M, D, shift, scale, mod_stride, rows, rows_per_mod, pend, err_flag, stream);
 }
 
 int launch_ln_affine(float* x, int ldx, f16* out, int ldo, int M, int D, const float* gamma, const float* beta,
@@ -898,12 +902,8 @@ int launch_ln_affine(float* x, int ldx, f16* out, int ldo, int M, int D, const f
     GTAV_REQUIRE(D % 64 == 0 && D <= 2048 && ldo == D, "ln_affine: D=%d must be %%64, <= 2048, ldo == D", D);
     GTAV_REQUIRE(!pend || !pend->parts || (pend->nsplit >= 1 && pend->nsplit <= 8 && pend->ld % 4 == 0 && (!pend->gate || pend->rows_per_gate > 0)),
                  "ln_affine: bad pending update");
-    LN_DISPATCH(1, gamma, beta, 0, (const int*)nullptr, 1);
-    GTAV_CHECK_HIP(hipGetLastError());
-    return 0;
+    return ln_launch(1, x, ldx, out, M, D, gamma, beta, 0, nullptr, 1, pend, err_flag, stream);
 }
-#undef LN_DISPATCH
-#undef LN_WAVE_ROW_
 
 int launch_branch_rows(const float* parts, int nsplit, size_t slab_stride, int ld, const float* bias, f16* y, int M, int N, int* err_flag, hipStream_t stream) {
     GTAV_REQUIRE(parts && y && nsplit >= 1 && nsplit <= 8 && M > 0 && N > 0 && N % 4 == 0 && ld % 4 == 0 && N <= ld && slab_stride >= (size_t)M * ld,

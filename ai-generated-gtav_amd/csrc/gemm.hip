@@ -2647,8 +2647,7 @@ static void lab_fields(GemmParams& q, int mask) {
 
 #define GEMM_LAUNCH(kern, grid, block) GTAV_LAUNCH(kern, grid, block, 0, stream, p)
 
-// CU count of the current device, asked once per device (the persistent kernels size their grids by it; the launchers that opt in to large dynamic LDS key
-// their per-device flag by *dev_out)
+// CU count of the current device, asked once per device (the persistent kernels size their grids by it)
 static int g_num_cus[64] = {0};
 static int device_cus(int* dev_out) {
     int dev = 0;
@@ -2662,20 +2661,13 @@ static int device_cus(int* dev_out) {
     return g_num_cus[dev & 63];
 }
 
-// Dynamic LDS above 64 KiB needs a per-device opt-in (hipFuncSetAttribute is a per-device setting), once per kernel instantiation: KERNEL is the template
-// argument so that every instantiation has its own word of per-device flags.  *cus (optional) = CU count of the current device.
+// ... of the persistent kernels: the opt-in (common.h lds_opt_in) and the CU count of the current device
 template <auto KERNEL>
-static int lds_opt_in(int lds, int* cus = nullptr) {
-    static unsigned long long devs = 0;
+static int lds_opt_in(int lds, int* cus) {
     int dev = 0;
-    const int n = device_cus(&dev);
-    GTAV_REQUIRE(n > 0, "gemm: no current device");
-    if (!(devs >> (dev & 63) & 1)) {
-        GTAV_CHECK_HIP(hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        devs |= 1ull << (dev & 63);
-    }
-    if (cus) *cus = n;
-    return 0;
+    *cus = device_cus(&dev);
+    GTAV_REQUIRE(*cus > 0, "gemm: no current device");
+    return lds_opt_in<KERNEL>(lds);
 }
 
 // block -> tile map constants of the loader-wave kernels (tile_map_fast); gn: the planner's group width for this tile (gemm_plan.h)

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include "gemm.h"
+#include "launch_plan.h"
 
 namespace gtav {
 
@@ -11,7 +12,12 @@ namespace gtav {
 // ---- skinny.hip --------------------------------------------------------------------------
 int launch_skinny_f32(const float* X, int ldx, const float* W, const float* bias, float* Y, int ldy, int M, int N,
                       int K, int act_silu, hipStream_t stream);
-int skinny_init();  // raises the dynamic-LDS limit of the skinny kernels (call once per process)
+// What a launch of problem a[] would run, as gtav_op_launch_plan reports it (include/gtav_amd.h: the kinds, their integers and the twelve outputs): the launcher's
+// own validation and plan, no device touched.  One per kernel file; attention.hip and train.hip hold several kinds.
+int skinny_launch_plan(const int* a, int* out12);
+int ln_launch_plan(const int* a, int* out12);
+int attn_launch_plan(int kind, const int* a, int* out12);
+int train_launch_plan(int kind, const int* a, int* out12);
 
 // ---- elementwise.hip ---------------------------------------------------------------------
 // Per-noise-step scalars of the fused sampler step, kept in device memory so that a captured hipGraph of the

@@ -7,6 +7,7 @@
 #include "ops.h"
 
 namespace gtav {
+using namespace gtav_shared;   // the instantiation lists and the planner (launch_plan.h)
 
 namespace {
 
@@ -114,70 +115,35 @@ __global__ __launch_bounds__(256) void skinny_f32_kernel(const float* __restrict
 
 }  // namespace
 
-// (FT, RT) variants: (1, 1) small projections; (4, 1) many features, tens of rows (the adaLN table at batch 1); (4, 2) / (8, 2) hundreds of rows
-#define GTAV_SKINNY_VARIANTS(X) X(0, 1, 1) X(1, 1, 1) X(0, 4, 1) X(1, 4, 1) X(0, 4, 2) X(1, 4, 2) X(0, 8, 2)
-#define GTAV_SKINNY_CHUNKED(X) X(5) X(6) X(7)   // (ACT 0, FT 4, RT, KC 128)
-int skinny_init() {
-    static unsigned long long done_devs = 0;   // the attribute is per device (see attention.hip)
-    int devid = 0;
-    GTAV_CHECK_HIP(hipGetDevice(&devid));
-    if (done_devs >> (devid & 63) & 1) return 0;
-#define GTAV_SKINNY_ATTR(A, F, R) GTAV_CHECK_HIP(hipFuncSetAttribute((const void*)skinny_f32_kernel<A, F, R>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));   // (launch_skinny_f32: SKINNY_LDS)
-    GTAV_SKINNY_VARIANTS(GTAV_SKINNY_ATTR)
-#undef GTAV_SKINNY_ATTR
-#define GTAV_SKINNY_ATTR_C(R) GTAV_CHECK_HIP(hipFuncSetAttribute((const void*)skinny_f32_kernel<0, 4, R, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    GTAV_SKINNY_CHUNKED(GTAV_SKINNY_ATTR_C)
-#undef GTAV_SKINNY_ATTR_C
-    done_devs |= 1ull << (devid & 63);
+// what a launch of this problem runs: the launcher's own refusals, then the planner (launch_plan.hip skinny_plan: the measured (FT, RT) / K-chunk rules)
+static int skinny_check_plan(int ldx, int ldy, int M, int N, int K, int act_silu, LaunchGeom* plan) {
+    GTAV_REQUIRE(M > 0 && N > 0 && N % 4 == 0, "skinny: bad M=%d N=%d", M, N);
+    // the bound on K is the LDS of ONE 16-row slab of X (what lds_opt_in raises the kernels to), not a round number: the second projection of the conditioning MLP reads
+    // hidden + the padded action columns, 2080 at hidden 2048 — K <= 2048 refused every forward of that width with actions
+    // (tests/test_gpu_models.py::test_hidden_2048_dit_forward_and_fused_spatial_switch)
+    constexpr int SKINNY_MAX_K = (LAUNCH_LDS_MAX / (16 * (int)sizeof(float)) - 8) / 32 * 32;   // 2528
+    GTAV_REQUIRE(K > 0 && K % 32 == 0 && K <= SKINNY_MAX_K, "skinny: K=%d must be a multiple of 32 and <= %d", K, SKINNY_MAX_K);
+    GTAV_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0 && ldx >= K && ldy >= N, "skinny: bad leading dims");
+    return skinny_plan(SkinnyProblem{M, N, K, act_silu != 0}, plan);
+}
+int skinny_launch_plan(const int* a, int* out12) {
+    LaunchGeom plan;
+    if (int rc_ = skinny_check_plan(a[2], a[1], a[0], a[1], a[2], a[3], &plan)) return rc_;
+    launch_plan_report(SKINNY_KERNELS[plan.kernel], plan, 0, 0, 0, out12);
     return 0;
 }
 
 int launch_skinny_f32(const float* X, int ldx, const float* W, const float* bias, float* Y, int ldy, int M, int N,
                       int K, int act_silu, hipStream_t stream) {
-    GTAV_REQUIRE(M > 0 && N > 0 && N % 4 == 0, "skinny: bad M=%d N=%d", M, N);
-    // the bound on K is the LDS of ONE 16-row slab of X (the attribute skinny_init sets), not a round number: the second projection of the conditioning MLP reads
-    // hidden + the padded action columns, 2080 at hidden 2048 — K <= 2048 refused every forward of that width with actions
-    // (tests/test_gpu_models.py::test_hidden_2048_dit_forward_and_fused_spatial_switch)
-    constexpr int SKINNY_LDS = 160 * 1024, SKINNY_MAX_K = (SKINNY_LDS / (16 * (int)sizeof(float)) - 8) / 32 * 32;   // 2528
-    GTAV_REQUIRE(K > 0 && K % 32 == 0 && K <= SKINNY_MAX_K, "skinny: K=%d must be a multiple of 32 and <= %d", K, SKINNY_MAX_K);
-    GTAV_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0 && ldx >= K && ldy >= N, "skinny: bad leading dims");
-    // four (eight) feature tiles per wave where that still leaves the chip full, 32-row slabs as soon as there are two of them: the adaLN table of a frame
-    // 1.52 -> 0.92 ms at 101 rows (batch 1), 11.3 -> 5.0 ms at 808 rows (batch 8)
-    static const int ft_min_blocks = GTAV_ENV_INT("GTAV_SKINNY_FT_MIN_BLOCKS", 1024);   // experiments build: a huge value = one tile per wave everywhere (A/B)
-    static const int variant = GTAV_ENV_INT("GTAV_SKINNY_VARIANT", 0);                  // experiments build: 41 / 42 / 82 force (FT, RT)
-    int ft = 1, rt = 1;
-    if ((long long)cdiv(N, 256) * cdiv(M, 16) >= ft_min_blocks) {
-        ft = 4;
-        if (M > 32 && (size_t)32 * (K + 8) * sizeof(float) <= 150 * 1024) {
-            rt = 2;
-            if (!act_silu && (long long)cdiv(N, 512) * cdiv(M, 32) >= ft_min_blocks) ft = 8;
-        }
-    }
-    // many features, more than two row tiles, no activation (the adaLN table): 80-112 rows per block on K chunks of 128 (44-61 KiB of LDS: two or three blocks per CU) — W is streamed once per 5-7 row tiles
-    static const int chunked = GTAV_ENV_INT("GTAV_SKINNY_CHUNKED", 1);   // experiments build: 0 = the whole-K slabs above (A/B)
-    if (chunked && !act_silu && M > 32 && K % 128 == 0 && (long long)cdiv(N, 256) >= 256 && variant == 0) {
-        const int tiles = cdiv(M, 16);
-        const int rtc = tiles <= 5 ? 5 : tiles == 6 ? 6 : tiles == 7 ? 7 : 6;   // one block of rows up to 112 rows, 96-row blocks beyond
-        dim3 grid(cdiv(N, 256), cdiv(M, 16 * rtc)), block(256);
-        const size_t lds = (size_t)16 * rtc * (128 + 8) * sizeof(float);
-#define GTAV_SKINNY_LAUNCH_C(R) if (rtc == R) hipLaunchKernelGGL((skinny_f32_kernel<0, 4, R, 128>), grid, block, lds, stream, X, ldx, W, bias, Y, ldy, M, N, K);
-        GTAV_SKINNY_CHUNKED(GTAV_SKINNY_LAUNCH_C)
-#undef GTAV_SKINNY_LAUNCH_C
+    LaunchGeom plan;
+    if (int rc_ = skinny_check_plan(ldx, ldy, M, N, K, act_silu, &plan)) return rc_;
+    return dispatch_kernel<kernel_count(SKINNY_KERNELS)>(plan.kernel, [&](auto I) {
+        constexpr KernelInst R = SKINNY_KERNELS[decltype(I)::value];
+        if (int rc_ = lds_opt_in<skinny_f32_kernel<R.a, R.b, R.c, R.d>>(LAUNCH_LDS_MAX)) return rc_;
+        hipLaunchKernelGGL((skinny_f32_kernel<R.a, R.b, R.c, R.d>), dim3(plan.gx, plan.gy), dim3(plan.block), plan.lds, stream, X, ldx, W, bias, Y, ldy, M, N, K);
         GTAV_CHECK_HIP(hipGetLastError());
         return 0;
-    }
-    if (variant == 41) ft = 4, rt = 1;
-    if (variant == 42) ft = 4, rt = 2;
-    if (variant == 82 && !act_silu) ft = 8, rt = 2;
-    dim3 grid(cdiv(N, 64 * ft), cdiv(M, 16 * rt)), block(256);
-    const size_t lds = (size_t)16 * rt * (K + 8) * sizeof(float);
-#define GTAV_SKINNY_LAUNCH(A, F, R)                                                                                               \
-    if (act_silu == A && ft == F && rt == R) hipLaunchKernelGGL((skinny_f32_kernel<A, F, R>), grid, block, lds, stream, X, ldx, W, bias, Y, ldy, M, N, K);
-    act_silu = act_silu ? 1 : 0;
-    GTAV_SKINNY_VARIANTS(GTAV_SKINNY_LAUNCH)
-#undef GTAV_SKINNY_LAUNCH
-    GTAV_CHECK_HIP(hipGetLastError());
-    return 0;
+    });
 }
 
 }  // namespace gtav

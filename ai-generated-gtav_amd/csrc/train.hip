@@ -9,6 +9,7 @@
 #include "ops.h"
 
 namespace gtav {
+using namespace gtav_shared;   // the instantiation lists and the planner (launch_plan.h)
 
 namespace {
 
@@ -523,7 +524,7 @@ __global__ void mse_bwd_patch_kernel(const float* __restrict__ vpred, const floa
 // Output: dqkv fp16 TILE-MAJOR logical [M][3 D] (q | k | v column blocks of the to_qkv Linear), dq / dk rotated back through the
 // interleaved-pair RoPE (the transpose of a rotation is the rotation by the negative angle).
 // ------------------------------------------------------------------------------------------------------------------------
-constexpr int AB_MAXS = 160;   // bound of the two LDS-resident kernels (DiT: 144); longer frames and S % 16 == 8 run attn_spatial_bwd_stream_kernel
+// (AB_MAXS = 160, the bound of the two LDS-resident kernels, and the LDS geometry ABM_* / ABS_* of the kernels below: launch_plan.h, beside the planner's LDS formulas)
 #ifdef GTAV_EXPERIMENTS
 #include "train_experiments.inc"   // laboratory: the VALU kernel, attn_spatial_bwd_kernel (A/B runs of the tools only)
 #endif
@@ -550,7 +551,6 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f16x4 lds_read_tr(const f16* p) {   // lane 4 q + p' of a 16-lane group passes row q, columns 4 p' ..; lane i gets column i of the 4 rows
     return __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p));
 }
-constexpr int ABM_LP = 72, ABM_DQP = 68, ABM_NW = 9, ABM_MAXT = AB_MAXS / 16;   // 9 waves: one query / key tile each at S = 144 (3 waves: 170 us per launch of 1280 items, 9 waves: 99 us)
 template <int DBG>   // experiments: 1 = no dQ atomics, 2 = no K = 16 MFMAs / transposed reads, 4 = no RoPE / LDS write-back of dK, dV (timing only)
 __global__ __launch_bounds__(64 * ABM_NW) void attn_spatial_bwd_mfma_kernel(const f16* __restrict__ Q, const f16* __restrict__ K, const f16* __restrict__ Vt,
                                                                             const f16* __restrict__ dO, int heads, int S, int D,
@@ -766,10 +766,6 @@ __global__ __launch_bounds__(64 * ABM_NW) void attn_spatial_bwd_mfma_kernel(cons
 // computed.  S may be any positive multiple of 8: rows at or beyond S are never read (zero-filled on the way into LDS / registers), padded keys
 // are masked out of P, padded queries are not stored.  LDS: 40 960 + 8 round_up(S, 16) bytes (S <= 15 360).
 // ------------------------------------------------------------------------------------------------------------------------
-constexpr int ABS_LP = 72, ABS_NW = 8, ABS_CH = 64;
-static inline size_t attn_bwd_stream_lds(int S) {
-    return (size_t)2 * ABS_CH * ABS_LP * 2 + (size_t)ABS_NW * 16 * ABS_LP * 2 + (size_t)ABS_NW * 256 * 2 + (size_t)2 * round_up(S, 16) * 4;
-}
 __global__ __launch_bounds__(64 * ABS_NW) void attn_spatial_bwd_stream_kernel(const f16* __restrict__ Q, const f16* __restrict__ K, const f16* __restrict__ Vt,
                                                                               const f16* __restrict__ dO, int heads, int S, int D,
                                                                               const float* __restrict__ rope_cs, f16* __restrict__ dqkv, int* err_flag) {
@@ -1421,7 +1417,6 @@ __global__ __launch_bounds__(256) void ada_bwd_dx_kernel(const float* __restrict
 // all R <= 80 rows (5 tiles); the dmod chunk goes through LDS 64 columns at a time (A operand: lane (li, g) reads row 16 t + li, column
 // 4 s + g), W rows stream straight into registers (B operand: 64-byte row segments).  The partial sums of a chunk are stored, not
 // added: ada_reduce_kernel sums the chunks in a fixed order (deterministic, no atomics).
-constexpr int ADA_KC = 1024, ADA_RT = 5, ADA_PITCH = 68;
 __global__ __launch_bounds__(1024) void ada_bwd_dx_mfma_kernel(const float* __restrict__ dmod, int MODW, const float* __restrict__ W, int D, int R,
                                                                float* __restrict__ part) {
     __shared__ float sd[16 * ADA_RT * ADA_PITCH];
@@ -1972,17 +1967,20 @@ int launch_ln_mod_bwd(const float* dxn, const float* x, const float* scale, int 
 // fused form of launch_ln_mod_bwd + launch_frame_reduce_ln (D = 256, 512, 1024 or 2048; part: ln_bwd_fused_workspace(frames, P, D) floats)
 bool ln_bwd_fused_ok(int D) { return D == 1024 || D == 2048 || D == 512 || D == 256; }
 size_t ln_bwd_fused_workspace(int frames, int P, int D) { return (size_t)frames * (size_t)cdiv(P, 16) * 2 * (size_t)D; }
+static int ln_bwd_fused_check_plan(int frames, int P, int D, bool part, LnBwdFusedPlan* plan) {
+    GTAV_REQUIRE(ln_bwd_fused_ok(D) && part && frames > 0 && P > 0, "ln_mod_bwd_fused: D=%d", D);
+    return ln_bwd_fused_plan(LnBwdFusedProblem{frames, P, D}, plan);
+}
 int launch_ln_mod_bwd_fused(const float* dxn, const float* x, const float* scale, int mod_stride, int frames, int P, int D, float* dres, int accumulate,
                             float* dshift, float* dscale, float* part, hipStream_t stream) {
-    GTAV_REQUIRE(ln_bwd_fused_ok(D) && part && frames > 0 && P > 0, "ln_mod_bwd_fused: D=%d", D);
-    const dim3 grid(cdiv(P, 16), frames);
-    if (D == 256) hipLaunchKernelGGL(ln_mod_bwd_fused_kernel<1>, grid, dim3(256), 0, stream, dxn, x, scale, mod_stride, P, dres, accumulate, part);
-    else if (D == 512) hipLaunchKernelGGL(ln_mod_bwd_fused_kernel<2>, grid, dim3(256), 0, stream, dxn, x, scale, mod_stride, P, dres, accumulate, part);
-    else if (D == 1024) hipLaunchKernelGGL(ln_mod_bwd_fused_kernel<4>, grid, dim3(256), 0, stream, dxn, x, scale, mod_stride, P, dres, accumulate, part);
-    else hipLaunchKernelGGL(ln_mod_bwd_fused_kernel<8>, grid, dim3(256), 0, stream, dxn, x, scale, mod_stride, P, dres, accumulate, part);
-    hipLaunchKernelGGL(frame_partials_reduce_kernel, dim3(cdiv(D, 256), frames), dim3(256), 0, stream, part, cdiv(P, 16), D, dshift, dscale, mod_stride);
-    GTAV_CHECK_HIP(hipGetLastError());
-    return 0;
+    LnBwdFusedPlan plan;
+    if (int rc_ = ln_bwd_fused_check_plan(frames, P, D, part != nullptr, &plan)) return rc_;
+    return dispatch_kernel<kernel_count(LN_BWD_FUSED_KERNELS)>(plan.kernel, [&](auto I) {
+        hipLaunchKernelGGL(ln_mod_bwd_fused_kernel<LN_BWD_FUSED_KERNELS[decltype(I)::value].a>, dim3(plan.gx, plan.gy), dim3(plan.block), 0, stream, dxn, x, scale, mod_stride, P, dres, accumulate, part);
+        hipLaunchKernelGGL(frame_partials_reduce_kernel, dim3(plan.reduce_gx, plan.reduce_gy), dim3(256), 0, stream, part, cdiv(P, 16), D, dshift, dscale, mod_stride);
+        GTAV_CHECK_HIP(hipGetLastError());
+        return 0;
+    });
 }
 int launch_frame_reduce_ln(const float* dxn, const float* x, const float* stats, int frames, int P, int D, float* dshift, float* dscale, int mod_stride,
                            hipStream_t stream) {
@@ -2076,67 +2074,59 @@ int launch_mse_bwd_patch(const float* vpred, const float* vtarget, int B, int T,
     GTAV_CHECK_HIP(hipGetLastError());
     return 0;
 }
-static int g_attn_bwd_dbg = GTAV_ENV_INT("GTAV_ATTN_BWD_DBG", 0);     // experiments build: timing variants of the MFMA kernel (wrong results)
-int launch_attn_spatial_bwd(const f16* Q, const f16* K, const f16* Vt, const f16* dO, int NB, int heads, int S, int D, const float* rope_cs, f16* dqkv,
-                            int* err_flag, hipStream_t stream) {
+static int attn_spatial_bwd_check_plan(int NB, int heads, int S, int D, LaunchGeom* plan) {
     GTAV_REQUIRE(S > 0 && S % 8 == 0 && D == heads * 64, "attn_spatial_bwd: S=%d must be a positive multiple of 8 (tokens per frame) and D=%d must be 64 x heads", S, D);
-    if (S > AB_MAXS || S % 16 != 0) {   // the streaming kernel; S <= 160 with S % 16 == 0 stays on the resident kernel below, bit for bit
-        const size_t lds = attn_bwd_stream_lds(S);
-        GTAV_REQUIRE(lds <= 160 * 1024, "attn_spatial_bwd: S=%d needs %zu bytes of LDS for its row statistics (S <= 15360)", S, lds);
-        hipLaunchKernelGGL(attn_spatial_bwd_stream_kernel, dim3(NB * heads), dim3(64 * ABS_NW), lds, stream, Q, K, Vt, dO, heads, S, D, rope_cs, dqkv, err_flag);
-        GTAV_CHECK_HIP(hipGetLastError());
+    if (int rc_ = attn_spatial_bwd_plan(AttnSpatialBwdProblem{NB, heads, S}, plan)) return rc_;
+    if (ATTN_SPATIAL_BWD_KERNELS[plan->kernel].family == LF_ATTN_S_BWD_STREAM) {
+        GTAV_REQUIRE(plan->lds <= LAUNCH_LDS_MAX, "attn_spatial_bwd: S=%d needs %zu bytes of LDS for its row statistics (S <= 15360)", S, plan->lds);
         return 0;
     }
-    const size_t lds_mfma = (size_t)4 * S * ABM_LP * 2 + (size_t)S * ABM_DQP * 4 + (size_t)2 * S * 4 + (size_t)ABM_NW * 256 * 2;
-    size_t lds_max = lds_mfma;
+    size_t lds_max = plan->lds;
 #ifdef GTAV_EXPERIMENTS
     if (attn_bwd_valu_lds(S) > lds_max) lds_max = attn_bwd_valu_lds(S);   // the VALU kernel (train_experiments.inc)
 #endif
-    static unsigned long long attr_devs = 0;
-    int dev = 0;
-    GTAV_CHECK_HIP(hipGetDevice(&dev));
-    if (!(attr_devs >> (dev & 63) & 1)) {
-        GTAV_CHECK_HIP(hipFuncSetAttribute((const void*)attn_spatial_bwd_mfma_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#ifdef GTAV_EXPERIMENTS
-        if (int rc_ = attn_bwd_valu_allow_lds()) return rc_;
-        GTAV_CHECK_HIP(hipFuncSetAttribute((const void*)attn_spatial_bwd_mfma_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        GTAV_CHECK_HIP(hipFuncSetAttribute((const void*)attn_spatial_bwd_mfma_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        GTAV_CHECK_HIP(hipFuncSetAttribute((const void*)attn_spatial_bwd_mfma_kernel<7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#endif
-        attr_devs |= 1ull << (dev & 63);
-    }
-    GTAV_REQUIRE(lds_max <= 160 * 1024, "attn_spatial_bwd: S=%d needs %zu bytes of LDS", S, lds_max);
-#ifdef GTAV_EXPERIMENTS
-    if (g_attn_bwd_valu)
-        launch_attn_bwd_valu(Q, K, Vt, dO, NB, heads, S, D, rope_cs, dqkv, err_flag, stream);
-    else if (g_attn_bwd_dbg == 1)
-        hipLaunchKernelGGL(attn_spatial_bwd_mfma_kernel<1>, dim3(NB * heads), dim3(64 * ABM_NW), lds_mfma, stream, Q, K, Vt, dO, heads, S, D, rope_cs, dqkv, err_flag);
-    else if (g_attn_bwd_dbg == 3)
-        hipLaunchKernelGGL(attn_spatial_bwd_mfma_kernel<3>, dim3(NB * heads), dim3(64 * ABM_NW), lds_mfma, stream, Q, K, Vt, dO, heads, S, D, rope_cs, dqkv, err_flag);
-    else if (g_attn_bwd_dbg == 7)
-        hipLaunchKernelGGL(attn_spatial_bwd_mfma_kernel<7>, dim3(NB * heads), dim3(64 * ABM_NW), lds_mfma, stream, Q, K, Vt, dO, heads, S, D, rope_cs, dqkv, err_flag);
-    else
-#endif
-        hipLaunchKernelGGL(attn_spatial_bwd_mfma_kernel<0>, dim3(NB * heads), dim3(64 * ABM_NW), lds_mfma, stream, Q, K, Vt, dO, heads, S, D, rope_cs, dqkv, err_flag);
-    GTAV_CHECK_HIP(hipGetLastError());
+    GTAV_REQUIRE(lds_max <= LAUNCH_LDS_MAX, "attn_spatial_bwd: S=%d needs %zu bytes of LDS", S, lds_max);
     return 0;
+}
+int launch_attn_spatial_bwd(const f16* Q, const f16* K, const f16* Vt, const f16* dO, int NB, int heads, int S, int D, const float* rope_cs, f16* dqkv,
+                            int* err_flag, hipStream_t stream) {
+    LaunchGeom plan;
+    if (int rc_ = attn_spatial_bwd_check_plan(NB, heads, S, D, &plan)) return rc_;
+    const dim3 grid(plan.gx), block(plan.block);
+#ifdef GTAV_EXPERIMENTS
+    if (g_attn_bwd_valu && ATTN_SPATIAL_BWD_KERNELS[plan.kernel].family == LF_ATTN_S_BWD_MFMA) return launch_attn_bwd_valu(Q, K, Vt, dO, NB, heads, S, D, rope_cs, dqkv, err_flag, stream);
+#endif
+    return dispatch_kernel<kernel_count(ATTN_SPATIAL_BWD_KERNELS)>(plan.kernel, [&](auto I) {
+        constexpr KernelInst R = ATTN_SPATIAL_BWD_KERNELS[decltype(I)::value];
+        if constexpr (!R.product && !GTAV_LAB_BUILD) {
+            GTAV_REQUIRE(false, "attn_spatial_bwd: this kernel exists only in the experiments build (csrc/build.sh exp)");
+        } else if constexpr (R.family == LF_ATTN_S_BWD_STREAM) {   // (launched without an LDS opt-in, as it always was)
+            hipLaunchKernelGGL(attn_spatial_bwd_stream_kernel, grid, block, plan.lds, stream, Q, K, Vt, dO, heads, S, D, rope_cs, dqkv, err_flag);
+        } else {
+            if (int rc_ = lds_opt_in<attn_spatial_bwd_mfma_kernel<R.a>>(LAUNCH_LDS_MAX)) return rc_;
+            hipLaunchKernelGGL(attn_spatial_bwd_mfma_kernel<R.a>, grid, block, plan.lds, stream, Q, K, Vt, dO, heads, S, D, rope_cs, dqkv, err_flag);
+        }
+        GTAV_CHECK_HIP(hipGetLastError());
+        return 0;
+    });
+}
+static int attn_temporal_bwd_check_plan(int B, int P, int D, int T, int Tmax, LaunchGeom* plan) {
+    GTAV_REQUIRE(T >= 1 && T <= 32 && T <= Tmax, "attn_temporal_bwd: a window of T=%d frames (1 .. 32, and at most the cache's Tmax=%d)", T, Tmax);
+    GTAV_REQUIRE(B >= 1 && P >= 1 && D >= 64 && D % 64 == 0 && (size_t)B * P * (D / 64) <= (size_t)1 << 27, "attn_temporal_bwd: B=%d P=%d D=%d", B, P, D);
+    return attn_temporal_bwd_plan(AttnTemporalBwdProblem{B, P, D, T}, plan);
 }
 int launch_attn_temporal_bwd(const f16* q, const f16* kv, const f16* dO, int B, int P, int D, int T, int Tmax, const float* rope_cs, f16* dqkv, int* err_flag,
                              hipStream_t stream) {
-    GTAV_REQUIRE(T >= 1 && T <= 32 && T <= Tmax, "attn_temporal_bwd: a window of T=%d frames (1 .. 32, and at most the cache's Tmax=%d)", T, Tmax);
-    GTAV_REQUIRE(B >= 1 && P >= 1 && D >= 64 && D % 64 == 0 && (size_t)B * P * (D / 64) <= (size_t)1 << 27, "attn_temporal_bwd: B=%d P=%d D=%d", B, P, D);
-    const size_t threads = (size_t)B * P * (D / 64) * 16;
-    const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
-    if (T > 8) {   // the streaming kernel; T <= 8 stays on the register-resident kernel below, bit for bit
-        hipLaunchKernelGGL(attn_temporal_bwd_stream_kernel, grid, block, 0, stream, q, kv, dO, B, P, D, T, Tmax, rope_cs, dqkv, err_flag);
+    LaunchGeom plan;
+    if (int rc_ = attn_temporal_bwd_check_plan(B, P, D, T, Tmax, &plan)) return rc_;
+    const dim3 grid(plan.gx), block(plan.block);
+    return dispatch_kernel<kernel_count(ATTN_TEMPORAL_BWD_KERNELS)>(plan.kernel, [&](auto I) {
+        constexpr KernelInst R = ATTN_TEMPORAL_BWD_KERNELS[decltype(I)::value];
+        if constexpr (R.family == LF_ATTN_T_BWD_STREAM) hipLaunchKernelGGL(attn_temporal_bwd_stream_kernel, grid, block, 0, stream, q, kv, dO, B, P, D, T, Tmax, rope_cs, dqkv, err_flag);
+        else hipLaunchKernelGGL(attn_temporal_bwd_kernel<R.a>, grid, block, 0, stream, q, kv, dO, B, P, D, Tmax, rope_cs, dqkv, err_flag);
         GTAV_CHECK_HIP(hipGetLastError());
         return 0;
-    }
-#define GTAV_TB(TT) case TT: hipLaunchKernelGGL(attn_temporal_bwd_kernel<TT>, grid, block, 0, stream, q, kv, dO, B, P, D, Tmax, rope_cs, dqkv, err_flag); break
-    switch (T) { GTAV_TB(1); GTAV_TB(2); GTAV_TB(3); GTAV_TB(4); GTAV_TB(5); GTAV_TB(6); GTAV_TB(7); GTAV_TB(8); }
-#undef GTAV_TB
-    GTAV_CHECK_HIP(hipGetLastError());
-    return 0;
+    });
 }
 int launch_silu(const float* x, int ldx, float* y, int ldy, int R, int C, hipStream_t stream) {
     hipLaunchKernelGGL(silu_kernel, dim3(grid_for((size_t)R * C)), dim3(256), 0, stream, x, ldx, y, ldy, R, C);
@@ -2149,42 +2139,68 @@ int launch_silu_bwd(const float* dy, int lddy, const float* x, int ldx, float* d
     return 0;
 }
 int launch_gemm_tn_f32(const float* dY, int lddy, const float* X, int ldx, int R, int N, int K, float* dW, int lddw, hipStream_t stream) {
-    if (N % 64 == 0 && K % 64 == 0)
-        hipLaunchKernelGGL(gemm_tn_f32_mfma_kernel, dim3(K / 64, cdiv(N, 256)), dim3(256), 0, stream, dY, lddy, X, ldx, R, N, K, dW, lddw);
-    else
-        hipLaunchKernelGGL(gemm_tn_f32_kernel, dim3(cdiv(K, 256), cdiv(N, 8)), dim3(256), 0, stream, dY, lddy, X, ldx, R, N, K, dW, lddw);
-    GTAV_CHECK_HIP(hipGetLastError());
-    return 0;
+    LaunchGeom plan;
+    if (int rc_ = gemm_tn_f32_plan(GemmF32Problem{R, N, K}, &plan)) return rc_;
+    const dim3 grid(plan.gx, plan.gy), block(plan.block);
+    return dispatch_kernel<kernel_count(GEMM_TN_F32_KERNELS)>(plan.kernel, [&](auto I) {
+        if constexpr (GEMM_TN_F32_KERNELS[decltype(I)::value].family == LF_GEMM_TN_MFMA) hipLaunchKernelGGL(gemm_tn_f32_mfma_kernel, grid, block, 0, stream, dY, lddy, X, ldx, R, N, K, dW, lddw);
+        else hipLaunchKernelGGL(gemm_tn_f32_kernel, grid, block, 0, stream, dY, lddy, X, ldx, R, N, K, dW, lddw);
+        GTAV_CHECK_HIP(hipGetLastError());
+        return 0;
+    });
+}
+static int gemm_nn_f32_check_plan(int lddy, int R, int N, int K, LaunchGeom* plan) {
+    GTAV_REQUIRE(N % 16 == 0 && lddy % 4 == 0 && (size_t)4 * N * sizeof(float) <= 64 * 1024, "gemm_nn_f32: N=%d (a multiple of 16; 4 rows of dY must fit 64 KiB of LDS)", N);
+    return gemm_nn_f32_plan(GemmF32Problem{R, N, K}, plan);
 }
 int launch_gemm_nn_f32(const float* dY, int lddy, const float* W, int ldw, int R, int N, int K, float* dX, int lddx, hipStream_t stream) {
-    GTAV_REQUIRE(N % 16 == 0 && lddy % 4 == 0 && (size_t)4 * N * sizeof(float) <= 64 * 1024, "gemm_nn_f32: N=%d (a multiple of 16; 4 rows of dY must fit 64 KiB of LDS)", N);
-    if ((size_t)16 * N * sizeof(float) <= 64 * 1024)   // rows of dY per block: as many of 16 / 8 / 4 as fit 64 KiB of LDS
-        hipLaunchKernelGGL(gemm_nn_f32_kernel<16>, dim3(cdiv(K, 64), cdiv(R, 16)), dim3(64), (size_t)16 * N * sizeof(float), stream, dY, lddy, W, ldw, R, N, K, dX, lddx);
-    else if ((size_t)8 * N * sizeof(float) <= 64 * 1024)
-        hipLaunchKernelGGL(gemm_nn_f32_kernel<8>, dim3(cdiv(K, 64), cdiv(R, 8)), dim3(64), (size_t)8 * N * sizeof(float), stream, dY, lddy, W, ldw, R, N, K, dX, lddx);
-    else
-        hipLaunchKernelGGL(gemm_nn_f32_kernel<4>, dim3(cdiv(K, 64), cdiv(R, 4)), dim3(64), (size_t)4 * N * sizeof(float), stream, dY, lddy, W, ldw, R, N, K, dX, lddx);
-    GTAV_CHECK_HIP(hipGetLastError());
-    return 0;
+    LaunchGeom plan;
+    if (int rc_ = gemm_nn_f32_check_plan(lddy, R, N, K, &plan)) return rc_;
+    return dispatch_kernel<kernel_count(GEMM_NN_F32_KERNELS)>(plan.kernel, [&](auto I) {
+        hipLaunchKernelGGL(gemm_nn_f32_kernel<GEMM_NN_F32_KERNELS[decltype(I)::value].a>, dim3(plan.gx, plan.gy), dim3(plan.block), plan.lds, stream, dY, lddy, W, ldw, R, N, K, dX, lddx);
+        GTAV_CHECK_HIP(hipGetLastError());
+        return 0;
+    });
 }
 size_t ada_bwd_dx_workspace(int MODW, int D, int R) { return (size_t)cdiv(MODW, ADA_KC) * R * D; }
 int launch_ada_bwd_dx(const float* dmod, int MODW, const float* W, int D, int R, float* dSc, float* part, hipStream_t stream) {
-    if (part && D % 64 == 0 && D <= 1024 && R <= 16 * ADA_RT) {
-        const int nchunk = cdiv(MODW, ADA_KC);
-        hipLaunchKernelGGL(ada_bwd_dx_mfma_kernel, dim3(nchunk), dim3(D), 0, stream, dmod, MODW, W, D, R, part);
+    GTAV_REQUIRE(part, "ada_bwd_dx: needs its partial-sum workspace (ada_bwd_dx_workspace)");
+    AdaBwdPlan plan;
+    if (int rc_ = ada_bwd_dx_plan(AdaBwdProblem{MODW, D, R}, &plan)) return rc_;
+    const dim3 grid(plan.gx, plan.gy), block(plan.block);
+    return dispatch_kernel<kernel_count(ADA_BWD_DX_KERNELS)>(plan.kernel, [&](auto I) {
+        if constexpr (ADA_BWD_DX_KERNELS[decltype(I)::value].family == LF_ADA_MFMA) hipLaunchKernelGGL(ada_bwd_dx_mfma_kernel, grid, block, 0, stream, dmod, MODW, W, D, R, part);
+        else hipLaunchKernelGGL(ada_bwd_dx_kernel, grid, block, 0, stream, dmod, MODW, W, D, R, ADA_VALU_KC, part);
         GTAV_CHECK_HIP(hipGetLastError());
-        const size_t n = (size_t)R * D;
-        hipLaunchKernelGGL(ada_reduce_kernel, dim3((unsigned)cdiv((long long)n, 256)), dim3(256), 0, stream, part, nchunk, n, dSc);
+        hipLaunchKernelGGL(ada_reduce_kernel, dim3(plan.reduce_gx), dim3(256), 0, stream, part, plan.nchunk, (size_t)R * D, dSc);
+        GTAV_CHECK_HIP(hipGetLastError());
+        return 0;
+    });
+}
+// gtav_op_launch_plan, kinds 3 .. 9 (include/gtav_amd.h lists their integers)
+int train_launch_plan(int kind, const int* a, int* out12) {
+    LaunchGeom plan;
+    if (kind == 3) {
+        if (int rc_ = attn_spatial_bwd_check_plan(a[0], a[1], a[2], 64 * a[1], &plan)) return rc_;
+        launch_plan_report(ATTN_SPATIAL_BWD_KERNELS[plan.kernel], plan, 0, 0, 0, out12);
+    } else if (kind == 4) {
+        if (int rc_ = attn_temporal_bwd_check_plan(a[0], a[1], a[2], a[3], 32, &plan)) return rc_;
+        launch_plan_report(ATTN_TEMPORAL_BWD_KERNELS[plan.kernel], plan, 0, 0, 0, out12);
+    } else if (kind == 6) {
+        if (int rc_ = gemm_tn_f32_plan(GemmF32Problem{a[0], a[1], a[2]}, &plan)) return rc_;
+        launch_plan_report(GEMM_TN_F32_KERNELS[plan.kernel], plan, 0, 0, 0, out12);
+    } else if (kind == 7) {
+        if (int rc_ = gemm_nn_f32_check_plan(a[1], a[0], a[1], a[2], &plan)) return rc_;
+        launch_plan_report(GEMM_NN_F32_KERNELS[plan.kernel], plan, 0, 0, 0, out12);
+    } else if (kind == 8) {
+        AdaBwdPlan ap;
+        if (int rc_ = ada_bwd_dx_plan(AdaBwdProblem{a[0], a[1], a[2]}, &ap)) return rc_;
+        launch_plan_report(ADA_BWD_DX_KERNELS[ap.kernel], ap, ap.nchunk, ap.reduce_gx, 0, out12);
     } else {
-        // shapes the matrix-core kernel does not take (hidden % 64 != 0, more than 80 conditioning rows): the VALU kernel, same fixed-order reduction
-        GTAV_REQUIRE(part, "ada_bwd_dx: needs its partial-sum workspace (ada_bwd_dx_workspace)");
-        const int KC = 2048, nchunk = cdiv(MODW, KC);    // (<= cdiv(MODW, ADA_KC) chunks: the workspace covers it)
-        hipLaunchKernelGGL(ada_bwd_dx_kernel, dim3(cdiv(D, 256), nchunk), dim3(256), 0, stream, dmod, MODW, W, D, R, KC, part);
-        GTAV_CHECK_HIP(hipGetLastError());
-        const size_t n = (size_t)R * D;
-        hipLaunchKernelGGL(ada_reduce_kernel, dim3((unsigned)cdiv((long long)n, 256)), dim3(256), 0, stream, part, nchunk, n, dSc);
+        LnBwdFusedPlan lp;
+        if (int rc_ = ln_bwd_fused_check_plan(a[0], a[1], a[2], true, &lp)) return rc_;
+        launch_plan_report(LN_BWD_FUSED_KERNELS[lp.kernel], lp, lp.reduce_gx, lp.reduce_gy, 0, out12);
     }
-    GTAV_CHECK_HIP(hipGetLastError());
     return 0;
 }
 int sumsq_parts(size_t n) { return grid_for(n, 256 * 8); }

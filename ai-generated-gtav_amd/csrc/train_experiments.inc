@@ -167,15 +167,14 @@ __global__ __launch_bounds__(NT) void attn_spatial_bwd_kernel(const f16* __restr
     sat_report(amax, err_flag);
 }
 
-// What launch_attn_spatial_bwd needs of it: the knob, the kernel's dynamic LDS, its per-device opt-in to more than 64 KiB, and the launch
+// What launch_attn_spatial_bwd needs of it: the knob, the kernel's dynamic LDS, and the launch (with its per-device opt-in to more than 64 KiB)
 static int g_attn_bwd_valu = GTAV_ENV_INT("GTAV_ATTN_BWD_VALU", 0);   // 1 = this kernel instead of attn_spatial_bwd_mfma_kernel (A/B runs)
 constexpr int AB_VALU_NT = 512;
 static size_t attn_bwd_valu_lds(int S) { return (size_t)4 * S * 72 * 2 + (size_t)2 * (AB_VALU_NT / 16) * (S + 4) * 4; }
-static int attn_bwd_valu_allow_lds() {
-    GTAV_CHECK_HIP(hipFuncSetAttribute((const void*)attn_spatial_bwd_kernel<AB_VALU_NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    return 0;
-}
-static void launch_attn_bwd_valu(const f16* Q, const f16* K, const f16* Vt, const f16* dO, int NB, int heads, int S, int D, const float* rope_cs, f16* dqkv,
-                                 int* err_flag, hipStream_t stream) {
+static int launch_attn_bwd_valu(const f16* Q, const f16* K, const f16* Vt, const f16* dO, int NB, int heads, int S, int D, const float* rope_cs, f16* dqkv,
+                                int* err_flag, hipStream_t stream) {
+    if (int rc_ = lds_opt_in<attn_spatial_bwd_kernel<AB_VALU_NT>>(LAUNCH_LDS_MAX)) return rc_;
     hipLaunchKernelGGL(attn_spatial_bwd_kernel<AB_VALU_NT>, dim3(NB * heads), dim3(AB_VALU_NT), attn_bwd_valu_lds(S), stream, Q, K, Vt, dO, heads, S, D, rope_cs, dqkv, err_flag);
+    GTAV_CHECK_HIP(hipGetLastError());
+    return 0;
 }

@@ -570,6 +570,23 @@ int gtav_op_gemm_choose_splitk(int32_t M, int32_t N, int32_t K);
  * Honours the calling thread's forced shape / stages (gtav_amd_testing.h); non-zero with gtav_last_error set for a shape id that does not exist, or exists
  * in the experiments build only. */
 int gtav_op_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t qkv_mode, int32_t S, int32_t splitk, int32_t rows_per_gate, int32_t* plan8);
+/* What a launch of one of the other kernel families would run, without touching a device: the launcher's own validation, then the planner it asks
+ * (csrc/launch_plan.h).  kind and its integers a0 .. (the rest are ignored):
+ *   0  LayerNorm (gtav_op_ln_modulate / gtav_op_ln_affine)   mode (0 modulate, 1 affine), M, D, pending slabs, output row permutation, k_save, k_load (flags 0 / 1)
+ *   1  spatial attention                                     NB, heads, S, q_prescaled
+ *   2  temporal attention                                    B, P, D, Tq, t0, Tmax
+ *   3  spatial attention backward                            NB, heads, S
+ *   4  temporal attention backward                           B, P, D, T
+ *   5  skinny fp32 GEMM (gtav_op_skinny_f32)                 M, N, K, act_silu
+ *   6  fp32 dW += dY^T X (gtav_op_train_gemm_tn_f32)         R, N, K
+ *   7  fp32 dX = dY W (gtav_op_train_gemm_nn_f32)            R, N, K
+ *   8  adaLN backward dSc = dmod W_ada                       MODW, D, R
+ *   9  fused LayerNorm-modulate backward                     frames, P, D
+ * plan12 = {kernel family (csrc/launch_plan.h LaunchFamily), its template arguments a, b, c, d (unused: 0), grid x, grid y, block threads, dynamic LDS bytes,
+ * x0, x1, x2}, with x0 .. of kind 1: query splits of the one-pass kernel, query blocks per (frame, head) of the flash kernel; kind 2: one block per query
+ * frame (0 / 1); kind 8: chunks of MODW, grid of the reduction launch behind it; kind 9: grid x, y of the reduction launch behind it; else 0.
+ * Non-zero with gtav_last_error set where the launch itself would refuse the problem. */
+int gtav_op_launch_plan(int32_t kind, int32_t a0, int32_t a1, int32_t a2, int32_t a3, int32_t a4, int32_t a5, int32_t a6, int32_t* plan12);
 /* 1 when the model runs a residual GEMM of this shape (out-proj, fc2) with the in-place gated residual epilogue (epilogue 4) instead of split-K slabs
  * reduced by the following LayerNorm: large M on the persistent loader-wave kernel (csrc/gemm_plan.h gemm_resid_inplace_ok). */
 int gtav_op_gemm_resid_inplace(int32_t M, int32_t N, int32_t K);
