@@ -1,4 +1,17 @@
-"""ctypes binding of libgtav_amd.so (the C-ABI declared in include/gtav_amd.h).
+"""ctypes binding of libgtav_amd.so, derived from the C headers that declare its ABI.
+
+include/gtav_amd.h and include/gtav_amd_testing.h (and csrc/experiments.h for the experiments build) are the ONLY source of the binding: `parse_header`
+reads every function declaration, the two config structs and the integer #defines, and SIGNATURES / _RESTYPES / EXP_SIGNATURES / DitConfig / VaeConfig /
+CONSTANTS are computed from that at import.  The mapping is fixed:
+
+    int32_t c_int32   int64_t c_int64   uint32_t c_uint32   uint64_t c_uint64   float c_float   double c_double
+    const char* c_char_p          any other pointer, of any depth and pointee: c_void_p
+    return: int c_int, void None, const char* c_char_p
+
+Host out-parameters (`int64_t* bytes`, `float* out4_host`, `gtav_dit** out`, ...) are therefore c_void_p like device pointers: a header cannot say which
+scalar pointers are host pointers.  c_void_p takes what the call sites pass (byref(...), a ctypes array, cast(...), None, an integer address); ctypes no
+longer checks the pointee of those few pointers, and in exchange every argument of every entry point is typed by the header itself.  A declaration
+the reader cannot type (another scalar type, a function pointer, `...`, an array, unbalanced parentheses) fails the import by name: it never guesses.
 
 There is NO fallback: if the shared library is missing or a symbol is absent, import of this module
 raises.  `build()` compiles it in-tree with hipcc for gfx950 (a GPU is not needed to build).
@@ -7,11 +20,14 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgtav_amd.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gtav_amd.h")
+TESTING_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gtav_amd_testing.h")      # csrc/api_internal.h includes it
+EXP_HEADER_PATH = os.path.join(_HERE, "csrc", "experiments.h")
 
 
 class GtavError(RuntimeError):
@@ -29,7 +45,7 @@ class GtavRangeSwitch(GtavError):
 def build(force: bool = False) -> str:
     """Compile csrc/*.hip into libgtav_amd.so (hipcc --offload-arch=gfx950). Returns the library path."""
     src_dir = os.path.join(_HERE, "csrc")
-    srcs = [os.path.join(src_dir, f) for f in os.listdir(src_dir)] + [HEADER_PATH]
+    srcs = [os.path.join(src_dir, f) for f in os.listdir(src_dir)] + [HEADER_PATH, TESTING_HEADER_PATH]
     if not force and os.path.exists(LIB_PATH):
         if os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(s) for s in srcs):
             return LIB_PATH
@@ -37,169 +53,114 @@ def build(force: bool = False) -> str:
     return LIB_PATH
 
 
-class DitConfig(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("input_h", "input_w", "patch_size", "in_channels", "hidden_size", "depth", "num_heads")] + [
-        ("mlp_ratio", C.c_float), ("external_cond_dim", C.c_int32), ("max_frames", C.c_int32), ("max_batch", C.c_int32),
-        ("max_cond_rows", C.c_int32)]
+_SCALARS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "float": C.c_float, "double": C.c_double}
+_RETURNS = {"int": C.c_int, "void": None, "const char*": C.c_char_p}
+_IDENT = r"[A-Za-z_]\w*"
 
 
-class VaeConfig(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("latent_dim", "input_height", "input_width", "patch_size", "enc_dim", "enc_depth",
-                                          "enc_heads", "dec_dim", "dec_depth", "dec_heads")] + [
-        ("mlp_ratio", C.c_float), ("use_variational", C.c_int32), ("max_frames_per_call", C.c_int32)]
+def ctype_of(ctype: str, where: str = "?"):
+    """The ctypes type of a parameter or field of C type `ctype` (the mapping of the module docstring); GtavError for a type outside it."""
+    if ctype == "const char*":
+        return C.c_char_p
+    if ctype.endswith("*"):
+        return C.c_void_p
+    if ctype.removeprefix("const ") not in _SCALARS:
+        raise GtavError(f"{where}: no ctypes mapping for the C type `{ctype}`")
+    return _SCALARS[ctype.removeprefix("const ")]
 
 
-_p, _i, _f, _l = C.c_void_p, C.c_int32, C.c_float, C.c_int64
-_u32, _u64 = C.c_uint32, C.c_uint64
+def _declarator(text, where):
+    """`const float* const* ws` -> ("const float* const*", "ws"); the name may be absent (""); anything but words and `*` is refused."""
+    toks = re.findall(r"\w+|\S", text)
+    if not toks or any(t != "*" and not re.fullmatch(_IDENT, t) for t in toks):
+        raise GtavError(f"{where}: cannot type `{' '.join(text.split())}`")
+    named = len(toks) > 1 and toks[-1] != "*" and toks[-1] not in _SCALARS and toks[-1] not in ("const", "void", "char", "int")
+    name = toks.pop() if named else ""
+    ctype = ""
+    for t in toks:
+        ctype += t if t == "*" or not ctype else " " + t
+    return ctype, name
 
-# name -> argtypes (restype is int unless listed in _RESTYPES)
-SIGNATURES = {
-    "gtav_last_error": [],
-    "gtav_abi_version": [],
-    "gtav_dit_create": [C.POINTER(DitConfig), C.POINTER(_p)],
-    "gtav_dit_destroy": [_p],
-    "gtav_dit_set_weight": [_p, C.c_char_p, _p, _l, _p],
-    "gtav_dit_finalize": [_p, _p],
-    "gtav_dit_get_weight": [_p, C.c_char_p, _p, _l, _p],
-    "gtav_dit_forward": [_p, _p, _p, _p, _p, _i, _i, _p],
-    "gtav_dit_set_schedule": [_p, C.POINTER(C.c_float), _i],
-    "gtav_dit_denoise_step": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _i, _i, _p, _p],
-    "gtav_dit_prepare_frame": [_p, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i, _p, _p],
-    "gtav_dit_check": [_p, _p],
-    "gtav_dit_operand_groups": [_p, C.POINTER(C.c_int32)],
-    "gtav_dit_set_operand_dtype": [_p, _i, _i],
-    "gtav_dit_get_operand_dtype": [_p, _i, C.POINTER(C.c_int32)],
-    "gtav_dit_autorange": [_p, C.POINTER(C.c_int32), _p],
-    "gtav_dit_train_param_count": [_p, C.POINTER(C.c_int64)],
-    "gtav_dit_train_allow_window": [_p, _i],
-    "gtav_dit_train_set_recompute": [_p, _i],
-    "gtav_dit_train_saved_bytes": [_p, C.POINTER(C.c_int64)],
-    "gtav_dit_train_allow_mixed": [_p, _i],
-    "gtav_dit_train_set_lora": [_p, _i, _f],
-    "gtav_dit_lora_get_merged": [_p, C.c_char_p, _p, _l, _p],
-    "gtav_dit_train_set_group_dtype": [_p, _i, _i, _p],
-    "gtav_dit_train_range_words": [_p, C.POINTER(C.c_int32), _p],
-    "gtav_dit_train_autorange": [_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _p],
-    "gtav_dit_train_enable": [_p, _p, _l],
-    "gtav_dit_train_enable_typed": [_p, _p, _l, _i],
-    "gtav_dit_set_loss_scale": [_p, _f],
-    "gtav_dit_set_grad_divisor": [_p, _f],
-    "gtav_dit_zero_grad": [_p, _p],
-    "gtav_dit_train_forward": [_p, _p, _p, _p, _p, _i, _i, _p],
-    "gtav_dit_train_forward_keep": [_p, _p, _p, _p, _p, _p, _i, _i, _p],
-    "gtav_dit_train_backward": [_p, _p, _p, _p],
-    "gtav_dit_train_backward_phases": [_p, _p, _p, _i, _i, _p],
-    "gtav_dit_train_param_range": [_p, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
-    "gtav_dit_get_grad": [_p, C.c_char_p, _p, _l, _p],
-    "gtav_dit_train_get_residual": [_p, _i, _p, _l, _p],
-    "gtav_dit_adamw_step": [_p, _f, _f, _f, _f, _f, _f, _p],
-    "gtav_dit_train_stats": [_p, C.POINTER(C.c_float), _p],
-    "gtav_dit_get_opt_state": [_p, C.c_char_p, _p, _p, _l, _p],
-    "gtav_dit_set_opt_state": [_p, C.c_char_p, _p, _p, _l, _p],
-    "gtav_dit_train_set_ema": [_p, _f, _i],
-    "gtav_dit_get_ema": [_p, C.c_char_p, _p, _l, _p],
-    "gtav_dit_set_ema": [_p, C.c_char_p, _p, _l, _p],
-    "gtav_dit_train_swap_ema": [_p, _p],
-    "gtav_dit_get_opt_step": [_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _p],
-    "gtav_dit_set_opt_step": [_p, _l, _l, _p],
-    "gtav_dit_set_graph": [_p, _i],
-    "gtav_dit_set_guidance": [_p, _i, _f],
-    "gtav_dit_set_fused_temporal": [_p, _i],
-    "gtav_dit_set_fused_spatial": [_p, _i],
-    "gtav_dit_fused_launches": [_p, _i, _i, _i],
-    "gtav_dit_set_weight_prefetch": [_p, _i],
-    "gtav_dit_set_weight_fill_policy": [_p, _i],
-    "gtav_dit_profile": [_p, _i],
-    "gtav_dit_profile_read": [_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)],
-    "gtav_timer_calibrate": [_i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), _p],
-    "gtav_comm_unique_id": [_p],
-    "gtav_comm_init": [C.POINTER(_p), _i, _i, _p],
-    "gtav_comm_allreduce_f32": [_p, _p, _l, _i, _p],
-    "gtav_comm_allgather": [_p, _p, _p, _l, _p],
-    "gtav_comm_destroy": [_p],
-    "gtav_vae_create": [C.POINTER(VaeConfig), C.POINTER(_p)],
-    "gtav_vae_destroy": [_p],
-    "gtav_vae_set_weight": [_p, C.c_char_p, _p, _l, _p],
-    "gtav_vae_finalize": [_p, _p],
-    "gtav_vae_get_weight": [_p, C.c_char_p, _p, _l, _p],
-    "gtav_vae_encode": [_p, _p, _f, _f, _p, _i, _p],
-    "gtav_vae_decode": [_p, _p, _f, _p, _f, _f, _i, _p],
-    "gtav_vae_check": [_p, _p],
-    "gtav_vae_set_operand_dtype": [_p, _i],
-    "gtav_vae_get_operand_dtype": [_p, C.POINTER(C.c_int32)],
-    "gtav_vae_profile": [_p, _i],
-    "gtav_vae_profile_read": [_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)],
-    "gtav_clamp_frames": [_p, _i, _i, _i, _i, _f, _f, _p],
-    "gtav_ddim_update": [_p, _p, _p, _i, _i, _p, _p, _i, _p],
-    "gtav_add_noise": [_p, _p, _p, _p, _i, _i, _f, _p],
-    "gtav_vtarget": [_p, _p, _p, _p, _i, _i, _f, _p],
-    "gtav_rng_normal": [_p, _l, _i, _i, _u64, _u32, _u32, _u32, _u32, _f, _p],
-    "gtav_noise_window_rng": [_p, _p, _p, _p, _i, _i, _i, _u64, _u32, _u32, _f, _p],
-    "gtav_vae_posterior_sample": [_p, _p, _i, _i, _i, _u64, _u32, _u32, _u32, _u32, _p],
-    "gtav_op_rng_bits": [_p, _i, _i, _u64, _u32, _u32, _u32, _u32, _p],
-    "gtav_mse": [_p, _l, _p, _l, _i, _i, _p, _p],
-    "gtav_axpy_f32": [_p, _p, _f, _l, _p],
-    "gtav_frames_to_u8": [_p, _p, _i, _i, _i, _p],
-    "gtav_moments_to_latents": [_p, _p, _i, _i, _i, _i, _f, _p],
-    "gtav_latents_to_tokens": [_p, _p, _i, _i, _i, _p],
-    "gtav_strip_to_frames": [_p, _i, _i, _i, _p, _i, _i, _p],
-    "gtav_resize_frames": [_p, _p, _i, _i, _i, _i, _i, _p],
-    "gtav_op_gemm_f16": [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _p, _i, _i, _p],
-    "gtav_op_gemm_qkv": [_p, _i, _p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _i, _p, _p],
-    "gtav_op_rope_interleave": [_p, _p, _p, _i, _p],
-    "gtav_op_skinny_f32": [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _p],
-    "gtav_op_ln_modulate": [_p, _p, _i, _i, _p, _p, _i, _i, _p],
-    "gtav_op_ln_affine": [_p, _p, _i, _i, _p, _p, _p],
-    "gtav_op_attn_spatial": [_p, _p, _p, _p, _i, _i, _i, _p],
-    "gtav_op_attn_temporal": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
-    "gtav_op_attn_temporal_bf16": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
-    "gtav_op_qkv_head_major": [_p, _p, _i, _p],
-    "gtav_op_gemm_tn": [_p, _p, _i, _i, _i, _p, _i, _p],
-    "gtav_op_gemm_dw_grouped": [_i, _p, _p, _p, _p, _p, _p, _i, _p],
-    "gtav_op_attn_spatial_bwd": [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p],
-    "gtav_op_attn_spatial_bwd_bf16": [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p],
-    "gtav_op_attn_temporal_bwd": [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p],
-    "gtav_op_attn_temporal_bwd_bf16": [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p],
-    "gtav_op_gemm_qkvt_attn": [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p],
-    "gtav_op_qkv_head_major_spatial": [_p, _p, _i, _p],
-    "gtav_op_gemm_qkvs_attn": [_p, _p, _i, _i, _i, _p, _p, _p],
-    "gtav_op_convert_f16": [_p, _i, _i, _i, _p, _i, _i, _i, _p],
-    "gtav_op_gemm_splitk_ln": [_p, _i, _p, _p, _i, _i, _i, _i, _p, _p, _p, _i, _i, _p, _p, _p, _i, _p],
-    "gtav_op_gemm_choose_splitk": [_i, _i, _i],
-    "gtav_op_gemm_plan": [_i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "gtav_op_launch_plan": [_i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "gtav_op_gemm_resid_inplace": [_i, _i, _i],
-    "gtav_op_gemm_set_stages": [_i],
-    "gtav_op_gemm_set_wm": [_i],
-    "gtav_op_set_operand_dtype": [_i],
-    "gtav_op_attn_spatial_prescaled": [_p, _p, _p, _p, _i, _i, _i, _p],
-    # test hooks over the backward-only training launchers (include/gtav_amd_testing.h)
-    "gtav_op_train_ln_mod_bwd": [_i, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p, _p, _p, _l, _p],
-    "gtav_op_train_gate_bwd": [_i, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _l, _p, _p],
-    "gtav_op_train_gelu_bwd": [_i, _p, _p, _p, _i, _i, _p, _p, _l, _p, _p],
-    "gtav_op_train_colsum_tiled": [_p, _i, _i, _p, _p, _l, _p],
-    "gtav_op_train_colsum_f32": [_p, _i, _i, _i, _p, _p, _l, _p],
-    "gtav_op_train_colsum_reduce_multi": [C.POINTER(_p), C.POINTER(_p), C.POINTER(_i), C.POINTER(_i), _i, _p],
-    "gtav_op_train_mse_bwd_patch": [_p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _i, _p, _p],
-    "gtav_op_train_to_tiled": [_p, _i, _i, _p, _p, _p],
-    "gtav_op_train_transpose_tiled": [_p, _i, _i, _p, _p],
-    "gtav_op_train_convert_t": [_p, _i, _i, _i, _p, _p],
-    "gtav_op_train_silu": [_p, _i, _p, _i, _i, _i, _p],
-    "gtav_op_train_silu_bwd": [_p, _i, _p, _i, _p, _i, _i, _i, _p],
-    "gtav_op_train_gemm_tn_f32": [_p, _i, _p, _i, _i, _i, _i, _p, _i, _p],
-    "gtav_op_train_gemm_nn_f32": [_p, _i, _p, _i, _i, _i, _i, _p, _i, _p],
-    "gtav_op_train_ada_bwd_dx": [_p, _i, _p, _i, _i, _p, _p, _l, _p],
-    # the deferred-residual LayerNorm with every LnPending field flat, and the branch image launch (include/gtav_amd_testing.h)
-    "gtav_op_ln_pending": [_i, _p, _i, _p, _i, _i, _p, _p, _i, _p, _i, _p, _i, _l, _i, _p, _p, _i, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p],
-    "gtav_op_branch_rows": [_p, _i, _l, _i, _p, _p, _i, _i, _p, _p],
-    # low-rank adapters: the gradient of one Linear and the merge of one Linear (kernel-level entry points of include/gtav_amd.h)
-    "gtav_op_lora_grads": [_p, _p, _p, _p, _i, _i, _i, _i, _f, _p, _p, _p, _l, _p, _p],
-    "gtav_op_lora_merge": [_p, _p, _p, _i, _i, _i, _f, _p, _p, _p, _p],
-}
-_RESTYPES = {"gtav_last_error": C.c_char_p, "gtav_dit_destroy": None, "gtav_vae_destroy": None, "gtav_op_gemm_set_stages": None,
-             "gtav_op_gemm_set_wm": None, "gtav_op_set_operand_dtype": None}
+
+def parse_header(text: str):
+    """The declarations of one plain-C header -> (functions, structs, constants):
+    functions  [(name, return type, [(C type, parameter name), ...]), ...] in header order
+    structs    {NAME: [(C type, field), ...]} of every `typedef struct NAME { ... } NAME;` (forward declarations are skipped)
+    constants  {NAME: int} of every `#define NAME <integer literal>` (a #define without a value, such as an include guard, is skipped)
+    Raises GtavError, naming the declaration, for whatever ctype_of / _declarator cannot type and for anything that is none of the above."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants = {}
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(\S.*?)[ \t]*$", text, flags=re.M):
+        try:
+            constants[name] = int(value, 0)
+        except ValueError:
+            raise GtavError(f"#define {name}: `{value}` is not an integer literal") from None
+    text = re.sub(r'extern\s+"C"\s*\{', " ", re.sub(r"^[ \t]*#.*$", "", text, flags=re.M))
+    structs = {}
+
+    def struct(m):
+        fields = structs.setdefault(m.group(3), [])
+        for decl in filter(str.strip, m.group(2).split(";")):               # `int32_t a, b, c` is three fields
+            first, *more = decl.split(",")
+            ctype, name = _declarator(first, m.group(3))
+            ctype_of(ctype, f"{m.group(3)}.{name}")
+            for field in [name] + [f.strip() for f in more]:
+                if not re.fullmatch(_IDENT, field):
+                    raise GtavError(f"{m.group(3)}: cannot type the field `{' '.join(decl.split())}`")
+                fields.append((ctype, field))
+        return " "
+    text = re.sub(rf"typedef\s+struct\s+({_IDENT})\s*\{{([^{{}}]*)\}}\s*({_IDENT})\s*;", struct, text)
+    functions = []
+    for stmt in text.replace("}", " ").split(";"):                           # (the brace that closes extern "C")
+        stmt = " ".join(stmt.split())
+        if not stmt or re.fullmatch(rf"typedef struct {_IDENT} {_IDENT}|struct {_IDENT}", stmt):
+            continue
+        m = re.fullmatch(rf"([^()]+?)\b({_IDENT}) ?\(([^()]*)\)", stmt)
+        if not m:                                                            # function pointers, unbalanced parentheses, anything that is no prototype
+            named = re.search(rf"({_IDENT}) ?\(", stmt)
+            raise GtavError(f"{named.group(1) if named else stmt[:60]}: cannot parse the declaration `{stmt[:120]}`")
+        name, (ret, _) = m.group(2), _declarator(m.group(1), m.group(2))
+        if ret not in _RETURNS:
+            raise GtavError(f"{name}: no ctypes mapping for the return type `{ret}`")
+        params = [] if m.group(3).strip() in ("", "void") else [_declarator(p, name) for p in m.group(3).split(",")]
+        for ctype, pname in params:
+            ctype_of(ctype, f"{name}({pname})")
+        functions.append((name, ret, params))
+    return functions, structs, constants
+
+
+DECLARATIONS = {}      # name -> (return type, [(C type, parameter name), ...]) of every entry point of the three headers, as the headers spell them
+STRUCTS = {}           # gtav_dit_config, gtav_vae_config -> [(C type, field), ...]
+CONSTANTS = {}         # the integer #defines: GTAV_PROFILE_CLASSES, GTAV_OPERAND_F16 / _BF16, GTAV_GEMM_WM_NT_WEIGHT_FILLS
+
+
+def _signatures(*paths):
+    """Reads the headers into DECLARATIONS / STRUCTS / CONSTANTS and returns their functions' name -> argtypes."""
+    table = {}
+    for path in paths:
+        with open(path) as f:
+            functions, structs, constants = parse_header(f.read())
+        STRUCTS.update(structs)
+        CONSTANTS.update(constants)
+        for name, ret, params in functions:
+            DECLARATIONS[name] = (ret, params)
+            table[name] = [ctype_of(ctype) for ctype, _ in params]
+    return table
+
+
+SIGNATURES = _signatures(HEADER_PATH, TESTING_HEADER_PATH)        # name -> argtypes
+EXP_SIGNATURES = _signatures(EXP_HEADER_PATH)                     # entry points of the experiments build only: the LayerNorm fold, set_debug, set_stamps
+_RESTYPES = {name: _RETURNS[ret] for name, (ret, _) in DECLARATIONS.items()}
+DitConfig = type("DitConfig", (C.Structure,), {"_fields_": [(f, ctype_of(t)) for t, f in STRUCTS["gtav_dit_config"]]})
+VaeConfig = type("VaeConfig", (C.Structure,), {"_fields_": [(f, ctype_of(t)) for t, f in STRUCTS["gtav_vae_config"]]})
 
 _lib = None
+
+
+def _bind(lib, table):
+    for name, argtypes in table.items():
+        fn = getattr(lib, name)  # AttributeError if the symbol is not exported
+        fn.argtypes, fn.restype = argtypes, _RESTYPES[name]
 
 
 def load() -> C.CDLL:
@@ -214,21 +175,12 @@ def load() -> C.CDLL:
     # up with two HIP runtimes — torch's sees the GPU, the one this library was bound to reports "no ROCm-capable device" (seen as build(); smoke() in one process)
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, argtypes in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the symbol is not exported
-        fn.argtypes = argtypes
-        fn.restype = _RESTYPES.get(name, C.c_int)
+    _bind(lib, SIGNATURES)
     _lib = lib
     return lib
 
 
 EXP_LIB_PATH = os.environ.get("GTAV_EXP_LIB") or os.path.join(_HERE, "libgtav_amd_exp.so")    # the override: A/B of two experiment builds (tools/ only)
-# entry points of the experiments build only (csrc/experiments.h): the LayerNorm fold
-EXP_SIGNATURES = {
-    "gtav_dit_set_fold": [_p, _i, _i, _i],
-    "gtav_op_gemm_fold_producer": [_p, _p, _p, _p, _i, _i, _i, _p, _p, _i, _i, _p, _p, _p],
-    "gtav_op_gemm_fold_consumer": [_p, _p, _i, _i, _i, _i, _p, _p, _p, _i, _i, _p, _i, _p],
-}
 
 
 def load_experiments(build_if_missing: bool = True) -> C.CDLL:
@@ -244,18 +196,8 @@ def load_experiments(build_if_missing: bool = True) -> C.CDLL:
         subprocess.run(["bash", os.path.join(_HERE, "csrc", "build.sh"), "exp"], check=True)
     import torch  # noqa: F401   (torch's HIP runtime first: see load())
     lib = C.CDLL(EXP_LIB_PATH)
-    for name, argtypes in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = _RESTYPES.get(name, C.c_int)
-    for name, argtypes in EXP_SIGNATURES.items():     # csrc/experiments.h
-        fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = C.c_int
-    lib.gtav_op_gemm_set_debug.argtypes = [_i]
-    lib.gtav_op_gemm_set_debug.restype = None
-    lib.gtav_op_gemm_set_stamps.argtypes = [_p, _i]
-    lib.gtav_op_gemm_set_stamps.restype = None
+    _bind(lib, SIGNATURES)
+    _bind(lib, EXP_SIGNATURES)     # csrc/experiments.h
     lib._gtav_experiments = True
     _lib = lib
     return lib

@@ -928,6 +928,7 @@ class DiT(_HipModule):
 
     PROFILE_CLASSES = ("ln_modulate", "gemm_qkv", "attn_spatial", "attn_temporal", "gemm_out", "gemm_fc1", "gemm_fc2", "other",
                        "empty_event_pair")
+    assert len(PROFILE_CLASSES) == _lib.CONSTANTS["GTAV_PROFILE_CLASSES"]
 
     def profile(self, enable: bool):
         """In-situ per-kernel-class HIP-event timing (measurement passes only; see include/gtav_amd.h).  Not one of the recorded settings: a handle that is
@@ -935,8 +936,8 @@ class DiT(_HipModule):
         _lib.check(_lib.load().gtav_dit_profile(self._handle, int(bool(enable))))
 
     def profile_read(self):
-        ms = (C.c_double * 9)()
-        n = (C.c_int64 * 9)()
+        ms = (C.c_double * _lib.CONSTANTS["GTAV_PROFILE_CLASSES"])()
+        n = (C.c_int64 * _lib.CONSTANTS["GTAV_PROFILE_CLASSES"])()
         _lib.check(_lib.load().gtav_dit_profile_read(self._handle, ms, n))
         return {k: (ms[i], n[i]) for i, k in enumerate(self.PROFILE_CLASSES)}
 

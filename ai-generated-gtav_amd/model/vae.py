@@ -186,6 +186,7 @@ class AutoencoderKL(_HipModule):
                 _lib.check(_lib.load().gtav_vae_check(self._handle, _lib.current_stream()))
 
     PROFILE_CLASSES = ("ln_affine", "gemm_qkv", "attn_spatial", "attn_temporal", "gemm_proj", "gemm_fc1", "gemm_fc2", "other", "empty_event_pair")
+    assert len(PROFILE_CLASSES) == _lib.CONSTANTS["GTAV_PROFILE_CLASSES"]
 
     def profile(self, enable: bool):
         """In-situ per-kernel-class HIP-event timing of encode / decode (measurement passes only; include/gtav_amd.h gtav_vae_profile).  Not one of the
@@ -195,8 +196,8 @@ class AutoencoderKL(_HipModule):
 
     def profile_read(self):
         import ctypes as C
-        ms = (C.c_double * 9)()
-        n = (C.c_int64 * 9)()
+        ms = (C.c_double * _lib.CONSTANTS["GTAV_PROFILE_CLASSES"])()
+        n = (C.c_int64 * _lib.CONSTANTS["GTAV_PROFILE_CLASSES"])()
         _lib.check(_lib.load().gtav_vae_profile_read(self._handle, ms, n))
         return {k: (ms[i], n[i]) for i, k in enumerate(self.PROFILE_CLASSES)}
 

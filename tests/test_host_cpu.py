@@ -30,11 +30,102 @@ def test_cabi_exports_every_declared_symbol():
     dll = ctypes.CDLL(L.LIB_PATH)
     missing = [n for n in sorted(declared) if not hasattr(dll, n)]
     assert not missing, f"symbols declared in the header but not exported: {missing}"
-    # the ctypes binding covers the whole header
-    assert declared == set(L.SIGNATURES), declared ^ set(L.SIGNATURES)
+    # the library exports exactly what the two headers declare, and the binding's header reader (the source of L.SIGNATURES) finds exactly those names
+    nm = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {ln.split()[-1] for ln in nm.splitlines() if ln.split() and ln.split()[-1].startswith("gtav_")}
+    assert exported == declared, exported ^ declared
+    read = [fn[0] for name in ("gtav_amd.h", "gtav_amd_testing.h") for fn in L.parse_header(open(os.path.join(ROOT, "include", name)).read())[0]]
+    assert len(read) == len(set(read)) and set(read) == declared == set(L.SIGNATURES), set(read) ^ declared
     lib = L.load()
     assert lib.gtav_abi_version() == 4
     assert lib.gtav_last_error() is not None
+
+
+SYNTHETIC_HEADER = """
+/* a block comment that holds a prototype: int gtav_x(int); */
+#ifndef GTAV_SYNTHETIC_H
+#define GTAV_SYNTHETIC_H
+#include <stdint.h>
+#define GTAV_HEX 0x1F   /* 31 */
+#define GTAV_DEC 9
+#ifdef __cplusplus
+extern "C" {
+#endif
+// a line comment that holds another: void gtav_y(float);
+typedef struct gtav_cfg {
+    int32_t a, b;   /* a comment between fields */
+    float c;
+    // and one more
+    uint64_t seed;
+} gtav_cfg;
+typedef struct gtav_dit gtav_dit;
+struct gtav_dit;
+const char* gtav_name(void);
+void gtav_nothing();
+int gtav_three_lines(gtav_dit* h, const char* name,
+                     const float* const* ws /* host array */, void* const*,
+                     gtav_dit** out, int64_t n, uint32_t u, double d);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+
+
+def test_header_reader_on_a_synthetic_header():
+    functions, structs, constants = L.parse_header(SYNTHETIC_HEADER)
+    assert functions == [
+        ("gtav_name", "const char*", []),
+        ("gtav_nothing", "void", []),
+        ("gtav_three_lines", "int", [("gtav_dit*", "h"), ("const char*", "name"), ("const float* const*", "ws"), ("void* const*", ""), ("gtav_dit**", "out"),
+                                     ("int64_t", "n"), ("uint32_t", "u"), ("double", "d")])]
+    assert structs == {"gtav_cfg": [("int32_t", "a"), ("int32_t", "b"), ("float", "c"), ("uint64_t", "seed")]}
+    assert constants == {"GTAV_HEX": 31, "GTAV_DEC": 9}                     # the include guard has no value
+    assert [L.ctype_of(t) for t, _ in functions[2][2]] == [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                           ctypes.c_uint32, ctypes.c_double]
+    assert [L.ctype_of(t) for t, _ in structs["gtav_cfg"]] == [ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_uint64]
+
+
+@pytest.mark.parametrize("name, text", [
+    ("gtav_bad_scalar", "int gtav_ok(int32_t a);\nint gtav_bad_scalar(float* x, size_t n);"),
+    ("gtav_bad_callback", "int gtav_bad_callback(void (*fn)(int32_t), void* stream);"),
+    ("gtav_bad_varargs", "int gtav_bad_varargs(const char* fmt, ...);"),
+    ("gtav_bad_array", "int gtav_bad_array(float x[4]);"),
+    ("gtav_bad_parens", "int gtav_bad_parens(int32_t a;\nint gtav_ok(int32_t a);"),
+    ("gtav_bad_return", "size_t gtav_bad_return(void);"),
+    ("gtav_bad_struct", "typedef struct gtav_bad_struct { int32_t a; long b; } gtav_bad_struct;"),
+    ("gtav_bad_by_value", "int gtav_bad_by_value(gtav_dit_config cfg);"),
+    ("GTAV_BAD_DEFINE", "#define GTAV_BAD_DEFINE 1.5f"),
+])
+def test_header_reader_refuses_what_it_cannot_type(name, text):
+    with pytest.raises(L.GtavError, match=name):
+        L.parse_header(text)
+
+
+def test_header_reader_on_the_real_headers():
+    """138 entry points in the two public headers, 5 in csrc/experiments.h; the tables of the binding are those declarations under the fixed mapping."""
+    read = lambda *p: L.parse_header(open(os.path.join(ROOT, *p)).read())
+    public = read("include", "gtav_amd.h")[0] + read("include", "gtav_amd_testing.h")[0]
+    exp = read("ai-generated-gtav_amd", "csrc", "experiments.h")[0]
+    assert len(public) == 138 and [f[0] for f in public] == list(L.SIGNATURES)
+    assert [f[0] for f in exp] == list(L.EXP_SIGNATURES) == ["gtav_op_gemm_set_debug", "gtav_op_gemm_set_stamps", "gtav_dit_set_fold", "gtav_op_gemm_fold_producer",
+                                                             "gtav_op_gemm_fold_consumer"]
+    restype = {"int": ctypes.c_int, "void": None, "const char*": ctypes.c_char_p}
+    for name, ret, params in public + exp:
+        assert L.DECLARATIONS[name] == (ret, params) and L._RESTYPES[name] is restype[ret], name
+        assert dict(L.SIGNATURES, **L.EXP_SIGNATURES)[name] == [L.ctype_of(t) for t, _ in params], name
+    # spot checks stated in C, one per kind of the mapping
+    assert L.DECLARATIONS["gtav_rng_normal"][1][4:6] == [("uint64_t", "seed"), ("uint32_t", "draw")] and L.SIGNATURES["gtav_rng_normal"][4:6] == [ctypes.c_uint64, ctypes.c_uint32]
+    assert L.DECLARATIONS["gtav_mse"][1][1] == ("int64_t", "a_stride") and L.SIGNATURES["gtav_mse"][1] is ctypes.c_int64
+    assert L.DECLARATIONS["gtav_dit_set_guidance"][1] == [("gtav_dit*", "h"), ("int32_t", "enable"), ("float", "scale")]
+    assert L.SIGNATURES["gtav_dit_set_guidance"] == [ctypes.c_void_p, ctypes.c_int32, ctypes.c_float]
+    assert L.SIGNATURES["gtav_dit_set_weight"] == [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+    assert len(L.SIGNATURES["gtav_op_ln_pending"]) == 28 and L._RESTYPES["gtav_last_error"] is ctypes.c_char_p and L._RESTYPES["gtav_dit_destroy"] is None
+    assert [f for f, _ in L.DitConfig._fields_] == ["input_h", "input_w", "patch_size", "in_channels", "hidden_size", "depth", "num_heads", "mlp_ratio",
+                                                    "external_cond_dim", "max_frames", "max_batch", "max_cond_rows"]
+    assert [t for _, t in L.DitConfig._fields_] == [ctypes.c_int32] * 7 + [ctypes.c_float] + [ctypes.c_int32] * 4 and ctypes.sizeof(L.DitConfig) == 48
+    assert [t for _, t in L.VaeConfig._fields_] == [ctypes.c_int32] * 10 + [ctypes.c_float] + [ctypes.c_int32] * 2 and ctypes.sizeof(L.VaeConfig) == 52
+    assert L.CONSTANTS == {"GTAV_PROFILE_CLASSES": 9, "GTAV_OPERAND_F16": 0, "GTAV_OPERAND_BF16": 1, "GTAV_GEMM_WM_NT_WEIGHT_FILLS": 0x100}
 
 
 def test_product_library_has_no_experiment_knobs():

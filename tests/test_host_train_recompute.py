@@ -44,7 +44,8 @@ def test_new_symbols_are_declared_bound_and_exported():
     assert re.search(r"\bint gtav_dit_train_set_recompute\(gtav_dit\* h, int32_t enable\);", code)
     assert re.search(r"\bint gtav_dit_train_saved_bytes\(gtav_dit\* h, int64_t\* bytes\);", code)
     assert L.SIGNATURES["gtav_dit_train_set_recompute"] == [ctypes.c_void_p, ctypes.c_int32]
-    assert L.SIGNATURES["gtav_dit_train_saved_bytes"] == [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]
+    assert L.SIGNATURES["gtav_dit_train_saved_bytes"] == [ctypes.c_void_p, ctypes.c_void_p]
+    assert L.DECLARATIONS["gtav_dit_train_saved_bytes"] == ("int", [("gtav_dit*", "h"), ("int64_t*", "bytes")])     # the C types the binding was derived from
     dll = ctypes.CDLL(L.LIB_PATH)
     assert hasattr(dll, "gtav_dit_train_set_recompute") and hasattr(dll, "gtav_dit_train_saved_bytes")
     assert L.load().gtav_abi_version() == 4          # new entry points, no changed signature
