@@ -498,8 +498,8 @@ int gtav_dit_prepare_frame(gtav_dit* h, int32_t B, int32_t F, int32_t start, int
                            const int32_t* t_steps_host, int32_t n_steps, const float* actions, void* stream) {
     GTAV_REQUIRE(h && t_steps_host, "prepare_frame: null argument");
     GTAV_REQUIRE(h->finalized, "prepare_frame: finalize the model first");
-    const int T = cur - start + 1;
-    GTAV_REQUIRE(start >= 0 && cur < F && T >= 1 && T <= h->maxT && B >= 1 && B <= h->maxB && n_steps >= 1 && n_steps <= 1024,
+    const int T = cur - start + 1 + (cur < start ? F : 0);   // start > cur: the ring window start .. F-1, 0 .. cur (include/gtav_amd.h)
+    GTAV_REQUIRE(start >= 0 && start < F && cur >= 0 && cur < F && T >= 1 && T <= h->maxT && B >= 1 && B <= h->maxB && n_steps >= 1 && n_steps <= 1024,
                  "prepare_frame: bad window [%d, %d] / steps %d", start, cur, n_steps);
     GTAV_REQUIRE(!actions || h->A > 0, "prepare_frame: model has no external_cond");
     // guided: the table doubles — rows [0, rows_cond) as always, rows [rows_cond, 2 rows_cond) the same (frame, step) rows of the unconditional branch
@@ -569,8 +569,8 @@ int gtav_dit_denoise_step(gtav_dit* h, float* x, int32_t B, int32_t F, int32_t s
                           int32_t cond_step, float* v_out, void* stream) {
     GTAV_REQUIRE(h && x, "denoise_step: null argument");
     GTAV_REQUIRE(h->finalized && !h->ac_host.empty(), "denoise_step: finalize the model and set the schedule first");
-    const int T = cur - start + 1;
-    GTAV_REQUIRE(start >= 0 && cur < F && T >= 1 && T <= h->maxT && B >= 1 && B <= h->maxB, "denoise_step: bad window [%d, %d] of %d frames", start, cur, F);
+    const int T = cur - start + 1 + (cur < start ? F : 0);   // start > cur: the ring window start .. F-1, 0 .. cur (include/gtav_amd.h)
+    GTAV_REQUIRE(start >= 0 && start < F && cur >= 0 && cur < F && T >= 1 && T <= h->maxT && B >= 1 && B <= h->maxB, "denoise_step: bad window [%d, %d] of %d frames", start, cur, F);
     GTAV_REQUIRE(t_cur >= 0 && t_cur < 1000 && t_next >= 0 && t_next < 1000 && t_ctx >= 0 && t_ctx < 1000, "denoise_step: timestep out of range");
     GTAV_REQUIRE(!actions || h->A > 0, "denoise_step: model has no external_cond");
     GTAV_REQUIRE(mode == 0 || mode == 1, "denoise_step: mode %d", mode);

@@ -368,7 +368,8 @@ __global__ void step_setup_kernel(StepParams* dst, StepParams v, int* frame_idx,
     for (int i = threadIdx.x; i < B * Tq; i += blockDim.x) {
         const int bi = i / Tq, tl = i - bi * Tq;
         const int uncond = bi >= Bc, b = uncond ? bi - Bc : bi;   // guided step: internal sample Bc + b reads the frames of sample b
-        frame_idx[i] = b * F + first + tl;
+        const int f = first + tl;
+        frame_idx[i] = b * F + (f < F ? f : f - F);               // ring window (first > cur): frames first .. F-1, 0 .. cur of the same buffer
         if (v.cond_step >= 0) {
             const int tw = use_cur ? T - 1 : tl;   // position inside the window
             const int r = (tw < T - 1 ? b * (T - 1) + tw : Bc * (T - 1) + v.cond_step * Bc + b) + (uncond ? uncond_row0 : 0);
@@ -444,6 +445,7 @@ __global__ void cond_inputs_frame_kernel(int rows, int rows_cond, int B, int T, 
     if (rc < nctx) {
         b = rc / (T - 1);
         frame = start + (rc - b * (T - 1));
+        if (frame >= F) frame -= F;                        // ring window (start > cur): action row f belongs to latent frame f
         t = t_ctx;
     } else {
         const int q = rc - nctx;
@@ -482,7 +484,9 @@ __global__ void cond_inputs_kernel(const int64_t* __restrict__ t64, int rows, in
         t = t < 0 ? 0 : 999;
     }
     for (int j = threadIdx.x; j < 256; j += blockDim.x) E[(size_t)r * 256 + j] = sincos[(size_t)t * 256 + j];
-    const float* arow = actions ? actions + ro * act_outer + (frame0 + ri) * act_inner : nullptr;
+    long long aoff = (frame0 + ri) * act_inner;
+    if (aoff >= act_outer) aoff -= act_outer;             // ring window (sp->first > sp->cur): the sample's act_outer / act_inner action rows are a ring like its frames
+    const float* arow = actions ? actions + ro * act_outer + aoff : nullptr;
     for (int j = threadIdx.x; j < Apad; j += blockDim.x) HC[(size_t)r * ldhc + D + j] = (arow && j < A) ? arow[j] : 0.f;
 }
 

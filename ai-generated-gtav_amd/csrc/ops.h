@@ -32,7 +32,7 @@ struct StepParams {
     int cond_step;  // >= 0: row set of the per-frame conditioning table prepared by gtav_dit_prepare_frame; -1: inline
     float guidance; // classifier-free guidance scale s of a guided step (gtav_dit_set_guidance): on the device, so one captured step replays for any s
 };
-// One launch ahead of the (possibly graph-replayed) step: *dst = v, frame_idx[b*Tq+tl] = b*F + first + tl
+// One launch ahead of the (possibly graph-replayed) step: *dst = v, frame_idx[b*Tq+tl] = b*F + (first + tl) % F
 // (first = use_cur ? v.cur : v.first) and, when v.cond_step >= 0, the conditioning-table row of every processed frame:
 // context frame (b, tl < T-1) -> b*(T-1)+tl, frame `cur` of sample b -> B*(T-1) + cond_step*B + b.
 // Guided step (Bc < B, B = 2 Bc internal samples): sample Bc + b is the unconditional twin of sample b — the same frames of x (no copy), and the same row
@@ -78,7 +78,7 @@ int launch_axpy_f32(float* y, const float* x, float alpha, size_t n, hipStream_t
 //   E[r][0:256] = sincos_table[t_r],  t_r = t64 ? t64[r] : (r % Tq == Tq - 1 ? t_cur : t_ctx)   (train_dit.py:64-91)
 //   HC[r][D : D+Apad] = actions[(r / Tq) * act_outer + (r % Tq) * act_inner + 0:A]  (zeros when actions == nullptr)
 // With `sp` (sampler step): t_ctx / t_cur come from *sp and the action row of (b, tl) is
-// actions[b * act_outer + ((use_cur ? sp->cur : sp->first) + tl) * act_inner].
+// actions[b * act_outer + ((use_cur ? sp->cur : sp->first) + tl) * act_inner], the offset inside the sample taken modulo act_outer (ring window).
 // Outer indices from `n_cond_outer` on (the unconditional half of a guided step) get zero action columns.
 int launch_cond_inputs(const int64_t* t64, int rows, int Tq, const StepParams* sp, int use_cur, const float* sincos /*[1000][256]*/,
                        float* E, const float* actions, int64_t act_outer, int64_t act_inner, int n_cond_outer, int A, float* HC, int ldhc,

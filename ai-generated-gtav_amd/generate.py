@@ -49,6 +49,27 @@ def vae_decode_frames(x: torch.Tensor, vae, scaling_factor: float = SCALING_FACT
     return out.reshape(B, t, vae.input_height, vae.input_width, 3)
 
 
+def noise_schedule(noise_steps: int):
+    """generate.py:194 + train_dit.py:70: (t_of, order) — the timestep of every noise index 0 .. noise_steps (linspace(0, 999), truncated like .long()) and the
+    order the indices are visited in, noise_steps down to 0."""
+    t_of = [int(v) for v in torch.linspace(0, 999, noise_steps + 1)]
+    return t_of, list(reversed(range(0, noise_steps + 1)))
+
+
+def denoise_frame(model, x: torch.Tensor, start: int, cur: int, t_of, order, act, stabilization_level: int, ctx_cache: bool, hoist_cond: bool):
+    """All noise steps of ONE generated frame (generate.py:204-220): frame `cur` of x (B, F, C, h, w) is denoised in place against the window that begins at
+    frame `start` — linear (start <= cur) or a ring (start > cur: frames start .. F-1, 0 .. cur, include/gtav_amd.h); `act` (B, F, A) or None is indexed like x.
+    The one per-frame body of generate_latents and of gtav_amd.play.PlaySession: both begin every frame with prepare_frame_ (hoist_cond) and a full-window step."""
+    B, F = x.shape[:2]
+    noise_steps = len(order) - 1
+    if hoist_cond:
+        model.prepare_frame_(B, F, start, cur, stabilization_level, [t_of[k] for k in order], act)
+    for step, noise_idx in enumerate(order):
+        cached = ctx_cache and noise_idx != noise_steps
+        model.denoise_step_(x, start, cur, stabilization_level, t_of[noise_idx], t_of[max(0, noise_idx - 1)],
+                            noise_idx <= 0, act, cached=cached, cond_step=step if hoist_cond else -1)
+
+
 @torch.inference_mode()
 def generate_latents(model, x_prompt: torch.Tensor, total_frames: int, noise_steps: int, noise_chunks: Optional[torch.Tensor] = None,
                      actions: Optional[torch.Tensor] = None, stabilization_level: int = 15, noise_abs_max: float = 20.0,
@@ -98,19 +119,12 @@ def generate_latents(model, x_prompt: torch.Tensor, total_frames: int, noise_ste
                                                      float(noise_abs_max), _lib.current_stream()))
     act = actions.to(dev, torch.float32).contiguous() if actions is not None else None
     model.set_schedule(_alphas_cumprod(clamp_min))
-    noise_range = torch.linspace(0, 999, noise_steps + 1)                      # generate.py:194 (float)
-    t_of = [int(v) for v in noise_range]                                       # long() truncation (train_dit.py:70)
-    order = list(reversed(range(0, noise_steps + 1)))
+    t_of, order = noise_schedule(noise_steps)
     x_init = x.clone() if getattr(model, "range_policy", "report") == "auto" else None
     for attempt in range(1 + (model.n_operand_groups if x_init is not None else 0)):
         for i in range(n_prompt, total_frames):
             start = max(0, i + 1 - model.max_frames)                              # generate.py:204
-            if hoist_cond:
-                model.prepare_frame_(B, total_frames, start, i, stabilization_level, [t_of[k] for k in order], act)
-            for step, noise_idx in enumerate(order):
-                cached = ctx_cache and noise_idx != noise_steps
-                model.denoise_step_(x, start, i, stabilization_level, t_of[noise_idx], t_of[max(0, noise_idx - 1)],
-                                    noise_idx <= 0, act, cached=cached, cond_step=step if hoist_cond else -1)
+            denoise_frame(model, x, start, i, t_of, order, act, stabilization_level, ctx_cache, hoist_cond)
         try:
             model.check()
             break

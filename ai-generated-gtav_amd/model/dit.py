@@ -904,10 +904,11 @@ class DiT(_HipModule):
 
     def prepare_frame_(self, B: int, F: int, start: int, cur: int, t_ctx: int, t_steps, actions: Optional[torch.Tensor] = None):
         """Builds the conditioning (adaLN) table for every noise step of one generated frame (gtav_dit_prepare_frame);
-        step k of that frame then passes cond_step=k to denoise_step_."""
+        step k of that frame then passes cond_step=k to denoise_step_.  start > cur is the ring window start .. F-1, 0 .. cur (include/gtav_amd.h)."""
         n = len(t_steps)
         Bi = self._internal_batch(B)
-        self._ensure(Bi, cur - start + 1, cond_rows=Bi * (cur - start + n))
+        T = cur - start + 1 + (F if cur < start else 0)
+        self._ensure(Bi, T, cond_rows=Bi * (T - 1 + n))
         arr = (C.c_int32 * n)(*[int(v) for v in t_steps])
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().gtav_dit_prepare_frame(self._handle, B, F, start, cur, int(t_ctx), arr, n, _lib.ptr(actions),
@@ -916,11 +917,12 @@ class DiT(_HipModule):
     def denoise_step_(self, x: torch.Tensor, start: int, cur: int, t_ctx: int, t_cur: int, t_next: int, is_final: bool,
                       actions: Optional[torch.Tensor] = None, cached: bool = False, v_out: Optional[torch.Tensor] = None,
                       cond_step: int = -1):
-        """In-place fused step on latents x (B, F, C, H, W) fp32 contiguous on the model's device."""
+        """In-place fused step on latents x (B, F, C, H, W) fp32 contiguous on the model's device.  start > cur is the ring window start .. F-1, 0 .. cur
+        (include/gtav_amd.h)."""
         assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
         B, F = x.shape[:2]
         if cond_step < 0:
-            self._ensure(self._internal_batch(B), cur - start + 1)
+            self._ensure(self._internal_batch(B), cur - start + 1 + (F if cur < start else 0))
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().gtav_dit_denoise_step(
                 self._handle, x.data_ptr(), B, F, start, cur, int(t_ctx), int(t_cur), int(t_next), int(bool(is_final)),

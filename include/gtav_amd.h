@@ -103,15 +103,26 @@ int gtav_dit_set_schedule(gtav_dit* h, const float* alphas_cumprod_host, int32_t
  *         gtav_dit_forward (which overwrites the caches), fails instead of attending to stale K/V.
  * actions (B, F, external_cond_dim) or NULL.  v_out (B, C, H, W) optional: v_pred of frame `cur`.
  * cond_step: -1 computes the conditioning c = t_emb(t) + action and its adaLN projections inside the step (as
- *   DiT.forward does, model/dit.py:359-366); >= 0 takes them from the table built by gtav_dit_prepare_frame. */
+ *   DiT.forward does, model/dit.py:359-366); >= 0 takes them from the table built by gtav_dit_prepare_frame.
+ * Ring window: besides 0 <= start <= cur < F the call takes 0 <= cur < start < F.  The window is then the
+ *   T = cur - start + 1 + F frames start, start + 1, .., F - 1, 0, .., cur of the same (B, F, n) buffer, in that temporal
+ *   order, frame `cur` is the one being denoised, and actions (B, F, A) is a ring in the same way: action row f belongs to
+ *   latent frame f.  T <= max_frames as ever; F may exceed max_frames.  A caller that keeps absolute frame f in slot f % F
+ *   generates without end in constant memory and never moves a frame.  start <= cur is the linear window, unchanged to the
+ *   bit.  (start, cur) repeats every F frames and the handle cannot see that x changed (as it cannot when a caller edits x
+ *   in place): a caller that overwrites ring slots begins every generated frame with gtav_dit_prepare_frame (if it uses the
+ *   table) and a mode-0 step, as the linear sampler loop does. */
 int gtav_dit_denoise_step(gtav_dit* h, float* x_dev, int32_t B, int32_t F, int32_t start, int32_t cur, int32_t t_ctx,
                           int32_t t_cur, int32_t t_next, int32_t is_final, const float* actions_dev, int32_t mode,
                           int32_t cond_step, float* v_out_dev, void* stream);
 /* The conditioning does not depend on x: for one generated frame (window [start, cur]) the adaLN table of every noise
  * step is computed at once — context rows with t_ctx, n_steps row sets for frame `cur` with t_steps_host[s] — so the
  * 0.8 GB of fp32 conditioning weights are streamed once per frame instead of once per step.  Same arithmetic, same
- * results; needs max_cond_rows >= B * (cur - start + n_steps).  A gtav_dit_forward or a cond_step = -1 step overwrites
- * the table: later cond_step >= 0 calls fail until prepare_frame is called again. */
+ * results; needs max_cond_rows >= B * (T - 1 + n_steps), T the window length.  A gtav_dit_forward or a cond_step = -1 step
+ * overwrites the table: later cond_step >= 0 calls fail until prepare_frame is called again.
+ * Ring window: 0 <= cur < start < F is taken as in gtav_dit_denoise_step (T = cur - start + 1 + F; the context rows read the
+ * action rows start, .., F - 1, 0, .., cur - 1).  The table is recorded under (B, F, start, cur), which a ring repeats every F
+ * frames: after new actions are written into ring slots, call prepare_frame again before the frame's first step. */
 int gtav_dit_prepare_frame(gtav_dit* h, int32_t B, int32_t F, int32_t start, int32_t cur, int32_t t_ctx,
                            const int32_t* t_steps_host, int32_t n_steps, const float* actions_dev, void* stream);
 
