@@ -496,6 +496,19 @@ int gtav_op_train_convert_t(const float* src, int32_t lds, int32_t R, int32_t C,
     GTAV_REQUIRE(src && dst && R >= 1 && C >= 1 && lds >= C, "op_train_convert_T: R=%d C=%d lds=%d", R, C, lds);
     return op_ops().convert_T(src, lds, R, C, (f16*)dst, (hipStream_t)stream);
 }
+// The two attention backward launches as a training handle makes them (api_train.hip): the thread's operand type and the caller's error word, where the product
+// entries gtav_op_attn_*_bwd[_bf16] above pass none.
+int gtav_op_train_attn_spatial_bwd(const void* q, const void* k, const void* vt, const void* d_o, int32_t NB, int32_t heads, int32_t S, const float* rope_cs,
+                                   void* dqkv, int32_t* err, void* stream) {
+    GTAV_REQUIRE(q && k && vt && d_o && rope_cs && dqkv, "op_train_attn_spatial_bwd: null argument");
+    return op_ops().attn_spatial_bwd((const f16*)q, (const f16*)k, (const f16*)vt, (const f16*)d_o, NB, heads, S, heads * 64, rope_cs, (f16*)dqkv, err,
+                                     (hipStream_t)stream);
+}
+int gtav_op_train_attn_temporal_bwd(const void* q, const void* kv, const void* d_o, int32_t B, int32_t P, int32_t D, int32_t T, int32_t Tmax, const float* rope_cs,
+                                    void* dqkv, int32_t* err, void* stream) {
+    GTAV_REQUIRE(q && kv && d_o && rope_cs && dqkv, "op_train_attn_temporal_bwd: null argument");
+    return op_ops().attn_temporal_bwd((const f16*)q, (const f16*)kv, (const f16*)d_o, B, P, D, T, Tmax, rope_cs, (f16*)dqkv, err, (hipStream_t)stream);
+}
 // Low-rank adapters, kernel level (include/gtav_amd.h): the gradient of one Linear as a LoRA training handle launches it, and the merge of one Linear (both images,
 // then the fp32 sum where w_f32 is given).  The launchers validate the shapes and the workspace by name.
 int gtav_op_lora_grads(const void* x, const void* dy, const float* a_f32, const float* b_f32, int32_t M, int32_t N, int32_t K, int32_t r, float s, float* dA,

@@ -53,6 +53,12 @@
  *   mse_bwd_patch, to_tiled, transpose_tiled, convert_t (launch_convert_T_f16)   the loss gradient and the layout converters
  *   silu, silu_bwd, gemm_tn_f32 (dW += dY^T X), gemm_nn_f32 (dX = dY W), ada_bwd_dx (part = ada_bwd_dx_workspace(MODW, D, R))
  * tests/test_gpu_ops_train.py runs them against fp64 math with the bounds of tests/parity_bounds.py.
+ *   attn_spatial_bwd, attn_temporal_bwd   launch_attn_spatial_bwd / launch_attn_temporal_bwd as a training handle makes them: the arguments of
+ *                             gtav_op_attn_spatial_bwd / gtav_op_attn_temporal_bwd (gtav_amd.h), which run "without an error word", plus the caller's `err`, in the
+ *                             thread's operand type.  The resident and the streaming kernel of each are chosen by the launcher (S <= 160 with S % 16 == 0; T <= 8).
+ *                             On fp16 operands a dS, dq, dk or dv beyond 65504 is stored clamped and raises ERR_F16_SAT (2) in `err` — the bit on which a training
+ *                             step skips its optimizer step; bf16 operands never raise it.  tests/test_gpu_ops_attn_bwd_bounds.py holds every output element to the
+ *                             derived bounds of tests/parity_bounds.py on flat AND peaked softmax rows, and the bit.
  *
  * gtav_op_ln_pending          ONE launch_ln_modulate (mode 0: p0 = shift, p1 = scale tables of row length mod_stride, indexed by rows / rows_per_mod) or
  *                             launch_ln_affine (mode 1: p0 = gamma, p1 = beta; rows, rows_per_mod and mod_stride unused) with a deferred residual update
@@ -100,6 +106,10 @@ int gtav_op_train_silu_bwd(const float* dy, int32_t lddy, const float* x, int32_
 int gtav_op_train_gemm_tn_f32(const float* dY, int32_t lddy, const float* X, int32_t ldx, int32_t R, int32_t N, int32_t K, float* dW, int32_t lddw, void* stream);
 int gtav_op_train_gemm_nn_f32(const float* dY, int32_t lddy, const float* W, int32_t ldw, int32_t R, int32_t N, int32_t K, float* dX, int32_t lddx, void* stream);
 int gtav_op_train_ada_bwd_dx(const float* dmod, int32_t MODW, const float* W, int32_t D, int32_t R, float* dSc, float* part, int64_t part_floats, void* stream);
+int gtav_op_train_attn_spatial_bwd(const void* q, const void* k, const void* vt, const void* d_o, int32_t NB, int32_t heads, int32_t S, const float* rope_cs,
+                                   void* dqkv, int32_t* err, void* stream);
+int gtav_op_train_attn_temporal_bwd(const void* q, const void* kv, const void* d_o, int32_t B, int32_t P, int32_t D, int32_t T, int32_t Tmax, const float* rope_cs,
+                                    void* dqkv, int32_t* err, void* stream);
 
 /* ---- the deferred-residual LayerNorm (see above) ---- */
 int gtav_op_ln_pending(int32_t mode, float* x, int32_t ldx, void* out, int32_t M, int32_t D, const float* p0, const float* p1, int32_t mod_stride,

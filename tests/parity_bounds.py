@@ -1,7 +1,7 @@
 """Inputs, fp64 references, error bounds and fp32 emulations of the operand-typed kernels, shared by tests/test_gpu_ops_typed.py (the kernels, on a GPU) and
 tests/test_host_parity_bounds.py (the bounds themselves, on the CPU).  Pure torch: nothing here loads the library.  The second half of the file holds the same
-for the backward-only training kernels (tests/test_gpu_ops_train.py) and the last part for the deferred-residual LayerNorm (tests/test_gpu_ops_ln_pending.py),
-each with its own head comment.
+for the backward-only training kernels (tests/test_gpu_ops_train.py), then the deferred-residual LayerNorm (tests/test_gpu_ops_ln_pending.py) and last the four
+attention backward kernels (tests/test_gpu_ops_attn_bwd_bounds.py), each with its own head comment.
 
 None of the bounds is taken from the code under test.  u is the unit roundoff of the operand type, 2^-11 for fp16 and 2^-8 for bf16.
 
@@ -934,3 +934,298 @@ def ln_pend_sat_case():
     c.slabs[0, 3, 5], c.slabs[1, 3, 5] = 40000.0, 40000.0
     c.slabs[0, 6, 60], c.slabs[1, 6, 60] = -30000.5, -40000.0
     return c
+
+
+# =======================================================================================================================================================
+# The attention backward kernels (csrc/train.hip attn_spatial_bwd_mfma_kernel / attn_spatial_bwd_stream_kernel, attn_temporal_bwd_kernel /
+# attn_temporal_bwd_stream_kernel): inputs, fp64 references, ONE bound per output element and the "perfect kernel of the design" with its wrong variants, shared
+# by tests/test_gpu_ops_attn_bwd_bounds.py (GPU) and tests/test_host_parity_bounds.py (CPU).
+#
+# The operation, per (item, head), n keys (S, or the t + 1 visible frames of query t), all in fp64 on the operands as rounded to the operand type:
+#     s = q k^T / 8,  P = softmax(s),  dP = dO v^T,  Dq_i = sum_j P_ij dP_ij,  dS = P (dP - Dq) / 8,  dv = P^T dO,  dq = dS k,  dk = dS^T q,
+#   then dq / dk rotated back through the launch's OWN fp32 table (RoPE^T: (a, b) -> (a cos + b sin, b cos - a sin) per pair).
+#
+# Inputs.  flat: unit normal.  sharp: q x 6 (the largest probability of a row has a median of about 0.65).  Planted keys (spatial `jump`; temporal `diagonal`,
+#   `first`, `ladder`): see attn_bwd_inputs / temporal_bwd_inputs.  dO x 2^e is exact in both types but for fp16 subnormals, and the reference uses the rounded dO.
+#
+# Why an ABSOLUTE per-element bound: a query dominated by one key has dS ~ 0 and a dq row that is nearly zero, so the rounded fp64 reference itself has a per-row
+#   relative L2 error of up to 1.0 there.  The forward tests' per-row instrument cannot be used on backward outputs.
+#
+# The bound counts roundings, first order; u = unit roundoff of the operand type x (1 + 2^-10), eps = 2^-24, sub = one subnormal step of the type.
+#   score       e_ij = 2 * 66 eps sum_d |q k| / 8   (64 exact products, 66 additions at most, doubled: the matrix pipe's rounding is not documented — acc_term)
+#   exponent    spatial: the argument is formed in base-2 units, s2 - lse2 with s2 = s log2 e: the constant, the product and the subtraction, three roundings of
+#                 at most eps (|s2| + |lse2|) each, and exp2 itself (1 ulp = 2 eps) -> as a relative error of P (x ln 2 < 1, not taken)
+#                 x_ij = 4 eps (|s_ij| + max(|lse_i|, |max_i|)) log2 e      (the statistics pass subtracts the row maximum, not lse: whichever is larger)
+#               temporal: __expf(s - max) is a base-2 evaluation whose argument is scaled in fp32: subtraction, constant, product (eps |s - max| each) + 2 eps of
+#                 exp2 = (3 |s - max| + 2) eps  <=  x_ij = (|s_ij - max_i| + 2) 2^-22
+#   rho_ij      relative error of the fp32 P_ij:  e_ij + x_ij  (numerator)  +  sum_j P_ij (e_ij + x_ij)  (the denominator is a sum of such terms: its relative error
+#               is their P-weighted mean)  +  (n + 4) 2^-23  (n exponentials of 1 ulp, n additions, the logarithm or the reciprocal and the product; a streaming
+#               sweep also rescales its running sum by exp2 of the maximum's rise, at most once per 64-key chunk: three roundings each, inside the n + 4)
+#   P           spatial, rounded to the operand type as an MFMA operand:  |dP_ij| <= (u + rho_ij) P + sub / 2 + 2^-126  (an fp32 exponential may flush below the
+#               smallest normal);  temporal, kept in fp32: rho_ij P + 2^-126
+#   dP          |d dP_ij| <= 2 * 66 eps sum_d |dO v|
+#   Dq          |d Dq_i| <= sum_j P |d dP| + sum_j rho_ij P |dP| + (n + 2) 2^-23 sum_j P |dP|      (n fused multiply-adds, the shuffles' additions, one division)
+#   dS          spatial: (u + rho_ij + 4 eps) |dS| + P (|d dP| + |d Dq|) / 8 + sub / 2   (subtraction, product, the exact / 8, then the 2-byte rounding);
+#               temporal: the same without u and sub / 2
+#   dv_jd       sum_i |dP_ij| |dO_id| + 2 (n + 2) eps sum_i P |dO|       (an fp32 sum of n terms, doubled on the matrix pipe — kept for the temporal kernels' fused
+#   dq_id       sum_j |d dS_ij| |k_jd| + 2 (n + 2) eps sum_j |dS| |k|     multiply-adds as well);  dk likewise with q
+#   rotation    (a, b) -> a cos + b sin: |d a| |cos| + |d b| |sin| + 3 eps (|a cos| + |b sin|)  (two products, one addition; the table is exact: both sides read it)
+#   store       + u |ref| + sub: ONE round to nearest of every output element (store_bound's first and last term)
+# Nothing above is taken from what a kernel returned.  If a kernel exceeds the bound on a term this derivation missed, the term is ADDED here with its derivation
+# (and the control below gets the matching rounding): never a factor.
+#
+# The control (AttnBwdCase.control / TemporalBwdCase.control): fp64 math with exactly the design's 2-byte roundings — spatial P, dS and the outputs, temporal the
+# outputs only — is "what a perfect kernel of this design returns" and must have NO element outside; each WRONG variant must leave the bound somewhere:
+#   "drop_last"   the last (visible) key left out of the row statistics lse and Dq — a wrong tail mask
+#   "rope_sign"   RoPE^T with the sign of the sine reversed (dq, dk)
+#   "stale_max"   the running sum not rescaled when a later 64-key chunk (temporal: a later key) raises the maximum
+#   "dq_chunk"    Dq without the terms of its last 64-key chunk
+#   "mask_plus" / "mask_minus"   temporal: query t sees keys s <= t + 1 / s <= t - 1 (query 0 keeps key 0)
+# Limit: because P and dS are rounded to 2 bytes BY DESIGN, the spatial bound carries u-sized terms of its own, and a truncating output store or a truncated dS
+# (errors of 2 u where u is allowed) stays around the bound (0.4 .. 1.1 of it): the host test prints those ratios and does not require them caught.  The temporal
+# bound has no such term, and a truncating store is caught there.
+# =======================================================================================================================================================
+FLUSH32 = 2.0 ** -126
+ATTN_BWD_RESIDENT = [(2, 2, 32), (1, 2, 144), (1, 1, 160)]                   # (NB, heads, S): two tiles and idle waves; production, one tile per wave; a wave with two tiles
+ATTN_BWD_STREAM = [(1, 1, 8), (2, 2, 72), (1, 2, 200), (1, 1, 576)]           # one half-empty tile; a chunk + half a tile; 4 chunks, 2 groups, ragged; 9 chunks, 5 groups
+ATTN_BWD_SHAPES = ATTN_BWD_RESIDENT + ATTN_BWD_STREAM
+ATTN_BWD_KINDS = ("flat", "sharp", "jump")
+ATTN_BWD_SCALED_SHAPES = [(2, 2, 72), (1, 2, 144)]                            # the shapes that also run dO x 2^-10 (fp16 subnormals) and x 2^8 (loss-scaled)
+ATTN_BWD_SCALES = (-10, 8)
+ATTN_BWD_SAT = [(2, 2, 32), (2, 2, 72)]                                       # fp16, sharp, dO x 2^13: dk leaves fp16, dS does not
+ATTN_BWD_SAT_SCALE = 13
+ATTN_BWD_MUTANT_MAX_S = 200
+TEMPORAL_BWD_RESIDENT = [(2, 3, 128, 1, 1), (2, 3, 128, 5, 8), (1, 3, 128, 8, 32)]      # (B, P, D, T, Tmax); P = 3: a partial block of clamped lanes
+TEMPORAL_BWD_STREAM = [(2, 3, 128, 9, 9), (1, 3, 128, 17, 32), (1, 5, 256, 32, 32)]
+TEMPORAL_BWD_SHAPES = TEMPORAL_BWD_RESIDENT + TEMPORAL_BWD_STREAM
+TEMPORAL_BWD_KINDS = ("flat", "sharp", "diagonal", "first", "ladder")
+
+
+def unrope(g, co, si, sign=1.0):
+    """RoPE^T of [..][pos][64] with the angles' cos / sin [pos][32]: the rotation by the negative angle.  sign = -1: the WRONG rotation by the positive one"""
+    a, b = g[..., 0::2], g[..., 1::2]
+    return torch.stack([a * co + sign * b * si, b * co - sign * a * si], dim=-1).reshape(g.shape)
+
+
+def unrope_bound(e, g, co, si):
+    """the rotation's line of the derivation: e = bound of the value in front of it, g = that value"""
+    ea, eb, a, b = e[..., 0::2], e[..., 1::2], g[..., 0::2].abs(), g[..., 1::2].abs()
+    co, si = co.abs(), si.abs()
+    return torch.stack([ea * co + eb * si + 3 * EPS32 * (a * co + b * si), eb * co + ea * si + 3 * EPS32 * (b * co + a * si)], dim=-1).reshape(g.shape)
+
+
+def rope_cs(ang):
+    """the launch's table: fp32 [pos][pair][cos, sin]"""
+    return torch.stack([ang.cos(), ang.sin()], dim=-1).reshape(ang.shape[0], 64).contiguous()
+
+
+def temporal_rope_angles(n):
+    """the `temporal` table of tests/test_gpu_ops_attn_temporal_bwd.py: position t x the language frequencies 10000^(-2 i / 64)"""
+    return torch.arange(n, dtype=torch.float32)[:, None] * (1.0 / (10000.0 ** (torch.arange(0, 64, 2).float() / 64)))[None, :]
+
+
+class _AttnBwdMath:
+    """The chain above on [..][n queries][64] q / dO and [..][n keys][64] k / v in fp64; mask [n][n] True = hidden (None: full attention); chunk = keys per
+    chunk of the streaming statistics (64 spatial, 1 temporal).  p_dtype: the type P and dS are rounded to (None: they stay as they are)."""
+
+    def __init__(self, q, k, v, g, mask, chunk):
+        self.q, self.k, self.v, self.g, self.mask, self.chunk = q, k, v, g, mask, chunk
+        self.n = q.shape[-2]
+
+    def scores(self, mask=None):
+        mask = self.mask if mask is None else mask
+        s = self.q @ self.k.transpose(-1, -2) / 8.0
+        return s if mask is None else s.masked_fill(mask, float("-inf"))
+
+    def reference(self):
+        s = self.scores()
+        mx = s.max(-1, keepdim=True).values
+        pu = torch.exp(s - mx)
+        Z = pu.sum(-1, keepdim=True)
+        P = pu / Z
+        dP = self.g @ self.v.transpose(-1, -2)
+        Dq = (P * dP).sum(-1, keepdim=True)
+        dS = P * (dP - Dq) / 8.0
+        return dict(s=s, mx=mx, lse=mx + torch.log(Z), P=P, dP=dP, Dq=Dq, dS=dS, dv=P.transpose(-1, -2) @ self.g, dq=dS @ self.k, dk=dS.transpose(-1, -2) @ self.q)
+
+    def bounds(self, r, dtype, spatial):
+        """bounds of dq, dk (in front of the rotation) and dv, per element: the derivation above, line by line"""
+        n, e = self.n, EPS32
+        nvis = float(n) if self.mask is None else (~self.mask).sum(-1, keepdim=True).double()         # keys a query sees
+        ncol = float(n) if self.mask is None else (~self.mask).sum(0)[:, None].double()               # queries that see a key (rows of dk / dv)
+        u, sub = (U[dtype] * (1 + 2.0 ** -10), SUBNORMAL[dtype]) if spatial else (0.0, 0.0)
+        q, k, v, g = self.q.abs(), self.k.abs(), self.v.abs(), self.g.abs()
+        P, dP, dS = r["P"], r["dP"].abs(), r["dS"].abs()
+        s = r["s"].masked_fill(self.mask, 0.0) if self.mask is not None else r["s"]
+        e_s = 2 * 66 * e * (q @ k.transpose(-1, -2)) / 8.0
+        if spatial:
+            x = 4 * e * (s.abs() + torch.maximum(r["lse"].abs(), r["mx"].abs())) * LOG2E
+        else:
+            x = ((s - r["mx"]).abs() + 2) * 2.0 ** -22
+        num = e_s + x
+        if self.mask is not None:
+            num = num.masked_fill(self.mask, 0.0)
+        rho = num + (P * num).sum(-1, keepdim=True) + (nvis + 4) * 2.0 ** -23
+        eP = (u + rho) * P + 0.5 * sub + FLUSH32
+        edP = 2 * 66 * e * (g @ v.transpose(-1, -2))
+        if self.mask is not None:
+            eP, edP = eP.masked_fill(self.mask, 0.0), edP.masked_fill(self.mask, 0.0)
+        eDq = (P * edP).sum(-1, keepdim=True) + (rho * P * dP).sum(-1, keepdim=True) + (nvis + 2) * 2.0 ** -23 * (P * dP).sum(-1, keepdim=True)
+        edS = (u + rho + 4 * e) * dS + P * (edP + eDq) / 8.0 + 0.5 * sub
+        if self.mask is not None:
+            edS = edS.masked_fill(self.mask, 0.0)
+        t = lambda m: m.transpose(-1, -2)
+        return dict(dv=t(eP) @ g + 2 * (ncol + 2) * e * (t(P) @ g), dq=edS @ k + 2 * (nvis + 2) * e * (dS @ k), dk=t(edS) @ q + 2 * (ncol + 2) * e * (t(dS) @ q))
+
+    def design(self, p_dtype, wrong=None, trunc_ds=False):
+        """dq, dk (in front of the rotation), dv and dS of a perfect kernel of the design (fp64 math, P and dS rounded to p_dtype where given), or of a WRONG one"""
+        n, C = self.n, self.chunk
+        mask = self.mask
+        if wrong == "mask_plus":
+            mask = torch.arange(n)[None, :] > torch.arange(n)[:, None] + 1
+        elif wrong == "mask_minus":
+            mask = torch.arange(n)[None, :] > (torch.arange(n)[:, None] - 1).clamp_min(0)
+        s = self.scores(mask)
+        vis = torch.ones(n, n, dtype=torch.bool) if mask is None else ~mask
+        last = (vis * torch.arange(n)[None, :]).max(-1).values
+        stat = vis.clone()                                   # the keys the row statistics include
+        if wrong == "drop_last":
+            stat[torch.arange(n), last] = False
+            stat[:, 0] |= ~stat.any(-1)                      # (a query with one visible key keeps it)
+        ss = s.masked_fill(~stat, float("-inf"))
+        mx = ss.max(-1, keepdim=True).values
+        if wrong == "stale_max":
+            run = torch.full_like(mx, float("-inf"))
+            Z = torch.zeros_like(mx)
+            for c0 in range(0, n, C):
+                blk = ss[..., c0:c0 + C]
+                run = torch.maximum(run, blk.max(-1, keepdim=True).values)
+                Z = Z + torch.exp(blk - run.masked_fill(run == float("-inf"), 0.0)).sum(-1, keepdim=True)      # the old sum is NOT rescaled to the new maximum
+        else:
+            Z = torch.exp(ss - mx).sum(-1, keepdim=True)
+        lse = mx + torch.log(Z)
+        P = torch.exp(s - lse)                               # every visible key, the one the statistics left out included
+        dP = self.g @ self.v.transpose(-1, -2)
+        dqm = stat.clone()
+        if wrong == "dq_chunk":
+            dqm[:, (n - 1) // C * C:] = False
+        Dq = (torch.exp(ss - lse).masked_fill(~dqm, 0.0) * dP).sum(-1, keepdim=True)
+        dS = P * (dP - Dq) / 8.0
+        if p_dtype is not None:
+            P = store_clamped(P, p_dtype).double()
+            dS = (store_trunc(dS.clamp(-F16_MAX, F16_MAX) if p_dtype is F16 else dS, p_dtype) if trunc_ds else store_clamped(dS, p_dtype)).double()
+        return dS @ self.k, dS.transpose(-1, -2) @ self.q, P.transpose(-1, -2) @ self.g, dS
+
+
+def attn_bwd_inputs(NB, heads, S, kind, scale_log2, dtype):
+    """q, k, v [NB][heads][S][64], dO [NB S][heads 64] in the operand type, the angles [S][32] of the launch's table.
+    jump: per (item, head), key 5 + 64 n = (0.5 + 0.5 n) q[7] for every n (a maximum that RISES in every 64-key chunk: the rescale path of the streaming sweep and of
+    every per-lane running maximum), then key S - 1 = 3 q[S - 1] (a dominant key in the last tile, which may be partial), then key 3 = 4 q[S / 2] (the maximum is met in
+    the first chunk and nothing later moves it)."""
+    q, k, v = (rand(NB, heads, S, 64, seed=i) for i in (1, 2, 3))
+    do = rand(NB * S, heads * 64, seed=4) * 2.0 ** scale_log2
+    if kind == "sharp":
+        q = q * 6.0
+    q = q.to(dtype)
+    if kind == "jump":
+        for n in range((S - 6) // 64 + 1):
+            k[:, :, 5 + 64 * n] = (0.5 + 0.5 * n) * q[:, :, 7].float()
+        k[:, :, S - 1] = 3.0 * q[:, :, S - 1].float()
+        k[:, :, 3] = 4.0 * q[:, :, S // 2].float()
+    return q, k.to(dtype), v.to(dtype), do.to(dtype), rand(S, 32, seed=5) * 3
+
+
+class AttnBwdCase:
+    """ref / tol [NB S][3 D] fp64: dq | dk | dv as the launch lays them out (column head 64 + d of each third).  peak: the largest |dS|, |dq|, |dk|, |dv| of the
+    fp64 reference (dq / dk rotated) — the error word must stay 0 while it is below a quarter of the type's largest finite value."""
+
+    def __init__(self, NB, heads, S, kind, scale_log2, dtype):
+        self.NB, self.heads, self.S, self.kind, self.scale_log2, self.dtype = NB, heads, S, kind, scale_log2, dtype
+        self.q, self.k, self.v, self.do, self.ang = attn_bwd_inputs(NB, heads, S, kind, scale_log2, dtype)
+        self.cs = rope_cs(self.ang)
+        self.co, self.si = self.cs[:, 0::2].double(), self.cs[:, 1::2].double()         # the fp32 table values: what the launch multiplies by
+        g4 = self.do.double().reshape(NB, S, heads, 64).permute(0, 2, 1, 3)
+        self.math = _AttnBwdMath(self.q.double(), self.k.double(), self.v.double(), g4, None, 64)
+        r = self.math.reference()
+        b = self.math.bounds(r, dtype, spatial=True)
+        u, sub = U[dtype] * (1 + 2.0 ** -10), SUBNORMAL[dtype]
+        outs = (unrope(r["dq"], self.co, self.si), unrope(r["dk"], self.co, self.si), r["dv"])
+        tols = (unrope_bound(b["dq"], r["dq"], self.co, self.si), unrope_bound(b["dk"], r["dk"], self.co, self.si), b["dv"])
+        self.ref = self.rows(*outs)
+        self.tol = self.rows(*tols) + u * self.ref.abs() + sub
+        self.max_ds = r["dS"].abs().max().item()
+        self.peak = max(self.max_ds, self.ref.abs().max().item())
+        self.pmax_median = r["P"].max(-1).values.median().item()
+
+    def rows(self, dq, dk, dv):
+        NB, heads, S = self.NB, self.heads, self.S
+        return torch.cat([x.permute(0, 2, 1, 3).reshape(NB * S, heads * 64) for x in (dq, dk, dv)], dim=1).contiguous()
+
+    def control(self, wrong=None, store=store_clamped, trunc_ds=False):
+        """[NB S][3 D] in the operand type: the perfect kernel of the design (or a wrong one), see the head of this section"""
+        dq, dk, dv, _ = self.math.design(self.dtype, wrong, trunc_ds)
+        sign = -1.0 if wrong == "rope_sign" else 1.0
+        out = self.rows(unrope(dq, self.co, self.si, sign), unrope(dk, self.co, self.si, sign), dv)
+        return store(out.clamp(-F16_MAX, F16_MAX) if self.dtype is F16 else out, self.dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def attn_bwd_case(NB, heads, S, kind, scale_log2, dtype):
+    return AttnBwdCase(NB, heads, S, kind, scale_log2, dtype)
+
+
+def temporal_bwd_inputs(B, P, D, T, Tmax, kind, dtype):
+    """q [B][T][P][D], kv [B][Tmax][P][2][D], dO [B T P][D] in the operand type.  Per (sample, position, head): diagonal k_t = 3 q_t (every query is dominated by
+    its own frame); first k_0 = 3 q_{T-1} (the last query's maximum is met at once and stays); ladder k_s = (0.5 + 0.25 s) q_{T-1} (its maximum rises with every
+    key).  Cache frames from T on hold ordinary values no kernel reads."""
+    q = rand(B, T, P, D, seed=1)
+    kv = rand(B, Tmax, P, 2, D, seed=2)
+    do = rand(B * T * P, D, seed=3)
+    if kind == "sharp":
+        q = q * 6.0
+    q = q.to(dtype)
+    qf = q.float()
+    if kind == "diagonal":
+        kv[:, :T, :, 0] = 3.0 * qf
+    elif kind == "first":
+        kv[:, 0, :, 0] = 3.0 * qf[:, T - 1]
+    elif kind == "ladder":
+        for s in range(T):
+            kv[:, s, :, 0] = (0.5 + 0.25 * s) * qf[:, T - 1]
+    return q, kv.to(dtype), do.to(dtype)
+
+
+class TemporalBwdCase:
+    """ref / tol [B T P][3 D] fp64, as AttnBwdCase; the table is temporal_rope_angles(Tmax), of which rows 0 .. T - 1 are used"""
+
+    def __init__(self, B, P, D, T, Tmax, kind, dtype):
+        self.args, self.kind, self.dtype = (B, P, D, T, Tmax), kind, dtype
+        self.q, self.kv, self.do = temporal_bwd_inputs(B, P, D, T, Tmax, kind, dtype)
+        self.cs = rope_cs(temporal_rope_angles(Tmax))
+        self.co, self.si = self.cs[:T, 0::2].double(), self.cs[:T, 1::2].double()
+        h = D // 64
+        item = lambda x: x.double().reshape(B, T, P, h, 64).permute(0, 2, 3, 1, 4)             # B P h T 64
+        mask = torch.arange(T)[None, :] > torch.arange(T)[:, None]
+        self.math = _AttnBwdMath(item(self.q), item(self.kv[:, :T, :, 0]), item(self.kv[:, :T, :, 1]), item(self.do.reshape(B, T, P, D)), mask, 1)
+        r = self.math.reference()
+        b = self.math.bounds(r, dtype, spatial=False)
+        u, sub = U[dtype] * (1 + 2.0 ** -10), SUBNORMAL[dtype]
+        self.ref = self.rows(unrope(r["dq"], self.co, self.si), unrope(r["dk"], self.co, self.si), r["dv"])
+        self.tol = self.rows(unrope_bound(b["dq"], r["dq"], self.co, self.si), unrope_bound(b["dk"], r["dk"], self.co, self.si), b["dv"]) + u * self.ref.abs() + sub
+        self.max_ds = r["dS"].abs().max().item()
+        self.peak = max(self.max_ds, self.ref.abs().max().item())
+
+    def rows(self, dq, dk, dv):
+        B, P, D, T, _ = self.args
+        return torch.cat([x.permute(0, 3, 1, 2, 4).reshape(B * T * P, D) for x in (dq, dk, dv)], dim=1).contiguous()
+
+    def control(self, wrong=None, store=store_clamped):
+        dq, dk, dv, _ = self.math.design(None, wrong)
+        sign = -1.0 if wrong == "rope_sign" else 1.0
+        out = self.rows(unrope(dq, self.co, self.si, sign), unrope(dk, self.co, self.si, sign), dv)
+        return store(out.clamp(-F16_MAX, F16_MAX) if self.dtype is F16 else out, self.dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def temporal_bwd_case(B, P, D, T, Tmax, kind, dtype):
+    return TemporalBwdCase(B, P, D, T, Tmax, kind, dtype)

@@ -1,4 +1,5 @@
-"""The bounds of tests/test_gpu_ops_typed.py and (second half) of tests/test_gpu_ops_train.py, checked on the CPU (no library, no GPU): a bound is only worth asserting if a correct kernel stays inside it and a
+"""The bounds of tests/test_gpu_ops_typed.py, (second half) of tests/test_gpu_ops_train.py and tests/test_gpu_ops_ln_pending.py and (last section) of
+tests/test_gpu_ops_attn_bwd_bounds.py, checked on the CPU (no library, no GPU): a bound is only worth asserting if a correct kernel stays inside it and a
 subtly wrong one does not.  For every per-element bound, an emulation in fp32 arithmetic with a round-to-nearest-even 2-byte store must leave NO element
 outside, and the same emulation with a TRUNCATING store (a dropped guard bit, a wrong pack instruction) must put at least 1 % of the elements outside.  For
 every per-row bound, the fp64 reference rounded to the operand type — the best any kernel can return — must stay below 0.6 of the bound in its worst row.
@@ -391,3 +392,106 @@ def test_ln_pending_saturating_branch_image():
     assert y16[3, 5].item() == PB.F16_MAX and y16[6, 60].item() == -PB.F16_MAX and torch.isfinite(y16.float()).all()
     assert ybf[3, 5].item() == 79872.0 and ybf[6, 60].item() == -70144.0                   # bf16's grid around 80000 / 70000.5 has steps of 512
     assert (c.branch32().abs() > PB.F16_MAX).sum().item() == 2
+
+
+# ======================================================================================================================================================
+# The bounds of tests/test_gpu_ops_attn_bwd_bounds.py (the four attention backward kernels).  For every case of the GPU file: "what a perfect kernel of the
+# design returns" (fp64 math with exactly the design's 2-byte roundings: P, dS and the outputs for the spatial pair, the outputs only for the temporal pair) has
+# NO element outside the bound, and every wrong kernel of tests/parity_bounds.py's list puts at least one element of dq / dk / dv outside.  A truncating output
+# store and a truncated dS are PRINTED for the spatial pair and not required caught (P and dS are rounded to 2 bytes by design, so the bound carries u-sized
+# terms of its own: the limit stated in the head comment there); the temporal bound has no such term and must catch the truncating store.
+# ======================================================================================================================================================
+ATTN_BWD_CASES = [(s, k, 0) for s in PB.ATTN_BWD_SHAPES for k in PB.ATTN_BWD_KINDS] + \
+                 [(s, k, e) for s in PB.ATTN_BWD_SCALED_SHAPES for k in PB.ATTN_BWD_KINDS for e in PB.ATTN_BWD_SCALES]
+ATTN_BWD_IDS = [f"{s[0]}x{s[1]}x{s[2]}-{k}-2^{e}" for s, k, e in ATTN_BWD_CASES]
+TEMPORAL_BWD_CASES = [(s, k) for s in PB.TEMPORAL_BWD_SHAPES for k in PB.TEMPORAL_BWD_KINDS]
+TEMPORAL_BWD_IDS = ["x".join(map(str, s)) + "-" + k for s, k in TEMPORAL_BWD_CASES]
+THIRDS = ("dq", "dk", "dv")
+
+
+def _thirds(c, got):
+    """worst ratio error / bound of dq, dk, dv"""
+    r = (got.double() - c.ref).abs() / c.tol
+    D = r.shape[1] // 3
+    return [r[:, i * D:(i + 1) * D].max().item() for i in range(3)]
+
+
+def _fmt(w):
+    return " ".join(f"{n} {x:.3g}" for n, x in zip(THIRDS, w))
+
+
+@DTYPES
+@pytest.mark.parametrize("shape,kind,e", ATTN_BWD_CASES, ids=ATTN_BWD_IDS)
+def test_attn_spatial_bwd_control_is_inside(shape, kind, e, dtype):
+    c = PB.attn_bwd_case(*shape, kind, e, dtype)
+    name = f"attn_spatial_bwd {shape} {kind} dO x 2^{e} {PB.NAME[dtype]}"
+    w = _thirds(c, c.control())
+    print(f"[bound control {name}] perfect kernel of the design: worst ratio {_fmt(w)}")
+    assert max(w) <= 1.0, (name, w)
+    assert c.peak < 0.25 * (PB.F16_MAX if dtype is PB.F16 else 3.3895313892515355e38), (name, c.peak)      # the GPU test expects a clear error word here
+    print(f"[bound control {name}] not required caught: truncating store {_fmt(_thirds(c, c.control(store=PB.store_trunc)))}; "
+          f"truncated dS {_fmt(_thirds(c, c.control(trunc_ds=True)))}")
+    if kind == "sharp" and e == 0 and shape[2] >= 32:
+        assert 0.4 < c.pmax_median < 0.9, c.pmax_median                # peaked rows: the largest probability of a row has a median of about 0.65
+    if kind == "flat" and shape[2] == 144:
+        assert c.pmax_median < 0.1
+
+
+@DTYPES
+@pytest.mark.parametrize("shape,kind", [(s, k) for s in PB.ATTN_BWD_SHAPES if s[2] <= PB.ATTN_BWD_MUTANT_MAX_S for k in PB.ATTN_BWD_KINDS],
+                         ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else v)
+def test_attn_spatial_bwd_wrong_kernels_are_outside(shape, kind, dtype):
+    c = PB.attn_bwd_case(*shape, kind, 0, dtype)
+    wrongs = ["drop_last", "rope_sign"] + (["stale_max", "dq_chunk"] if shape[2] > 64 else [])
+    for wrong in wrongs:
+        w = _thirds(c, c.control(wrong))
+        print(f"[bound control attn_spatial_bwd {shape} {kind} {PB.NAME[dtype]}] WRONG ({wrong}): worst ratio {_fmt(w)}")
+        assert max(w) > 1.0, (wrong, w)
+        if wrong == "rope_sign":
+            assert min(w[:2]) > 1.0 and w[2] <= 1.0, w            # dq AND dk, and only they
+
+
+@DTYPES
+@pytest.mark.parametrize("shape,kind", TEMPORAL_BWD_CASES, ids=TEMPORAL_BWD_IDS)
+def test_attn_temporal_bwd_control_and_wrong_kernels(shape, kind, dtype):
+    """T = 1 has P = 1, dS = 0 and dq = dk = 0 identically: no statistic, mask or rotation can be wrong there, so the wrong kernels start at T = 5."""
+    c = PB.temporal_bwd_case(*shape, kind, dtype)
+    T = shape[3]
+    name = f"attn_temporal_bwd {shape} {kind} {PB.NAME[dtype]}"
+    w = _thirds(c, c.control())
+    print(f"[bound control {name}] perfect kernel of the design: worst ratio {_fmt(w)}")
+    assert max(w) <= 1.0, (name, w)
+    assert c.peak < 0.25 * PB.F16_MAX
+    if T == 1:                                                      # (dv = dO there, a 2-byte value already: no store can round it wrongly either)
+        assert max(w) == 0.0
+        return
+    w = _thirds(c, c.control(store=PB.store_trunc))
+    print(f"[bound control {name}] WRONG (truncating store): worst ratio {_fmt(w)}")
+    # P and dS stay fp32, the store's u |ref| is the bound's only 2-byte term: dv leaves it in every case.  (dq / dk of a peaked row are sums of dS ~ 0 that cancel:
+    # there the fp32 terms of the bound outweigh u |ref|, and the truncation stays inside — 0.65 on `sharp` fp16 dq.)
+    assert w[2] > 1.0, w
+    for wrong in ["drop_last", "rope_sign", "mask_plus", "mask_minus"] + (["stale_max"] if kind == "ladder" else []):
+        w = _thirds(c, c.control(wrong))
+        print(f"[bound control {name}] WRONG ({wrong}): worst ratio {_fmt(w)}")
+        if kind == "diagonal" and T <= 8 and wrong in ("rope_sign", "mask_plus"):
+            # k_t = 3 q_t puts the own frame 24 above every other score (sd 3): with so few keys every other probability is e^-15 at most, dS, dq and dk are
+            # next to zero in fp64 already, and neither a rotation of them nor one more key of that weight moves anything by as much as the bound (printed
+            # above: 0.03 .. 0.15 of it).  Both are caught on `diagonal` from T = 9 on, where some off-diagonal score comes close enough.
+            continue
+        assert max(w) > 1.0, (wrong, w)
+
+
+@pytest.mark.parametrize("shape", PB.ATTN_BWD_SAT, ids=lambda s: "x".join(map(str, s)))
+def test_attn_spatial_bwd_saturation_preconditions(shape):
+    """fp16, sharp, dO x 2^13: some output leaves fp16 while dS stays far inside — what the GPU test's ERR_F16_SAT case needs of its inputs.  The perfect kernel
+    (clamped stores) stays inside the bound of the clamped reference: clamping cannot increase an error."""
+    c = PB.attn_bwd_case(*shape, "sharp", PB.ATTN_BWD_SAT_SCALE, PB.F16)
+    D = c.ref.shape[1] // 3
+    peaks = [c.ref[:, i * D:(i + 1) * D].abs().max().item() for i in range(3)]
+    print(f"[bound control attn_spatial_bwd saturation {shape}] fp64 max |dS| {c.max_ds:.4g}, max |dq| |dk| |dv| {_fmt(peaks)}")
+    assert max(peaks) > PB.F16_MAX and c.max_ds < 0.25 * PB.F16_MAX
+    got = c.control()
+    assert torch.isfinite(got.float()).all()
+    f, w = PB.outside((got.double() - c.ref.clamp(-PB.F16_MAX, PB.F16_MAX)).abs(), c.tol)
+    print(f"[bound control attn_spatial_bwd saturation {shape}] perfect kernel against the clamped reference: worst ratio {w:.3f}")
+    assert f == 0.0
