@@ -551,6 +551,44 @@ int gtav_op_train_ada_bwd_dx(const float* dmod, int32_t MODW, const float* W, in
     GTAV_OP_WS("op_train_ada_bwd_dx", part, part_floats, ada_bwd_dx_workspace(MODW, D, R));
     return launch_ada_bwd_dx(dmod, MODW, W, D, R, dSc, part, (hipStream_t)stream);
 }
+// The optimizer step, kernel level (include/gtav_amd_testing.h): the norm's partial sums, the step coefficient, the multi-tensor AdamW launch in its three modes
+// over work items cut by the handle's own planner (api_internal.h adam_plan_items), and the overflow publisher — each the launcher gtav_dit_adamw_step runs.
+int gtav_op_train_sumsq_parts(int64_t n) { return sumsq_parts((size_t)n); }
+int gtav_op_train_sumsq(const float* g, int64_t n, float* part, int64_t part_floats, void* stream) {
+    GTAV_OP_WS("op_train_sumsq", part, part_floats, sumsq_parts((size_t)n));
+    return launch_sumsq(g, (size_t)n, part, (hipStream_t)stream);
+}
+int gtav_op_train_clip_coef(float* ctl, const float* part, int32_t nparts, float inv_scale, float max_norm, float beta1, float beta2, float ema_decay,
+                            int32_t ema_warmup, int32_t* err, void* stream) {
+    return launch_clip_coef(ctl, part, nparts, inv_scale, max_norm, beta1, beta2, ema_decay, ema_warmup, err, (hipStream_t)stream);
+}
+int gtav_op_train_adamw_multi(int32_t mode, int32_t n_params, float* const* p, const int32_t* ldp, const int32_t* R, const int32_t* C, const float* const* g,
+                              float* const* m, float* const* v, float* const* e, void* const* w16, const int32_t* Cp16, void* const* wT, const int32_t* RpT,
+                              void* desc, int64_t desc_bytes, const float* ctl, float lr, float beta1, float beta2, float eps, float wd, void* stream) {
+    GTAV_REQUIRE(mode >= 0 && mode <= 2 && n_params >= 1, "op_train_adamw_multi: mode=%d (0 step, 1 step + averaged weights, 2 swap), %d parameters", mode, n_params);
+    std::vector<AdamParam> ap((size_t)n_params);
+    std::vector<AdamItem> ai;
+    for (int pi = 0; pi < n_params; ++pi) {
+        AdamParam& d = ap[pi];
+        memset(&d, 0, sizeof(d));
+        d.p = p[pi]; d.ldp = ldp[pi]; d.R = R[pi]; d.C = C[pi]; d.g = g[pi]; d.m = m[pi]; d.v = v[pi]; d.e = e[pi];
+        d.w16 = (f16*)w16[pi]; d.Cp16 = Cp16[pi]; d.wT = (f16*)wT[pi]; d.RpT = RpT[pi];
+        adam_plan_items(d, pi, ai);
+    }
+    const size_t pb = ap.size() * sizeof(AdamParam), ib = ai.size() * sizeof(AdamItem);
+    GTAV_REQUIRE(desc && desc_bytes >= (int64_t)(pb + ib), "op_train_adamw_multi: descriptor buffer of %lld bytes, %lld needed (%d parameters, %zu work items)",
+                 (long long)(desc ? desc_bytes : 0), (long long)(pb + ib), n_params, ai.size());
+    GTAV_REQUIRE(!ai.empty(), "op_train_adamw_multi: no work item");
+    // (blocking copies, as gtav_dit_train_enable fills its tables: the one hook that synchronises)
+    GTAV_CHECK_HIP(hipMemcpy(desc, ap.data(), pb, hipMemcpyHostToDevice));
+    GTAV_CHECK_HIP(hipMemcpy((char*)desc + pb, ai.data(), ib, hipMemcpyHostToDevice));
+    const AdamParam* dp = (const AdamParam*)desc;
+    const AdamItem* di = (const AdamItem*)((char*)desc + pb);
+    if (mode == 0) return op_ops().adamw_multi(dp, di, (int)ai.size(), ctl, lr, beta1, beta2, eps, wd, (hipStream_t)stream);
+    if (mode == 1) return op_ops().adamw_multi_ema(dp, di, (int)ai.size(), ctl, lr, beta1, beta2, eps, wd, (hipStream_t)stream);
+    return op_ops().adamw_swap_ema(dp, di, (int)ai.size(), (hipStream_t)stream);
+}
+int gtav_op_train_overflow_publish(const int32_t* err, float* g, void* stream) { return launch_overflow_publish(err, g, (hipStream_t)stream); }
 #undef GTAV_OP_WS
 
 }  // extern "C"

@@ -27,6 +27,18 @@ using namespace gtav;
     } while (0)
 
 namespace gtav {
+// The work items of the multi-tensor AdamW launch for parameter `pi` (train.hip adamw_multi_kernel), appended to `items`: one per 64 x 64 tile of a GEMM weight
+// (w16 set; the tile index, row-major over the tiles), one per run of up to 4096 elements of an fp32 parameter (its first element).  The ONE planner of that
+// launch: gtav_dit_train_enable and the test hook gtav_op_train_adamw_multi both call it.
+inline void adam_plan_items(const AdamParam& d, int pi, std::vector<AdamItem>& items) {
+    if (d.w16) {
+        const unsigned nt = (unsigned)(cdiv(d.R, 64) * cdiv(d.C, 64));
+        for (unsigned i = 0; i < nt; ++i) items.push_back(AdamItem{pi, i});
+    } else {
+        const size_t n = (size_t)d.R * d.C;
+        for (size_t st = 0; st < n; st += 4096) items.push_back(AdamItem{pi, (unsigned)st});
+    }
+}
 namespace api {
 
 // ------------------------------------------------------------------------------------------------

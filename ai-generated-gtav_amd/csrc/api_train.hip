@@ -205,13 +205,7 @@ static int train_enable_body(gtav_dit* h, float* grad_arena_dev, int64_t grad_ar
             d.p = sl->master; d.ldp = f16w ? sl->C : sl->Cp; d.R = sl->R; d.C = sl->C; d.g = sl->grad; d.m = sl->am; d.v = sl->av; d.e = sl->ema;
             if (f16w) { d.w16 = (f16*)sl->dst; d.Cp16 = sl->Cp; d.wT = sl->wT; d.RpT = round_up(sl->R, 64); }
             ap.push_back(d);
-            if (f16w) {
-                const unsigned nt = (unsigned)(cdiv(sl->R, 64) * cdiv(sl->C, 64));
-                for (unsigned i = 0; i < nt; ++i) ai.push_back(AdamItem{(int)pi, i});
-            } else {
-                const size_t n = (size_t)sl->R * sl->C;
-                for (size_t st = 0; st < n; st += 4096) ai.push_back(AdamItem{(int)pi, (unsigned)st});
-            }
+            adam_plan_items(d, (int)pi, ai);   // (a GEMM weight's image sl->dst is never null: w16 set <=> f16w)
         }
         RET_IF(a.alloc_t(&t.adam_params, ap.size()));
         RET_IF(a.alloc_t(&t.adam_items, ai.size()));

@@ -170,8 +170,6 @@ int launch_err_fold(int* words, int* sticky, int dst_word, int n_groups, hipStre
 // ema_decay > 0 (a handle with averaged weights): ctl[7] = the decay of the step being applied, ema_decay or with ema_warmup min(ema_decay, (1 + t) / (10 + t))
 int launch_clip_coef(float* ctl, const float* part, int nparts, float inv_scale, float max_norm, float beta1, float beta2, float ema_decay, int ema_warmup,
                      int* err_flag, hipStream_t stream);
-int launch_adamw(float* p, int ldp, int R, int C, const float* g, float* m, float* v, const float* ctl, float lr, float beta1, float beta2, float eps,
-                 float wd, hipStream_t stream);
 // Low-rank adapters (ops_typed.inc launch_lora_grads): the planning of the gradient launches, pure host arithmetic.  The contraction over the M token rows is
 // cut into at most LORA_MAX_SPLITS runs of whole 128-row tiles; every run stores a partial [N + K][r] result which a second pass adds in run order.
 // Workspace, in floats: t^T and u^T as 2-byte [r][round_up(M, 128)] each (r * round_up(M, 128) floats together), the adapters rounded to the operand type, A^ [r][K]

@@ -1541,28 +1541,9 @@ __global__ __launch_bounds__(256) void clip_coef_kernel(float* ctl, const float*
     }
     ctl[3] = norm;
 }
-__global__ void adamw_kernel(float* __restrict__ p, int ldp, int R, int C, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                             const float* __restrict__ ctl, float lr, float beta1, float beta2, float eps, float wd) {
-    const float coef = ctl[1];
-    if (coef == 0.f) return;               // overflow: skip the step
-    const float bc1 = ctl[5], bc2 = ctl[6];
-    const size_t total = (size_t)R * C;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-        const int c = (int)(idx % C);
-        const size_t r = idx / C;
-        const float gr = g[idx] * coef;
-        const float mm = beta1 * m[idx] + (1.0f - beta1) * gr;
-        const float vv = beta2 * v[idx] + (1.0f - beta2) * gr * gr;
-        m[idx] = mm;
-        v[idx] = vv;
-        float* pp = p + r * ldp + c;
-        const float w = *pp * (1.0f - lr * wd);
-        *pp = w - (lr / bc1) * mm / (sqrtf(vv) / sqrtf(bc2) + eps);
-    }
-}
 
 // Multi-tensor AdamW (one launch for the whole model) fused with the refresh of the fp16 GEMM operands.  The host cuts every parameter
-// into work items (api_train.hip gtav_dit_train_enable): a 64 x 64 tile of a GEMM weight, or a run of up to 4096 elements of an fp32
+// into work items (api_internal.h adam_plan_items, for gtav_dit_train_enable and for the test hook alike): a 64 x 64 tile of a GEMM weight, or a run of up to 4096 elements of an fp32
 // parameter.  A block updates its item in fp32 and, for a GEMM weight, writes the tile straight into the tile-major fp16 W (16 bytes
 // along c) and, through an LDS transpose, into the tile-major fp16 W^T (16 bytes along r): the separate convert passes (two more reads
 // of the 0.8 GB of masters, 370 launches) and 300 per-parameter AdamW launches are gone.
@@ -2307,13 +2288,6 @@ int launch_lora_grads(const f16* X, const f16* dY, const float* A, const float* 
     switch (r) { GTAV_LORA_R(1); GTAV_LORA_R(2); GTAV_LORA_R(4); }
 #undef GTAV_LORA_R
     hipLaunchKernelGGL(lora_reduce_kernel, dim3((unsigned)cdiv((N + K) * r, 256)), dim3(256), 0, stream, (const float*)part, splits, N, K, r, s, dA, dB);
-    GTAV_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-int launch_adamw(float* p, int ldp, int R, int C, const float* g, float* m, float* v, const float* ctl, float lr, float beta1, float beta2, float eps,
-                 float wd, hipStream_t stream) {
-    hipLaunchKernelGGL(adamw_kernel, dim3(grid_for((size_t)R * C)), dim3(256), 0, stream, p, ldp, R, C, g, m, v, ctl, lr, beta1, beta2, eps, wd);
     GTAV_CHECK_HIP(hipGetLastError());
     return 0;
 }

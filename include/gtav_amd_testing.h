@@ -59,6 +59,25 @@
  *                             On fp16 operands a dS, dq, dk or dv beyond 65504 is stored clamped and raises ERR_F16_SAT (2) in `err` — the bit on which a training
  *                             step skips its optimizer step; bf16 operands never raise it.  tests/test_gpu_ops_attn_bwd_bounds.py holds every output element to the
  *                             derived bounds of tests/parity_bounds.py on flat AND peaked softmax rows, and the bit.
+ *   sumsq_parts, sumsq, clip_coef, adamw_multi, overflow_publish   the optimizer step as gtav_dit_adamw_step launches it: launch_sumsq (part = sumsq_parts(n) floats, its
+ *                             size in part_floats, refused by name when short), launch_clip_coef (ctl = the caller's 8 device floats of csrc/ops_typed.inc: the hook
+ *                             reads ctl[2], ctl[4] and writes ctl[0 .. 7] as the kernel does; err may be null), launch_overflow_publish, and
+ *   adamw_multi               mode 0 / 1 / 2 = launch_adamw_multi / _multi_ema / _swap_ema in the thread's operand type, over n_params parameters given as HOST arrays
+ *                             of n_params entries each: p, ldp, R, C (the fp32 master and its leading dimension), g, m, v, e (contiguous [R][C]; e may hold nulls in
+ *                             mode 0), w16, Cp16, wT, RpT (the two 2-byte images of a GEMM weight: w16 null = an fp32 parameter trained in place, wT null = no
+ *                             transposed image).  The work items — one per 64 x 64 tile of a GEMM weight, one per 4096-element run of an fp32 parameter — are cut by
+ *                             the function gtav_dit_train_enable cuts them with (csrc/api_internal.h adam_plan_items).  `desc` is a caller-owned DEVICE buffer of
+ *                             desc_bytes for the AdamParam [n_params] and AdamItem [items] tables (88 and 8 bytes each), refused by name when too small.  Unlike every
+ *                             other hook this one SYNCHRONISES: it fills `desc` with two blocking hipMemcpy, as gtav_dit_train_enable fills the handle's tables.
+ *                             It validates nothing else: pointers, shapes and alignment (16-byte rows for a GEMM weight with C % 4 == 0) are the caller's.
+ *                             A documented property of the design: clip_coef computes the bias corrections ctl[5] / ctl[6] = 1 - powf(beta, t) in fp32, so at small t
+ *                             they inherit the cancellation — |ctl[5 | 6] - (1 - beta^t)| <= 2 ulp(beta^t) + 2^-24 (1 - beta^t), which at beta2 = 0.999 and t = 2, 3 is
+ *                             about 2000 x 2^-24 of the correction and half of that on the update; below 8 x 2^-24 from t = 1000 on.
+ *                             tests/test_gpu_ops_optimizer.py holds, in both operand types and between NaN guard words: every element of w, m, v (and the shadow e)
+ *                             to a derived bound against fp64 AdamW (tests/parity_bounds.py, last section) at t = 1, 2, 3, 1000 and 100000; exact zeros; BOTH images,
+ *                             pads included, bit for bit equal to gtav_op_convert_f16 / gtav_op_train_convert_t of the master the launch wrote; a skipped step and a
+ *                             swap writing exactly what they should; equal bits from the kernel's three code paths; the sum of squares, every field of clip_coef, and
+ *                             the published overflow.
  *
  * gtav_op_ln_pending          ONE launch_ln_modulate (mode 0: p0 = shift, p1 = scale tables of row length mod_stride, indexed by rows / rows_per_mod) or
  *                             launch_ln_affine (mode 1: p0 = gamma, p1 = beta; rows, rows_per_mod and mod_stride unused) with a deferred residual update
@@ -110,6 +129,16 @@ int gtav_op_train_attn_spatial_bwd(const void* q, const void* k, const void* vt,
                                    void* dqkv, int32_t* err, void* stream);
 int gtav_op_train_attn_temporal_bwd(const void* q, const void* kv, const void* d_o, int32_t B, int32_t P, int32_t D, int32_t T, int32_t Tmax, const float* rope_cs,
                                     void* dqkv, int32_t* err, void* stream);
+
+/* ---- the optimizer step (see above); host arrays of n_params entries, desc / ctl / part on the device ---- */
+int gtav_op_train_sumsq_parts(int64_t n);
+int gtav_op_train_sumsq(const float* g, int64_t n, float* part, int64_t part_floats, void* stream);
+int gtav_op_train_clip_coef(float* ctl, const float* part, int32_t nparts, float inv_scale, float max_norm, float beta1, float beta2, float ema_decay,
+                            int32_t ema_warmup, int32_t* err, void* stream);
+int gtav_op_train_adamw_multi(int32_t mode, int32_t n_params, float* const* p, const int32_t* ldp, const int32_t* R, const int32_t* C, const float* const* g,
+                              float* const* m, float* const* v, float* const* e, void* const* w16, const int32_t* Cp16, void* const* wT, const int32_t* RpT,
+                              void* desc, int64_t desc_bytes, const float* ctl, float lr, float beta1, float beta2, float eps, float wd, void* stream);
+int gtav_op_train_overflow_publish(const int32_t* err, float* g, void* stream);
 
 /* ---- the deferred-residual LayerNorm (see above) ---- */
 int gtav_op_ln_pending(int32_t mode, float* x, int32_t ldx, void* out, int32_t M, int32_t D, const float* p0, const float* p1, int32_t mod_stride,

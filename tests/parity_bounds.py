@@ -1,7 +1,7 @@
 """Inputs, fp64 references, error bounds and fp32 emulations of the operand-typed kernels, shared by tests/test_gpu_ops_typed.py (the kernels, on a GPU) and
 tests/test_host_parity_bounds.py (the bounds themselves, on the CPU).  Pure torch: nothing here loads the library.  The second half of the file holds the same
-for the backward-only training kernels (tests/test_gpu_ops_train.py), then the deferred-residual LayerNorm (tests/test_gpu_ops_ln_pending.py) and last the four
-attention backward kernels (tests/test_gpu_ops_attn_bwd_bounds.py), each with its own head comment.
+for the backward-only training kernels (tests/test_gpu_ops_train.py), then the deferred-residual LayerNorm (tests/test_gpu_ops_ln_pending.py), the four
+attention backward kernels (tests/test_gpu_ops_attn_bwd_bounds.py) and last the optimizer step (tests/test_gpu_ops_optimizer.py), each with its own head comment.
 
 None of the bounds is taken from the code under test.  u is the unit roundoff of the operand type, 2^-11 for fp16 and 2^-8 for bf16.
 
@@ -19,6 +19,7 @@ Global and per-row relative L2: the project's fp16 figure of the op (2e-5 fp32 o
 import functools
 import math
 
+import numpy as np
 import torch
 
 F16, BF16 = torch.float16, torch.bfloat16
@@ -1229,3 +1230,396 @@ class TemporalBwdCase:
 @functools.lru_cache(maxsize=None)
 def temporal_bwd_case(B, P, D, T, Tmax, kind, dtype):
     return TemporalBwdCase(B, P, D, T, Tmax, kind, dtype)
+
+
+# =======================================================================================================================================================
+# The optimizer step (tests/test_gpu_ops_optimizer.py): sumsq_kernel, clip_coef_kernel and the three modes of adamw_multi_kernel (csrc/train.hip), through the
+# hooks gtav_op_train_sumsq / _clip_coef / _adamw_multi.  Everything is fp32; u = EPS32 = 2^-24 is the unit roundoff, and every bound below is a COUNT of
+# roundings times u times the magnitude the rounding acts on, to first order, times (1 + 2^-10) for the second-order terms (the largest first-order sum in
+# this section is a few thousand u, whose square is far below 2^-10 of it).  Nothing here was fitted to what a GPU returned.
+#
+# Reference: fp64 AdamW with torch.optim.AdamW's semantics on the fp32 inputs, every hyperparameter and the coefficient c rounded to fp32 first (the C ABI passes
+# floats):  gc = g c;  m = b1 m0 + (1 - b1) gc;  v = b2 v0 + (1 - b2) gc^2;  w = w0 (1 - lr wd) - (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps).
+#
+# The kernel (one text for its three code paths):  gr = g * coef;  mm = beta1 * m + (1 - beta1) * gr;  vv = beta2 * v + (1 - beta2) * gr * gr;
+#   decay = 1 - lr * wd;  step = lr / ctl[5];  rs2 = 1 / sqrtf(ctl[6]);  w = w * decay - step * mm / (sqrtf(vv) * rs2 + eps).  Division and square root are
+#   correctly rounded; the compiler may contract any product into the following sum (one rounding fewer, never more).
+#   m   gr, 1 - b1, two products, the sum: 4 roundings, and m0 and gc may cancel, so the magnitude is |b1 m0| + |(1 - b1) gc|, not |m|
+#   v   gr (twice: it is squared), 1 - b2, two products of the second term, the sum: 6 roundings on non-negative terms, so 6 u v
+#   w   first term: decay (the inner product lr wd is below 2^-6, its rounding does not reach decay's last bit: 1, counted as 2), the product, the final
+#       subtraction: 4 u |w0 decay|.  Update q = step mm / den: step 1 (+ rho1, below), the product 1, the quotient 1, the final subtraction 1, and den =
+#       sqrt(vv) rs2 + eps, a sum of positive terms: half of v's 6, sqrtf 1, rs2 2 (+ rho2 / 2), the product 1, the sum 1 = 8: (12 u + rho1 + rho2 / 2) |q|.
+#       And the error already in mm, an ABSOLUTE one because of the cancellation: (lr / bc1) / den times m's bound.
+#
+# The bias corrections are a documented property of the design: clip_coef_kernel computes 1 - powf(beta, t) in fp32.  powf may be off by POWF_ULPS = 2 units in
+# the last place of beta^t (the HIP math tables give powf 1 ulp; 2 allows for one more, as the file doubles every undocumented rounding), the subtraction
+# rounds once more, so |ctl[5 | 6] - (1 - beta^t)| <= bc_allowed(beta, t) = 2 ulp(beta^t) + u (1 - beta^t), and rho = bc_allowed / (1 - beta^t) is what the
+# step size (rho1) and, through the square root, the denominator (rho2 / 2) inherit.  At t = 2, 3 and beta2 = 0.999 the cancellation makes rho2 about 2000 u
+# (1 - beta2^2 = 0.002, ulp(0.998) = 2^-24 = 2 u), at t >= 1000 it is below 8 u.  The GPU test holds ctl[5] and ctl[6] themselves to bc_allowed.
+#
+# Averaged weights (mode 1): e = fmaf(d, e0, (1 - d) * w) on the master the launch wrote: EMA_ROUNDINGS = 3 (1 - d, the product, the fma), each of a value no
+# larger than max(|e0|, |w|) — the recurrence bound tests/test_gpu_train_ema.py sums over its steps (ema_step_bound, moved here from there).
+#
+# Sum of squares: every term is >= 0, so the bound is relative: (the longest chain of roundings a term passes) u.  sumsq_kernel: the square 1, the per-thread
+# loop ceil(n / 4 / threads) adds, the folds of the four accumulators and of the four lanes 2 + 2, the n % 4 tail 3 more adds on thread 0, block_sum 6 + 4
+# (a 64-lane tree, then the four waves in order); clip_coef_kernel: ceil(parts / 256) adds and block_sum again: sumsq_depth(n).  The norm takes half of that
+# (the square root) + sqrtf + the product with inv_scale; the clipped coefficient the norm's + the sum with 1e-6, the quotient and the product.
+# =======================================================================================================================================================
+SECOND_ORDER = 1.0 + 2.0 ** -10
+F32_MIN_SUB = 2.0 ** -149
+POWF_ULPS = 2
+EMA_ROUNDINGS = 3             # DESIGN.md 7 "Averaged weights"
+ERR_NONFINITE = 4             # csrc/common.h
+ADAM_BETAS, ADAM_EPS = (0.9, 0.999), 1e-7                      # oracle/ref_cpu.py adamw_reference
+ADAM_SETTINGS = {"base": dict(lr=1e-3, wd=0.01), "nowd": dict(lr=1e-2, wd=0.0)}
+ADAM_INV_SCALE = 2.0 ** -16                                    # loss scale 2^16, folded into the coefficient
+ADAM_COEFS = ("unclipped", "clipped")                          # max_norm = 0 (ctl[1] = inv_scale bit for bit) / max_norm = 0.9 of the norm (coefficient near 0.9 inv_scale)
+ADAM_STARTS = ("fresh", 1000, 100000)                          # zero moments and t = 1, 2, 3 in sequence / non-trivial moments and ctl[4] = t - 1
+ADAM_FRESH_STEPS = 3
+# (kind, R, C): "gemm" has both images, "gemm_nowt" no W^T (the patch embedding's form), "f32" trains in place (w16 null), "f32_strided" is a view with ldp = 1024
+# whose 24-float gaps hold NaN.  GEMM and fp32 parameters alternate, so an item's parameter index is never its position in a sorted list.
+ADAM_PARAMS = [("gemm", 64, 64), ("f32", 1, 1), ("gemm", 128, 192), ("f32", 1, 4095), ("gemm", 65, 64), ("f32", 1, 4096), ("gemm", 16, 64), ("f32", 1, 4097),
+               ("gemm", 64, 68), ("f32", 1, 8193), ("gemm", 256, 100), ("f32_strided", 3, 1000), ("gemm", 70, 66), ("gemm_nowt", 65, 64)]
+ADAM_STRIDED_LDP = 1024
+# "one arithmetic": the same 16 x 64 values in an interior tile (parameter 2, tile (1, 1)), an element-wise tile (parameter 12: C % 4 != 0) and an fp32 run
+# (parameter 7, elements 0 .. 1023) of the same launch
+ADAM_PROBE = {"interior": (2, slice(64, 80), slice(64, 128)), "edge": (12, slice(0, 16), slice(0, 64)), "run": (7, slice(0, 1), slice(0, 1024))}
+ADAM_BEYOND_F16 = (70000.0, -100000.0, 65520.0, -65504.0)      # masters at elements 3 .. 6 of every GEMM weight: clamped in the fp16 image, never inf
+
+
+def f32(x):
+    return float(np.float32(x))
+
+
+def round_up(a, b):
+    return (a + b - 1) // b * b
+
+
+def ulp32(x):
+    """one unit in the last place of the fp32 number nearest to x > 0 (0 where x underflows fp32 altogether)"""
+    return 2.0 ** max(math.floor(math.log2(x)) - 23, -149) if x > 0.0 else 0.0
+
+
+def bc_ref(beta, t):
+    return 1.0 - f32(beta) ** t
+
+
+def bc_allowed(beta, t):
+    return POWF_ULPS * ulp32(f32(beta) ** t) + EPS32 * bc_ref(beta, t)
+
+
+def bc_emulate(beta, t, ulps=0):
+    """1 - powf(beta, t) in fp32 with the powf that is as far above (ulps > 0) or below (ulps < 0) the true power as |ulps| units in the last place allow"""
+    true = f32(beta) ** t
+    p = np.float32(true)
+    while ulps:
+        q = np.nextafter(p, np.float32(2.0 if ulps > 0 else -1.0), dtype=np.float32)
+        if abs(float(q) - true) > abs(ulps) * ulp32(true):
+            break
+        p = q
+    return float(np.float32(1.0) - p)
+
+
+def ema_step_bound(e_prev, w):
+    """one applied step of e = fmaf(d, e_prev, (1 - d) w) against the fp64 recurrence on the same fp32 masters"""
+    return EMA_ROUNDINGS * EPS32 * torch.maximum(e_prev.double().abs(), w.double().abs())
+
+
+def adam_reference(w0, g, m0, v0, coef, t, lr, wd):
+    """-> dict of fp64 tensors: the references w, m, v and the bounds tol_w, tol_m, tol_v (the head comment of this section)"""
+    b1, b2, eps, lr, wd, coef = f32(ADAM_BETAS[0]), f32(ADAM_BETAS[1]), f32(ADAM_EPS), f32(lr), f32(wd), f32(coef)
+    w0, g, m0, v0 = (x.double() for x in (w0, g, m0, v0))
+    gc = g * coef
+    m = b1 * m0 + (1.0 - b1) * gc
+    v = b2 * v0 + (1.0 - b2) * gc * gc
+    bc1, bc2 = bc_ref(b1, t), bc_ref(b2, t)
+    den = v.sqrt() / math.sqrt(bc2) + eps
+    q = (lr / bc1) * m / den
+    decay = 1.0 - lr * wd
+    u = EPS32 * SECOND_ORDER
+    tol_m = 4 * u * ((b1 * m0).abs() + ((1.0 - b1) * gc).abs()) + F32_MIN_SUB
+    tol_v = 6 * u * v + F32_MIN_SUB
+    rho1, rho2 = bc_allowed(b1, t) / bc1, bc_allowed(b2, t) / bc2
+    tol_w = SECOND_ORDER * (4 * EPS32 * (w0 * decay).abs() + (12 * EPS32 + rho1 + 0.5 * rho2) * q.abs() + (lr / bc1) / den * tol_m) + F32_MIN_SUB
+    return dict(w=w0 * decay - q, m=m, v=v, tol_w=tol_w, tol_m=tol_m, tol_v=tol_v)
+
+
+ADAM_WRONG = ("eps_in_sqrt", "no_sqrt_bc2", "bc_t_minus_1", "decay_after", "m_unclipped", "v_unsquared", "no_decay_f32", "run_start")
+
+
+def _fma(a, b, c):
+    """a * b + c rounded once (the product of two fp32 numbers is exact in fp64; the double rounding of the sum moves a tie in one case in 2^29)"""
+    return (a.double() * b.double() + c.double()).float()
+
+
+def adam_emulate(w0, g, m0, v0, coef, t, lr, wd, contract, pow_ulps=0, wrong=None, is_f32=False, inv_scale=ADAM_INV_SCALE):
+    """The kernel as designed, in float32 torch arithmetic (every operation rounded once; contract: every product the source leaves to the compiler fused into
+    the following sum) -> (w, m, v) fp32.  wrong: one of ADAM_WRONG, a kernel that is subtly not the design."""
+    F = lambda x: torch.tensor(x, dtype=torch.float32)
+    b1, b2, eps, lr, wd, c = (F(x) for x in (ADAM_BETAS[0], ADAM_BETAS[1], ADAM_EPS, lr, wd, coef))
+    tt = t - 1 if wrong == "bc_t_minus_1" else t
+    bc1, bc2 = F(bc_emulate(ADAM_BETAS[0], tt, pow_ulps)), F(bc_emulate(ADAM_BETAS[1], tt, pow_ulps))
+    one = F(1.0)
+    gr = g * c
+    gm = g * F(inv_scale) if wrong == "m_unclipped" else gr
+    if contract:
+        mm = _fma(b1, m0, (one - b1) * gm)
+        vv = _fma(b2, v0, (one - b2) * gr) if wrong == "v_unsquared" else _fma((one - b2) * gr, gr, b2 * v0)
+    else:
+        mm = b1 * m0 + (one - b1) * gm
+        vv = b2 * v0 + ((one - b2) * gr if wrong == "v_unsquared" else (one - b2) * gr * gr)
+    decay = one - lr * wd
+    if wrong == "no_decay_f32" and is_f32:
+        decay = one
+    step = lr / bc1
+    rs2 = one / bc2 if wrong == "no_sqrt_bc2" else one / torch.sqrt(bc2)
+    if wrong == "eps_in_sqrt":
+        den = torch.sqrt(vv * (rs2 * rs2) + eps)
+    else:
+        den = _fma(torch.sqrt(vv), rs2, eps) if contract else torch.sqrt(vv) * rs2 + eps
+    q = step * mm / den
+    if wrong == "decay_after":
+        w = (w0 - q) * decay
+    else:
+        w = _fma(w0, decay, -q) if contract else w0 * decay - q
+    if wrong == "run_start" and is_f32 and w.numel() > 4096:          # every run but the first starts one element late: elements 4096, 8192, .. are never visited
+        w, mm, vv = w.clone(), mm.clone(), vv.clone()
+        for x, x0 in ((w, w0), (mm, m0), (vv, v0)):
+            x.reshape(-1)[4096::4096] = x0.reshape(-1)[4096::4096]
+    return w, mm, vv
+
+
+def ema_emulate(e0, w, d):
+    d = torch.tensor(d, dtype=torch.float32)
+    return _fma(d, e0, (torch.tensor(1.0) - d) * w)
+
+
+class AdamParamSpec:
+    """shape and image geometry of one parameter, as gtav_dit_train_enable computes them: Cp16 = Slot::Cp = round_up(C, 64), the W image round_up(R, 128) rows
+    of it, RpT = round_up(R, 64), the W^T image round_up(C, 128) * round_up(R, 64) elements"""
+
+    def __init__(self, kind, R, C):
+        self.kind, self.R, self.C = kind, R, C
+        self.gemm, self.has_wT = kind.startswith("gemm"), kind == "gemm"
+        self.ldp = ADAM_STRIDED_LDP if kind == "f32_strided" else C
+        self.Cp16, self.RpT = (round_up(C, 64), round_up(R, 64)) if self.gemm else (0, 0)
+        self.w16_elems = round_up(R, 128) * self.Cp16
+        self.wT_elems = round_up(C, 128) * self.RpT if self.has_wT else 0
+
+
+class AdamCase:
+    """One launch over ADAM_PARAMS.  g is the SCALED gradient (what the arena holds): g inv_scale is sign x log-uniform over 1e-13 .. 1e3 (1e-12 .. 1e2 and more
+    after either coefficient), 5 % exact zeros, 10 % within a decade of eps; weights N(0, 0.02) and ADAM_BEYOND_F16; the shadow e0 = w0 + N(0, 0.01).
+    start "fresh": zero moments (a zero gradient there is the exact-zero case).  Otherwise m0 about gc (a fifth of them of the opposite sign: cancellation),
+    v0 about gc^2, and small non-zero moments under the zero gradients."""
+
+    def __init__(self, setting, coef_kind, start):
+        self.setting, self.coef_kind, self.start = setting, coef_kind, start
+        self.lr, self.wd = ADAM_SETTINGS[setting]["lr"], ADAM_SETTINGS[setting]["wd"]
+        self.params = [AdamParamSpec(*p) for p in ADAM_PARAMS]
+        self.steps = list(range(1, ADAM_FRESH_STEPS + 1)) if start == "fresh" else [start]
+        self.w0, self.g, self.m0, self.v0, self.e0 = [], [], [], [], []
+        for i, p in enumerate(self.params):
+            gen = torch.Generator().manual_seed(1000 + i)
+            n = p.R * p.C
+            r = lambda: torch.rand(n, generator=gen, dtype=torch.float64)
+            mag = 10.0 ** (r() * 16.0 - 13.0)
+            pick = r()
+            mag = torch.where(pick < 0.10, ADAM_EPS * 10.0 ** (r() - 0.5), mag)
+            mag = torch.where(pick > 0.95, torch.zeros_like(mag), mag)
+            sign = torch.where(r() < 0.5, -1.0, 1.0)
+            gc = (sign * mag).float()
+            w0 = torch.randn(n, generator=gen) * 0.02
+            if p.gemm:
+                w0[3:3 + len(ADAM_BEYOND_F16)] = torch.tensor(ADAM_BEYOND_F16)
+            if start == "fresh":
+                m0, v0 = torch.zeros(n), torch.zeros(n)
+            else:
+                flip = torch.where(r() < 0.2, -1.0, 1.0)
+                m0 = (gc.double() * (0.5 + r()) * flip).float()
+                v0 = (gc.double() ** 2 * (0.5 + 1.5 * r())).float()
+                zero = gc == 0
+                m0 = torch.where(zero, (torch.randn(n, generator=gen) * 1e-3), m0)
+                v0 = torch.where(zero, (1e-6 * (0.5 + r())).float(), v0)
+            e0 = w0 + torch.randn(n, generator=gen) * 0.01
+            g = gc * (1.0 / ADAM_INV_SCALE)                                      # (a power of two: exact)
+            for lst, x in zip((self.w0, self.g, self.m0, self.v0, self.e0), (w0, g, m0, v0, e0)):
+                lst.append(x.reshape(p.R, p.C).clone())
+        for lst in (self.w0, self.g, self.m0, self.v0, self.e0):
+            pi, rs, cs = ADAM_PROBE["interior"]
+            probe = lst[pi][rs, cs].clone()
+            for where in ("edge", "run"):
+                pj, rs2, cs2 = ADAM_PROBE[where]
+                lst[pj][rs2, cs2] = probe.reshape(lst[pj][rs2, cs2].shape)
+        for i, p in enumerate(self.params):                                      # a run boundary is never a zero gradient: the off-by-one run must show
+            if not p.gemm and p.R * p.C > 4096:
+                self.g[i].reshape(-1)[4095::4096] = 1e-3 / ADAM_INV_SCALE
+                self.g[i].reshape(-1)[4096::4096] = -2e-3 / ADAM_INV_SCALE
+        self.g_flat = torch.cat([x.reshape(-1) for x in self.g])                 # the gradient arena, parameter after parameter
+        self.norm64 = math.sqrt((self.g_flat.double() ** 2).sum().item()) * ADAM_INV_SCALE
+        self.max_norm = 0.0 if coef_kind == "unclipped" else f32(0.9 * self.norm64)
+
+    def probe(self, tensors, where):
+        pi, rs, cs = ADAM_PROBE[where]
+        return tensors[pi][rs, cs].reshape(-1)
+
+
+@functools.lru_cache(maxsize=None)
+def adam_case(setting, coef_kind, start):
+    return AdamCase(setting, coef_kind, start)
+
+
+# ---- the sum of squares ---------------------------------------------------------------------------------------------------------------------------------------
+SUMSQ_N = (1, 3, 4, 5, 2047, 2048, 2049, 8 * 2048 + 3, 2 ** 20 + 1)
+SUMSQ_SPECIAL_N = (2049 + 2, 8 * 2048 + 3)                     # n % 4 == 3: the tail is elements n - 3 .. n - 1
+SUMSQ_SPECIALS = tuple((v, where) for v in ("inf", "nan") for where in ("tail", "body"))
+
+
+def sumsq_parts(n):
+    return min(max((n + 2047) // 2048, 1), 4096)                # csrc/train.hip sumsq_parts
+
+
+def sumsq_depth(n, parts=None):
+    """the longest chain of roundings between a term and ctl[0] (the head comment of this section)"""
+    parts = sumsq_parts(n) if parts is None else parts
+    per_thread = -(-(n // 4) // (parts * 256)) if n >= 4 else 0
+    return 1 + per_thread + 4 + 3 + 10 + -(-parts // 256) + 10
+
+
+def _tree64(x):
+    """[.., 64] -> [..]: wave_sum_dpp, a balanced tree (lanes, quads, half rows, rows, row pairs, all)"""
+    while x.shape[-1] > 1:
+        x = x[..., 0::2] + x[..., 1::2]
+    return x[..., 0]
+
+
+def _block_sum(x):
+    """[blocks, 256] -> [blocks]: the 64-lane tree of every wave, then the four waves in order from 0"""
+    wv = _tree64(x.reshape(-1, 4, 64))
+    t = torch.zeros(wv.shape[0])
+    for i in range(4):
+        t = t + wv[:, i]
+    return t
+
+
+def parts_sum_emulate(part):
+    """clip_coef_kernel's sum of the partial sums: thread j adds parts j, j + 256, .. in order, then block_sum"""
+    n = part.numel()
+    pad = torch.zeros(round_up(n, 256))
+    pad[:n] = part
+    a = torch.zeros(256)
+    for row in pad.reshape(-1, 256):
+        a = a + row
+    return _block_sum(a[None])[0]
+
+
+class SumsqCase:
+    """n values, sign x log-uniform over 12 decades (1e-6 .. 1e6); ref: the fp64 sum of squares; tol: sumsq_depth(n) u ref.  special (value, where): ONE element is
+    inf or NaN, in the n % 4 tail (the last element) or in the body (element 5)"""
+
+    def __init__(self, n, special=None):
+        self.n, self.special = n, special
+        gen = torch.Generator().manual_seed(n)
+        mag = 10.0 ** (torch.rand(n, generator=gen, dtype=torch.float64) * 12.0 - 6.0)
+        self.g = (mag * torch.where(torch.rand(n, generator=gen) < 0.5, -1.0, 1.0)).float()
+        if special:
+            assert n % 4 and n > 8
+            self.g[n - 1 if special[1] == "tail" else 5] = float(special[0])
+        self.parts = sumsq_parts(n)
+        self.ref = (self.g.double() ** 2).sum().item()
+        self.tol = sumsq_depth(n) * EPS32 * SECOND_ORDER * self.ref
+
+    def emulate(self, contract=False, wrong=None):
+        """sumsq_kernel, then clip_coef_kernel's sum -> ctl[0] as a float.  wrong: "tail_dropped" / "tail_twice" """
+        n, n4, threads = self.n, self.n // 4, self.parts * 256
+        rows = -(-n4 // threads) if n4 else 0
+        g4 = torch.zeros(max(rows, 1) * threads, 4)
+        g4.reshape(-1)[:n4 * 4] = self.g[:n4 * 4]
+        g4 = g4.reshape(max(rows, 1), threads, 4)
+        idx = torch.arange(threads)
+        cnt = torch.where(idx < n4, (n4 - 1 - idx) // threads + 1, torch.zeros_like(idx))            # float4 rows of thread idx: idx, idx + threads, ..
+        acc = [torch.zeros(threads, 4) for _ in range(4)]
+        add = (lambda a, v: _fma(v, v, a)) if contract else (lambda a, v: a + v * v)
+        for k in range(rows):
+            # the unrolled loop runs while four rows are left (row k goes to accumulator k % 4 of that group), the remainder loop adds into a0
+            in_group = (k // 4 * 4 + 3 < cnt)[:, None]
+            live = (k < cnt)[:, None]
+            for j in range(4):
+                tgt = (in_group & (k % 4 == j)) | (~in_group & (j == 0))
+                acc[j] = torch.where(live & tgt, add(acc[j], g4[k]), acc[j])
+        q = (acc[0] + acc[1]) + (acc[2] + acc[3])
+        a = (q[:, 0] + q[:, 1]) + (q[:, 2] + q[:, 3])
+        tail = self.g[n4 * 4:]
+        for rep in range({"tail_dropped": 0, "tail_twice": 2}.get(wrong, 1)):
+            for x in tail:
+                a[0] = _fma(x, x, a[0]) if contract else a[0] + x * x
+        return parts_sum_emulate(_block_sum(a.reshape(self.parts, 256))).item()
+
+
+@functools.lru_cache(maxsize=None)
+def sumsq_case(n, special=None):
+    return SumsqCase(n, special)
+
+
+# ---- the coefficient ------------------------------------------------------------------------------------------------------------------------------------------
+class ClipCase:
+    """One launch of clip_coef_kernel on caller-made partial sums.  expect(): what every word must hold afterwards.
+      skip        a non-finite sum, or ERR_F16_SAT / ERR_NONFINITE in the error word: ctl[1] = 0, ctl[2] one higher, ctl[4 .. 7] keep their bits, the two bits
+                  are cleared and every other bit of the word survives
+      applied     ctl[1] = inv_scale BIT FOR BIT when max_norm = 0 or the norm is below it, else inv_scale max_norm / (norm + 1e-6) within coef_tol; ctl[4] one
+                  higher, ctl[5] / ctl[6] within bc_allowed of 1 - beta^t, ctl[7] = train.ema_decay_at(t) bit for bit with ema_decay > 0 and untouched without
+      both        ctl[0] the sum within (chain of the parts' sum) u, ctl[3] the unscaled norm (or non-finite as the sum is)"""
+    CTL_IN = (-1.0, -2.0, 7.0, -3.0, 41.0, 0.25, 0.125, 0.0625)      # what ctl holds before: every word recognisable, 41 applied and 7 skipped steps
+    OTHER_BIT = 1                                                    # ERR_TIMESTEP: not the optimizer's to clear
+
+    def __init__(self, name, ssq, nparts, inv_scale, max_norm, err_bits=None, ema_decay=0.0, warmup=False, special=None):
+        self.name, self.inv_scale, self.max_norm, self.ema_decay, self.warmup = name, f32(inv_scale), f32(max_norm), f32(ema_decay), warmup
+        gen = torch.Generator().manual_seed(nparts)
+        share = torch.rand(nparts, generator=gen, dtype=torch.float64) + 0.1
+        self.part = (share / share.sum() * ssq).float()
+        if special:
+            self.part[nparts // 2] = float(special)
+        self.err_in = None if err_bits is None else (err_bits | self.OTHER_BIT)
+        self.ssq = self.part.double().sum().item()
+        self.finite = math.isfinite(self.ssq)
+        self.depth = -(-nparts // 256) + 10
+        self.norm = math.sqrt(self.ssq) * self.inv_scale if self.finite else self.ssq
+        self.skip = not self.finite or bool((self.err_in or 0) & (ERR_F16_SAT | ERR_NONFINITE))
+        self.t = self.CTL_IN[4] + 1
+        u = EPS32 * SECOND_ORDER
+        self.ssq_tol = self.depth * u * self.ssq if self.finite else None
+        self.norm_tol = (self.depth / 2 + 2) * u * self.norm if self.finite else None
+        self.clipped = self.finite and self.max_norm > 0.0 and self.norm + 1e-6 > self.max_norm
+        if self.clipped:
+            self.coef = self.inv_scale * self.max_norm / (self.norm + f32(1e-6))
+            self.coef_tol = (self.depth / 2 + 5) * u * self.coef
+            assert self.norm * (1 - 1e-3) > self.max_norm                    # (never a norm so close to the threshold that a rounding decides)
+        else:
+            self.coef = self.inv_scale
+            assert self.max_norm == 0.0 or not self.finite or self.norm * (1 + 1e-3) < self.max_norm
+
+    def emulate(self, wrong=None):
+        """ctl[1] of an applied step in fp32.  wrong: "no_1e-6" """
+        F = lambda x: torch.tensor(x, dtype=torch.float32)
+        norm = torch.sqrt(parts_sum_emulate(self.part)) * F(self.inv_scale)
+        if not self.max_norm > 0.0:
+            return self.inv_scale
+        den = norm if wrong == "no_1e-6" else norm + F(1e-6)
+        return (F(self.inv_scale) * torch.minimum(F(1.0), F(self.max_norm) / den)).item()
+
+
+S, N = ERR_F16_SAT, ERR_NONFINITE
+CLIP_CASES = {c.name: c for c in (
+    ClipCase("no clipping", 3.0e9, 9, 2.0 ** -16, 0.0),
+    ClipCase("below max_norm", 3.0e9, 300, 2.0 ** -16, 2.0, err_bits=0),
+    ClipCase("above max_norm", 3.0e9, 257, 2.0 ** -16, 0.25, err_bits=0, ema_decay=0.999),
+    ClipCase("above max_norm, warm-up", 3.0e9, 1, 2.0 ** -16, 0.25, ema_decay=0.9999, warmup=True),
+    ClipCase("warm-up past its end", 3.0e9, 8, 2.0 ** -16, 0.0, ema_decay=0.5, warmup=True),
+    ClipCase("small norm", 1.0e-6, 5, 1.0, 1.0e-4),                          # norm 1e-3: the one place where the 1e-6 of the denominator is a part in a thousand
+    ClipCase("inf sum", 3.0e9, 300, 2.0 ** -16, 1.0, err_bits=0, ema_decay=0.999, special="inf"),
+    ClipCase("nan sum", 3.0e9, 9, 2.0 ** -16, 0.0, special="nan"),
+    ClipCase("saturation bit", 3.0e9, 9, 2.0 ** -16, 1.0, err_bits=S, ema_decay=0.999),
+    ClipCase("non-finite bit", 3.0e9, 9, 2.0 ** -16, 0.0, err_bits=N),
+    ClipCase("both bits", 3.0e9, 9, 2.0 ** -16, 1.0, err_bits=S | N, ema_decay=0.999, warmup=True),
+)}
+del S, N

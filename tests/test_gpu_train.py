@@ -88,6 +88,34 @@ def test_adamw_step_matches_torch():
         assert rel_l2(m.grad(k), grads2[k]) < GRAD_TOL, k
 
 
+@TC.DTYPES
+def test_images_after_a_step_are_the_images_of_the_pulled_masters(dtype):
+    """One applied step, pull_weights, and a FRESH training handle loaded with those masters: the same forward bits and the same gradient arena bits for the same
+    batch.  The stepped handle computes with the W and W^T images the AdamW launch wrote, the fresh one with what the converters make of the masters: equal
+    results tie both images of the real parameter list to their masters (kernel level: tests/test_gpu_ops_optimizer.py)."""
+    sd, (x, t, a, vt), _, _, grads = TC.oracle(KW, 2, 3, True)
+    m = TC.model(KW, 2, 3, dtype)
+    m.forward_train(x, t, a)                      # builds the handle
+    flat = torch.cat([grads[k].reshape(-1) for k in sorted(k for k in sd if not k.endswith("freqs"))]) * m.loss_scale
+    m.grad_arena.copy_(flat.to(m.grad_arena.device))
+    m.adamw_step(1e-3, weight_decay=0.01, max_grad_norm=1.0)
+    applied, skipped, _ = m.train_stats()
+    assert applied and skipped == 0
+    m.pull_weights()
+    stepped = {k: v.clone() for k, v in m._sd.items()}
+    assert not torch.equal(stepped["blocks.0.s_mlp.fc1.weight"], sd["blocks.0.s_mlp.fc1.weight"])
+    fresh = TC.model(KW, 2, 3, dtype, sd=stepped)
+    out = []
+    for h in (m, fresh):
+        v = h.forward_train(x, t, a)
+        h.zero_grad()
+        h.backward_(v, vt)
+        h.check()
+        out.append((v.float().cpu().clone(), h.grad_arena.cpu().clone()))
+    assert torch.equal(out[0][0].view(torch.int32), out[1][0].view(torch.int32))
+    assert torch.equal(out[0][1].view(torch.int32), out[1][1].view(torch.int32))
+
+
 def test_overflow_skips_the_step():
     m, sd, x, t, a, vt = _setup()
     v = m.forward_train(x, t, a)

@@ -4,17 +4,18 @@ are the CPU oracle's, copied into the arena as tests/test_gpu_train.py test_adam
 
 The recurrence bound is derived, not tuned.  The device computes, per element and applied step, e' = fmaf(d, e, (1 - d) * w) in fp32 (train.hip ADAM_STEP_EMA):
 C_ROUND = 3 roundings — 1 - d, the product, the fma — each at most 2^-24 of a value no larger than max(|e|, |w|), and an error already in e is multiplied by
-d < 1.  So against the fp64 recurrence on the same fp32 masters |ema - e_K| <= C_ROUND 2^-24 sum_k max(|e_{k-1}|, |w_k|)."""
+d < 1.  So against the fp64 recurrence on the same fp32 masters |ema - e_K| <= C_ROUND 2^-24 sum_k max(|e_{k-1}|, |w_k|): one term per applied step, which is
+tests/parity_bounds.py ema_step_bound (tests/test_gpu_ops_optimizer.py holds a single launch to the same term)."""
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
+import parity_bounds as PB  # noqa: E402
 import train_cases as TC  # noqa: E402
 from train_cases import TOY_KW as KW  # noqa: E402
 
-C_ROUND = 3               # DESIGN.md 7 "Averaged weights"
-EPS = 2.0 ** -24
+assert PB.EMA_ROUNDINGS == 3         # C_ROUND: DESIGN.md 7 "Averaged weights"
 LR, WD, CLIP = 1e-3, 0.01, 1.0
 GEMM_W = "blocks.0.s_mlp.fc1.weight"          # the largest GEMM weight of the toy model, [1024][256]
 KW_EDGE = dict(KW, in_channels=4)             # 16 features per patch: x_embedder.proj.weight [256][16] and final_layer.linear.weight [16][256] are edge tiles
@@ -75,7 +76,7 @@ def _recurrence(m, e0, flat, K, decay, warmup, big):
         d = ema_decay_at(n, decay, warmup)        # float32(d_n) as a double; 1 - d below is then exact in fp64
         for k in names:
             wk = w[k].double()
-            bound[k] += C_ROUND * EPS * torch.maximum(e_ref[k].abs(), wk.abs())
+            bound[k] += PB.ema_step_bound(e_ref[k], wk)
             e_ref[k] = d * e_ref[k] + (1.0 - d) * wk
     applied, skipped, _ = m.train_stats()
     assert applied and skipped == 0
@@ -148,7 +149,7 @@ def test_skipped_step_leaves_the_shadow_and_the_count(dtype):
     bmax = 0.0
     for k in e1:
         ref = d2 * e1[k].double() + (1.0 - d2) * w2[k].double()
-        bound = C_ROUND * EPS * torch.maximum(e1[k].abs(), w2[k].abs()).double()
+        bound = PB.ema_step_bound(e1[k], w2[k])
         assert ((e2[k].double() - ref).abs() <= bound).all(), k
         if k == GEMM_W:
             bmax = float(bound.max())

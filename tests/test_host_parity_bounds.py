@@ -1,5 +1,5 @@
-"""The bounds of tests/test_gpu_ops_typed.py, (second half) of tests/test_gpu_ops_train.py and tests/test_gpu_ops_ln_pending.py and (last section) of
-tests/test_gpu_ops_attn_bwd_bounds.py, checked on the CPU (no library, no GPU): a bound is only worth asserting if a correct kernel stays inside it and a
+"""The bounds of tests/test_gpu_ops_typed.py, (second half) of tests/test_gpu_ops_train.py and tests/test_gpu_ops_ln_pending.py, of
+tests/test_gpu_ops_attn_bwd_bounds.py and (last section) of tests/test_gpu_ops_optimizer.py, checked on the CPU (no library, no GPU): a bound is only worth asserting if a correct kernel stays inside it and a
 subtly wrong one does not.  For every per-element bound, an emulation in fp32 arithmetic with a round-to-nearest-even 2-byte store must leave NO element
 outside, and the same emulation with a TRUNCATING store (a dropped guard bit, a wrong pack instruction) must put at least 1 % of the elements outside.  For
 every per-row bound, the fp64 reference rounded to the operand type — the best any kernel can return — must stay below 0.6 of the bound in its worst row.
@@ -495,3 +495,131 @@ def test_attn_spatial_bwd_saturation_preconditions(shape):
     f, w = PB.outside((got.double() - c.ref.clamp(-PB.F16_MAX, PB.F16_MAX)).abs(), c.tol)
     print(f"[bound control attn_spatial_bwd saturation {shape}] perfect kernel against the clamped reference: worst ratio {w:.3f}")
     assert f == 0.0
+
+
+# ======================================================================================================================================================
+# The bounds of tests/test_gpu_ops_optimizer.py (sumsq_kernel, clip_coef_kernel, adamw_multi_kernel).  "The kernel as designed" is a float32 emulation of the
+# source's arithmetic (tests/parity_bounds.py adam_emulate, SumsqCase.emulate, ClipCase.emulate), run with every product the source leaves to the compiler
+# rounded on its own AND fused into the following sum, and with a powf that is exact, 2 ulp low and 2 ulp high: all of them inside every bound at every case
+# the GPU file runs.  Every wrong kernel of the issue's list is outside on at least one element of at least one case; the cases that cannot show one are named.
+# ======================================================================================================================================================
+ADAM_CASES = [(s, c, st) for s in PB.ADAM_SETTINGS for c in PB.ADAM_COEFS for st in PB.ADAM_STARTS]
+ADAM_IDS = [f"{s}-{c}-{st}" for s, c, st in ADAM_CASES]
+
+
+def _ratio(got, ref, tol):
+    """worst |got - ref| / tol; a non-finite result is outside whatever the bound"""
+    r = (got.double() - ref).abs() / tol
+    return torch.where(torch.isfinite(r), r, torch.full_like(r, float("inf"))).max().item()
+
+
+def _adam_coef(c):
+    """ctl[1] as clip_coef_kernel forms it in fp32 from a correctly rounded norm"""
+    import numpy as np
+    inv, norm = np.float32(PB.ADAM_INV_SCALE), np.float32(c.norm64)
+    return float(inv) if c.max_norm == 0.0 else float(inv * min(np.float32(1.0), np.float32(c.max_norm) / (norm + np.float32(1e-6))))
+
+
+def _adam_step(c, state, coef, t, **kw):
+    """one emulated launch from `state` (w, m, v per parameter) -> (new state, worst ratio per output against the reference of the same inputs)"""
+    out, worst = [], {"w": 0.0, "m": 0.0, "v": 0.0}
+    for p, g, (w0, m0, v0) in zip(c.params, c.g, state):
+        r = PB.adam_reference(w0, g, m0, v0, coef, t, c.lr, c.wd)
+        got = PB.adam_emulate(w0, g, m0, v0, coef, t, c.lr, c.wd, is_f32=not p.gemm, **kw)
+        for k, x in zip("wmv", got):
+            worst[k] = max(worst[k], _ratio(x, r[k], r["tol_" + k]))
+        out.append(got)
+    return out, worst
+
+
+@pytest.mark.parametrize("setting,coef_kind,start", ADAM_CASES, ids=ADAM_IDS)
+def test_adam_emulation_is_inside_the_bound(setting, coef_kind, start):
+    c = PB.adam_case(setting, coef_kind, start)
+    coef = _adam_coef(c)
+    assert (coef == PB.ADAM_INV_SCALE) == (coef_kind == "unclipped") and 0.85 * PB.ADAM_INV_SCALE < coef
+    gc = torch.cat([g.reshape(-1) for g in c.g]).double().abs() * coef
+    assert gc[gc > 0].min() < 1e-12 and gc.max() > 1e2 and (gc == 0).any() and ((gc > PB.ADAM_EPS / 10 ** 0.5) & (gc < PB.ADAM_EPS * 10 ** 0.5)).sum() > 0.1 * gc.numel()
+    for contract in (False, True):
+        for ulps in (-PB.POWF_ULPS, 0, PB.POWF_ULPS):
+            state = list(zip(c.w0, c.m0, c.v0))
+            for t in c.steps:
+                e0 = [PB.ema_emulate(e, s[0], 0.999) for e, s in zip(c.e0, state)]                 # (mode 1's shadow: any e0, the master of the step before)
+                state, worst = _adam_step(c, state, coef, t, contract=contract, pow_ulps=ulps)
+                we = max(_ratio(PB.ema_emulate(e, s[0], 0.999), 0.999 * e.double() + (1.0 - PB.f32(0.999)) * s[0].double() + (PB.f32(0.999) - 0.999) * e.double(),
+                                PB.ema_step_bound(e, s[0])) for e, s in zip(e0, state))
+                print(f"[bound control adamw {setting} {coef_kind} t={t} contraction {'on' if contract else 'off'} powf {ulps:+d} ulp] kernel as designed: worst ratio "
+                      f"w {worst['w']:.3f} m {worst['m']:.3f} v {worst['v']:.3f} e {we:.3f}")
+                assert max(worst.values()) <= 1.0 and we <= 1.0, (t, contract, ulps, worst, we)
+
+
+def _adam_cannot_show(wrong, setting, coef_kind, start):
+    """The cases in which a wrong kernel computes what the design computes, or differs by less than the design's own fp32 rounding allows:
+      m_unclipped   without clipping the coefficient IS inv_scale
+      no_decay_f32, decay_after   wd = 0: there is no decay to misplace
+      decay_after   a fresh start: the misplaced decay moves the update by lr wd = 1e-5 of itself, and at t = 1 the fp32 bias correction 1 - powf(0.999, 1) alone
+                    is allowed 2 ulp of 0.999 in 0.001, which is 6e-5 of the update
+      bc_t_minus_1, no_sqrt_bc2   t = 100000: 0.999^t is below 1e-43, both corrections are 1 for either t, and so is the square root"""
+    return (wrong == "m_unclipped" and coef_kind == "unclipped") or (wrong in ("no_decay_f32", "decay_after") and setting == "nowd") or \
+           (wrong == "decay_after" and start == "fresh") or (wrong in ("bc_t_minus_1", "no_sqrt_bc2") and start == 100000)
+
+
+@pytest.mark.parametrize("setting,coef_kind,start", ADAM_CASES, ids=ADAM_IDS)
+def test_adam_wrong_kernels_are_outside(setting, coef_kind, start):
+    c = PB.adam_case(setting, coef_kind, start)
+    coef = _adam_coef(c)
+    state = list(zip(c.w0, c.m0, c.v0))
+    for wrong in PB.ADAM_WRONG:
+        _, worst = _adam_step(c, state, coef, c.steps[0], contract=False, wrong=wrong)
+        print(f"[bound control adamw {setting} {coef_kind} {start}] WRONG ({wrong}): worst ratio w {worst['w']:.3g} m {worst['m']:.3g} v {worst['v']:.3g}")
+        assert (max(worst.values()) > 1.0) != _adam_cannot_show(wrong, setting, coef_kind, start), (wrong, worst)
+
+
+def test_adam_every_wrong_kernel_is_shown_somewhere():
+    for wrong in PB.ADAM_WRONG:
+        assert any(not _adam_cannot_show(wrong, *case) for case in ADAM_CASES), wrong
+
+
+def test_adam_probe_is_one_set_of_values():
+    """what "one arithmetic" of the GPU file relies on: the interior tile, the element-wise tile and the fp32 run hold the same inputs"""
+    c = PB.adam_case("base", "clipped", 1000)
+    for lst in (c.w0, c.g, c.m0, c.v0, c.e0):
+        a = c.probe(lst, "interior")
+        assert a.numel() == 1024 and torch.equal(a, c.probe(lst, "edge")) and torch.equal(a, c.probe(lst, "run")) and a.abs().max() > 0
+    assert [p.kind for p in c.params].count("f32_strided") == 1 and sum(not p.has_wT and p.gemm for p in c.params) == 1
+
+
+@pytest.mark.parametrize("n", PB.SUMSQ_N)
+def test_sumsq_emulation_and_dropped_tail(n):
+    """n % 4 == 0 has no tail to drop or repeat; elsewhere a tail term shows when it is more than sumsq_depth(n) 2^-24 of the sum — always at n < 4 (the sum IS the
+    tail), by the draw of the values at the larger n (printed)."""
+    c = PB.sumsq_case(n)
+    for contract in (False, True):
+        w = abs(c.emulate(contract) - c.ref) / c.tol
+        print(f"[bound control sumsq n={n} contraction {'on' if contract else 'off'}] kernel as designed: worst ratio {w:.3f} (chain of {PB.sumsq_depth(n)})")
+        assert w <= 1.0
+    for wrong in ("tail_dropped", "tail_twice"):
+        w = abs(c.emulate(wrong=wrong) - c.ref) / c.tol
+        print(f"[bound control sumsq n={n}] WRONG ({wrong}): ratio {w:.3g}")
+        if n < 4:
+            assert w > 1.0, (wrong, w)
+        if n % 4 == 0:
+            assert c.emulate(wrong=wrong) == c.emulate()
+
+
+@pytest.mark.parametrize("name", list(PB.CLIP_CASES))
+def test_clip_coefficient_bound(name):
+    """norm + 1e-6 replaced by norm: within the fp32 range it shows where the norm is small — `small norm` (1e-3, a part in a thousand).  At the training-sized norms
+    of the other clipped cases 1e-6 is a part in a million of the norm, about twice their bound: printed, not required."""
+    c = PB.CLIP_CASES[name]
+    if c.skip:
+        assert c.err_in is None or c.err_in & PB.ClipCase.OTHER_BIT
+        return
+    got = c.emulate()
+    if not c.clipped:
+        assert got == c.coef == c.inv_scale
+        return
+    w, ww = abs(got - c.coef) / c.coef_tol, abs(c.emulate("no_1e-6") - c.coef) / c.coef_tol
+    print(f"[bound control clip_coef {name}] kernel as designed: ratio {w:.3f}; WRONG (norm + 1e-6 -> norm): ratio {ww:.3g}")
+    assert w <= 1.0
+    if name == "small norm":
+        assert ww > 100.0
