@@ -29,6 +29,16 @@ def rel_l2_logged(a, b, what="", tag="rel_l2"):
     return v
 
 
+def assert_declared_plan(family, *args):
+    """Before a launch of one of the non-GEMM families: the problem is a row of the declared table (tests/parity_bounds.py DECLARED_PLANS; a KeyError names one
+    that is not) and the library in THIS process plans it as declared — the instantiation and the launch form tests/test_host_op_coverage.py counted."""
+    import parity_bounds as PB
+    declared = PB.declared_plan(family, args)
+    got = PB.query_plan(L.load(), family, args)
+    assert got == declared, f"{family} {args}: the library plans {got}, the table declares {declared}"
+    return declared
+
+
 def tiled_index(R, K):
     """Offsets (in halves) of element (r, k) in the GEMM's tile-major operand layout (csrc/common.h tiled_off)."""
     r = torch.arange(R)[:, None]

@@ -1,7 +1,8 @@
 """Inputs, fp64 references, error bounds and fp32 emulations of the operand-typed kernels, shared by tests/test_gpu_ops_typed.py (the kernels, on a GPU) and
 tests/test_host_parity_bounds.py (the bounds themselves, on the CPU).  Pure torch: nothing here loads the library.  The second half of the file holds the same
 for the backward-only training kernels (tests/test_gpu_ops_train.py), then the deferred-residual LayerNorm (tests/test_gpu_ops_ln_pending.py), the four
-attention backward kernels (tests/test_gpu_ops_attn_bwd_bounds.py) and last the optimizer step (tests/test_gpu_ops_optimizer.py), each with its own head comment.
+attention backward kernels (tests/test_gpu_ops_attn_bwd_bounds.py), the optimizer step (tests/test_gpu_ops_optimizer.py), the skinny fp32 GEMM (tests/test_gpu_ops.py)
+and last the declared launch plans of every op-level parity problem (tests/test_host_op_coverage.py), each with its own head comment.
 
 None of the bounds is taken from the code under test.  u is the unit roundoff of the operand type, 2^-11 for fp16 and 2^-8 for bf16.
 
@@ -272,11 +273,11 @@ ATTN_NB, ATTN_HEADS = 2, 3
 
 class AttnCase:
     """q, k, v [NB][heads][S][64] in the operand type; ref [NB S][heads 64] fp64.  jump: the two dominating keys of test_attention_flash_running_max_jump.
-    prescaled: q_ps = q * log2 e / 8 rounded on the host, and the reference is the base-2 softmax of THAT q."""
+    prescaled: q_ps = q * log2 e / 8 rounded on the host, and the reference is the base-2 softmax of THAT q.  The fp64 softmax is formed one item at a time;
+    the probabilities p (what control() needs) are kept only at the default 2 x 3 items — at 256 items of S = 256 they would be 130 MB."""
 
-    def __init__(self, S, dtype, jump=None, prescaled=False):
-        NB, heads = ATTN_NB, ATTN_HEADS
-        self.S, self.dtype = S, dtype
+    def __init__(self, S, dtype, jump=None, prescaled=False, NB=ATTN_NB, heads=ATTN_HEADS):
+        self.S, self.dtype, self.NB, self.heads = S, dtype, NB, heads
         q, k, v = (rand(NB, heads, S, 64, seed=i).to(dtype) for i in (1, 2, 3))
         if jump is None:
             q = (q.float() * 1.5).to(dtype)
@@ -285,16 +286,22 @@ class AttnCase:
             k[0, 1, 70] = (q[0, 1, 150].float() * jump).to(dtype)          # and one in the second key block
             self.dominated = ((1, 2, 7), (0, 1, 150))
         self.k, self.v = k, v
-        if prescaled:
-            self.q = (q.double() * (LOG2E / 8)).to(dtype)
-            s = self.q.double() @ k.double().transpose(-1, -2)
-            p = torch.exp2(s - s.max(-1, keepdim=True).values)
-        else:
-            self.q = q
-            s = q.double() @ k.double().transpose(-1, -2) / 8.0
-            p = torch.exp(s - s.max(-1, keepdim=True).values)
-        self.p = p / p.sum(-1, keepdim=True)
-        self.ref4 = self.p @ v.double()                                        # NB heads S 64
+        self.q = (q.double() * (LOG2E / 8)).to(dtype) if prescaled else q
+        keep_p = (NB, heads) == (ATTN_NB, ATTN_HEADS)
+        ps, refs = [], []
+        for b in range(NB):
+            if prescaled:
+                s = self.q[b].double() @ k[b].double().transpose(-1, -2)
+                p = torch.exp2(s - s.max(-1, keepdim=True).values)
+            else:
+                s = q[b].double() @ k[b].double().transpose(-1, -2) / 8.0
+                p = torch.exp(s - s.max(-1, keepdim=True).values)
+            p = p / p.sum(-1, keepdim=True)
+            refs.append(p @ v[b].double())
+            if keep_p:
+                ps.append(p)
+        self.p = torch.stack(ps) if keep_p else None
+        self.ref4 = torch.stack(refs)                                          # NB heads S 64
         self.ref = self.ref4.permute(0, 2, 1, 3).reshape(NB * S, heads * 64)
 
     def control(self, requantized_q=False):
@@ -314,8 +321,15 @@ class AttnCase:
 
 
 @functools.lru_cache(maxsize=None)
-def attn_case(S, dtype, jump=None, prescaled=False):
-    return AttnCase(S, dtype, jump, prescaled)
+def _attn_case_cached(S, dtype, jump, prescaled, NB, heads):
+    return AttnCase(S, dtype, jump, prescaled, NB, heads)
+
+
+def attn_case(S, dtype, jump=None, prescaled=False, NB=ATTN_NB, heads=ATTN_HEADS):
+    """(the cases of hundreds of items are used by one test each and hold tens of MB: built, not kept)"""
+    if NB * heads > 64:
+        return AttnCase(S, dtype, jump, prescaled, NB, heads)
+    return _attn_case_cached(S, dtype, jump, prescaled, NB, heads)
 
 
 def attn_rows(x4):
@@ -327,7 +341,8 @@ def attn_rows(x4):
 TEMPORAL_TOL = 6e-4
 # (B, P, D, Tq, t0, Tmax)
 TEMPORAL_CASES = [(2, 24, 256, Tq, t0, Tmax) for (Tq, t0, Tmax) in ((5, 0, 5), (1, 4, 5), (3, 5, 8), (1, 7, 32), (1, 8, 32), (9, 3, 16), (32, 0, 32), (1, 31, 32))] + \
-                 [(2, 3, 256, 12, 0, 12)]        # 6 columns: a partial block
+                 [(2, 3, 256, 12, 0, 12)] + \
+                 [(8, 128, 256, 3, 2, 8), (8, 128, 256, 3, 5, 8)]        # 6 columns: a partial block; 1024 columns: the query frames of a window in ONE block, at 5 and 8 visible frames
 
 
 class TemporalCase:
@@ -918,6 +933,7 @@ LN_PEND_CASES = {
     "d1792": dict(D=1792, M=33, nsplit=8, mode=1, gate=False),                                    # 7 waves
     "d2048": dict(D=2048, M=130, nsplit=8, mode=0, P=26),
     "d1024_step": dict(D=1024, M=720, nsplit=4, mode=0, P=144),                                   # the batch-1 step's launch, in place, repeated
+    "d192_train": dict(D=192, M=33, nsplit=2, mode=1, gate=False, ld=200),                        # the affine form with k_save, then its k_load re-run: no product caller, the hook launches it
 }
 LN_PEND_WRONG = ("drop", "again", "gate", "bias", "tperm")
 
@@ -996,7 +1012,8 @@ ATTN_BWD_SCALES = (-10, 8)
 ATTN_BWD_SAT = [(2, 2, 32), (2, 2, 72)]                                       # fp16, sharp, dO x 2^13: dk leaves fp16, dS does not
 ATTN_BWD_SAT_SCALE = 13
 ATTN_BWD_MUTANT_MAX_S = 200
-TEMPORAL_BWD_RESIDENT = [(2, 3, 128, 1, 1), (2, 3, 128, 5, 8), (1, 3, 128, 8, 32)]      # (B, P, D, T, Tmax); P = 3: a partial block of clamped lanes
+TEMPORAL_BWD_RESIDENT = [(2, 3, 128, 1, 1), (2, 3, 128, 5, 8), (1, 3, 128, 8, 32)] + \
+                        [(2, 3, 128, T, 8) for T in (2, 3, 4, 6, 7)]      # (B, P, D, T, Tmax); P = 3: a partial block of clamped lanes; attn_temporal_bwd_kernel<TT> has one instantiation per T
 TEMPORAL_BWD_STREAM = [(2, 3, 128, 9, 9), (1, 3, 128, 17, 32), (1, 5, 256, 32, 32)]
 TEMPORAL_BWD_SHAPES = TEMPORAL_BWD_RESIDENT + TEMPORAL_BWD_STREAM
 TEMPORAL_BWD_KINDS = ("flat", "sharp", "diagonal", "first", "ladder")
@@ -1623,3 +1640,336 @@ CLIP_CASES = {c.name: c for c in (
     ClipCase("both bits", 3.0e9, 9, 2.0 ** -16, 1.0, err_bits=S | N, ema_decay=0.999, warmup=True),
 )}
 del S, N
+
+
+# =======================================================================================================================================================
+# The skinny fp32 GEMM (csrc/skinny.hip): Y = act(X W^T + bias) on v_mfma_f32_16x16x4_f32, shared by tests/test_gpu_ops.py test_skinny_f32 and
+# tests/test_host_parity_bounds.py.  Two assertions per case:
+#   per element against fp64:  |pre - ref| <= sum_bound(K, sum_k |x w|, mfma=True)  +  eps (sum_k |x w| + |b|)   (the one rounding of the bias add; no bias, no term)
+#     act = 1 (SiLU): that bound times the slope s (1 + |x| (1 - s)) >= |d/dx x sigmoid(x)| (the magnitudes SiluCase's derivative bound uses), plus SiluCase's
+#     evaluation error 10 eps |ref| + SILU_ABS.  First order, like every bound of this file.
+#   bit for bit across instantiations:  Y[m][n] depends on row m of X and row n of W only, and skinny.hip promises the same fp32 fma chain in the same order for every
+#     (FT, RT, KC) — so 64 output columns of any case equal the output of the 64-feature problem on those rows of W, which plans to (act, 1, 1, 0).
+# The chain, which skinny_emulate follows: per 32 columns of K, eight MFMAs; MFMA (h, e) adds the four products at k = kb + 16 h + 4 g + e, g = 0 .. 3, to the accumulator.
+# =======================================================================================================================================================
+# (M, N, K, act, call): call "" = contiguous rows and a bias; "ld" = ldx = K + 4 and ldy = N + 4 with NaN guard columns; "nobias" = bias == NULL (and "ld")
+SKINNY_CASES = [
+    (5, 1024, 256, 1, ""), (16, 6144, 1056, 0, "ld"), (37, 192, 1024, 1, "nobias"), (808, 6144, 1024, 0, ""), (131, 320, 1024, 1, "ld"),   # 808: the adaLN rows of a batch-8 frame; 131: a ragged last slab
+    (16, 262148, 32, 0, "ld"),        # (0, 4, 1, 0); N % 16 == 4: a partly live last wave
+    (20, 131076, 64, 1, ""),          # (1, 4, 1, 0)
+    (48, 87556, 32, 1, "ld"),         # (1, 4, 2, 0): a ragged second slab
+    (1000, 16388, 96, 0, "nobias"),   # (0, 8, 2, 0): K % 128 != 0 keeps it off the chunked path
+    (40, 65540, 256, 0, "ld"),        # (0, 4, 5, 128): two K chunks; N = 65540: the last block has one live wave and three that only stage
+    (90, 65540, 128, 0, "nobias"),    # (0, 4, 6, 128)
+    (101, 65540, 256, 0, ""),         # (0, 4, 7, 128): the batch-1 frame's row count
+    (200, 65540, 128, 0, "ld"),       # (0, 4, 6, 128): three row blocks, the last with 8 live rows
+]
+SKINNY_HOST_CASES = [(40, 68, 256, 0, True), (20, 68, 64, 1, True), (37, 132, 128, 0, False), (5, 64, 96, 1, False)]      # (M, N, K, act, bias): the CPU control's sizes
+
+
+class SkinnyCase:
+    def __init__(self, M, N, K, act, bias=True):
+        self.M, self.N, self.K, self.act = M, N, K, act
+        self.x, self.w = rand(M, K, seed=1), rand(N, K, seed=2, scale=1 / math.sqrt(K))
+        self.b = rand(N, seed=3) if bias else None
+        x, w = self.x.double(), self.w.double()
+        pre, mag = x @ w.t(), x.abs() @ w.abs().t()
+        tol = sum_bound(K, mag, mfma=True)
+        if bias:
+            pre = pre + self.b.double()
+            tol = tol + EPS32 * (mag + self.b.double().abs())
+        del mag
+        if act:
+            s, s1 = torch.sigmoid(pre), torch.sigmoid(-pre)
+            self.ref = pre * s
+            self.tol = s * (1.0 + pre.abs() * s1) * tol + 10 * EPS32 * self.ref.abs() + SILU_ABS
+        else:
+            self.ref, self.tol = pre, tol
+
+    def windows(self, ft):
+        """first columns of the three 64-column windows of the bit-equality check: the first block, a block boundary inside N (blocks are 64 FT features wide; the
+        middle of N where there is one block only), the last 64 columns with the ragged tail"""
+        N = self.N
+        mid = 64 * ft - 32 if N >= 64 * ft + 32 else max(0, (N // 2 - 32) // 4 * 4)
+        return sorted({0, mid, N - 64})
+
+
+def skinny_emulate(x, w, b, act, wrong=None):
+    """the kernel's chain in fp32 arithmetic.  wrong: "chunk" = the last 128 columns of K left out (a dropped last K chunk), "bias2" = the bias added twice"""
+    M, K = x.shape
+    N = w.shape[0]
+    if wrong == "chunk":
+        K -= 128
+    xr, wr = x[:, :K].reshape(M, K // 32, 2, 4, 4), w[:, :K].reshape(N, K // 32, 2, 4, 4)      # [..][kb][h][g][e]
+    acc = torch.zeros(M, N)
+    for kb in range(K // 32):
+        for h in range(2):
+            for e in range(4):
+                p = xr[:, None, kb, h, :, e] * wr[None, :, kb, h, :, e]
+                acc = acc + (((p[..., 0] + p[..., 1]) + p[..., 2]) + p[..., 3])
+    if b is not None:
+        acc = acc + b
+        if wrong == "bias2":
+            acc = acc + b
+    return acc / (1.0 + torch.exp(-acc)) if act else acc
+
+
+def skinny_case(M, N, K, act, bias=True):
+    """(not kept: the large cases hold hundreds of MB of fp64)"""
+    return SkinnyCase(M, N, K, act, bias)
+
+
+# =======================================================================================================================================================
+# The declared launch plans.  Every instantiation a non-GEMM launcher can pick computes the same result, so a parity test cannot see which one it ran; and a
+# kernel that no parity test ever runs is compared with nothing.  op_rows() lists every op-level parity problem of the families of csrc/launch_plan.h — the
+# tables above as they are, and the lists that stood inline in tests/test_gpu_ops.py — each with the arguments of gtav_op_launch_plan and the plan it is
+# DECLARED to produce: the instantiation (family number of LaunchFamily, a, b, c, d) and, for spatial and temporal attention, the launch form.
+#   tests/test_host_op_coverage.py (CPU): the library returns the declared plan for every row; per family the declared instantiations are the product list of
+#     launch_plan.h but for a literal list of exceptions; every launch form occurs on every instantiation that can take it.
+#   The GPU tests take their problems from these tables only and call helpers.assert_declared_plan before a launch: a problem that is not declared fails there,
+#     and so does a library on the GPU machine that plans otherwise than the CPU test proved.
+# Launch forms.  One-pass spatial kernel: "qsplit=1" (one block per (frame, head): from 512 pairs on) / "qsplit>1" (the query tiles split over grid y); NK = 2 and 4
+# have at most four query tiles and never split.  Register-resident temporal kernel: "one" (Tq = 1), "split" (one block per query frame: fewer than 1024
+# columns), "loop" (Tq > 1 in one block: 1024 columns or more).  Every other kernel has one form, None.
+# =======================================================================================================================================================
+LN_OPS_SHAPES = [(128, 96), (256, 96), (512, 96), (1024, 96), (2048, 160), (1024, 2304), (1024, 1027), (1024, 46080)]      # tests/test_gpu_ops.py test_layernorm_kernels: (D, M); 46 080: the batched VAE's rows
+LN_LARGE_MEAN_D, LN_LARGE_MEAN_M = (128, 1024), 64
+# every descriptor tests/test_gpu_ops_ln_pending.py launches: (case, slabs, output row permutation, k_save, k_load)
+LN_PEND_LAUNCHES = [(n, 1, 0, 0, 0) for n in ("d64", "d192", "d1280", "d1792", "d2048", "d1024_step", "d1024_train")] + \
+                   [("d256_rows", 1, 1, 0, 0), ("d256_rows", 1, 0, 0, 0), ("d1280_tperm", 1, 1, 0, 0), ("d1280_tperm", 1, 0, 0, 0), ("d256_tperm", 0, 1, 0, 0), ("d256_tperm", 0, 0, 0, 0),
+                    ("d1024_train", 1, 0, 1, 0), ("d1024_train", 0, 0, 0, 1), ("d192_train", 1, 0, 1, 0), ("d192_train", 1, 0, 0, 0), ("d192_train", 0, 0, 0, 1), ("sat", 1, 0, 0, 0)]
+ATTN_PRESCALED_S = [200, 576]
+# (NB, heads, S, prescaled) beyond ATTN_S at 2 x 3: what each selects is declared below
+ATTN_EXTRA = [(2, 3, 40, 0), (2, 3, 104, 0), (2, 3, 184, 0), (2, 3, 184, 1), (2, 3, 256, 1),                # NK = 4, NK = 8, <3,3,1,*>, <2,3,0,1>
+              (64, 4, 256, 0), (64, 4, 256, 1), (64, 4, 200, 0), (64, 4, 200, 1),                           # NQT = 4: a padding tie once NB heads nqb >= 512
+              (128, 4, 72, 0), (128, 4, 104, 0), (128, 4, 144, 0)]                                          # qsplit == 1: 512 (frame, head) pairs, the batch-8 launch
+ATTN_OPS_SHAPES = [(5, 16, 144), (2, 16, 576), (3, 4, 32), (1, 2, 72), (1, 2, 200), (3, 8, 256), (1, 3, 328), (5, 16, 576), (1, 2, 1152)]    # tests/test_gpu_ops.py test_attention_spatial
+ATTN_OPS_SPIKE = (1, 1, 144)
+ATTN_OPS_JUMP = [(576, 4.0), (576, 0.45), (200, 4.0)]                                                        # (S, jump) at 2 x 3
+TEMPORAL_OPS_GEOMETRY, TEMPORAL_OPS_WINDOWS = (2, 24, 256, 5), [(5, 0), (1, 4), (2, 1), (1, 0)]             # tests/test_gpu_ops.py test_attention_temporal: (B, P, D, Tmax), (Tq, t0)
+ATTN_BWD_OPS_SHAPES = [(3, 2, 144), (2, 4, 32), (1, 1, 160)]                                                 # tests/test_gpu_ops.py test_attention_spatial_backward_mfma
+LN_BWD_LARGE_MEAN = [(256, 2, 24), (1024, 2, 24)]
+
+OP_KIND = {"layernorm": 0, "attn_spatial": 1, "attn_temporal": 2, "attn_spatial_bwd": 3, "attn_temporal_bwd": 4, "skinny": 5, "gemm_tn_f32": 6, "gemm_nn_f32": 7,
+           "ada_bwd_dx": 8, "ln_mod_bwd_fused": 9}
+LF_ATTN_1P, LF_ATTN_T = 2, 4            # csrc/launch_plan.h LaunchFamily: the two kernels with more than one launch form
+
+
+def op_problems():
+    """(family, arguments of gtav_op_launch_plan, the table the problem comes from), one per problem and table"""
+    out = []
+    for D, M in LN_SHAPES + LN_OPS_SHAPES:
+        out += [("layernorm", (mode, M, D, 0, 0, 0, 0), "LN_SHAPES / LN_OPS_SHAPES") for mode in (0, 1)]
+    out += [("layernorm", (1, LN_LARGE_MEAN_M, D, 0, 0, 0, 0), "LN_LARGE_MEAN_D") for D in LN_LARGE_MEAN_D]
+    for name, slabs, perm, k_save, k_load in LN_PEND_LAUNCHES:
+        c = dict(D=64, M=8, mode=0) if name == "sat" else LN_PEND_CASES[name]
+        out.append(("layernorm", (c["mode"], c["M"], c["D"], slabs, perm, k_save, k_load), "LN_PEND_LAUNCHES"))
+    out += [("attn_spatial", (ATTN_NB, ATTN_HEADS, S, 0), "ATTN_S") for S in ATTN_S]
+    out += [("attn_spatial", (ATTN_NB, ATTN_HEADS, S, 1), "ATTN_PRESCALED_S") for S in ATTN_PRESCALED_S]
+    out += [("attn_spatial", a, "ATTN_EXTRA") for a in ATTN_EXTRA]
+    out += [("attn_spatial", a + (0,), "ATTN_OPS_SHAPES") for a in ATTN_OPS_SHAPES + [ATTN_OPS_SPIKE]]
+    out += [("attn_spatial", (ATTN_NB, ATTN_HEADS, S, 0), "ATTN_OPS_JUMP") for S in sorted({s for s, _ in ATTN_OPS_JUMP})]
+    out += [("attn_temporal", a, "TEMPORAL_CASES") for a in TEMPORAL_CASES]
+    B, P, D, Tmax = TEMPORAL_OPS_GEOMETRY
+    out += [("attn_temporal", (B, P, D, Tq, t0, Tmax), "TEMPORAL_OPS_WINDOWS") for Tq, t0 in TEMPORAL_OPS_WINDOWS]
+    out += [("attn_spatial_bwd", a, "ATTN_BWD_SHAPES / ATTN_BWD_OPS_SHAPES") for a in ATTN_BWD_SHAPES + ATTN_BWD_OPS_SHAPES]
+    out += [("attn_temporal_bwd", (B, P, D, T), "TEMPORAL_BWD_SHAPES") for B, P, D, T, _ in TEMPORAL_BWD_SHAPES]
+    out += [("skinny", (M, N, K, act), "SKINNY_CASES") for M, N, K, act, _ in SKINNY_CASES]
+    out += [("gemm_tn_f32", a[:3], "GEMM_TN_F32_*") for a in GEMM_TN_F32_MFMA + GEMM_TN_F32_VALU]
+    out += [("gemm_nn_f32", a, "GEMM_NN_F32") for a in GEMM_NN_F32]
+    out += [("ada_bwd_dx", a, "ADA_BWD_*") for a in ADA_BWD_MFMA + ADA_BWD_VALU]
+    out += [("ln_mod_bwd_fused", (f, P, D), "LN_BWD_SHAPES / LN_BWD_LARGE_MEAN") for D, f, P in LN_BWD_SHAPES + LN_BWD_LARGE_MEAN if D in LN_BWD_FUSED_D]
+    seen, rows = set(), []
+    for r in out:
+        if r[:2] not in seen:
+            seen.add(r[:2])
+            rows.append(r)
+    return rows
+
+
+def plan_form(family, args, plan12):
+    """the launch form of a plan (the twelve integers of gtav_op_launch_plan), None for a kernel that has one form only"""
+    if family == "attn_spatial" and plan12[0] == LF_ATTN_1P:
+        return "qsplit=1" if plan12[9] == 1 else "qsplit>1"
+    if family == "attn_temporal" and plan12[0] == LF_ATTN_T:
+        return "one" if args[3] == 1 else "split" if plan12[9] == 1 else "loop"
+    return None
+
+
+def query_plan(lib, family, args):
+    """gtav_op_launch_plan of `lib` (a ctypes library that exports it) -> ((family number, a, b, c, d), form)"""
+    import ctypes
+    out = (ctypes.c_int32 * 12)()
+    rc = lib.gtav_op_launch_plan(OP_KIND[family], *(tuple(args) + (0,) * (7 - len(args))), out)
+    assert rc == 0, (family, args, "refused")
+    return tuple(out[:5]), plan_form(family, args, list(out))
+
+
+# (family, arguments) -> ((family number, a, b, c, d), form).  Written down, not computed: a planner rule that moves shows here, in a row that names what it
+# was meant to run.  The comments name the kernel of each group.
+DECLARED_PLANS = {
+    # ---- layernorm
+    ("layernorm", (0, 96, 128, 0, 0, 0, 0)): ((1, 0, 0, 0, 0), None),
+    ("layernorm", (1, 96, 128, 0, 0, 0, 0)): ((1, 1, 0, 0, 0), None),
+    ("layernorm", (0, 96, 256, 0, 0, 0, 0)): ((0, 0, 1, 0, 0), None),
+    ("layernorm", (1, 96, 256, 0, 0, 0, 0)): ((0, 1, 1, 0, 0), None),
+    ("layernorm", (0, 1027, 1024, 0, 0, 0, 0)): ((0, 0, 4, 0, 0), None),
+    ("layernorm", (1, 1027, 1024, 0, 0, 0, 0)): ((0, 1, 4, 0, 0), None),
+    ("layernorm", (0, 160, 2048, 0, 0, 0, 0)): ((0, 0, 8, 0, 0), None),
+    ("layernorm", (1, 160, 2048, 0, 0, 0, 0)): ((0, 1, 8, 0, 0), None),
+    ("layernorm", (0, 96, 1280, 0, 0, 0, 0)): ((1, 0, 0, 0, 0), None),
+    ("layernorm", (1, 96, 1280, 0, 0, 0, 0)): ((1, 1, 0, 0, 0), None),
+    ("layernorm", (0, 33, 1792, 0, 0, 0, 0)): ((1, 0, 0, 0, 0), None),
+    ("layernorm", (1, 33, 1792, 0, 0, 0, 0)): ((1, 1, 0, 0, 0), None),
+    ("layernorm", (0, 96, 512, 0, 0, 0, 0)): ((0, 0, 2, 0, 0), None),
+    ("layernorm", (1, 96, 512, 0, 0, 0, 0)): ((0, 1, 2, 0, 0), None),
+    ("layernorm", (0, 96, 1024, 0, 0, 0, 0)): ((0, 0, 4, 0, 0), None),
+    ("layernorm", (1, 96, 1024, 0, 0, 0, 0)): ((0, 1, 4, 0, 0), None),
+    ("layernorm", (0, 2304, 1024, 0, 0, 0, 0)): ((0, 0, 4, 0, 0), None),
+    ("layernorm", (1, 2304, 1024, 0, 0, 0, 0)): ((0, 1, 4, 0, 0), None),
+    ("layernorm", (0, 46080, 1024, 0, 0, 0, 0)): ((0, 0, 4, 0, 0), None),
+    ("layernorm", (1, 46080, 1024, 0, 0, 0, 0)): ((0, 1, 4, 0, 0), None),
+    ("layernorm", (1, 64, 128, 0, 0, 0, 0)): ((1, 1, 0, 0, 0), None),
+    ("layernorm", (1, 64, 1024, 0, 0, 0, 0)): ((0, 1, 4, 0, 0), None),
+    ("layernorm", (0, 40, 64, 1, 0, 0, 0)): ((1, 0, 1, 0, 0), None),
+    ("layernorm", (1, 33, 192, 1, 0, 0, 0)): ((1, 1, 1, 0, 0), None),
+    ("layernorm", (0, 96, 1280, 1, 0, 0, 0)): ((1, 0, 1, 0, 0), None),
+    ("layernorm", (1, 33, 1792, 1, 0, 0, 0)): ((1, 1, 1, 0, 0), None),
+    ("layernorm", (0, 130, 2048, 1, 0, 0, 0)): ((1, 0, 1, 0, 0), None),
+    ("layernorm", (0, 720, 1024, 1, 0, 0, 0)): ((1, 0, 1, 0, 0), None),
+    ("layernorm", (0, 300, 1024, 1, 0, 0, 0)): ((1, 0, 1, 0, 0), None),
+    ("layernorm", (0, 160, 256, 1, 1, 0, 0)): ((1, 0, 1, 0, 0), None),
+    ("layernorm", (0, 160, 256, 1, 0, 0, 0)): ((1, 0, 1, 0, 0), None),
+    ("layernorm", (0, 96, 1280, 1, 1, 0, 0)): ((1, 0, 1, 0, 0), None),
+    ("layernorm", (0, 144, 256, 0, 1, 0, 0)): ((1, 0, 0, 0, 0), None),
+    ("layernorm", (0, 144, 256, 0, 0, 0, 0)): ((0, 0, 1, 0, 0), None),
+    ("layernorm", (0, 300, 1024, 1, 0, 1, 0)): ((1, 0, 1, 1, 0), None),
+    ("layernorm", (0, 300, 1024, 0, 0, 0, 1)): ((1, 0, 0, 2, 0), None),
+    ("layernorm", (1, 33, 192, 1, 0, 1, 0)): ((1, 1, 1, 1, 0), None),
+    ("layernorm", (1, 33, 192, 0, 0, 0, 1)): ((1, 1, 0, 2, 0), None),
+    ("layernorm", (0, 8, 64, 1, 0, 0, 0)): ((1, 0, 1, 0, 0), None),
+    # ---- attn_spatial
+    ("attn_spatial", (2, 3, 32, 0)): ((2, 4, 2, 0, 0), 'qsplit=1'),
+    ("attn_spatial", (2, 3, 72, 0)): ((2, 4, 6, 0, 0), 'qsplit>1'),
+    ("attn_spatial", (2, 3, 144, 0)): ((2, 4, 10, 0, 0), 'qsplit>1'),
+    ("attn_spatial", (2, 3, 200, 0)): ((3, 2, 3, 1, 0), None),
+    ("attn_spatial", (2, 3, 256, 0)): ((3, 2, 3, 0, 0), None),
+    ("attn_spatial", (2, 3, 576, 0)): ((3, 3, 3, 0, 0), None),
+    ("attn_spatial", (2, 3, 200, 1)): ((3, 2, 3, 1, 1), None),
+    ("attn_spatial", (2, 3, 576, 1)): ((3, 3, 3, 0, 1), None),
+    ("attn_spatial", (2, 3, 40, 0)): ((2, 4, 4, 0, 0), 'qsplit=1'),
+    ("attn_spatial", (2, 3, 104, 0)): ((2, 4, 8, 0, 0), 'qsplit>1'),
+    ("attn_spatial", (2, 3, 184, 0)): ((3, 3, 3, 1, 0), None),
+    ("attn_spatial", (2, 3, 184, 1)): ((3, 3, 3, 1, 1), None),
+    ("attn_spatial", (2, 3, 256, 1)): ((3, 2, 3, 0, 1), None),
+    ("attn_spatial", (64, 4, 256, 0)): ((3, 4, 2, 0, 0), None),
+    ("attn_spatial", (64, 4, 256, 1)): ((3, 4, 2, 0, 1), None),
+    ("attn_spatial", (64, 4, 200, 0)): ((3, 4, 2, 1, 0), None),
+    ("attn_spatial", (64, 4, 200, 1)): ((3, 4, 2, 1, 1), None),
+    ("attn_spatial", (128, 4, 72, 0)): ((2, 4, 6, 0, 0), 'qsplit=1'),
+    ("attn_spatial", (128, 4, 104, 0)): ((2, 4, 8, 0, 0), 'qsplit=1'),
+    ("attn_spatial", (128, 4, 144, 0)): ((2, 4, 10, 0, 0), 'qsplit=1'),
+    ("attn_spatial", (5, 16, 144, 0)): ((2, 4, 10, 0, 0), 'qsplit>1'),
+    ("attn_spatial", (2, 16, 576, 0)): ((3, 3, 3, 0, 0), None),
+    ("attn_spatial", (3, 4, 32, 0)): ((2, 4, 2, 0, 0), 'qsplit=1'),
+    ("attn_spatial", (1, 2, 72, 0)): ((2, 4, 6, 0, 0), 'qsplit>1'),
+    ("attn_spatial", (1, 2, 200, 0)): ((3, 2, 3, 1, 0), None),
+    ("attn_spatial", (3, 8, 256, 0)): ((3, 2, 3, 0, 0), None),
+    ("attn_spatial", (1, 3, 328, 0)): ((3, 2, 3, 1, 0), None),
+    ("attn_spatial", (5, 16, 576, 0)): ((3, 3, 3, 0, 0), None),
+    ("attn_spatial", (1, 2, 1152, 0)): ((3, 2, 3, 0, 0), None),
+    ("attn_spatial", (1, 1, 144, 0)): ((2, 4, 10, 0, 0), 'qsplit>1'),
+    # ---- attn_temporal
+    ("attn_temporal", (2, 24, 256, 5, 0, 5)): ((4, 5, 0, 0, 0), 'split'),
+    ("attn_temporal", (2, 24, 256, 1, 4, 5)): ((4, 5, 0, 0, 0), 'one'),
+    ("attn_temporal", (2, 24, 256, 3, 5, 8)): ((4, 8, 0, 0, 0), 'split'),
+    ("attn_temporal", (2, 24, 256, 1, 7, 32)): ((4, 8, 0, 0, 0), 'one'),
+    ("attn_temporal", (2, 24, 256, 1, 8, 32)): ((5, 1, 8, 0, 0), None),
+    ("attn_temporal", (2, 24, 256, 9, 3, 16)): ((5, 8, 4, 0, 0), None),
+    ("attn_temporal", (2, 24, 256, 32, 0, 32)): ((5, 8, 4, 0, 0), None),
+    ("attn_temporal", (2, 24, 256, 1, 31, 32)): ((5, 1, 8, 0, 0), None),
+    ("attn_temporal", (2, 3, 256, 12, 0, 12)): ((5, 8, 4, 0, 0), None),
+    ("attn_temporal", (8, 128, 256, 3, 2, 8)): ((4, 5, 0, 0, 0), 'loop'),
+    ("attn_temporal", (8, 128, 256, 3, 5, 8)): ((4, 8, 0, 0, 0), 'loop'),
+    ("attn_temporal", (2, 24, 256, 2, 1, 5)): ((4, 5, 0, 0, 0), 'split'),
+    ("attn_temporal", (2, 24, 256, 1, 0, 5)): ((4, 5, 0, 0, 0), 'one'),
+    # ---- attn_spatial_bwd
+    ("attn_spatial_bwd", (2, 2, 32)): ((6, 0, 0, 0, 0), None),
+    ("attn_spatial_bwd", (1, 2, 144)): ((6, 0, 0, 0, 0), None),
+    ("attn_spatial_bwd", (1, 1, 160)): ((6, 0, 0, 0, 0), None),
+    ("attn_spatial_bwd", (1, 1, 8)): ((7, 0, 0, 0, 0), None),
+    ("attn_spatial_bwd", (2, 2, 72)): ((7, 0, 0, 0, 0), None),
+    ("attn_spatial_bwd", (1, 2, 200)): ((7, 0, 0, 0, 0), None),
+    ("attn_spatial_bwd", (1, 1, 576)): ((7, 0, 0, 0, 0), None),
+    ("attn_spatial_bwd", (3, 2, 144)): ((6, 0, 0, 0, 0), None),
+    ("attn_spatial_bwd", (2, 4, 32)): ((6, 0, 0, 0, 0), None),
+    # ---- attn_temporal_bwd
+    ("attn_temporal_bwd", (2, 3, 128, 1)): ((8, 1, 0, 0, 0), None),
+    ("attn_temporal_bwd", (2, 3, 128, 5)): ((8, 5, 0, 0, 0), None),
+    ("attn_temporal_bwd", (1, 3, 128, 8)): ((8, 8, 0, 0, 0), None),
+    ("attn_temporal_bwd", (2, 3, 128, 2)): ((8, 2, 0, 0, 0), None),
+    ("attn_temporal_bwd", (2, 3, 128, 3)): ((8, 3, 0, 0, 0), None),
+    ("attn_temporal_bwd", (2, 3, 128, 4)): ((8, 4, 0, 0, 0), None),
+    ("attn_temporal_bwd", (2, 3, 128, 6)): ((8, 6, 0, 0, 0), None),
+    ("attn_temporal_bwd", (2, 3, 128, 7)): ((8, 7, 0, 0, 0), None),
+    ("attn_temporal_bwd", (2, 3, 128, 9)): ((9, 0, 0, 0, 0), None),
+    ("attn_temporal_bwd", (1, 3, 128, 17)): ((9, 0, 0, 0, 0), None),
+    ("attn_temporal_bwd", (1, 5, 256, 32)): ((9, 0, 0, 0, 0), None),
+    # ---- skinny
+    ("skinny", (5, 1024, 256, 1)): ((10, 1, 1, 1, 0), None),
+    ("skinny", (16, 6144, 1056, 0)): ((10, 0, 1, 1, 0), None),
+    ("skinny", (37, 192, 1024, 1)): ((10, 1, 1, 1, 0), None),
+    ("skinny", (808, 6144, 1024, 0)): ((10, 0, 4, 2, 0), None),
+    ("skinny", (131, 320, 1024, 1)): ((10, 1, 1, 1, 0), None),
+    ("skinny", (16, 262148, 32, 0)): ((10, 0, 4, 1, 0), None),
+    ("skinny", (20, 131076, 64, 1)): ((10, 1, 4, 1, 0), None),
+    ("skinny", (48, 87556, 32, 1)): ((10, 1, 4, 2, 0), None),
+    ("skinny", (1000, 16388, 96, 0)): ((10, 0, 8, 2, 0), None),
+    ("skinny", (40, 65540, 256, 0)): ((10, 0, 4, 5, 128), None),
+    ("skinny", (90, 65540, 128, 0)): ((10, 0, 4, 6, 128), None),
+    ("skinny", (101, 65540, 256, 0)): ((10, 0, 4, 7, 128), None),
+    ("skinny", (200, 65540, 128, 0)): ((10, 0, 4, 6, 128), None),
+    # ---- gemm_tn_f32
+    ("gemm_tn_f32", (5, 64, 64)): ((11, 0, 0, 0, 0), None),
+    ("gemm_tn_f32", (17, 256, 128)): ((11, 0, 0, 0, 0), None),
+    ("gemm_tn_f32", (80, 128, 64)): ((11, 0, 0, 0, 0), None),
+    ("gemm_tn_f32", (16, 64, 25)): ((12, 0, 0, 0, 0), None),
+    ("gemm_tn_f32", (5, 30, 25)): ((12, 0, 0, 0, 0), None),
+    ("gemm_tn_f32", (5, 64, 25)): ((12, 0, 0, 0, 0), None),
+    # ---- gemm_nn_f32
+    ("gemm_nn_f32", (1, 256, 64)): ((13, 16, 0, 0, 0), None),
+    ("gemm_nn_f32", (1, 256, 100)): ((13, 16, 0, 0, 0), None),
+    ("gemm_nn_f32", (17, 256, 64)): ((13, 16, 0, 0, 0), None),
+    ("gemm_nn_f32", (17, 256, 100)): ((13, 16, 0, 0, 0), None),
+    ("gemm_nn_f32", (1, 2048, 64)): ((13, 8, 0, 0, 0), None),
+    ("gemm_nn_f32", (1, 2048, 100)): ((13, 8, 0, 0, 0), None),
+    ("gemm_nn_f32", (17, 2048, 64)): ((13, 8, 0, 0, 0), None),
+    ("gemm_nn_f32", (17, 2048, 100)): ((13, 8, 0, 0, 0), None),
+    ("gemm_nn_f32", (1, 4096, 64)): ((13, 4, 0, 0, 0), None),
+    ("gemm_nn_f32", (1, 4096, 100)): ((13, 4, 0, 0, 0), None),
+    ("gemm_nn_f32", (17, 4096, 64)): ((13, 4, 0, 0, 0), None),
+    ("gemm_nn_f32", (17, 4096, 100)): ((13, 4, 0, 0, 0), None),
+    # ---- ada_bwd_dx
+    ("ada_bwd_dx", (3584, 256, 6)): ((14, 0, 0, 0, 0), None),
+    ("ada_bwd_dx", (1216, 64, 80)): ((14, 0, 0, 0, 0), None),
+    ("ada_bwd_dx", (2048, 1024, 17)): ((14, 0, 0, 0, 0), None),
+    ("ada_bwd_dx", (3584, 256, 81)): ((15, 0, 0, 0, 0), None),
+    ("ada_bwd_dx", (1216, 100, 6)): ((15, 0, 0, 0, 0), None),
+    ("ada_bwd_dx", (28672, 2048, 6)): ((15, 0, 0, 0, 0), None),
+    # ---- ln_mod_bwd_fused
+    ("ln_mod_bwd_fused", (3, 24, 256)): ((16, 1, 0, 0, 0), None),
+    ("ln_mod_bwd_fused", (2, 16, 512)): ((16, 2, 0, 0, 0), None),
+    ("ln_mod_bwd_fused", (2, 40, 1024)): ((16, 4, 0, 0, 0), None),
+    ("ln_mod_bwd_fused", (1, 17, 2048)): ((16, 8, 0, 0, 0), None),
+    ("ln_mod_bwd_fused", (2, 24, 256)): ((16, 1, 0, 0, 0), None),
+    ("ln_mod_bwd_fused", (2, 24, 1024)): ((16, 4, 0, 0, 0), None),
+}
+
+
+def op_rows():
+    """[(family, arguments, (instantiation, form), table)]: op_problems() with the declared plans; a problem without one is a KeyError that names it"""
+    return [(f, a, DECLARED_PLANS[(f, a)], src) for f, a, src in op_problems()]
+
+
+def declared_plan(family, args):
+    return DECLARED_PLANS[(family, tuple(args))]

@@ -8,7 +8,8 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from helpers import dev, gemm, pad_weight_f16, rel_l2, stream, tiled_index, to_tiled_f16, untile  # noqa: E402
+import parity_bounds as PB  # noqa: E402
+from helpers import assert_declared_plan, dev, gemm, pad_weight_f16, rel_l2, stream, tiled_index, to_tiled_f16, untile  # noqa: E402
 from gtav_amd import lib as L  # noqa: E402
 
 
@@ -163,20 +164,46 @@ def test_gemm_qkv_temporal_layout():
     assert kv[:, :t0].abs().max().item() == 0  # untouched cache slots
 
 
-@pytest.mark.parametrize("M,N,K,act", [(5, 1024, 256, 1), (16, 6144, 1056, 0), (37, 192, 1024, 1), (808, 6144, 1024, 0), (131, 320, 1024, 1)])
-def test_skinny_f32(M, N, K, act):
-    """(808 = the adaLN table rows of a batch-8 frame, 131 = a ragged last slab)"""
-    x, w, b = _rand(M, K, seed=1), _rand(N, K, scale=1 / math.sqrt(K), seed=2), _rand(N, seed=3)
-    y = torch.full((M, N), float("nan"), device=dev())
-    xd, wd, bd = x.to(dev()), w.to(dev()), b.to(dev())
-    L.check(L.load().gtav_op_skinny_f32(xd.data_ptr(), K, wd.data_ptr(), bd.data_ptr(), y.data_ptr(), N, M, N, K, act, stream()))
-    ref = x.double() @ w.double().t() + b.double()
-    if act:
-        ref = torch.nn.functional.silu(ref)
-    assert rel_l2(y, ref) < 2e-6
+def _skinny(lib, xd, ldx, wd, bd, M, N, K, act, ldy):
+    y = torch.full((M, ldy), float("nan"), device=dev())
+    L.check(lib.gtav_op_skinny_f32(xd.data_ptr(), ldx, wd.data_ptr(), L.ptr(bd), y.data_ptr(), ldy, M, N, K, act, stream()))
+    torch.cuda.synchronize()
+    return y
 
 
-@pytest.mark.parametrize("D,M", [(128, 96), (256, 96), (512, 96), (1024, 96), (2048, 160), (1024, 2304), (1024, 1027), (1024, 46080)])
+@pytest.mark.parametrize("M,N,K,act,call", PB.SKINNY_CASES, ids=[f"{m}-{n}-{k}-{a}" for m, n, k, a, _ in PB.SKINNY_CASES])
+def test_skinny_f32(M, N, K, act, call):
+    """Every instantiation of skinny_f32_kernel (tests/parity_bounds.py SKINNY_CASES says which case selects which, and why it has its shape), with and without
+    a bias, on contiguous rows and with ldx > K, ldy > N between NaN guard columns.  Two assertions (derived in parity_bounds.py, controlled on the CPU in
+    tests/test_host_parity_bounds.py): every element inside its fp64 bound; and three 64-column windows of the output — the first block, a block boundary, the
+    ragged tail — equal BIT FOR BIT to the 64-feature launch on the same rows of W, which runs the (act, 1, 1, 0) kernel: the same fp32 fma chain in the same
+    order for every (FT, RT, KC), as csrc/skinny.hip promises.  profiles/op_parity_instantiations/margins.txt holds the measured margins."""
+    lib = L.load()
+    inst, _ = assert_declared_plan("skinny", M, N, K, act)
+    c = PB.skinny_case(M, N, K, act, bias=call != "nobias")
+    pad = 0 if call == "" else 4
+    ldx, ldy = K + pad, N + pad
+    x = torch.full((M, ldx), float("nan"))
+    x[:, :K] = c.x
+    xd, wd, bd = x.to(dev()), c.w.to(dev()), (c.b.to(dev()) if c.b is not None else None)
+    y = _skinny(lib, xd, ldx, wd, bd, M, N, K, act, ldy)
+    assert torch.isnan(y[:, N:]).all(), "the guard columns behind a row of Y were written"
+    got = y[:, :N].cpu()
+    assert torch.isfinite(got).all()
+    frac, worst = PB.outside((got.double() - c.ref).abs(), c.tol)
+    name = f"skinny {M}x{N}x{K} act={act}{' ' + call if call else ''} <{inst[1]},{inst[2]},{inst[3]},{inst[4]}>"
+    print(f"[margin {name}] per element: worst error / bound {worst:.3f}")
+    assert worst <= 1.0, (name, worst, frac)
+    windows = c.windows(inst[2])
+    for n_a in windows:
+        assert PB.query_plan(lib, "skinny", (M, 64, K, act)) == ((inst[0], act, 1, 1, 0), None)
+        ys = _skinny(lib, xd, ldx, wd[n_a:n_a + 64], bd[n_a:n_a + 64] if bd is not None else None, M, 64, K, act, 64)
+        same = torch.equal(ys.view(torch.int32), y[:, n_a:n_a + 64].contiguous().view(torch.int32))
+        assert same, f"{name}: columns {n_a} .. {n_a + 63} differ in their bits from the <{act},1,1,0> launch on the same rows of W"
+    print(f"[margin {name}] bit-equal to the <{act},1,1,0> launch in the 64-column windows at {windows}")
+
+
+@pytest.mark.parametrize("D,M", PB.LN_OPS_SHAPES)
 def test_layernorm_kernels(D, M):
     """No pending update: D = 128 runs the one-block-per-row kernel, the others the one-wave-per-row kernel (NV = D / 256 float4 per lane; round 5) — 1027 rows
     leave a ragged last block, 46 080 are the batched VAE's rows (80 frames)."""
@@ -185,6 +212,7 @@ def test_layernorm_kernels(D, M):
     mod = _rand(M // P, 2 * D, seed=2)
     out = torch.zeros((M + 127) // 128 * 128, D, device=dev(), dtype=torch.float16)
     md, xd = mod.to(dev()), x.to(dev())
+    assert_declared_plan("layernorm", 0, M, D, 0, 0, 0, 0)
     L.check(L.load().gtav_op_ln_modulate(xd.data_ptr(), out.data_ptr(), M, D, md.data_ptr(), md[:, D:].data_ptr(), 2 * D, P,
                                          stream()))
     xh = torch.nn.functional.layer_norm(x, (D,), eps=1e-6)
@@ -193,26 +221,29 @@ def test_layernorm_kernels(D, M):
     assert rel_l2(untile(out, M, D).float(), ref) < 5e-4
     g, b = _rand(D, seed=3) * 0.1 + 1, _rand(D, seed=4) * 0.1
     gd, bd = g.to(dev()), b.to(dev())
+    assert_declared_plan("layernorm", 1, M, D, 0, 0, 0, 0)
     L.check(L.load().gtav_op_ln_affine(xd.data_ptr(), out.data_ptr(), M, D, gd.data_ptr(), bd.data_ptr(), stream()))
     assert rel_l2(untile(out, M, D).float(), torch.nn.functional.layer_norm(x, (D,), g, b, eps=1e-6)) < 5e-4
 
 
-@pytest.mark.parametrize("D", [128, 1024])
+@pytest.mark.parametrize("D", PB.LN_LARGE_MEAN_D)
 def test_layernorm_statistics_with_a_large_mean(D):
     """The one-pass statistics subtract the row's first element before squaring (both LayerNorm kernels): a row of 300 +- 0.02 must not lose its variance
     to cancellation (E[x^2] - E[x]^2 in fp32 would: 9e4 against 4e-4)."""
-    M = 64
+    M = PB.LN_LARGE_MEAN_M
     x = 300.0 + 0.02 * _rand(M, D, seed=5)
     g, b = _rand(D, seed=3) * 0.1 + 1, _rand(D, seed=4) * 0.1
     out = torch.zeros(128, D, device=dev(), dtype=torch.float16)
     xd, gd, bd = x.to(dev()), g.to(dev()), b.to(dev())
+    assert_declared_plan("layernorm", 1, M, D, 0, 0, 0, 0)
     L.check(L.load().gtav_op_ln_affine(xd.data_ptr(), out.data_ptr(), M, D, gd.data_ptr(), bd.data_ptr(), stream()))
     ref = torch.nn.functional.layer_norm(x.double(), (D,), g.double(), b.double(), eps=1e-6)
     assert rel_l2(untile(out, M, D).float(), ref) < 1e-3
 
 
-@pytest.mark.parametrize("NB,heads,S", [(5, 16, 144), (2, 16, 576), (3, 4, 32), (1, 2, 72), (1, 2, 200), (3, 8, 256), (1, 3, 328), (5, 16, 576), (1, 2, 1152)])
+@pytest.mark.parametrize("NB,heads,S", PB.ATTN_OPS_SHAPES)
 def test_attention_spatial(NB, heads, S):
+    assert_declared_plan("attn_spatial", NB, heads, S, 0)
     q, k, v = (_rand(NB, heads, S, 64, seed=i).half() for i in (1, 2, 3))
     q = q * 1.5
     vt = v.transpose(-1, -2).contiguous()
@@ -226,7 +257,8 @@ def test_attention_spatial(NB, heads, S):
 
 def test_attention_spatial_online_softmax_spike():
     """Forces the running max to jump in a LATER key block (the rescale branch of the online softmax)."""
-    NB, heads, S = 1, 1, 144
+    NB, heads, S = PB.ATTN_OPS_SPIKE
+    assert_declared_plan("attn_spatial", NB, heads, S, 0)
     q, k, v = (_rand(NB, heads, S, 64, seed=i).half() for i in (1, 2, 3))
     k[0, 0, 130] = q[0, 0, 7] * 4  # key 130 (third block) dominates query 7
     vt = v.transpose(-1, -2).contiguous()
@@ -239,13 +271,14 @@ def test_attention_spatial_online_softmax_spike():
     assert rel_l2(got[7], ref[7]) < 2e-3
 
 
-@pytest.mark.parametrize("S,jump", [(576, 4.0), (576, 0.45), (200, 4.0)])
+@pytest.mark.parametrize("S,jump", PB.ATTN_OPS_JUMP)
 def test_attention_flash_running_max_jump(S, jump):
     """Long sequences run the flash kernel (csrc/attention.hip attn_flash_kernel), whose reference maximum moves only when a key block's maximum
     exceeds it by more than 8 in the exponent: a key in a LATE block that dominates one query by far more than that (jump = 4: the rescale
     branch), and one that stays under the threshold (jump = 0.45: probabilities up to 2^8 against the stale maximum), against fp32 math on
     every row; 50 repetitions must agree bit for bit (the ring is refilled by LDS-DMA while it is read)."""
-    NB, heads = 2, 3
+    NB, heads = PB.ATTN_NB, PB.ATTN_HEADS
+    assert_declared_plan("attn_spatial", NB, heads, S, 0)
     q, k, v = (_rand(NB, heads, S, 64, seed=i).half() for i in (1, 2, 3))
     late = S - 9
     k[1, 2, late] = q[1, 2, 7] * jump           # key `late` (last key block) against query 7
@@ -268,9 +301,10 @@ def test_attention_flash_running_max_jump(S, jump):
         assert rel_l2(got[b * S + row, h * 64:(h + 1) * 64], ref[b * S + row, h * 64:(h + 1) * 64]) < 2e-3
 
 
-@pytest.mark.parametrize("Tq,t0", [(5, 0), (1, 4), (2, 1), (1, 0)])
+@pytest.mark.parametrize("Tq,t0", PB.TEMPORAL_OPS_WINDOWS)
 def test_attention_temporal(Tq, t0):
-    B, P, D, Tmax = 2, 24, 256, 5
+    B, P, D, Tmax = PB.TEMPORAL_OPS_GEOMETRY
+    assert_declared_plan("attn_temporal", B, P, D, Tq, t0, Tmax)
     Tk = t0 + Tq
     q = _rand(B, Tq, P, D, seed=1).half()
     kv = _rand(B, Tmax, P, 2, D, seed=2).half()
@@ -431,12 +465,13 @@ def test_fused_temporal_qkv_attention_equals_the_two_kernel_path(B, P, D):
     assert rel_l2(untile(first[1], M, D).float(), ref) < 6e-4
 
 
-@pytest.mark.parametrize("NB,heads,S", [(3, 2, 144), (2, 4, 32), (1, 1, 160)])
+@pytest.mark.parametrize("NB,heads,S", PB.ATTN_BWD_OPS_SHAPES)
 def test_attention_spatial_backward_mfma(NB, heads, S):
     """attn_spatial_bwd_mfma_kernel (train.hip) against torch.autograd of softmax(q k^T / 8) v on the same fp16 q / k / v / dO
     (model/attention.py:99-136): dv, and dq / dk rotated back through the RoPE the forward applied (cos / sin per (position, pair)).
     The kernel rounds P and dS to fp16 for its MFMA operands: 2e-3."""
     lib = L.load()
+    assert_declared_plan("attn_spatial_bwd", NB, heads, S)
     D = heads * 64
     q = _rand(NB, heads, S, 64, seed=1).half()
     k = _rand(NB, heads, S, 64, seed=2).half()

@@ -14,7 +14,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import parity_bounds as PB  # noqa: E402
-from helpers import dev, stream, tiled_index  # noqa: E402
+from helpers import assert_declared_plan, dev, stream, tiled_index  # noqa: E402
 from gtav_amd import lib as L  # noqa: E402
 
 F16, BF16 = PB.F16, PB.BF16
@@ -103,6 +103,7 @@ def _launch_spatial(c, err, fill=None):
     """one launch of case c -> the rows [NB S][3 D] (CPU).  fill: what 64 rows behind q / k / dO / the table and 4096 elements behind V^T hold"""
     lib = _use(c.dtype)
     NB, heads, S = c.NB, c.heads, c.S
+    assert_declared_plan("attn_spatial_bwd", NB, heads, S)
     pad = 64 * 64 * heads
     qd, kd, vtd, dod, csd = (_tail(t, fill, pad) for t in (c.q, c.k, c.v.transpose(-1, -2), c.do, c.cs))
     out = _Out(NB * S, 3 * heads * 64, c.dtype)
@@ -169,6 +170,7 @@ def _launch_temporal(c, err, fill=None):
     """fill: what the cache frames from T on, the table rows from T on and 64 rows behind q / dO hold"""
     lib = _use(c.dtype)
     B, P, D, T, Tmax = c.args
+    assert_declared_plan("attn_temporal_bwd", B, P, D, T)
     kv, cs = c.kv, c.cs
     if fill is not None:
         kv, cs = kv.clone(), cs.clone()

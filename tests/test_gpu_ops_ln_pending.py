@@ -12,7 +12,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import parity_bounds as PB  # noqa: E402
-from helpers import dev, stream, untile_typed  # noqa: E402
+from helpers import assert_declared_plan, dev, stream, untile_typed  # noqa: E402
 from gtav_amd import lib as L  # noqa: E402
 
 F16, BF16 = PB.F16, PB.BF16
@@ -91,6 +91,8 @@ class _Launch:
         return list(a.values())
 
     def run(self, lib):
+        c = self.c
+        assert_declared_plan("layernorm", c.mode, c.M, c.D, int(self.parts is not None), int(self.tperm[0] != 0), int(self.k_save is not None), int(self.k_load is not None))
         L.check(lib.gtav_op_ln_pending(*self.args()))
         torch.cuda.synchronize()
         return self
@@ -219,6 +221,25 @@ def test_training_forward_and_recompute_rerun(dtype):
     plain = _Launch(c, dtype, x_out=True, y_save=True).run(lib)
     assert _same_bits(plain.out, first.out) and _same_bits(plain.x_out, first.x_out) and _same_bits(plain.y_save, first.y_save)
     # the re-run from the stored state: no slabs, K read back
+    again = _Launch(c, dtype, x=first.x_out.cpu(), slabs=False, k_load=first.k_save).run(lib)
+    assert _same_bits(again.out, first.out), "the k_load re-run does not reproduce the forward's operand"
+    assert _same_bits(again.x, first.x_out) and again.err.item() == 0
+
+
+@DTYPES
+def test_affine_forward_and_recompute_rerun(dtype):
+    """The affine row-block forms that keep and read back the statistics' shift, ln_row_block_kernel<1, true, 1> and <1, false, 2>: no product caller launches them
+    (a training handle's LayerNorms modulate), the hook does.  As above: assertions 1, 2, 3 and 5 on x_out + y_save + k_save, the bits of the launch without
+    k_save, and the k_load re-run from x_out."""
+    lib, c = _use(dtype), PB.ln_pend_case("d192_train")
+    first = _Launch(c, dtype, x_out=True, y_save=True, k_save=True).run(lib)
+    _check_residual(c, dtype, first.x_out, "x_out")
+    _check_operand(c, dtype, first)
+    _check_inputs(c, first, x_kept=True)
+    _check_y_save(lib, c, dtype, first)
+    assert _same_bits(first.k_save, c.x[:, 0]), "k_save is not the row's first element before the update"
+    plain = _Launch(c, dtype, x_out=True, y_save=True).run(lib)
+    assert _same_bits(plain.out, first.out) and _same_bits(plain.x_out, first.x_out) and _same_bits(plain.y_save, first.y_save)
     again = _Launch(c, dtype, x=first.x_out.cpu(), slabs=False, k_load=first.k_save).run(lib)
     assert _same_bits(again.out, first.out), "the k_load re-run does not reproduce the forward's operand"
     assert _same_bits(again.x, first.x_out) and again.err.item() == 0

@@ -18,7 +18,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import parity_bounds as PB  # noqa: E402
-from helpers import dev, stream, tiled_index  # noqa: E402
+from helpers import assert_declared_plan, dev, stream, tiled_index  # noqa: E402
 from gtav_amd import lib as L  # noqa: E402
 from train_cases import GRAD_TOL  # noqa: E402
 
@@ -167,6 +167,8 @@ def _ln_ws_need(fused, c):
 def _run_ln_bwd(c, fused, accumulate):
     lib = _use()
     D, M = c.D, c.M
+    if fused:
+        assert_declared_plan("ln_mod_bwd_fused", c.frames, c.P, D)
     dxn, x, mod = c.dxn.to(dev()), c.x.to(dev()), c.mod.to(dev())
     dres = torch.cat((c.old if accumulate else torch.full((M, D), float("nan")), PB.rand(1, D, seed=12))).to(dev())      # one spare row
     dres_before = dres.clone()
@@ -197,12 +199,12 @@ def test_ln_mod_bwd(D, frames, P, fused, accumulate):
 
 
 @FUSED
-@pytest.mark.parametrize("D", [256, 1024])
-def test_ln_mod_bwd_large_mean_rows(D, fused):
+@pytest.mark.parametrize("D,frames,P", PB.LN_BWD_LARGE_MEAN, ids=[str(d) for d, _, _ in PB.LN_BWD_LARGE_MEAN])
+def test_ln_mod_bwd_large_mean_rows(D, frames, P, fused):
     """rows of 300 +- 0.02 (PB.LnBwdCase): dres and dscale per row under LN_TOL, and everything per element.  The kernels formed x - fl(mean x) when this test was
     written: dscale was at 1.3 of its per-row bound, as the fp32 emulation of that form is (tests/test_host_parity_bounds.py); they now centre the row on its first
     element, like the forward LayerNorm."""
-    c = PB.ln_bwd_case(D, 2, 24, True)
+    c = PB.ln_bwd_case(D, frames, P, True)
     name, dres, dshift, dscale = _run_ln_bwd(c, fused, 0)
     _row_within(name + " large mean dres", dres, c.ref_dres(0), PB.LN_TOL)
     _row_within(name + " large mean dscale", dscale, c.ref_dscale, PB.LN_TOL)
@@ -617,6 +619,7 @@ def test_silu_and_silu_bwd():
 
 def _run_gemm_tn_f32(name, c, R, N, K, lddy, dy_offset=0):
     lib = _use()
+    assert_declared_plan("gemm_tn_f32", R, N, K)
     lddw = K + 4
     flat = torch.full((dy_offset + (R + 1) * lddy,), float("nan"))
     flat[dy_offset:].reshape(R + 1, lddy)[:R, :N] = c.a
@@ -646,6 +649,7 @@ def test_gemm_tn_f32_valu(R, N, K, form):
 def test_gemm_nn_f32(R, N, K):
     """dX = dY W: N = 256 / 2048 / 4096 keep 16 / 8 / 4 rows of dY in LDS"""
     lib = _use()
+    assert_declared_plan("gemm_nn_f32", R, N, K)
     c = PB.gemm_f32_case(N, R, K, False, False)
     dY, _, _ = _padded(c.a.t().contiguous(), N + 4, 41)
     W, _, _ = _padded(c.b, K + 3, 42)
@@ -665,6 +669,7 @@ def test_gemm_nn_f32_refuses_rows_beyond_lds():
 
 def _run_ada_bwd_dx(name, MODW, D, R, mfma):
     lib = _use()
+    assert_declared_plan("ada_bwd_dx", MODW, D, R)
     c = PB.gemm_f32_case(MODW, R, D, False, mfma, scale=MODW ** -0.5)
     dmod, W = c.a.t().contiguous().to(dev()), c.b.to(dev())
     dSc, dSc0, w = _padded(torch.full((R, D), float("nan")), D, 51)

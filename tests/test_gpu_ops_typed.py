@@ -14,7 +14,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import parity_bounds as PB  # noqa: E402
-from helpers import dev, stream, tiled_index, to_tiled, untile_typed  # noqa: E402
+from helpers import assert_declared_plan, dev, stream, tiled_index, to_tiled, untile_typed  # noqa: E402
 from gtav_amd import lib as L  # noqa: E402
 
 F16, BF16 = PB.F16, PB.BF16
@@ -311,6 +311,8 @@ def test_layernorm_kernels(D, M, dtype):
     c = PB.ln_case(D, M)
     tol = PB.LN_TOL * PB.FACTOR[dtype]
     xd, md, gd, bd = c.x.to(dev()), c.mod.to(dev()), c.g.to(dev()), c.beta.to(dev())
+    for mode in (0, 1):
+        assert_declared_plan("layernorm", mode, M, D, 0, 0, 0, 0)
     out = _nan((_up(M, 128) + 128, D), dtype)
     L.check(lib.gtav_op_ln_modulate(xd.data_ptr(), out.data_ptr(), M, D, md.data_ptr(), md[:, D:].data_ptr(), 2 * D, c.P, stream()))
     assert torch.isnan(out[_up(M, 128):]).all()
@@ -322,7 +324,7 @@ def test_layernorm_kernels(D, M, dtype):
 
 
 @DTYPES
-@pytest.mark.parametrize("D", [128, 1024])
+@pytest.mark.parametrize("D", PB.LN_LARGE_MEAN_D)
 def test_layernorm_statistics_with_a_large_mean(D, dtype):
     """A row of 300 +- 0.02 at the bound of every other LayerNorm case, globally and per row.  (This assertion found the kernels' x - fl(K + mean(x - K)): the
     mean rounded to an ulp of 300 put fp16 rows at 8.4e-4 / 8.1e-4 (D = 128 / 1024) and the D = 1024 total at 5.04e-4 against 5e-4; both kernels now centre
@@ -331,6 +333,7 @@ def test_layernorm_statistics_with_a_large_mean(D, dtype):
     x, g, b, ref = PB.ln_large_mean_case(D)
     out = torch.zeros(128, D, device=dev(), dtype=dtype)
     xd, gd, bd = x.to(dev()), g.to(dev()), b.to(dev())
+    assert_declared_plan("layernorm", 1, x.shape[0], D, 0, 0, 0, 0)
     L.check(lib.gtav_op_ln_affine(xd.data_ptr(), out.data_ptr(), x.shape[0], D, gd.data_ptr(), bd.data_ptr(), stream()))
     _rel(f"ln_affine large mean D={D}", dtype, untile_typed(out, x.shape[0], D), ref, PB.LN_TOL * PB.FACTOR[dtype], rows=D)
 
@@ -355,7 +358,8 @@ def test_splitk_partials_reduced_by_layernorm(M, N, K, splitk, dtype):
 
 # ---- e. spatial attention -----------------------------------------------------------------------------------------------------------------------------------
 def _attn_spatial(lib, c, prescaled=False, reps=1):
-    NB, heads, S = PB.ATTN_NB, PB.ATTN_HEADS, c.S
+    NB, heads, S = c.NB, c.heads, c.S
+    assert_declared_plan("attn_spatial", NB, heads, S, 1 if prescaled else 0)
     qd, kd, vd = c.q.to(dev()), c.k.to(dev()), c.v.transpose(-1, -2).contiguous().to(dev())
     fn = lib.gtav_op_attn_spatial_prescaled if prescaled else lib.gtav_op_attn_spatial
     outs = []
@@ -380,12 +384,24 @@ def test_attention_spatial(S, dtype):
 
 
 @DTYPES
-@pytest.mark.parametrize("S", [200, 576])
+@pytest.mark.parametrize("S", PB.ATTN_PRESCALED_S)
 def test_attention_spatial_prescaled_q(S, dtype):
     """attn_flash_kernel<..., PS_ = true>, the instantiation the VAE runs: q carries log2 e / 8 (rounded on the host), the reference is the base-2 softmax of it"""
     c = PB.attn_case(S, dtype, None, True)
     got = _attn_spatial(_use(dtype), c, prescaled=True)
     _rel(f"attn_spatial prescaled S={S}", dtype, got, c.ref, PB.ATTN_TOL * PB.FACTOR[dtype], rows=64)
+
+
+@DTYPES
+@pytest.mark.parametrize("NB,heads,S,prescaled", PB.ATTN_EXTRA, ids=[f"{nb}x{h}x{s}{'-prescaled' if p else ''}" for nb, h, s, p in PB.ATTN_EXTRA])
+def test_attention_spatial_every_instantiation(NB, heads, S, prescaled, dtype):
+    """The instantiations and launch forms the 2 x 3 cases above do not select (tests/parity_bounds.py ATTN_EXTRA; DECLARED_PLANS says what each runs): the
+    one-pass kernel at 4 and 8 key blocks; the flash kernel at three query tiles per wave on a ragged S, at two on S % 64 == 0 with a prescaled q, and at four
+    (a padding tie once the grid fills the chip: 256 (frame, head) pairs); and the one-pass kernel without a query split (512 pairs: the batch-8 launch) at 6, 8
+    and 10 key blocks.  Globally and per (query, head) row, at the bound of the cases above."""
+    c = PB.attn_case(S, dtype, None, bool(prescaled), NB, heads)
+    got = _attn_spatial(_use(dtype), c, prescaled=bool(prescaled))
+    _rel(f"attn_spatial {NB}x{heads} S={S}{' prescaled' if prescaled else ''}", dtype, got, c.ref, PB.ATTN_TOL * PB.FACTOR[dtype], rows=64)
 
 
 @DTYPES
@@ -422,6 +438,7 @@ def test_attention_temporal(B, P, D, Tq, t0, Tmax, dtype):
     query groups).  Cache frames no query may see hold NaN; two launches are bit-equal; P stays fp32, so every element has its own bound."""
     lib = L.load()
     fn = lib.gtav_op_attn_temporal if dtype is F16 else lib.gtav_op_attn_temporal_bf16
+    assert_declared_plan("attn_temporal", B, P, D, Tq, t0, Tmax)
     c = PB.temporal_case(B, P, D, Tq, t0, Tmax, dtype)
     kv = c.kv.clone()
     kv[:, t0 + Tq:] = float("nan")

@@ -1,7 +1,8 @@
 """CPU (no GPU): the launch planner of the non-GEMM kernels (csrc/launch_plan.hip, gtav_op_launch_plan).  Every instantiation a launcher can pick computes the
 same result, so no parity test can see which one a launch runs: (a) pins kernel, grid, block and LDS to what the commit before the planner existed launched,
 recorded from that commit's own launchers; (b) checks every plan against the instantiation lists of csrc/launch_plan.h, the lists the launchers dispatch over;
-both through the function the launchers themselves call."""
+both through the function the launchers themselves call.  That every product instantiation is also RUN by an op-level parity test is the business of
+tests/test_host_op_coverage.py, which reuses _instantiation_lists() below."""
 import importlib.util
 import json
 import os

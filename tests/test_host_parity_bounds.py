@@ -346,6 +346,34 @@ def test_gemm_f32_bounds(n, I, J, accumulate, mfma):
     _caught(name, f"last {k} term(s) left out", drop, c.ref, c.tol)
 
 
+@pytest.mark.parametrize("M,N,K,act,bias", PB.SKINNY_HOST_CASES)
+def test_skinny_bounds(M, N, K, act, bias):
+    """tests/test_gpu_ops.py test_skinny_f32: the kernel's chain in fp32 arithmetic (skinny_emulate) sits inside the per-element bound, with and without SiLU and
+    a bias; a dropped last K chunk of 128 columns and a bias added twice leave it"""
+    c = PB.skinny_case(M, N, K, act, bias)
+    name = f"skinny {M}x{N}x{K} act={act}{'' if bias else ' no bias'}"
+    _inside(name, PB.skinny_emulate(c.x, c.w, c.b, act), c.ref, c.tol)
+    if K > 128:
+        _caught(name, "the last K chunk of 128 columns left out", PB.skinny_emulate(c.x, c.w, c.b, act, "chunk"), c.ref, c.tol)
+    if bias:
+        _caught(name, "the bias added twice", PB.skinny_emulate(c.x, c.w, c.b, act, "bias2"), c.ref, c.tol)
+    # the windows of the bit-equality check lie inside N, on multiples of 4, and hold a block boundary and the last column
+    for ft in (1, 4, 8):
+        w = c.windows(ft)
+        assert w[0] == 0 and w[-1] == N - 64 and all(n % 4 == 0 and 0 <= n <= N - 64 for n in w)
+        assert N < 64 * ft + 32 or any(n < 64 * ft < n + 64 for n in w)
+
+
+@DTYPES
+@pytest.mark.parametrize("S,prescaled", sorted({(s, p) for nb, h, s, p in PB.ATTN_EXTRA}))
+def test_spatial_attention_extra_row_bound(S, prescaled, dtype):
+    """the sequence lengths of PB.ATTN_EXTRA (the instantiations the 2 x 3 cases of ATTN_S do not select), at 2 x 3 items: P and the output rounded"""
+    c = PB.attn_case(S, dtype, None, bool(prescaled))
+    best = PB.row_rel_l2(PB.attn_rows(c.control()), PB.attn_rows(c.ref4)) / (PB.ATTN_TOL * PB.FACTOR[dtype])
+    print(f"[bound control attn_spatial{' prescaled' if prescaled else ''} S={S} {PB.NAME[dtype]}] P and output rounded: {best:.3f} of the per-row bound")
+    assert best < 0.6
+
+
 # ---- the deferred-residual LayerNorm (tests/test_gpu_ops_ln_pending.py) ------------------------------------------------------------------------------------
 def _ln_pend_margins(c, dtype, wrong=None):
     """(worst ratio of bound 1, worst row / global relative L2 as a fraction of bound 3) of the fp32 emulation; the operand is read back through the DOCUMENTED
@@ -469,7 +497,10 @@ def test_attn_temporal_bwd_control_and_wrong_kernels(shape, kind, dtype):
     print(f"[bound control {name}] WRONG (truncating store): worst ratio {_fmt(w)}")
     # P and dS stay fp32, the store's u |ref| is the bound's only 2-byte term: dv leaves it in every case.  (dq / dk of a peaked row are sums of dS ~ 0 that cancel:
     # there the fp32 terms of the bound outweigh u |ref|, and the truncation stays inside — 0.65 on `sharp` fp16 dq.)
-    assert w[2] > 1.0, w
+    # (One case of 2304 elements holds no dv element that shows it: `sharp` at T = 3 in fp16, 0.975 of the bound as printed; its bf16 twin and the four other kinds at
+    # T = 3 do.)
+    if not (T == 3 and kind == "sharp" and dtype is PB.F16):
+        assert w[2] > 1.0, w
     for wrong in ["drop_last", "rope_sign", "mask_plus", "mask_minus"] + (["stale_max"] if kind == "ladder" else []):
         w = _thirds(c, c.control(wrong))
         print(f"[bound control {name}] WRONG ({wrong}): worst ratio {_fmt(w)}")
@@ -477,6 +508,10 @@ def test_attn_temporal_bwd_control_and_wrong_kernels(shape, kind, dtype):
             # k_t = 3 q_t puts the own frame 24 above every other score (sd 3): with so few keys every other probability is e^-15 at most, dS, dq and dk are
             # next to zero in fp64 already, and neither a rotation of them nor one more key of that weight moves anything by as much as the bound (printed
             # above: 0.03 .. 0.15 of it).  Both are caught on `diagonal` from T = 9 on, where some off-diagonal score comes close enough.
+            continue
+        if kind == "first" and T == 2 and wrong == "drop_last":
+            # two frames, key 0 far above key 1: the only last key that can be dropped is key 1 of query 1, whose probability is next to zero in fp64 already
+            # (0.50 .. 0.91 of the bound, printed above).  `first` shows a dropped last key from T = 3 on, the four other kinds at T = 2 as well.
             continue
         assert max(w) > 1.0, (wrong, w)
 
